@@ -22,6 +22,10 @@ Timing: W untimed steps, then EXACTLY K steps between barrier + synchronize, max
 eval-mode loss of THIS model on the seed-1000 batch with the value the imported reference gave for the same weights and
 batch (tests/golden/bench_expected.json) and fails the run when they disagree.  Rank 0 prints ONE JSON line.
 
+--dump-outputs DIR: right after the K timed steps, rank 0 writes what the last of them gave its caller as DIR/<name>.npy
+(float32, float64 kept; at most 16 MB per array; train: loss, kld, nce and a seeded sample of the updated parameters; fwd: heat maps and embeddings; see
+step_outputs).  Weights and batch are drawn from fixed seeds, so two builds run with the same arguments see the same inputs.
+
 Extra objects: "roofline" for the dominant kernel, measured live with HIP events on the launch stream over an
 instrumented pass, and "cpu_baseline" = the CPU oracle (a port, plain PyTorch fp32) timed on the host cores on a
 bounded sample of the same workload (rank 0, N = 1 only).
@@ -82,7 +86,12 @@ def parse():
                    help="write the ORDERED list of one step's GEMM launches (kernel name, shape, event-timed us) as JSON: "
                         "tools/trace_gemm_map.py zips it with a rocprofv3 kernel trace of the graph replay")
     p.add_argument("--one-stream", action="store_true", help="audio trunk on the video trunk's stream (CSTS_AMD.TWO_STREAMS False)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step gave its caller as DIR/<name>.npy (rank 0; see step_outputs)")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 class GemmTimer:
@@ -321,6 +330,49 @@ class OpTimer:
                 d["bound"] = "hbm" if d["hbm_frac"] >= d["mfma_frac"] else "mfma"
             out[k] = d
         return out
+
+
+# ------------------------------------------------------------------------------------------------ output dump
+DUMP_MAX_ELEMS = 4 << 20        # one dumped array: at most 16 MB (a fixed, seeded sample of anything larger)
+PARAM_SAMPLE = 16384            # elements per parameter tensor in params_sample.npy (the whole tensor when smaller)
+
+
+def _sample(flat, n, g):
+    """`n` elements of the 1-D tensor `flat` at indices drawn from the CPU generator `g` (sorted; same draw on every run)."""
+    idx = torch.randint(0, flat.numel(), (n,), generator=g).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def step_outputs(mode, res, core):
+    """What a caller of the timed step received from its last run, copied to the host as (name, tensor) pairs.
+    train: loss, kld, nce (the step's return value) and params_sample = the parameters that step updated, PARAM_SAMPLE
+    seeded elements of every tensor concatenated in named_parameters() order (all 524 tensors are 753 MB).
+    fwd: heatmaps (frame_softmax of the logits), video_embed, audio_embed."""
+    g = torch.Generator().manual_seed(0)
+    with torch.no_grad():
+        if mode == "fwd":
+            out = list(zip(("heatmaps", "video_embed", "audio_embed"), res))
+        else:
+            out = [(n, t) for n, t in zip(("loss", "kld", "nce"), res) if t is not None]
+            parts = []
+            for _, p in core.named_parameters():
+                flat = p.detach().reshape(-1)
+                parts.append(_sample(flat, PARAM_SAMPLE, g) if flat.numel() > PARAM_SAMPLE else flat)
+            out.append(("params_sample", torch.cat([t.float() for t in parts])))
+        host = []
+        for name, t in out:
+            flat = t.detach().reshape(-1)
+            if flat.numel() > DUMP_MAX_ELEMS:
+                t = _sample(flat, DUMP_MAX_ELEMS, g)
+            host.append((name, t.detach().to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32)))
+    return host
+
+
+def dump_outputs(path, arrays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays:
+        np.save(os.path.join(path, name + ".npy"), t.numpy())
 
 
 # ------------------------------------------------------------------------------------------------ CPU baseline
@@ -658,6 +710,9 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t)
+    if args.dump_outputs and rank == 0:
+        # now, before the steps below overwrite the graph's output buffers and update the weights again
+        dump_outputs(args.dump_outputs, step_outputs(args.mode, res, core))
     clips = b * world * args.steps
     value = clips / dt
     ms_per_step = dt / args.steps * 1e3

@@ -133,16 +133,16 @@ def test_optimizer_param_groups():
     assert any(p is m.pos_embed_spatial for g in opt.param_groups if g["weight_decay"] > 0 for p in g["params"])
 
 
-def test_cli_parsing_and_yaml_tuple_strings():
+def test_cli_parsing_and_yaml_tuple_strings(tmp_path):
     from csts_amd.cli import parse_args, load_config
     args = parse_args(["--cfg", YAML, "--init_method", "tcp://127.0.0.1:9997", "NUM_GPUS", "8", "TRAIN.BATCH_SIZE", "32",
-                       "MODEL.LOSS_FUNC", "kldiv+egonce", "OUTPUT_DIR", "/tmp/csts_test_out"])
+                       "MODEL.LOSS_FUNC", "kldiv+egonce", "OUTPUT_DIR", str(tmp_path)])
     cfg = load_config(args)
     assert cfg.NUM_GPUS == 8 and cfg.TRAIN.BATCH_SIZE == 32 and cfg.MODEL.LOSS_FUNC == "kldiv+egonce"
     assert cfg.MVIT.PATCH_KERNEL == [3, 7, 7] and cfg.SOLVER.COSINE_END_LR == 1e-6
     for y in ("configs/Aria/CSTS_Aria_Gaze_Forecast.yaml", "configs/Aria/CSTS_Aria_Gaze_Estimation.yaml",
               "configs/Ego4D/CSTS_Ego4D_Gaze_Estimation.yaml"):
-        c = load_config(parse_args(["--cfg", os.path.join(ROOT, y), "OUTPUT_DIR", "/tmp/csts_test_out"]))
+        c = load_config(parse_args(["--cfg", os.path.join(ROOT, y), "OUTPUT_DIR", str(tmp_path)]))
         assert c.MODEL.MODEL_NAME == "CSTS" and c.DATA.NUM_FRAMES == 8 and c.DATA.TRAIN_CROP_SIZE == 256
 
 
