@@ -152,7 +152,7 @@ class OptFactored(C.Structure):
 
 
 # name -> (restype, argtypes); every symbol include/csts_hip.h declares
-_I, _F = C.c_int, C.c_float
+_I, _F, _U32 = C.c_int, C.c_float, C.c_uint32
 class TransposeTile(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("R", C.c_int), ("C", C.c_int), ("r0", C.c_int), ("c0", C.c_int)]
 
@@ -208,6 +208,10 @@ SYMBOLS = {
     "csts_copy_token_segments": (_I, [C.POINTER(TokenSegment), _I, _I, _I, _I, vp]),
     "csts_rows_scatter_add": (_I, [C.POINTER(KvRowsGeom), vp, _I, vp, _I, vp]),
     "csts_scale_rows": (_I, [vp, _I, vp, i64, vp, _I, i64, i64, vp]),
+    "csts_dropout_fwd": (_I, [vp, vp, vp, i64, vp, _I, vp, _U32, _U32, _F, i64, i64, vp]),
+    "csts_dropout_bwd": (_I, [vp, _I, vp, i64, vp, _I, vp, _U32, _U32, _F, i64, i64, vp]),
+    "csts_dropout_mask": (_I, [vp, _U32, _U32, vp, i64, vp]),
+    "csts_dropout_mask_host": (_I, [_U32, _U32, _U32, _U32, C.c_uint64, i64, vp]),
     "csts_add2": (_I, [vp, _I, vp, _I, vp, vp, i64, vp]),
     "csts_add2_scaled_copy": (_I, [vp, _I, vp, _I, vp, vp, vp, i64, i64, vp]),
     "csts_rowdot2": (_I, [vp, _I, vp, _I, vp, i64, _I, vp]),

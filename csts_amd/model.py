@@ -93,6 +93,7 @@ class Runtime:
         self.loss_scaling = compute == "fp16"
         self.act_dt = self.compute            # dtype of GEMM inputs / q,k,v / MLP hidden
         self.stream_dt = L.F32                # residual stream, LN statistics, softmax, losses
+        self.drop_key = None                  # dropout key of the current forward (CSTS.forward), None in eval / at rate 0
 
 
 # --------------------------------------------------------------------------- parameter containers
@@ -131,12 +132,16 @@ class Block(nn.Module):
     """One transformer block of the path.  kind: 'enc' (MultiScaleBlock, attention.py:165-248), 'dec'
     (MultiScaleDecoderBlock, :395-479), 'spatial' / 'temporal' (av_attention.py:373-473 / :156-250)."""
 
-    def __init__(self, kind, dim, dim_out, heads, stride_q, stride_kv, has_pool_q, has_pool_kv, mlp_hidden, drop_path, rt):
+    def __init__(self, kind, dim, dim_out, heads, stride_q, stride_kv, has_pool_q, has_pool_kv, mlp_hidden, drop_path, rt,
+                 drop_rate=0.0, dropout_site=0):
+        """drop_rate: MVIT.DROPOUT_RATE (proj_drop and Mlp.drop, train mode only); dropout_site: the first of the block's three
+        dropout sites (include/csts_hip.h), the key is the one CSTS.forward drew (Runtime.drop_key)."""
         super().__init__()
         self.kind, self.dim, self.dim_out, self.heads = kind, dim, dim_out, heads
         self.stride_q, self.stride_kv = tuple(stride_q), tuple(stride_kv)
         self.has_pool_q, self.has_pool_kv = has_pool_q, has_pool_kv
         self.drop_prob = float(drop_path)
+        self.drop_rate, self.dropout_site = float(drop_rate), int(dropout_site)
         self.rt = rt
         self.norm1 = nn.LayerNorm(dim, eps=1e-6)
         self.attn = _Attention(dim, heads, kind, has_pool_q, has_pool_kv, stride_q, stride_kv)
@@ -162,10 +167,19 @@ class Block(nn.Module):
             m2 = torch.floor(keep + torch.rand(B, dtype=torch.float32, device=device))
         return (m1 / keep).contiguous(), (m2 / keep).contiguous()
 
+    def _dropout(self):
+        """The block's ops.Dropout (proj site; the MLP takes the next two) in train mode with a non-zero rate, else None."""
+        if self.drop_rate == 0.0 or not self.training:
+            return None
+        if self.rt.drop_key is None:
+            raise L.CstsError("Block dropout in train mode needs the per-forward key CSTS.forward draws")
+        return ops.Dropout(self.rt.drop_key, self.dropout_site, self.drop_rate)
+
     def forward(self, x, thw, keep_masks=None, want_attn=False, spatial_audio_attn=False, x_add=None):
         """x_add (optional): a skip tensor to be added to x first (the decoder's `feat + en_feat`,
         custom_multimodal_builder.py:467-479): folded into norm1's kernel, which then also writes the sum."""
         rt = self.rt
+        drop = self._dropout()
         a = self.attn
         B, N, Cc = x.shape
         H = self.heads
@@ -201,7 +215,7 @@ class Block(nn.Module):
         res_up = None
         if self.kind == "dec":
             q_thw = [t * s for t, s in zip(thw, self.stride_q)]
-            if ops.res_up_ok(q_thw) and x.dtype == torch.float32:
+            if ops.res_up_ok(q_thw) and x.dtype == torch.float32 and drop is None:
                 x_res, res_up = x, (list(thw), q_thw)     # the proj GEMM's epilogue up-samples the skip itself
             else:
                 x_res = ops.trilinear(x, thw, self.stride_q)
@@ -214,7 +228,7 @@ class Block(nn.Module):
         Nq = o.shape[1]
         s_attn, s_mlp = self._drop_scales(B, x.device, keep_masks)
         x1 = ops.linear(o, a.proj.weight, a.proj.bias, residual=x_res, row_scale=s_attn, rows_per_scale=Nq, out_dt=L.F32,
-                        compute=rt.compute, w16=w16(a.proj), w16t=w16t(a.proj), res_up=res_up)
+                        compute=rt.compute, w16=w16(a.proj), w16t=w16t(a.proj), res_up=res_up, drop=drop)
         if self.dim != self.dim_out:        # norm2's output feeds fc1 AND the skip projection (attention.py:243-246)
             xn2, xn2b, x1 = ops.layer_norm(x1, self.norm2.weight, self.norm2.bias, 1e-6, rt.act_dt, passthrough=True, fanout=True)
             base = ops.linear(xn2b, self.proj.weight, self.proj.bias, out_dt=L.F32, compute=rt.compute, w16=w16(self.proj),
@@ -224,7 +238,8 @@ class Block(nn.Module):
             base = x1
         out = ops.mlp(xn2, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight, self.mlp.fc2.bias, residual=base,
                       row_scale=s_mlp, rows_per_scale=Nq, act_dt=rt.act_dt, out_dt=L.F32, compute=rt.compute,
-                      w16_1=w16(self.mlp.fc1), w16_2=w16(self.mlp.fc2), w16t_1=w16t(self.mlp.fc1), w16t_2=w16t(self.mlp.fc2))
+                      w16_1=w16(self.mlp.fc1), w16_2=w16(self.mlp.fc2), w16t_1=w16t(self.mlp.fc1), w16t_2=w16t(self.mlp.fc2),
+                      drop=drop.at(1) if drop is not None else None)
         extra = None
         if spatial_audio_attn:       # av_attention.py:360-370: (per-head rescaled audio->pixel map, its head mean per token)
             T, HW = thw[0], thw[1] * thw[2]
@@ -254,9 +269,12 @@ class CSTS(nn.Module):
         if cfg.MVIT.NORM != "layernorm":
             raise NotImplementedError("Only supports layernorm.")          # :63
         if cfg.MVIT.CLS_EMBED_ON or not cfg.MVIT.SEP_POS_EMBED or cfg.MVIT.PATCH_2D or cfg.MVIT.POOL_FIRST \
-                or cfg.MVIT.MODE != "conv" or cfg.MVIT.DROPOUT_RATE > 0 or cfg.MVIT.NORM_STEM:
+                or cfg.MVIT.MODE != "conv" or cfg.MVIT.NORM_STEM:
             raise NotImplementedError("csts_amd implements the configuration of the shipped CSTS YAMLs: no class "
-                                      "token, separable pos-embed, 3-D patches, conv pooling, no dropout, no stem norm")
+                                      "token, separable pos-embed, 3-D patches, conv pooling, no stem norm")
+        self.drop_rate = float(cfg.MVIT.DROPOUT_RATE)
+        if not (0.0 <= self.drop_rate < 1.0):
+            raise ValueError(f"MVIT.DROPOUT_RATE must be in [0, 1), got {cfg.MVIT.DROPOUT_RATE}")
         amd = getattr(cfg, "CSTS_AMD", None)
         self.rt = Runtime(resolve_compute(cfg))
         if bool(getattr(cfg.MODEL, "ACT_CHECKPOINT", False)):
@@ -316,14 +334,15 @@ class CSTS(nn.Module):
             has_q = len(stride_q[i]) > 0
             has_kv = len(stride_kv[i]) > 0
             self.blocks.append(Block("enc", dim, dim_out, heads, stride_q[i] if has_q else (1, 1, 1),
-                                     stride_kv[i] if has_kv else (1, 1, 1), has_q, has_kv, int(dim * mlp_ratio), dpr[i], rt))
+                                     stride_kv[i] if has_kv else (1, 1, 1), has_q, has_kv, int(dim * mlp_ratio), dpr[i], rt,
+                                     self.drop_rate))
         # ---- audio encoder (:184-216)
         a_dim, a_out, a_heads = [96, 192, 384, 768], [192, 384, 768, 768], [1, 2, 4, 8]
         a_sq = [None, (1, 2, 2), (1, 2, 2), (1, 2, 2)]
         a_skv = [(1, 8, 8), (1, 4, 4), (1, 2, 2), (1, 1, 1)]
         self.blocks_audio = nn.ModuleList([
             Block("enc", a_dim[i], a_out[i], a_heads[i], a_sq[i] or (1, 1, 1), a_skv[i], a_sq[i] is not None, True,
-                  int(a_dim[i] * mlp_ratio), 0.0, rt) for i in range(4)])
+                  int(a_dim[i] * mlp_ratio), 0.0, rt, self.drop_rate) for i in range(4)])
         token_dim = self.blocks[-1].dim_out
         if "nce" in cfg.MODEL.LOSS_FUNC:                                   # :221-224
             self.vision_proj = nn.Linear(token_dim, 256)
@@ -333,17 +352,23 @@ class CSTS(nn.Module):
         self.audio_pool = nn.Conv3d(token_dim, token_dim, kernel_size=fk, stride=1)
         self.audio_pool2 = nn.Conv3d(token_dim, token_dim, kernel_size=fk, stride=1)
         self.temporal_fusion = Block("temporal", token_dim, token_dim, heads, (1, 1, 1), (1, 1, 1), False, False,
-                                     int(token_dim * mlp_ratio), 0.0, rt)
+                                     int(token_dim * mlp_ratio), 0.0, rt, self.drop_rate)
         self.spatial_fusion = Block("spatial", token_dim, token_dim, heads, (1, 1, 1), (1, 1, 1), False, False,
-                                    int(token_dim * mlp_ratio), 0.0, rt)
+                                    int(token_dim * mlp_ratio), 0.0, rt, self.drop_rate)
         # ---- decoder (:271-299); MLP hidden = 4 * dim_out (attention.py:444)
         d_in, d_out, d_heads = [768, 768, 384, 192], [768, 384, 192, 96], [8, 4, 4, 2]
         d_sq = [(1, 2, 2), (1, 2, 2), (1, 2, 2), (2, 1, 1)]
         d_skv = [(1, 2, 2), (1, 4, 4), (1, 8, 8), (1, 16, 16)]
         for i in range(4):
             setattr(self, f"decode_block{i + 1}",
-                    Block("dec", d_in[i], d_out[i], d_heads[i], d_sq[i], d_skv[i], True, True, int(d_out[i] * mlp_ratio), 0.0, rt))
+                    Block("dec", d_in[i], d_out[i], d_heads[i], d_sq[i], d_skv[i], True, True, int(d_out[i] * mlp_ratio), 0.0, rt,
+                          self.drop_rate))
         self.classifier = nn.Conv3d(96, 1, kernel_size=1)
+        # dropout sites (include/csts_hip.h): 0 / 1 = video / audio pos_drop, 2 + 3*i .. 4 + 3*i for the i-th Block in
+        # registration order (blocks, blocks_audio, temporal_fusion, spatial_fusion, decode_block1..4)
+        for i, blk in enumerate([m_ for m_ in self.modules() if isinstance(m_, Block)]):
+            blk.dropout_site = 2 + 3 * i
+        self._dropout_key = None
         # ---- init (:304-325): trunc_normal(.02) pos-embeds and Linear weights, LN 1/0; convs keep torch default
         for p_ in (self.pos_embed_spatial, self.pos_embed_temporal, self.pos_embed_spatial_audio, self.pos_embed_temporal_audio):
             trunc_normal_(p_, std=0.02)
@@ -418,6 +443,19 @@ class CSTS(nn.Module):
         scales = torch.floor(keep + torch.rand(keep.shape[0], B, dtype=torch.float32, device=device)) / keep
         return {n: ("scales", scales[2 * i], scales[2 * i + 1]) for i, (n, _) in enumerate(named)}
 
+    def _draw_dropout_key(self, device):
+        """The dropout key of one forward (train mode, MVIT.DROPOUT_RATE > 0): ONE 64-bit draw from torch's device generator
+        (graph-safe like the drop-path draw: a captured forward draws a fresh key on every replay, into the buffer the captured
+        backward reads; reproducible under torch.manual_seed).  The host never reads it."""
+        if not self.training or self.drop_rate == 0.0:
+            self.rt.drop_key = self._dropout_key = None
+            return
+        key = torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64, device=device)
+        self.rt.drop_key = self._dropout_key = key
+
+    def _pos_drop(self, site):
+        return ops.Dropout(self.rt.drop_key, site, self.drop_rate) if self.rt.drop_key is not None else None
+
     def _audio_stream(self):
         # kept outside the module's attributes: a HIP stream can be neither pickled nor deep-copied
         st = _SIDE_STREAMS.get(self)
@@ -465,6 +503,7 @@ class CSTS(nn.Module):
         km = keep_masks or {}
         if self.training and keep_masks is None:
             km = self._draw_drop_paths(inpt.shape[0], inpt.device)
+        self._draw_dropout_key(inpt.device)
         twins = self._refresh_w16(defer_twins=self.two_streams and HEAD_STREAMS)
         feats, geo = self.forward_trunk(inpt, y, km, boundary, twins=twins)
         if boundary is not None:
@@ -504,14 +543,17 @@ class CSTS(nn.Module):
         transpose set whose refresh _refresh_w16 left to this function."""
         rt = self.rt
         pe, pa = self.patch_embed, self.patch_embed_audio
-        audio_embed = lambda: ops.patch_embed(y.float(), pa.proj.weight, pa.proj.bias, self.pos_embed_spatial_audio,
-                                              self.pos_embed_temporal_audio, pa.kernel, pa.stride, pa.padding, rt.act_dt, rt.compute)
+        # pos_drop (custom_multimodal_builder.py:375-377) right after the position embedding, in front of the first blocks
+        audio_embed = lambda: ops.dropout(ops.patch_embed(y.float(), pa.proj.weight, pa.proj.bias, self.pos_embed_spatial_audio,
+                                                          self.pos_embed_temporal_audio, pa.kernel, pa.stride, pa.padding, rt.act_dt,
+                                                          rt.compute), self._pos_drop(1))
         early_side = self.two_streams and HEAD_STREAMS          # the audio patch embedding and the twin refresh start the side stream
         if twins is not None and not early_side:
             twins.refresh()
         yt = None if early_side else audio_embed()
         xt = ops.patch_embed(inpt.float(), pe.proj.weight, pe.proj.bias, self.pos_embed_spatial, self.pos_embed_temporal,
                              pe.kernel, pe.stride, pe.padding, rt.act_dt, rt.compute)
+        xt = ops.dropout(xt, self._pos_drop(0))
         T, H, W = self.patch_dims
         thw, thw_a = [T, H, W], [T, H, W]
         # encoder features the decoder re-uses (:384,389,396,403): each goes through ops.tap, so that its two gradients

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import functools
 import math
 import os
 import weakref
@@ -1016,15 +1017,114 @@ def layer_norm(x, gamma, beta, eps, out_dt, passthrough: bool = False, fanout: b
     return LayerNormFn.apply(x, gamma, beta, eps, out_dt, passthrough, fanout, addend)
 
 
+# ----------------------------------------------------------------------------------------- element dropout
+class Dropout:
+    """One dropout site of one forward: nn.Dropout(p) in train mode (csts_dropout_fwd / _bwd).  key: int64 tensor of one element
+    on the device (the forward's key, never read by the host); site: the fixed site id (include/csts_hip.h); p in (0, 1).
+    For a Block, site is the base of its three sites (2 + 3*i): proj = site, MLP hidden = site + 1, MLP out = site + 2."""
+    __slots__ = ("key", "site", "p", "thr", "scale")
+
+    def __init__(self, key: torch.Tensor, site: int, p: float):
+        if not (0.0 < p < 1.0):
+            raise ValueError(f"dropout rate must be in (0, 1), got {p}")
+        if key.dtype != torch.int64 or key.numel() != 1 or not key.is_cuda:
+            raise L.CstsError("dropout key must be a one-element int64 GPU tensor")
+        self.key, self.site, self.p = key, int(site), float(p)
+        self.thr, self.scale = dropout_params(p)
+
+    def at(self, offset: int) -> "Dropout":
+        return Dropout(self.key, self.site + offset, self.p)
+
+
+@functools.lru_cache(maxsize=None)
+def dropout_params(p: float):
+    """(thr, scale) of rate p: drop iff Philox word < thr = floor(p * 2^32) (double), kept elements times 1.0f / (1.0f - p)."""
+    thr = min(int(math.floor(float(p) * 4294967296.0)), 0xFFFFFFFF)
+    one = torch.tensor(1.0, dtype=torch.float32)
+    scale = float(one / (one - torch.tensor(float(p), dtype=torch.float32)))
+    return thr, scale
+
+
+def _aligned(t: torch.Tensor) -> torch.Tensor:
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _dropout_fwd(z: torch.Tensor, drop: Dropout, residual=None, row_scale=None, rows_per_scale=1):
+    """z <- residual + row_scale * mask * scale * z, in place (z: a fresh contiguous GEMM output)."""
+    cols = z.shape[-1]
+    rows = z.numel() // cols
+    if residual is not None:
+        residual = _aligned(residual if residual.dtype == z.dtype else residual.to(z.dtype))
+    L.check(_lib().csts_dropout_fwd(_p(z), _p(residual), _p(row_scale), rows_per_scale, _p(z), _dt(z), _p(drop.key), drop.site,
+                                    drop.thr, drop.scale, rows, cols, _stream()), "csts_dropout_fwd")
+    return z
+
+
+def _dropout_bwd(dy: torch.Tensor, drop: Dropout, row_scale=None, rows_per_scale=1, out_dt=None, inplace=False):
+    """dy * row_scale * mask * scale: a new tensor of dtype out_dt (default: dy's), or dy itself (inplace)."""
+    cols = dy.shape[-1]
+    rows = dy.numel() // cols
+    if inplace:
+        out = dy
+    else:
+        dy = _aligned(dy)
+        out = torch.empty(dy.shape, dtype=dy.dtype if out_dt is None else torch_dtype(out_dt), device=dy.device)
+    L.check(_lib().csts_dropout_bwd(_p(dy), _dt(dy), _p(row_scale), rows_per_scale, _p(out), _dt(out), _p(drop.key), drop.site,
+                                    drop.thr, drop.scale, rows, cols, _stream()), "csts_dropout_bwd")
+    return out
+
+
+class DropoutFn(Function):
+    """Out-of-place nn.Dropout(p) of a whole tensor (pos_drop, custom_multimodal_builder.py:375-377)."""
+
+    @staticmethod
+    def forward(ctx, x, drop: Dropout):
+        _need_gpu(x)
+        ctx.drop = drop
+        return _dropout_bwd(x, drop)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _dropout_bwd(dy, ctx.drop), None
+
+
+def dropout(x: torch.Tensor, drop: Optional[Dropout]):
+    return x if drop is None else DropoutFn.apply(x, drop)
+
+
+def dropout_mask(key: torch.Tensor, site: int, rows: int, cols: int, p: float) -> torch.Tensor:
+    """The (rows, cols) uint8 drop mask (1 = dropped) of a site under `key`, evaluated on the device (csts_dropout_mask)."""
+    _need_gpu(key)
+    thr, _ = dropout_params(p)
+    out = torch.empty(rows, cols, dtype=torch.uint8, device=key.device)
+    L.check(_lib().csts_dropout_mask(_p(key), int(site), thr, _p(out), rows * cols, _stream()), "csts_dropout_mask")
+    return out
+
+
+def dropout_mask_host(key: int, site: int, first: int, count: int, p: float):
+    """The same mask evaluated on the CPU (csts_dropout_mask_host): a uint8 numpy array of elements first .. first + count - 1."""
+    import numpy as np
+    thr, _ = dropout_params(p)
+    out = np.zeros(max(count, 1), dtype=np.uint8)
+    k = int(key) & 0xFFFFFFFFFFFFFFFF
+    L.check(_lib().csts_dropout_mask_host(k & 0xFFFFFFFF, k >> 32, int(site), thr, int(first), int(count),
+                                          out.ctypes.data_as(C.c_void_p)), "csts_dropout_mask_host")
+    return out[:count]
+
+
 # ----------------------------------------------------------------------------------------- Linear
 class LinearFn(Function):
     """y = (x W^T + b) * row_scale + residual  (nn.Linear: attention.py:130,159,232,246; drop_path + residual
     of attention.py:242,247 folded into the epilogue)."""
 
     @staticmethod
-    def forward(ctx, x, W, b, residual, row_scale, rows_per_scale: int, out_dt: int, compute: int, w16, w16t=None, res_up=None):
+    def forward(ctx, x, W, b, residual, row_scale, rows_per_scale: int, out_dt: int, compute: int, w16, w16t=None, res_up=None,
+                drop=None):
         """res_up = (coarse thw, fine thw): `residual` is the decoder skip on the COARSE grid and the GEMM epilogue adds
-        nn.Upsample(scale_factor=stride_q, mode='trilinear')(residual) (attention.py:463-471) -- x_res is never written."""
+        nn.Upsample(scale_factor=stride_q, mode='trilinear')(residual) (attention.py:463-471) -- x_res is never written.
+        drop (optional Dropout): y = residual + row_scale * dropout(x W^T + b) -- the GEMM runs without its residual / row-scale
+        epilogue and csts_dropout_fwd applies mask, drop-path and residual in one pass over its output."""
         _need_gpu(x, W)
         x = x.contiguous()
         W = W.contiguous()
@@ -1035,8 +1135,15 @@ class LinearFn(Function):
         if residual is not None:
             residual = residual.contiguous()
         Wop = w16 if (w16 is not None and compute == BF16) else W     # bf16 shadow of the fp32 master weight
-        gemm(L.GEMM_NT, x, 0, K, Wop, 0, K, y, N, M, N, K, compute=compute, bias=b, residual=residual, ldr=N,
-             row_scale=row_scale, rows_per_scale=rows_per_scale, res_up=res_up)
+        if drop is not None:
+            if res_up is not None:
+                raise L.CstsError("linear(drop=...) does not take res_up: up-sample the skip first (ops.trilinear)")
+            gemm(L.GEMM_NT, x, 0, K, Wop, 0, K, y, N, M, N, K, compute=compute, bias=b)
+            _dropout_fwd(y, drop, residual, row_scale, rows_per_scale)
+        else:
+            gemm(L.GEMM_NT, x, 0, K, Wop, 0, K, y, N, M, N, K, compute=compute, bias=b, residual=residual, ldr=N,
+                 row_scale=row_scale, rows_per_scale=rows_per_scale, res_up=res_up)
+        ctx.drop = drop
         ctx.res_up = None
         if res_up is not None:
             thw_c, thw_f = list(res_up[0]), list(res_up[1])
@@ -1055,9 +1162,12 @@ class LinearFn(Function):
         x, W, row_scale = ctx.saved_tensors
         M, N, K, rps, compute, has_b, has_res, res_dtype = ctx.meta
         sc = (row_scale, rps) if row_scale is not None else None
-        d16 = _grad16(dy, compute, sc) if dy.is_contiguous() else None     # with drop-path: the copy pre-multiplied by it
+        drop = ctx.drop
+        d16 = _grad16(dy, compute, sc) if (dy.is_contiguous() and drop is None) else None   # with drop-path: pre-multiplied
         dy = dy.contiguous()
-        if d16 is not None:
+        if drop is not None:               # the masked copy (times drop-path), straight to bf16 when the GEMMs run in bf16
+            dys = _dropout_bwd(dy, drop, row_scale, rps, out_dt=BF16 if (compute == BF16 and BF16_GRAD_COPY) else None)
+        elif d16 is not None:
             dys = d16
         elif row_scale is not None:        # drop-path: the scaled copy goes straight to bf16 when the GEMMs run in bf16
             dys = scale_rows(dy, row_scale, rps, M, N, out_dt=BF16 if (compute == BF16 and BF16_GRAD_COPY) else None)
@@ -1083,7 +1193,7 @@ class LinearFn(Function):
                 L.check(_lib().csts_trilinear_bwd(C.byref(g), _p(dy), _dt(dy), _p(dres), _dt(dres), _stream()), "csts_trilinear_bwd(res_up)")
             else:
                 dres = dy if dy.dtype == res_dtype else dy.to(res_dtype)
-        return dx, dW, db, dres, None, None, None, None, None, None, None
+        return dx, dW, db, dres, None, None, None, None, None, None, None, None
 
 
 def _dgrad(dy, W, Wt, dx, M, N, K, compute, epilogue=L.EPI_NONE, aux=None):
@@ -1131,8 +1241,11 @@ def res_up_ok(thw_fine) -> bool:
 
 
 def linear(x, W, b=None, *, residual=None, row_scale=None, rows_per_scale=1, out_dt=F32, compute=F32, w16=None, w16t=None,
-           res_up=None):
-    y = LinearFn.apply(x, W, b, residual, row_scale, rows_per_scale, out_dt, compute, w16, w16t, res_up)
+           res_up=None, drop: Optional[Dropout] = None):
+    """drop: nn.Dropout on the Linear's output before drop-path and the residual add (proj_drop, attention.py:159-161)."""
+    y = LinearFn.apply(x, W, b, residual, row_scale, rows_per_scale, out_dt, compute, w16, w16t, res_up, drop)
+    if drop is not None:        # an elementwise mask: the next LayerNorm must not pre-scale its gradient copy by row_scale alone
+        return y
     return _mark_scaled_output(y, row_scale if residual is not None else None, rows_per_scale)
 
 
@@ -1142,7 +1255,10 @@ class MlpFn(Function):
 
     @staticmethod
     def forward(ctx, x, W1, b1, W2, b2, residual, row_scale, rows_per_scale: int, act_dt: int, out_dt: int, compute: int,
-                w16_1, w16_2, w16t_1=None, w16t_2=None):
+                w16_1, w16_2, w16t_1=None, w16t_2=None, drop=None):
+        """drop (optional Dropout, sites drop.site = hidden, drop.site + 1 = out): Mlp.drop of common.py:26-34 on the GELU output
+        (in place on g: the masked g is what fc2 and fc2's weight gradient read) and on fc2's output (csts_dropout_fwd with
+        drop-path and residual, the GEMM without that epilogue)."""
         _need_gpu(x, W1, W2)
         ctx.params = (W1, b1, W2, b2)
         ctx.w16t = (None, None)
@@ -1163,8 +1279,14 @@ class MlpFn(Function):
         y = torch.empty(*x.shape[:-1], N, dtype=torch_dtype(out_dt), device=x.device)
         if residual is not None:
             residual = residual.contiguous()
-        gemm(L.GEMM_NT, g, 0, Hd, W2, 0, Hd, y, N, M, N, Hd, compute=compute, bias=b2, residual=residual, ldr=N,
-             row_scale=row_scale, rows_per_scale=rows_per_scale)
+        ctx.drop = drop
+        if drop is not None:
+            _dropout_fwd(g, drop)
+            gemm(L.GEMM_NT, g, 0, Hd, W2, 0, Hd, y, N, M, N, Hd, compute=compute, bias=b2)
+            _dropout_fwd(y, drop.at(1), residual, row_scale, rows_per_scale)
+        else:
+            gemm(L.GEMM_NT, g, 0, Hd, W2, 0, Hd, y, N, M, N, Hd, compute=compute, bias=b2, residual=residual, ldr=N,
+                 row_scale=row_scale, rows_per_scale=rows_per_scale)
         if train:
             ctx.save_for_backward(x, W1, W2, h, g, row_scale)
         ctx.meta = (M, K, Hd, N, rows_per_scale, compute, residual is not None)
@@ -1175,9 +1297,12 @@ class MlpFn(Function):
         x, W1, W2, h, g, row_scale = ctx.saved_tensors
         M, K, Hd, N, rps, compute, has_res = ctx.meta
         sc = (row_scale, rps) if row_scale is not None else None
-        d16 = _grad16(dy, compute, sc) if dy.is_contiguous() else None     # with drop-path: the copy pre-multiplied by it
+        drop = ctx.drop
+        d16 = _grad16(dy, compute, sc) if (dy.is_contiguous() and drop is None) else None   # with drop-path: pre-multiplied
         dy = dy.contiguous()
-        if d16 is not None:
+        if drop is not None:
+            dys = _dropout_bwd(dy, drop.at(1), row_scale, rps, out_dt=BF16 if (compute == BF16 and BF16_GRAD_COPY) else None)
+        elif d16 is not None:
             dys = d16
         elif row_scale is not None:
             dys = scale_rows(dy, row_scale, rps, M, N, out_dt=BF16 if (compute == BF16 and BF16_GRAD_COPY) else None)
@@ -1187,18 +1312,23 @@ class MlpFn(Function):
         dW2, db2 = _wgrad(dys, g, M, N, Hd, compute, want_bias=True, params=(P2, pb2))
         dh = torch.empty_like(h)
         _dgrad(dys, W2, ctx.w16t[1], dh, M, N, Hd, compute, epilogue=L.EPI_DGELU, aux=h)
+        if drop is not None:               # dh = (dys W2) * GELU'(h) * mask * scale
+            _dropout_bwd(dh, drop, inplace=True)
         dW1, db1 = _wgrad(dh, x, M, Hd, K, compute, want_bias=True, params=(P1, pb1))
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             _dgrad(dh, W1, ctx.w16t[0], dx, M, Hd, K, compute)
-        return dx, dW1, db1, dW2, db2, (dy if has_res else None), None, None, None, None, None, None, None, None, None
+        return dx, dW1, db1, dW2, db2, (dy if has_res else None), None, None, None, None, None, None, None, None, None, None
 
 
 def mlp(x, W1, b1, W2, b2, *, residual=None, row_scale=None, rows_per_scale=1, act_dt=F32, out_dt=F32, compute=F32,
-        w16_1=None, w16_2=None, w16t_1=None, w16t_2=None):
+        w16_1=None, w16_2=None, w16t_1=None, w16t_2=None, drop: Optional[Dropout] = None):
+    """drop: Mlp.drop (common.py:26-34) at sites drop.site (GELU output) and drop.site + 1 (fc2 output)."""
     y = MlpFn.apply(x, W1, b1, W2, b2, residual, row_scale, rows_per_scale, act_dt, out_dt, compute, w16_1, w16_2,
-                    w16t_1, w16t_2)
+                    w16t_1, w16t_2, drop)
+    if drop is not None:
+        return y
     return _mark_scaled_output(y, row_scale if residual is not None else None, rows_per_scale)
 
 

@@ -286,6 +286,30 @@ int csts_copy_token_segments(const csts_token_segment* segs, int nseg, int B, in
 int csts_scale_rows(const void* x, int x_dt, const float* row_scale, int64_t rows_per_scale, void* out, int out_dt,
                     int64_t M, int64_t N, hipStream_t stream);   /* drop-path backward (common.py:46-59) */
 
+/* ---- element dropout, nn.Dropout(MVIT.DROPOUT_RATE) in train mode (csts_amd/csrc/dropout.hip): pos_drop
+ *      (custom_multimodal_builder.py:375-377), proj_drop (attention.py:159-161,390; av_attention.py:148,353), Mlp.drop on the
+ *      GELU output and on fc2's output (common.py:26-34).
+ *      Mask function: a pure function of (key, site, e, thr), whatever the grid, stream or tile shape.  key: one 64-bit word per
+ *      forward, in DEVICE memory (never read by the host: no sync, graph-capturable); e: the element's flat row-major index in
+ *      the site's logical (rows, cols) tensor.  Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53 / 0xCD9E8D57, key
+ *      increments 0x9E3779B9 / 0xBB67AE85) with key (lo32(key), hi32(key)) on the counter (lo32(e >> 2), hi32(e >> 2), site, 0);
+ *      element e takes output word e & 3 and is DROPPED iff word < thr, thr = floor(p * 2^32) (computed by the caller in double;
+ *      an integer compare, no float in the decision).  A kept element is multiplied by scale = 1.0f / (1.0f - p) (fp32).
+ *      Sites: 0 video pos_drop, 1 audio pos_drop; 2 + 3*i + {0 attention proj, 1 MLP hidden, 2 MLP out} for the i-th Block in
+ *      module registration order: blocks.0..15, blocks_audio.0..3, temporal_fusion, spatial_fusion, decode_block1..4.
+ *      dropout_fwd: y = residual + row_scale[r / rows_per_scale] * keep * scale * z (residual / row_scale optional, both NULL =
+ *                   the in-place form; y == z allowed), one dtype for z, residual and y.
+ *      dropout_bwd: out = dy * row_scale[r / rows_per_scale] * keep * scale (row_scale optional), into fp32 or the 16-bit type --
+ *                   the masked form of csts_scale_rows; in place when out == dy (same dtype).
+ *      All tensors contiguous and 16-byte aligned.  dropout_mask: out[e] = 1 if dropped (n elements, out 8-byte aligned).
+ *      dropout_mask_host: the same function on the CPU (HOST memory) for elements first .. first + count - 1. */
+int csts_dropout_fwd(const void* z, const void* residual, const float* row_scale, int64_t rows_per_scale, void* y, int dt,
+                     const uint64_t* key, uint32_t site, uint32_t thr, float scale, int64_t rows, int64_t cols, hipStream_t stream);
+int csts_dropout_bwd(const void* dy, int dy_dt, const float* row_scale, int64_t rows_per_scale, void* out, int out_dt,
+                     const uint64_t* key, uint32_t site, uint32_t thr, float scale, int64_t rows, int64_t cols, hipStream_t stream);
+int csts_dropout_mask(const uint64_t* key, uint32_t site, uint32_t thr, uint8_t* out, int64_t n, hipStream_t stream);
+int csts_dropout_mask_host(uint32_t key0, uint32_t key1, uint32_t site, uint32_t thr, uint64_t first, int64_t count, uint8_t* out);
+
 int csts_rowdot2(const void* a, int a_dt, const void* b, int b_dt, float* out, int64_t M, int C,
                  hipStream_t stream);   /* out[m] = <a[m,:], b[m,:]>: gradient of a per-row weight */
 
