@@ -95,7 +95,8 @@ def eval_epoch(cfg, model, cur_epoch: int, dev, rank: int, world: int):
     n = int(getattr(cfg.CSTS_AMD, "EVAL_STEPS", 2))
     acc = [0.0, 0.0, 0.0]
     for it in range(n):
-        batch = T.synthetic_batch(b, cfg.DATA.NUM_FRAMES, cfg.DATA.TEST_CROP_SIZE, 500000 + rank + 7919 * it, dev)
+        batch = T.synthetic_batch(b, cfg.DATA.NUM_FRAMES, cfg.DATA.TEST_CROP_SIZE, 500000 + rank + 7919 * it, dev,
+                                  spatial=T.spatial_config(cfg, train=False))
         preds = losses.frame_softmax(model([batch["video"]], batch["audio"]), temperature=2)
         labels_hm, labels = batch["labels_hm"], batch["labels"]
         if world > 1:
@@ -120,6 +121,7 @@ def train(cfg):
     rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
     dev = torch.device("cuda", torch.cuda.current_device())
     steps = cfg.CSTS_AMD.STEPS_PER_EPOCH
+    spatial = T.spatial_config(cfg, train=True)       # CSTS_AMD.SYNTHETIC_SOURCE_HW: on-device scale jitter / crop / flip
     from . import checkpoint as ck
     scaler = T.scaler_of(optimizer)        # fp16 mode: GradScaler state (train_avgaze_net.py:277), saved as "scaler_state"
     start_epoch = ck.load_train_checkpoint(cfg, model, optimizer, scaler=scaler)          # train_avgaze_net.py:280
@@ -137,7 +139,8 @@ def train(cfg):
     for epoch in range(start_epoch, last):
         t0 = time.time()
         for it in range(steps):
-            batch = T.synthetic_batch(b, cfg.DATA.NUM_FRAMES, cfg.DATA.TRAIN_CROP_SIZE, 1000 + rank + 7919 * (epoch * steps + it), dev)
+            batch = T.synthetic_batch(b, cfg.DATA.NUM_FRAMES, cfg.DATA.TRAIN_CROP_SIZE, 1000 + rank + 7919 * (epoch * steps + it), dev,
+                                      spatial=spatial)
             lr = T.get_lr_at_epoch(cfg, epoch + float(it) / steps)
             if getattr(cfg.CSTS_AMD, "HIP_GRAPH", True):
                 if graphed is None:
@@ -176,7 +179,7 @@ def test(cfg):
     world = max(cfg.NUM_GPUS, 1)
     b = max(1, min(cfg.TEST.BATCH_SIZE // world, 8))
     dev = torch.device("cuda", torch.cuda.current_device())
-    batch = T.synthetic_batch(b, cfg.DATA.NUM_FRAMES, cfg.DATA.TEST_CROP_SIZE, 2000, dev)
+    batch = T.synthetic_batch(b, cfg.DATA.NUM_FRAMES, cfg.DATA.TEST_CROP_SIZE, 2000, dev, spatial=T.spatial_config(cfg, train=False))
     preds = losses.frame_softmax(model([batch["video"]], batch["audio"]), temperature=2)
     # tools/test_avgaze_net.py:66-69: min-max rescale per frame, then the adaptive-threshold F1 -- both on the device
     from . import metrics

@@ -82,7 +82,8 @@ def get_cfg() -> CfgNode:
                    CHECKPOINT_FILE_PATH="")
     c.DATA = _node(PATH_PREFIX="", NUM_FRAMES=8, SAMPLING_RATE=8, TRAIN_JITTER_SCALES=[256, 320], TRAIN_CROP_SIZE=224,
                    TEST_CROP_SIZE=256, INPUT_CHANNEL_NUM=[3, 3], TARGET_FPS=30, USE_OFFSET_SAMPLING=False,
-                   GAUSSIAN_KERNEL=19, MEAN=[0.45, 0.45, 0.45], STD=[0.225, 0.225, 0.225])
+                   GAUSSIAN_KERNEL=19, MEAN=[0.45, 0.45, 0.45], STD=[0.225, 0.225, 0.225], RANDOM_FLIP=True,
+                   INV_UNIFORM_SAMPLE=False)
     c.MVIT = _node(MODE="conv", POOL_FIRST=False, CLS_EMBED_ON=True, PATCH_KERNEL=[3, 7, 7], PATCH_STRIDE=[2, 4, 4],
                    PATCH_PADDING=[2, 4, 4], PATCH_2D=False, EMBED_DIM=96, NUM_HEADS=1, MLP_RATIO=4.0, QKV_BIAS=True,
                    DROPPATH_RATE=0.1, DEPTH=16, NORM="layernorm", DIM_MUL=[], HEAD_MUL=[], POOL_KV_STRIDE=None,
@@ -108,6 +109,7 @@ def get_cfg() -> CfgNode:
     # this implementation's switches
     c.CSTS_AMD = _node(COMPUTE="auto",               # "fp32": exact-fp32 MFMA parity mode ; "bf16": throughput mode ; "fp16": the reference's autocast arithmetic + dynamic loss scaling ; "auto": by TRAIN.MIXED_PRECISION (model.resolve_compute)
                        SYNTHETIC_DATA=True,          # the data pipeline is out of scope: synthetic clips
+                       SYNTHETIC_SOURCE_HW=[],       # [H, W]: synthetic uint8 frames at that size go through the on-device spatial sampling (inputs.spatial_sampling): train mode in the train loop, test mode in eval / test; [] = frames at the crop size, normalised only
                        STEPS_PER_EPOCH=50,
                        EPOCHS_THIS_RUN=0,            # > 0: stop this invocation after that many epochs (pre-emption; the next one auto-resumes)
                        EVAL_STEPS=2,                 # synthetic validation iterations of the periodic eval pass (TRAIN.EVAL_PERIOD)

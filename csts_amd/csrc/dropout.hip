@@ -10,31 +10,11 @@
 // Memory-bound elementwise passes: 8 elements per lane and iteration = two Philox blocks, 16-byte (bf16x8 / 2 x float4) loads
 // and stores; the last partial group goes element by element.
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
-constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;
-constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
-
-__host__ __device__ __forceinline__ void mulhilo(uint32_t a, uint32_t b, uint32_t& hi, uint32_t& lo) {
-  const uint64_t p = (uint64_t)a * b;
-  hi = (uint32_t)(p >> 32);
-  lo = (uint32_t)p;
-}
-
-// Philox4x32-10 (Salmon et al., SC'11): ten rounds, the key bumped by the Weyl constants between rounds
-__host__ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    uint32_t hi0, lo0, hi1, lo1;
-    mulhilo(PHILOX_M0, c[0], hi0, lo0);
-    mulhilo(PHILOX_M1, c[2], hi1, lo1);
-    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-    c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-    k0 += PHILOX_W0;
-    k1 += PHILOX_W1;
-  }
-}
+using csts_philox::philox4x32_10;
 
 // the four words of Philox block `blk` (= element index >> 2) of a site
 __host__ __device__ __forceinline__ void dropout_block(uint32_t k0, uint32_t k1, uint32_t site, uint64_t blk, uint32_t w[4]) {

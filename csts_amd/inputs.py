@@ -71,9 +71,131 @@ def gaze_heatmaps(labels: torch.Tensor, H: int = 64, W: int = 64, ksize: int = 1
     return out
 
 
-def assemble_batch(frames_u8, wav, frames_idx, frame_length, labels):
+def spatial_sampling(frames_u8: torch.Tensor, labels: torch.Tensor, crop_size: int, *, train: bool, min_scale: int = 0,
+                     max_scale: int = 0, spatial_idx: int = 1, random_flip: bool = True, inverse_uniform: bool = False,
+                     mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225), generator=None, return_params: bool = False,
+                     key: torch.Tensor = None):
+    """slowfast/datasets/utils.py::spatial_sampling(..., gaze_loc=labels) on the device, fused with frame normalisation.
+
+    frames_u8 uint8 (B, T, H, W, 3), labels (B, T, L >= 2) with x, y in columns 0, 1 -> video fp32 (B, 3, T, S, S) and the
+    transformed labels fp64 (B, T, L) [and the int32 params (B, 5) = new h, new w, y0, x0, flip].  train=True: short-side
+    jitter in [min_scale, max_scale] (DATA.TRAIN_JITTER_SCALES), gaze-aware random crop, flip with probability 0.5
+    (DATA.RANDOM_FLIP); the clip variates come from a 64-bit key drawn once per call from `generator` (torch's default
+    device generator when None), so the call needs no host sync, can be captured in a graph and follows torch.manual_seed.
+    train=False: short side resized to crop_size and the uniform crop `spatial_idx` (0, 1, 2); no draw.  key: an int64 (1,)
+    device tensor to use instead of the draw (the kernel reads it when it runs).  include/csts_hip.h states the rule."""
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 5 or frames_u8.shape[-1] != 3:
+        raise ValueError(f"frames must be uint8 (B, T, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
+    B, T, H, W, _ = frames_u8.shape
+    if labels.dim() != 3 or tuple(labels.shape[:2]) != (B, T) or labels.shape[2] < 2 or not labels.is_floating_point():
+        raise ValueError(f"labels must be floating (B, T, L >= 2) = ({B}, {T}, L), got {tuple(labels.shape)} {labels.dtype}")
+    S = int(crop_size)
+    if not 1 <= T <= 64:
+        raise ValueError(f"spatial sampling takes 1 <= T <= 64 frames per clip, got {T}")
+    if S < 1:
+        raise ValueError(f"crop_size must be positive, got {S}")
+    if train:
+        min_scale, max_scale = int(min_scale), int(max_scale)
+        if min_scale < S:
+            raise ValueError(f"the short side would end up below the crop: min_scale {min_scale} < crop_size {S}")
+        if max_scale < min_scale:
+            raise ValueError(f"max_scale {max_scale} < min_scale {min_scale}")
+        idx = -1
+    else:
+        idx = int(spatial_idx)
+        if idx not in (0, 1, 2):
+            raise ValueError(f"spatial_idx must be 0, 1 or 2 in test mode, got {spatial_idx}")
+    _gpu(frames_u8, labels)
+    x = frames_u8.contiguous()
+    if x.data_ptr() % 16:
+        x = x.clone()
+    lab = labels.to(torch.float64).contiguous()
+    ncol = lab.shape[2]
+    dev = x.device
+    lib = L.load()
+    if not train:
+        key = None
+    elif key is None:
+        key = torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64, device=dev, generator=generator)
+    elif key.dtype != torch.int64 or key.numel() != 1 or key.device != dev:
+        raise ValueError("key must be an int64 tensor of one element on the frames' device")
+    params = torch.empty(B, 5, dtype=torch.int32, device=dev)
+    new_labels = torch.empty_like(lab)
+    L.check(lib.csts_spatial_params(key.data_ptr() if key is not None else None, lab.data_ptr(), B, T, ncol, H, W, S, min_scale,
+                                     max_scale, idx, int(bool(random_flip)), int(bool(inverse_uniform)), params.data_ptr(),
+                                     new_labels.data_ptr(), _s()), "csts_spatial_params")
+    video = spatial_sample(x, params, S, mean=mean, std=std)
+    return (video, new_labels, params) if return_params else (video, new_labels)
+
+
+def spatial_sample(frames_u8: torch.Tensor, params: torch.Tensor, crop_size: int, mean=(0.45, 0.45, 0.45),
+                   std=(0.225, 0.225, 0.225)) -> torch.Tensor:
+    """The pixel pass of spatial_sampling alone: uint8 (B, T, H, W, 3) + int32 params (B, 5) = new h, new w, y0, x0, flip ->
+    fp32 (B, 3, T, S, S) = normalised bilinear resize (F.interpolate, align_corners=False) + crop + horizontal flip."""
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 5 or frames_u8.shape[-1] != 3:
+        raise ValueError(f"frames must be uint8 (B, T, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
+    B, T, H, W, _ = frames_u8.shape
+    if params.dtype != torch.int32 or tuple(params.shape) != (B, 5):
+        raise ValueError(f"params must be int32 ({B}, 5), got {tuple(params.shape)} {params.dtype}")
+    _gpu(frames_u8, params)
+    x = frames_u8.contiguous()
+    if x.data_ptr() % 16:
+        x = x.clone()
+    S = int(crop_size)
+    out = torch.empty(B, 3, T, S, S, dtype=torch.float32, device=x.device)
+    f3 = C.c_float * 3
+    par = params.contiguous()
+    L.check(L.load().csts_spatial_sample(x.data_ptr(), par.data_ptr(), out.data_ptr(), B, T, H, W, S, f3(*mean), f3(*std), _s()),
+            "csts_spatial_sample")
+    return out
+
+
+def spatial_rule_host(labels, H: int, W: int, crop_size: int, *, train: bool, uniforms=None, min_scale: int = 0,
+                      max_scale: int = 0, spatial_idx: int = 1, random_flip: bool = True, inverse_uniform: bool = False):
+    """The rule of spatial_sampling on the CPU (csts_spatial_rule_host) from explicit variates: labels float64 (B, T, L),
+    uniforms float64 (B, 4) (train) -> (params int32 (B, 5) = new h, new w, y0, x0, flip, labels float64 (B, T, L))."""
+    import numpy as np
+    lab = np.ascontiguousarray(labels, dtype=np.float64)
+    if lab.ndim != 3:
+        raise ValueError(f"labels must be (B, T, L), got shape {lab.shape}")
+    B, T, ncol = lab.shape
+    u = None
+    if train:
+        u = np.ascontiguousarray(uniforms, dtype=np.float64)
+        if u.shape != (B, 4):
+            raise ValueError(f"uniforms must be ({B}, 4), got {u.shape}")
+    params = np.zeros((B, 5), dtype=np.int32)
+    out = np.zeros_like(lab)
+    L.check(L.load().csts_spatial_rule_host(lab.ctypes.data, B, T, ncol, H, W, int(crop_size), int(min_scale), int(max_scale),
+                                            -1 if train else int(spatial_idx), int(bool(random_flip)), int(bool(inverse_uniform)),
+                                            u.ctypes.data if u is not None else None, params.ctypes.data, out.ctypes.data),
+            "csts_spatial_rule_host")
+    return params, out
+
+
+def spatial_uniforms_host(key: int, first: int, count: int):
+    """The variates u0..u3 (float64 (count, 4)) spatial_sampling draws for clips first .. first + count - 1 under a 64-bit key
+    (csts_spatial_uniforms_host)."""
+    import numpy as np
+    key &= (1 << 64) - 1
+    out = np.zeros((count, 4), dtype=np.float64)
+    L.check(L.load().csts_spatial_uniforms_host(key & 0xFFFFFFFF, key >> 32, first, count, out.ctypes.data),
+            "csts_spatial_uniforms_host")
+    return out
+
+
+def assemble_batch(frames_u8, wav, frames_idx, frame_length, labels, spatial=None):
     """uint8 frames (B, T, H, W, 3), waveform (B, n), sampled frame indices (B, T), gaze labels (B, T, 3) -> the batch
-    dict the training step takes (video, audio, labels_hm, labels)."""
-    return {"video": normalize_frames(frames_u8),
+    dict the training step takes (video, audio, labels_hm, labels).  spatial: None (frames normalised at the size they
+    come in), or the keyword arguments of spatial_sampling (crop_size, train, ...): the video is spatially sampled, and
+    the heat maps ((S/4)^2) and the returned labels are the transformed ones (ego4d_avgaze_forecast.py:302-326)."""
+    if spatial is None:
+        return {"video": normalize_frames(frames_u8),
+                "audio": audio_windows(stft_logpower(wav), frames_idx, frame_length),
+                "labels_hm": gaze_heatmaps(labels), "labels": labels}
+    kw = dict(spatial)
+    S = int(kw.pop("crop_size"))
+    video, new_labels = spatial_sampling(frames_u8, labels, S, **kw)
+    return {"video": video,
             "audio": audio_windows(stft_logpower(wav), frames_idx, frame_length),
-            "labels_hm": gaze_heatmaps(labels), "labels": labels}
+            "labels_hm": gaze_heatmaps(new_labels, H=S // 4, W=S // 4), "labels": new_labels}

@@ -239,29 +239,59 @@ def _clip_and_step(cfg, model, optimizer):
     optimizer.step()
 
 
-def synthetic_batch(B: int, num_frames: int, crop: int, seed: int, device, pipeline: str = "device") -> Dict[str, torch.Tensor]:
+def spatial_config(cfg, train: bool):
+    """Keyword arguments of synthetic_batch(spatial=...) from CSTS_AMD.SYNTHETIC_SOURCE_HW = [H, W] (None when it is unset):
+    train mode with DATA.TRAIN_JITTER_SCALES / RANDOM_FLIP / INV_UNIFORM_SAMPLE, or test mode with the centre crop
+    (spatial_idx 1, TEST.NUM_SPATIAL_CROPS == 1 in the reference: ego4d_avgaze_forecast.py:165)."""
+    hw = list(getattr(cfg.CSTS_AMD, "SYNTHETIC_SOURCE_HW", None) or [])
+    if not hw:
+        return None
+    if len(hw) != 2:
+        raise ValueError(f"CSTS_AMD.SYNTHETIC_SOURCE_HW must be [] or [H, W], got {hw}")
+    d = {"source_hw": (int(hw[0]), int(hw[1])), "train": train, "mean": tuple(cfg.DATA.MEAN), "std": tuple(cfg.DATA.STD)}
+    if train:
+        d.update(min_scale=int(cfg.DATA.TRAIN_JITTER_SCALES[0]), max_scale=int(cfg.DATA.TRAIN_JITTER_SCALES[1]),
+                 random_flip=bool(cfg.DATA.RANDOM_FLIP), inverse_uniform=bool(cfg.DATA.INV_UNIFORM_SAMPLE))
+    else:
+        d.update(spatial_idx=1)
+    return d
+
+
+def synthetic_batch(B: int, num_frames: int, crop: int, seed: int, device, pipeline: str = "device",
+                    spatial: Optional[dict] = None) -> Dict[str, torch.Tensor]:
     """Synthetic clips generated ON DEVICE following the dataset contract (SURVEY.md 8(d);
     ego4d_avgaze_forecast.py:214-221,294-335): normalised uint8 video, log-power STFT windows of 24 kHz noise
     (n_fft 511, hop 120, win 240: data/preprocess.py:276-290), 19x19-Gaussian gaze heatmaps.
     pipeline="device": raw uint8 frames / waveform / gaze points go through the HIP input pipeline (csts_amd.inputs);
-    pipeline="torch": the same quantities with torch ops (torch.stft), the cross-check."""
+    pipeline="torch": the same quantities with torch ops (torch.stft), the cross-check.
+    spatial (device pipeline only; spatial_config): the uint8 frames are drawn at spatial["source_hw"] and spatially sampled
+    to crop x crop on the device (inputs.spatial_sampling, its key drawn from this batch's generator); heat maps and labels
+    are the transformed ones."""
     g = torch.Generator(device=device).manual_seed(seed)
     T, S = num_frames, crop
+    if spatial is not None and not (pipeline == "device" and torch.device(device).type == "cuda"):
+        raise ValueError("spatial sampling runs in the device pipeline only")
     if pipeline == "device" and torch.device(device).type == "cuda":
         from . import inputs
-        frames = torch.randint(0, 256, (B, T, S, S, 3), generator=g, device=device, dtype=torch.uint8)
+        H, W = spatial["source_hw"] if spatial is not None else (S, S)
+        frames = torch.randint(0, 256, (B, T, H, W, 3), generator=g, device=device, dtype=torch.uint8)
         n = 24000 * 5
         wav = 0.1 * torch.randn(B, n, generator=g, device=device) + 0.05 * torch.sin(
             2 * math.pi * 440.0 * torch.arange(n, device=device) / 24000.0)[None]
         xy = torch.rand(B, T, 2, generator=g, device=device)
         labels = torch.cat([xy, torch.zeros(B, T, 1, device=device)], dim=-1)
         frames_idx = (torch.arange(T, device=device, dtype=torch.float32) + 0.5)[None].expand(B, T)
-        batch = inputs.assemble_batch(frames, wav, frames_idx, float(T), labels)
+        sp = None
+        if spatial is not None:
+            sp = {k: v for k, v in spatial.items() if k != "source_hw"}
+            sp.update(crop_size=S, generator=g)
+        batch = inputs.assemble_batch(frames, wav, frames_idx, float(T), labels, spatial=sp)
         if S != 256:      # the 224^2 extension: S frequency bins x S columns around each frame, (S/4)^2 heat maps
             o = (256 - S) // 2
             batch["audio"] = batch["audio"][:, :, :, :S, o:o + S].contiguous()
-            batch["labels_hm"] = inputs.gaze_heatmaps(labels, H=S // 4, W=S // 4)
-        batch["labels"] = labels.double()
+            if sp is None:
+                batch["labels_hm"] = inputs.gaze_heatmaps(labels, H=S // 4, W=S // 4)
+        batch["labels"] = batch["labels"].double()
         return batch
     u = torch.randint(0, 256, (B, 3, T, S, S), generator=g, device=device).float()
     video = (u / 255.0 - 0.45) / 0.225

@@ -430,6 +430,45 @@ int csts_audio_windows(const float* spec, const int* centers, float* out, int B,
 int csts_gaze_heatmaps(const float* labels, int label_stride, float* heatmaps, int64_t nframes, int H, int W, int ksize,
                        hipStream_t stream);
 
+/* ---- spatial sampling on the device (csts_amd/csrc/spatial.hip): slowfast/datasets/utils.py::spatial_sampling(frames,
+ *      gaze_loc=label, ...) of the reference (ego4d_avgaze_forecast.py:302-311, aria_avgaze_forecast.py): short-side scale
+ *      jitter, gaze-aware crop and horizontal flip in train mode (spatial_idx -1, transform.py:43-97,155-197,235-262), a
+ *      short-side resize to S and a uniform crop in test mode (spatial_idx 0/1/2, transform.py:327-387).
+ *      Per clip: frames (T, H, W, 3) uint8 channels-last, labels (T, L) fp64 with x, y in columns 0, 1 (L >= 2, T <= 64); every
+ *      clip of a call has one H, W.  Rule (fp64, no contraction; u0..u3 in [0, 1)):
+ *        size = train ? rint(min + (max - min) u0)  [inv_uniform: rint(1 / (1/max + (1/min - 1/max) u0))]  : S   (half to even)
+ *        no resize if the short side == size, else short -> size, long -> floor(long / short * size)   => new h, new w
+ *        train, new h == new w == S: offsets 0, labels returned untouched (not clipped).
+ *        train otherwise, per axis of extent E (x: new w, u1; y: new h, u2): E == S -> 0; else g = sort(label * E),
+ *          low = max(0, max(g) - S), high = min(E - S, min(g)); while low > high drop g's first element if len(g) is even,
+ *          its last if odd; offset = int(low) if low == high else int(low + (high - low) u).  (Where the reference would
+ *          empty g -- one point left outside [0, E] -- the offset is min(E - S, low).)
+ *        test: offsets ceil((E - S) / 2); along the long axis (y if new h > new w, else x) idx 0 -> 0, idx 2 -> E - S.
+ *        labels (unless untouched) = clip((label * E - offset) / S, 0, 1) in columns 0, 1; columns >= 2 copied.
+ *        flip = train && random_flip && u3 < 0.5: label x -> 1 - x, pixels mirrored in x.
+ *      Variates: u[b][0..3] = Philox4x32-10 with key (lo32(key), hi32(key)) on the counters (lo32(b), hi32(b), 0x53504154, j),
+ *      j = 0 gives u0, u1 and j = 1 gives u2, u3, from the word pairs (w0, w1) and (w2, w3) as ((a >> 5) * 2^26 + (b >> 6)) * 2^-53.
+ *      key: one 64-bit word in DEVICE memory (no host sync, graph-capturable); unused (may be NULL) in test mode.
+ *      Train mode needs S <= min <= max; min / max are unused in test mode.
+ *      spatial_params: labels (B, T, L) -> params int32 [B][5] = {new h, new w, y0, x0, flip}, labels_out (B, T, L) fp64.
+ *      spatial_sample: frames (B, T, H, W, 3) uint8 + params -> fp32 (B, 3, T, S, S),
+ *        out[b][c][t][i][j] = (bilerp(y0 + i, x0 + j') / 255 - mean[c]) * (1 / std[c]), j' = flip ? S - 1 - j : j; bilerp =
+ *        F.interpolate(bilinear, align_corners=False, no antialias) of the clip to (new h, new w): scale = in / out (fp32),
+ *        src = max((dst + 0.5) scale - 0.5, 0), i0 = min(floor(src), in - 1), i1 = min(i0 + 1, in - 1), lambda = src - i0.
+ *        Unresized clips equal frames_normalize bit for bit.  Params outside the rule's range give a NaN clip.  W <= 6000,
+ *        frames and out 16-byte aligned.
+ *      spatial_rule_host: the rule on HOST memory from explicit variates uniforms[B][4] (NULL allowed in test mode).
+ *      spatial_uniforms_host: u[i][0..3] of clips first .. first + count - 1 (HOST memory). */
+int csts_spatial_params(const uint64_t* key, const double* labels, int B, int T, int L, int H, int W, int S, int min_scale,
+                        int max_scale, int spatial_idx, int random_flip, int inv_uniform, int* params, double* labels_out,
+                        hipStream_t stream);
+int csts_spatial_sample(const uint8_t* frames_thwc, const int* params, float* out, int B, int T, int H, int W, int S,
+                        const float mean[3], const float std[3], hipStream_t stream);
+int csts_spatial_rule_host(const double* labels, int B, int T, int L, int H, int W, int S, int min_scale, int max_scale,
+                           int spatial_idx, int random_flip, int inv_uniform, const double* uniforms, int* params,
+                           double* labels_out);
+int csts_spatial_uniforms_host(uint32_t key0, uint32_t key1, uint64_t first, int64_t count, double* out);
+
 #ifdef __cplusplus
 }
 #endif
