@@ -16,19 +16,21 @@ N = 1 replays the whole iteration as ONE HIP graph; N > 1 replays a chain of gra
 eagerly between them (csts_amd.train.SegmentedTrainStep).
 --mode fwd (BASELINE config 2): eval-mode forward + frame_softmax of the same batch, one HIP graph.
 
-Timing: W untimed steps, then EXACTLY K steps between barrier + synchronize, max over ranks -> `value`.  Beside it:
-`median_step_ms` = median of >= 50 single steps timed with HIP events after >= 10 warm-up steps; `fwd_ms` /
-`loss_ms` / `bwd_ms` / `optimizer_ms` (N = 1, train) = medians of the graph chain's segments.  `loss_check` compares the
-eval-mode loss of THIS model on the seed-1000 batch with the value the imported reference gave for the same weights and
-batch (tests/golden/bench_expected.json) and fails the run when they disagree.  Rank 0 prints ONE JSON line.
+Timing: W untimed steps, then EXACTLY K steps between barrier + synchronize, max over ranks -> `value`.  A plain run does
+nothing else: set up, warm up, time the K steps, write --dump-outputs, and rank 0 prints ONE JSON line.
 
 --dump-outputs DIR: right after the K timed steps, rank 0 writes what the last of them gave its caller as DIR/<name>.npy
 (float32, float64 kept; at most 16 MB per array; train: loss, kld, nce and a seeded sample of the updated parameters; fwd: heat maps and embeddings; see
 step_outputs).  Weights and batch are drawn from fixed seeds, so two builds run with the same arguments see the same inputs.
 
-Extra objects: "roofline" for the dominant kernel, measured live with HIP events on the launch stream over an
-instrumented pass, and "cpu_baseline" = the CPU oracle (a port, plain PyTorch fp32) timed on the host cores on a
-bounded sample of the same workload (rank 0, N = 1 only).
+--full adds what the headline does not need (each one can be switched off with its --no-* option):
+`loss_check` compares the eval-mode loss of THIS model on the seed-1000 batch with the value the imported reference gave
+for the same weights and batch (tests/golden/bench_expected.json) and fails the run when they disagree; after the timed
+steps, `median_step_ms` = median of >= 50 single steps timed with HIP events after >= 10 warm-up steps; `fwd_ms` /
+`loss_ms` / `bwd_ms` / `optimizer_ms` (N = 1, train) = medians of the graph chain's segments; "roofline" for the dominant
+kernel, measured live with HIP events on the launch stream over an instrumented pass (--op-breakdown, --dump-gemm and
+--dump-gemm-order write from that pass); and "cpu_baseline" = the CPU oracle (a port, plain PyTorch fp32) timed on the
+host cores on a bounded sample of the same workload (rank 0, N = 1 only).
 """
 import argparse
 import json
@@ -61,9 +63,12 @@ def parse():
     p.add_argument("--batch-per-gpu", type=int, default=4)
     p.add_argument("--compute", default="bf16", choices=["bf16", "fp32", "fp16"],
                    help="bf16: the headline mode; fp32: the parity-certified mode; fp16: the reference's autocast arithmetic + dynamic loss scaling")
-    p.add_argument("--median-steps", type=int, default=50, help="single steps timed with HIP events for median_step_ms")
+    p.add_argument("--full", action="store_true",
+                   help="also run the loss check, median_step_ms, the segment split, the roofline pass and the CPU baseline "
+                        "(the --no-* options below switch single ones off)")
+    p.add_argument("--median-steps", type=int, default=50, help="--full: single steps timed with HIP events for median_step_ms")
     p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--quick-cpu-baseline", action="store_true", help="only the headline CPU sample (B=2 at the benchmarked grid)")
+    p.add_argument("--quick-cpu-baseline", action="store_true", help="--full: only the headline CPU sample (B=2 at the benchmarked grid)")
     p.add_argument("--no-roofline", action="store_true")
     p.add_argument("--no-segments", action="store_true", help="skip the forward / backward / optimizer split (N = 1, train)")
     p.add_argument("--no-loss-check", action="store_true")
@@ -91,6 +96,8 @@ def parse():
     args = p.parse_args()
     if args.steps < 1 or args.warmup < 0:
         p.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and (args.op_breakdown or args.dump_gemm or args.dump_gemm_order):
+        p.error("--op-breakdown, --dump-gemm and --dump-gemm-order come from the roofline pass: add --full")
     return args
 
 
@@ -622,7 +629,7 @@ def main():
     model = build_model(cfg)
     core = model.module if isinstance(model, GradAllReduce) else model
     check = None
-    if rank == 0 and not args.no_loss_check:
+    if rank == 0 and args.full and not args.no_loss_check:
         check = loss_check(cfg, core, args.frames, b, S, dev, T)
     if train and dist_path and not isinstance(model, GradAllReduce):
         model = GradAllReduce(model, bucket_mb=cfg.CSTS_AMD.GRAD_BUCKET_MB)
@@ -718,22 +725,25 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     last_loss = float(res[0]) if train else None
 
+    # ---- everything below up to the result line runs with --full only
     # ---- median of single steps by HIP events (>= 10 warm-up steps have run by now: warmup + the timed ones)
-    extra_warm = max(0, 10 - args.warmup - args.steps) if args.median_steps > 0 else 0
-    for _ in range(extra_warm):
-        step()
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.median_steps + 1)]
-    evs[0].record()
-    for i in range(args.median_steps):
-        step()
-        evs[i + 1].record()
-    torch.cuda.synchronize()
-    per_step = [evs[i].elapsed_time(evs[i + 1]) for i in range(args.median_steps)]
-    median_ms = statistics.median(per_step) if per_step else None
+    median_ms = None
+    if args.full:
+        extra_warm = max(0, 10 - args.warmup - args.steps) if args.median_steps > 0 else 0
+        for _ in range(extra_warm):
+            step()
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.median_steps + 1)]
+        evs[0].record()
+        for i in range(args.median_steps):
+            step()
+            evs[i + 1].record()
+        torch.cuda.synchronize()
+        per_step = [evs[i].elapsed_time(evs[i + 1]) for i in range(args.median_steps)]
+        median_ms = statistics.median(per_step) if per_step else None
 
     # ---- forward / loss / backward / optimizer split: the same step as a chain of graphs, each segment timed by events
     segments = None
-    if train and world == 1 and not dist_path and not args.no_segments and not args.no_graph:
+    if args.full and train and world == 1 and not dist_path and not args.no_segments and not args.no_graph:
         try:
             seg = T.SegmentedTrainStep(cfg, model, opt, batch, warmup=1, trunk_cut=0)
             for _ in range(3):
@@ -753,7 +763,7 @@ def main():
             segments = {"error": repr(e)}
 
     roof = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # every rank runs the instrumented steps (they contain the gradient collectives); rank 0 reports its own timings
         _mode = _ops.GROUP_WGRADS
         if train and step_kind != "eager" and _mode == "capture":
@@ -924,9 +934,9 @@ def main():
                        "note": ("256^2 not 224^2: the reference's (1,8,8) fusion convs reject 224^2 (SURVEY.md D1)" if S == 256 else
                                 "EXTENSION, parity unpinned: 224^2 with (1,7,7) fusion kernels (CSTS_AMD.FUSION_KERNEL_FROM_GRID); "
                                 "the reference cannot run this grid, FLOP/byte figures scaled by (224/256)^2")},
-            "median_step_ms": round(median_ms, 3) if median_ms is not None else None,
-            "median_over_steps": args.median_steps,
-            "median_clips_per_s": round(b * world / median_ms * 1e3, 3) if median_ms else None,
+            **({"median_step_ms": round(median_ms, 3) if median_ms is not None else None,
+                "median_over_steps": args.median_steps,
+                "median_clips_per_s": round(b * world / median_ms * 1e3, 3) if median_ms else None} if args.full else {}),
             "end_to_end_roofline": {"mfma_frac": round(per_gpu * gflop / 1e3 / PEAK_BF16_TFLOPS, 4),
                                     "hbm_frac": round(per_gpu * gb / PEAK_HBM_GBS, 4),
                                     "gflop_per_clip": round(gflop, 1), "gb_per_clip": round(gb, 2)},
@@ -944,7 +954,7 @@ def main():
                 rc = 3
         if roof is not None:
             out["roofline"] = roof
-        if world == 1 and not dist_path and not args.no_cpu_baseline:
+        if args.full and world == 1 and not dist_path and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.frames, args.mode, args.quick_cpu_baseline, batch=args.batch_per_gpu)
             except Exception as e:  # keep the line valid even if the host runs out of memory

@@ -568,6 +568,18 @@ def test_bench_gpus_n_without_launcher_never_measures_fewer_ranks():
     assert p.returncode == 2 and p.stdout.strip() == "" and "refusing" in p.stderr
 
 
+def test_bench_roofline_dumps_need_full():
+    """--op-breakdown / --dump-gemm / --dump-gemm-order are written by the roofline pass, which only --full runs: without
+    --full they are refused before anything starts instead of leaving no file behind."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for opt in ("--op-breakdown", "--dump-gemm", "--dump-gemm-order"):
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", opt, os.devnull],
+                           capture_output=True, text=True, timeout=300)
+        assert p.returncode == 2 and p.stdout.strip() == "" and "--full" in p.stderr, (opt, p.stderr[-2000:])
+
+
 def test_act_checkpoint_key_is_logged_not_ignored(caplog):
     """MODEL.ACT_CHECKPOINT (custom_multimodal_builder.py:154,178,214: fairscale checkpoint_wrapper) changes memory, not
     values: accepted, and the decision is logged when the key is set."""

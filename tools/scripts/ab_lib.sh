@@ -8,7 +8,7 @@ cd "$R"
 for i in $(seq 1 $N); do
   for v in old new; do
     if [ $v = old ]; then export CSTS_HIP_LIB=$OLD; else unset CSTS_HIP_LIB; fi
-    python bench.py --steps 20 --warmup 5 --median-steps 30 --no-cpu-baseline --no-roofline --no-segments --no-loss-check 2>/dev/null \
+    python bench.py --full --steps 20 --warmup 5 --median-steps 30 --no-cpu-baseline --no-roofline --no-segments --no-loss-check 2>/dev/null \
       | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', d['ms_per_step'], d['median_step_ms'])"
   done
 done

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 O="$R/gpurun_out/${1:-mfma_util}"
 mkdir -p $O
 cd "$R"
-B="python3 bench.py --one-stream --median-steps 0 --no-cpu-baseline --no-segments --no-loss-check"
+B="python3 bench.py --full --one-stream --median-steps 0 --no-cpu-baseline --no-segments --no-loss-check"
 python tools/step_kernel_counts.py --help > /dev/null 2>&1 || true
 # graph replay: kernel durations + the ordered GEMM list (algorithmic bytes / flops per kernel name)
 timeout -k 10 600 $B --steps 5 --warmup 3 --dump-gemm-order $O/order.json > $O/bench.json 2> $O/bench.err

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 O="$R/gpurun_out/r2v2"
 mkdir -p $O
 cd "$R"
-timeout -k 10 900 python bench.py --op-breakdown $O/op_breakdown.txt --dump-gemm $O/gemm_shapes.txt > $O/bench.json 2> $O/bench.err
+timeout -k 10 900 python bench.py --full --op-breakdown $O/op_breakdown.txt --dump-gemm $O/gemm_shapes.txt > $O/bench.json 2> $O/bench.err
 tail -c 600 $O/bench.json
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o x -- python3 bench.py --steps 4 --warmup 2 --median-steps 0 --quick-cpu-baseline --no-segments --no-loss-check --no-roofline > $O/prof_bench.txt 2>&1
 python tools/sum_kernel_trace.py $O/prof _kernel > $O/kernel_by_grid.txt

@@ -1,5 +1,5 @@
 """Per-shape GEMM launch durations INSIDE THE HIP-GRAPH REPLAY: zip the ordered launch list of one step
-(bench.py --one-stream --dump-gemm-order order.json) with a rocprofv3 --kernel-trace of `bench.py --one-stream` (one stream,
+(bench.py --full --one-stream --dump-gemm-order order.json) with a rocprofv3 --kernel-trace of `bench.py --one-stream` (one stream,
 so the trace's start order is the issue order).
 
     python tools/trace_gemm_map.py <trace dir> <order.json> [<out.txt>]
