@@ -1,14 +1,17 @@
-// Multi-tensor optimizer step of the CSTS training iteration: the L2 gradient-norm clip of
-// tools/train_avgaze_net.py:105-106 (torch.nn.utils.clip_grad_norm_, max_norm 1.0) and the AdamW update of
-// slowfast/models/optimizer.py:85-93 (torch.optim.AdamW, eps 1e-8, weight decay 0 on 1-D parameters and biases),
-// over all ~524 parameter tensors in TWO launches instead of ~65, with the bf16 shadow weights the GEMMs read
-// refreshed by the same pass.  Pure HBM streaming: 30 bytes per parameter (read p, g, m, v; write p, m, v, w16).
+// Multi-tensor optimizer step of the CSTS training iteration: the gradient clip of
+// tools/train_avgaze_net.py:101-106 (torch.nn.utils.clip_grad_norm_ or clip_grad_value_) and the update rule of
+// slowfast/models/optimizer.py:82-108 (SOLVER.OPTIMIZING_METHOD: torch.optim.AdamW eps 1e-8, torch.optim.Adam, torch.optim.SGD;
+// weight decay 0 on 1-D parameters and biases), over all ~524 parameter tensors in THREE launches instead of ~65, with the bf16
+// shadow weights the GEMMs read refreshed by the same pass.  Pure HBM streaming, bytes per parameter: AdamW / Adam 30 (read p,
+// g, m, v; write p, m, v, w16), SGD with momentum 22 (read p, g, buf; write p, buf, w16), SGD without momentum 14.
 //
 // Layout: the host describes the parameter set once as a CHUNK list (chunk -> tensor id, element offset; chunks never
 // straddle tensors) plus a per-tensor table; only the gradient pointers change between steps.  Step count, learning
-// rate and the clip coefficient live in device memory, so a captured HIP graph replays the schedule correctly.
+// rate and the clip coefficient live in device memory, so a captured HIP graph replays the schedule correctly.  The update rule
+// is a template parameter of the update kernels (their names stay opt_adamw_*: the trace tools find step boundaries by them).
 #include "common.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -137,9 +140,60 @@ __device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v,
   p -= step_size * (m / denom);
 }
 
-template <bool G16>
+// the rule's run-time parameters (csts_opt_rule)
+struct RuleK {
+  float momentum, dampening;
+  float clip_value;    // > 0: clip_grad_value_ (the VC instantiations)
+  int nesterov;
+  float* buf_step;     // SGD with momentum: per tensor, the step count at which its momentum buffer was initialised (0: never)
+};
+
+// Per-parameter update of rule R (CSTS_OPT_ADAMW / ADAM / SGD), with value clipping when VC (a template flag: the clamp costs the
+// MFMA form of the update 14 VGPRs, one wave per SIMD, and the plain AdamW instantiation stays the code it was).  g arrives loss-scaled and unclipped; clip = the norm clip
+// coefficient times 1 / loss scale (state[2]).  Value clipping (clip_grad_value_) clamps the unscaled gradient before weight decay,
+// the order of scaler.unscale_ -> clip_grad_value_ -> scaler.step.  SGD: `first` = this tensor's momentum buffer is initialised
+// by this step (torch: buf = clone(d)); m is the momentum buffer, v unused.
+template <int R, bool VC>
+__device__ __forceinline__ void rule_one(float& p, float g, float& m, float& v, float clip, float lr, float wd, float b1, float b2, float eps,
+                                         float step_size, float rsqrt_bc2, const RuleK& r, bool first) {
+  g *= clip;
+  if constexpr (VC) g = g < -r.clip_value ? -r.clip_value : (g > r.clip_value ? r.clip_value : g);     // torch.clamp (NaN stays NaN)
+  if constexpr (R == CSTS_OPT_ADAMW) {
+    adamw_one(p, g, m, v, 1.f, lr, wd, b1, b2, eps, step_size, rsqrt_bc2);
+  } else if constexpr (R == CSTS_OPT_ADAM) {
+    g += wd * p;                            // coupled L2 decay (torch.optim.Adam: grad.add(param, alpha=wd))
+    m += (1.f - b1) * (g - m);
+    v = b2 * v + (1.f - b2) * g * g;
+    const float denom = sqrtf(v) * rsqrt_bc2 + eps;
+    p -= step_size * (m / denom);
+  } else {                                  // torch.optim.SGD
+    float d = g + wd * p;
+    if (r.momentum != 0.f) {
+      m = first ? d : r.momentum * m + (1.f - r.dampening) * d;
+      d = r.nesterov ? d + r.momentum * m : m;
+    }
+    p -= lr * d;
+  }
+}
+
+// SGD with momentum: is the buffer of tensor `ti` initialised by this step?  Every workgroup of the tensor reads the flag before
+// any of them writes it, or reads the value this step writes (the current step count): both mean "first".  Written by one lane of
+// one workgroup per tensor after its update, never on a skipped step (the caller returns before).
+template <int R> __device__ __forceinline__ bool rule_first(const RuleK& r, int ti, float step) {
+  if constexpr (R != CSTS_OPT_SGD) return false;
+  if (r.momentum == 0.f) return false;
+  const float f = r.buf_step[ti];
+  return f == 0.f || f == step;
+}
+template <int R> __device__ __forceinline__ void rule_mark(const RuleK& r, int ti, float step, bool first, bool leader) {
+  if constexpr (R == CSTS_OPT_SGD) {
+    if (first && leader) r.buf_step[ti] = step;
+  }
+}
+
+template <bool G16, int R, bool VC>
 __global__ __launch_bounds__(OPT_THREADS) void opt_adamw_kernel(OptTables t, int chunk_elems, const float* __restrict__ lr_ptr,
-                                                                const float* __restrict__ state, float b1, float b2, float eps) {
+                                                                const float* __restrict__ state, float b1, float b2, float eps, RuleK rk) {
   const int c = blockIdx.x;
   const int ti = t.chunk_tensor[c];
   const char* g = reinterpret_cast<const char*>(t.grads[ti]);
@@ -150,9 +204,13 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_adamw_kernel(OptTables t, int
   const float lr = *lr_ptr, step = state[0], clip = state[2];
   const float bc1 = 1.f - powf(b1, step), bc2 = 1.f - powf(b2, step);
   const float step_size = lr / bc1, rsqrt_bc2 = 1.f / sqrtf(bc2);
+  constexpr bool USE_V = R != CSTS_OPT_SGD;
+  const bool use_m = R != CSTS_OPT_SGD || rk.momentum != 0.f;       // SGD without momentum keeps no buffer: m / v are never touched
+  if ((use_m && tt.m == nullptr) || (USE_V && tt.v == nullptr)) return;      // the table is device memory: a missing buffer is never dereferenced
+  const bool first = rule_first<R>(rk, ti, step);
   float* p = reinterpret_cast<float*>(tt.p) + off;
-  float* m = reinterpret_cast<float*>(tt.m) + off;
-  float* v = reinterpret_cast<float*>(tt.v) + off;
+  float* m = use_m ? reinterpret_cast<float*>(tt.m) + off : nullptr;
+  float* v = USE_V ? reinterpret_cast<float*>(tt.v) + off : nullptr;
   bf16* w16 = tt.w16 ? reinterpret_cast<bf16*>(tt.w16) + off : nullptr;
   g += off * (G16 ? 2 : 4);
   const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) == 0 &&
@@ -160,19 +218,22 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_adamw_kernel(OptTables t, int
   int64_t done = 0;
   if (vec) {
     const int64_t n4 = n / OPT_VEC;
-    const StreamOut sp(p, n * 4), sm(m, n * 4), sv(v, n * 4), sw(w16 ? (void*)w16 : (void*)p, n * 2);     // chunk_elems * 4 < 2^31 (csts_adamw_step)
+    const StreamOut sp(p, n * 4), sm(m ? (void*)m : (void*)p, n * 4), sv(v ? (void*)v : (void*)p, n * 4),
+        sw(w16 ? (void*)w16 : (void*)p, n * 2);     // chunk_elems * 4 < 2^31 (csts_opt_step)
     auto f4 = [](const float4& x) { f32x4 o; o[0] = x.x; o[1] = x.y; o[2] = x.z; o[3] = x.w; return o; };
     for (int64_t i = threadIdx.x; i < n4; i += OPT_THREADS) {
       float4 pp = ld4s(p, i);
       const float4 gg = ldg4<G16>(g, i);
-      float4 mm = ld4s(m, i), vv = ld4s(v, i);
-      adamw_one(pp.x, gg.x, mm.x, vv.x, clip, lr, tt.weight_decay, b1, b2, eps, step_size, rsqrt_bc2);
-      adamw_one(pp.y, gg.y, mm.y, vv.y, clip, lr, tt.weight_decay, b1, b2, eps, step_size, rsqrt_bc2);
-      adamw_one(pp.z, gg.z, mm.z, vv.z, clip, lr, tt.weight_decay, b1, b2, eps, step_size, rsqrt_bc2);
-      adamw_one(pp.w, gg.w, mm.w, vv.w, clip, lr, tt.weight_decay, b1, b2, eps, step_size, rsqrt_bc2);
+      float4 mm = make_float4(0.f, 0.f, 0.f, 0.f), vv = mm;
+      if (use_m && !first) mm = ld4s(m, i);
+      if (USE_V) vv = ld4s(v, i);
+      rule_one<R, VC>(pp.x, gg.x, mm.x, vv.x, clip, lr, tt.weight_decay, b1, b2, eps, step_size, rsqrt_bc2, rk, first);
+      rule_one<R, VC>(pp.y, gg.y, mm.y, vv.y, clip, lr, tt.weight_decay, b1, b2, eps, step_size, rsqrt_bc2, rk, first);
+      rule_one<R, VC>(pp.z, gg.z, mm.z, vv.z, clip, lr, tt.weight_decay, b1, b2, eps, step_size, rsqrt_bc2, rk, first);
+      rule_one<R, VC>(pp.w, gg.w, mm.w, vv.w, clip, lr, tt.weight_decay, b1, b2, eps, step_size, rsqrt_bc2, rk, first);
       sp.st16((int)i * 16, f4(pp));
-      sm.st16((int)i * 16, f4(mm));
-      sv.st16((int)i * 16, f4(vv));
+      if (use_m) sm.st16((int)i * 16, f4(mm));
+      if (USE_V) sv.st16((int)i * 16, f4(vv));
       if (w16) {
         bf16x4 w;
         w[0] = (bf16)pp.x; w[1] = (bf16)pp.y; w[2] = (bf16)pp.z; w[3] = (bf16)pp.w;
@@ -182,11 +243,14 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_adamw_kernel(OptTables t, int
     done = n4 * OPT_VEC;
   }
   for (int64_t i = done + threadIdx.x; i < n; i += OPT_THREADS) {
-    float pp = p[i], mm = m[i], vv = v[i];
-    adamw_one(pp, ldg<G16>(g, i), mm, vv, clip, lr, tt.weight_decay, b1, b2, eps, step_size, rsqrt_bc2);
-    p[i] = pp; m[i] = mm; v[i] = vv;
+    float pp = p[i], mm = use_m && !first ? m[i] : 0.f, vv = USE_V ? v[i] : 0.f;
+    rule_one<R, VC>(pp, ldg<G16>(g, i), mm, vv, clip, lr, tt.weight_decay, b1, b2, eps, step_size, rsqrt_bc2, rk, first);
+    p[i] = pp;
+    if (use_m) m[i] = mm;
+    if (USE_V) v[i] = vv;
     if (w16) w16[i] = (bf16)pp;
   }
+  rule_mark<R>(rk, ti, step, first, off == 0 && threadIdx.x == 0);
 }
 
 
@@ -274,8 +338,9 @@ __global__ __launch_bounds__(1024) void factored_sq_finish_kernel(FactoredList l
 // tile: FR rows n x FK columns k; g[n][k] = sum_t dy[t][n] A[t][k] in fp32, then the AdamW update of csts_adamw_step.  A thread owns
 // 4 consecutive columns of FR / 4 rows: one float4 of the operand tile per token row feeds all of them from registers.
 constexpr int FR = 32;
+template <int R, bool VC>
 __global__ __launch_bounds__(256) void opt_adamw_factored_kernel(FactoredList l, const float* __restrict__ lr_ptr,
-                                                                 const float* __restrict__ state, float b1, float b2, float eps) {
+                                                                 const float* __restrict__ state, float b1, float b2, float eps, RuleK rk) {
   extern __shared__ __attribute__((aligned(16))) float fsm[];                     // [T][FK] operand tile, then [T][FR] dY tile
   if (state[3] != 0.f) return;                                  // step skipped by the loss scaler
   const csts_opt_factored& it = l.it[blockIdx.z];
@@ -299,6 +364,9 @@ __global__ __launch_bounds__(256) void opt_adamw_factored_kernel(FactoredList l,
   const float lr = *lr_ptr, step = state[0], clip = state[2];
   const float bc1 = 1.f - powf(b1, step), bc2 = 1.f - powf(b2, step);
   const float step_size = lr / bc1, rsqrt_bc2 = 1.f / sqrtf(bc2);
+  const bool use_m = R != CSTS_OPT_SGD || rk.momentum != 0.f;
+  constexpr bool USE_V = R != CSTS_OPT_SGD;
+  const bool first = rule_first<R>(rk, it.tensor, step);
   const int kq = (threadIdx.x & 63) * 4;                        // 4 consecutive columns
   const int nr = threadIdx.x >> 6;                              // rows nr, nr + 4, ..., nr + FR - 4
   constexpr int RPT = FR / 4;
@@ -318,20 +386,23 @@ __global__ __launch_bounds__(256) void opt_adamw_factored_kernel(FactoredList l,
     const int n = n0 + nr + 4 * rr;
     if (n >= it.N) continue;
     const int64_t at = (int64_t)n * it.K + k0 + kq;
-    float4 pp = *reinterpret_cast<float4*>(it.p + at), mm = *reinterpret_cast<float4*>(it.m + at), vv = *reinterpret_cast<float4*>(it.v + at);
-    adamw_one(pp.x, g[rr][0], mm.x, vv.x, clip, lr, it.weight_decay, b1, b2, eps, step_size, rsqrt_bc2);
-    adamw_one(pp.y, g[rr][1], mm.y, vv.y, clip, lr, it.weight_decay, b1, b2, eps, step_size, rsqrt_bc2);
-    adamw_one(pp.z, g[rr][2], mm.z, vv.z, clip, lr, it.weight_decay, b1, b2, eps, step_size, rsqrt_bc2);
-    adamw_one(pp.w, g[rr][3], mm.w, vv.w, clip, lr, it.weight_decay, b1, b2, eps, step_size, rsqrt_bc2);
+    float4 pp = *reinterpret_cast<float4*>(it.p + at), mm = make_float4(0.f, 0.f, 0.f, 0.f), vv = mm;
+    if (use_m && !first) mm = *reinterpret_cast<float4*>(it.m + at);
+    if (USE_V) vv = *reinterpret_cast<float4*>(it.v + at);
+    rule_one<R, VC>(pp.x, g[rr][0], mm.x, vv.x, clip, lr, it.weight_decay, b1, b2, eps, step_size, rsqrt_bc2, rk, first);
+    rule_one<R, VC>(pp.y, g[rr][1], mm.y, vv.y, clip, lr, it.weight_decay, b1, b2, eps, step_size, rsqrt_bc2, rk, first);
+    rule_one<R, VC>(pp.z, g[rr][2], mm.z, vv.z, clip, lr, it.weight_decay, b1, b2, eps, step_size, rsqrt_bc2, rk, first);
+    rule_one<R, VC>(pp.w, g[rr][3], mm.w, vv.w, clip, lr, it.weight_decay, b1, b2, eps, step_size, rsqrt_bc2, rk, first);
     *reinterpret_cast<float4*>(it.p + at) = pp;
-    *reinterpret_cast<float4*>(it.m + at) = mm;
-    *reinterpret_cast<float4*>(it.v + at) = vv;
+    if (use_m) *reinterpret_cast<float4*>(it.m + at) = mm;
+    if (USE_V) *reinterpret_cast<float4*>(it.v + at) = vv;
     if (it.w16 != nullptr) {
       bf16x4 w;
       w[0] = (bf16)pp.x; w[1] = (bf16)pp.y; w[2] = (bf16)pp.z; w[3] = (bf16)pp.w;
       *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16*>(it.w16) + at) = w;
     }
   }
+  rule_mark<R>(rk, it.tensor, step, first, blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0);
 }
 
 // 16-bit operand form: g = dY^T A on the matrix cores (dY rounded to the 16-bit type, fp32 accumulation -- the arithmetic of the TN
@@ -339,8 +410,9 @@ __global__ __launch_bounds__(256) void opt_adamw_factored_kernel(FactoredList l,
 // straight from memory in MFMA layout (dY 98 KB and the k-columns of A: L2-resident), and p / m / v stream through once with the
 // optimizer's cache policy.  Accumulator r of lane l is row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31: a half-wave
 // touches 128 contiguous bytes of a row per access.
+template <int R, bool VC>
 __global__ __launch_bounds__(256) void opt_adamw_factored_mfma_kernel(FactoredList l, const float* __restrict__ lr_ptr,
-                                                                      const float* __restrict__ state, float b1, float b2, float eps) {
+                                                                      const float* __restrict__ state, float b1, float b2, float eps, RuleK rk) {
   if (state[3] != 0.f) return;                                  // step skipped by the loss scaler
   const csts_opt_factored& it = l.it[blockIdx.z];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -375,9 +447,13 @@ __global__ __launch_bounds__(256) void opt_adamw_factored_mfma_kernel(FactoredLi
 #else
   constexpr int LD_AUX = 2, ST_AUX = 17;                        // nontemporal loads, write-through stores (common.h)
 #endif
+  const bool use_m = R != CSTS_OPT_SGD || rk.momentum != 0.f;
+  constexpr bool USE_V = R != CSTS_OPT_SGD;
+  const bool first = rule_first<R>(rk, it.tensor, step);
   const int bytes = (int)((int64_t)N * K * 4);
-  const auto rp = __builtin_amdgcn_make_buffer_rsrc(it.p, 0, bytes, 0x00020000), rm = __builtin_amdgcn_make_buffer_rsrc(it.m, 0, bytes, 0x00020000),
-             rv = __builtin_amdgcn_make_buffer_rsrc(it.v, 0, bytes, 0x00020000),
+  const auto rp = __builtin_amdgcn_make_buffer_rsrc(it.p, 0, bytes, 0x00020000),
+             rm = __builtin_amdgcn_make_buffer_rsrc(use_m ? (void*)it.m : (void*)it.p, 0, bytes, 0x00020000),
+             rv = __builtin_amdgcn_make_buffer_rsrc(USE_V ? (void*)it.v : (void*)it.p, 0, bytes, 0x00020000),
              rw = __builtin_amdgcn_make_buffer_rsrc(it.w16 != nullptr ? it.w16 : (void*)it.p, 0, bytes / 2, 0x00020000);
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
@@ -387,37 +463,39 @@ __global__ __launch_bounds__(256) void opt_adamw_factored_mfma_kernel(FactoredLi
       const int n = n0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
       const int off = (n < N) ? (n * K + kl + 32 * j) * 4 : 0;
       pp[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, off, 0, LD_AUX));
-      mm[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rm, off, 0, LD_AUX));
-      vv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rv, off, 0, LD_AUX));
+      mm[r] = use_m && !first ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rm, off, 0, LD_AUX)) : 0.f;
+      vv[r] = USE_V ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rv, off, 0, LD_AUX)) : 0.f;
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int n = n0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
       if (n >= N) continue;
       const int off = (n * K + kl + 32 * j) * 4;
-      adamw_one(pp[r], acc[j][r], mm[r], vv[r], clip, lr, it.weight_decay, b1, b2, eps, step_size, rsqrt_bc2);
+      rule_one<R, VC>(pp[r], acc[j][r], mm[r], vv[r], clip, lr, it.weight_decay, b1, b2, eps, step_size, rsqrt_bc2, rk, first);
       __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, pp[r]), rp, off, 0, ST_AUX);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, mm[r]), rm, off, 0, ST_AUX);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vv[r]), rv, off, 0, ST_AUX);
+      if (use_m) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, mm[r]), rm, off, 0, ST_AUX);
+      if (USE_V) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vv[r]), rv, off, 0, ST_AUX);
       if (it.w16 != nullptr) __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (bf16)pp[r]), rw, off / 2, 0, ST_AUX);
     }
   }
+  rule_mark<R>(rk, it.tensor, step, first, blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0);
 }
 
 }  // namespace
 
 constexpr int FT_MFMA = 256;  // token rows the MFMA form of the update takes (no LDS tile, a k-loop over T): the data-parallel chain's W * B * T' rows at 8 ranks
-static int factored_fill(const csts_opt_factored* items, int nitems, FactoredList& l, int* max_k, int* max_n, int max_t = FT) {
+static int factored_fill(const csts_opt_factored* items, int nitems, FactoredList& l, int* max_k, int* max_n, int max_t = FT,
+                         bool need_m = true, bool need_v = true) {
   CSTS_REQUIRE(items != nullptr && nitems > 0 && nitems <= FMAX, "1 .. 8 items per call");
   *max_k = 0; *max_n = 0;
   int64_t off = 0;
   for (int i = 0; i < nitems; ++i) {
     const csts_opt_factored& it = items[i];
-    CSTS_REQUIRE(it.p && it.m && it.v && it.dy && it.a, "null pointer");
+    CSTS_REQUIRE(it.p && (it.m || !need_m) && (it.v || !need_v) && it.dy && it.a, "null pointer");
     CSTS_REQUIRE(it.T > 0 && it.T <= max_t && it.K > 0 && it.K % FK == 0 && it.N > 0 && it.N % 16 == 0,
                  "T <= 64 (256 for the update with 16-bit operands), K % 256 == 0, N % 16 == 0");
     CSTS_REQUIRE(it.a_dt == CSTS_F32 || it.a_dt == CSTS_HALF, "bad a dtype");
-    CSTS_REQUIRE(aligned16(it.p) && aligned16(it.m) && aligned16(it.v) && (it.w16 == nullptr || ((uintptr_t)it.w16 & 7) == 0), "alignment");
+    CSTS_REQUIRE(aligned16(it.p) && (!need_m || aligned16(it.m)) && (!need_v || aligned16(it.v)) && (it.w16 == nullptr || ((uintptr_t)it.w16 & 7) == 0), "alignment");
     l.it[i] = it;
     l.ws_off[i] = off;
     off += (int64_t)(it.K / FK) * it.T * it.T;
@@ -436,7 +514,7 @@ extern "C" int csts_factored_sqnorm(const csts_opt_factored* items, int nitems, 
                                     hipStream_t stream) {
   FactoredList l;
   int mk, mn;
-  if (int rc = factored_fill(items, nitems, l, &mk, &mn)) return rc;
+  if (int rc = factored_fill(items, nitems, l, &mk, &mn, FT, false, false)) return rc;     // the norm reads dy and a only
   CSTS_REQUIRE(out_sq != nullptr && workspace != nullptr && aligned16(workspace) && ws_bytes >= csts_factored_sqnorm_workspace(items, nitems), "workspace too small");
   float* slabs = reinterpret_cast<float*>(workspace);
   int mt = 0;
@@ -454,33 +532,77 @@ extern "C" int csts_factored_sqnorm(const csts_opt_factored* items, int nitems, 
   CSTS_LAUNCH_CHECK();
   return 0;
 }
-extern "C" int csts_adamw_factored(const csts_opt_factored* items, int nitems, const float* state, const float* lr, float beta1,
-                                   float beta2, float eps, hipStream_t stream) {
+static int rule_check(const csts_opt_rule* rule, RuleK* rk) {
+  CSTS_REQUIRE(rule != nullptr, "null rule");
+  CSTS_REQUIRE(rule->kind == CSTS_OPT_ADAMW || rule->kind == CSTS_OPT_ADAM || rule->kind == CSTS_OPT_SGD, "bad rule kind");
+  CSTS_REQUIRE(rule->kind == CSTS_OPT_SGD || (rule->momentum == 0.f && rule->dampening == 0.f && rule->nesterov == 0),
+               "momentum / dampening / nesterov belong to the SGD rule");
+  CSTS_REQUIRE(rule->momentum >= 0.f && rule->dampening >= 0.f && rule->dampening <= 1.f, "bad momentum / dampening");
+  CSTS_REQUIRE(!rule->nesterov || (rule->momentum > 0.f && rule->dampening == 0.f), "nesterov needs momentum and zero dampening");
+  CSTS_REQUIRE(rule->clip_value == rule->clip_value, "bad clip_value");
+  const bool sgd_m = rule->kind == CSTS_OPT_SGD && rule->momentum != 0.f;
+  CSTS_REQUIRE(!sgd_m || rule->buf_step != nullptr, "SGD with momentum needs buf_step");
+  *rk = RuleK{rule->momentum, rule->dampening, rule->clip_value > 0.f ? rule->clip_value : 0.f, rule->nesterov ? 1 : 0,
+              sgd_m ? rule->buf_step : nullptr};
+  return 0;
+}
+// m / v of a tensor or item: required where the rule reads them, may be NULL elsewhere
+static bool rule_uses_m(const csts_opt_rule* rule) { return rule->kind != CSTS_OPT_SGD || rule->momentum != 0.f; }
+static bool rule_uses_v(const csts_opt_rule* rule) { return rule->kind != CSTS_OPT_SGD; }
+
+// k(rule, value clip) with both as compile-time constants
+template <typename K3> static void launch_rule(int kind, bool vc, K3 k) {
+  using VT = std::true_type;
+  using VF = std::false_type;
+  if (kind == CSTS_OPT_ADAMW) vc ? k(std::integral_constant<int, CSTS_OPT_ADAMW>{}, VT{}) : k(std::integral_constant<int, CSTS_OPT_ADAMW>{}, VF{});
+  else if (kind == CSTS_OPT_ADAM) vc ? k(std::integral_constant<int, CSTS_OPT_ADAM>{}, VT{}) : k(std::integral_constant<int, CSTS_OPT_ADAM>{}, VF{});
+  else vc ? k(std::integral_constant<int, CSTS_OPT_SGD>{}, VT{}) : k(std::integral_constant<int, CSTS_OPT_SGD>{}, VF{});
+}
+
+extern "C" int csts_opt_factored_step(const csts_opt_factored* items, int nitems, const csts_opt_rule* rule, const float* state,
+                                      const float* lr, float beta1, float beta2, float eps, hipStream_t stream) {
+  RuleK rk;
+  if (int rc = rule_check(rule, &rk)) return rc;
   FactoredList l;
   int mk, mn;
   bool half_ops = items != nullptr && nitems > 0 && nitems <= FMAX;
   for (int i = 0; half_ops && i < nitems; ++i) half_ops = items[i].a_dt == CSTS_HALF && (int64_t)items[i].N * items[i].K * 4 < ((int64_t)1 << 31) && items[i].K % 64 == 0;
-  if (int rc = factored_fill(items, nitems, l, &mk, &mn, half_ops ? FT_MFMA : FT)) return rc;
+  if (int rc = factored_fill(items, nitems, l, &mk, &mn, half_ops ? FT_MFMA : FT, rule_uses_m(rule), rule_uses_v(rule))) return rc;
   CSTS_REQUIRE(state != nullptr && lr != nullptr, "null state");
+  for (int i = 0; i < nitems; ++i) CSTS_REQUIRE(items[i].tensor >= 0, "bad item tensor index");
   int mt = 0;
   for (int i = 0; i < nitems; ++i) mt = std::max(mt, items[i].T);
   bool all16 = true;
   for (int i = 0; i < nitems; ++i) all16 = all16 && items[i].a_dt == CSTS_HALF && (int64_t)items[i].N * items[i].K * 4 < ((int64_t)1 << 31) && items[i].K % 64 == 0;
   if (all16) {
-    hipLaunchKernelGGL(opt_adamw_factored_mfma_kernel, dim3((unsigned)(mk / FK), (unsigned)cdiv(mn, 32), (unsigned)nitems), dim3(256), 0, stream, l, lr,
-                       state, beta1, beta2, eps);
+    launch_rule(rule->kind, rk.clip_value > 0.f, [&](auto R, auto V) {
+      hipLaunchKernelGGL((opt_adamw_factored_mfma_kernel<decltype(R)::value, decltype(V)::value>), dim3((unsigned)(mk / FK), (unsigned)cdiv(mn, 32), (unsigned)nitems),
+                         dim3(256), 0, stream, l, lr, state, beta1, beta2, eps, rk);
+    });
     CSTS_LAUNCH_CHECK();
     return 0;
   }
   const size_t sm = (size_t)mt * (FK + FR) * sizeof(float);
-  CSTS_REQUIRE(sm <= 64 * 1024 || csts_dyn_lds_optin(reinterpret_cast<const void*>(&opt_adamw_factored_kernel), (int)sm), "LDS opt-in failed");
-  hipLaunchKernelGGL(opt_adamw_factored_kernel, dim3((unsigned)(mk / FK), (unsigned)cdiv(mn, FR), (unsigned)nitems), dim3(256), sm, stream, l, lr,
-                     state, beta1, beta2, eps);
+  int rc = 0;
+  launch_rule(rule->kind, rk.clip_value > 0.f, [&](auto R, auto V) {
+    const void* fn = reinterpret_cast<const void*>(&opt_adamw_factored_kernel<decltype(R)::value, decltype(V)::value>);
+    if (sm > 64 * 1024 && !csts_dyn_lds_optin(fn, (int)sm)) { rc = -1; return; }
+    hipLaunchKernelGGL((opt_adamw_factored_kernel<decltype(R)::value, decltype(V)::value>), dim3((unsigned)(mk / FK), (unsigned)cdiv(mn, FR), (unsigned)nitems), dim3(256), sm,
+                       stream, l, lr, state, beta1, beta2, eps, rk);
+  });
+  CSTS_REQUIRE(rc == 0, "LDS opt-in failed");
   CSTS_LAUNCH_CHECK();
   return 0;
 }
+extern "C" int csts_adamw_factored(const csts_opt_factored* items, int nitems, const float* state, const float* lr, float beta1,
+                                   float beta2, float eps, hipStream_t stream) {
+  const csts_opt_rule rule{CSTS_OPT_ADAMW, 0.f, 0.f, 0, 0.f, 0, nullptr};
+  return csts_opt_factored_step(items, nitems, &rule, state, lr, beta1, beta2, eps, stream);
+}
 
-extern "C" int csts_adamw_step(const csts_opt_args* a, hipStream_t stream) {
+extern "C" int csts_opt_step(const csts_opt_args* a, const csts_opt_rule* rule, hipStream_t stream) {
+  RuleK rk;
+  if (int rc = rule_check(rule, &rk)) return rc;
   CSTS_REQUIRE(a != nullptr, "null args");
   CSTS_REQUIRE(a->nchunks > 0 && a->ntensors > 0 && a->chunk_elems > 0 && a->chunk_elems % 4 == 0 && a->chunk_elems <= (1 << 28), "bad chunking");
   CSTS_REQUIRE(a->chunk_tensor && a->chunk_off && a->tensors && a->grads, "null table");
@@ -489,6 +611,7 @@ extern "C" int csts_adamw_step(const csts_opt_args* a, hipStream_t stream) {
   CSTS_REQUIRE(a->grad_dt == CSTS_F32 || a->grad_dt == CSTS_HALF, "bad gradient dtype");
   CSTS_REQUIRE(a->n_extra_sq >= 0 && a->n_extra_sq <= 1024 && (a->n_extra_sq == 0 || a->extra_sq != nullptr), "bad extra_sq");
   CSTS_REQUIRE(a->scaler == nullptr || (a->growth > 1.f && a->backoff > 0.f && a->backoff < 1.f && a->growth_interval > 0), "bad loss-scaler parameters");
+  CSTS_REQUIRE(!(rule->clip_value > 0.f && a->max_grad_norm > 0.f), "clip_value and max_grad_norm are exclusive (the reference's if / elif)");
   OptTables t{a->chunk_tensor, a->chunk_off, a->tensors, a->grads};
   const bool g16 = a->grad_dt != CSTS_F32;
   const dim3 grid((unsigned)a->nchunks), block(OPT_THREADS);
@@ -498,8 +621,16 @@ extern "C" int csts_adamw_step(const csts_opt_args* a, hipStream_t stream) {
   hipLaunchKernelGGL(opt_norm_finish_kernel, dim3(1), dim3(1024), 0, stream, a->partial, a->nchunks, a->max_grad_norm, a->state,
                      a->scaler, a->growth, a->backoff, a->growth_interval, a->extra_sq, a->n_extra_sq);
   CSTS_LAUNCH_CHECK();
-  if (g16) hipLaunchKernelGGL(opt_adamw_kernel<true>, grid, block, 0, stream, t, a->chunk_elems, a->lr, a->state, a->beta1, a->beta2, a->eps);
-  else hipLaunchKernelGGL(opt_adamw_kernel<false>, grid, block, 0, stream, t, a->chunk_elems, a->lr, a->state, a->beta1, a->beta2, a->eps);
+  launch_rule(rule->kind, rk.clip_value > 0.f, [&](auto R, auto V) {
+    constexpr int RR = decltype(R)::value;
+    constexpr bool VV = decltype(V)::value;
+    if (g16) hipLaunchKernelGGL((opt_adamw_kernel<true, RR, VV>), grid, block, 0, stream, t, a->chunk_elems, a->lr, a->state, a->beta1, a->beta2, a->eps, rk);
+    else hipLaunchKernelGGL((opt_adamw_kernel<false, RR, VV>), grid, block, 0, stream, t, a->chunk_elems, a->lr, a->state, a->beta1, a->beta2, a->eps, rk);
+  });
   CSTS_LAUNCH_CHECK();
   return 0;
+}
+extern "C" int csts_adamw_step(const csts_opt_args* a, hipStream_t stream) {
+  const csts_opt_rule rule{CSTS_OPT_ADAMW, 0.f, 0.f, 0, 0.f, 0, nullptr};
+  return csts_opt_step(a, &rule, stream);
 }

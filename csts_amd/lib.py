@@ -42,7 +42,7 @@ def half_dtype():
     return torch.float16 if HALF == "fp16" else torch.bfloat16
 
 
-ABI_VERSION = 7   # == CSTS_ABI_VERSION of include/csts_hip.h this binding mirrors (struct layouts below)
+ABI_VERSION = 8   # == CSTS_ABI_VERSION of include/csts_hip.h this binding mirrors (struct layouts below)
 F32, BF16 = 0, 1
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 EPI_NONE, EPI_GELU, EPI_DGELU = 0, 1, 2
@@ -148,7 +148,15 @@ class OptArgs(C.Structure):
 
 class OptFactored(C.Structure):
     _fields_ = [("p", vp), ("m", vp), ("v", vp), ("w16", vp), ("dy", vp), ("a", vp), ("a_dt", C.c_int),
-                ("N", C.c_int), ("K", C.c_int), ("T", C.c_int), ("weight_decay", C.c_float), ("pad_", C.c_int)]
+                ("N", C.c_int), ("K", C.c_int), ("T", C.c_int), ("weight_decay", C.c_float), ("tensor", C.c_int)]
+
+
+OPT_ADAMW, OPT_ADAM, OPT_SGD = 0, 1, 2
+
+
+class OptRule(C.Structure):
+    _fields_ = [("kind", C.c_int), ("momentum", C.c_float), ("dampening", C.c_float), ("nesterov", C.c_int),
+                ("clip_value", C.c_float), ("pad_", C.c_int), ("buf_step", vp)]
 
 
 # name -> (restype, argtypes); every symbol include/csts_hip.h declares
@@ -235,6 +243,8 @@ SYMBOLS = {
     "csts_factored_sqnorm_workspace": (sz, [C.POINTER(OptFactored), _I]),
     "csts_factored_sqnorm": (_I, [C.POINTER(OptFactored), _I, vp, vp, sz, vp]),
     "csts_adamw_factored": (_I, [C.POINTER(OptFactored), _I, vp, vp, _F, _F, _F, vp]),
+    "csts_opt_step": (_I, [C.POINTER(OptArgs), C.POINTER(OptRule), vp]),
+    "csts_opt_factored_step": (_I, [C.POINTER(OptFactored), _I, C.POINTER(OptRule), vp, vp, _F, _F, _F, vp]),
     "csts_frames_normalize": (_I, [vp, vp, _I, i64, _I, C.c_float * 3, C.c_float * 3, vp]),
     "csts_stft_frames": (_I, [_I, _I, _I]),
     "csts_stft_logpower": (_I, [vp, vp, _I, _I, _I, _I, _I, _F, vp]),

@@ -2,7 +2,7 @@
 never ships to the GPU box).  It reproduces the timed iteration -- LR set, forward, frame_softmax + KLDiv +
 LOSS_ALPHA * EgoNCE, backward (+ RCCL gradient all-reduce), L2 clip 1.0, AdamW -- without the reference's
 per-iteration host syncs (isnan / .item() / metric gathers run only when asked).  The optimizer is the device-side
-csts_amd.optim.FusedAdamW (clip + AdamW + bf16 shadow refresh in three launches); the LR schedule is
+csts_amd.optim.FusedAdamW / FusedAdam / FusedSGD (clip + update + bf16 shadow refresh in three launches); the LR schedule is
 slowfast/utils/lr_policy.py's cosine.  Three ways to run the step: eagerly (train_step), as ONE HIP graph
 (GraphedTrainStep, single GPU) or as a chain of HIP graphs with the loss and the RCCL collectives issued eagerly
 between them (SegmentedTrainStep, the data-parallel step)."""
@@ -48,11 +48,18 @@ def set_lr(optimizer, new_lr: float):
 
 
 def construct_optimizer(model, cfg, capturable: bool = False, device_fused: bool = True):
-    """AdamW(eps 1e-8) with zero weight decay on 1-D parameters and biases
-    (slowfast/models/optimizer.py:11-108 for OPTIMIZING_METHOD adamw, ZERO_WD_1D_PARAM).
-    On the GPU this is csts_amd.optim.FusedAdamW: clip_grad_norm_ (train_avgaze_net.py:105-106) + AdamW + bf16 shadow
-    refresh in three launches; device_fused=False gives stock torch.optim.AdamW (the numerics cross-check)."""
-    assert cfg.SOLVER.OPTIMIZING_METHOD == "adamw", "the CSTS YAMLs train with adamw"
+    """The optimizer of SOLVER.OPTIMIZING_METHOD with zero weight decay on 1-D parameters and biases
+    (slowfast/models/optimizer.py:11-108, ZERO_WD_1D_PARAM): sgd (MOMENTUM, DAMPENING, NESTEROV), adam (betas (0.9, 0.999),
+    coupled L2 decay) or adamw (eps 1e-8).  On the GPU this is csts_amd.optim.FusedSGD / FusedAdam / FusedAdamW: the clip of
+    train_avgaze_net.py:103-106 (SOLVER.CLIP_GRAD_VAL, else CLIP_GRAD_L2NORM) + the update + bf16 shadow refresh in three
+    launches; device_fused=False gives the stock torch optimizer of the method (the numerics cross-check)."""
+    s = cfg.SOLVER
+    method = s.OPTIMIZING_METHOD
+    if method not in ("sgd", "adam", "adamw"):
+        raise NotImplementedError("Does not support {} optimizer".format(method))
+    if method == "sgd" and s.NESTEROV and (s.MOMENTUM <= 0 or s.DAMPENING != 0):
+        raise ValueError("Nesterov momentum requires a momentum and zero dampening (SOLVER.NESTEROV with SOLVER.MOMENTUM "
+                         f"{s.MOMENTUM}, SOLVER.DAMPENING {s.DAMPENING})")
     core = model.module if isinstance(model, GradAllReduce) else model
     skip = core.no_weight_decay() if hasattr(core, "no_weight_decay") else {}
     decay, no_decay = [], []
@@ -64,40 +71,50 @@ def construct_optimizer(model, cfg, capturable: bool = False, device_fused: bool
         for p in m.parameters(recurse=False):
             if not p.requires_grad:
                 continue
-            if name in skip or (cfg.SOLVER.ZERO_WD_1D_PARAM and (p.dim() == 1 or name.endswith(".bias"))):
+            if name in skip or (s.ZERO_WD_1D_PARAM and (p.dim() == 1 or name.endswith(".bias"))):
                 no_decay.append(p)
             else:
                 decay.append(p)
-    groups = [g for g in ({"params": decay, "weight_decay": cfg.SOLVER.WEIGHT_DECAY},
+    groups = [g for g in ({"params": decay, "weight_decay": s.WEIGHT_DECAY},
                           {"params": no_decay, "weight_decay": 0.0}) if g["params"]]
     fused = all(p.is_cuda for g in groups for p in g["params"])     # one multi-tensor kernel per group on the GPU
-    if fused and device_fused and not cfg.SOLVER.CLIP_GRAD_VAL:
-        from .optim import FusedAdamW
+    # CLIP_GRAD_VAL takes precedence over CLIP_GRAD_L2NORM (train_avgaze_net.py:103-106: if / elif)
+    clip_value = float(s.CLIP_GRAD_VAL or 0.0)
+    max_norm = 0.0 if clip_value > 0.0 else float(s.CLIP_GRAD_L2NORM or 0.0)
+    if fused and device_fused:
+        from . import optim as O
         shadows = {}
         if hasattr(core, "_refresh_w16"):
             core._refresh_w16()
             shadows = {id(l.weight): l._w16 for l in (getattr(core, "_w16_all", None) or getattr(core, "_w16_lins", []))}
             core.w16_external = True
-        return FusedAdamW(groups, lr=cfg.SOLVER.BASE_LR, eps=1e-8, max_grad_norm=float(cfg.SOLVER.CLIP_GRAD_L2NORM or 0.0),
-                          shadows=shadows, loss_scaling=bool(getattr(getattr(core, "rt", None), "loss_scaling", False)))
+        kw = dict(max_grad_norm=max_norm, clip_value=clip_value, shadows=shadows,
+                  loss_scaling=bool(getattr(getattr(core, "rt", None), "loss_scaling", False)))
+        if method == "sgd":
+            return O.FusedSGD(groups, lr=s.BASE_LR, momentum=s.MOMENTUM, dampening=s.DAMPENING, nesterov=s.NESTEROV, **kw)
+        if method == "adam":
+            return O.FusedAdam(groups, lr=s.BASE_LR, betas=(0.9, 0.999), eps=1e-8, **kw)
+        return O.FusedAdamW(groups, lr=s.BASE_LR, eps=1e-8, **kw)
     if bool(getattr(getattr(core, "rt", None), "loss_scaling", False)):
         # fp16 compute mode: the GradScaler semantics (unscale, non-finite check, skipped step, back-off / growth) live inside
-        # FusedAdamW's kernels.  A stock torch optimizer would train on unscaled fp16 gradients that underflow silently and the
-        # checkpoint would carry no scaler_state: refuse instead.
+        # the fused optimizers' kernels.  A stock torch optimizer would train on unscaled fp16 gradients that underflow silently and
+        # the checkpoint would carry no scaler_state: refuse instead.
         raise RuntimeError("CSTS_AMD.COMPUTE fp16 (TRAIN.MIXED_PRECISION) needs the device-fused optimizer: it carries the dynamic loss "
-                           "scaling.  Unset SOLVER.CLIP_GRAD_VAL (use CLIP_GRAD_L2NORM), keep the model on the GPU and "
-                           "device_fused=True, or train in CSTS_AMD.COMPUTE bf16 / fp32.")
-    kw = {}
+                           "scaling.  Keep the model on the GPU and device_fused=True, or train in CSTS_AMD.COMPUTE bf16 / fp32.")
+    if method == "sgd":
+        return torch.optim.SGD(groups, lr=s.BASE_LR, momentum=s.MOMENTUM, weight_decay=s.WEIGHT_DECAY, dampening=s.DAMPENING,
+                               nesterov=s.NESTEROV)
+    cls = torch.optim.Adam if method == "adam" else torch.optim.AdamW
+    hp = {"betas": (0.9, 0.999)} if method == "adam" else {"eps": 1e-8}
     if fused and capturable:      # lr lives in a device tensor so that a captured step can follow the schedule
-        kw = {"capturable": True}
-        lr0 = torch.tensor(float(cfg.SOLVER.BASE_LR), dtype=torch.float32, device=groups[0]["params"][0].device)
-        return torch.optim.AdamW(groups, lr=lr0, eps=1e-8, weight_decay=cfg.SOLVER.WEIGHT_DECAY, fused=True, **kw)
-    return torch.optim.AdamW(groups, lr=cfg.SOLVER.BASE_LR, eps=1e-8, weight_decay=cfg.SOLVER.WEIGHT_DECAY, fused=fused)
+        lr0 = torch.tensor(float(s.BASE_LR), dtype=torch.float32, device=groups[0]["params"][0].device)
+        return cls(groups, lr=lr0, weight_decay=s.WEIGHT_DECAY, fused=True, capturable=True, **hp)
+    return cls(groups, lr=s.BASE_LR, weight_decay=s.WEIGHT_DECAY, fused=fused, **hp)
 
 
 class LossScaler:
     """The reference's `scaler` object (torch.cuda.amp.GradScaler, tools/train_avgaze_net.py:277) for the fp16 compute mode: the
-    state lives on the device inside FusedAdamW (its kernels unscale, skip and update); this view gives the harness scale() and
+    state lives on the device inside the fused optimizer (its kernels unscale, skip and update); this view gives the harness scale() and
     the checkpoint code state_dict() / load_state_dict() ("scaler_state", slowfast/utils/checkpoint.py:133-134,351-352)."""
 
     def __init__(self, optimizer):
@@ -149,7 +166,7 @@ def _factored_on(cfg, core) -> bool:
 
 def _factored_params(cfg, core, optimizer):
     """The fusion-conv weights whose gradient the optimizer can form on the fly from its rank-(B T') factors
-    (FusedAdamW.set_factored; CSTS_AMD.FACTORED_ADAMW): never written to memory, never read back."""
+    (FusedOptimizer.set_factored; CSTS_AMD.FACTORED_ADAMW, which keeps its name and applies to every method): never written to memory, never read back."""
     if not _factored_on(cfg, core) or not hasattr(optimizer, "set_factored"):
         return []
     ws = [m.weight for m in (getattr(core, n, None) for n in ("vision_pool", "audio_pool", "audio_pool2")) if m is not None]
@@ -168,7 +185,7 @@ def backward_with_factors(cfg, model, loss, optimizer):
         backward_scaled(loss, optimizer)
         return
     # "accept": FusionConvFn.backward asks BEFORE it drops dW -- a geometry the factored update does not take (more than
-    # FusedAdamW.FACTORED_MAX_T token rows: large per-GPU batches) runs the ordinary TN GEMM and lands in p.grad as usual
+    # FusedOptimizer.FACTORED_MAX_T token rows: large per-GPU batches) runs the ordinary TN GEMM and lands in p.grad as usual
     sink = {"params": {p.data_ptr() for p in fac}, "items": [], "accept": lambda W, bt: optimizer.factored_ok(W, bt)}
     ops.set_factor_sink(sink)
     try:
@@ -229,9 +246,9 @@ def train_step(cfg, model, batch: Dict[str, torch.Tensor], optimizer=None, lr: O
 
 
 def _clip_and_step(cfg, model, optimizer):
-    """train_avgaze_net.py:101-109 (clip, then step); FusedAdamW clips inside its own kernels."""
-    from .optim import FusedAdamW
-    if not isinstance(optimizer, FusedAdamW):
+    """train_avgaze_net.py:101-109 (clip, then step); the fused optimizers clip inside their own kernels."""
+    from .optim import FusedOptimizer
+    if not isinstance(optimizer, FusedOptimizer):
         if cfg.SOLVER.CLIP_GRAD_VAL:
             torch.nn.utils.clip_grad_value_(model.parameters(), cfg.SOLVER.CLIP_GRAD_VAL)
         elif cfg.SOLVER.CLIP_GRAD_L2NORM:
@@ -319,18 +336,19 @@ def synthetic_batch(B: int, num_frames: int, crop: int, seed: int, device, pipel
 
 
 class _TrainStateSnapshot:
-    """Parameters, optimizer moments / step count and the device RNG state, taken before the warm-up iterations of a graph
+    """Parameters, optimizer buffers / step count and the device RNG state, taken before the warm-up iterations of a graph
     capture and put back after it: warm-up runs REAL optimizer steps (lazy tables, autotuned plans and the allocator have to
-    see the real thing), and a fresh or resumed run must not start two AdamW steps down the road with the schedule's
+    see the real thing), and a fresh or resumed run must not start two optimizer steps down the road with the schedule's
     learning rate ignored (the capture itself executes nothing)."""
 
     def __init__(self, model, optimizer):
         self.params = [p for p in model.parameters()]
         self.values = [p.detach().clone() for p in self.params]
         self.opt = optimizer
-        if hasattr(optimizer, "exp_avg"):                       # csts_amd.optim.FusedAdamW
-            self.opt_state = (optimizer.exp_avg.clone(), optimizer.exp_avg_sq.clone(), optimizer.state_t.clone(), optimizer._lr.clone())
-            self.scaler = optimizer.scaler_t.clone() if getattr(optimizer, "scaler_t", None) is not None else None
+        from .optim import FusedOptimizer
+        self.fused = isinstance(optimizer, FusedOptimizer)
+        if self.fused:          # buffers, momentum first-step flags, step / norm / clip / skipped, lr, loss scaler
+            self.opt_state = [t.clone() for t in optimizer.device_state()]
         else:
             import copy
             self.opt_state = copy.deepcopy(optimizer.state_dict())
@@ -339,11 +357,9 @@ class _TrainStateSnapshot:
     def restore(self):
         with torch.no_grad():
             torch._foreach_copy_(self.params, self.values)      # bumps the version counters: bf16 shadows refresh on the next run
-        if hasattr(self.opt, "exp_avg"):
-            a, b, c, d = self.opt_state
-            self.opt.exp_avg.copy_(a); self.opt.exp_avg_sq.copy_(b); self.opt.state_t.copy_(c); self.opt._lr.copy_(d)
-            if self.scaler is not None:
-                self.opt.scaler_t.copy_(self.scaler)
+        if self.fused:
+            for t, v in zip(self.opt.device_state(), self.opt_state):
+                t.copy_(v)
         else:
             self.opt.load_state_dict(self.opt_state)
         if self.rng is not None:
@@ -497,7 +513,7 @@ class SegmentedTrainStep:
                         views.append(f16[o:o + p.numel()].view_as(p))
                         o += (p.numel() + 3) // 4 * 4
                     self.flat16.append((f16, views))
-                if hasattr(optimizer, "set_external_grads"):     # FusedAdamW reads the 16-bit buckets directly (fp32 accumulation)
+                if hasattr(optimizer, "set_external_grads"):     # the fused optimizers read the 16-bit buckets directly (fp32 accumulation)
                     optimizer.set_external_grads({id(p): v for (_, views), ps in zip(self.flat16, self.buckets)
                                                   for p, v in zip(ps, views)}, L.BF16)
         self.events = None
@@ -856,7 +872,7 @@ class SegmentedTrainStep:
 
     def _bucket16_back(self):
         """16-bit buckets with an optimizer that reads p.grad (stock torch optimizers; the gloo CPU tests): the averaged 16-bit
-        values go back into the fp32 bucket views.  FusedAdamW reads the 16-bit buckets itself (set_external_grads): p.grad then
+        values go back into the fp32 bucket views.  The fused optimizers read the 16-bit buckets themselves (set_external_grads): p.grad then
         keeps this rank's LOCAL fp32 gradients and averaged_grads() returns what the optimizer consumes."""
         if self.dist and self.bucket16 and not hasattr(self.opt, "set_external_grads"):
             for k in range(len(self.buckets)):

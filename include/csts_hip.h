@@ -32,10 +32,10 @@ enum { CSTS_EPI_NONE = 0, CSTS_EPI_GELU = 1, CSTS_EPI_DGELU = 2 };
 enum { CSTS_MASK_NONE = 0, CSTS_MASK_SPATIAL = 1 };
 
 /* Version of this header's struct layouts and call semantics.  Bumped whenever a struct grows or a field changes meaning
- * (2: csts_gemm_args.res_up; 3: compact k|v rows, 16-bit build, loss scaler in csts_opt_args; 4: csts_opt_args.extra_sq, factored AdamW; 5: grouped stencil weight gradients; 6: csts_copy_token_segments, csts_wgrad_grouped8_limited; 7: csts_wgrad_grouped5, csts_gemm algo 500).  csts_abi_version() returns the value the
+ * (2: csts_gemm_args.res_up; 3: compact k|v rows, 16-bit build, loss scaler in csts_opt_args; 4: csts_opt_args.extra_sq, factored AdamW; 5: grouped stencil weight gradients; 6: csts_copy_token_segments, csts_wgrad_grouped8_limited; 7: csts_wgrad_grouped5, csts_gemm algo 500; 8: csts_opt_rule, csts_opt_step, csts_opt_factored_step, csts_opt_factored.tensor replaces pad_).  csts_abi_version() returns the value the
  * LIBRARY was built with: a caller must compare it with the CSTS_ABI_VERSION it was compiled against and refuse a mismatch
  * (the Python binding does, csts_amd/lib.py::load). */
-#define CSTS_ABI_VERSION 7
+#define CSTS_ABI_VERSION 8
 const char* csts_last_error(void);
 int csts_abi_version(void);
 int csts_half_kind(void);   /* the 16-bit type behind CSTS_BF16 in THIS library: 0 bfloat16 (libcsts_hip.so), 1 IEEE half (libcsts_hip_f16.so) */
@@ -384,6 +384,32 @@ typedef struct {
 } csts_opt_args;
 int csts_adamw_step(const csts_opt_args* args, hipStream_t stream);
 
+/* Update rule of the optimizer step (SOLVER.OPTIMIZING_METHOD, slowfast/models/optimizer.py:82-108) and the value clip
+ * (SOLVER.CLIP_GRAD_VAL, tools/train_avgaze_net.py:103-104).  g below is the unscaled gradient, clipped; wd the tensor's weight decay.
+ *   CSTS_OPT_ADAMW  torch.optim.AdamW: what csts_adamw_step computes (bit-identical with clip_value <= 0).
+ *   CSTS_OPT_ADAM   torch.optim.Adam (amsgrad off): g += wd p, then the moments, bias corrections and step of AdamW, no decoupled decay.
+ *   CSTS_OPT_SGD    torch.optim.SGD: d = g + wd p; with momentum != 0, buf = d on the buffer's first step, else
+ *                   buf = momentum buf + (1 - dampening) d, and d = d + momentum buf (nesterov) or buf; p -= lr d.  m is the momentum
+ *                   buffer, v unused; with momentum == 0 m and v are unused.
+ * m and v may be NULL where the rule does not use them (csts_opt_factored_step refuses NULL where it does; csts_opt_step's table is
+ * device memory: a tensor whose required buffer is NULL is left untouched).  clip_value > 0: every unscaled gradient element is
+ * clamped to [-clip_value, clip_value] before weight decay (clip_grad_value_ after scaler.unscale_); it excludes max_grad_norm > 0.
+ * The norm pass still runs (the loss scaler's non-finite check, state[1] for logging); the clip coefficient is then 1 / scale.
+ * buf_step (SGD with momentum only, else ignored): fp32[ntensors] device memory, per tensor (index of csts_opt_args.tensors, or
+ * csts_opt_factored.tensor) the step count (state[0]) at which its momentum buffer was initialised, 0 = never.  The update writes it;
+ * set it to a value no step count takes (e.g. -1) when a buffer is loaded from a checkpoint.  A step the loss scaler skips leaves it
+ * alone, so a captured graph replays the "first step" correctly.  csts_opt_step: three launches for every rule (like csts_adamw_step);
+ * csts_opt_factored_step: csts_adamw_factored with a rule. */
+enum { CSTS_OPT_ADAMW = 0, CSTS_OPT_ADAM = 1, CSTS_OPT_SGD = 2 };
+typedef struct {
+  int kind;
+  float momentum, dampening; int nesterov;     /* CSTS_OPT_SGD only (0 for the other rules); nesterov needs momentum > 0, dampening 0 */
+  float clip_value;                            /* <= 0: off */
+  int pad_;
+  float* buf_step;
+} csts_opt_rule;
+int csts_opt_step(const csts_opt_args* args, const csts_opt_rule* rule, hipStream_t stream);
+
 /* Factored AdamW: the weight gradient of a fusion conv (custom_multimodal_builder.py:227-229) is dW[N][K] = dY[T][N]^T A[T][K]
  * with T = B * T' token rows (32 at b = 4, 16 frames) for N x K = 768 x 49152 -- a rank-T update.  Instead of writing dW to
  * memory (151 MB, read twice by the clip norm and the update) the optimizer forms g = dY^T A ON THE FLY, in fp32, inside the
@@ -398,12 +424,15 @@ int csts_adamw_step(const csts_opt_args* args, hipStream_t stream);
 typedef struct {
   float* p; float* m; float* v; void* w16;
   const float* dy; const void* a; int a_dt;
-  int N, K, T; float weight_decay; int pad_;
+  int N, K, T; float weight_decay;
+  int tensor;                  /* index into csts_opt_rule.buf_step (SGD with momentum; ignored otherwise) */
 } csts_opt_factored;
 size_t csts_factored_sqnorm_workspace(const csts_opt_factored* items, int nitems);
 int csts_factored_sqnorm(const csts_opt_factored* items, int nitems, float* out_sq, void* workspace, size_t ws_bytes, hipStream_t stream);
 int csts_adamw_factored(const csts_opt_factored* items, int nitems, const float* state, const float* lr, float beta1, float beta2,
                         float eps, hipStream_t stream);
+int csts_opt_factored_step(const csts_opt_factored* items, int nitems, const csts_opt_rule* rule, const float* state, const float* lr,
+                           float beta1, float beta2, float eps, hipStream_t stream);
 
 /* ---- evaluation metric ("next" row): metrics.adaptive_f1 (slowfast/utils/metrics.py:9-74) with the
  *      per-frame min-max rescale of its callers (tools/test_avgaze_net.py:66-68, tools/train_avgaze_net.py:125-127) folded
