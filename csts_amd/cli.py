@@ -80,11 +80,17 @@ def is_eval_epoch(cfg, cur_epoch: int) -> bool:
     return cur_epoch + 1 == cfg.SOLVER.MAX_EPOCH or (cur_epoch + 1) % cfg.TRAIN.EVAL_PERIOD == 0
 
 
+def _meters_on(cfg) -> bool:
+    return bool(getattr(cfg.CSTS_AMD, "GAZE_METERS", False))
+
+
 @torch.no_grad()
 def eval_epoch(cfg, model, cur_epoch: int, dev, rank: int, world: int):
     """tools/train_avgaze_net.py:158-219 on synthetic validation clips: eval-mode forward -> frame_softmax(T = 2) -> gather of
     predictions / heat-map labels / gaze labels over the ranks (:192-193) -> min-max rescale + adaptive_f1 on the device
-    (:196-199) -> the epoch means the reference's ValGazeMeter logs (meters.py: f1 / recall / precision)."""
+    (:196-199) -> the plain means of the per-batch values.  With CSTS_AMD.GAZE_METERS the record follows ValGazeMeter instead
+    (meters.py:401-417,455-475): a device-resident "val" meter gathers the per-frame counts, weighs recall and precision of
+    each batch by its sample count and derives f1 from the totals."""
     from . import train as T
     from . import losses, metrics
     from . import distributed as du
@@ -94,17 +100,26 @@ def eval_epoch(cfg, model, cur_epoch: int, dev, rank: int, world: int):
     b = max(1, cfg.TRAIN.BATCH_SIZE // world)
     n = int(getattr(cfg.CSTS_AMD, "EVAL_STEPS", 2))
     acc = [0.0, 0.0, 0.0]
+    meter = metrics.GazeMeter(cfg.TRAIN.DATASET, cfg.LOG_PERIOD, dev, "val") if _meters_on(cfg) else None
     for it in range(n):
         batch = T.synthetic_batch(b, cfg.DATA.NUM_FRAMES, cfg.DATA.TEST_CROP_SIZE, 500000 + rank + 7919 * it, dev,
                                   spatial=T.spatial_config(cfg, train=False))
         preds = losses.frame_softmax(model([batch["video"]], batch["audio"]), temperature=2)
         labels_hm, labels = batch["labels_hm"], batch["labels"]
+        if meter is not None:
+            meter.update(preds, labels_hm, labels)
+            continue
         if world > 1:
             preds, labels_hm, labels = du.all_gather([preds, labels_hm, labels])
         f1, recall, precision, threshold = metrics.adaptive_f1(preds, labels_hm, labels, dataset=cfg.TRAIN.DATASET, rescale=True)
         acc = [a + v for a, v in zip(acc, (f1, recall, precision))]
-    _log({"_type": "val_epoch", "epoch": cur_epoch + 1, "f1": acc[0] / n, "recall": acc[1] / n, "precision": acc[2] / n,
-          "iters": n})
+    if meter is not None:
+        ep = meter.epoch_stats()
+        _log({"_type": "val_epoch", "epoch": cur_epoch + 1, "f1": ep["f1"], "recall": ep["recall"], "precision": ep["precision"],
+              "iters": n})
+    else:
+        _log({"_type": "val_epoch", "epoch": cur_epoch + 1, "f1": acc[0] / n, "recall": acc[1] / n, "precision": acc[2] / n,
+              "iters": n})
     if was_training:
         model.train()
 
@@ -131,6 +146,13 @@ def train(cfg):
     # the iteration runs from HIP graphs (the step is launch-bound from Python): one graph on a single GPU, a chain of graphs
     # with the RCCL collectives issued eagerly between them when data-parallel (train.SegmentedTrainStep)
     graphed = None
+    # CSTS_AMD.GAZE_METERS: TrainGazeMeter on the device (train_avgaze_net.py:124-131).  One GPU: its two kernels are part of the
+    # captured step.  Data-parallel: fed eagerly from the forward graph's static logits after the chain (softmax, count, count
+    # gather, update; no host sync).  Read on the host at the log points only.
+    meter = None
+    if _meters_on(cfg):
+        from . import losses, metrics
+        meter = metrics.GazeMeter(cfg.TRAIN.DATASET, cfg.LOG_PERIOD, dev, "train")
     # CSTS_AMD.EPOCHS_THIS_RUN > 0 ends this invocation after that many epochs (a pre-empted job, for resume tests); the
     # schedule and the checkpoint / eval periods still follow SOLVER.MAX_EPOCH
     last = cfg.SOLVER.MAX_EPOCH
@@ -144,22 +166,34 @@ def train(cfg):
             lr = T.get_lr_at_epoch(cfg, epoch + float(it) / steps)
             if getattr(cfg.CSTS_AMD, "HIP_GRAPH", True):
                 if graphed is None:
-                    graphed = (T.GraphedTrainStep if world == 1 else T.SegmentedTrainStep)(cfg, model, optimizer, batch)
+                    graphed = T.GraphedTrainStep(cfg, model, optimizer, batch, meter=meter) if world == 1 else \
+                        T.SegmentedTrainStep(cfg, model, optimizer, batch)
                 loss, kld, nce = graphed.run(batch, lr)
+                if meter is not None and world > 1:
+                    with torch.no_grad():
+                        meter.update(losses.frame_softmax(graphed.outs[0], temperature=2), batch["labels_hm"], batch["labels"])
             else:
-                loss, kld, nce = T.train_step(cfg, model, batch, optimizer, lr)
+                loss, kld, nce = T.train_step(cfg, model, batch, optimizer, lr, meter=meter)
             if (it + 1) % cfg.LOG_PERIOD == 0:
                 vals = T.du.all_reduce([loss, kld] + ([nce] if nce is not None else []))
                 lv = float(vals[0])
                 if not (lv == lv) or lv in (float("inf"), float("-inf")):
                     raise RuntimeError("ERROR: Got NaN losses")      # misc.check_nan_losses (misc.py:26-33)
-                _log({"_type": "train_iter", "epoch": epoch + 1, "iter": it + 1, "lr": lr,
-                      "lr_device": float(optimizer.param_groups[0]["lr"]),        # what the (captured) optimizer kernels read
-                      "loss_scale": scaler.get_scale() if scaler is not None else None,
-                      "loss": lv,
-                      "kldiv_loss": float(vals[1]), "nce_loss": float(vals[2]) if nce is not None else None})
+                stats = {"_type": "train_iter", "epoch": epoch + 1, "iter": it + 1, "lr": lr,
+                         "lr_device": float(optimizer.param_groups[0]["lr"]),        # what the (captured) optimizer kernels read
+                         "loss_scale": scaler.get_scale() if scaler is not None else None,
+                         "loss": lv,
+                         "kldiv_loss": float(vals[1]), "nce_loss": float(vals[2]) if nce is not None else None}
+                if meter is not None:
+                    stats.update(meter.window_median())      # f1 / recall / precision medians over LOG_PERIOD batches, last threshold
+                _log(stats)
         torch.cuda.synchronize()
-        _log({"_type": "train_epoch", "epoch": epoch + 1, "clips_per_s": steps * b * world / (time.time() - t0)})
+        stats = {"_type": "train_epoch", "epoch": epoch + 1, "clips_per_s": steps * b * world / (time.time() - t0)}
+        if meter is not None:
+            ep = meter.epoch_stats()                         # TrainGazeMeter.log_epoch_stats, then reset (train_avgaze_net.py:154-155)
+            stats.update(f1=ep["f1"], recall=ep["recall"], precision=ep["precision"])
+            meter.reset()
+        _log(stats)
         if getattr(cfg.CSTS_AMD, "SAVE_CHECKPOINTS", False) and is_checkpoint_epoch(cfg, epoch):
             path = ck.save_checkpoint(cfg.OUTPUT_DIR, model, optimizer, epoch, cfg, scaler=scaler)  # train_avgaze_net.py:337-346 (0.75 GB + moments)
             _log({"_type": "checkpoint", "epoch": epoch + 1, "path": path,
@@ -187,6 +221,21 @@ def test(cfg):
                                                            dataset=cfg.TEST.DATASET, rescale=True)
     _log({"_type": "test", "preds_shape": list(preds.shape), "preds_sum": float(preds.sum()), "f1": f1, "recall": recall,
           "precision": precision, "threshold": float(threshold)})
+    if _meters_on(cfg):
+        # TestGazeMeter (test_avgaze_net.py:87-92): CSTS_AMD.TEST_STEPS batches (the first is the one above), then ONE adaptive F1
+        # over every frame seen with one common threshold -- from the meter's per-threshold sums, no prediction is kept
+        rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
+        steps = max(1, int(getattr(cfg.CSTS_AMD, "TEST_STEPS", 1)))
+        meter = metrics.GazeMeter(cfg.TEST.DATASET, cfg.LOG_PERIOD, dev, "test")
+        for it in range(steps):
+            if it:
+                batch = T.synthetic_batch(b, cfg.DATA.NUM_FRAMES, cfg.DATA.TEST_CROP_SIZE, 2000 + rank + 7919 * it, dev,
+                                          spatial=T.spatial_config(cfg, train=False))
+                preds = losses.frame_softmax(model([batch["video"]], batch["audio"]), temperature=2)
+            meter.update(preds, batch["labels_hm"], batch["labels"])
+        ds = meter.dataset_stats()
+        _log({"_type": "test_final", "recall": ds["recall"], "precision": ds["precision"], "f1": ds["f1"],
+              "threshold": ds["threshold"], "iters": steps})
 
 
 def main(argv=None):

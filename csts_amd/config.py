@@ -113,6 +113,8 @@ def get_cfg() -> CfgNode:
                        STEPS_PER_EPOCH=50,
                        EPOCHS_THIS_RUN=0,            # > 0: stop this invocation after that many epochs (pre-emption; the next one auto-resumes)
                        EVAL_STEPS=2,                 # synthetic validation iterations of the periodic eval pass (TRAIN.EVAL_PERIOD)
+                       GAZE_METERS=False,            # True: device-resident TrainGazeMeter / ValGazeMeter / TestGazeMeter (metrics.GazeMeter): f1 / recall / precision / threshold in train_iter (window medians over LOG_PERIOD) and train_epoch, the sample-weighted val_epoch, and a test_final record; the training step gains two kernels
+                       TEST_STEPS=1,                 # synthetic test iterations the test meter sees before test_final (GAZE_METERS only)
                        GRAD_BUCKET_MB=64,
                        FACTORED_ADAMW=True,          # 16-bit compute modes, every OPTIMIZING_METHOD (the name predates sgd / adam): the fused optimizer forms the fusion convs' weight gradient dY^T A on the matrix cores inside their update, from the rank-(B T') factors (never written / re-read: 453 MB per step; -0.3 ms at b = 4)
                        FUSION_GRAD_FACTORS=True,     # data-parallel chain: the ranks all-gather the rank-(B*T') factors of the three fusion-conv weight gradients (3.2 MB each) instead of all-reducing 151 MB each

@@ -256,6 +256,11 @@ SYMBOLS = {
     "csts_spatial_uniforms_host": (_I, [_U32, _U32, C.c_uint64, i64, vp]),
     "csts_adaptive_f1_workspace": (sz, [i64, _I]),
     "csts_adaptive_f1": (_I, [vp, vp, vp, vp, _I, i64, _I, _I, vp, vp, sz, vp]),
+    "csts_f1_counts": (_I, [vp, vp, vp, _I, i64, _I, _I, vp, vp]),
+    "csts_gaze_meter_state_bytes": (sz, [_I, _I]),
+    "csts_gaze_meter_reset": (_I, [vp, _I, _I, vp]),
+    "csts_gaze_meter_update": (_I, [vp, vp, i64, i64, _I, _I, _I, i64, _I, vp, vp]),
+    "csts_gaze_meter_update_host": (_I, [vp, vp, i64, i64, _I, _I, _I, i64, _I, vp]),
 }
 
 

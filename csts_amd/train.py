@@ -216,9 +216,10 @@ def compute_loss(cfg, model, video, audio, labels_hm, keep_masks=None):
     return kld, kld, None, preds
 
 
-def train_step(cfg, model, batch: Dict[str, torch.Tensor], optimizer=None, lr: Optional[float] = None, keep_masks=None):
+def train_step(cfg, model, batch: Dict[str, torch.Tensor], optimizer=None, lr: Optional[float] = None, keep_masks=None, meter=None):
     """One iteration: forward + loss + backward (+ gradient all-reduce) [+ clip + AdamW when an optimizer is given].
-    Returns (loss, kld, nce) as device tensors (no host sync)."""
+    ``meter`` (metrics.GazeMeter): fed the step's softmaxed predictions and batch["labels"] after the loss
+    (train_avgaze_net.py:124-131), on the device.  Returns (loss, kld, nce) as device tensors (no host sync)."""
     if optimizer is not None and lr is not None:
         set_lr(optimizer, lr)
     if optimizer is not None and getattr(optimizer, "_ext_grads", None) is not None:
@@ -229,7 +230,9 @@ def train_step(cfg, model, batch: Dict[str, torch.Tensor], optimizer=None, lr: O
     else:
         for p in model.parameters():
             p.grad = None
-    loss, kld, nce, _ = compute_loss(cfg, model, batch["video"], batch["audio"], batch["labels_hm"], keep_masks)
+    loss, kld, nce, preds = compute_loss(cfg, model, batch["video"], batch["audio"], batch["labels_hm"], keep_masks)
+    if meter is not None:
+        meter.update(preds, batch["labels_hm"], batch["labels"])
     if optimizer is not None:
         backward_with_factors(cfg, model, loss, optimizer)
     else:
@@ -372,18 +375,22 @@ class GraphedTrainStep:
     replayed: ~2000 kernel launches per step become one graph launch, so the step is bounded by the kernels, not by
     Python/ctypes dispatch.  Single-process only (the RCCL bucket all-reduce path stays eager).  Inputs are copied
     into static buffers; the learning rate lives in a device tensor (set_lr) so the schedule still applies.
-    Drop-path masks are drawn by torch's graph-safe Philox generator on every replay."""
+    Drop-path masks are drawn by torch's graph-safe Philox generator on every replay.
+    ``meter`` (metrics.GazeMeter): ``labels`` joins the static inputs and the meter's two kernels run on the step's predictions
+    inside the graph, after the loss; its iteration counter lives on the device, so every replay fills the next ring slot.
+    Without a meter the captured graph is unchanged."""
 
-    def __init__(self, cfg, model, optimizer, example_batch, warmup: int = 2, allow_collectives: bool = False):
+    def __init__(self, cfg, model, optimizer, example_batch, warmup: int = 2, allow_collectives: bool = False, meter=None):
         # RCCL collectives can be captured too (torch's ProcessGroupNCCL supports it), but that path has only been run
         # with ONE rank here (bench.py --rehearse-dist --ddp-graph): multi-GPU runs stay eager unless asked otherwise.
         assert allow_collectives or not isinstance(model, GradAllReduce), "graph capture is single-GPU; multi-GPU runs eagerly"
         if isinstance(model, GradAllReduce):
             warmup = max(warmup, 3)          # bucket order and per-bucket streams are learnt in the first iterations
-        self.cfg, self.model, self.opt = cfg, model, optimizer
-        self.static = {k: example_batch[k].clone() for k in ("video", "audio", "labels_hm")}
+        self.cfg, self.model, self.opt, self.meter = cfg, model, optimizer, meter
+        self.static = {k: example_batch[k].clone() for k in ("video", "audio", "labels_hm") + (("labels",) if meter is not None else ())}
         if getattr(optimizer, "_ext_grads", None) is not None:
             optimizer.set_external_grads(None)       # bucket views of an earlier SegmentedTrainStep on this optimizer
+        meter_state = meter.state.clone() if meter is not None else None      # the warm-up iterations must not count
         from . import ops
         mode = ops.GROUP_WGRADS
         if mode == "capture":
@@ -410,11 +417,16 @@ class GraphedTrainStep:
         finally:
             ops.GROUP_WGRADS = mode
             snap.restore()
+            if meter is not None:
+                meter.state.copy_(meter_state)
 
     def _step(self):
         self.opt.zero_grad(set_to_none=True)
-        loss, kld, nce, _ = compute_loss(self.cfg, self.model, self.static["video"], self.static["audio"],
-                                         self.static["labels_hm"])
+        loss, kld, nce, preds = compute_loss(self.cfg, self.model, self.static["video"], self.static["audio"],
+                                             self.static["labels_hm"])
+        if self.meter is not None:
+            self.meter.update(preds, self.static["labels_hm"], self.static["labels"])
+            self.preds = preds.detach()          # static output of the graph: the heat maps the meter saw in the last replay
         backward_with_factors(self.cfg, self.model, loss, self.opt)
         if isinstance(self.model, GradAllReduce):
             self.model.finish()

@@ -442,6 +442,37 @@ size_t csts_adaptive_f1_workspace(int64_t nframes, int nthr);
 int csts_adaptive_f1(const float* preds, const float* labels_hm, const uint8_t* tracked, const float* thresholds, int nthr,
                      int64_t nframes, int hw, int rescale, float* out, void* workspace, size_t ws_bytes, hipStream_t stream);
 
+/* ---- gaze meters: TrainGazeMeter / ValGazeMeter / TestGazeMeter (slowfast/utils/meters.py:19-146,200-475) as running
+ *      statistics in ONE caller-owned device buffer, so the metric can live inside a captured training step.
+ *      f1_counts: the count launch of csts_adaptive_f1 alone.  counts[f] = {tp[nthr], fg_preds[nthr], fg_labels} (int32) of frame
+ *        f; these integers are all the metric needs of a frame, so ranks exchange them instead of the predictions.
+ *      gaze_meter_update: one workgroup.  frame_types[f * type_stride] (fp64, 8-byte aligned) is the gaze type of frame f: pass
+ *        &labels[0][2] and the row length of the (nframes, L) label matrix.  The kernel
+ *        1. forms recall / precision / f1 per threshold over the frames with type == fixation_type and picks the first
+ *           maximum, with the fp32 arithmetic of csts_adaptive_f1 (no such frame: NaN, as torch.mean of an empty selection);
+ *        2. adds to the data-set sums, per threshold, sum tp / (fg_labels + 1e-6) and sum tp / (fg_preds + 1e-6) in fp64 and
+ *           the number of tracked frames in int64: sufficient statistics of TestGazeMeter.finalize_metrics (meters.py:132-146),
+ *           which keeps every prediction and calls adaptive_f1 once;
+ *        3. adds recall w, precision w, w to the epoch totals (fp64); w = mb_size if mb_size >= 0 (TrainGazeMeter, meters.py:
+ *           272-280: batch size x ranks), otherwise the number of frames with type == weight_type.  ValGazeMeter and
+ *           TestGazeMeter count labels[:, 2] == 1 (meters.py:87-88,409-410) although adaptive_f1 tracks type 0 on every data set
+ *           but egteagaze; the reference is followed literally, so their callers pass weight_type 1;
+ *        4. writes {f1, recall, precision, threshold index} of this batch into slot (iterations % window) of a ring and
+ *           increments the iteration counter, which lives in the buffer: a replayed graph needs no changed argument.
+ *        No allocation, no synchronisation, no host read.
+ *      state (8-byte aligned, gaze_meter_state_bytes(nthr, window) bytes, zero = empty; gaze_meter_reset zeroes it):
+ *        int64 iterations, tracked frames | fp64 sum recall w, sum precision w, sum w | fp64 recall sums[nthr], precision
+ *        sums[nthr] | fp32 ring[window][4].
+ *      gaze_meter_update_host: the same rule (the same function) on HOST memory. */
+int csts_f1_counts(const float* preds, const float* labels_hm, const float* thresholds, int nthr, int64_t nframes, int hw, int rescale,
+                   int* counts, hipStream_t stream);
+size_t csts_gaze_meter_state_bytes(int nthr, int window);
+int csts_gaze_meter_reset(void* state, int nthr, int window, hipStream_t stream);
+int csts_gaze_meter_update(const int* counts, const double* frame_types, int64_t type_stride, int64_t nframes, int nthr,
+                           int fixation_type, int weight_type, int64_t mb_size, int window, void* state, hipStream_t stream);
+int csts_gaze_meter_update_host(const int* counts, const double* frame_types, int64_t type_stride, int64_t nframes, int nthr,
+                                int fixation_type, int weight_type, int64_t mb_size, int window, void* state);
+
 /* ---- input pipeline on the device ("next" row): what the reference does on the CPU just before the
  *      model is called.  frames_normalize: uint8 (B, T*H*W, C) -> fp32 (B, C, T*H*W), (x/255 - mean)/std
  *      (slowfast/datasets/utils.py:290-307, ego4d_avgaze_forecast.py:294-296).  stft_logpower: fp32 waveform (B, n) ->
