@@ -1258,10 +1258,9 @@ void launch3_mt(const Params& p, int stages, dim3 grid, hipStream_t s) {
   else hipLaunchKernelGGL((gemm3_kernel<MT, 3>), grid, dim3(256), 0, s, p);
 }
 // persistent launch: min(tiles, 256 CUs x workgroups that fit a CU's 160 KiB of LDS) workgroups, a multiple of 8
-void launch3(Params p, const csts_gemm_args* a, int mt, int stages, int wpc, hipStream_t s) {
-  const int64_t ntiles = cdiv(a->M, 64 * mt) * p.ntiles_n;
+void launch3(Params p, int mt, int stages, int wpc, hipStream_t s) {
+  const int64_t ntiles = cdiv(p.M, 64 * mt) * p.ntiles_n;
   p.ntiles = ntiles;
-  p.stamps = (a->split_k <= 1 && a->workspace != nullptr && a->ws_bytes >= 8192) ? reinterpret_cast<unsigned long long*>(a->workspace) : nullptr;
   const int stage_bytes = (64 * mt + 128) * 128;
   const int fit = std::max(1, (160 * 1024) / (stages * stage_bytes));
   if (wpc <= 0 || wpc > fit) wpc = fit;
@@ -1332,6 +1331,110 @@ static void tiny_launch(const Params& p, hipStream_t s) {
   else hipLaunchKernelGGL((gemm_tiny_kernel<LAYOUT, true>), dim3((unsigned)cdiv(outs, 4)), dim3(256), 0, s, p);
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------- the route
+// Which kernel runs a problem, decided ONCE: csts_gemm launches what route() answers; csts_gemm_plan and csts_gemm_kernel_name
+// report it.  A new kernel family gets its tests here, in the order they are tried, and a case in csts_gemm and in
+// csts_gemm_kernel_name.
+enum Family { TINY, GENERIC, V2, RING3, G4, G5 };
+struct Route {
+  Family family;
+  int split;               // k-splits asked for (>= 1)
+  bool det;                // deterministic split-k: partial slabs in the workspace + finishing pass
+  int tile_rows, stages;   // GENERIC / V2: row tile; RING3: 64 * mt, ring stages
+  int variant, wpc;        // G4: variant code (gemm4.hip); RING3 / G4: workgroups per CU (0 = as many as fit)
+  int64_t k_chunk;         // K range of one split
+  int nsplit;              // k-splits that result
+};
+
+// 0, or -1 with csts_last_error set: a forced algo that cannot run the problem, a malformed res_up
+int route(const csts_gemm_args* a, Route* r) {
+  *r = Route{};
+  r->split = r->nsplit = 1;
+  if (tiny_ok(a)) {          // (no split-k there)
+    r->family = TINY;
+    return 0;
+  }
+  const int split = r->split = a->split_k > 1 ? a->split_k : 1;
+  r->det = split > 1 && a->workspace != nullptr;
+  const bool use_v2 = v2_ok(a);
+  const int bk = use_v2 ? BK2 : BK;
+  r->k_chunk = cdiv(cdiv(a->K, bk), split) * bk;
+  r->nsplit = (int)cdiv(a->K, r->k_chunk);
+  const int forced = a->algo % 1000;
+  if (a->res_up[3] > 0) {
+    const int Ti = a->res_up[0], Hi = a->res_up[1], Wi = a->res_up[2], To = a->res_up[3], Ho = a->res_up[4], Wo = a->res_up[5];
+    auto p2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
+    CSTS_REQUIRE(a->residual != nullptr && a->res_row_mod == 0 && split == 1, "res_up needs a residual, no res_row_mod, split_k == 1");
+    CSTS_REQUIRE(Ti > 0 && Hi > 0 && Wi > 0 && p2(To) && p2(Ho) && p2(Wo), "res_up: fine grid sizes must be powers of two");
+    CSTS_REQUIRE(To >= Ti && Ho >= Hi && Wo >= Wi && a->M % ((int64_t)To * Ho * Wo) == 0, "res_up: M must be B * To * Ho * Wo");
+    CSTS_REQUIRE(forced < 300, "res_up is not available in the persistent LDS-DMA kernels");
+  }
+  if (forced >= 300 && forced < 400) {   // forced: 1000 * workgroups-per-CU (0 = as many as LDS allows) + 300 + 10 * (tile_rows / 64) + stages
+    CSTS_REQUIRE(v3_ok(a, split), "algo 3xx (persistent LDS-DMA NT kernel) not applicable to this problem");
+    const int code = forced - 300, mt = code / 10, st = code % 10;
+    CSTS_REQUIRE((mt == 1 || mt == 2 || mt == 4) && st >= 2 && st <= 4 && !(mt == 4 && st == 4), "bad algo 3xx code");
+    r->family = RING3; r->tile_rows = 64 * mt; r->stages = st; r->wpc = a->algo / 1000;
+    return 0;
+  }
+  if (forced >= 400 && forced < 500) {   // forced: 1000 * workgroups-per-CU + 400 + gemm4 variant code (gemm4.hip)
+    CSTS_REQUIRE(v3_ok(a, split), "algo 4xx (8-wave LDS-DMA NT kernel) not applicable to this problem");
+    CSTS_REQUIRE(a->K % 64 == 0, "algo 4xx needs K % 64 == 0 (no k-tail instantiations)");
+    r->family = G4; r->variant = forced - 400; r->wpc = a->algo / 1000;
+    return 0;
+  }
+  if (forced == 500 || forced == 503 || forced == 506) {   // forced: the streaming thin-operand kernel (gemm5.hip; 503 / 506: 96 / 192 columns per workgroup at K = 192)
+    CSTS_REQUIRE(csts_gemm5_ok(a, split), "algo 500 (streaming thin-operand NT kernel) not applicable to this problem");
+    r->family = G5;
+    return 0;
+  }
+  int mt3;
+  if (pick5(a, split)) r->family = G5;
+  else if (pick4(a, split, &r->variant)) r->family = G4;
+  else if (pick3(a, split, &mt3, &r->stages)) { r->family = RING3; r->tile_rows = 64 * mt3; }
+  else if (use_v2) { r->family = V2; r->tile_rows = pick_tile_rows(a, cdiv(a->N, BN) * r->nsplit); }
+  else { r->family = GENERIC; r->tile_rows = BM; }
+  return 0;
+}
+
+// The kernel parameters of a routed call: everything but the per-family tile counts, which the launchers fill in.  The one place
+// they come from -- csts_gemm launches with them, csts_gemm_kernel_name reads the epilogue form off them.
+Params fill_params(const csts_gemm_args* a, const Route& r) {
+  Params p{};
+  p.A = a->A; p.B = a->B; p.C = a->C; p.bias = a->bias; p.aux = a->aux; p.residual = a->residual;
+  p.row_scale = a->row_scale;
+  p.ws = r.det ? reinterpret_cast<float*>(a->workspace) : nullptr;
+  p.colsum = a->colsum;
+  p.colsum_ws = (a->colsum != nullptr && r.det) ? p.ws + (int64_t)r.nsplit * a->M * a->N : nullptr;
+  p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc; p.ldaux = a->ldaux; p.ldr = a->ldr;
+  p.M = a->M; p.N = a->N; p.K = a->K; p.res_row_mod = a->res_row_mod;
+  p.rows_per_scale = a->rows_per_scale > 0 ? a->rows_per_scale : 1;
+  p.a_dt = a->a_dt; p.b_dt = a->b_dt; p.c_dt = a->c_dt; p.aux_dt = a->aux_dt; p.r_dt = a->r_dt;
+  p.epilogue = a->epilogue; p.split_k = r.split; p.k_chunk = r.k_chunk;
+  static const int res_lines = [] { const char* e = getenv("CSTS_GEMM_RES_LINES"); return (e && e[0] == '0') ? 0 : 1; }();
+  p.res_lines = res_lines;
+  // gemm4's store-aware k-tile waits, OFF by default: measured neutral on the 2-stage ring (21.63 vs 21.63 ms per step,
+  // profiles/r4_gemm4_store_aware_ab.txt) and mixed with the 4-stage short-K ring (CSTS_GEMM4_SHORTK=64: -16 .. -18 % on two shapes,
+  // +6 .. +10 % on the DGELU forms, the largest fc1 + GELU unchanged at 2.96 TB/s) -- the drain of the previous tile's stores is NOT what
+  // holds these GEMMs at 3 TB/s
+  static const int store_aware = [] { const char* e = getenv("CSTS_GEMM4_STORE_AWARE"); return (e && e[0] == '1') ? 1 : 0; }();
+  p.store_aware = store_aware;
+  // diagnostics builds of the ring kernels (-DCSTS_GEMM3_STAMPS / -DCSTS_GEMM4_STAMPS) write their cycle stamps into the workspace
+  p.stamps = (r.split == 1 && a->workspace != nullptr && a->ws_bytes >= 8192) ? reinterpret_cast<unsigned long long*>(a->workspace) : nullptr;
+  if (a->res_up[3] > 0) {
+    auto lg = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
+    p.ru_Ti = a->res_up[0]; p.ru_Hi = a->res_up[1]; p.ru_Wi = a->res_up[2]; p.ru_To = a->res_up[3]; p.ru_Ho = a->res_up[4]; p.ru_Wo = a->res_up[5];
+    p.ru_lw = lg(p.ru_Wo); p.ru_lh = lg(p.ru_Ho); p.ru_lt = lg(p.ru_To);
+  }
+  auto vec_ok = [](const void* ptr, int dt, int64_t ld) {
+    return aligned16(ptr) && (ld % (dt == CSTS_F32 ? 4 : 8) == 0);
+  };
+  p.a_vec = vec_ok(a->A, a->a_dt, a->lda);
+  p.b_vec = vec_ok(a->B, a->b_dt, a->ldb);
+  p.ntiles_n = (int)cdiv(a->N, BN);
+  return p;
+}
+
 }  // namespace
 
 extern "C" int csts_gemm(const csts_gemm_args* a, hipStream_t stream) {
@@ -1340,139 +1443,57 @@ extern "C" int csts_gemm(const csts_gemm_args* a, hipStream_t stream) {
   CSTS_REQUIRE(a->layout >= CSTS_GEMM_NT && a->layout <= CSTS_GEMM_TN, "bad layout");
   CSTS_REQUIRE(a->A && a->B && a->C, "null operand");
   CSTS_REQUIRE(a->compute == CSTS_F32 || a->compute == CSTS_BF16, "bad compute dtype");
-  const int split = a->split_k > 1 ? a->split_k : 1;
-  const bool det = split > 1 && a->workspace != nullptr;   // deterministic: partial slabs + finishing pass
+  if (a->epilogue == CSTS_EPI_DGELU) CSTS_REQUIRE(a->aux != nullptr, "DGELU needs aux (pre-activation)");
+  Route r;
+  if (route(a, &r) != 0) return -1;
+  const int split = r.split;
+  const bool det = r.det;
   if (split > 1 && !det) {
     CSTS_REQUIRE(a->c_dt == CSTS_F32, "split-k accumulates with fp32 atomics: C must be f32 (pre-zeroed)");
     CSTS_REQUIRE(a->epilogue == CSTS_EPI_NONE && !a->residual && !a->row_scale, "atomic split-k allows bias only");
   }
-  if (a->epilogue == CSTS_EPI_DGELU) CSTS_REQUIRE(a->aux != nullptr, "DGELU needs aux (pre-activation)");
-  if (tiny_ok(a)) {
-    Params q{};
-    q.A = a->A; q.B = a->B; q.C = a->C; q.bias = a->bias;
-    q.lda = a->lda; q.ldb = a->ldb; q.ldc = a->ldc; q.M = a->M; q.N = a->N; q.K = a->K;
-    if (a->layout == CSTS_GEMM_NT) tiny_launch<CSTS_GEMM_NT>(q, stream);
-    else if (a->layout == CSTS_GEMM_NN) tiny_launch<CSTS_GEMM_NN>(q, stream);
-    else tiny_launch<CSTS_GEMM_TN>(q, stream);
-    CSTS_LAUNCH_CHECK();
-    return 0;
-  }
-  Params p;
-  p.A = a->A; p.B = a->B; p.C = a->C; p.bias = a->bias; p.aux = a->aux; p.residual = a->residual;
-  p.row_scale = a->row_scale;
-  p.ws = det ? reinterpret_cast<float*>(a->workspace) : nullptr;
-  p.colsum = a->colsum;
-  p.colsum_ws = nullptr;
-  p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc; p.ldaux = a->ldaux; p.ldr = a->ldr;
-  p.M = a->M; p.N = a->N; p.K = a->K; p.res_row_mod = a->res_row_mod;
-  p.rows_per_scale = a->rows_per_scale > 0 ? a->rows_per_scale : 1;
-  p.a_dt = a->a_dt; p.b_dt = a->b_dt; p.c_dt = a->c_dt; p.aux_dt = a->aux_dt; p.r_dt = a->r_dt;
-  p.epilogue = a->epilogue; p.split_k = split;
-  static const int res_lines = [] { const char* e = getenv("CSTS_GEMM_RES_LINES"); return (e && e[0] == '0') ? 0 : 1; }();
-  p.res_lines = res_lines;
-  p.ru_Ti = p.ru_Hi = p.ru_Wi = p.ru_To = p.ru_Ho = p.ru_Wo = p.ru_lw = p.ru_lh = p.ru_lt = 0;
-  if (a->res_up[3] > 0) {
-    const int Ti = a->res_up[0], Hi = a->res_up[1], Wi = a->res_up[2], To = a->res_up[3], Ho = a->res_up[4], Wo = a->res_up[5];
-    auto p2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
-    auto lg = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-    CSTS_REQUIRE(a->residual != nullptr && a->res_row_mod == 0 && split == 1, "res_up needs a residual, no res_row_mod, split_k == 1");
-    CSTS_REQUIRE(Ti > 0 && Hi > 0 && Wi > 0 && p2(To) && p2(Ho) && p2(Wo), "res_up: fine grid sizes must be powers of two");
-    CSTS_REQUIRE(To >= Ti && Ho >= Hi && Wo >= Wi && a->M % ((int64_t)To * Ho * Wo) == 0, "res_up: M must be B * To * Ho * Wo");
-    CSTS_REQUIRE(a->algo % 1000 < 300, "res_up is not available in the persistent LDS-DMA kernels");
-    p.ru_Ti = Ti; p.ru_Hi = Hi; p.ru_Wi = Wi; p.ru_To = To; p.ru_Ho = Ho; p.ru_Wo = Wo;
-    p.ru_lw = lg(Wo); p.ru_lh = lg(Ho); p.ru_lt = lg(To);
-  }
-  auto vec_ok = [](const void* ptr, int dt, int64_t ld) {
-    return aligned16(ptr) && (ld % (dt == CSTS_F32 ? 4 : 8) == 0);
-  };
-  p.a_vec = vec_ok(a->A, a->a_dt, a->lda);
-  p.b_vec = vec_ok(a->B, a->b_dt, a->ldb);
-  const bool use_v2 = v2_ok(a);
-  const int bk = use_v2 ? BK2 : BK;
-  const int64_t ktiles = cdiv(a->K, bk);
-  p.k_chunk = cdiv(ktiles, split) * bk;
-  const int64_t nsplit = cdiv(a->K, p.k_chunk);
+  const int64_t nsplit = r.nsplit;
   if (det) CSTS_REQUIRE(a->ws_bytes >= (size_t)nsplit * a->M * a->N * sizeof(float), "split-k workspace too small");
-  if (a->colsum != nullptr) {
+  if (a->colsum != nullptr && r.family != TINY) {
+    const bool use_v2 = r.family == V2;
     CSTS_REQUIRE(use_v2 && a->layout == CSTS_GEMM_TN, "fused colsum needs the TN bf16 v2 kernel (see csts_gemm_v2_eligible)");
     CSTS_REQUIRE(split == 1 || det, "fused colsum with split-k needs the deterministic workspace");
-    if (split > 1) {
-      CSTS_REQUIRE(a->ws_bytes >= (size_t)nsplit * a->M * (a->N + 1) * sizeof(float), "workspace too small for colsum partials");
-      p.colsum_ws = p.ws + nsplit * a->M * a->N;
+    if (split > 1) CSTS_REQUIRE(a->ws_bytes >= (size_t)nsplit * a->M * (a->N + 1) * sizeof(float), "workspace too small for colsum partials");
+  }
+  const Params p = fill_params(a, r);
+  CSTS_REQUIRE(cdiv(a->M, BM) * p.ntiles_n < (int64_t)1 << 31, "grid too large");
+  const dim3 grid((unsigned)(cdiv(a->M, r.tile_rows > 0 ? r.tile_rows : BM) * p.ntiles_n), (unsigned)nsplit, 1);   // GENERIC / V2
+  switch (r.family) {
+    case TINY:
+      if (a->layout == CSTS_GEMM_NT) tiny_launch<CSTS_GEMM_NT>(p, stream);
+      else if (a->layout == CSTS_GEMM_NN) tiny_launch<CSTS_GEMM_NN>(p, stream);
+      else tiny_launch<CSTS_GEMM_TN>(p, stream);
+      break;
+    case G5: CSTS_REQUIRE(csts_gemm5_launch(p, a, stream), "gemm5 launch failed"); break;
+    case G4: CSTS_REQUIRE(csts_gemm4_launch(p, r.variant, r.wpc, stream), "gemm4 variant is not instantiated"); break;
+    case RING3: launch3(p, r.tile_rows / 64, r.stages, r.wpc, stream); break;
+    case V2: {
+      const int mt = r.tile_rows;
+      const bool af = a->a_dt == CSTS_F32, bf = a->b_dt == CSTS_F32;
+      if (a->layout == CSTS_GEMM_NT) {
+        if (bf) launch2<true, true, false, true>(p, mt, grid, stream);
+        else launch2<true, true, false, false>(p, mt, grid, stream);            // bf16 shadow weights
+      } else if (a->layout == CSTS_GEMM_NN) {
+        if (af && bf) launch2<true, false, true, true>(p, mt, grid, stream);
+        else if (!af && bf) launch2<true, false, false, true>(p, mt, grid, stream);
+        else if (af) launch2<true, false, true, false>(p, mt, grid, stream);
+        else launch2<true, false, false, false>(p, mt, grid, stream);
+      } else {
+        if (af) launch2<false, false, true, false>(p, mt, grid, stream);
+        else launch2<false, false, false, false>(p, mt, grid, stream);
+      }
+      break;
     }
-  }
-  p.ntiles_n = (int)cdiv(a->N, BN);
-  int64_t mtiles = cdiv(a->M, BM);
-  CSTS_REQUIRE(mtiles * p.ntiles_n < (int64_t)1 << 31, "grid too large");
-  if (a->algo % 1000 >= 300 && a->algo % 1000 < 400) {   // forced: 1000 * workgroups-per-CU (0 = as many as LDS allows) + 300 + 10 * (tile_rows / 64) + stages
-    CSTS_REQUIRE(v3_ok(a, split), "algo 3xx (persistent LDS-DMA NT kernel) not applicable to this problem");
-    const int code = a->algo % 1000 - 300, mt = code / 10, st = code % 10;
-    CSTS_REQUIRE((mt == 1 || mt == 2 || mt == 4) && st >= 2 && st <= 4 && !(mt == 4 && st == 4), "bad algo 3xx code");
-    launch3(p, a, mt, st, a->algo / 1000, stream);
-    CSTS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (a->algo % 1000 >= 400 && a->algo % 1000 < 500) {   // forced: 1000 * workgroups-per-CU + 400 + gemm4 variant code (gemm4.hip)
-    CSTS_REQUIRE(v3_ok(a, split), "algo 4xx (8-wave LDS-DMA NT kernel) not applicable to this problem");
-    CSTS_REQUIRE(a->K % 64 == 0, "algo 4xx needs K % 64 == 0 (no k-tail instantiations)");
-    CSTS_REQUIRE(csts_gemm4_launch(p, a, a->algo % 1000 - 400, a->algo / 1000, stream), "unknown gemm4 variant");
-    CSTS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (a->algo % 1000 == 500 || a->algo % 1000 == 503 || a->algo % 1000 == 506) {   // forced: the streaming thin-operand kernel (gemm5.hip; 503 / 506: 96 / 192 columns per workgroup at K = 192)
-    CSTS_REQUIRE(csts_gemm5_ok(a, split), "algo 500 (streaming thin-operand NT kernel) not applicable to this problem");
-    CSTS_REQUIRE(csts_gemm5_launch(p, a, stream), "gemm5 launch failed");
-    CSTS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (pick5(a, split)) {
-    CSTS_REQUIRE(csts_gemm5_launch(p, a, stream), "gemm5 launch failed");
-    CSTS_LAUNCH_CHECK();
-    return 0;
-  }
-  {
-    int v4;
-    if (pick4(a, split, &v4)) {
-      CSTS_REQUIRE(csts_gemm4_launch(p, a, v4, 0, stream), "gemm4 heuristic picked a variant that is not instantiated");
-      CSTS_LAUNCH_CHECK();
-      return 0;
-    }
-    int mt3, st3;
-    if (pick3(a, split, &mt3, &st3)) {
-      launch3(p, a, mt3, st3, 0, stream);
-      CSTS_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  if (use_v2) {
-    int mt = pick_tile_rows(a, p.ntiles_n * nsplit);
-    mtiles = cdiv(a->M, mt);
-    dim3 grid2((unsigned)(mtiles * p.ntiles_n), (unsigned)nsplit, 1);
-    const bool af = a->a_dt == CSTS_F32, bf = a->b_dt == CSTS_F32;
-    if (a->layout == CSTS_GEMM_NT) {
-      if (bf) launch2<true, true, false, true>(p, mt, grid2, stream);
-      else launch2<true, true, false, false>(p, mt, grid2, stream);            // bf16 shadow weights
-    } else if (a->layout == CSTS_GEMM_NN) {
-      if (af && bf) launch2<true, false, true, true>(p, mt, grid2, stream);
-      else if (!af && bf) launch2<true, false, false, true>(p, mt, grid2, stream);
-      else if (af) launch2<true, false, true, false>(p, mt, grid2, stream);
-      else launch2<true, false, false, false>(p, mt, grid2, stream);
-    } else {
-      if (af) launch2<false, false, true, false>(p, mt, grid2, stream);
-      else launch2<false, false, false, false>(p, mt, grid2, stream);
-    }
-    CSTS_LAUNCH_CHECK();
-    if (det) {
-      launch_finish(p, (int)nsplit, stream);
-      CSTS_LAUNCH_CHECK();
-    }
-    return 0;
-  }
-  dim3 grid((unsigned)(mtiles * p.ntiles_n), (unsigned)nsplit, 1);
-  switch (a->layout) {
-    case CSTS_GEMM_NT: launch<true, true>(p, a->compute, grid, stream); break;
-    case CSTS_GEMM_NN: launch<true, false>(p, a->compute, grid, stream); break;
-    default: launch<false, false>(p, a->compute, grid, stream); break;
+    case GENERIC:
+      if (a->layout == CSTS_GEMM_NT) launch<true, true>(p, a->compute, grid, stream);
+      else if (a->layout == CSTS_GEMM_NN) launch<true, false>(p, a->compute, grid, stream);
+      else launch<false, false>(p, a->compute, grid, stream);
+      break;
   }
   CSTS_LAUNCH_CHECK();
   if (det) {
@@ -1484,76 +1505,39 @@ extern "C" int csts_gemm(const csts_gemm_args* a, hipStream_t stream) {
 
 extern "C" int csts_gemm_v2_eligible(const csts_gemm_args* a) { return a != nullptr && v2_ok(a) ? 1 : 0; }
 
-// Which kernel csts_gemm would launch for these arguments (host-only; used by bench.py to name the kernel a timed call
-// ran, exactly as rocprofv3 prints it): v2 = 1 -> gemm2_kernel<A_KC, B_KC, A_F32, B_F32, tile_rows / 64, 2>; v2 = 30 + stages ->
-// gemm3_kernel<tile_rows / 64, stages>; 0 -> gemm_kernel; -1 -> gemm_tiny_kernel.
+// The route in the encoding of include/csts_hip.h (host-only).
 extern "C" int csts_gemm_plan(const csts_gemm_args* a, int* v2, int* tile_rows, int* nsplit) {
   CSTS_REQUIRE(a != nullptr && v2 && tile_rows && nsplit, "null pointer");
-  const int split = a->split_k > 1 ? a->split_k : 1;
-  const bool use_v2 = v2_ok(a);
-  const int bk = use_v2 ? BK2 : BK;
-  const int64_t k_chunk = cdiv(cdiv(a->K, bk), split) * bk;
-  const int64_t ns = cdiv(a->K, k_chunk);
-  int mt3, st3, v4;
-  if (tiny_ok(a)) {                     // gemm_tiny_kernel<layout, wave mode>
-    *v2 = -1;
-    *nsplit = 1;
-    *tile_rows = 0;
-    return 0;
-  }
-  if (pick5(a, split)) {               // gemm5 (name: csts_gemm_kernel_name)
-    *v2 = 500;
-    *nsplit = 1;
-    *tile_rows = 0;
-    return 0;
-  }
-  if (pick4(a, split, &v4)) {          // gemm4 variant v4 (name: csts_gemm_kernel_name)
-    *v2 = 400 + v4;
-    *nsplit = 1;
-    *tile_rows = 0;
-    return 0;
-  }
-  if (pick3(a, split, &mt3, &st3)) {   // gemm3_kernel<tile_rows / 64, stages>
-    *v2 = 30 + st3;
-    *nsplit = 1;
-    *tile_rows = 64 * mt3;
-    return 0;
-  }
-  *v2 = use_v2 ? 1 : 0;
-  *nsplit = (int)ns;
-  *tile_rows = use_v2 ? pick_tile_rows(a, cdiv(a->N, BN) * ns) : BM;
+  Route r;
+  if (route(a, &r) != 0) return -1;
+  static const int code[] = {/* TINY */ -1, /* GENERIC */ 0, /* V2 */ 1, /* RING3 */ 30, /* G4 */ 400, /* G5 */ 500};
+  *v2 = code[r.family] + (r.family == RING3 ? r.stages : 0) + (r.family == G4 ? r.variant : 0);
+  *tile_rows = r.tile_rows;
+  *nsplit = r.nsplit;
   return 0;
 }
 
-// The same decision as a kernel NAME, spelled as rocprofv3 prints it (bench.py attributes its HIP-event timings to it).
+// The route as a kernel NAME, spelled as rocprofv3 prints it (bench.py attributes its HIP-event timings to it; host-only).
 extern "C" int csts_gemm_kernel_name(const csts_gemm_args* a, char* buf, int buflen, int* nsplit) {
   CSTS_REQUIRE(a != nullptr && buf != nullptr && buflen > 0 && nsplit != nullptr, "null pointer");
-  int v2 = 0, rows = 0;
-  if (csts_gemm_plan(a, &v2, &rows, nsplit) != 0) return -1;
+  Route r;
+  if (route(a, &r) != 0) return -1;
+  *nsplit = r.nsplit;
   auto tf = [](bool b) { return b ? "true" : "false"; };
-  Params q{};          // what the gemm4 epilogue-form choice looks at
-  q.M = a->M; q.N = a->N; q.K = a->K; q.c_dt = a->c_dt; q.residual = a->residual; q.row_scale = a->row_scale; q.bias = a->bias;
-  q.epilogue = a->epilogue; q.aux = a->aux; q.aux_dt = a->aux_dt;
-  if (a->algo % 1000 >= 400 && a->algo % 1000 < 500) {
-    *nsplit = 1;
-    return csts_gemm4_name(q, a->algo % 1000 - 400, buf, buflen) ? 0 : -1;
+  switch (r.family) {
+    case TINY: snprintf(buf, buflen, "gemm_tiny_kernel<%d, %s>", a->layout, tf(a->K > 16)); break;
+    case G5: CSTS_REQUIRE(csts_gemm5_name(a, buf, buflen), "gemm5 does not carry this problem"); break;
+    case G4: CSTS_REQUIRE(csts_gemm4_name(fill_params(a, r), r.variant, buf, buflen), "gemm4 variant is not instantiated"); break;
+    case RING3: snprintf(buf, buflen, "gemm3_kernel<%d, %d>", r.tile_rows / 64, r.stages); break;
+    case V2:
+      snprintf(buf, buflen, "gemm2_kernel<%s, %s, %s, %s, %d, 2>", tf(a->layout != CSTS_GEMM_TN), tf(a->layout == CSTS_GEMM_NT),
+               tf(a->a_dt == CSTS_F32), tf(a->b_dt == CSTS_F32), r.tile_rows / 64);
+      break;
+    case GENERIC:
+      snprintf(buf, buflen, "gemm_kernel<%s, %s, %s>", tf(a->layout != CSTS_GEMM_TN), tf(a->layout == CSTS_GEMM_NT),
+               tf(a->compute == CSTS_F32));
+      break;
   }
-  if (a->algo % 1000 == 500 || a->algo % 1000 == 503 || a->algo % 1000 == 506 || v2 == 500) {
-    *nsplit = 1;
-    return csts_gemm5_name(a, buf, buflen) ? 0 : -1;
-  }
-  if (v2 < 0) {
-    snprintf(buf, buflen, "gemm_tiny_kernel<%d, %s>", a->layout, tf(a->K > 16));
-    return 0;
-  }
-  if (v2 >= 400) return csts_gemm4_name(q, v2 - 400, buf, buflen) ? 0 : -1;
-  if (v2 >= 30) snprintf(buf, buflen, "gemm3_kernel<%d, %d>", rows / 64, v2 - 30);
-  else if (v2)
-    snprintf(buf, buflen, "gemm2_kernel<%s, %s, %s, %s, %d, 2>", tf(a->layout != CSTS_GEMM_TN), tf(a->layout == CSTS_GEMM_NT),
-             tf(a->a_dt == CSTS_F32), tf(a->b_dt == CSTS_F32), rows / 64);
-  else
-    snprintf(buf, buflen, "gemm_kernel<%s, %s, %s>", tf(a->layout != CSTS_GEMM_TN), tf(a->layout == CSTS_GEMM_NT),
-             tf(a->compute == CSTS_F32));
   return 0;
 }
 

@@ -467,69 +467,73 @@ int gemm4_form(const Params& p, int BM, int BN) {
   return 0;
 }
 
-template <int WM, int MT, int NT, int S, bool FORMS, int NP = 0>
-bool launch4(Params p, int wpc, hipStream_t s) {
+// one variant's launch: the instantiation that carries `form` (gemm4_form, or 0 where the variant has the generic epilogue only)
+template <int WM, int MT, int NT, int S, bool FORMS, int NP>
+void launch4(Params p, int form, int wpc, hipStream_t s) {
   typedef G4<WM, MT, NT, S, NP> G;
-  if (p.K % BK2 != 0) return false;
   const int64_t ntiles = cdiv(p.M, G::BM) * cdiv(p.N, G::BN);
   p.ntiles = ntiles;
   p.ntiles_n = (int)cdiv(p.N, G::BN);
   if (wpc <= 0 || wpc > G::WG) wpc = G::WG;
   const int64_t g = std::min<int64_t>(cdiv(ntiles, 8) * 8, (int64_t)256 * wpc);
   const dim3 grid((unsigned)g), block(G::NTHR);
-  const int form = FORMS ? gemm4_form(p, G::BM, G::BN) : 0;
   if constexpr (FORMS) {
-    if (form == 1) { hipLaunchKernelGGL((gemm4_kernel<WM, MT, NT, S, 1, NP>), grid, block, 0, s, p); return true; }
-    if (form == 2) { hipLaunchKernelGGL((gemm4_kernel<WM, MT, NT, S, 2, NP>), grid, block, 0, s, p); return true; }
-    if (form == 3) { hipLaunchKernelGGL((gemm4_kernel<WM, MT, NT, S, 3, NP>), grid, block, 0, s, p); return true; }
-    if (form == 4) { hipLaunchKernelGGL((gemm4_kernel<WM, MT, NT, S, 4, NP>), grid, block, 0, s, p); return true; }
-    if (form == 5) { hipLaunchKernelGGL((gemm4_kernel<WM, MT, NT, S, 5, NP>), grid, block, 0, s, p); return true; }
+    if (form == 1) { hipLaunchKernelGGL((gemm4_kernel<WM, MT, NT, S, 1, NP>), grid, block, 0, s, p); return; }
+    if (form == 2) { hipLaunchKernelGGL((gemm4_kernel<WM, MT, NT, S, 2, NP>), grid, block, 0, s, p); return; }
+    if (form == 3) { hipLaunchKernelGGL((gemm4_kernel<WM, MT, NT, S, 3, NP>), grid, block, 0, s, p); return; }
+    if (form == 4) { hipLaunchKernelGGL((gemm4_kernel<WM, MT, NT, S, 4, NP>), grid, block, 0, s, p); return; }
+    if (form == 5) { hipLaunchKernelGGL((gemm4_kernel<WM, MT, NT, S, 5, NP>), grid, block, 0, s, p); return; }
   }
   hipLaunchKernelGGL((gemm4_kernel<WM, MT, NT, S, 0, NP>), grid, block, 0, s, p);
-  return true;
 }
 
-struct Variant { int code, wm, mt, nt, s; };
 // shape ids: 0 = 256x128, 1 = 256x192, 2 = 256x256 (8 waves, wave tile 64 x 64/96/128);
 //            3 = 128x128, 6 = 128x192, 4 = 128x256 (8 waves, wave tile 32 x 64/96/128); 5 = 128x128 on 4 waves (wave tile 64 x 64);
 //            7 = 64x192 on 4 waves (wave tile 32 x 96; round 5: M = 8192 problems with 128 or fewer 128 x 192 tiles -- half the CUs idle);
+//            8 = wave-specialised (4 producer waves, 3-stage ring, one workgroup per CU -- G4::WG): 83 = 128 x 192, 84 = 128 x 128
 // (4-wave workgroups with 64 x 96 / 64 x 128 / 128 x 64 wave tiles -- fewer LDS fragment bytes per MFMA -- measured 10-90 %
 //  slower than the 8-wave 128 x 192 variant on every CSTS shape and were removed: profiles/r2_gemm4_lab2.txt)
-// last column: the specialised epilogue forms exist (the variants the library picks by itself)
+// columns: code, WM, MT, NT, S, the specialised epilogue forms exist (the variants the library picks by itself), NP
 #define G4_VARIANTS(X) \
-  X(2, 4, 2, 2, 2, false) X(3, 4, 2, 2, 3, false) X(12, 4, 2, 3, 2, false) X(22, 4, 2, 4, 2, false) \
-  X(32, 4, 1, 2, 2, true) X(33, 4, 1, 2, 3, true) X(34, 4, 1, 2, 4, true) X(62, 4, 1, 3, 2, true) X(63, 4, 1, 3, 3, true) X(64, 4, 1, 3, 4, true) X(42, 4, 1, 4, 2, false) \
-  X(52, 2, 2, 2, 2, false) X(72, 2, 1, 3, 2, true) X(73, 2, 1, 3, 3, true) X(74, 2, 1, 3, 4, true)
+  X(2, 4, 2, 2, 2, false, 0) X(3, 4, 2, 2, 3, false, 0) X(12, 4, 2, 3, 2, false, 0) X(22, 4, 2, 4, 2, false, 0) \
+  X(32, 4, 1, 2, 2, true, 0) X(33, 4, 1, 2, 3, true, 0) X(34, 4, 1, 2, 4, true, 0) X(62, 4, 1, 3, 2, true, 0) X(63, 4, 1, 3, 3, true, 0) \
+  X(64, 4, 1, 3, 4, true, 0) X(42, 4, 1, 4, 2, false, 0) X(52, 2, 2, 2, 2, false, 0) X(72, 2, 1, 3, 2, true, 0) X(73, 2, 1, 3, 3, true, 0) \
+  X(74, 2, 1, 3, 4, true, 0) X(83, 4, 1, 3, 3, true, 4) X(84, 4, 1, 2, 3, true, 4)
+
+// a variant resolved to the template arguments of its kernel, and the launcher of that instantiation family
+struct Variant {
+  int code, wm, mt, nt, s, np;
+  bool forms;
+  void (*launch)(Params, int form, int wpc, hipStream_t);
+};
+#define X(code, wm, mt, nt, st, forms, np) {code, wm, mt, nt, st, np, forms, launch4<wm, mt, nt, st, forms, np>},
+const Variant VARIANTS[] = {G4_VARIANTS(X)};
+#undef X
+
+// the variant's row and the epilogue form this problem takes in it; nullptr: no such variant, or K % 64 != 0 (not instantiated)
+const Variant* resolve4(const Params& p, int variant, int* form) {
+  if (p.K % BK2 != 0) return nullptr;
+  for (const Variant& v : VARIANTS)
+    if (v.code == variant) {
+      *form = v.forms ? gemm4_form(p, v.wm * 32 * v.mt, 64 * v.nt) : 0;
+      return &v;
+    }
+  return nullptr;
+}
 
 }  // namespace
 
-// wave-specialised variants (4 producer waves, 3-stage ring, one workgroup per CU): 83 = 128 x 192, 84 = 128 x 128
-bool csts_gemm4_launch(const csts_gemm_params& p0, const csts_gemm_args* a, int variant, int wpc, hipStream_t s) {
-  csts_gemm_params p = p0;
-  // OFF by default: measured neutral on the 2-stage ring (21.63 vs 21.63 ms per step, profiles/r4_gemm4_store_aware_ab.txt) and
-  // mixed with the 4-stage short-K ring (CSTS_GEMM4_SHORTK=64: -16 .. -18 % on two shapes, +6 .. +10 % on the DGELU forms, the
-  // largest fc1 + GELU unchanged at 2.96 TB/s) -- the drain of the previous tile's stores is NOT what holds these GEMMs at 3 TB/s
-  static const int store_aware = [] { const char* e = getenv("CSTS_GEMM4_STORE_AWARE"); return (e && e[0] == '1') ? 1 : 0; }();
-  p.store_aware = store_aware;
-  p.stamps = (a != nullptr && a->workspace != nullptr && a->ws_bytes >= 8192) ? reinterpret_cast<unsigned long long*>(a->workspace) : nullptr;
-  if (variant == 83) return launch4<4, 1, 3, 3, true, 4>(p, 1, s);
-  if (variant == 84) return launch4<4, 1, 2, 3, true, 4>(p, 1, s);
-#define X(code, wm, mt, nt, st, forms) if (variant == code) return launch4<wm, mt, nt, st, forms>(p, wpc, s);
-  G4_VARIANTS(X)
-#undef X
-  return false;
+bool csts_gemm4_launch(const csts_gemm_params& p, int variant, int wpc, hipStream_t s) {
+  int form;
+  const Variant* v = resolve4(p, variant, &form);
+  if (v != nullptr) v->launch(p, form, wpc, s);
+  return v != nullptr;
 }
 
 // the kernel csts_gemm4_launch starts for these parameters, as rocprofv3 prints it
 bool csts_gemm4_name(const csts_gemm_params& p, int variant, char* buf, int buflen) {
-  if (variant == 83 || variant == 84) {
-    const int nt = variant == 83 ? 3 : 2;
-    snprintf(buf, buflen, "gemm4_kernel<4, 1, %d, 3, %d, 4>", nt, gemm4_form(p, 128, 64 * nt));
-    return true;
-  }
-#define X(code, wm, mt, nt, st, forms) if (variant == code) { \
-    snprintf(buf, buflen, "gemm4_kernel<%d, %d, %d, %d, %d, 0>", wm, mt, nt, st, forms ? gemm4_form(p, wm * 32 * mt, 64 * nt) : 0); return true; }
-  G4_VARIANTS(X)
-#undef X
-  return false;
+  int form;
+  const Variant* v = resolve4(p, variant, &form);
+  if (v != nullptr) snprintf(buf, buflen, "gemm4_kernel<%d, %d, %d, %d, %d, %d>", v->wm, v->mt, v->nt, v->s, form, v->np);
+  return v != nullptr;
 }

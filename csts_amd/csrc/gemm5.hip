@@ -373,16 +373,24 @@ bool csts_gemm5_ok(const csts_gemm_args* a, int split) {
   return true;
 }
 
+// the instantiation gemm5_kernel<KCH, NB, W, form> a problem takes (csts_gemm5_ok holds)
+struct G5Config { int kch, nb, w, form; };
+static G5Config gemm5_config(const csts_gemm_args* a) {
+  const int kch = (int)(a->K / 96), nb = gemm5_nb(a);
+  return {kch, nb, ((kch == 2 && nb == 6) || kch == 4) ? 6 : 8, gemm5_form(a)};
+}
+
 bool csts_gemm5_launch(const csts_gemm_params& p, const csts_gemm_args* a, hipStream_t s) {
-  const int form = gemm5_form(a), nb = gemm5_nb(a);
-  if (a->K == 96) return nb == 6 ? launch5<1, 6>(p, form, s) : launch5<1, 3>(p, form, s);
-  if (a->K == 384) return launch5<4, 3, 6>(p, form, s);
-  return nb == 6 ? launch5<2, 6, 6>(p, form, s) : launch5<2, 3>(p, form, s);
+  const G5Config c = gemm5_config(a);
+#define X(KCH, NB, W) if (c.kch == KCH && c.nb == NB && c.w == W) return launch5<KCH, NB, W>(p, c.form, s);
+  X(1, 6, 8) X(1, 3, 8) X(2, 6, 6) X(2, 3, 8) X(4, 3, 6)
+#undef X
+  return false;
 }
 
 // the kernel csts_gemm5_launch starts, as rocprofv3 prints it
 bool csts_gemm5_name(const csts_gemm_args* a, char* buf, int buflen) {
-  const int nb = gemm5_nb(a);
-  snprintf(buf, buflen, "gemm5_kernel<%d, %d, %d, %d>", (int)(a->K / 96), nb, ((a->K == 192 && nb == 6) || a->K == 384) ? 6 : 8, gemm5_form(a));
+  const G5Config c = gemm5_config(a);
+  snprintf(buf, buflen, "gemm5_kernel<%d, %d, %d, %d>", c.kch, c.nb, c.w, c.form);
   return true;
 }

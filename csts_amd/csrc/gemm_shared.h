@@ -174,8 +174,8 @@ __device__ __forceinline__ void st4x2_bf16_whole(bf16* base, int64_t at, const f
 }  // namespace
 
 // gemm4.hip: persistent NT kernel, 256-row (8-wave) and 128-row (4- or 8-wave) tiles, LDS-DMA ring.
-// variant = 10 * shape + stages (see gemm4.hip); returns false when the variant does not exist.
-bool csts_gemm4_launch(const csts_gemm_params& p, const csts_gemm_args* a, int variant, int wpc, hipStream_t s);
+// variant = 10 * shape + stages (see gemm4.hip); both resolve (variant, p) the same way and return false when the variant does not exist.
+bool csts_gemm4_launch(const csts_gemm_params& p, int variant, int wpc, hipStream_t s);
 bool csts_gemm4_name(const csts_gemm_params& p, int variant, char* buf, int buflen);
 
 // gemm5.hip: streaming NT kernel for the thin problems (K = 96 / 192, N % 96 == 0, large M): weights resident in LDS, one stream per wave.

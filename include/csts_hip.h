@@ -74,9 +74,16 @@ typedef struct {
 } csts_gemm_args;
 int csts_gemm(const csts_gemm_args* args, hipStream_t stream);
 size_t csts_gemm_splitk_workspace(int64_t M, int64_t N, int64_t K, int split_k);
+/* Host-only queries of the ONE routing decision csts_gemm launches by (a forced args->algo included; a call csts_gemm would reject
+   because its forced algo cannot run the problem returns -1 here too, with csts_last_error set).
+   csts_gemm_plan: *nsplit = k-splits, and the kernel as a code in *v2 with its row tile in *tile_rows:
+     -1 gemm_tiny_kernel (tile_rows 0) ; 0 gemm_kernel (fp32 / unaligned operands, tile_rows 128) ;
+     1 gemm2_kernel<.., tile_rows / 64, 2> (register-staged 16-bit kernel) ; 30 + stages gemm3_kernel<tile_rows / 64, stages> (persistent
+     LDS-DMA NT kernel) ; 400 + variant gemm4_kernel (8-wave LDS-DMA NT kernel, tile_rows 0) ; 500 gemm5_kernel (streaming thin-operand NT
+     kernel, tile_rows 0). */
 int csts_gemm_plan(const csts_gemm_args* args, int* v2, int* tile_rows, int* nsplit);
-/* The kernel csts_gemm would launch, by NAME as rocprofv3 prints it (for attributing live timings); *nsplit = k-splits. */
-int csts_gemm_kernel_name(const csts_gemm_args* a, char* buf, int buflen, int* nsplit);   /* which kernel / tile / k-split csts_gemm picks: v2 = 0 generic, 1 register-staged bf16 kernel, 30 + stages = persistent LDS-DMA NT kernel */
+/* The same route by NAME, with every template argument, as rocprofv3 prints it (for attributing live timings); *nsplit = k-splits. */
+int csts_gemm_kernel_name(const csts_gemm_args* a, char* buf, int buflen, int* nsplit);
 int csts_gemm_v2_eligible(const csts_gemm_args* args);   /* 1 when the fast bf16 kernel (and fused colsum) applies */
 
 /* Grouped weight gradients: every dW[M,N] = dY[tokens,M]^T X[tokens,N] of a backward pass (nn.Linear weight gradients of

@@ -2,6 +2,8 @@
 reference of the same op on the same seeded inputs.  Tolerances: fp32 mode (exact-fp32 MFMA) 2e-5 rel-L2;
 bf16 mode 2e-2 rel-L2 (operands rounded to bf16, fp32 accumulation)."""
 import math
+import os
+import sys
 
 import pytest
 import torch
@@ -17,6 +19,9 @@ if not torch.cuda.is_available():  # collected everywhere, run only on the GPU b
 from csts_amd import lib as L          # noqa: E402
 from csts_amd import ops               # noqa: E402
 from oracle import csts_oracle as O    # noqa: E402
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+from gemm_route_table import case_label, gemm_args, kernel_name   # noqa: E402
 
 DEV = torch.device("cuda:0")
 TOL = {L.F32: 2e-5, L.BF16: 2e-2}
@@ -220,15 +225,60 @@ def test_gemm5_streaming_thin_kernel(algo, M, N, K):
     got = run(algo, odt=torch.float32, bias=b)                                    # plain fp32 output
     assert rel_l2(got, pre) < 1e-4 and torch.equal(got, run(2, odt=torch.float32, bias=b))
     if algo == 0 and K != 384:                                                    # the library does route these shapes to gemm5 (K = 384: opt-in)
-        a = L.GemmArgs()
-        a.layout, a.M, a.N, a.K, a.compute = L.GEMM_NT, M, N, K, L.BF16
-        a.A, a.a_dt, a.lda, a.B, a.b_dt, a.ldb = A.data_ptr(), L.BF16, K, W.data_ptr(), L.BF16, K
         o = torch.empty(M, N, device=DEV, dtype=dt)
-        a.C, a.c_dt, a.ldc = o.data_ptr(), L.BF16, N
-        import ctypes as C
-        buf, ns = C.create_string_buffer(160), C.c_int(0)
-        assert ops._lib().csts_gemm_kernel_name(C.byref(a), buf, 160, C.byref(ns)) == 0
-        assert buf.value.decode().startswith("gemm5_kernel<"), buf.value
+        rc, name, _ = kernel_name(gemm_args("NT", M, N, K, ptrs=dict(A=A.data_ptr(), B=W.data_ptr(), C=o.data_ptr())))
+        assert rc == 0
+        assert name.startswith("gemm5_kernel<"), name
+
+
+# (kernel the fixture names, M, N, K, gemm_args keywords): NT lines of tests/golden/gemm_routes.txt, one or more per kernel family
+# and per forced range
+ROUTED = [
+    ("gemm_tiny_kernel<0, false>", 4, 256, 4, dict(a="f32", b="f32", c="f32", compute="f32", bias=True)),
+    ("gemm_kernel<true, true, true>", 300, 200, 96, dict(a="f32", b="f32", c="f32", compute="f32")),
+    ("gemm2_kernel<true, true, false, false, 1, 2>", 520, 384, 96, dict(bias=True)),
+    ("gemm3_kernel<1, 3>", 300, 96, 1040, dict(c="f32", bias=True, res="f32")),
+    ("gemm4_kernel<4, 1, 3, 2, 2, 0>", 8192, 1536, 384, dict(bias=True, epi="gelu", aux="bf16")),
+    ("gemm5_kernel<1, 6, 8, 1>", 16384, 192, 96, dict(bias=True, epi="gelu", aux="bf16")),
+    ("gemm3_kernel<1, 3>", 8192, 1536, 384, dict(algo=313)),
+    ("gemm3_kernel<2, 2>", 8192, 384, 1536, dict(algo=1322, bias=True, epi="gelu", aux="bf16")),
+    ("gemm4_kernel<4, 1, 3, 3, 5, 0>", 8192, 384, 1536, dict(algo=463, c="f32", bias=True, res="f32")),
+    ("gemm4_kernel<4, 1, 3, 3, 0, 0>", 8192, 384, 1536, dict(algo=463, c="f32", res="bf16")),
+    ("gemm5_kernel<2, 3, 8, 0>", 16384, 192, 192, dict(algo=500)),
+    ("gemm5_kernel<2, 6, 6, 0>", 16384, 192, 192, dict(algo=506)),
+]
+
+
+@pytest.mark.parametrize("want,M,N,K,kw", ROUTED)
+def test_gemm_route_names_a_kernel_that_runs(want, M, N, K, kw, golden_dir):
+    """The routing table (tests/test_gemm_route_host.py) says WHICH kernel a call takes; this says the kernel it names can run the
+    problem: for cases of the fixture over all six families and the forced 3xx / 4xx / 5xx ranges, the name asked for with the real
+    operands is the fixture's, and ops.gemm on those operands agrees with fp32 torch (nn.Linear + GELU / residual:
+    attention.py:130,159,238-248) -- 6e-3 rel-L2 for 16-bit outputs, 1e-4 for fp32 outputs, as in the tests above."""
+    label = case_label("NT", M, N, K, **kw)
+    line = next(l for l in open(os.path.join(golden_dir, "gemm_routes.txt")) if l.startswith(label + " | "))
+    assert f" | {want} | " in line
+    dts = {"f32": torch.float32, "bf16": torch.bfloat16}
+    A, W = rnd(M, K, seed=1).to(dts[kw.get("a", "bf16")]), rnd(N, K, seed=2, scale=0.2).to(dts[kw.get("b", "bf16")])
+    b = rnd(N, seed=3) if kw.get("bias") else None
+    res = rnd(M, N, seed=4).to(dts[kw["res"]]) if kw.get("res") else None
+    aux = torch.full((M + 1, N), 7.0, device=DEV, dtype=dts[kw["aux"]]) if kw.get("aux") else None
+    out = torch.full((M + 1, N), 7.0, device=DEV, dtype=dts[kw.get("c", "bf16")])
+    ptrs = dict(A=A.data_ptr(), B=W.data_ptr(), C=out.data_ptr(), bias=b.data_ptr() if b is not None else 0,
+                aux=aux.data_ptr() if aux is not None else 0, residual=res.data_ptr() if res is not None else 0)
+    rc, name, _ = kernel_name(gemm_args("NT", M, N, K, ptrs=ptrs, **kw))
+    assert rc == 0 and name == want, name
+    compute = L.F32 if kw.get("compute") == "f32" else L.BF16
+    ops.gemm(L.GEMM_NT, A, 0, K, W, 0, K, out, N, M, N, K, compute=compute, bias=b, aux=aux, residual=res, ldr=N if res is not None else 0,
+             epilogue=L.EPI_GELU if kw.get("epi") == "gelu" else L.EPI_NONE, algo=kw.get("algo", 0))
+    pre = A.float() @ W.float().t() + (b if b is not None else 0)
+    ref = (F.gelu(pre) if kw.get("epi") == "gelu" else pre) + (res.float() if res is not None else 0)
+    tol = 1e-4 if out.dtype == torch.float32 else 6e-3
+    err = rel_l2(out[:M].float(), ref)
+    print(f"{label}: {name}  rel-L2 {err:.3e} (bound {tol:g})")
+    assert err < tol and (out[M] == 7).all()
+    if aux is not None:
+        assert rel_l2(aux[:M].float(), pre) < 6e-3 and (aux[M] == 7).all()
 
 
 @pytest.mark.parametrize("compute", [L.F32, L.BF16])
