@@ -143,6 +143,7 @@ class Block(nn.Module):
         self.drop_prob = float(drop_path)
         self.drop_rate, self.dropout_site = float(drop_rate), int(dropout_site)
         self.rt = rt
+        self.checkpointed = False           # set by CSTS for its encoder blocks when MODEL.ACT_CHECKPOINT is on
         self.norm1 = nn.LayerNorm(dim, eps=1e-6)
         self.attn = _Attention(dim, heads, kind, has_pool_q, has_pool_kv, stride_q, stride_kv)
         self.norm2 = nn.LayerNorm(dim, eps=1e-6)
@@ -277,11 +278,16 @@ class CSTS(nn.Module):
             raise ValueError(f"MVIT.DROPOUT_RATE must be in [0, 1), got {cfg.MVIT.DROPOUT_RATE}")
         amd = getattr(cfg, "CSTS_AMD", None)
         self.rt = Runtime(resolve_compute(cfg))
-        if bool(getattr(cfg.MODEL, "ACT_CHECKPOINT", False)):
-            # custom_multimodal_builder.py:154,178,214 wrap every block in fairscale's checkpoint_wrapper: a memory-for-recompute
-            # trade that leaves every value unchanged.  Never ignored silently: logged, like TRAIN.MIXED_PRECISION.
-            _log.warning("MODEL.ACT_CHECKPOINT True: activation checkpointing is not applied here -- the saved activations of the "
-                         "largest shipped configuration (32x256^2, B=1) peak at 11.6 GiB of 288 GB, and results do not depend on it")
+        # custom_multimodal_builder.py:154,178,214 wrap every video and audio encoder block in fairscale's checkpoint_wrapper: the
+        # block keeps its input and recomputes its forward in backward (ops.CheckpointFn); no value changes, no parameter is renamed
+        self.act_checkpoint = bool(getattr(cfg.MODEL, "ACT_CHECKPOINT", False))
+        if self.act_checkpoint:
+            if SPLIT_STAGE3:
+                raise NotImplementedError("MODEL.ACT_CHECKPOINT True cannot be combined with the CSTS_SPLIT_STAGE3 experiment (half-batch "
+                                          "chains of blocks 4..13 on two streams): unset one of them")
+            # never acted on silently: the decision is logged, like TRAIN.MIXED_PRECISION
+            _log.warning("MODEL.ACT_CHECKPOINT True: the video and audio encoder blocks keep only their input and recompute their forward "
+                         "in backward (same kernels, same drop-path scales and dropout masks: results do not depend on the key)")
         self.two_streams = bool(getattr(amd, "TWO_STREAMS", True)) if amd is not None else True
         rt = self.rt
         S, T = cfg.DATA.TRAIN_CROP_SIZE, cfg.DATA.NUM_FRAMES
@@ -369,6 +375,8 @@ class CSTS(nn.Module):
         for i, blk in enumerate([m_ for m_ in self.modules() if isinstance(m_, Block)]):
             blk.dropout_site = 2 + 3 * i
         self._dropout_key = None
+        for blk in list(self.blocks) + list(self.blocks_audio):     # exactly the reference's set: not the fusion blocks, not the decoder
+            blk.checkpointed = self.act_checkpoint
         # ---- init (:304-325): trunc_normal(.02) pos-embeds and Linear weights, LN 1/0; convs keep torch default
         for p_ in (self.pos_embed_spatial, self.pos_embed_temporal, self.pos_embed_spatial_audio, self.pos_embed_temporal_audio):
             trunc_normal_(p_, std=0.02)
@@ -462,6 +470,18 @@ class CSTS(nn.Module):
         if st is None:
             st = _SIDE_STREAMS[self] = torch.cuda.Stream()
         return st
+
+    def checkpointed_blocks(self):
+        """Names of the blocks that recompute their forward in backward (MODEL.ACT_CHECKPOINT): the 16 video and 4 audio encoder
+        blocks when the key is on, none when it is off."""
+        return [n for n, m_ in self.named_modules() if isinstance(m_, Block) and m_.checkpointed]
+
+    def _run_block(self, blk, x, thw, km, lane=0):
+        """One encoder block: as ever, or -- MODEL.ACT_CHECKPOINT, and only when a tape is being recorded -- as one checkpointed
+        autograd node.  lane: 0 = video trunk, 1 = audio trunk (the two may run their backward side by side)."""
+        if blk.checkpointed and torch.is_grad_enabled():
+            return ops.checkpoint_block(blk, x, thw, km, lane)
+        return blk(x, thw, km)
 
     def head_parameters(self):
         """Parameters of everything after the encoder trunks (fusion convs and blocks, decoder, classifier, EgoNCE
@@ -562,9 +582,9 @@ class CSTS(nn.Module):
         inter = [keep]
         inter_thw = [list(thw)]
 
-        def run(t, shape, blocks, names):
+        def run(t, shape, blocks, names):        # the audio trunk
             for blk, nm in zip(blocks, names):
-                t, shape, _ = blk(t, shape, km.get(nm))
+                t, shape, _ = self._run_block(blk, t, shape, km.get(nm), lane=1)
             return t, shape
 
         vb, ab = self.blocks, self.blocks_audio
@@ -602,7 +622,7 @@ class CSTS(nn.Module):
                 continue
             if cut_at and i == cut_at:
                 xt = boundary.inner([xt])[0]
-            xt, thw, _ = blk(xt, thw, km.get(nm))
+            xt, thw, _ = self._run_block(blk, xt, thw, km.get(nm))
             if i in (0, 2, 13):                  # the encoder features the decoder re-uses (:389,396,403)
                 xt, keep = ops.tap(xt, rt.compute)
                 inter.append(keep)

@@ -176,6 +176,81 @@ def reset_deferred():
     _deferred_task[0] = -1
 
 
+# A backward pass that starts INSIDE a backward pass (an activation-checkpointed block re-runs its forward and back-propagates
+# through the fresh sub-graph from its own backward: CheckpointFn) is a graph task of its own.  Its queues must not be mixed
+# with the outer pass's, and the outer pass's must not be taken for a dead pass's leftovers.  nested_backward() is the scope of
+# such an inner pass: it sets the outer pass's queues aside (a stack of frames), the inner pass queues into empty ones and its
+# own final callback finishes them -- its weight gradients, reductions and hand-overs are complete, and its operands released,
+# when the inner torch.autograd.backward returns -- and the outer queues come back untouched.
+_frames = []            # saved frames of the suspended outer passes, innermost last
+_nest_lane = [None]     # None at top level; inside nested_backward the lane label of the inner pass (selects its host tables)
+
+
+def _frame_state():
+    lists = (_deferred, _assign, _wgq, _wg_pending, _swq, _swq_early_keep, _sw_keep)
+    dicts = (_wg_prod, _sw_prod)
+    cells = (_deferred_task, _wg_work, _w8_count, _swq_count, _swq_early_used, _wg_side_used, _sw_used)
+    return lists, dicts, cells
+
+
+def _frame_empty() -> bool:
+    lists, dicts, _ = _frame_state()
+    return not any(lists) and not any(dicts)
+
+
+def _push_frame(lane):
+    lists, dicts, cells = _frame_state()
+    _frames.append(([list(l_) for l_ in lists], [dict(d_) for d_ in dicts], [c_[0] for c_ in cells], _nest_lane[0]))
+    for l_ in lists:
+        l_.clear()
+    for d_ in dicts:
+        d_.clear()
+    _deferred_task[0], _wg_work[0], _w8_count[0], _swq_count[0] = -1, 0.0, 0, 0
+    _swq_early_used[0] = _wg_side_used[0] = _sw_used[0] = False
+    _nest_lane[0] = lane
+
+
+def _pop_frame():
+    if not _frame_empty() or _deferred_task[0] != -1:
+        reset_deferred()                # the inner pass raised before its final callback ran: its leftovers go, the outer queue stays
+    lists, dicts, cells = _frame_state()
+    s_lists, s_dicts, s_cells, lane = _frames.pop()
+    for l_, v_ in zip(lists, s_lists):
+        l_[:] = v_
+    for d_, v_ in zip(dicts, s_dicts):
+        d_.clear()
+        d_.update(v_)
+    for c_, v_ in zip(cells, s_cells):
+        c_[0] = v_
+    _nest_lane[0] = lane
+
+
+@contextlib.contextmanager
+def nested_backward(lane=0):
+    """Scope of a backward pass run from inside another pass's node (torch.autograd.backward in a Function's backward): the
+    outer pass's deferred work is set aside and comes back untouched; everything the inner pass defers is finished by the inner
+    pass's own final callback, on the stream the inner pass was started from, before the scope ends.  lane: a small label for
+    that stream -- inner passes that may run concurrently on different streams (the video and the audio trunk) need different
+    lanes, because a lane owns the device tables its finishing launches read."""
+    _push_frame(lane)
+    try:
+        yield
+    finally:
+        _pop_frame()
+
+
+def _table_key(dev_index, *extra):
+    """Key of a flush's host -> device table: per device at top level (as ever), per (device, lane) inside a nested pass -- a
+    nested flush on the audio stream must not overwrite the table a nested flush on the main stream is still reading."""
+    lane = _nest_lane[0]
+    key = (dev_index,) + extra if extra else dev_index
+    return key if lane is None else ("nested", lane, key)
+
+
+# host tables of nested flushes: one block's work per upload, one upload per checkpointed block and capture
+_NESTED_CAPTURES = 32
+
+
 def _can_defer(*params) -> bool:
     """True when the caller may leave its gradient for the end-of-backward flush: inside a backward pass, and every
     given parameter is a leaf the flush can assign to (None entries are ignored)."""
@@ -238,7 +313,8 @@ def _hand_over():
         else:
             p_.grad.add_(g_)
     _assign.clear()
-    _grad_targets_used.clear()
+    if _nest_lane[0] is None:           # a nested pass ends in the middle of the outer one: the bucket views stay single-use until that ends
+        _grad_targets_used.clear()
 
 
 def _targets_reset():
@@ -249,7 +325,8 @@ def flush_deferred():
     """Finish the queued weight gradients and every deferred reduction on the current stream, then hand the results to
     their parameters (idempotent)."""
     _deferred_task[0] = -1
-    if _w8_count[0]:
+    nested = _nest_lane[0] is not None
+    if _w8_count[0] and not nested:
         _w8_total[0] = _w8_count[0]
     _w8_count[0] = 0
     # the grouped stencil weight gradients (0.8 ms of load-latency-bound work, no matrix math) run on a side stream BESIDE the
@@ -257,7 +334,9 @@ def flush_deferred():
     _swq_count[0] = 0
     _sw_prod.clear()
     tail = None
-    if _swq and _wgq and STENCIL_TAIL_SIDE and _swq[0][5][0].is_cuda:
+    # (a nested pass finishes ONE block: its two or three pools stay on the pass's own stream -- a fork / join pair per block would
+    # cost more in the captured graph than the overlap returns, and the audio trunk's blocks already run beside the video trunk's)
+    if _swq and _wgq and STENCIL_TAIL_SIDE and _swq[0][5][0].is_cuda and not nested:
         cur = torch.cuda.current_stream()
         tail = _tail_side.get(cur.device.index)
         if tail is None:
@@ -292,9 +371,10 @@ def flush_deferred():
     items = sorted(_deferred, key=lambda it: (wide(it), it[3]))
     _deferred.clear()
     dev = items[0][0].device
-    tab = _deferred_tables.get(dev.index)
+    tkey = _table_key(dev.index)
+    tab = _deferred_tables.get(tkey)
     if tab is None:
-        tab = _deferred_tables[dev.index] = HostTable(C.sizeof(L.ReduceDesc) * 2048, dev, ring=4, captures=16)
+        tab = _deferred_tables[tkey] = HostTable(C.sizeof(L.ReduceDesc) * 2048, dev, ring=4, captures=_NESTED_CAPTURES if nested else 16)
     # one launch per size class (the grid is sized by the widest reduction of the launch)
     descs = (L.ReduceDesc * len(items))()
     for i, (ws, out, nrows, ncols) in enumerate(items):
@@ -513,10 +593,13 @@ def flush_wgrads(side: bool = False, only_w8: bool = False, w8: str = "all"):
     dev = q[0][0].device
     # (w8 = "exclude" runs on the tail side stream CONCURRENTLY with the "only" launch of the main stream: its own device table -- one table
     # for both let the second upload overwrite the items the first launch was still reading: a GPU memory fault, round 5)
-    key = (dev.index, "x" if w8 == "exclude" else side)
+    key = _table_key(dev.index, "x" if w8 == "exclude" else side)
     tab = _wg_tables.get(key)
     if tab is None:
-        tab = _wg_tables[key] = HostTable(C.sizeof(L.WgradItem) * 24576, dev, ring=8, captures=40 if side else 16)
+        if _nest_lane[0] is not None:   # one block's items per upload (a single tile class is capped at 16384 items)
+            tab = _wg_tables[key] = HostTable(C.sizeof(L.WgradItem) * 16384, dev, ring=8, captures=_NESTED_CAPTURES)
+        else:
+            tab = _wg_tables[key] = HostTable(C.sizeof(L.WgradItem) * 24576, dev, ring=8, captures=40 if side else 16)
     keep = []
     launch_stream = None
     if side:
@@ -684,9 +767,11 @@ def flush_stencil_wgrads():
     q = list(_swq)
     _swq.clear()
     dev = q[0][5][0].device
-    tab = _swq_tables.get(dev.index)
+    tkey = _table_key(dev.index)
+    tab = _swq_tables.get(tkey)
     if tab is None:
-        tab = _swq_tables[dev.index] = HostTable(L.DWCONV_WGRAD_TABLE_ENTRY * 256, dev, ring=4, captures=16)
+        tab = _swq_tables[tkey] = HostTable(L.DWCONV_WGRAD_TABLE_ENTRY * 256, dev, ring=4,
+                                            captures=_NESTED_CAPTURES if _nest_lane[0] is not None else 16)
     for dt in sorted({e[4] for e in q}):
         sel = [e for e in q if e[4] == dt]
         if len(sel) > 256:
@@ -2223,6 +2308,82 @@ def split_tokens(x, n: int):
 def tap(x, compute):
     """(x_a, x_b): two aliases of x, one per consumer."""
     return TapFn.apply(x, compute)
+
+
+# ----------------------------------------------------------------------------------------- activation checkpointing
+class _GradCatch(Function):
+    """Identity in front of a recomputed block: its backward keeps the block-input gradient -- the very tensor object the block's
+    first LayerNorm returned, with the 16-bit copy attached to it (_attach16) -- for CheckpointFn to pass on, and gives autograd
+    nothing to accumulate."""
+
+    @staticmethod
+    def forward(ctx, x, box):
+        ctx.box = box
+        ctx.set_materialize_grads(False)
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        ctx.box.append(g)
+        return None, None
+
+
+class CheckpointFn(Function):
+    """One encoder block as ONE autograd node (MODEL.ACT_CHECKPOINT: fairscale's checkpoint_wrapper around every video / audio
+    encoder block, custom_multimodal_builder.py:154,178,214).  Forward runs the block without a tape and keeps its input, the token
+    grid, the drop-path scales, the dropout key and the stream; backward re-runs the block with a tape on that stream -- same
+    kernels, same scales, same key, hence the same masks -- and back-propagates through the fresh sub-graph as a nested pass
+    (nested_backward): the block's parameter gradients reach the parameters there (AccumulateGrad, or the nested pass's own
+    end-of-pass hand-over), and the recomputed activations are gone when this node returns."""
+
+    @staticmethod
+    def forward(ctx, x, block, thw, km, lane, box):
+        _need_gpu(x)
+        ctx.block, ctx.thw, ctx.km, ctx.lane = block, list(thw), km, lane
+        ctx.key = block.rt.drop_key
+        ctx.stream = torch.cuda.current_stream()
+        ctx.prod_scale = getattr(x, "_csts_prod_scale", None)
+        ctx.save_for_backward(x)
+        ctx.set_materialize_grads(False)
+        with torch.no_grad():
+            out, q_thw, _ = block(x, thw, km)
+        box["thw"], box["prod_scale"] = q_thw, getattr(out, "_csts_prod_scale", None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        if dy is None:
+            return None, None, None, None, None, None
+        x, = ctx.saved_tensors
+        block, rt = ctx.block, ctx.block.rt
+        caught = []
+        key_now, rt.drop_key = rt.drop_key, ctx.key
+        try:
+            with torch.cuda.stream(ctx.stream), nested_backward(ctx.lane):
+                with torch.enable_grad():
+                    xin = _GradCatch.apply(x.detach().requires_grad_(True), caught)
+                    if ctx.prod_scale is not None:      # what the producer of x left for the LayerNorm that reads it
+                        xin._csts_prod_scale = ctx.prod_scale
+                    out, _, _ = block(xin, ctx.thw, ctx.km)
+                torch.autograd.backward(out, dy)
+                del out, xin
+        finally:
+            rt.drop_key = key_now
+        return (caught[0] if caught else None), None, None, None, None, None
+
+
+def checkpoint_block(block, x, thw, km=None, lane=0):
+    """block(x, thw, km) -> (out, thw_out, None) with the block's activations recomputed in backward (CheckpointFn).  The
+    drop-path scales are fixed here, once, so that both runs of the block read the same tensors.  lane: see nested_backward."""
+    s1, s2 = block._drop_scales(x.shape[0], x.device, km)
+    km = ("scales", s1, s2) if s1 is not None else None
+    if not x.requires_grad:             # nothing in front of the block trains: the node still has to run for the block's own parameters
+        x = x.detach().requires_grad_(True)
+    box = {}
+    out = CheckpointFn.apply(x, block, thw, km, lane, box)
+    if box["prod_scale"] is not None:
+        out._csts_prod_scale = box["prod_scale"]
+    return out, box["thw"], None
 
 
 def cast(x: torch.Tensor, dt: int) -> torch.Tensor:
