@@ -5,12 +5,15 @@ by NAME AND SHAPE (fine-tuning from a Kinetics MViT-B or from released CSTS weig
 (SURVEY.md 8(f) rank 4): plain torch on the host, no kernels."""
 from __future__ import annotations
 
+import logging
 import os
 from collections import OrderedDict
 
 import torch
 import torch.nn.functional as F
 import yaml
+
+_log = logging.getLogger("csts_amd")
 
 
 def get_checkpoint_dir(path_to_job):
@@ -171,3 +174,16 @@ def load_train_checkpoint(cfg, model, optimizer, scaler=None):
                                 clear_name_pattern=getattr(cfg.TRAIN, "CHECKPOINT_CLEAR_NAME_PATTERN", ()))
         return epoch + 1
     return 0
+
+
+def load_test_checkpoint(cfg, model):
+    """checkpoint.py:579-614, first and last branch: with TEST.CHECKPOINT_FILE_PATH set, load that file into the model by the
+    name-and-shape rule of load_checkpoint (no optimizer, the epoch is not used, the data-parallel wrapper is stripped);
+    otherwise say that the weights are the random initialisation and return.  The reference's two branches in between -- the
+    last checkpoint of OUTPUT_DIR, then TRAIN.CHECKPOINT_FILE_PATH -- are NOT taken here: they would change what a
+    `TRAIN.ENABLE True TEST.ENABLE True` command prints after a checkpointed training run, and with the key empty every command
+    behaves as it did before the key was read.  Name the file to test."""
+    if cfg.TEST.CHECKPOINT_FILE_PATH != "":
+        load_checkpoint(cfg.TEST.CHECKPOINT_FILE_PATH, model, cfg.NUM_GPUS > 1, None)
+        return
+    _log.warning("Unknown way of loading checkpoint. Using with random initialization, only for debugging.")

@@ -208,7 +208,9 @@ def test(cfg):
     from .build import build_model
     from . import train as T
     from . import losses
+    from . import checkpoint as ck
     model = build_model(cfg)
+    ck.load_test_checkpoint(cfg, model)          # tools/test_avgaze_net.py:120 (TEST.CHECKPOINT_FILE_PATH; "" = random weights)
     model.eval()
     world = max(cfg.NUM_GPUS, 1)
     b = max(1, min(cfg.TEST.BATCH_SIZE // world, 8))

@@ -1,0 +1,170 @@
+// Gaze head of the inference path: everything a consumer of a prediction needs from one read of a frame's logits.
+// frame_softmax (slowfast/utils/utils.py:5-12, temperature 2 on this path), the per-frame min-max rescale of the test driver
+// (tools/test_avgaze_net.py:68-70), the gaze point = the arg-max cell mapped back by the inverse of the centre rule of
+// _get_gaussian_map (ego4d_avgaze_forecast.py:404-407) and the peak probability.  include/csts_hip.h states the rule.
+// One workgroup of 256 lanes per frame; the frame stays in registers (NCH x 4 values per lane) between the three reductions
+// (max + arg-max together, exp-sum, min) and the writes, so the logits are read once and nothing is re-read from memory.
+#include "common.h"
+
+namespace {
+
+constexpr int DEC_MAX_NCH = CSTS_GAZE_DECODE_MAX_HW / 1024;      // 4-value chunks per lane at the largest frame
+
+// Element r of chunk c of lane tid.  VEC: 4 consecutive cells per chunk (128-bit stores, 64- / 128-bit loads); otherwise the
+// cells of a chunk are 256 apart (frames whose size or address does not allow vector access).
+template <bool VEC>
+__device__ __forceinline__ int cell_of(int c, int r, int tid) {
+  return VEC ? (c * 256 + tid) * 4 + r : (c * 4 + r) * 256 + tid;
+}
+
+// (value, index) pair with "larger value wins, lowest index on ties"
+__device__ __forceinline__ void take_max(float& v, int& i, float ov, int oi) {
+  if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+}
+
+template <int NCH, bool VEC>
+__global__ __launch_bounds__(256) void gaze_decode_kernel(const void* __restrict__ logits, int dt, int H, int W, float inv_temp,
+                                                          float* __restrict__ preds, float* __restrict__ rescaled,
+                                                          float* __restrict__ points, float* __restrict__ peak) {
+  __shared__ float red_v[3][4];
+  __shared__ int red_i[4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int hw = H * W;
+  const int64_t frame = blockIdx.x, base = frame * hw;
+  float x[NCH * 4];                     // logits, then exp(logit / temperature - max)
+  // ---- one read of the frame
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    if (VEC) {
+      const int at = (c * 256 + tid) * 4;
+      if (at < hw) {                    // hw % 4 == 0 on this path: a chunk is inside the frame or outside it
+        if (dt == CSTS_F32) {
+          const f32x4 v = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(logits) + base + at);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) x[c * 4 + r] = v[r];
+        } else {
+          const bf16x4 v = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16*>(logits) + base + at);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) x[c * 4 + r] = (float)v[r];
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) x[c * 4 + r] = -INFINITY;
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int at = cell_of<false>(c, r, tid);
+        x[c * 4 + r] = at < hw ? ld_as_f32(logits, dt, base + at) : -INFINITY;
+      }
+    }
+  }
+  // ---- max and arg-max of the logits together (the softmax is monotone: this is the heat map's maximum; a lane walks its
+  // cells in ascending index order, so `>` keeps the lowest index)
+  float bv = -INFINITY;
+  int bi = 0x7fffffff;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int at = cell_of<VEC>(c, r, tid);
+      if (at < hw) take_max(bv, bi, x[c * 4 + r], at);
+    }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) take_max(bv, bi, __shfl_xor(bv, o, 64), __shfl_xor(bi, o, 64));
+  if (lane == 0) { red_v[0][w] = bv; red_i[w] = bi; }
+  __syncthreads();
+  bv = red_v[0][0]; bi = red_i[0];
+#pragma unroll
+  for (int k = 1; k < 4; ++k) take_max(bv, bi, red_v[0][k], red_i[k]);
+  if (bi >= hw) bi = 0;                 // a frame without a comparable value (all NaN): still a cell of the frame
+  const float mx = bv * inv_temp;       // = max of logit * inv_temp (inv_temp > 0)
+  // ---- exp-sum and min (cells outside the frame hold exp(-inf) = 0 and are kept out of the min)
+  float s = 0.f, emin = INFINITY;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float e = __expf(x[c * 4 + r] * inv_temp - mx);
+      x[c * 4 + r] = e;
+      s += e;
+      if (cell_of<VEC>(c, r, tid) < hw) emin = fminf(emin, e);
+    }
+  s = wave_sum(s);
+  if (lane == 0) red_v[1][w] = s;
+  __syncthreads();
+  s = red_v[1][0] + red_v[1][1] + red_v[1][2] + red_v[1][3];
+  emin = -wave_max(-emin);
+  if (lane == 0) red_v[2][w] = emin;
+  __syncthreads();
+  emin = fminf(fminf(red_v[2][0], red_v[2][1]), fminf(red_v[2][2], red_v[2][3]));
+  const float inv = 1.f / s;
+  const float pmax = __expf(bv * inv_temp - mx) * inv;      // the arg-max cell's probability (exp(0) = 1)
+  const float pmin = emin * inv;                            // min of e * inv: the product is monotone in e
+  const float denom = pmax - pmin + 1e-6f;
+  // ---- writes
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    if (VEC) {
+      const int at = (c * 256 + tid) * 4;
+      if (at < hw) {
+        f32x4 p, q;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { p[r] = x[c * 4 + r] * inv; q[r] = (p[r] - pmin) / denom; }
+        if (preds) *reinterpret_cast<f32x4*>(preds + base + at) = p;
+        if (rescaled) *reinterpret_cast<f32x4*>(rescaled + base + at) = q;
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int at = cell_of<false>(c, r, tid);
+        if (at < hw) {
+          const float p = x[c * 4 + r] * inv;
+          if (preds) preds[base + at] = p;
+          if (rescaled) rescaled[base + at] = (p - pmin) / denom;
+        }
+      }
+    }
+  }
+  if (tid == 0) {
+    if (points) {
+      const int row = bi / W, col = bi - row * W;
+      points[frame * 2] = (float)col / (float)W;
+      points[frame * 2 + 1] = (float)row / (float)H;
+    }
+    if (peak) peak[frame] = pmax;
+  }
+}
+
+template <int NCH>
+void launch_decode(bool vec, unsigned nframes, hipStream_t stream, const void* logits, int dt, int H, int W, float inv_temp,
+                   float* preds, float* rescaled, float* points, float* peak) {
+  if (vec) hipLaunchKernelGGL((gaze_decode_kernel<NCH, true>), dim3(nframes), dim3(256), 0, stream, logits, dt, H, W, inv_temp, preds,
+                              rescaled, points, peak);
+  else hipLaunchKernelGGL((gaze_decode_kernel<NCH, false>), dim3(nframes), dim3(256), 0, stream, logits, dt, H, W, inv_temp, preds,
+                          rescaled, points, peak);
+}
+
+}  // namespace
+
+extern "C" int csts_gaze_decode(const void* logits, int dt, int64_t nframes, int H, int W, float temperature, float* preds,
+                                float* rescaled, float* points, float* peak, hipStream_t stream) {
+  CSTS_REQUIRE(logits, "null logits");
+  CSTS_REQUIRE(dt == CSTS_F32 || dt == CSTS_BF16, "logits must be fp32 or the library's 16-bit type");
+  CSTS_REQUIRE(nframes >= 1 && nframes < ((int64_t)1 << 31), "1 <= frames < 2^31");
+  CSTS_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W <= CSTS_GAZE_DECODE_MAX_HW, "1 <= H * W <= CSTS_GAZE_DECODE_MAX_HW (the frame is held in registers)");
+  CSTS_REQUIRE(temperature > 0.f, "temperature must be positive");
+  if (!preds && !rescaled && !points && !peak) return 0;
+  const int hw = H * W;
+  const bool vec = hw % 4 == 0 && aligned16(logits) && aligned16(preds) && aligned16(rescaled);
+  const int nch = (int)cdiv(hw, 1024);
+  static_assert(DEC_MAX_NCH == 8, "the dispatch below covers 1, 2, 4 and 8 chunks per lane");
+  const unsigned n = (unsigned)nframes;
+  const float it = 1.f / temperature;
+  if (nch <= 1) launch_decode<1>(vec, n, stream, logits, dt, H, W, it, preds, rescaled, points, peak);
+  else if (nch <= 2) launch_decode<2>(vec, n, stream, logits, dt, H, W, it, preds, rescaled, points, peak);
+  else if (nch <= 4) launch_decode<4>(vec, n, stream, logits, dt, H, W, it, preds, rescaled, points, peak);
+  else launch_decode<8>(vec, n, stream, logits, dt, H, W, it, preds, rescaled, points, peak);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}

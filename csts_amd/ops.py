@@ -2589,3 +2589,35 @@ def sim_matrix(a, b, eps=1e-8):
 
 def egonce(sim, temperature=0.05):
     return EgoNCEFn.apply(sim, float(temperature))
+
+
+# ----------------------------------------------------------------------------------------- inference head
+_DECODE_OUTPUTS = ("preds", "rescaled", "points", "peak")
+
+
+def gaze_decode(logits, temperature=2.0, want=_DECODE_OUTPUTS):
+    """csts_gaze_decode on the (B, 1, T, H, W) model output (fp32 or the library's 16-bit type): one read of each frame's logits
+    gives preds = frame_softmax(logits, temperature) and rescaled = its per-frame min-max rescale (tools/test_avgaze_net.py:68-70),
+    both fp32 shaped like logits, points (B, T, 2) = (x, y) of the frame's maximum in [0, 1) and peak (B, T) = its probability.
+    Returns a dict of the outputs named in `want`; the others are not computed.  Inference only: raises when the logits
+    carry a gradient.  No host sync: it can be captured in a graph."""
+    _need_gpu(logits)
+    if logits.requires_grad and torch.is_grad_enabled():
+        raise L.CstsError("gaze_decode is the inference head: it has no backward (call it under torch.no_grad(), or use "
+                          "frame_softmax for a differentiable heat map)")
+    want = tuple(want)
+    unknown = [k for k in want if k not in _DECODE_OUTPUTS]
+    if unknown or not want:
+        raise ValueError(f"want must name some of {_DECODE_OUTPUTS}, got {want}")
+    if logits.dim() != 5 or logits.shape[1] != 1:
+        raise ValueError(f"logits must be (B, 1, T, H, W), got {tuple(logits.shape)}")
+    x = logits.detach().contiguous()
+    B, _, T, H, W = x.shape
+    dev = x.device
+    out = {}
+    for k, shape in (("preds", x.shape), ("rescaled", x.shape), ("points", (B, T, 2)), ("peak", (B, T))):
+        if k in want:
+            out[k] = torch.empty(shape, dtype=torch.float32, device=dev)
+    L.check(_lib().csts_gaze_decode(_p(x), _dt(x), B * T, H, W, float(temperature), _p(out.get("preds")), _p(out.get("rescaled")),
+                                    _p(out.get("points")), _p(out.get("peak")), _stream()), "csts_gaze_decode")
+    return out

@@ -35,7 +35,7 @@ enum { CSTS_MASK_NONE = 0, CSTS_MASK_SPATIAL = 1 };
  * (2: csts_gemm_args.res_up; 3: compact k|v rows, 16-bit build, loss scaler in csts_opt_args; 4: csts_opt_args.extra_sq, factored AdamW; 5: grouped stencil weight gradients; 6: csts_copy_token_segments, csts_wgrad_grouped8_limited; 7: csts_wgrad_grouped5, csts_gemm algo 500; 8: csts_opt_rule, csts_opt_step, csts_opt_factored_step, csts_opt_factored.tensor replaces pad_).  csts_abi_version() returns the value the
  * LIBRARY was built with: a caller must compare it with the CSTS_ABI_VERSION it was compiled against and refuse a mismatch
  * (the Python binding does, csts_amd/lib.py::load). */
-#define CSTS_ABI_VERSION 8
+#define CSTS_ABI_VERSION 9
 const char* csts_last_error(void);
 int csts_abi_version(void);
 int csts_half_kind(void);   /* the 16-bit type behind CSTS_BF16 in THIS library: 0 bfloat16 (libcsts_hip.so), 1 IEEE half (libcsts_hip_f16.so) */
@@ -535,6 +535,25 @@ int csts_spatial_rule_host(const double* labels, int B, int T, int L, int H, int
                            int spatial_idx, int random_flip, int inv_uniform, const double* uniforms, int* params,
                            double* labels_out);
 int csts_spatial_uniforms_host(uint32_t key0, uint32_t key1, uint64_t first, int64_t count, double* out);
+
+/* ---- gaze head of the inference path (csts_amd/csrc/decode.hip): one read of a frame's logits gives every consumer of a
+ *      prediction what it needs.  logits: nframes = B * T frames of H * W cells each, the (B, 1, T, H, W) model output, fp32
+ *      (dt CSTS_F32) or the 16-bit type of the library (dt CSTS_BF16); arithmetic is fp32 in both libraries.  Rule, per frame,
+ *      with z[i] = logits[i] * (1 / temperature) (temperature > 0; 2 on this path):
+ *        preds[i]    = exp(z[i] - max z) / sum_j exp(z[j] - max z)          frame_softmax, slowfast/utils/utils.py:5-12
+ *        rescaled[i] = (preds[i] - min preds) / (max preds - min preds + 1e-6)   tools/test_avgaze_net.py:68-70
+ *        i*          = the lowest flat index whose logit is the frame's maximum (the softmax is monotone, so this is the
+ *                      maximum of the heat map; comparing logits keeps two cells apart whose probabilities round alike)
+ *        points      = {(i* mod W) / W, (i* div W) / H}: x then y in [0, 1), the inverse of the centre rule mu_x = round(x W),
+ *                      mu_y = round(y H) of _get_gaussian_map (ego4d_avgaze_forecast.py:404-407)
+ *        peak        = preds[i*]
+ *      Outputs fp32: preds and rescaled [nframes][H * W], points [nframes][2], peak [nframes]; each may be NULL and is then
+ *      skipped.  One workgroup per frame holds the frame in registers, so H * W <= CSTS_GAZE_DECODE_MAX_HW (32 values per lane
+ *      of 256); nframes >= 1.  128-bit accesses when H * W is a multiple of 4 and logits, preds and rescaled are 16-byte
+ *      aligned, scalar ones otherwise.  One launch; no allocation, no synchronisation, no host read: graph-capturable. */
+#define CSTS_GAZE_DECODE_MAX_HW 8192
+int csts_gaze_decode(const void* logits, int dt, int64_t nframes, int H, int W, float temperature, float* preds, float* rescaled,
+                     float* points, float* peak, hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,71 @@
+#!/usr/bin/env python3
+"""Gaze predictions of trained weights for one clip (one process, one GPU):
+
+    python tools/predict.py --cfg configs/Ego4D/CSTS_Ego4D_Gaze_Forecast.yaml --checkpoint checkpoint_epoch_00015.pyth \
+        --clip clip.npz --out gaze.npz [KEY VALUE ...]
+
+--clip: an .npz with frames_u8 uint8 (B, T, H, W, 3), wav fp32 (B, n) at 24 kHz, frames_idx (B, T) and frame_length (scalar), the
+arguments of csts_amd.GazePredictor.predict.  Without it a synthetic batch (train.synthetic_batch, --seed) stands in.
+--checkpoint: a .pyth file; without it TEST.CHECKPOINT_FILE_PATH of the configuration is used, and with that empty the weights
+are the random initialisation.  --out receives points (B, T, 2), peak (B, T), heatmaps and rescaled (B, T, S/4, S/4) as numpy
+arrays; one json_stats line reports their shapes and the checkpoint path."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from csts_amd.config import assert_and_infer_cfg, load_yaml      # noqa: E402
+from csts_amd.infer import GazePredictor                         # noqa: E402
+
+CLIP_KEYS = ("frames_u8", "wav", "frames_idx", "frame_length")
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="CSTS (MI355X) gaze prediction.")
+    p.add_argument("--cfg", dest="cfg_file", default=os.path.join(ROOT, "configs/Ego4D/CSTS_Ego4D_Gaze_Forecast.yaml"), type=str)
+    p.add_argument("--checkpoint", default=None, type=str, help=".pyth file (default: TEST.CHECKPOINT_FILE_PATH)")
+    p.add_argument("--clip", default=None, type=str, help=".npz with " + ", ".join(CLIP_KEYS))
+    p.add_argument("--seed", default=2000, type=int, help="seed of the synthetic batch used without --clip")
+    p.add_argument("--batch", default=2, type=int, help="clips in the synthetic batch used without --clip")
+    p.add_argument("--no-graph", action="store_true", help="launch the kernels eagerly instead of replaying a HIP graph")
+    p.add_argument("--out", required=True, type=str, help=".npz to write")
+    p.add_argument("opts", default=None, nargs=argparse.REMAINDER, help="KEY VALUE overrides")
+    return p.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    cfg = assert_and_infer_cfg(load_yaml(args.cfg_file, ["NUM_GPUS", 1] + list(args.opts or [])))
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/predict.py needs an MI355X: there is no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    torch.manual_seed(cfg.RNG_SEED)
+    predictor = GazePredictor(cfg, args.checkpoint, device=dev, graph=not args.no_graph)
+    if args.clip is not None:
+        with np.load(args.clip) as z:
+            missing = [k for k in CLIP_KEYS if k not in z.files]
+            if missing:
+                raise SystemExit(f"{args.clip} lacks {missing}: a clip holds {list(CLIP_KEYS)}")
+            out = predictor.predict(torch.from_numpy(z["frames_u8"]).to(dev), torch.from_numpy(z["wav"]).float().to(dev),
+                                    torch.from_numpy(z["frames_idx"]).float().to(dev), float(z["frame_length"]))
+        source = args.clip
+    else:
+        from csts_amd import train as T
+        batch = T.synthetic_batch(args.batch, cfg.DATA.NUM_FRAMES, cfg.DATA.TEST_CROP_SIZE, args.seed, dev,
+                                  spatial=T.spatial_config(cfg, train=False))
+        out = predictor.predict_batch(batch)
+        source = f"synthetic_batch(seed={args.seed})"
+    arrays = {k: out[k].cpu().numpy() for k in ("points", "peak", "rescaled", "heatmaps")}
+    np.savez(args.out, **arrays)
+    print("json_stats: " + json.dumps({"_type": "predict", "checkpoint": predictor.checkpoint_path, "source": source,
+                                       "graph": predictor.graph, "out": args.out,
+                                       "shapes": {k: list(v.shape) for k, v in arrays.items()}}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
