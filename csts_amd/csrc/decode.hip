@@ -4,6 +4,11 @@
 // _get_gaussian_map (ego4d_avgaze_forecast.py:404-407) and the peak probability.  include/csts_hip.h states the rule.
 // One workgroup of 256 lanes per frame; the frame stays in registers (NCH x 4 values per lane) between the three reductions
 // (max + arg-max together, exp-sum, min) and the writes, so the logits are read once and nothing is re-read from memory.
+//
+// gaze_track: the per-frame track of a whole video from the per-window heat maps above.  Windows that overlap predict the same
+// video frame several times; the track is the mean heat map per frame, decoded again (rescale, arg-max point, peak).  One
+// workgroup per OUTPUT frame walks the list of prediction rows that target it and keeps the running sum in registers in the
+// layout of gaze_decode, so every row is read once, nothing is re-read and no atomics are needed: the sum has one fixed order.
 #include "common.h"
 
 namespace {
@@ -145,6 +150,111 @@ void launch_decode(bool vec, unsigned nframes, hipStream_t stream, const void* l
                           rescaled, points, peak);
 }
 
+// One workgroup per output frame f: order[offsets[f] .. offsets[f + 1]) are its prediction rows, added in that order.
+template <int NCH, bool VEC>
+__global__ __launch_bounds__(256) void gaze_track_kernel(const float* __restrict__ preds, const int* __restrict__ order,
+                                                         const int* __restrict__ offsets, int H, int W,
+                                                         float* __restrict__ heatmaps, float* __restrict__ rescaled,
+                                                         float* __restrict__ points, float* __restrict__ peak,
+                                                         int* __restrict__ count) {
+  __shared__ float red_v[2][4];
+  __shared__ int red_i[4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int hw = H * W;
+  const int64_t frame = blockIdx.x, base = frame * hw;
+  const int beg = offsets[frame], n = offsets[frame + 1] - beg;          // uniform over the workgroup
+  float m[NCH * 4];
+#pragma unroll
+  for (int k = 0; k < NCH * 4; ++k) m[k] = 0.f;
+  for (int j = 0; j < n; ++j) {
+    const float* row = preds + (int64_t)order[beg + j] * hw;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      if (VEC) {
+        const int at = (c * 256 + tid) * 4;
+        if (at < hw) {                  // hw % 4 == 0 on this path: a chunk is inside the frame or outside it
+          const f32x4 v = *reinterpret_cast<const f32x4*>(row + at);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) m[c * 4 + r] += v[r];
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int at = cell_of<false>(c, r, tid);
+          if (at < hw) m[c * 4 + r] += row[at];
+        }
+      }
+    }
+  }
+  const float inv = n > 0 ? 1.f / (float)n : 0.f;
+  // ---- the mean map, its max + arg-max (a lane walks its cells in ascending index order) and its min
+  float bv = -INFINITY, mn = INFINITY;
+  int bi = 0x7fffffff;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int at = cell_of<VEC>(c, r, tid);
+      m[c * 4 + r] *= inv;
+      if (at < hw) {
+        take_max(bv, bi, m[c * 4 + r], at);
+        mn = fminf(mn, m[c * 4 + r]);
+      }
+    }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) take_max(bv, bi, __shfl_xor(bv, o, 64), __shfl_xor(bi, o, 64));
+  mn = -wave_max(-mn);
+  if (lane == 0) { red_v[0][w] = bv; red_i[w] = bi; red_v[1][w] = mn; }
+  __syncthreads();
+  bv = red_v[0][0]; bi = red_i[0];
+#pragma unroll
+  for (int k = 1; k < 4; ++k) take_max(bv, bi, red_v[0][k], red_i[k]);
+  if (bi >= hw) bi = 0;                 // a frame without a comparable value (all NaN): still a cell of the frame
+  mn = fminf(fminf(red_v[1][0], red_v[1][1]), fminf(red_v[1][2], red_v[1][3]));
+  const float denom = bv - mn + 1e-6f;
+  // ---- writes (an uncovered frame: m = 0 everywhere, so the maps below are 0)
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    if (VEC) {
+      const int at = (c * 256 + tid) * 4;
+      if (at < hw) {
+        f32x4 p, q;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { p[r] = m[c * 4 + r]; q[r] = (p[r] - mn) / denom; }
+        if (heatmaps) *reinterpret_cast<f32x4*>(heatmaps + base + at) = p;
+        if (rescaled) *reinterpret_cast<f32x4*>(rescaled + base + at) = q;
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int at = cell_of<false>(c, r, tid);
+        if (at < hw) {
+          if (heatmaps) heatmaps[base + at] = m[c * 4 + r];
+          if (rescaled) rescaled[base + at] = (m[c * 4 + r] - mn) / denom;
+        }
+      }
+    }
+  }
+  if (tid == 0) {
+    if (points) {
+      const int row = bi / W, col = bi - row * W;
+      points[frame * 2] = n > 0 ? (float)col / (float)W : __builtin_nanf("");
+      points[frame * 2 + 1] = n > 0 ? (float)row / (float)H : __builtin_nanf("");
+    }
+    if (peak) peak[frame] = n > 0 ? bv : 0.f;
+    if (count) count[frame] = n;
+  }
+}
+
+template <int NCH>
+void launch_track(bool vec, unsigned nframes, hipStream_t stream, const float* preds, const int* order, const int* offsets, int H,
+                  int W, float* heatmaps, float* rescaled, float* points, float* peak, int* count) {
+  if (vec) hipLaunchKernelGGL((gaze_track_kernel<NCH, true>), dim3(nframes), dim3(256), 0, stream, preds, order, offsets, H, W,
+                              heatmaps, rescaled, points, peak, count);
+  else hipLaunchKernelGGL((gaze_track_kernel<NCH, false>), dim3(nframes), dim3(256), 0, stream, preds, order, offsets, H, W,
+                          heatmaps, rescaled, points, peak, count);
+}
+
 }  // namespace
 
 extern "C" int csts_gaze_decode(const void* logits, int dt, int64_t nframes, int H, int W, float temperature, float* preds,
@@ -165,6 +275,24 @@ extern "C" int csts_gaze_decode(const void* logits, int dt, int64_t nframes, int
   else if (nch <= 2) launch_decode<2>(vec, n, stream, logits, dt, H, W, it, preds, rescaled, points, peak);
   else if (nch <= 4) launch_decode<4>(vec, n, stream, logits, dt, H, W, it, preds, rescaled, points, peak);
   else launch_decode<8>(vec, n, stream, logits, dt, H, W, it, preds, rescaled, points, peak);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_gaze_track(const float* preds, const int* order, const int* offsets, int64_t F, int H, int W, float* heatmaps,
+                               float* rescaled, float* points, float* peak, int* count, hipStream_t stream) {
+  CSTS_REQUIRE(preds && order && offsets, "null preds, order or offsets");
+  CSTS_REQUIRE(F >= 1 && F < ((int64_t)1 << 31), "1 <= frames < 2^31");
+  CSTS_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W <= CSTS_GAZE_DECODE_MAX_HW, "1 <= H * W <= CSTS_GAZE_DECODE_MAX_HW (the frame is held in registers)");
+  if (!heatmaps && !rescaled && !points && !peak && !count) return 0;
+  const int hw = H * W;
+  const bool vec = hw % 4 == 0 && aligned16(preds) && aligned16(heatmaps) && aligned16(rescaled);
+  const int nch = (int)cdiv(hw, 1024);
+  const unsigned n = (unsigned)F;
+  if (nch <= 1) launch_track<1>(vec, n, stream, preds, order, offsets, H, W, heatmaps, rescaled, points, peak, count);
+  else if (nch <= 2) launch_track<2>(vec, n, stream, preds, order, offsets, H, W, heatmaps, rescaled, points, peak, count);
+  else if (nch <= 4) launch_track<4>(vec, n, stream, preds, order, offsets, H, W, heatmaps, rescaled, points, peak, count);
+  else launch_track<8>(vec, n, stream, preds, order, offsets, H, W, heatmaps, rescaled, points, peak, count);
   CSTS_LAUNCH_CHECK();
   return 0;
 }

@@ -12,6 +12,10 @@
 // align_corners=False, no antialias) + crop + flip + (x/255 - mean)/std.  A wave owns one output row: it stages the span of
 // the two source rows that row reads in LDS with 16-byte loads, then each lane forms 4 consecutive pixels of every channel
 // plane and stores them as one float4 per plane (the output writes are the dominant traffic).
+//
+// clip_sample: the same pass with an index table in front of it.  The clips are windows of ONE resident video (N, H, W, 3):
+// frame t of clip b is video[clamp(frames_idx[b][t], 0, N - 1)], read on the device, so overlapping windows are sampled straight
+// out of the video without first being gathered into a (B, T, H, W, 3) tensor of their own.
 #include "common.h"
 #include "philox.h"
 
@@ -139,10 +143,13 @@ __global__ __launch_bounds__(64) void spatial_params_kernel(const uint64_t* __re
   spatial_rule(labels + off, a, u, params + 5 * b, out + off, g);
 }
 
-// grid (ceil(S / 4), T, B), 256 threads; dynamic LDS: 4 waves x 2 source rows x rowcap bytes
-__global__ __launch_bounds__(256) void spatial_sample_kernel(const uint8_t* __restrict__ src, const int* __restrict__ params,
-                                                             float* __restrict__ out, int T, int H, int W, int S, int64_t src_bytes,
-                                                             int rowcap, float3 mean, float3 inv_std) {
+// grid (ceil(S / 4), T, B), 256 threads; dynamic LDS: 4 waves x 2 source rows x rowcap bytes.
+// INDEXED: src is a video of nsrc frames and frames_idx [B][T] names the frame of each (b, t); otherwise frame (b, t) is b * T + t.
+template <bool INDEXED>
+__global__ __launch_bounds__(256) void spatial_sample_kernel(const uint8_t* __restrict__ src, const int* __restrict__ frames_idx,
+                                                             int64_t nsrc, const int* __restrict__ params, float* __restrict__ out,
+                                                             int T, int H, int W, int S, int64_t src_bytes, int rowcap, float3 mean,
+                                                             float3 inv_std) {
   extern __shared__ __align__(16) uint8_t lds[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int i = blockIdx.x * SAMPLE_ROWS + wv;                 // output row of this wave
@@ -166,9 +173,13 @@ __global__ __launch_bounds__(256) void spatial_sample_kernel(const uint8_t* __re
   const int xlo = min((int)fmaxf(((float)x0 + 0.5f) * sx - 0.5f, 0.f), W - 1);
   const int xhi = min((int)fmaxf(((float)(x0 + S - 1) + 0.5f) * sx - 0.5f, 0.f) + 1, W - 1);
   uint8_t* rows = lds + wv * 2 * rowcap;
+  // the source frame: a frame of H * W * 3 bytes starts at any byte, so the 16-byte chunks below are laid out from the byte
+  // offset in src (16-byte aligned itself), never from the offset inside the frame
+  int64_t frame = (int64_t)b * T + t;
+  if (INDEXED) frame = min(max((int64_t)frames_idx[frame], (int64_t)0), nsrc - 1);     // as temporal_sampling clamps
   int shift[2];
   for (int r = 0; r < 2; ++r) {
-    const int64_t row0 = (((int64_t)b * T + t) * H + (r ? yb : ya)) * W * 3;
+    const int64_t row0 = (frame * H + (r ? yb : ya)) * W * 3;
     const int64_t beg = row0 + (int64_t)xlo * 3, end = row0 + (int64_t)(xhi + 1) * 3;
     const int64_t a0 = beg & ~(int64_t)15, nbytes = ((end + 15) & ~(int64_t)15) - a0;    // <= 3 W + 30 <= rowcap
     shift[r] = (int)(beg - a0);
@@ -232,6 +243,22 @@ SpatialRule make_rule(int T, int L, int H, int W, int S, int min_scale, int max_
   return SpatialRule{T, L, H, W, S, min_scale, max_scale, spatial_idx, random_flip ? 1 : 0, inv_uniform ? 1 : 0};
 }
 
+// the one launch behind csts_spatial_sample (frames_idx NULL: nsrc = B * T frames in clip order) and csts_clip_sample
+template <bool INDEXED>
+int launch_sample(const uint8_t* src, const int* frames_idx, int64_t nsrc, const int* params, float* out, int B, int T, int H, int W,
+                  int S, const float mean[3], const float std[3], hipStream_t stream) {
+  const int rowcap = (3 * W + 30 + 15) / 16 * 16;
+  const int lds = SAMPLE_ROWS * 2 * rowcap;
+  if (lds > 65536)
+    CSTS_REQUIRE(csts_dyn_lds_optin(reinterpret_cast<const void*>(&spatial_sample_kernel<INDEXED>), lds), "LDS opt-in");
+  const float3 m = make_float3(mean[0], mean[1], mean[2]), is = make_float3(1.f / std[0], 1.f / std[1], 1.f / std[2]);
+  const int64_t src_bytes = nsrc * H * W * 3;
+  hipLaunchKernelGGL(spatial_sample_kernel<INDEXED>, dim3((unsigned)cdiv(S, SAMPLE_ROWS), T, B), dim3(256), lds, stream, src,
+                     frames_idx, nsrc, params, out, T, H, W, S, src_bytes, rowcap, m, is);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int csts_spatial_params(const uint64_t* key, const double* labels, int B, int T, int L, int H, int W, int S, int min_scale,
@@ -251,15 +278,16 @@ extern "C" int csts_spatial_sample(const uint8_t* frames_thwc, const int* params
   CSTS_REQUIRE(B > 0 && T > 0 && H > 0 && W > 0 && S > 0 && S <= 4096 && W <= 6000 && B <= 65535 && T <= 65535,
                "bad sizes (W <= 6000, S <= 4096)");
   CSTS_REQUIRE(aligned16(frames_thwc) && aligned16(out), "frames and output must be 16-byte aligned");
-  const int rowcap = (3 * W + 30 + 15) / 16 * 16;
-  const int lds = SAMPLE_ROWS * 2 * rowcap;
-  if (lds > 65536) CSTS_REQUIRE(csts_dyn_lds_optin(reinterpret_cast<const void*>(&spatial_sample_kernel), lds), "LDS opt-in");
-  const float3 m = make_float3(mean[0], mean[1], mean[2]), is = make_float3(1.f / std[0], 1.f / std[1], 1.f / std[2]);
-  const int64_t src_bytes = (int64_t)B * T * H * W * 3;
-  hipLaunchKernelGGL(spatial_sample_kernel, dim3((unsigned)cdiv(S, SAMPLE_ROWS), T, B), dim3(256), lds, stream, frames_thwc, params,
-                     out, T, H, W, S, src_bytes, rowcap, m, is);
-  CSTS_LAUNCH_CHECK();
-  return 0;
+  return launch_sample<false>(frames_thwc, nullptr, (int64_t)B * T, params, out, B, T, H, W, S, mean, std, stream);
+}
+
+extern "C" int csts_clip_sample(const uint8_t* video_nhwc, int64_t N, const int* frames_idx, const int* params, float* out, int B,
+                                int T, int H, int W, int S, const float mean[3], const float std[3], hipStream_t stream) {
+  CSTS_REQUIRE(video_nhwc && frames_idx && params && out && mean && std, "bad args");
+  CSTS_REQUIRE(N >= 1 && B > 0 && T > 0 && T <= SPATIAL_MAX_T && H > 0 && W > 0 && S > 0 && S <= 4096 && W <= 6000 && B <= 65535,
+               "bad sizes (N >= 1, T <= 64, W <= 6000, S <= 4096)");
+  CSTS_REQUIRE(aligned16(video_nhwc) && aligned16(out), "video and output must be 16-byte aligned");
+  return launch_sample<true>(video_nhwc, frames_idx, N, params, out, B, T, H, W, S, mean, std, stream);
 }
 
 extern "C" int csts_spatial_rule_host(const double* labels, int B, int T, int L, int H, int W, int S, int min_scale, int max_scale,

@@ -15,6 +15,81 @@ from . import lib as L
 from . import ops
 
 TEMPERATURE = 2.0          # frame_softmax temperature of the train / val / test drivers of the reference
+AUDIO_WIDTH = 256          # spectrogram columns per audio window (ego4d_avgaze_forecast.py:218-219)
+
+
+def plan_video(cfg, n_frames, fps=None, stride=None, segment=None, cols=None):
+    """The windows predict_video cuts a recording of n_frames frames into, on the host (numpy arrays).
+
+    A window is one clip of the dataset cfg.TEST.DATASET names: `segment` frames from its origin o_w = w * stride, of which
+    the first `observed` are seen.  Its T input frames follow the reference's temporal rule on the observed part
+    (inputs.temporal_indices) and its T predictions target
+      forecast, not aria: 150 / 86 frames, inputs clip 1 of TEST.NUM_ENSEMBLE_VIEWS, targets linspace(86, 149, T)
+                          (ego4d_avgaze_forecast.py:197,234-235);
+      forecast and aria:  100 / 60 frames, same inputs, targets linspace(60 + rate, 99, T) (aria_avgaze_forecast.py:192,230-231);
+      estimation:         round(5 fps) frames, all observed, inputs clip 0, targets = the input frames (ego4d_avgaze.py:263-267),
+    all local to the origin.  Default stride: segment - observed (forecast: the predicted spans tile the video) or
+    ceil(clip size) (estimation).  `segment` overrides the table; the forecast rows then scale observed and the targets by
+    segment / table segment, floored.  windows = floor((n_frames - observed) / stride) + 1; fewer than `observed` frames is an
+    error.  Targets >= n_frames stay in the plan (gaze_track drops them).  fps defaults to DATA.TARGET_FPS.
+
+    cols (optional): the columns of ONE spectrogram of the whole waveform.  The plan then holds the audio window centres by the
+    rule of ego4d_avgaze_forecast.py:215-219 applied to the window's slice [c0, c1) = [floor(o cols / n), floor((o + observed)
+    cols / n)): centre = c0 + round(local / observed * (c1 - c0)) clipped to [c0 + 128, c1 - 1 - 128]; a slice narrower than
+    257 columns is an error.
+
+    Returns {"windows", "segment", "observed", "stride", "clip_size", "origins" (windows,), "inputs" and "targets" (T,) local,
+    "frames_idx" int32 and "target_idx" int64 (windows, T) absolute [, "audio_centers" int32 (windows, T)]}."""
+    import math
+    import numpy as np
+    from .inputs import temporal_indices
+    n_frames = int(n_frames)
+    T, rate, target_fps = int(cfg.DATA.NUM_FRAMES), int(cfg.DATA.SAMPLING_RATE), cfg.DATA.TARGET_FPS
+    fps = target_fps if fps is None else fps
+    views = int(cfg.TEST.NUM_ENSEMBLE_VIEWS)
+    name = str(cfg.TEST.DATASET).lower()
+    clip_size = ((rate + 1) * (T - 1) + 1) / target_fps * fps
+    if "forecast" in name:
+        seg0, obs0, first0 = (100, 60, 60 + rate) if "aria" in name else (150, 86, 86)
+        seg = seg0 if segment is None else int(segment)
+        if seg < 1:
+            raise ValueError(f"segment must be positive, got {segment}")
+        observed = obs0 * seg // seg0
+        if observed < 1 or observed >= seg:
+            raise ValueError(f"a segment of {seg} frames leaves no observed / predicted part ({observed} observed)")
+        targets = np.linspace(first0, seg0 - 1, T).astype(np.int64) * seg // seg0
+        _, _, inputs_local = temporal_indices(observed, T, rate, 1, views, target_fps=target_fps, fps=fps)
+        default_stride = seg - observed
+    else:
+        seg = int(round(5 * fps)) if segment is None else int(segment)
+        if seg < 1:
+            raise ValueError(f"segment must be positive, got {segment}")
+        observed = seg
+        _, _, inputs_local = temporal_indices(seg, T, rate, 0, views, target_fps=target_fps, fps=fps)
+        targets = inputs_local.copy()
+        default_stride = int(math.ceil(clip_size))
+    stride = default_stride if stride is None else int(stride)
+    if stride < 1:
+        raise ValueError(f"stride must be positive, got {stride}")
+    if n_frames < observed:
+        raise ValueError(f"the video has {n_frames} frames, one window observes {observed}")
+    windows = (n_frames - observed) // stride + 1
+    origins = np.arange(windows, dtype=np.int64) * stride
+    plan = {"windows": windows, "segment": seg, "observed": observed, "stride": stride, "clip_size": clip_size,
+            "origins": origins, "inputs": inputs_local.astype(np.int64), "targets": targets.astype(np.int64),
+            "frames_idx": (origins[:, None] + inputs_local[None, :]).astype(np.int32),
+            "target_idx": (origins[:, None] + targets[None, :]).astype(np.int64)}
+    if cols is not None:
+        cols = int(cols)
+        c0 = origins * cols // n_frames
+        c1 = (origins + observed) * cols // n_frames
+        if int((c1 - c0).min()) < AUDIO_WIDTH + 1:
+            raise ValueError(f"the spectrogram slice of a window has {int((c1 - c0).min())} columns ({cols} for {n_frames} frames), "
+                             f"an audio window needs {AUDIO_WIDTH + 1}")
+        centers = c0[:, None] + np.rint(inputs_local[None, :].astype(np.float64) / observed * (c1 - c0)[:, None]).astype(np.int64)
+        half = AUDIO_WIDTH // 2
+        plan["audio_centers"] = np.clip(centers, (c0 + half)[:, None], (c1 - 1 - half)[:, None]).astype(np.int32)
+    return plan
 
 
 def _core(model):
@@ -172,3 +247,65 @@ class GazePredictor:
                 out = eval_forward(self.model, video.contiguous(), audio.contiguous())
         return {"points": out["points"], "peak": out["peak"], "heatmaps": out["preds"].squeeze(1),
                 "rescaled": out["rescaled"].squeeze(1)}
+
+    @torch.no_grad()
+    def predict_video(self, frames_u8, wav, fps=None, stride=None, batch=None, return_heatmaps=True):
+        """A whole recording in, one gaze track out: frames_u8 uint8 (N, H, W, 3) and wav fp32 (n,) at 24 kHz, both resident on
+        the device -> {"points": (N, 2), "peak": (N,), "count": (N,) int32 = windows that predicted the frame, "heatmaps" and
+        "rescaled": (N, S/4, S/4) (left out with return_heatmaps=False), "windows": their number}, on the device.
+
+        The windows are plan_video's (stride in frames; fps defaults to DATA.TARGET_FPS).  One log-power STFT of the whole
+        waveform serves every window; each batch of `batch` windows (default min(TEST.BATCH_SIZE, 8)) is sampled straight out
+        of the video (inputs.clip_sample under one row of test-mode spatial parameters: short side to S, centre crop; S x S
+        sources are normalised as they are), gets its audio windows (inputs.audio_windows_at) and runs predict_batch.  The last
+        batch is filled up by repeating its last window, so one graph shape serves the video; the repeats are dropped.  The
+        windows * T heat maps are averaged per video frame and decoded again by ops.gaze_track; frames no window predicts have
+        count 0, NaN points and zero maps."""
+        for t in (frames_u8, wav):
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
+        from . import inputs
+        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
+            raise ValueError(f"frames must be uint8 (N, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
+        if wav.dim() != 1 or not wav.is_floating_point():
+            raise ValueError(f"wav must be a floating (n,) waveform, got {tuple(wav.shape)} {wav.dtype}")
+        N, H, W, _ = frames_u8.shape
+        cfg = self.cfg
+        S = int(cfg.DATA.TEST_CROP_SIZE)
+        T = int(cfg.DATA.NUM_FRAMES)
+        mean, std = tuple(cfg.DATA.MEAN), tuple(cfg.DATA.STD)
+        nb = min(int(cfg.TEST.BATCH_SIZE), 8) if batch is None else int(batch)
+        if nb < 1:
+            raise ValueError(f"batch must be positive, got {batch}")
+        with torch.cuda.device(self.device):
+            dev = frames_u8.device
+            spec = inputs.stft_logpower(wav[None])
+            plan = plan_video(cfg, N, fps=fps, stride=stride, cols=spec.shape[2])
+            nwin = plan["windows"]
+            if (H, W) == (S, S):
+                row = [[S, S, 0, 0, 0]]                       # identity: bit-equal to normalize_frames
+            else:
+                import numpy as np
+                row = inputs.spatial_rule_host(np.zeros((1, T, 2)), H, W, S, train=False, spatial_idx=1)[0].tolist()
+            params = torch.tensor(row, dtype=torch.int32, device=dev).repeat(nb, 1)
+            frames_idx = torch.from_numpy(plan["frames_idx"]).to(dev)
+            centers = torch.from_numpy(plan["audio_centers"]).to(dev)
+            o = (AUDIO_WIDTH - S) // 2
+            preds = torch.empty(nwin * T, S // 4, S // 4, dtype=torch.float32, device=dev)
+            for w0 in range(0, nwin, nb):
+                n = min(nb, nwin - w0)
+                sel = slice(w0, w0 + n)
+                idx, cen = frames_idx[sel], centers[sel]
+                if n < nb:                                    # pad by repeating the last window: one graph shape per video
+                    idx = torch.cat([idx, idx[-1:].expand(nb - n, T)])
+                    cen = torch.cat([cen, cen[-1:].expand(nb - n, T)])
+                video = inputs.clip_sample(frames_u8, idx, params, S, mean=mean, std=std)
+                audio = inputs.audio_windows_at(spec, cen, AUDIO_WIDTH)
+                if S != AUDIO_WIDTH:   # S frequency bins x S columns around each frame, as predict() cuts them
+                    audio = audio[:, :, :, :S, o:o + S].contiguous()
+                out = self.predict_batch({"video": video, "audio": audio})
+                preds[w0 * T:(w0 + n) * T] = out["heatmaps"][:n].reshape(n * T, S // 4, S // 4)
+            want = ("points", "peak", "count") + (("heatmaps", "rescaled") if return_heatmaps else ())
+            track = ops.gaze_track(preds, torch.from_numpy(plan["target_idx"].reshape(-1)).to(dev), N, want=want)
+        track["windows"] = nwin
+        return track

@@ -61,6 +61,58 @@ def audio_windows(spec: torch.Tensor, frames_idx: torch.Tensor, frame_length: fl
     return out
 
 
+def audio_windows_at(spec: torch.Tensor, centers: torch.Tensor, width: int = 256) -> torch.Tensor:
+    """Windows of ONE spectrogram at given centre columns: spec (nbins, cols) or (1, nbins, cols) + centers int (B, T) ->
+    (B, 1, T, nbins, width), window (b, t) = spec[:, c - width/2 : c + width/2] (csts_audio_windows).  For clips that are windows
+    of one recording and share its spectrogram (infer.plan_video works the centres out); centres are kept inside
+    [width/2, cols - 1 - width/2] as audio_windows keeps them."""
+    _gpu(spec, centers)
+    if spec.dim() == 3 and spec.shape[0] == 1:
+        spec = spec[0]
+    if spec.dim() != 2 or centers.dim() != 2 or centers.is_floating_point():
+        raise ValueError(f"spec must be (nbins, cols) and centers integer (B, T), got {tuple(spec.shape)} and "
+                         f"{tuple(centers.shape)} {centers.dtype}")
+    nbins, cols = spec.shape
+    B, T = centers.shape
+    if cols < width + 1:
+        raise ValueError(f"the spectrogram has {cols} columns, a window needs {width + 1}")
+    c = centers.to(torch.int32).clamp(width // 2, cols - 1 - width // 2).contiguous()
+    out = torch.empty(B, 1, T, nbins, width, dtype=torch.float32, device=spec.device)
+    # one "clip" of B * T windows: every window reads the same spectrogram
+    L.check(L.load().csts_audio_windows(spec.contiguous().float().data_ptr(), c.data_ptr(), out.data_ptr(), 1, B * T, nbins, cols,
+                                        width, _s()), "csts_audio_windows")
+    return out
+
+
+def temporal_indices(video_size: int, num_frames: int, sampling_rate: int, clip_idx: int, num_clips: int, *, target_fps=30,
+                     fps=30, use_offset: bool = False, u: float = None):
+    """The frames of one clip by the reference's temporal rule, decode-everything path (slowfast/datasets/decoder.py:12-68 and
+    the tail of decode(), :396-411) -> (start, end, index): index int64 (num_frames,) numpy.
+
+    clip_size = ((sampling_rate + 1) * (num_frames - 1) + 1) / target_fps * fps; delta = max(video_size - clip_size, 0);
+    start = delta * clip_idx / num_clips, or with use_offset floor(delta / 2) (num_clips 1) / clip_idx * floor(delta /
+    (num_clips - 1)), or u * delta for clip_idx -1 (random sampling: u in [0, 1) is the variate random.uniform consumed);
+    end = start + clip_size - 1; index = linspace(start, end, num_frames) clamped to [0, video_size - 1] and truncated.  The
+    linspace is torch's, fp32 on the CPU, as in the reference, so fractional positions truncate identically."""
+    import math
+    video_size, num_frames, clip_idx, num_clips = int(video_size), int(num_frames), int(clip_idx), int(num_clips)
+    if video_size < 1 or num_frames < 1 or num_clips < 1:
+        raise ValueError(f"video_size, num_frames and num_clips must be positive, got {video_size}, {num_frames}, {num_clips}")
+    clip_size = ((sampling_rate + 1) * (num_frames - 1) + 1) / target_fps * fps
+    delta = max(video_size - clip_size, 0)
+    if clip_idx == -1:
+        if u is None or not 0.0 <= u < 1.0:
+            raise ValueError(f"clip_idx -1 (random sampling) needs its variate u in [0, 1), got {u}")
+        start = 0 + (delta - 0) * u                     # random.uniform(0, delta)
+    elif use_offset:
+        start = math.floor(delta / 2) if num_clips == 1 else clip_idx * math.floor(delta / (num_clips - 1))
+    else:
+        start = delta * clip_idx / num_clips
+    end = start + clip_size - 1
+    index = torch.clamp(torch.linspace(start, end, num_frames), 0, video_size - 1).long()
+    return start, end, index.numpy()
+
+
 def gaze_heatmaps(labels: torch.Tensor, H: int = 64, W: int = 64, ksize: int = 19) -> torch.Tensor:
     """labels (B, T, >=2) with x, y in [0, 1] -> (B, T, H, W) maps summing to 1 per frame."""
     _gpu(labels)
@@ -147,6 +199,37 @@ def spatial_sample(frames_u8: torch.Tensor, params: torch.Tensor, crop_size: int
     par = params.contiguous()
     L.check(L.load().csts_spatial_sample(x.data_ptr(), par.data_ptr(), out.data_ptr(), B, T, H, W, S, f3(*mean), f3(*std), _s()),
             "csts_spatial_sample")
+    return out
+
+
+def clip_sample(video_u8: torch.Tensor, frames_idx: torch.Tensor, params: torch.Tensor, crop_size: int,
+                mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225)) -> torch.Tensor:
+    """spatial_sample of clips that are windows of ONE resident video, without gathering them first: video uint8 (N, H, W, 3),
+    frames_idx int32 (B, T) frame numbers (clamped to [0, N - 1] on the device, as the reference's temporal_sampling clamps),
+    params int32 (B, 5) -> fp32 (B, 3, T, S, S), bit for bit spatial_sample(video[frames_idx], params, S).  The table is read
+    by the kernel when it runs: no host sync, graph-capturable (csts_clip_sample)."""
+    if video_u8.dtype != torch.uint8 or video_u8.dim() != 4 or video_u8.shape[-1] != 3 or video_u8.shape[0] < 1:
+        raise ValueError(f"video must be uint8 (N >= 1, H, W, 3), got {tuple(video_u8.shape)} {video_u8.dtype}")
+    N, H, W, _ = video_u8.shape
+    if frames_idx.dtype != torch.int32 or frames_idx.dim() != 2:
+        raise ValueError(f"frames_idx must be int32 (B, T), got {tuple(frames_idx.shape)} {frames_idx.dtype}")
+    B, T = frames_idx.shape
+    if not 1 <= T <= 64 or B < 1:
+        raise ValueError(f"clip sampling takes B >= 1 clips of 1 <= T <= 64 frames, got B {B}, T {T}")
+    if params.dtype != torch.int32 or tuple(params.shape) != (B, 5):
+        raise ValueError(f"params must be int32 ({B}, 5), got {tuple(params.shape)} {params.dtype}")
+    S = int(crop_size)
+    if S < 1:
+        raise ValueError(f"crop_size must be positive, got {S}")
+    _gpu(video_u8, frames_idx, params)
+    x = video_u8.contiguous()
+    if x.data_ptr() % 16:
+        x = x.clone()
+    out = torch.empty(B, 3, T, S, S, dtype=torch.float32, device=x.device)
+    f3 = C.c_float * 3
+    idx, par = frames_idx.contiguous(), params.contiguous()
+    L.check(L.load().csts_clip_sample(x.data_ptr(), N, idx.data_ptr(), par.data_ptr(), out.data_ptr(), B, T, H, W, S, f3(*mean),
+                                      f3(*std), _s()), "csts_clip_sample")
     return out
 
 

@@ -252,6 +252,7 @@ SYMBOLS = {
     "csts_gaze_heatmaps": (_I, [vp, _I, vp, i64, _I, _I, _I, vp]),
     "csts_spatial_params": (_I, [vp, vp, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, vp, vp, vp]),
     "csts_spatial_sample": (_I, [vp, vp, vp, _I, _I, _I, _I, _I, C.c_float * 3, C.c_float * 3, vp]),
+    "csts_clip_sample": (_I, [vp, i64, vp, vp, vp, _I, _I, _I, _I, _I, C.c_float * 3, C.c_float * 3, vp]),
     "csts_spatial_rule_host": (_I, [vp, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, vp, vp, vp]),
     "csts_spatial_uniforms_host": (_I, [_U32, _U32, C.c_uint64, i64, vp]),
     "csts_adaptive_f1_workspace": (sz, [i64, _I]),
@@ -262,6 +263,7 @@ SYMBOLS = {
     "csts_gaze_meter_update": (_I, [vp, vp, i64, i64, _I, _I, _I, i64, _I, vp, vp]),
     "csts_gaze_meter_update_host": (_I, [vp, vp, i64, i64, _I, _I, _I, i64, _I, vp]),
     "csts_gaze_decode": (_I, [vp, _I, i64, _I, _I, _F, vp, vp, vp, vp, vp]),
+    "csts_gaze_track": (_I, [vp, vp, vp, i64, _I, _I, vp, vp, vp, vp, vp, vp]),
 }
 
 

@@ -2621,3 +2621,44 @@ def gaze_decode(logits, temperature=2.0, want=_DECODE_OUTPUTS):
     L.check(_lib().csts_gaze_decode(_p(x), _dt(x), B * T, H, W, float(temperature), _p(out.get("preds")), _p(out.get("rescaled")),
                                     _p(out.get("points")), _p(out.get("peak")), _stream()), "csts_gaze_decode")
     return out
+
+
+_TRACK_OUTPUTS = ("heatmaps", "rescaled", "points", "peak", "count")
+
+
+def gaze_track(preds, target_idx, n_frames, want=_TRACK_OUTPUTS):
+    """csts_gaze_track: P per-window heat maps preds (P, H, W) fp32, each predicting video frame target_idx[p] (int64 (P,)), ->
+    one entry per frame of the video: heatmaps (n_frames, H, W) = the mean of the maps that target the frame (added in
+    ascending p), rescaled = its min-max rescale, points (n_frames, 2) and peak (n_frames,) as gaze_decode defines them on
+    that mean, count (n_frames,) int32 = how many maps the frame got.  Frames nobody predicts: maps 0, points NaN, peak 0.
+    Targets outside [0, n_frames) are dropped.  The row lists are built on the device (stable sort by target; the list
+    bounds by a binary search of the sorted targets, which unlike torch.bincount reads nothing back): no host sync."""
+    _need_gpu(preds, target_idx)
+    want = tuple(want)
+    unknown = [k for k in want if k not in _TRACK_OUTPUTS]
+    if unknown or not want:
+        raise ValueError(f"want must name some of {_TRACK_OUTPUTS}, got {want}")
+    if preds.dim() != 3 or preds.dtype != torch.float32:
+        raise ValueError(f"preds must be fp32 (P, H, W), got {tuple(preds.shape)} {preds.dtype}")
+    P, H, W = preds.shape
+    n_frames = int(n_frames)
+    if target_idx.dtype != torch.int64 or tuple(target_idx.shape) != (P,):
+        raise ValueError(f"target_idx must be int64 ({P},), got {tuple(target_idx.shape)} {target_idx.dtype}")
+    if n_frames < 1 or P < 1:
+        raise ValueError(f"gaze_track needs P >= 1 maps and n_frames >= 1, got {P} and {n_frames}")
+    x = preds.detach().contiguous()
+    dev = x.device
+    inside = (target_idx >= 0) & (target_idx < n_frames)
+    bucket = torch.where(inside, target_idx, torch.full_like(target_idx, n_frames))      # n_frames: the discard bucket
+    sorted_t, order = torch.sort(bucket, stable=True)
+    offsets = torch.searchsorted(sorted_t, torch.arange(n_frames + 1, device=dev, dtype=torch.int64)).to(torch.int32)
+    order = order.to(torch.int32)
+    out = {}
+    for k, shape, dt in (("heatmaps", (n_frames, H, W), torch.float32), ("rescaled", (n_frames, H, W), torch.float32),
+                         ("points", (n_frames, 2), torch.float32), ("peak", (n_frames,), torch.float32),
+                         ("count", (n_frames,), torch.int32)):
+        if k in want:
+            out[k] = torch.empty(shape, dtype=dt, device=dev)
+    L.check(_lib().csts_gaze_track(_p(x), _p(order), _p(offsets), n_frames, H, W, _p(out.get("heatmaps")), _p(out.get("rescaled")),
+                                   _p(out.get("points")), _p(out.get("peak")), _p(out.get("count")), _stream()), "csts_gaze_track")
+    return out

@@ -524,6 +524,12 @@ int csts_gaze_heatmaps(const float* labels, int label_stride, float* heatmaps, i
  *        src = max((dst + 0.5) scale - 0.5, 0), i0 = min(floor(src), in - 1), i1 = min(i0 + 1, in - 1), lambda = src - i0.
  *        Unresized clips equal frames_normalize bit for bit.  Params outside the rule's range give a NaN clip.  W <= 6000,
  *        frames and out 16-byte aligned.
+ *      clip_sample: spatial_sample with an index table in front of it, for clips that are windows of ONE resident video
+ *        video_nhwc (N, H, W, 3) uint8, N >= 1: out[b][c][t] is what spatial_sample writes for the frame
+ *        video[min(max(frames_idx[b][t], 0), N - 1)] under params[b] (the clamp of temporal_sampling, decoder.py:26-27), bit
+ *        for bit the result of gathering the frames into (B, T, H, W, 3) first.  frames_idx int32 [B][T] is read on the DEVICE
+ *        when the kernel runs (no host sync, graph-capturable; rewriting the table between replays resamples).  A frame starts
+ *        at byte idx * H * W * 3, at any alignment; only video and out must be 16-byte aligned.  T <= 64, W <= 6000.
  *      spatial_rule_host: the rule on HOST memory from explicit variates uniforms[B][4] (NULL allowed in test mode).
  *      spatial_uniforms_host: u[i][0..3] of clips first .. first + count - 1 (HOST memory). */
 int csts_spatial_params(const uint64_t* key, const double* labels, int B, int T, int L, int H, int W, int S, int min_scale,
@@ -531,6 +537,8 @@ int csts_spatial_params(const uint64_t* key, const double* labels, int B, int T,
                         hipStream_t stream);
 int csts_spatial_sample(const uint8_t* frames_thwc, const int* params, float* out, int B, int T, int H, int W, int S,
                         const float mean[3], const float std[3], hipStream_t stream);
+int csts_clip_sample(const uint8_t* video_nhwc, int64_t N, const int* frames_idx, const int* params, float* out, int B, int T,
+                     int H, int W, int S, const float mean[3], const float std[3], hipStream_t stream);
 int csts_spatial_rule_host(const double* labels, int B, int T, int L, int H, int W, int S, int min_scale, int max_scale,
                            int spatial_idx, int random_flip, int inv_uniform, const double* uniforms, int* params,
                            double* labels_out);
@@ -554,6 +562,24 @@ int csts_spatial_uniforms_host(uint32_t key0, uint32_t key1, uint64_t first, int
 #define CSTS_GAZE_DECODE_MAX_HW 8192
 int csts_gaze_decode(const void* logits, int dt, int64_t nframes, int H, int W, float temperature, float* preds, float* rescaled,
                      float* points, float* peak, hipStream_t stream);
+
+/* ---- gaze track of a whole video (csts_amd/csrc/decode.hip): P heat maps preds [P][H * W] fp32 (the preds of gaze_decode of
+ *      every window), each predicting one video frame, become one map per output frame f in [0, F).
+ *      order[offsets[f] .. offsets[f + 1]) lists the rows of preds that target frame f, in ascending row order (offsets
+ *      int32 [F + 1], non-decreasing, order int32 with values in [0, P); both in DEVICE memory).  Rule, per frame, with
+ *      n = offsets[f + 1] - offsets[f]:
+ *        m        = (((0 + row_0) + row_1) + ... + row_{n-1}) * (1 / n)      fp32, rows added in list order
+ *        heatmaps = m;  rescaled = (m - min m) / (max m - min m + 1e-6)
+ *        i*       = the lowest flat index whose m is the maximum;  points = {(i* mod W) / W, (i* div W) / H};  peak = m[i*]
+ *        count    = n
+ *      exactly as csts_gaze_decode defines rescaled, points and peak, on the mean map.  n == 0 (no window predicts the frame):
+ *      heatmaps and rescaled 0, points NaN, peak 0, count 0.  Outputs: heatmaps and rescaled [F][H * W], points [F][2],
+ *      peak [F] fp32, count [F] int32; each may be NULL and is then skipped.  One workgroup per output frame keeps the sum in
+ *      registers: H * W <= CSTS_GAZE_DECODE_MAX_HW, 1 <= F < 2^31.  No atomics: the result is deterministic.  128-bit accesses
+ *      when H * W is a multiple of 4 and preds, heatmaps and rescaled are 16-byte aligned, scalar ones otherwise.  One launch;
+ *      no allocation, no synchronisation, no host read: graph-capturable. */
+int csts_gaze_track(const float* preds, const int* order, const int* offsets, int64_t F, int H, int W, float* heatmaps,
+                    float* rescaled, float* points, float* peak, int* count, hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Gaze predictions of trained weights for one clip (one process, one GPU):
+"""Gaze predictions of trained weights for one clip or a whole video (one process, one GPU):
 
     python tools/predict.py --cfg configs/Ego4D/CSTS_Ego4D_Gaze_Forecast.yaml --checkpoint checkpoint_epoch_00015.pyth \
         --clip clip.npz --out gaze.npz [KEY VALUE ...]
@@ -8,7 +8,14 @@
 arguments of csts_amd.GazePredictor.predict.  Without it a synthetic batch (train.synthetic_batch, --seed) stands in.
 --checkpoint: a .pyth file; without it TEST.CHECKPOINT_FILE_PATH of the configuration is used, and with that empty the weights
 are the random initialisation.  --out receives points (B, T, 2), peak (B, T), heatmaps and rescaled (B, T, S/4, S/4) as numpy
-arrays; one json_stats line reports their shapes and the checkpoint path."""
+arrays; one json_stats line reports their shapes and the checkpoint path.
+
+    python tools/predict.py --cfg ... --checkpoint ... --video video.npz [--stride k] [--fps f] --out track.npz
+
+--video: an .npz with frames_u8 uint8 (N, H, W, 3), wav fp32 (n,) at 24 kHz and optionally fps (scalar): the whole recording goes
+through csts_amd.GazePredictor.predict_video (windows by csts_amd.plan_video, --stride frames apart) and --out receives the
+per-frame track: points (N, 2), peak (N,), count (N,), heatmaps and rescaled (N, S/4, S/4); the json_stats line has
+"_type": "predict_video".  --video and --clip exclude each other."""
 import argparse
 import json
 import os
@@ -23,6 +30,7 @@ from csts_amd.config import assert_and_infer_cfg, load_yaml      # noqa: E402
 from csts_amd.infer import GazePredictor                         # noqa: E402
 
 CLIP_KEYS = ("frames_u8", "wav", "frames_idx", "frame_length")
+VIDEO_KEYS = ("frames_u8", "wav")
 
 
 def parse_args(argv=None):
@@ -30,12 +38,18 @@ def parse_args(argv=None):
     p.add_argument("--cfg", dest="cfg_file", default=os.path.join(ROOT, "configs/Ego4D/CSTS_Ego4D_Gaze_Forecast.yaml"), type=str)
     p.add_argument("--checkpoint", default=None, type=str, help=".pyth file (default: TEST.CHECKPOINT_FILE_PATH)")
     p.add_argument("--clip", default=None, type=str, help=".npz with " + ", ".join(CLIP_KEYS))
+    p.add_argument("--video", default=None, type=str, help=".npz with " + ", ".join(VIDEO_KEYS) + " [, fps]: a whole recording")
+    p.add_argument("--stride", default=None, type=int, help="frames between windows of --video (default: csts_amd.plan_video's)")
+    p.add_argument("--fps", default=None, type=float, help="frame rate of --video (default: its fps entry, else DATA.TARGET_FPS)")
     p.add_argument("--seed", default=2000, type=int, help="seed of the synthetic batch used without --clip")
     p.add_argument("--batch", default=2, type=int, help="clips in the synthetic batch used without --clip")
     p.add_argument("--no-graph", action="store_true", help="launch the kernels eagerly instead of replaying a HIP graph")
     p.add_argument("--out", required=True, type=str, help=".npz to write")
     p.add_argument("opts", default=None, nargs=argparse.REMAINDER, help="KEY VALUE overrides")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.video is not None and args.clip is not None:
+        p.error("--video and --clip exclude each other: a whole recording or one clip")
+    return args
 
 
 def main(argv=None):
@@ -46,6 +60,22 @@ def main(argv=None):
     dev = torch.device("cuda", torch.cuda.current_device())
     torch.manual_seed(cfg.RNG_SEED)
     predictor = GazePredictor(cfg, args.checkpoint, device=dev, graph=not args.no_graph)
+    if args.video is not None:
+        with np.load(args.video) as z:
+            missing = [k for k in VIDEO_KEYS if k not in z.files]
+            if missing:
+                raise SystemExit(f"{args.video} lacks {missing}: a video holds {list(VIDEO_KEYS)} and optionally fps")
+            fps = args.fps if args.fps is not None else (float(z["fps"]) if "fps" in z.files else None)
+            out = predictor.predict_video(torch.from_numpy(z["frames_u8"]).to(dev), torch.from_numpy(z["wav"]).float().to(dev),
+                                          fps=fps, stride=args.stride)
+        arrays = {k: out[k].cpu().numpy() for k in ("points", "peak", "count", "rescaled", "heatmaps")}
+        np.savez(args.out, **arrays)
+        print("json_stats: " + json.dumps({"_type": "predict_video", "checkpoint": predictor.checkpoint_path, "source": args.video,
+                                           "graph": predictor.graph, "out": args.out, "windows": out["windows"],
+                                           "frames": int(arrays["count"].shape[0]),
+                                           "covered_frames": int((arrays["count"] > 0).sum()),
+                                           "shapes": {k: list(v.shape) for k, v in arrays.items()}}), flush=True)
+        return
     if args.clip is not None:
         with np.load(args.clip) as z:
             missing = [k for k in CLIP_KEYS if k not in z.files]
