@@ -92,6 +92,33 @@ def plan_video(cfg, n_frames, fps=None, stride=None, segment=None, cols=None):
     return plan
 
 
+def points_to_source(points, params_row, crop_size):
+    """Gaze points (N, 2) = (x, y) normalised on the S x S crop -> the same points normalised on the SOURCE frame the crop was cut
+    from: x_src = (x S + x0) / new w, y_src = (y S + y0) / new h, the inverse of the label rule of the spatial sampling.
+    params_row: (new h, new w, y0, x0, flip) on the host.  float64 on the device of `points`; NaN stays NaN."""
+    nh, nw, y0, x0 = (int(v) for v in list(params_row)[:4])
+    S = float(int(crop_size))
+    p = points.to(torch.float64)
+    if p.dim() != 2 or p.shape[1] != 2:
+        raise ValueError(f"points must be (N, 2), got {tuple(points.shape)}")
+    # the divisors are tensors: torch divides a device tensor by a host scalar as a multiplication by its reciprocal, one ulp off
+    # the quotient the formula states; tensor / tensor is the IEEE division on either device
+    x, y = p[:, 0], p[:, 1]
+    return torch.stack([(x * S + float(x0)) / torch.full_like(x, float(nw)), (y * S + float(y0)) / torch.full_like(y, float(nh))],
+                       dim=-1)
+
+
+def marker_centers(points_source, H, W):
+    """Source-normalised points (N, 2) -> int32 (N, 2) marker centres (X, Y) = floor(p * (W, H)) in source pixels, (-1, -1) where
+    the point is NaN (ops.gaze_overlay leaves such a frame untouched)."""
+    p = points_source.to(torch.float64)
+    if p.dim() != 2 or p.shape[1] != 2:
+        raise ValueError(f"points must be (N, 2), got {tuple(points_source.shape)}")
+    c = torch.floor(p * torch.tensor([float(W), float(H)], dtype=torch.float64, device=p.device))
+    bad = torch.isnan(p).any(dim=-1, keepdim=True)
+    return torch.where(bad, torch.full_like(c, -1.0), c).to(torch.int32)
+
+
 def _core(model):
     return model.module if hasattr(model, "module") else model
 
@@ -249,7 +276,51 @@ class GazePredictor:
                 "rescaled": out["rescaled"].squeeze(1)}
 
     @torch.no_grad()
-    def predict_video(self, frames_u8, wav, fps=None, stride=None, batch=None, return_heatmaps=True):
+    def _video_params_row(self, H, W):
+        """The one row of test-mode spatial parameters a whole video is sampled under: (new h, new w, y0, x0, flip)."""
+        S = int(self.cfg.DATA.TEST_CROP_SIZE)
+        if (H, W) == (S, S):
+            return [S, S, 0, 0, 0]                            # identity: bit-equal to normalize_frames
+        import numpy as np
+        from . import inputs
+        T = int(self.cfg.DATA.NUM_FRAMES)
+        return inputs.spatial_rule_host(np.zeros((1, T, 2)), H, W, S, train=False, spatial_idx=1)[0][0].tolist()
+
+    @torch.no_grad()
+    def render_track(self, frames_u8, track, alpha=0.4, radius=5, out=None, chunk=None):
+        """The track of predict_video drawn onto its recording: frames_u8 uint8 (N, H, W, 3) on the device and the dict
+        predict_video returned (it must hold "rescaled" and "points") -> uint8 (N, H, W, 3): the heat map of every predicted
+        frame blended over the crop the model saw and a disc at the gaze point (ops.gaze_overlay, csts_gaze_overlay); frames no
+        window predicts (NaN points) come back as they are.  The crop is the one predict_video sampled: identity for S x S
+        sources, else short side to S and centre crop.  chunk: frames per kernel launch (default: all).  out=frames_u8 renders
+        in place."""
+        if not torch.is_tensor(frames_u8) or not frames_u8.is_cuda:
+            raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
+        if "rescaled" not in track or "points" not in track:
+            raise ValueError("render_track needs the track's \"rescaled\" and \"points\": call predict_video with return_heatmaps=True")
+        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
+            raise ValueError(f"frames must be uint8 (N, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
+        N, H, W, _ = frames_u8.shape
+        if track["rescaled"].shape[0] != N or tuple(track["points"].shape) != (N, 2):
+            raise ValueError(f"the track holds {track['rescaled'].shape[0]} frames, the recording {N}")
+        step = N if chunk is None else int(chunk)
+        if step < 1:
+            raise ValueError(f"chunk must be positive, got {chunk}")
+        S = int(self.cfg.DATA.TEST_CROP_SIZE)
+        with torch.cuda.device(self.device):
+            row = self._video_params_row(H, W)
+            params = torch.tensor(row, dtype=torch.int32, device=frames_u8.device)
+            centers = marker_centers(points_to_source(track["points"], row, S), H, W)
+            if out is None:
+                out = torch.empty_like(frames_u8)
+            for a in range(0, N, step):
+                sel = slice(a, min(a + step, N))
+                ops.gaze_overlay(frames_u8[sel], track["rescaled"][sel], params, S, centers=centers[sel], alpha=alpha,
+                                 radius=radius, out=out[sel])
+        return out
+
+    @torch.no_grad()
+    def predict_video(self, frames_u8, wav, fps=None, stride=None, batch=None, return_heatmaps=True, overlay=False):
         """A whole recording in, one gaze track out: frames_u8 uint8 (N, H, W, 3) and wav fp32 (n,) at 24 kHz, both resident on
         the device -> {"points": (N, 2), "peak": (N,), "count": (N,) int32 = windows that predicted the frame, "heatmaps" and
         "rescaled": (N, S/4, S/4) (left out with return_heatmaps=False), "windows": their number}, on the device.
@@ -260,7 +331,9 @@ class GazePredictor:
         sources are normalised as they are), gets its audio windows (inputs.audio_windows_at) and runs predict_batch.  The last
         batch is filled up by repeating its last window, so one graph shape serves the video; the repeats are dropped.  The
         windows * T heat maps are averaged per video frame and decoded again by ops.gaze_track; frames no window predicts have
-        count 0, NaN points and zero maps."""
+        count 0, NaN points and zero maps.  The points are in the crop's coordinates.  overlay=True adds "points_source" (N, 2)
+        float64 = the points normalised on the source frame (points_to_source) and "overlay" uint8 (N, H, W, 3) =
+        render_track of this track with its defaults."""
         for t in (frames_u8, wav):
             if not torch.is_tensor(t) or not t.is_cuda:
                 raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
@@ -282,12 +355,8 @@ class GazePredictor:
             spec = inputs.stft_logpower(wav[None])
             plan = plan_video(cfg, N, fps=fps, stride=stride, cols=spec.shape[2])
             nwin = plan["windows"]
-            if (H, W) == (S, S):
-                row = [[S, S, 0, 0, 0]]                       # identity: bit-equal to normalize_frames
-            else:
-                import numpy as np
-                row = inputs.spatial_rule_host(np.zeros((1, T, 2)), H, W, S, train=False, spatial_idx=1)[0].tolist()
-            params = torch.tensor(row, dtype=torch.int32, device=dev).repeat(nb, 1)
+            row = self._video_params_row(H, W)
+            params = torch.tensor([row], dtype=torch.int32, device=dev).repeat(nb, 1)
             frames_idx = torch.from_numpy(plan["frames_idx"]).to(dev)
             centers = torch.from_numpy(plan["audio_centers"]).to(dev)
             o = (AUDIO_WIDTH - S) // 2
@@ -305,7 +374,12 @@ class GazePredictor:
                     audio = audio[:, :, :, :S, o:o + S].contiguous()
                 out = self.predict_batch({"video": video, "audio": audio})
                 preds[w0 * T:(w0 + n) * T] = out["heatmaps"][:n].reshape(n * T, S // 4, S // 4)
-            want = ("points", "peak", "count") + (("heatmaps", "rescaled") if return_heatmaps else ())
+            want = ("points", "peak", "count") + (("heatmaps", "rescaled") if return_heatmaps or overlay else ())
             track = ops.gaze_track(preds, torch.from_numpy(plan["target_idx"].reshape(-1)).to(dev), N, want=want)
+            if overlay:
+                track["points_source"] = points_to_source(track["points"], row, S)
+                track["overlay"] = self.render_track(frames_u8, track)
+                if not return_heatmaps:
+                    del track["heatmaps"], track["rescaled"]
         track["windows"] = nwin
         return track

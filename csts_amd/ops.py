@@ -2662,3 +2662,67 @@ def gaze_track(preds, target_idx, n_frames, want=_TRACK_OUTPUTS):
     L.check(_lib().csts_gaze_track(_p(x), _p(order), _p(offsets), n_frames, H, W, _p(out.get("heatmaps")), _p(out.get("rescaled")),
                                    _p(out.get("points")), _p(out.get("peak")), _p(out.get("count")), _stream()), "csts_gaze_track")
     return out
+
+
+# ----------------------------------------------------------------------------------------- gaze overlay
+def jet_table():
+    """The heat colours of gaze_overlay on the host: uint8 numpy (256, 3) RGB, row q = the classic JET by the integer formula of
+    include/csts_hip.h, r = clamp(383 - |4q - 765|, 0, 255), g = clamp(383 - |4q - 510|, 0, 255), b = clamp(383 - |4q - 255|, 0, 255)."""
+    import numpy as np
+    q4 = 4 * np.arange(256, dtype=np.int64)
+    return np.stack([np.clip(383 - np.abs(q4 - c), 0, 255) for c in (765, 510, 255)], axis=-1).astype(np.uint8)
+
+
+def _overlay_params(params, crop_size, device):
+    """The params row of gaze_overlay as an int32 device tensor.  A row given on the host (5 integers) is checked against the
+    sampler's range and uploaded; a device tensor is taken as it is (the kernel reads it when it runs: no host sync)."""
+    if torch.is_tensor(params):
+        _need_gpu(params)
+        if params.dtype != torch.int32 or params.numel() != 5:
+            raise ValueError(f"params must hold 5 int32 values (new h, new w, y0, x0, flip), got {tuple(params.shape)} {params.dtype}")
+        return params.contiguous()
+    import numpy as np
+    row = np.asarray(params)
+    if row.size != 5 or not np.issubdtype(row.dtype, np.integer):
+        raise ValueError(f"params must hold 5 integers (new h, new w, y0, x0, flip), got {params!r}")
+    nh, nw, y0, x0, flip = (int(v) for v in row.reshape(5))
+    if flip != 0:
+        raise ValueError("gaze_overlay draws test-mode crops, which are never flipped: params has flip != 0")
+    S = int(crop_size)
+    if nh < S or nw < S or not 0 <= y0 <= nh - S or not 0 <= x0 <= nw - S:
+        raise ValueError(f"params {(nh, nw, y0, x0)} do not hold a {S} x {S} crop")
+    return torch.tensor([nh, nw, y0, x0, 0], dtype=torch.int32, device=device)
+
+
+def gaze_overlay(frames_u8, rescaled, params, crop_size, centers=None, alpha=0.4, radius=5, out=None):
+    """csts_gaze_overlay: frames uint8 (N, H, W, 3) RGB + rescaled fp32 (N, mh, mw) in [0, 1] (gaze_decode / gaze_track) -> uint8
+    (N, H, W, 3): inside the crop that `params` (new h, new w, y0, x0, flip = 0: the row of inputs.spatial_sample / clip_sample,
+    5 integers on the host or an int32 device tensor) cut out of the frame, (1 - alpha) frame + alpha JET(map), the map sampled
+    bilinearly; outside it the frame; a filled (0, 255, 0) disc of `radius` pixels at centers int32 (N, 2) = (X, Y) in source
+    pixels.  A frame whose centre X is negative comes back untouched; centers=None draws no markers.  out=frames_u8 renders
+    in place.  One launch, no host sync: it can be captured in a graph.  The rule is stated in include/csts_hip.h."""
+    _need_gpu(frames_u8, rescaled, centers, out)
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
+        raise ValueError(f"frames must be uint8 (N, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
+    N, H, W, _ = frames_u8.shape
+    if rescaled.dtype != torch.float32 or rescaled.dim() != 3 or rescaled.shape[0] != N:
+        raise ValueError(f"rescaled must be fp32 ({N}, mh, mw), got {tuple(rescaled.shape)} {rescaled.dtype}")
+    if centers is not None and (centers.dtype != torch.int32 or tuple(centers.shape) != (N, 2)):
+        raise ValueError(f"centers must be int32 ({N}, 2), got {tuple(centers.shape)} {centers.dtype}")
+    alpha, radius, S = float(alpha), int(radius), int(crop_size)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha must lie in [0, 1], got {alpha}")
+    if radius < 0 or S < 1 or N < 1:
+        raise ValueError(f"gaze_overlay needs N >= 1 frames, crop_size >= 1 and radius >= 0, got {N}, {S} and {radius}")
+    if not frames_u8.is_contiguous():
+        raise ValueError("frames must be contiguous (N, H, W, 3)")
+    if out is None:
+        out = torch.empty_like(frames_u8)
+    elif out.dtype != torch.uint8 or out.shape != frames_u8.shape or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous uint8 {tuple(frames_u8.shape)}, got {tuple(out.shape)} {out.dtype}")
+    par = _overlay_params(params, S, frames_u8.device)
+    maps = rescaled.detach().contiguous()
+    cen = None if centers is None else centers.contiguous()
+    L.check(_lib().csts_gaze_overlay(_p(frames_u8), _p(maps), _p(cen), _p(par), _p(out), N, H, W, S, maps.shape[1], maps.shape[2],
+                                     alpha, radius, _stream()), "csts_gaze_overlay")
+    return out

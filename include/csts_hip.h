@@ -581,6 +581,40 @@ int csts_gaze_decode(const void* logits, int dt, int64_t nframes, int H, int W, 
 int csts_gaze_track(const float* preds, const int* order, const int* offsets, int64_t F, int H, int W, float* heatmaps,
                     float* rescaled, float* points, float* peak, int* count, hipStream_t stream);
 
+/* ---- gaze overlay (csts_amd/csrc/overlay.hip): the heat map of a gaze track blended onto the source frames and a disc at the
+ *      gaze point, what slowfast/visualization/visualization.py (vis_inference, vis_video_forecasting) draws with cv2: map
+ *      resized to the frame, JET colours, 0.6 frame + 0.4 heat, a filled green circle.  cv2 is not a dependency, so the rule
+ *      below is this project's own statement of it; it is not pinned against cv2's pixels.
+ *      frames_nhwc (N, H, W, 3) uint8 RGB; rescaled (N, mh, mw) fp32 in [0, 1], the `rescaled` of gaze_decode / gaze_track (no
+ *      min-max here); centers int32 [N][2] = marker centre (X, Y) in source pixels, X < 0: no marker and an untouched frame;
+ *      centers NULL: no markers at all; params int32 [5] in DEVICE memory = {new h, new w, y0, x0, flip}, the row
+ *      csts_spatial_sample / csts_clip_sample took: how the S x S crop the map covers was cut from the frame; out (N, H, W, 3)
+ *      uint8, may alias frames_nhwc (the op is elementwise per pixel).  Rule per output pixel (n, Y, X), nh = new h, nw = new w:
+ *        inside the crop  iff  y0 * 2H <= (2Y + 1) * nh < (y0 + S) * 2H  and  x0 * 2W <= (2X + 1) * nw < (x0 + S) * 2W  (64-bit
+ *                         integers): the pixel centre, taken through the resize H -> nh, lies in the crop's extent.  flip is
+ *                         ignored (test mode never flips).  A row outside the sampler's range (nh < S, nw < S, an offset outside
+ *                         [0, n - S], a side above 2^24) has no inside.
+ *        outside the crop, or a frame whose centre X < 0:  out = frame, byte for byte.
+ *        inside, crop coordinates:  cy = (Y + 0.5) * nh / H - 0.5 - y0, then the map position my = (cy + 0.5) * mh / S - 0.5; x
+ *                         alike.  Both are evaluated EXACTLY, as the rational my = A / D with A = ((2Y + 1) nh - 2H y0) mh - H S
+ *                         and D = 2 H S in 64-bit integers.
+ *        inside, bilinear sample with the edge clamp of spatial_sample:  src = max(my, 0), i0 = min(floor(src), mh - 1),
+ *                         i1 = min(i0 + 1, mh - 1), lambda = src - i0 = fl((A mod D) / D) (0 where A <= 0); then in fp32
+ *                         top = fma(lx, m[i0][j1] - m[i0][j0], m[i0][j0]), bot likewise on row i1, v = fma(ly, bot - top, top).
+ *        inside, quantise:  q = min(255, (int)(v * 255))   (fp32 product, truncation)
+ *        heat colour (integers, the classic JET):  r = clamp(383 - |4q - 765|, 0, 255), g = clamp(383 - |4q - 510|, 0, 255),
+ *                         b = clamp(383 - |4q - 255|, 0, 255)
+ *        blend:           out_c = (uint8) rintf((1 - alpha) * frame_c + alpha * heat_c), fp32 without contraction, 0 <= alpha <= 1
+ *                         (at the default 0.4 the exact value is a multiple of 0.2, never a tie)
+ *        marker:          where (X - cX)^2 + (Y - cY)^2 <= radius^2 (radius >= 0) the pixel is (0, 255, 0), inside or outside
+ *                         the crop.
+ *      One launch, no allocation, no host read (params and centers are read on the device): graph-capturable.  The map is staged
+ *      in LDS per workgroup: mh * mw <= CSTS_GAZE_DECODE_MAX_HW.  96-bit loads and stores, 4 pixels a lane, when W % 4 == 0 and
+ *      frames and out are 4-byte aligned; byte accesses otherwise, with the same bytes out.  N >= 1, H <= 65535, W <= 8192,
+ *      S <= 4096, N * ceil(H / 32) < 2^31. */
+int csts_gaze_overlay(const uint8_t* frames_nhwc, const float* rescaled, const int* centers, const int* params, uint8_t* out,
+                      int64_t N, int H, int W, int S, int mh, int mw, float alpha, int radius, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

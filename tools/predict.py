@@ -15,7 +15,10 @@ arrays; one json_stats line reports their shapes and the checkpoint path.
 --video: an .npz with frames_u8 uint8 (N, H, W, 3), wav fp32 (n,) at 24 kHz and optionally fps (scalar): the whole recording goes
 through csts_amd.GazePredictor.predict_video (windows by csts_amd.plan_video, --stride frames apart) and --out receives the
 per-frame track: points (N, 2), peak (N,), count (N,), heatmaps and rescaled (N, S/4, S/4); the json_stats line has
-"_type": "predict_video".  --video and --clip exclude each other."""
+"_type": "predict_video".  --video and --clip exclude each other.
+--overlay (with --video): --out also receives points_source (N, 2), the points normalised on the source frame, and overlay uint8
+(N, H, W, 3), the track drawn onto the recording (GazePredictor.render_track).  --overlay-dir DIR [--overlay-every K] additionally
+writes every K-th overlay frame as DIR/frame_000000.png through PIL; without PIL one line says so and no image is written."""
 import argparse
 import json
 import os
@@ -41,6 +44,9 @@ def parse_args(argv=None):
     p.add_argument("--video", default=None, type=str, help=".npz with " + ", ".join(VIDEO_KEYS) + " [, fps]: a whole recording")
     p.add_argument("--stride", default=None, type=int, help="frames between windows of --video (default: csts_amd.plan_video's)")
     p.add_argument("--fps", default=None, type=float, help="frame rate of --video (default: its fps entry, else DATA.TARGET_FPS)")
+    p.add_argument("--overlay", action="store_true", help="with --video: add points_source and the rendered overlay to --out")
+    p.add_argument("--overlay-dir", default=None, type=str, help="with --video: also write overlay frames as PNGs here (implies --overlay)")
+    p.add_argument("--overlay-every", default=1, type=int, help="write every K-th frame to --overlay-dir")
     p.add_argument("--seed", default=2000, type=int, help="seed of the synthetic batch used without --clip")
     p.add_argument("--batch", default=2, type=int, help="clips in the synthetic batch used without --clip")
     p.add_argument("--no-graph", action="store_true", help="launch the kernels eagerly instead of replaying a HIP graph")
@@ -49,7 +55,22 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.video is not None and args.clip is not None:
         p.error("--video and --clip exclude each other: a whole recording or one clip")
+    if (args.overlay or args.overlay_dir) and args.video is None:
+        p.error("--overlay and --overlay-dir draw onto a recording: they need --video")
+    if args.overlay_every < 1:
+        p.error("--overlay-every must be positive")
     return args
+
+
+def write_pngs(overlay, directory, every):
+    try:
+        from PIL import Image
+    except ImportError:
+        print(f"PIL is not installed: no PNG written to {directory}", flush=True)
+        return
+    os.makedirs(directory, exist_ok=True)
+    for i in range(0, overlay.shape[0], every):
+        Image.fromarray(overlay[i]).save(os.path.join(directory, f"frame_{i:06d}.png"))
 
 
 def main(argv=None):
@@ -67,9 +88,12 @@ def main(argv=None):
                 raise SystemExit(f"{args.video} lacks {missing}: a video holds {list(VIDEO_KEYS)} and optionally fps")
             fps = args.fps if args.fps is not None else (float(z["fps"]) if "fps" in z.files else None)
             out = predictor.predict_video(torch.from_numpy(z["frames_u8"]).to(dev), torch.from_numpy(z["wav"]).float().to(dev),
-                                          fps=fps, stride=args.stride)
-        arrays = {k: out[k].cpu().numpy() for k in ("points", "peak", "count", "rescaled", "heatmaps")}
+                                          fps=fps, stride=args.stride, overlay=bool(args.overlay or args.overlay_dir))
+        keys = ("points", "peak", "count", "rescaled", "heatmaps") + (("points_source", "overlay") if "overlay" in out else ())
+        arrays = {k: out[k].cpu().numpy() for k in keys}
         np.savez(args.out, **arrays)
+        if args.overlay_dir is not None:
+            write_pngs(arrays["overlay"], args.overlay_dir, args.overlay_every)
         print("json_stats: " + json.dumps({"_type": "predict_video", "checkpoint": predictor.checkpoint_path, "source": args.video,
                                            "graph": predictor.graph, "out": args.out, "windows": out["windows"],
                                            "frames": int(arrays["count"].shape[0]),
