@@ -7,6 +7,7 @@ Each Function cites the reference op it replaces (paths under the reference repo
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes as C
 import functools
@@ -140,91 +141,55 @@ class HostTable:
 # finished tensor to its leaf parameter itself: p.grad = g, or p.grad += g when a gradient is already there.  Strong
 # references to operands, partial rows and results are held until then.
 #
-# The queues belong to ONE backward pass, identified by autograd's graph-task id: final callbacks are dropped when
-# backward raises, so a pass that finds another pass's leftovers discards them (stale device addresses) and registers
-# its own callback.
-_deferred = []          # (ws tensor, out tensor, nrows, ncols)
-_assign = []            # (leaf parameter, finished gradient tensor)
-_deferred_task = [-1]   # graph-task id the queues belong to (-1: none)
-_deferred_tables = {}   # device index -> HostTable
+# Everything a backward pass postpones to its end lives in ONE object, a _Pass: the queues, autograd's graph-task id of the
+# pass that owns them, the side streams the pass has forked launches onto and the tensors those launches still use.  The
+# module has one current pass (_pass) and a stack of suspended outer ones (_suspended, see nested_backward).  Final callbacks
+# are dropped when backward raises, so a pass that finds another task id's leftovers discards them (stale device addresses:
+# reset_deferred, which first waits for the side streams of the dead pass) and registers its own callback.  A new kind of
+# per-pass state is a new field of _Pass -- reset, suspension and the flush need no word about it.
+#
+# What outlives a pass stays at module level: the streams and host tables (expensive to create, and a captured graph replays
+# copies out of the tables' buffers), the cached launch plans, the previous pass's 192 x 384 count, the gradient targets.
 DEFER_REDUCTIONS = os.environ.get("CSTS_DEFER_REDUCE", "1") != "0"
+
+
+class _Pass:
+    """The deferred work of ONE backward pass."""
+
+    def __init__(self, lane=None):
+        self.lane = lane        # None at top level; inside nested_backward the lane label of the inner pass (selects its host tables)
+        self.task = -1          # graph-task id the queues belong to (-1: none)
+        self.deferred = []      # (ws tensor, out tensor, nrows, ncols)
+        self.assign = []        # (leaf parameter, finished gradient tensor)
+        self.wgq = []           # (dY, X, dW, db, tokens, N_out, K_in)
+        self.wg_prod = {}       # raw stream id -> torch stream that produced operands queued since the last flush
+        self.w8_count = 0       # 192 x 384-class problems queued so far
+        self.swq = []           # (DwconvGeom copy, fine ptr, coarse ptr, workspace ptr, dt, (tensors kept alive))
+        self.forked = []        # side streams with launches of this pass in flight, in fork order
+        self.keep = []          # what those launches read / write, alive until the streams are joined
+
+
+_pass = _Pass()
+_suspended = []         # the outer passes set aside by nested_backward, innermost last
+_w8_total = [0]         # 192 x 384-class problems of the whole PREVIOUS pass: tells this one which problem is its last
+_side_streams = {}      # (role, device index) -> stream: created once, the captured steps name them
+_tables = {}            # (kind, _table_key) -> HostTable: pinned rings and device buffers, created once per device and lane
 
 
 def reset_deferred():
     """Drop everything queued for an end-of-backward flush (used when a backward pass died before its final callback)."""
-    if _wg_side_used[0]:                # a dead pass may have launches in flight that read / write what is dropped below
-        for st in _wg_side.values():
-            st.synchronize()
-        _wg_side_used[0] = False
-    if _sw_used[0]:
-        for st in _sw_side.values():
-            st.synchronize()
-        _sw_used[0] = False
-    _sw_keep.clear()
-    _swq.clear()
-    _swq_count[0] = 0
-    _sw_prod.clear()
-    _swq_early_keep.clear()
-    _swq_early_used[0] = False
-    _deferred.clear()
-    _assign.clear()
-    _wgq.clear()
-    _wg_pending.clear()
-    _wg_prod.clear()
-    _wg_work[0] = 0.0
-    _w8_count[0] = 0
-    _deferred_task[0] = -1
+    global _pass
+    for st in _pass.forked:             # a dead pass may have launches in flight that read / write what is dropped below
+        st.synchronize()
+    _pass = _Pass(_pass.lane)
 
 
 # A backward pass that starts INSIDE a backward pass (an activation-checkpointed block re-runs its forward and back-propagates
 # through the fresh sub-graph from its own backward: CheckpointFn) is a graph task of its own.  Its queues must not be mixed
 # with the outer pass's, and the outer pass's must not be taken for a dead pass's leftovers.  nested_backward() is the scope of
-# such an inner pass: it sets the outer pass's queues aside (a stack of frames), the inner pass queues into empty ones and its
-# own final callback finishes them -- its weight gradients, reductions and hand-overs are complete, and its operands released,
-# when the inner torch.autograd.backward returns -- and the outer queues come back untouched.
-_frames = []            # saved frames of the suspended outer passes, innermost last
-_nest_lane = [None]     # None at top level; inside nested_backward the lane label of the inner pass (selects its host tables)
-
-
-def _frame_state():
-    lists = (_deferred, _assign, _wgq, _wg_pending, _swq, _swq_early_keep, _sw_keep)
-    dicts = (_wg_prod, _sw_prod)
-    cells = (_deferred_task, _wg_work, _w8_count, _swq_count, _swq_early_used, _wg_side_used, _sw_used)
-    return lists, dicts, cells
-
-
-def _frame_empty() -> bool:
-    lists, dicts, _ = _frame_state()
-    return not any(lists) and not any(dicts)
-
-
-def _push_frame(lane):
-    lists, dicts, cells = _frame_state()
-    _frames.append(([list(l_) for l_ in lists], [dict(d_) for d_ in dicts], [c_[0] for c_ in cells], _nest_lane[0]))
-    for l_ in lists:
-        l_.clear()
-    for d_ in dicts:
-        d_.clear()
-    _deferred_task[0], _wg_work[0], _w8_count[0], _swq_count[0] = -1, 0.0, 0, 0
-    _swq_early_used[0] = _wg_side_used[0] = _sw_used[0] = False
-    _nest_lane[0] = lane
-
-
-def _pop_frame():
-    if not _frame_empty() or _deferred_task[0] != -1:
-        reset_deferred()                # the inner pass raised before its final callback ran: its leftovers go, the outer queue stays
-    lists, dicts, cells = _frame_state()
-    s_lists, s_dicts, s_cells, lane = _frames.pop()
-    for l_, v_ in zip(lists, s_lists):
-        l_[:] = v_
-    for d_, v_ in zip(dicts, s_dicts):
-        d_.clear()
-        d_.update(v_)
-    for c_, v_ in zip(cells, s_cells):
-        c_[0] = v_
-    _nest_lane[0] = lane
-
-
+# such an inner pass: it sets the outer pass aside, the inner pass queues into a fresh one and its own final callback finishes
+# that -- its weight gradients, reductions and hand-overs are complete, and its operands released, when the inner
+# torch.autograd.backward returns -- and the outer pass comes back untouched.
 @contextlib.contextmanager
 def nested_backward(lane=0):
     """Scope of a backward pass run from inside another pass's node (torch.autograd.backward in a Function's backward): the
@@ -232,23 +197,61 @@ def nested_backward(lane=0):
     pass's own final callback, on the stream the inner pass was started from, before the scope ends.  lane: a small label for
     that stream -- inner passes that may run concurrently on different streams (the video and the audio trunk) need different
     lanes, because a lane owns the device tables its finishing launches read."""
-    _push_frame(lane)
+    global _pass
+    _suspended.append(_pass)
+    _pass = _Pass(lane)
     try:
         yield
     finally:
-        _pop_frame()
+        reset_deferred()                # the inner pass raised before its final callback ran: its leftovers go, the outer queue stays
+        _pass = _suspended.pop()
 
 
 def _table_key(dev_index, *extra):
     """Key of a flush's host -> device table: per device at top level (as ever), per (device, lane) inside a nested pass -- a
     nested flush on the audio stream must not overwrite the table a nested flush on the main stream is still reading."""
-    lane = _nest_lane[0]
+    lane = _pass.lane
     key = (dev_index,) + extra if extra else dev_index
     return key if lane is None else ("nested", lane, key)
 
 
 # host tables of nested flushes: one block's work per upload, one upload per checkpointed block and capture
 _NESTED_CAPTURES = 32
+
+
+def _host_table(kind, dev, nbytes, ring, captures, *extra):
+    """The HostTable of this flush: one per kind ("reduce", "wgrad", "stencil"), device, lane and `extra`, created on first use.
+    captures: the capture buffers of a top-level table (a nested pass's table has _NESTED_CAPTURES)."""
+    key = (kind, _table_key(dev.index, *extra))
+    tab = _tables.get(key)
+    if tab is None:
+        tab = _tables[key] = HostTable(nbytes, dev, ring=ring, captures=captures if _pass.lane is None else _NESTED_CAPTURES)
+    return tab
+
+
+def _fork(role, device, producers):
+    """The side stream `role` ("early", "tail") of `device`, waiting for everything enqueued so far on the `producers` streams
+    (autograd runs every node of a device on ONE thread: whatever produced the operands is already enqueued there), and
+    recorded as forked by the current pass: _join makes the pass's stream wait for it, reset_deferred the host."""
+    st = _side_streams.get((role, device.index))
+    if st is None:
+        st = _side_streams[(role, device.index)] = torch.cuda.Stream(device=device)
+    for p_ in producers:
+        st.wait_stream(p_)
+    if st not in _pass.forked:
+        _pass.forked.append(st)
+    return st
+
+
+def _join():
+    """Make the current stream wait for every side stream this pass forked (the last forked first), then release what the
+    launches there were using."""
+    if _pass.forked:
+        cur = torch.cuda.current_stream()
+        for st in reversed(_pass.forked):
+            cur.wait_stream(st)
+        _pass.forked.clear()
+    _pass.keep.clear()
 
 
 def _can_defer(*params) -> bool:
@@ -262,21 +265,23 @@ def _can_defer(*params) -> bool:
     tid = torch._C._current_graph_task_id()
     if tid < 0:                        # not inside a backward pass
         return False
-    if _deferred_task[0] != tid:
+    if _pass.task != tid:
         reset_deferred()               # leftovers of a pass that raised before its callback ran
         torch.autograd.Variable._execution_engine.queue_callback(flush_deferred)
-        _deferred_task[0] = tid
+        _pass.task = tid
     return True
 
 
 def _defer(ws: torch.Tensor, out: torch.Tensor, nrows: int, ncols: int):
-    _deferred.append((ws, out, int(nrows), int(ncols)))
+    _pass.deferred.append((ws, out, int(nrows), int(ncols)))
 
 
 # Gradient targets (csts_amd.train.SegmentedTrainStep, data-parallel chain): parameter storage address -> a view of a flat
 # all-reduce bucket shaped like the parameter.  A producer that allocates a parameter gradient (queued Linear weight gradients,
 # the fusion convs' TN GEMM) writes it THERE, so the bucket needs no copy afterwards.  One use per backward pass: a second
 # gradient for the same parameter (a module applied twice) gets an ordinary buffer and is accumulated as before.
+# (Module level: the targets are set once per step object, and a bucket view stays single-use across the nested passes of the
+# outer pass -- _hand_over of the OUTER pass frees them.)
 _grad_targets = {}
 _grad_targets_used = set()
 
@@ -302,79 +307,51 @@ def _grad_buffer(param_like, shape, device):
 
 def _assign_later(param, grad):
     if param is not None and grad is not None:
-        _assign.append((param, grad))
+        _pass.assign.append((param, grad))
 
 
 def _hand_over():
     """Give the finished gradients to their parameters (stream-ordered after the finishing kernels)."""
-    for p_, g_ in _assign:
+    for p_, g_ in _pass.assign:
         if p_.grad is None:
             p_.grad = g_ if g_.dtype == p_.dtype else g_.to(p_.dtype)
         else:
             p_.grad.add_(g_)
-    _assign.clear()
-    if _nest_lane[0] is None:           # a nested pass ends in the middle of the outer one: the bucket views stay single-use until that ends
+    _pass.assign.clear()
+    if _pass.lane is None:              # a nested pass ends in the middle of the outer one: the bucket views stay single-use until that ends
         _grad_targets_used.clear()
-
-
-def _targets_reset():
-    _grad_targets_used.clear()
 
 
 def flush_deferred():
     """Finish the queued weight gradients and every deferred reduction on the current stream, then hand the results to
     their parameters (idempotent)."""
-    _deferred_task[0] = -1
-    nested = _nest_lane[0] is not None
-    if _w8_count[0] and not nested:
-        _w8_total[0] = _w8_count[0]
-    _w8_count[0] = 0
+    ps = _pass
+    ps.task = -1
+    nested = ps.lane is not None
+    if ps.w8_count and not nested:
+        _w8_total[0] = ps.w8_count
+    ps.w8_count = 0
     # the grouped stencil weight gradients (0.8 ms of load-latency-bound work, no matrix math) run on a side stream BESIDE the
     # grouped Linear weight gradients (MFMA-bound, one persistent workgroup per CU whose last items leave most CUs idle)
-    _swq_count[0] = 0
-    _sw_prod.clear()
-    tail = None
     # (a nested pass finishes ONE block: its two or three pools stay on the pass's own stream -- a fork / join pair per block would
     # cost more in the captured graph than the overlap returns, and the audio trunk's blocks already run beside the video trunk's)
-    if _swq and _wgq and STENCIL_TAIL_SIDE and _swq[0][5][0].is_cuda and not nested:
+    if ps.swq and ps.wgq and STENCIL_TAIL_SIDE and ps.swq[0][5][0].is_cuda and not nested:
         cur = torch.cuda.current_stream()
-        tail = _tail_side.get(cur.device.index)
-        if tail is None:
-            tail = _tail_side[cur.device.index] = torch.cuda.Stream(device=cur.device)
-        tail.wait_stream(cur)
-        if W8_PARALLEL:
-            # Round 5 experiment: the 192 x 384 class (310 items on 256 CUs: its second round fills a fifth of the chip) FIRST and alone on this
-            # stream, every other weight-gradient launch on the side stream -- they can take the CUs its second round leaves idle
-            flush_wgrads(w8="only")
-        with torch.cuda.stream(tail):
-            keep = flush_stencil_wgrads()
-            if W8_PARALLEL:
-                flush_wgrads(w8="exclude")
-    flush_wgrads()
-    if tail is not None:
-        torch.cuda.current_stream().wait_stream(tail)
-        del keep        # allocated on this stream, read on `tail`: alive until the join above
+        with torch.cuda.stream(_fork("tail", cur.device, [cur])):
+            ps.keep.append(flush_stencil_wgrads())      # allocated on this stream, read on the tail stream: alive until the join
+        flush_wgrads()
     else:
+        flush_wgrads()
         flush_stencil_wgrads()
-    if _swq_early_used[0]:
-        for st in _tail_side.values():
-            torch.cuda.current_stream().wait_stream(st)
-        _swq_early_used[0] = False
-        _swq_early_keep.clear()
-    _join_wgrad_side()
-    _join_stencil_side()
-    if not _deferred:
+    _join()
+    if not ps.deferred:
         _hand_over()
         return
     # wide & shallow (split-K slabs) after narrow & deep (LayerNorm / stencil partial rows): two kernels
     wide = lambda it: it[3] >= 8192 and it[3] % 4 == 0 and it[2] <= 64
-    items = sorted(_deferred, key=lambda it: (wide(it), it[3]))
-    _deferred.clear()
-    dev = items[0][0].device
-    tkey = _table_key(dev.index)
-    tab = _deferred_tables.get(tkey)
-    if tab is None:
-        tab = _deferred_tables[tkey] = HostTable(C.sizeof(L.ReduceDesc) * 2048, dev, ring=4, captures=_NESTED_CAPTURES if nested else 16)
+    items = sorted(ps.deferred, key=lambda it: (wide(it), it[3]))
+    ps.deferred.clear()
+    tab = _host_table("reduce", items[0][0].device, C.sizeof(L.ReduceDesc) * 2048, 4, 16)
     # one launch per size class (the grid is sized by the widest reduction of the launch)
     descs = (L.ReduceDesc * len(items))()
     for i, (ws, out, nrows, ncols) in enumerate(items):
@@ -418,7 +395,6 @@ WGRAD8_CHUNK = int(os.environ.get("CSTS_WGRAD8_CHUNK", "8192"))
 # Round 5: the thin layers (output and input features multiples of 96 that the 192 x 384 class does not take; bf16 dY) as 96 x 96 tiles, one
 # (tile, token chunk) item per WAVE of csts_wgrad_grouped5 (wgrad5.hip: every wave its own LDS-DMA stream, no workgroup barrier)
 WG_DUMP = os.environ.get("CSTS_WGRAD_DUMP", "")
-WGRAD_CAST_F32 = os.environ.get("CSTS_WGRAD_CAST_F32", "0") == "1"      # measured neutral (19.39 vs 19.39 ms, gpurun_out/r5al): off
 WGRAD5 = os.environ.get("CSTS_WGRAD5", "1") != "0"
 WGRAD5_CHUNK = int(os.environ.get("CSTS_WGRAD5_CHUNK", "4096"))
 WGRAD5_STRIDED = os.environ.get("CSTS_WGRAD5_STRIDED", "1") != "0"
@@ -427,21 +403,48 @@ WGRAD5_MIN = int(os.environ.get("CSTS_WGRAD5_MIN", "96"))          # layers with
 # and the remaining 128-wide items (wgrad5 and the stencil kernel side by side take the SUM of their times: profiles/r5_wgrad5.txt)
 WGRAD5_POS = os.environ.get("CSTS_WGRAD5_POS", "mid")
 WGRAD_CHUNK = int(os.environ.get("CSTS_WGRAD_CHUNK", "8192"))   # tokens per work item (measured per step: 4096 -> 24.93 ms, 8192 -> 24.95, 16384 -> 25.47)
-_wgq = []               # (dY, X, dW, db, tokens, N_out, K_in)
 WG_STATS = None         # a list while bench.py instruments a step: (C-ABI entry, algorithmic bytes, flop) per grouped launch
-_wg_tables = {}
-# Optional: every WG_FLUSH_GFLOP of queued work goes out as its own grouped launch on a SIDE stream, beside the rest of
-# backward (the idea: backward's kernels are small, and the audio trunk on its own stream was worth 8 ms of a 41 ms step).
-# Operands, slabs and results stay referenced until the final callback has joined the side stream.
-# MEASURED SLOWER on MI355X (bench.py, same box, ms per step): one launch at the end 25.19-25.28, flushes of 600 / 350 / 200
-# GFLOP on the side stream 25.62 / 25.46-25.51 / 26.74 -- backward does not leave the matrix pipes idle enough for a second
-# MFMA-heavy kernel beside it.  Default 0 (off); the switch stays for re-measuring on other workloads.
-WG_FLUSH_FLOP = float(os.environ.get("CSTS_WGRAD_FLUSH_GFLOP", "0")) * 1e9
-_wg_work = [0.0]
-_wg_prod = {}           # raw stream id -> torch stream that produced operands queued since the last flush
-_wg_side = {}           # device index -> side stream
-_wg_pending = []        # strong references of side-stream flushes in flight
-_wg_side_used = [False]
+# WGRAD8_LAST (with CSTS_STENCIL_TAIL_SIDE=1): the 192 x 384 class -- one 144 KB-LDS workgroup per CU, nothing fits beside it -- goes
+# last, so that the grouped stencil weight gradients on the side stream (vector-bound, 20 KB of LDS, 124 registers) start beside the
+# 128-wide classes (memory-bound, 40 KB of LDS, 154 registers), which they CAN share a CU with: -0.2 ... -0.26 ms per step
+# (profiles/r5_wgrad_tail_ab.txt).  The same side stream was neutral in round 4 only because that class went first.  =0 restores either.
+WGRAD8_LAST = os.environ.get("CSTS_WGRAD8_LAST", "1") != "0"
+STENCIL_TAIL_SIDE = os.environ.get("CSTS_STENCIL_TAIL_SIDE", "1") != "0"
+# Round 5 (CSTS_WGRAD8_EARLY_WGS = n > 0): the grouped weight gradients of the 384- / 768-channel stages (wgrad8: matrix-bound, 1.1 ms, one
+# 144 KB-LDS workgroup per CU) are launched on n workgroups on the side stream as soon as the backward pass has produced their last operand
+# -- the rest of backward (the 96- / 192-channel stages: large-M, memory-bound kernels, a third of the trunk backward) runs beside them on
+# the remaining CUs -- instead of on all CUs after the pass (profiles/r5_wgrad8_early_ab.txt).
+W8_EARLY_WGS = int(os.environ.get("CSTS_WGRAD8_EARLY_WGS", "0"))
+# Retired experiments (measured slower or neutral: DESIGN.md, "Retired switches"): the code and the environment variables are gone;
+# the names stay as inert constants for callers that set them back to their defaults.  Nothing reads them.
+WG_FLUSH_FLOP, W8_PARALLEL, WGRAD_CAST_F32 = 0.0, False, False
+
+# The tile classes of a grouped launch, one row each: tile rows x columns (output x input features), the module attribute that
+# holds its tokens per work item (read at call time), the token granule its k-loop needs, whether its items may interleave
+# 16-token stages (WGRAD5_STRIDED), the C-ABI entry (also its name in WG_STATS) and that entry's arguments between the item
+# count and the stream.  192 x 384 on 8-wave workgroups where it divides the layer (the 384- and 768-channel stages: half the
+# operand bytes per FLOP of a 128 x 128 tile); 96 x 96 per wave for the thin layers; else 256 x 128 where 256 divides the output
+# rows; else 128 x 128.  fp32 dY (a handful per step: the stage-transition projections, whose output gradient has no 16-bit
+# copy) is always 128 x 128: the kernel rounds it to the 16-bit type while staging.
+_WgClass = collections.namedtuple("_WgClass", "name rows cols chunk granule strided entry args")
+_WG_CLASSES = {c.name: c for c in (
+    _WgClass("192", 192, 384, "WGRAD8_CHUNK", 64, False, "csts_wgrad_grouped8", ()),
+    _WgClass("96", 96, 96, "WGRAD5_CHUNK", 16, True, "csts_wgrad_grouped5", ()),
+    _WgClass("256", 256, 128, "WGRAD_CHUNK", 1, False, "csts_wgrad_grouped", (0, 256)),
+    _WgClass("128", 128, 128, "WGRAD_CHUNK", 1, False, "csts_wgrad_grouped", (0, 128)),
+    _WgClass("128f", 128, 128, "WGRAD_CHUNK", 1, False, "csts_wgrad_grouped", (1, 128)),
+)}
+
+
+def _wg_class(dy_is_f32, tokens, N, K):
+    """The tile class of the problem dW[N, K] = dY[tokens, N]^T X[tokens, K] under the current switches."""
+    if dy_is_f32:
+        return _WG_CLASSES["128f"]
+    for name, on in (("192", WGRAD8), ("96", WGRAD5 and min(N, K) >= WGRAD5_MIN)):
+        c = _WG_CLASSES[name]
+        if on and N % c.rows == 0 and K % c.cols == 0 and tokens % c.granule == 0 and globals()[c.chunk] % c.granule == 0:
+            return c
+    return _WG_CLASSES["256" if N % 256 == 0 else "128"]
 
 
 def queue_wgrad(dY, X, tokens, N, K, Wp, bp):
@@ -457,38 +460,22 @@ def queue_wgrad(dY, X, tokens, N, K, Wp, bp):
         return False
     dW = _grad_buffer(Wp, (N, K), dY.device)
     db = _grad_buffer(bp, (N,), dY.device) if bp is not None else None
-    _wgq.append((dY, X, dW, db, tokens, N, K))
+    _pass.wgq.append((dY, X, dW, db, tokens, N, K))
     _assign_later(Wp, dW)
     _assign_later(bp, db)
     cur = torch.cuda.current_stream()
-    _wg_prod[cur.cuda_stream] = cur
-    _wg_work[0] += 2.0 * tokens * N * K
-    if WG_FLUSH_FLOP > 0 and _wg_work[0] >= WG_FLUSH_FLOP:
-        flush_wgrads(side=True)
-    if W8_EARLY_WGS > 0 and _is_w8(dY, tokens, N, K):
+    _pass.wg_prod[cur.cuda_stream] = cur
+    if W8_EARLY_WGS > 0 and _wg_class(dY.dtype == torch.float32, tokens, N, K).name == "192":
         # the 192 x 384 class goes out EARLY, on few workgroups, as soon as its last problem of this backward pass is queued (the count
         # of the previous pass tells which one that is; a wrong guess only moves work between this launch and the final one)
-        _w8_count[0] += 1
-        if _w8_count[0] == _w8_total[0]:
-            flush_wgrads(side=True, only_w8=True)
+        _pass.w8_count += 1
+        if _pass.w8_count == _w8_total[0]:
+            flush_wgrads(only_w8=True)
     return True
 
 
-# Round 5 (CSTS_WGRAD8_EARLY_WGS = n > 0): the grouped weight gradients of the 384- / 768-channel stages (wgrad8: matrix-bound, 1.1 ms, one
-# 144 KB-LDS workgroup per CU) are launched on n workgroups on the side stream as soon as the backward pass has produced their last operand
-# -- the rest of backward (the 96- / 192-channel stages: large-M, memory-bound kernels, a third of the trunk backward) runs beside them on
-# the remaining CUs -- instead of on all CUs after the pass (profiles/r5_wgrad8_early_ab.txt).
-W8_EARLY_WGS = int(os.environ.get("CSTS_WGRAD8_EARLY_WGS", "0"))
-_w8_count = [0]         # 192 x 384-class problems queued so far in this backward pass
-_w8_total = [0]         # ... in the whole previous pass
-
-
-def _is_w8(dY, tokens, N, K):
-    return bool(WGRAD8 and dY.dtype != torch.float32 and N % 192 == 0 and K % 384 == 0 and tokens % 64 == 0 and WGRAD8_CHUNK % 64 == 0)
-
-
 _WG_DTYPE = None
-_wg_plans = {}          # (tuple of (tokens, N, K) per problem) -> cached work-item layout
+_wg_plans = {}          # (tuple of (tokens, N, K) per problem, class geometry) -> cached work-item layout: a function of shapes alone
 
 
 def _wg_dtype():
@@ -566,97 +553,42 @@ def _wg_plan(sig, rows=128, cols=128, chunk_tokens=None, strided=False):
     return plan
 
 
-def flush_wgrads(side: bool = False, only_w8: bool = False, w8: str = "all"):
-    """Launch the queued weight gradients: on the current stream (end of backward), or -- side=True, from queue_wgrad in
-    the middle of backward -- on the side stream, after everything the producing streams have enqueued so far.  only_w8: just the
-    192 x 384-class problems (on W8_EARLY_WGS workgroups); everything else stays queued."""
-    if not _wgq:
+def flush_wgrads(only_w8: bool = False):
+    """Launch the queued weight gradients on the current stream (end of backward).  only_w8 (from queue_wgrad, in the middle of
+    backward): just the 192 x 384-class problems, on W8_EARLY_WGS workgroups on the "early" side stream, after everything the
+    producing streams have enqueued so far; everything else stays queued."""
+    ps = _pass
+    if not ps.wgq:
         return
     import numpy as np
-    if only_w8 or w8 != "all":      # w8 = "only" / "exclude": the 192 x 384 class alone (a full launch) / everything but it; the rest stays queued
-        q = [t for t in _wgq if _is_w8(t[0], t[4], t[5], t[6])]
-        rest = [t for t in _wgq if not _is_w8(t[0], t[4], t[5], t[6])]
-        if w8 == "exclude":
-            q, rest = rest, q
-        _wgq.clear()
-        _wgq.extend(rest)
+    q = [(t, _wg_class(t[0].dtype == torch.float32, t[4], t[5], t[6])) for t in ps.wgq]
+    ps.wgq.clear()
+    if only_w8:
+        ps.wgq.extend(t for t, c in q if c.name != "192")
+        q = [(t, c) for t, c in q if c.name == "192"]
         if not q:
             return
-    else:
-        q = list(_wgq)
-        _wgq.clear()
-        _wg_work[0] = 0.0
     if WG_DUMP and not os.path.exists(WG_DUMP):      # diagnostics: the problem list of one flush, for tools/wgrad5_bench.py
         with open(WG_DUMP, "w") as f:
-            for t in q:
+            for t, _ in q:
                 f.write(f"{'f32' if t[0].dtype == torch.float32 else 'h16'} {t[4]} {t[5]} {t[6]} {t[0].stride(0)} {t[1].stride(0)} {int(t[3] is not None)}\n")
-    dev = q[0][0].device
-    # (w8 = "exclude" runs on the tail side stream CONCURRENTLY with the "only" launch of the main stream: its own device table -- one table
-    # for both let the second upload overwrite the items the first launch was still reading: a GPU memory fault, round 5)
-    key = _table_key(dev.index, "x" if w8 == "exclude" else side)
-    tab = _wg_tables.get(key)
-    if tab is None:
-        if _nest_lane[0] is not None:   # one block's items per upload (a single tile class is capped at 16384 items)
-            tab = _wg_tables[key] = HostTable(C.sizeof(L.WgradItem) * 16384, dev, ring=8, captures=_NESTED_CAPTURES)
-        else:
-            tab = _wg_tables[key] = HostTable(C.sizeof(L.WgradItem) * 24576, dev, ring=8, captures=40 if side else 16)
-    keep = []
-    launch_stream = None
-    if side:
-        launch_stream = _wg_side.get(dev.index)
-        if launch_stream is None:
-            # CSTS_WG_SIDE_PRIO=low: the early weight-gradient flushes on a LOW-priority stream (experiment, round 5: they should only
-            # fill the CUs the activation-gradient chain leaves idle, not delay it)
-            prio = 0
-            if os.environ.get("CSTS_WG_SIDE_PRIO", "") == "low":
-                try:
-                    prio = max(torch.cuda.Stream.priority_range())
-                except Exception:
-                    prio = 0
-            launch_stream = _wg_side[dev.index] = torch.cuda.Stream(device=dev, priority=prio)
-        for st in _wg_prod.values():          # autograd runs every node of this device on ONE thread: whatever produced the
-            ev = torch.cuda.Event()           # queued operands is already enqueued on these streams
-            ev.record(st)
-            launch_stream.wait_event(ev)
-        _wg_side_used[0] = True
-    _wg_prod.clear()
-    # Round 5: fp32 dY of layers the LDS-DMA classes can take (a handful per step: the stage-transition projections, whose output gradient
-    # has no 16-bit copy) is cast to the 16-bit type first -- the 128-wide fp32-dY class rounds it the same way while staging, but as 4
-    # problems / ~330 workgroups of its own it took 0.28 ms per step for 153 MB (profiles/r5_final_mfma_util.txt); as 16-bit operands
-    # they ride in the 192 x 384 / 96 x 96 launches.  Whole step: neutral -- the fp32 class runs beside the stencil weight gradients, which bound that
-    # part of the tail either way -- so this is opt-in (CSTS_WGRAD_CAST_F32=1).
-    if WGRAD_CAST_F32:
-        with (torch.cuda.stream(launch_stream) if launch_stream is not None else contextlib.nullcontext()):
-            for i, t in enumerate(q):
-                if t[0].dtype == torch.float32 and (_is_w8(t[1], t[4], t[5], t[6]) or
-                                                    (WGRAD5 and t[5] % 96 == 0 and t[6] % 96 == 0 and t[4] % 16 == 0 and min(t[5], t[6]) >= WGRAD5_MIN)):
-                    d16 = torch.empty(t[0].shape, dtype=L.half_dtype(), device=t[0].device)
-                    cast_into(d16, t[0])
-                    q[i] = (d16,) + tuple(t[1:])
-    # tile classes: 192 x 384 on 8-wave workgroups where it divides the layer (the 384- and 768-channel stages: half the
-    # operand bytes per FLOP of a 128 x 128 tile); else 256 x 128 where 256 divides the output rows; else 128 x 128
-    def tile_class(t):
-        if t[0].dtype == torch.float32:
-            return (True, 128)
-        if WGRAD8 and t[5] % 192 == 0 and t[6] % 384 == 0 and t[4] % 64 == 0 and WGRAD8_CHUNK % 64 == 0:
-            return (False, 192)
-        if WGRAD5 and t[5] % 96 == 0 and t[6] % 96 == 0 and t[4] % 16 == 0 and WGRAD5_CHUNK % 16 == 0 and min(t[5], t[6]) >= WGRAD5_MIN:
-            return (False, 96)
-        return (False, 256 if t[5] % 256 == 0 else 128)
-    pend = []           # (item table image, items, tile rows, fp32 dY) per tile class
-    # WGRAD8_LAST (with CSTS_STENCIL_TAIL_SIDE=1): the 192 x 384 class -- one 144 KB-LDS workgroup per CU, nothing fits beside it -- goes
-    # last, so that the grouped stencil weight gradients on the side stream (vector-bound, 20 KB of LDS, 124 registers) start beside the
-    # 128-wide classes (memory-bound, 40 KB of LDS, 154 registers), which they CAN share a CU with
-    order = (((False, 96), (False, 256), (False, 128), (True, 128), (False, 192)) if WGRAD8_LAST
-             else ((False, 192), (False, 96), (False, 256), (False, 128), (True, 128)))
+    dev = q[0][0][0].device
+    # (the early launch runs on the side stream CONCURRENTLY with launches of the main stream: its own device table -- one table for two
+    # streams let the second upload overwrite the items the first launch was still reading: a GPU memory fault, round 5.  A nested
+    # pass uploads one block's items at a time: a single tile class is capped at 16384 items)
+    tab = _host_table("wgrad", dev, C.sizeof(L.WgradItem) * (24576 if ps.lane is None else 16384), 8, 40 if only_w8 else 16, only_w8)
+    launch_stream = _fork("early", dev, ps.wg_prod.values()) if only_w8 else None
+    ps.wg_prod.clear()
+    pend = []           # (item table image, items, tile class) per tile class
+    order = ("96", "256", "128", "128f", "192") if WGRAD8_LAST else ("192", "96", "256", "128", "128f")
     if WGRAD8_LAST and WGRAD5_POS == "mid":
-        order = ((False, 256), (False, 128), (True, 128), (False, 96), (False, 192))
-    for a_f32, rows in order:
-        probs = [t for t in q if tile_class(t) == (a_f32, rows)]
+        order = ("256", "128", "128f", "96", "192")
+    for c in (_WG_CLASSES[name] for name in order):
+        probs = [t for t, c_ in q if c_ is c]
         if not probs:
             continue
-        CH = WGRAD8_CHUNK if rows == 192 else (WGRAD5_CHUNK if rows == 96 else WGRAD_CHUNK)
-        tmpl, valid, pidx, chunk, n_items, CHs = _wg_plan(tuple((t[4], t[5], t[6]) for t in probs), rows, {192: 384, 96: 96}.get(rows, 128), CH, strided=(rows == 96 and WGRAD5_STRIDED))
+        tmpl, valid, pidx, chunk, n_items, CHs = _wg_plan(tuple((t[4], t[5], t[6]) for t in probs), c.rows, c.cols, globals()[c.chunk],
+                                                          strided=c.strided and WGRAD5_STRIDED)
         A = np.empty(len(probs), dtype=np.uint64); B = np.empty_like(A); Cb = np.empty_like(A); Cs = np.zeros_like(A)
         cstride = np.zeros(len(probs), dtype=np.uint64); sstride = np.zeros_like(cstride)
         for i, (dY, X, dW, db, tokens, N, K) in enumerate(probs):
@@ -664,16 +596,14 @@ def flush_wgrads(side: bool = False, only_w8: bool = False, w8: str = "all"):
             nch = -(-tokens // CHs[i])
             if nch == 1:
                 Cb[i], Cs[i] = dW.data_ptr(), (db.data_ptr() if db is not None else 0)
-            else:          # several token chunks: one partial slab per chunk, summed by the batched reducer
+            else:          # several token chunks: one partial slab per chunk, summed by the batched reducer (which keeps the slabs alive)
                 slab = torch.empty(nch, N, K, dtype=torch.float32, device=dev)
                 _defer(slab, dW, nch, N * K)
                 Cb[i], cstride[i] = slab.data_ptr(), N * K * 4
-                cs = None
                 if db is not None:
                     cs = torch.empty(nch, N, dtype=torch.float32, device=dev)
                     _defer(cs, db, nch, N)
                     Cs[i], sstride[i] = cs.data_ptr(), N * 4
-                keep.append((slab, cs))
         arr = tmpl.copy()
         ch = chunk.astype(np.uint64)
         arr["A"][valid] = A[pidx]
@@ -681,10 +611,9 @@ def flush_wgrads(side: bool = False, only_w8: bool = False, w8: str = "all"):
         arr["C"][valid] = Cb[pidx] + ch * cstride[pidx]
         arr["colsum"][valid] = Cs[pidx] + ch * sstride[pidx]
         if WG_STATS is not None:      # dY + X read once, dW written once; 2 tokens N K flop
-            WG_STATS.append(("csts_wgrad_grouped8" if rows == 192 else ("csts_wgrad_grouped5" if rows == 96 else "csts_wgrad_grouped"),
-                             sum(t[4] * t[5] * t[0].element_size() + t[4] * t[6] * 2 + t[5] * t[6] * 4 for t in probs),
+            WG_STATS.append((c.entry, sum(t[4] * t[5] * t[0].element_size() + t[4] * t[6] * 2 + t[5] * t[6] * 4 for t in probs),
                              sum(2.0 * t[4] * t[5] * t[6] for t in probs)))
-        pend.append((arr.tobytes(), n_items, rows, a_f32))
+        pend.append((arr.tobytes(), n_items, c))
     # the item tables of all tile classes travel in ONE host -> device copy (a copy node per class cost ~12 us each in the replayed
     # step, gap included); one copy per class only when they do not fit the table together
     with (torch.cuda.stream(launch_stream) if launch_stream is not None else contextlib.nullcontext()):
@@ -695,41 +624,21 @@ def flush_wgrads(side: bool = False, only_w8: bool = False, w8: str = "all"):
         base = None
         if pend and total <= tab.nbytes:
             base = tab.upload(b"".join(blob + bytes((-len(blob)) % 256) for blob, *_ in pend))
-        for (blob, n_items, rows, a_f32), off in zip(pend, offs):
+        for (blob, n_items, c), off in zip(pend, offs):
             ptr = base + off if base is not None else tab.upload(blob)
-            if rows == 192 and only_w8:
-                L.check(_lib().csts_wgrad_grouped8_limited(ptr, n_items, W8_EARLY_WGS, _stream()), "csts_wgrad_grouped8_limited")
-            elif rows == 192:
-                L.check(_lib().csts_wgrad_grouped8(ptr, n_items, _stream()), "csts_wgrad_grouped8")
-            elif rows == 96:
-                L.check(_lib().csts_wgrad_grouped5(ptr, n_items, _stream()), "csts_wgrad_grouped5")
-            else:
-                L.check(_lib().csts_wgrad_grouped(ptr, n_items, 1 if a_f32 else 0, rows, _stream()), "csts_wgrad_grouped")
-    if side:
-        _wg_pending.append((q, keep))      # alive until the final callback has joined the side stream
-    del q, keep
+            entry, args = ("csts_wgrad_grouped8_limited", (W8_EARLY_WGS,)) if only_w8 else (c.entry, c.args)
+            L.check(getattr(_lib(), entry)(ptr, n_items, *args, _stream()), entry)
+    if only_w8:
+        ps.keep.append(q)       # the operands, alive until the final callback has joined the side stream
 
 
 # Stencil weight gradients, grouped (csts_dwconv_wgrad_grouped): 34 first-stage launches of ~24 us per step -- each a single round
 # of <= 1024 latency-bound workgroups -- become ONE launch at the end of backward (their second stages were deferred already).
 # Same policy as the grouped Linear weight gradients: while the step is captured (GROUP_WGRADS), and only when the gradient may be
-# deferred; the operands (the saved q / k / v tensors and the conv-output gradients) stay alive until the flush.
+# deferred; the operands (the saved q / k / v tensors and the conv-output gradients) stay alive until the flush.  With
+# STENCIL_TAIL_SIDE that launch (vector-issue-bound, 20 KB of LDS, 124 registers) runs on the "tail" side stream beside the 128-wide
+# classes of the grouped Linear weight gradients (flush_deferred).
 STENCIL_WGRAD_GROUPED = os.environ.get("CSTS_STENCIL_WGRAD_GROUPED", "1") != "0"
-# Round 5: the grouped stencil weight gradients (vector-issue-bound, 20 KB of LDS, 124 registers) run on a side stream BESIDE the 128-wide
-# classes of the grouped Linear weight gradients (memory-bound, 40 KB of LDS, 154 registers): the two share CUs, -0.2 ... -0.26 ms per step
-# (profiles/r5_wgrad_tail_ab.txt).  What made the same side stream neutral in round 4 was the ORDER: the 192 x 384 class went first, and
-# its one 144 KB-LDS workgroup per CU leaves no room for anything else -- it now goes last (WGRAD8_LAST).  =0 restores either.
-WGRAD8_LAST = os.environ.get("CSTS_WGRAD8_LAST", "1") != "0"
-W8_PARALLEL = os.environ.get("CSTS_W8_PARALLEL", "0") == "1"
-STENCIL_TAIL_SIDE = os.environ.get("CSTS_STENCIL_TAIL_SIDE", "1") != "0"
-_tail_side = {}         # device index -> stream
-_swq = []               # (DwconvGeom copy, fine ptr, coarse ptr, workspace ptr, dt, (tensors kept alive))
-SWG_EARLY = int(os.environ.get("CSTS_SWG_EARLY", "0"))
-_swq_count = [0]        # stencil problems queued so far in this backward pass
-_sw_prod = {}           # raw id -> stream: the streams that queued them
-_swq_early_keep = []    # operands of an early launch, alive until the final join
-_swq_early_used = [False]
-_swq_tables = {}        # device index -> HostTable
 
 
 def _stencil_group_now() -> bool:
@@ -741,37 +650,15 @@ def _queue_stencil_wgrad(g, fine, fine_off, coarse, coarse_off, ws):
     of `ws` itself)."""
     gg = L.DwconvGeom()
     C.memmove(C.byref(gg), C.byref(g), C.sizeof(L.DwconvGeom))
-    _swq.append((gg, _p(fine, fine_off), _p(coarse, coarse_off), _p(ws), _dt(fine), (fine, coarse, ws)))
-    cur = torch.cuda.current_stream()
-    _sw_prod[cur.cuda_stream] = cur
-    _swq_count[0] += 1
-    if SWG_EARLY > 0 and _swq_count[0] == SWG_EARLY and fine.is_cuda:
-        # Round 5 experiment (CSTS_SWG_EARLY=n): the first n problems of this backward pass (the head's and the late stages' pools: their
-        # operands are complete long before the pass ends) go out NOW as one grouped launch on the tail side stream, beside the rest of
-        # backward -- ONE fork; the join is the final flush's (the per-pool side launches of round 4 paid 34 fork / join pairs)
-        tail = _tail_side.get(cur.device.index)
-        if tail is None:
-            tail = _tail_side[cur.device.index] = torch.cuda.Stream(device=cur.device)
-        for st in _sw_prod.values():
-            ev = torch.cuda.Event()
-            ev.record(st)
-            tail.wait_event(ev)
-        with torch.cuda.stream(tail):
-            _swq_early_keep.append(flush_stencil_wgrads())
-        _swq_early_used[0] = True
+    _pass.swq.append((gg, _p(fine, fine_off), _p(coarse, coarse_off), _p(ws), _dt(fine), (fine, coarse, ws)))
 
 
 def flush_stencil_wgrads():
-    if not _swq:
+    if not _pass.swq:
         return None
-    q = list(_swq)
-    _swq.clear()
-    dev = q[0][5][0].device
-    tkey = _table_key(dev.index)
-    tab = _swq_tables.get(tkey)
-    if tab is None:
-        tab = _swq_tables[tkey] = HostTable(L.DWCONV_WGRAD_TABLE_ENTRY * 256, dev, ring=4,
-                                            captures=_NESTED_CAPTURES if _nest_lane[0] is not None else 16)
+    q = list(_pass.swq)
+    _pass.swq.clear()
+    tab = _host_table("stencil", q[0][5][0].device, L.DWCONV_WGRAD_TABLE_ENTRY * 256, 4, 16)
     for dt in sorted({e[4] for e in q}):
         sel = [e for e in q if e[4] == dt]
         if len(sel) > 256:
@@ -790,50 +677,6 @@ def flush_stencil_wgrads():
                              sum(54.0 * cells(e[0])[1] * e[0].C for e in sel)))
         L.check(_lib().csts_dwconv_wgrad_grouped(ptr, len(sel), nblocks.value, dt, _stream()), "csts_dwconv_wgrad_grouped")
     return q            # the operands: the caller keeps them alive until the launch stream has been joined
-
-
-# Stencil weight gradients (csts_dwconv_wgrad / _wgrad2: 34 launches of ~24 us per step, latency-bound, 0.16 of the HBM roofline)
-# feed nothing but the end-of-backward reduction: with deferred reductions they run on a SIDE stream beside the rest of backward
-# (one side stream per producing stream: the audio trunk's backward has its own) and are joined by the final flush.
-STENCIL_WGRAD_SIDE = os.environ.get("CSTS_STENCIL_WGRAD_SIDE", "0") == "1"     # MEASURED SLOWER (21.3 -> 22.2 ms per step, profiles/r4_stencil_wgrad_side_ab.txt): 34 fork / join pairs inside the captured graph cost more than the overlap returns; off
-_sw_side = {}            # raw id of the producing stream -> side stream
-_sw_used = [False]
-_sw_keep = []            # tensors read / written on a side stream, alive until the join
-
-
-def _stencil_side(*tensors):
-    """Side stream for a stencil weight-gradient launch issued from the current stream, already waiting for everything queued on
-    it so far; `tensors` (operands, workspace) are kept alive and marked as used there."""
-    cur = torch.cuda.current_stream()
-    st = _sw_side.get(cur.cuda_stream)
-    if st is None:
-        st = _sw_side[cur.cuda_stream] = torch.cuda.Stream(device=cur.device)
-    st.wait_stream(cur)
-    for t in tensors:
-        if t is not None:
-            t.record_stream(st)
-            _sw_keep.append(t)
-    _sw_used[0] = True
-    return st
-
-
-def _join_stencil_side():
-    if _sw_used[0]:
-        cur = torch.cuda.current_stream()
-        for st in _sw_side.values():
-            cur.wait_stream(st)
-        _sw_used[0] = False
-    _sw_keep.clear()
-
-
-def _join_wgrad_side():
-    """Make the current stream wait for the side-stream weight-gradient launches of this backward pass."""
-    if _wg_side_used[0]:
-        cur = torch.cuda.current_stream()
-        for st in _wg_side.values():
-            cur.wait_stream(st)
-        _wg_side_used[0] = False
-    _wg_pending.clear()
 
 
 # ----------------------------------------------------------------------------------------- raw wrappers
@@ -1629,17 +1472,12 @@ class AttnInnerFn(Function):
                     _queue_stencil_wgrad(g, dc, 0, qkv, slot * Cc, wws)
                 else:
                     _queue_stencil_wgrad(g, qkv, slot * Cc, dc, 0, wws)
-            side = _stencil_side(dc, qkv, wws) if (defer and not grouped and STENCIL_WGRAD_SIDE) else None
-            with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-                sw = _stream()
-                if grouped:
-                    pass
-                elif transposed:   # fine = dc (output side), coarse = qkv slot
-                    L.check(lib.csts_dwconv_wgrad(C.byref(g), _p(dc), _dt(dc), _p(qkv, slot * Cc), _dt(qkv), dwp, _p(wws),
-                                                  wws.numel(), sw), "csts_dwconv_wgrad")
-                else:            # fine = qkv slot, coarse = dc
-                    L.check(lib.csts_dwconv_wgrad(C.byref(g), _p(qkv, slot * Cc), _dt(qkv), _p(dc), _dt(dc), dwp, _p(wws),
-                                                  wws.numel(), sw), "csts_dwconv_wgrad")
+            elif transposed:   # fine = dc (output side), coarse = qkv slot
+                L.check(lib.csts_dwconv_wgrad(C.byref(g), _p(dc), _dt(dc), _p(qkv, slot * Cc), _dt(qkv), dwp, _p(wws),
+                                              wws.numel(), s), "csts_dwconv_wgrad")
+            else:            # fine = qkv slot, coarse = dc
+                L.check(lib.csts_dwconv_wgrad(C.byref(g), _p(qkv, slot * Cc), _dt(qkv), _p(dc), _dt(dc), dwp, _p(wws),
+                                              wws.numel(), s), "csts_dwconv_wgrad")
             if transposed:
                 L.check(lib.csts_dwconv_strided(C.byref(g), _p(dc), _dt(dc), _p(w), _p(dqkv, slot * Cc), _dt(dqkv), s),
                         "csts_dwconv_strided(bwd)")
@@ -1682,11 +1520,9 @@ class AttnInnerFn(Function):
             if grouped:
                 for i in (0, 1):
                     _queue_stencil_wgrad(g, kv_fine, kv_off[i], dc2[i], 0, wws[i * wsz:(i + 1) * wsz])
-            side = _stencil_side(dc2, kv_fine, wws) if (defer and not grouped and STENCIL_WGRAD_SIDE) else None
-            with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-                if not grouped:
-                    L.check(lib.csts_dwconv_wgrad2(C.byref(g), vp2(_p(kv_fine, kv_off[0]), _p(kv_fine, kv_off[1])), _dt(kv_fine),
-                                               vp2(_p(dc2[0]), _p(dc2[1])), _dt(dc2), dwp, _p(wws), wws.numel(), _stream()), "csts_dwconv_wgrad2")
+            else:
+                L.check(lib.csts_dwconv_wgrad2(C.byref(g), vp2(_p(kv_fine, kv_off[0]), _p(kv_fine, kv_off[1])), _dt(kv_fine),
+                                               vp2(_p(dc2[0]), _p(dc2[1])), _dt(dc2), dwp, _p(wws), wws.numel(), s), "csts_dwconv_wgrad2")
             if defer:
                 nrow = wsz // (HD * 27 * 4)
                 _defer(wws[:wsz], dw[0], nrow, HD * 27)
@@ -1798,12 +1634,12 @@ class QkvCompactFn(Function):
                 and Wp.dtype == torch.float32 and _can_defer(Wp, bp):
             dWf = _grad_buffer(Wp, (3 * Cc, K), x.device)
             dbf = _grad_buffer(bp, (3 * Cc,), x.device) if bp is not None else None
-            _wgq.append((dq, x, dWf[:Cc], dbf[:Cc] if dbf is not None else None, B * N, Cc, K))
-            _wgq.append((dkv, xk, dWf[Cc:], dbf[Cc:] if dbf is not None else None, B * Nc, 2 * Cc, K))
+            _pass.wgq.append((dq, x, dWf[:Cc], dbf[:Cc] if dbf is not None else None, B * N, Cc, K))
+            _pass.wgq.append((dkv, xk, dWf[Cc:], dbf[Cc:] if dbf is not None else None, B * Nc, 2 * Cc, K))
             _assign_later(Wp, dWf)
             _assign_later(bp, dbf)
             cur = torch.cuda.current_stream()
-            _wg_prod[cur.cuda_stream] = cur
+            _pass.wg_prod[cur.cuda_stream] = cur
             queued = True
         if not queued:
             dW = torch.empty(3 * Cc, K, dtype=torch.float32, device=x.device)

@@ -6,7 +6,8 @@ colsum given and NULL, padding slots, operands read in place from wider buffers,
 csts_wgrad_grouped8_limited on the same tables at every grid size that matters (bit-identical to the full launch);
 csts_wgrad_grouped5 and csts_wgrad_grouped (both dY types) on raw tables; the host path (ops.queue_wgrad -> ops.flush_wgrads ->
 the deferred slab reductions) on a problem list that reaches every tile class, checked through ops.WG_STATS; the in-line split-K
-path; the early 192 x 384 flush on the side stream with a wrong guess of the problem count in both directions; a captured
+path; the early 192 x 384 flush on the side stream with a wrong guess of the problem count in both directions, and a pass that
+dies with that launch in flight; a captured
 flush replayed with new operands; and the fp16 library (tests/fp16_wgrad_worker.py, child process).
 
 Bars: rel-L2 per dW / db at about 4x the worst value measured on MI355X (constants below).  Element-wise,
@@ -50,9 +51,9 @@ REL_FP16_DB = 4e-7      # fp16 library, db: 9.8e-8
 @pytest.fixture(autouse=True)
 def _defaults(monkeypatch):
     """The tile-class switches at their defaults whatever the environment says (the assertions name the classes)."""
-    for k, v in (("WGRAD8", True), ("WGRAD5", True), ("WGRAD5_STRIDED", True), ("WGRAD_CAST_F32", False), ("W8_EARLY_WGS", 0),
-                 ("WGRAD8_CHUNK", 8192), ("WGRAD5_CHUNK", 4096), ("WGRAD_CHUNK", 8192), ("WGRAD5_MIN", 96), ("WG_FLUSH_FLOP", 0.0),
-                 ("W8_PARALLEL", False), ("DEFER_REDUCTIONS", True)):
+    for k, v in (("WGRAD8", True), ("WGRAD5", True), ("WGRAD5_STRIDED", True), ("W8_EARLY_WGS", 0),
+                 ("WGRAD8_CHUNK", 8192), ("WGRAD5_CHUNK", 4096), ("WGRAD_CHUNK", 8192), ("WGRAD5_MIN", 96),
+                 ("DEFER_REDUCTIONS", True)):
         monkeypatch.setattr(ops, k, v)
     ops.reset_deferred()
     yield
@@ -286,6 +287,48 @@ def test_early_wgrad8_flush_wrong_guess_both_ways(monkeypatch):
             if b is not None:
                 b.grad = gb
             _check_grad(W, b, dY, X, REL_HOST, REL_HOST_DB, name)
+
+
+class _Boom(torch.autograd.Function):
+    """A node whose backward raises once the early launch of the pass is on the side stream."""
+
+    @staticmethod
+    def forward(ctx, z):
+        return z.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        assert ops._pass.forked and not ops._pass.wgq and ops._pass.keep      # early launch enqueued, its operands held
+        raise RuntimeError("boom")
+
+
+def test_dead_pass_with_early_flush_in_flight(monkeypatch):
+    """W8_EARLY_WGS > 0, four 192 x 384-class layers (tokens 64 k, one and several tiles): a pass counts them, a clean pass launches
+    them early; then a pass whose LAST backward node raises a Python exception with that early launch in flight on the side stream
+    (its final callback, and so the join, never run); then a clean pass again.  The pass after the dead one must wait for the side
+    stream before it drops the dead pass's operands and must start from empty queues: its dW / db are bit-identical to the clean
+    pass before, and equal fp64."""
+    monkeypatch.setattr(ops, "GROUP_WGRADS", "always")
+    monkeypatch.setattr(ops, "W8_EARLY_WGS", 64)
+    spec = [("w8_a", 256, 192, 384, H, True, "192"), ("w8_b", 320, 384, 384, H, False, "192"),
+            ("w8_c", 448, 192, 768, H, True, "192"), ("w8_d", 576, 384, 768, H, True, "192")]
+    layers = _make_layers(spec, 21)
+    ops._w8_total[0] = 0
+    _linear_pass(layers)                                      # counts
+    assert ops._w8_total[0] == 4
+    clean = _linear_pass(layers)                              # early launch at the fourth problem
+    z = torch.zeros(1, device=DEV, requires_grad=True)
+    r = _Boom.apply(z)                                        # made first: the lowest sequence number, so backward runs it last
+    ys = [ops.linear(X, W, b, out_dt=L.BF16, compute=L.BF16) for _, dY, X, W, b, _ in layers]
+    with pytest.raises(RuntimeError, match="boom"):
+        torch.autograd.backward(ys + [r], [dY for _, dY, _, _, _, _ in layers] + [torch.ones_like(r)])
+    assert ops._pass.forked and ops._pass.assign              # the dead pass's leftovers, a launch in flight among them
+    after = _linear_pass(layers)
+    assert not ops._pass.forked and not ops._pass.assign and ops._w8_total[0] == 4
+    for lay, (gw, gb), (cw, cb) in zip(layers, after, clean):
+        name, dY, X, W, b, cls = lay
+        assert torch.equal(gw, cw) and (gb is None or torch.equal(gb, cb)), name
+        _check_grad(W, b, dY, X, REL_HOST, REL_HOST_DB, name)
 
 
 def test_captured_flush_replays_with_new_operands(monkeypatch):

@@ -30,14 +30,21 @@ def _b4_step():
             dt, tokens, N, K = line.split()[:4]
             tokens, N, K = int(tokens), int(N), int(K)
             if dt == "f32":
-                out["128f"].append((tokens, N, K))
+                cls = "128f"
             elif N % 192 == 0 and K % 384 == 0 and tokens % 64 == 0:
-                out["192"].append((tokens, N, K))
+                cls = "192"
             elif N % 96 == 0 and K % 96 == 0 and tokens % 16 == 0 and min(N, K) >= 96:
-                out["96"].append((tokens, N, K))
+                cls = "96"
             else:
-                out["256" if N % 256 == 0 else "128"].append((tokens, N, K))
+                cls = "256" if N % 256 == 0 else "128"
+            out[cls].append((tokens, N, K))
+            assert ops._wg_class(dt == "f32", tokens, N, K).name == cls, line       # ops' own table names the same class
     return out
+
+
+# problems per tile class that flush_wgrads made of tools/wgrad_problems_b4.txt before the class table existed (counted there
+# through its _wg_plan calls and launches, default switches)
+B4_CLASS_COUNTS = {"192": 79, "96": 30, "256": 0, "128": 0, "128f": 4}
 
 
 def check_plan(sig, cls):
@@ -104,6 +111,7 @@ def check_plan(sig, cls):
 def test_b4_step_plans():
     """The real problem list of a b = 4 step, every tile class it reaches."""
     step = _b4_step()
+    assert {k: len(step[k]) for k in B4_CLASS_COUNTS} == B4_CLASS_COUNTS
     assert step["192"] and step["96"] and step["128f"]
     check_plan(step["192"], "192")
     check_plan(step["96"], "96")

@@ -28,7 +28,7 @@ def enqueue():
     for dY, X, t, N, K, hb in prob:
         dW = torch.empty(N, K, device=dev)
         db = torch.empty(N, device=dev) if hb else None
-        ops._wgq.append((dY, X, dW, db, t, N, K))
+        ops._pass.wgq.append((dY, X, dW, db, t, N, K))
         outs.append((dW, db))
     ops.flush_wgrads()
     ops.flush_deferred()

@@ -23,7 +23,7 @@ for w8 in (True, False, True, False):
         for dY, X, N, K in prob:
             dW = torch.empty(N, K, device=dev)
             db = torch.empty(N, device=dev)
-            ops._wgq.append((dY, X, dW, db, tokens, N, K))
+            ops._pass.wgq.append((dY, X, dW, db, tokens, N, K))
             outs.append((dW, db))
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()

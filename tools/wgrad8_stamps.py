@@ -15,7 +15,7 @@ prob = [(torch.randn(tokens, N, device=dev).bfloat16(), torch.randn(tokens, K, d
 ops.WGRAD8 = True
 for it in range(3):
     for dY, X, N, K in prob:
-        ops._wgq.append((dY, X, torch.empty(N, K, device=dev), torch.empty(N, device=dev), tokens, N, K))
+        ops._pass.wgq.append((dY, X, torch.empty(N, K, device=dev), torch.empty(N, device=dev), tokens, N, K))
     ops.flush_wgrads(); ops.flush_deferred()
 torch.cuda.synchronize()
 buf = (C.c_ulonglong * 4096)()
