@@ -1,7 +1,8 @@
 """Command line + launcher: this package's counterpart of tools/run_net.py:11-25, slowfast/utils/parser.py:13-94,
 slowfast/utils/misc.py:283-311 and slowfast/utils/multiprocessing.py:9-62.  Same flags (--cfg, --init_method,
 --shard_id, --num_shards, trailing KEY VALUE opts); one process per GPU via torch.multiprocessing.spawn, RCCL
-process group, then the train / test drivers below on SYNTHETIC clips (the dataset pipeline is out of scope)."""
+process group, then the train / test drivers below on synthetic clips, or with CSTS_AMD.SYNTHETIC_DATA False on the recorded
+clips under CSTS_AMD.DATA_ROOT (csts_amd.datasets; decoding is out of scope)."""
 from __future__ import annotations
 
 import argparse
@@ -84,13 +85,28 @@ def _meters_on(cfg) -> bool:
     return bool(getattr(cfg.CSTS_AMD, "GAZE_METERS", False))
 
 
+def _recorded(cfg) -> bool:
+    return not getattr(cfg.CSTS_AMD, "SYNTHETIC_DATA", True)
+
+
+def _clip_loader(cfg, split: str, batch: int, dev, rank: int, world: int):
+    """The loader of one split of the recorded clips (CSTS_AMD.DATA_ROOT), logged once."""
+    from . import datasets
+    store = datasets.ClipStore(cfg, split, dev)
+    loader = datasets.ClipLoader(store, batch=batch, world=world, rank=rank)
+    _log({"_type": "data", "split": split, "dataset": store.dataset, "clips": len(store), "batch": batch,
+          "steps_per_epoch": loader.steps(), "resident_mb": float(store.clip_bytes.sum()) / 2 ** 20})
+    return loader
+
+
 @torch.no_grad()
-def eval_epoch(cfg, model, cur_epoch: int, dev, rank: int, world: int):
+def eval_epoch(cfg, model, cur_epoch: int, dev, rank: int, world: int, loader=None):
     """tools/train_avgaze_net.py:158-219 on synthetic validation clips: eval-mode forward -> frame_softmax(T = 2) -> gather of
     predictions / heat-map labels / gaze labels over the ranks (:192-193) -> min-max rescale + adaptive_f1 on the device
     (:196-199) -> the plain means of the per-batch values.  With CSTS_AMD.GAZE_METERS the record follows ValGazeMeter instead
     (meters.py:401-417,455-475): a device-resident "val" meter gathers the per-frame counts, weighs recall and precision of
-    each batch by its sample count and derives f1 from the totals."""
+    each batch by its sample count and derives f1 from the totals.  loader (datasets.ClipLoader of the val split): the pass walks
+    the whole split instead, its short last batch included."""
     from . import train as T
     from . import losses, metrics
     from . import distributed as du
@@ -101,9 +117,13 @@ def eval_epoch(cfg, model, cur_epoch: int, dev, rank: int, world: int):
     n = int(getattr(cfg.CSTS_AMD, "EVAL_STEPS", 2))
     acc = [0.0, 0.0, 0.0]
     meter = metrics.GazeMeter(cfg.TRAIN.DATASET, cfg.LOG_PERIOD, dev, "val") if _meters_on(cfg) else None
-    for it in range(n):
-        batch = T.synthetic_batch(b, cfg.DATA.NUM_FRAMES, cfg.DATA.TEST_CROP_SIZE, 500000 + rank + 7919 * it, dev,
-                                  spatial=T.spatial_config(cfg, train=False))
+    if loader is not None:
+        batches = loader.epoch(cur_epoch, log=_log)
+        n = loader.steps(cur_epoch)
+    else:
+        batches = (T.synthetic_batch(b, cfg.DATA.NUM_FRAMES, cfg.DATA.TEST_CROP_SIZE, 500000 + rank + 7919 * it, dev,
+                                     spatial=T.spatial_config(cfg, train=False)) for it in range(n))
+    for batch in batches:
         preds = losses.frame_softmax(model([batch["video"]], batch["audio"]), temperature=2)
         labels_hm, labels = batch["labels_hm"], batch["labels"]
         if meter is not None:
@@ -137,6 +157,20 @@ def train(cfg):
     dev = torch.device("cuda", torch.cuda.current_device())
     steps = cfg.CSTS_AMD.STEPS_PER_EPOCH
     spatial = T.spatial_config(cfg, train=True)       # CSTS_AMD.SYNTHETIC_SOURCE_HW: on-device scale jitter / crop / flip
+    loader = val_loader = None
+    if _recorded(cfg):
+        # recorded clips: the epoch is the train split (STEPS_PER_EPOCH is ignored; the "data" record holds its length)
+        loader = _clip_loader(cfg, "train", b, dev, rank, world)
+        val_loader = _clip_loader(cfg, "val", max(1, b), dev, rank, world)
+        steps = loader.steps()
+        if steps < 1:
+            raise ValueError(f"the train split holds {len(loader.store)} clips: fewer than one batch of {b} per rank")
+
+    def batches_of(epoch):
+        if loader is not None:
+            return loader.epoch(epoch, log=_log)
+        return (T.synthetic_batch(b, cfg.DATA.NUM_FRAMES, cfg.DATA.TRAIN_CROP_SIZE, 1000 + rank + 7919 * (epoch * steps + it), dev,
+                                  spatial=spatial) for it in range(steps))
     from . import checkpoint as ck
     scaler = T.scaler_of(optimizer)        # fp16 mode: GradScaler state (train_avgaze_net.py:277), saved as "scaler_state"
     start_epoch = ck.load_train_checkpoint(cfg, model, optimizer, scaler=scaler)          # train_avgaze_net.py:280
@@ -160,9 +194,7 @@ def train(cfg):
         last = min(last, start_epoch + int(cfg.CSTS_AMD.EPOCHS_THIS_RUN))
     for epoch in range(start_epoch, last):
         t0 = time.time()
-        for it in range(steps):
-            batch = T.synthetic_batch(b, cfg.DATA.NUM_FRAMES, cfg.DATA.TRAIN_CROP_SIZE, 1000 + rank + 7919 * (epoch * steps + it), dev,
-                                      spatial=spatial)
+        for it, batch in enumerate(batches_of(epoch)):
             lr = T.get_lr_at_epoch(cfg, epoch + float(it) / steps)
             if getattr(cfg.CSTS_AMD, "HIP_GRAPH", True):
                 if graphed is None:
@@ -193,13 +225,15 @@ def train(cfg):
             ep = meter.epoch_stats()                         # TrainGazeMeter.log_epoch_stats, then reset (train_avgaze_net.py:154-155)
             stats.update(f1=ep["f1"], recall=ep["recall"], precision=ep["precision"])
             meter.reset()
+        if loader is not None:
+            stats["replaced_clips"] = loader.replaced      # clips whose label rows ran out, replaced so far (datasets.ClipLoader.table)
         _log(stats)
         if getattr(cfg.CSTS_AMD, "SAVE_CHECKPOINTS", False) and is_checkpoint_epoch(cfg, epoch):
             path = ck.save_checkpoint(cfg.OUTPUT_DIR, model, optimizer, epoch, cfg, scaler=scaler)  # train_avgaze_net.py:337-346 (0.75 GB + moments)
             _log({"_type": "checkpoint", "epoch": epoch + 1, "path": path,
                   "optimizer_steps": int(optimizer.step_count()) if hasattr(optimizer, "step_count") else None})
         if is_eval_epoch(cfg, epoch):                                         # train_avgaze_net.py:338,355-356
-            eval_epoch(cfg, model, epoch, dev, rank, world)
+            eval_epoch(cfg, model, epoch, dev, rank, world, loader=val_loader)
 
 
 @torch.no_grad()
@@ -215,6 +249,8 @@ def test(cfg):
     world = max(cfg.NUM_GPUS, 1)
     b = max(1, min(cfg.TEST.BATCH_SIZE // world, 8))
     dev = torch.device("cuda", torch.cuda.current_device())
+    if _recorded(cfg):
+        return _test_recorded(cfg, model, b, dev, world)
     batch = T.synthetic_batch(b, cfg.DATA.NUM_FRAMES, cfg.DATA.TEST_CROP_SIZE, 2000, dev, spatial=T.spatial_config(cfg, train=False))
     preds = losses.frame_softmax(model([batch["video"]], batch["audio"]), temperature=2)
     # tools/test_avgaze_net.py:66-69: min-max rescale per frame, then the adaptive-threshold F1 -- both on the device
@@ -238,6 +274,23 @@ def test(cfg):
         ds = meter.dataset_stats()
         _log({"_type": "test_final", "recall": ds["recall"], "precision": ds["precision"], "f1": ds["f1"],
               "threshold": ds["threshold"], "iters": steps})
+
+
+def _test_recorded(cfg, model, b: int, dev, world: int):
+    """The whole test split of the recorded clips through TestGazeMeter (test_avgaze_net.py:87-92): ONE adaptive F1 over every
+    frame of the split with one common threshold -> a test_final record; iters = the batches walked."""
+    from . import losses, metrics
+    rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
+    loader = _clip_loader(cfg, "test", b, dev, rank, world)
+    meter = metrics.GazeMeter(cfg.TEST.DATASET, cfg.LOG_PERIOD, dev, "test")
+    iters = 0
+    for batch in loader.epoch(0, log=_log):
+        preds = losses.frame_softmax(model([batch["video"]], batch["audio"]), temperature=2)
+        meter.update(preds, batch["labels_hm"], batch["labels"])
+        iters += 1
+    ds = meter.dataset_stats()
+    _log({"_type": "test_final", "recall": ds["recall"], "precision": ds["precision"], "f1": ds["f1"],
+          "threshold": ds["threshold"], "iters": iters, "clips": len(loader.store)})
 
 
 def main(argv=None):

@@ -108,7 +108,9 @@ def get_cfg() -> CfgNode:
     c.DIST_BACKEND = "nccl"          # == RCCL on ROCm
     # this implementation's switches
     c.CSTS_AMD = _node(COMPUTE="auto",               # "fp32": exact-fp32 MFMA parity mode ; "bf16": throughput mode ; "fp16": the reference's autocast arithmetic + dynamic loss scaling ; "auto": by TRAIN.MIXED_PRECISION (model.resolve_compute)
-                       SYNTHETIC_DATA=True,          # the data pipeline is out of scope: synthetic clips
+                       SYNTHETIC_DATA=True,          # True: synthetic clips drawn every step; False: the recorded clips under DATA_ROOT (csts_amd.datasets; decoding stays out of scope: the clips are pre-decoded .npz files)
+                       DATA_ROOT="",                 # the data set's directory: train.csv, test.csv, clips/<video>/<clip>.npz, gaze_frame_label/<video>_frame_label.csv (csts_amd/datasets.py; tools/make_toy_dataset.py writes a small one)
+                       DATA_RESIDENT_GB=0,           # 0: the whole split lives on the device (an error names this key when it does not fit); > 0: an epoch's permutation is cut into consecutive groups of at most that many GiB, each uploaded before its batches run
                        SYNTHETIC_SOURCE_HW=[],       # [H, W]: synthetic uint8 frames at that size go through the on-device spatial sampling (inputs.spatial_sampling): train mode in the train loop, test mode in eval / test; [] = frames at the crop size, normalised only
                        STEPS_PER_EPOCH=50,
                        EPOCHS_THIS_RUN=0,            # > 0: stop this invocation after that many epochs (pre-emption; the next one auto-resumes)
@@ -136,6 +138,12 @@ def assert_and_infer_cfg(cfg: CfgNode) -> CfgNode:
         cfg.SOLVER.WARMUP_START_LR *= cfg.NUM_SHARDS
         cfg.SOLVER.COSINE_END_LR *= cfg.NUM_SHARDS
     assert cfg.SHARD_ID < cfg.NUM_SHARDS
+    if not getattr(cfg.CSTS_AMD, "SYNTHETIC_DATA", True):
+        if not str(getattr(cfg.CSTS_AMD, "DATA_ROOT", "") or ""):
+            raise ValueError("config error: CSTS_AMD.SYNTHETIC_DATA False needs CSTS_AMD.DATA_ROOT (the directory of the recorded clips)")
+        if cfg.NUM_GPUS > 1:
+            raise NotImplementedError("config error: recorded clips (CSTS_AMD.SYNTHETIC_DATA False) run on NUM_GPUS 1; the "
+                                      "data-parallel walk of the val / test splits is a follow-up")
     return cfg
 
 

@@ -233,6 +233,150 @@ def clip_sample(video_u8: torch.Tensor, frames_idx: torch.Tensor, params: torch.
     return out
 
 
+def _clip_table(clips, B=None):
+    """The clip table {byte offset, N, H, W} as a contiguous int64 (B, 4) tensor; the caller validates its rows."""
+    if clips.dtype != torch.int64 or clips.dim() != 2 or clips.shape[1] != 4 or clips.shape[0] < 1 or \
+            (B is not None and clips.shape[0] != B):
+        raise ValueError(f"clips must be int64 ({'B' if B is None else B}, 4) = byte offset, N, H, W, got {tuple(clips.shape)} "
+                         f"{clips.dtype}")
+    return clips.contiguous()
+
+
+def batch_params(labels: torch.Tensor, clips: torch.Tensor, crop_size: int, *, train: bool, min_scale: int = 0, max_scale: int = 0,
+                 spatial_idx: int = 1, random_flip: bool = True, inverse_uniform: bool = False, generator=None,
+                 key: torch.Tensor = None, clips_host=None):
+    """The rule pass of spatial_sampling for clips of B recordings of B frame sizes (csts_batch_params): labels floating
+    (B, T, L >= 2), clips int64 (B, 4) = {byte offset, N, H, W} on the device (H, W are read there) -> (params int32 (B, 5),
+    labels fp64 (B, T, L)).  Clip b draws the variates u[b] under the key (drawn from `generator` as spatial_sampling draws it,
+    or given), so with equal sizes the result is spatial_sampling's.  clips_host: the same table on the host (anything
+    numpy.asarray takes); given, its H, W are validated without a device read (ValueError)."""
+    if labels.dim() != 3 or labels.shape[2] < 2 or not labels.is_floating_point():
+        raise ValueError(f"labels must be floating (B, T, L >= 2), got {tuple(labels.shape)} {labels.dtype}")
+    B, T, ncol = labels.shape
+    tab = _clip_table(clips, B)
+    S = int(crop_size)
+    if not 1 <= T <= 64:
+        raise ValueError(f"spatial sampling takes 1 <= T <= 64 frames per clip, got {T}")
+    if S < 1:
+        raise ValueError(f"crop_size must be positive, got {S}")
+    if train:
+        min_scale, max_scale = int(min_scale), int(max_scale)
+        if min_scale < S:
+            raise ValueError(f"the short side would end up below the crop: min_scale {min_scale} < crop_size {S}")
+        if max_scale < min_scale:
+            raise ValueError(f"max_scale {max_scale} < min_scale {min_scale}")
+        idx = -1
+    else:
+        idx = int(spatial_idx)
+        if idx not in (0, 1, 2):
+            raise ValueError(f"spatial_idx must be 0, 1 or 2 in test mode, got {spatial_idx}")
+    if clips_host is not None:
+        import numpy as np
+        hw = np.asarray(clips_host).reshape(-1, 4)[:, 2:]
+        if hw.shape[0] != B or int(hw.min()) < 1:
+            raise ValueError(f"the clip table must hold {B} rows with H, W >= 1, got {hw.tolist()}")
+    _gpu(labels, tab)
+    lab = labels.to(torch.float64).contiguous()
+    dev = lab.device
+    if not train:
+        key = None
+    elif key is None:
+        key = torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64, device=dev, generator=generator)
+    elif key.dtype != torch.int64 or key.numel() != 1 or key.device != dev:
+        raise ValueError("key must be an int64 tensor of one element on the labels' device")
+    params = torch.empty(B, 5, dtype=torch.int32, device=dev)
+    new_labels = torch.empty_like(lab)
+    L.check(L.load().csts_batch_params(key.data_ptr() if key is not None else None, lab.data_ptr(), tab.data_ptr(), B, T, ncol, S,
+                                       min_scale, max_scale, idx, int(bool(random_flip)), int(bool(inverse_uniform)),
+                                       params.data_ptr(), new_labels.data_ptr(), _s()), "csts_batch_params")
+    return params, new_labels
+
+
+def batch_sample(arena_u8: torch.Tensor, clips: torch.Tensor, frames_idx: torch.Tensor, params: torch.Tensor, crop_size: int,
+                 clips_host, mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225), out: torch.Tensor = None) -> torch.Tensor:
+    """clip_sample for clips of B different recordings in ONE launch (csts_batch_sample): arena_u8 uint8 (bytes,) holds the
+    recordings back to back at any byte, clips int64 (B, 4) = {byte offset, N, H, W} on the device, frames_idx int32 (B, T)
+    (clamped to [0, N_b - 1] on the device), params int32 (B, 5) -> fp32 (B, 3, T, S, S); clip b is, bit for bit,
+    clip_sample(recording_b, frames_idx[b:b+1], params[b:b+1], S).  clips_host: the table on the host; every row must lie inside
+    the arena with N, H, W >= 1 (ValueError) -- the device reads the tables when the kernel runs and gives a NaN clip for a row
+    that does not, so a captured launch stays safe when the tables are rewritten."""
+    import numpy as np
+    if arena_u8.dtype != torch.uint8 or arena_u8.dim() != 1 or arena_u8.numel() < 3:
+        raise ValueError(f"the arena must be uint8 (bytes,), got {tuple(arena_u8.shape)} {arena_u8.dtype}")
+    if frames_idx.dtype != torch.int32 or frames_idx.dim() != 2:
+        raise ValueError(f"frames_idx must be int32 (B, T), got {tuple(frames_idx.shape)} {frames_idx.dtype}")
+    B, T = frames_idx.shape
+    if not 1 <= T <= 64 or B < 1:
+        raise ValueError(f"clip sampling takes B >= 1 clips of 1 <= T <= 64 frames, got B {B}, T {T}")
+    tab = _clip_table(clips, B)
+    if params.dtype != torch.int32 or tuple(params.shape) != (B, 5):
+        raise ValueError(f"params must be int32 ({B}, 5), got {tuple(params.shape)} {params.dtype}")
+    S = int(crop_size)
+    if S < 1:
+        raise ValueError(f"crop_size must be positive, got {S}")
+    host = np.asarray(clips_host, dtype=np.int64).reshape(-1, 4)
+    if host.shape[0] != B:
+        raise ValueError(f"the host clip table has {host.shape[0]} rows, the batch {B}")
+    nbytes = arena_u8.numel()
+    for b, (off, n, h, w) in enumerate(host.tolist()):
+        if n < 1 or h < 1 or w < 1 or w > 6000 or off < 0 or off + n * h * w * 3 > nbytes:
+            raise ValueError(f"clip {b}: recording (offset {off}, N {n}, H {h}, W {w}) does not lie inside the arena of {nbytes} "
+                             "bytes (or W > 6000)")
+    _gpu(arena_u8, tab, frames_idx, params)
+    if not arena_u8.is_contiguous() or arena_u8.data_ptr() % 16:
+        raise ValueError("the arena must be contiguous and 16-byte aligned")
+    if out is None:
+        out = torch.empty(B, 3, T, S, S, dtype=torch.float32, device=arena_u8.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, 3, T, S, S) or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"out must be a contiguous fp32 ({B}, 3, {T}, {S}, {S}) GPU tensor")
+    f3 = C.c_float * 3
+    idx, par = frames_idx.contiguous(), params.contiguous()
+    L.check(L.load().csts_batch_sample(arena_u8.data_ptr(), nbytes, tab.data_ptr(), idx.data_ptr(), par.data_ptr(), out.data_ptr(),
+                                       B, T, S, int(host[:, 3].max()), f3(*mean), f3(*std), _s()), "csts_batch_sample")
+    return out
+
+
+def audio_gather(spec_arena: torch.Tensor, specs: torch.Tensor, centers: torch.Tensor, nbins: int, specs_host, width: int = 256,
+                 out: torch.Tensor = None) -> torch.Tensor:
+    """audio_windows_at for clips of B different recordings in ONE launch (csts_audio_gather): spec_arena fp32 (floats,) holds
+    one (nbins, stride_b) spectrogram per clip, specs int64 (B, 3) = {float offset, row stride, usable columns} on the device,
+    centers int32 (B, T) -> (B, 1, T, nbins, width); window (b, t) = spec_b[:, c - width/2 : c + width/2], c clamped to
+    [width/2, usable_b - 1 - width/2] on the device: audio_windows_at(spec_b[:, :usable_b], centers[b:b+1]).  specs_host: the
+    table on the host, validated against the arena (ValueError)."""
+    import numpy as np
+    if spec_arena.dtype != torch.float32 or spec_arena.dim() != 1:
+        raise ValueError(f"the spectrogram arena must be fp32 (floats,), got {tuple(spec_arena.shape)} {spec_arena.dtype}")
+    if centers.dtype != torch.int32 or centers.dim() != 2:
+        raise ValueError(f"centers must be int32 (B, T), got {tuple(centers.shape)} {centers.dtype}")
+    B, T = centers.shape
+    if specs.dtype != torch.int64 or tuple(specs.shape) != (B, 3):
+        raise ValueError(f"specs must be int64 ({B}, 3) = float offset, row stride, usable columns, got {tuple(specs.shape)} "
+                         f"{specs.dtype}")
+    nbins, width = int(nbins), int(width)
+    if nbins < 1 or width < 2 or width % 2 or B < 1 or T < 1 or B * T > 65535:
+        raise ValueError(f"bad sizes: nbins {nbins}, width {width} (even), B {B}, T {T} (B * T <= 65535)")
+    host = np.asarray(specs_host, dtype=np.int64).reshape(-1, 3)
+    if host.shape[0] != B:
+        raise ValueError(f"the host spectrogram table has {host.shape[0]} rows, the batch {B}")
+    nfl = spec_arena.numel()
+    for b, (off, stride, usable) in enumerate(host.tolist()):
+        if off < 0 or usable > stride or off + nbins * stride > nfl:
+            raise ValueError(f"clip {b}: spectrogram (offset {off}, stride {stride}, usable {usable}) does not lie inside the arena "
+                             f"of {nfl} floats")
+        if usable < width + 1:
+            raise ValueError(f"clip {b}: the spectrogram has {usable} usable columns, a window needs {width + 1}")
+    _gpu(spec_arena, specs, centers)
+    if not spec_arena.is_contiguous():
+        raise ValueError("the spectrogram arena must be contiguous")
+    if out is None:
+        out = torch.empty(B, 1, T, nbins, width, dtype=torch.float32, device=spec_arena.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, 1, T, nbins, width) or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"out must be a contiguous fp32 ({B}, 1, {T}, {nbins}, {width}) GPU tensor")
+    L.check(L.load().csts_audio_gather(spec_arena.data_ptr(), specs.contiguous().data_ptr(), centers.contiguous().data_ptr(),
+                                       out.data_ptr(), B, T, nbins, width, _s()), "csts_audio_gather")
+    return out
+
+
 def spatial_rule_host(labels, H: int, W: int, crop_size: int, *, train: bool, uniforms=None, min_scale: int = 0,
                       max_scale: int = 0, spatial_idx: int = 1, random_flip: bool = True, inverse_uniform: bool = False):
     """The rule of spatial_sampling on the CPU (csts_spatial_rule_host) from explicit variates: labels float64 (B, T, L),

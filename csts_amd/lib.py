@@ -255,6 +255,9 @@ SYMBOLS = {
     "csts_clip_sample": (_I, [vp, i64, vp, vp, vp, _I, _I, _I, _I, _I, C.c_float * 3, C.c_float * 3, vp]),
     "csts_spatial_rule_host": (_I, [vp, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, vp, vp, vp]),
     "csts_spatial_uniforms_host": (_I, [_U32, _U32, C.c_uint64, i64, vp]),
+    "csts_batch_params": (_I, [vp, vp, vp, _I, _I, _I, _I, _I, _I, _I, _I, _I, vp, vp, vp]),
+    "csts_batch_sample": (_I, [vp, i64, vp, vp, vp, vp, _I, _I, _I, _I, C.c_float * 3, C.c_float * 3, vp]),
+    "csts_audio_gather": (_I, [vp, vp, vp, vp, _I, _I, _I, _I, vp]),
     "csts_adaptive_f1_workspace": (sz, [i64, _I]),
     "csts_adaptive_f1": (_I, [vp, vp, vp, vp, _I, i64, _I, _I, vp, vp, sz, vp]),
     "csts_f1_counts": (_I, [vp, vp, vp, _I, i64, _I, _I, vp, vp]),

@@ -544,6 +544,32 @@ int csts_spatial_rule_host(const double* labels, int B, int T, int L, int H, int
                            double* labels_out);
 int csts_spatial_uniforms_host(uint32_t key0, uint32_t key1, uint64_t first, int64_t count, double* out);
 
+/* ---- batch assembly from many recordings (csts_amd/csrc/batch.hip, csts_amd/datasets.py): the clips of one batch come from B
+ *      different recordings, possibly of B frame sizes, all resident in arenas.  Every table below is DEVICE memory, read when
+ *      the kernel runs: no host sync, no allocation, no atomics, graph-capturable; rewriting the tables between replays
+ *      assembles the next batch.
+ *      batch_params: csts_spatial_params with the frame size of clip b taken from clips[b] = {byte offset, N, H, W} (int64; only
+ *        H, W are read here).  Clip b draws the variates u[b] of the rule above, so a batch of equal sizes equals
+ *        csts_spatial_params bit for bit.  A row with H or W below 1 or outside the rule's range gives params {-1 x 5} (a NaN clip
+ *        in every sample pass) and NaN labels.
+ *      batch_sample: the pixel rule of csts_spatial_sample / csts_clip_sample, clip b read from its own recording: frame t of
+ *        clip b is frame min(max(frames_idx[b][t], 0), N_b - 1) of the (N_b, H_b, W_b, 3) uint8 recording that starts at byte
+ *        clips[b][0] of arena_u8.  A recording starts at any byte; only arena_u8 and out must be 16-byte aligned.  LDS is sized
+ *        from max_W (<= 6000).  A row gives a NaN clip and reads nothing if [offset, offset + N H W 3) leaves [0, arena_bytes), or
+ *        W > max_W, or N, H or W is below 1; no byte at or past arena_bytes is ever read.  out fp32 (B, 3, T, S, S), T <= 64.
+ *      audio_gather: window (b, t) = spec_b[:, c - width/2 : c + width/2] with c = centers[b][t] clamped to
+ *        [width/2, usable_b - 1 - width/2]; spec_b starts at float specs[b][0] of spec_arena and has rows of specs[b][1] floats, of
+ *        which the first specs[b][2] = usable_b are read (the trimmed spectrogram of ego4d_avgaze_forecast.py:215); specs int64
+ *        [B][3].  out (B, 1, T, nbins, width), width even, B * T <= 65535.  A row with a negative offset, usable > stride or usable <
+ *        width + 1 gives NaN windows and reads nothing; the caller vouches that offset + nbins * stride stays inside the arena. */
+int csts_batch_params(const uint64_t* key, const double* labels, const int64_t* clips, int B, int T, int L, int S, int min_scale,
+                      int max_scale, int spatial_idx, int random_flip, int inv_uniform, int* params, double* labels_out,
+                      hipStream_t stream);
+int csts_batch_sample(const uint8_t* arena_u8, int64_t arena_bytes, const int64_t* clips, const int* frames_idx, const int* params,
+                      float* out, int B, int T, int S, int max_W, const float mean[3], const float std[3], hipStream_t stream);
+int csts_audio_gather(const float* spec_arena, const int64_t* specs, const int* centers, float* out, int B, int T, int nbins,
+                      int width, hipStream_t stream);
+
 /* ---- gaze head of the inference path (csts_amd/csrc/decode.hip): one read of a frame's logits gives every consumer of a
  *      prediction what it needs.  logits: nframes = B * T frames of H * W cells each, the (B, 1, T, H, W) model output, fp32
  *      (dt CSTS_F32) or the 16-bit type of the library (dt CSTS_BF16); arithmetic is fp32 in both libraries.  Rule, per frame,
