@@ -150,44 +150,17 @@ void launch_decode(bool vec, unsigned nframes, hipStream_t stream, const void* l
                           rescaled, points, peak);
 }
 
-// One workgroup per output frame f: order[offsets[f] .. offsets[f + 1]) are its prediction rows, added in that order.
+// The tail gaze_track and gaze_track_fill share: the frame's map m (registers, layout of cell_of) -> its max + arg-max (a lane
+// walks its cells in ascending index order) and its min, then heatmaps = m, rescaled, points and peak of frame blockIdx.x.
+// live = false (nobody predicts the frame; the caller passes m = 0): maps 0, points NaN, peak 0.
 template <int NCH, bool VEC>
-__global__ __launch_bounds__(256) void gaze_track_kernel(const float* __restrict__ preds, const int* __restrict__ order,
-                                                         const int* __restrict__ offsets, int H, int W,
-                                                         float* __restrict__ heatmaps, float* __restrict__ rescaled,
-                                                         float* __restrict__ points, float* __restrict__ peak,
-                                                         int* __restrict__ count) {
+__device__ __forceinline__ void track_tail(const float (&m)[NCH * 4], bool live, int H, int W, float* __restrict__ heatmaps,
+                                           float* __restrict__ rescaled, float* __restrict__ points, float* __restrict__ peak) {
   __shared__ float red_v[2][4];
   __shared__ int red_i[4];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int hw = H * W;
   const int64_t frame = blockIdx.x, base = frame * hw;
-  const int beg = offsets[frame], n = offsets[frame + 1] - beg;          // uniform over the workgroup
-  float m[NCH * 4];
-#pragma unroll
-  for (int k = 0; k < NCH * 4; ++k) m[k] = 0.f;
-  for (int j = 0; j < n; ++j) {
-    const float* row = preds + (int64_t)order[beg + j] * hw;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      if (VEC) {
-        const int at = (c * 256 + tid) * 4;
-        if (at < hw) {                  // hw % 4 == 0 on this path: a chunk is inside the frame or outside it
-          const f32x4 v = *reinterpret_cast<const f32x4*>(row + at);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) m[c * 4 + r] += v[r];
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int at = cell_of<false>(c, r, tid);
-          if (at < hw) m[c * 4 + r] += row[at];
-        }
-      }
-    }
-  }
-  const float inv = n > 0 ? 1.f / (float)n : 0.f;
-  // ---- the mean map, its max + arg-max (a lane walks its cells in ascending index order) and its min
   float bv = -INFINITY, mn = INFINITY;
   int bi = 0x7fffffff;
 #pragma unroll
@@ -195,7 +168,6 @@ __global__ __launch_bounds__(256) void gaze_track_kernel(const float* __restrict
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int at = cell_of<VEC>(c, r, tid);
-      m[c * 4 + r] *= inv;
       if (at < hw) {
         take_max(bv, bi, m[c * 4 + r], at);
         mn = fminf(mn, m[c * 4 + r]);
@@ -238,12 +210,52 @@ __global__ __launch_bounds__(256) void gaze_track_kernel(const float* __restrict
   if (tid == 0) {
     if (points) {
       const int row = bi / W, col = bi - row * W;
-      points[frame * 2] = n > 0 ? (float)col / (float)W : __builtin_nanf("");
-      points[frame * 2 + 1] = n > 0 ? (float)row / (float)H : __builtin_nanf("");
+      points[frame * 2] = live ? (float)col / (float)W : __builtin_nanf("");
+      points[frame * 2 + 1] = live ? (float)row / (float)H : __builtin_nanf("");
     }
-    if (peak) peak[frame] = n > 0 ? bv : 0.f;
-    if (count) count[frame] = n;
+    if (peak) peak[frame] = live ? bv : 0.f;
   }
+}
+
+// One workgroup per output frame f: order[offsets[f] .. offsets[f + 1]) are its prediction rows, added in that order.
+template <int NCH, bool VEC>
+__global__ __launch_bounds__(256) void gaze_track_kernel(const float* __restrict__ preds, const int* __restrict__ order,
+                                                         const int* __restrict__ offsets, int H, int W,
+                                                         float* __restrict__ heatmaps, float* __restrict__ rescaled,
+                                                         float* __restrict__ points, float* __restrict__ peak,
+                                                         int* __restrict__ count) {
+  const int tid = threadIdx.x;
+  const int hw = H * W;
+  const int64_t frame = blockIdx.x;
+  const int beg = offsets[frame], n = offsets[frame + 1] - beg;          // uniform over the workgroup
+  float m[NCH * 4];
+#pragma unroll
+  for (int k = 0; k < NCH * 4; ++k) m[k] = 0.f;
+  for (int j = 0; j < n; ++j) {
+    const float* row = preds + (int64_t)order[beg + j] * hw;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      if (VEC) {
+        const int at = (c * 256 + tid) * 4;
+        if (at < hw) {                  // hw % 4 == 0 on this path: a chunk is inside the frame or outside it
+          const f32x4 v = *reinterpret_cast<const f32x4*>(row + at);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) m[c * 4 + r] += v[r];
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int at = cell_of<false>(c, r, tid);
+          if (at < hw) m[c * 4 + r] += row[at];
+        }
+      }
+    }
+  }
+  const float inv = n > 0 ? 1.f / (float)n : 0.f;
+#pragma unroll
+  for (int k = 0; k < NCH * 4; ++k) m[k] *= inv;
+  track_tail<NCH, VEC>(m, n > 0, H, W, heatmaps, rescaled, points, peak);
+  if (tid == 0 && count) count[frame] = n;
 }
 
 template <int NCH>
@@ -253,6 +265,80 @@ void launch_track(bool vec, unsigned nframes, hipStream_t stream, const float* p
                               heatmaps, rescaled, points, peak, count);
   else hipLaunchKernelGGL((gaze_track_kernel<NCH, false>), dim3(nframes), dim3(256), 0, stream, preds, order, offsets, H, W,
                           heatmaps, rescaled, points, peak, count);
+}
+
+// gaze_track_fill: one workgroup per output frame n.  A predicted frame (count[n] > 0) passes through; any other frame looks
+// for its nearest predicted neighbours a < n < b itself, at most max_gap - 1 frames each way (count is read at wave-uniform
+// addresses), and takes H_a (hold) or wa H_a + wb H_b (linear) when b - a <= max_gap.  The map then goes through track_tail,
+// so a predicted frame leaves with the bits gaze_track wrote for it.
+template <int NCH, bool VEC>
+__device__ __forceinline__ void load_map(float (&m)[NCH * 4], const float* __restrict__ row, int hw, int tid) {
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    if (VEC) {
+      const int at = (c * 256 + tid) * 4;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (at < hw) v = *reinterpret_cast<const f32x4*>(row + at);       // hw % 4 == 0 on this path
+#pragma unroll
+      for (int r = 0; r < 4; ++r) m[c * 4 + r] = v[r];
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int at = cell_of<false>(c, r, tid);
+        m[c * 4 + r] = at < hw ? row[at] : 0.f;
+      }
+    }
+  }
+}
+
+template <int NCH, bool VEC>
+__global__ __launch_bounds__(256) void gaze_fill_kernel(const float* __restrict__ maps, const int* __restrict__ count, int F, int H,
+                                                        int W, int mode, int max_gap, float* __restrict__ heatmaps,
+                                                        float* __restrict__ rescaled, float* __restrict__ points,
+                                                        float* __restrict__ peak, int* __restrict__ neighbours) {
+  const int tid = threadIdx.x;
+  const int hw = H * W;
+  const int n = blockIdx.x;                                               // uniform over the workgroup, as a, b below
+  int a = -1, b = -1;
+  if (count[n] > 0) {
+    a = b = n;
+  } else {
+    const int lo = max(n - (max_gap - 1), 0);
+    for (int j = n - 1; j >= lo; --j)
+      if (count[j] > 0) { a = j; break; }
+    if (a >= 0) {
+      const int hi = (int)min((int64_t)a + max_gap, (int64_t)F - 1);     // b - a <= max_gap
+      for (int j = n + 1; j <= hi; ++j)
+        if (count[j] > 0) { b = j; break; }
+    }
+    if (b < 0) a = -1;
+  }
+  float m[NCH * 4];
+  if (a < 0) {
+#pragma unroll
+    for (int k = 0; k < NCH * 4; ++k) m[k] = 0.f;
+  } else {
+    load_map<NCH, VEC>(m, maps + (int64_t)a * hw, hw, tid);
+    if (mode == 1 && b != a) {
+      float hb[NCH * 4];
+      load_map<NCH, VEC>(hb, maps + (int64_t)b * hw, hw, tid);
+      const float span = (float)(b - a);
+      const float wa = (float)(b - n) / span, wb = (float)(n - a) / span;
+#pragma unroll
+      for (int k = 0; k < NCH * 4; ++k) m[k] = wa * m[k] + wb * hb[k];
+    }
+  }
+  track_tail<NCH, VEC>(m, a >= 0, H, W, heatmaps, rescaled, points, peak);
+  if (tid == 0 && neighbours) { neighbours[2 * (int64_t)n] = a; neighbours[2 * (int64_t)n + 1] = b; }
+}
+
+template <int NCH>
+void launch_fill(bool vec, unsigned nframes, hipStream_t stream, const float* maps, const int* count, int H, int W, int mode,
+                 int max_gap, float* heatmaps, float* rescaled, float* points, float* peak, int* neighbours) {
+  if (vec) hipLaunchKernelGGL((gaze_fill_kernel<NCH, true>), dim3(nframes), dim3(256), 0, stream, maps, count, (int)nframes, H, W,
+                              mode, max_gap, heatmaps, rescaled, points, peak, neighbours);
+  else hipLaunchKernelGGL((gaze_fill_kernel<NCH, false>), dim3(nframes), dim3(256), 0, stream, maps, count, (int)nframes, H, W,
+                          mode, max_gap, heatmaps, rescaled, points, peak, neighbours);
 }
 
 }  // namespace
@@ -293,6 +379,30 @@ extern "C" int csts_gaze_track(const float* preds, const int* order, const int* 
   else if (nch <= 2) launch_track<2>(vec, n, stream, preds, order, offsets, H, W, heatmaps, rescaled, points, peak, count);
   else if (nch <= 4) launch_track<4>(vec, n, stream, preds, order, offsets, H, W, heatmaps, rescaled, points, peak, count);
   else launch_track<8>(vec, n, stream, preds, order, offsets, H, W, heatmaps, rescaled, points, peak, count);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_gaze_track_fill(const float* heatmaps, const int* count, int64_t F, int H, int W, int mode, int max_gap,
+                                    float* out_heatmaps, float* out_rescaled, float* out_points, float* out_peak,
+                                    int* out_neighbours, hipStream_t stream) {
+  CSTS_REQUIRE(heatmaps && count, "null heatmaps or count");
+  CSTS_REQUIRE(F >= 1 && F < ((int64_t)1 << 31), "1 <= frames < 2^31");
+  CSTS_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W <= CSTS_GAZE_DECODE_MAX_HW, "1 <= H * W <= CSTS_GAZE_DECODE_MAX_HW (the frame is held in registers)");
+  CSTS_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (hold) or 1 (linear)");
+  CSTS_REQUIRE(max_gap >= 1 && max_gap <= CSTS_GAZE_FILL_MAX_GAP, "1 <= max_gap <= CSTS_GAZE_FILL_MAX_GAP");
+  CSTS_REQUIRE(out_heatmaps != heatmaps && out_rescaled != heatmaps && (const void*)out_points != (const void*)heatmaps &&
+                   (const void*)out_peak != (const void*)heatmaps && (const void*)out_neighbours != (const void*)heatmaps,
+               "no output may be heatmaps (a frame reads its neighbours' maps)");
+  if (!out_heatmaps && !out_rescaled && !out_points && !out_peak && !out_neighbours) return 0;
+  const int hw = H * W;
+  const bool vec = hw % 4 == 0 && aligned16(heatmaps) && aligned16(out_heatmaps) && aligned16(out_rescaled);
+  const int nch = (int)cdiv(hw, 1024);
+  const unsigned n = (unsigned)F;
+  if (nch <= 1) launch_fill<1>(vec, n, stream, heatmaps, count, H, W, mode, max_gap, out_heatmaps, out_rescaled, out_points, out_peak, out_neighbours);
+  else if (nch <= 2) launch_fill<2>(vec, n, stream, heatmaps, count, H, W, mode, max_gap, out_heatmaps, out_rescaled, out_points, out_peak, out_neighbours);
+  else if (nch <= 4) launch_fill<4>(vec, n, stream, heatmaps, count, H, W, mode, max_gap, out_heatmaps, out_rescaled, out_points, out_peak, out_neighbours);
+  else launch_fill<8>(vec, n, stream, heatmaps, count, H, W, mode, max_gap, out_heatmaps, out_rescaled, out_points, out_peak, out_neighbours);
   CSTS_LAUNCH_CHECK();
   return 0;
 }

@@ -92,6 +92,59 @@ def plan_video(cfg, n_frames, fps=None, stride=None, segment=None, cols=None):
     return plan
 
 
+def default_max_gap(plan):
+    """The widest step between two consecutive predictions of one window of `plan` (plan_video): max(diff(plan["targets"])) =
+    SAMPLING_RATE + 1 for the shipped YAMLs (9 for Ego4D, 5 for Aria).  As the max_gap of fill_track it fills the gaps inside a
+    window and the one-frame seam between default-stride windows, and leaves a stretch nobody forecasts empty."""
+    import numpy as np
+    targets = np.asarray(plan["targets"], dtype=np.int64)
+    if targets.size < 2:
+        return 1
+    return max(1, int(np.diff(targets).max()))
+
+
+def fill_plan(count, max_gap):
+    """The rule of csts_gaze_track_fill (include/csts_hip.h) on the host: count (N,) = windows per frame -> int64 (N, 2)
+    neighbours.  A predicted frame n (count > 0) has (n, n).  Any other frame has a = the largest predicted frame below it and
+    b = the smallest above it; both exist and b - a <= max_gap: (a, b), the frame is filled; otherwise (-1, -1).  Nothing
+    before the first or after the last predicted frame is filled."""
+    import numpy as np
+    count = np.asarray(count).reshape(-1)
+    max_gap = int(max_gap)
+    if max_gap < 1:
+        raise ValueError(f"max_gap must be positive, got {max_gap}")
+    N = count.shape[0]
+    idx = np.arange(N, dtype=np.int64)
+    pred = count > 0
+    a = np.maximum.accumulate(np.where(pred, idx, -1))                             # the last predicted frame <= n
+    b = np.minimum.accumulate(np.where(pred, idx, N)[::-1])[::-1]                  # the first predicted frame >= n, N: none
+    ok = pred | ((a >= 0) & (b < N) & (b - a <= max_gap))
+    return np.where(ok[:, None], np.stack([a, b], axis=-1), -1).astype(np.int64)
+
+
+def fill_track(track, mode="linear", max_gap=None, plan=None):
+    """The sparse track of predict_video with the frames between neighbouring predictions filled (ops.gaze_track_fill,
+    csts_gaze_track_fill).  track: a dict with "heatmaps" fp32 (N, h, w) and "count" int32 (N,) on the device -- what
+    predict_video returned, or the arrays of its .npz moved to the device.  mode "hold" repeats the earlier map (what the
+    reference's visualisation does), "linear" blends the two neighbours by time.  max_gap: the widest distance b - a between
+    two predictions that is still filled; None takes default_max_gap(plan) and needs plan= (the plan_video result of the
+    recording).  Returns a NEW dict: "heatmaps", "rescaled", "points" and "peak" filled (predicted frames keep their bits),
+    "neighbours" int32 (N, 2), "filled" bool (N,) = count == 0 and a neighbour exists, "max_gap" = the gap that was applied
+    (a host int); "count" and every other entry as they
+    were, except "points_source" and "overlay", which describe the sparse track and are left out.  The input is not modified."""
+    if "heatmaps" not in track or "count" not in track:
+        raise ValueError("fill_track needs the track's \"heatmaps\" and \"count\": call predict_video with return_heatmaps=True")
+    if max_gap is None:
+        if plan is None:
+            raise ValueError("fill_track needs max_gap, or plan= (the plan_video result) to take default_max_gap from")
+        max_gap = default_max_gap(plan)
+    out = {k: v for k, v in track.items() if k not in ("points_source", "overlay")}
+    out.update(ops.gaze_track_fill(track["heatmaps"], track["count"], mode=mode, max_gap=int(max_gap)))
+    out["filled"] = (track["count"] == 0) & (out["neighbours"][:, 0] >= 0)
+    out["max_gap"] = int(max_gap)
+    return out
+
+
 def points_to_source(points, params_row, crop_size):
     """Gaze points (N, 2) = (x, y) normalised on the S x S crop -> the same points normalised on the SOURCE frame the crop was cut
     from: x_src = (x S + x0) / new w, y_src = (y S + y0) / new h, the inverse of the label rule of the spatial sampling.
@@ -320,7 +373,8 @@ class GazePredictor:
         return out
 
     @torch.no_grad()
-    def predict_video(self, frames_u8, wav, fps=None, stride=None, batch=None, return_heatmaps=True, overlay=False):
+    def predict_video(self, frames_u8, wav, fps=None, stride=None, batch=None, return_heatmaps=True, overlay=False, fill=None,
+                      max_gap=None):
         """A whole recording in, one gaze track out: frames_u8 uint8 (N, H, W, 3) and wav fp32 (n,) at 24 kHz, both resident on
         the device -> {"points": (N, 2), "peak": (N,), "count": (N,) int32 = windows that predicted the frame, "heatmaps" and
         "rescaled": (N, S/4, S/4) (left out with return_heatmaps=False), "windows": their number}, on the device.
@@ -333,7 +387,16 @@ class GazePredictor:
         windows * T heat maps are averaged per video frame and decoded again by ops.gaze_track; frames no window predicts have
         count 0, NaN points and zero maps.  The points are in the crop's coordinates.  overlay=True adds "points_source" (N, 2)
         float64 = the points normalised on the source frame (points_to_source) and "overlay" uint8 (N, H, W, 3) =
-        render_track of this track with its defaults."""
+        render_track of this track with its defaults.
+
+        fill: None (the sparse track above), "hold" or "linear": the track is fill_track of the sparse one, so every frame
+        between two predictions at most max_gap frames apart (default: default_max_gap of the plan, SAMPLING_RATE + 1) carries
+        a map and a point; "count" stays, "neighbours" (N, 2) int32, "filled" (N,) bool and "max_gap" (the gap applied, a host
+        int) are added, and overlay=True draws the filled track.  Still one forward pass per window."""
+        if fill not in (None, "hold", "linear"):
+            raise ValueError(f"fill must be None, \"hold\" or \"linear\", got {fill!r}")
+        if fill is None and max_gap is not None:
+            raise ValueError("max_gap belongs to a fill mode: pass fill=\"hold\" or fill=\"linear\"")
         for t in (frames_u8, wav):
             if not torch.is_tensor(t) or not t.is_cuda:
                 raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
@@ -374,12 +437,17 @@ class GazePredictor:
                     audio = audio[:, :, :, :S, o:o + S].contiguous()
                 out = self.predict_batch({"video": video, "audio": audio})
                 preds[w0 * T:(w0 + n) * T] = out["heatmaps"][:n].reshape(n * T, S // 4, S // 4)
-            want = ("points", "peak", "count") + (("heatmaps", "rescaled") if return_heatmaps or overlay else ())
-            track = ops.gaze_track(preds, torch.from_numpy(plan["target_idx"].reshape(-1)).to(dev), N, want=want)
+            target = torch.from_numpy(plan["target_idx"].reshape(-1)).to(dev)
+            if fill is None:
+                want = ("points", "peak", "count") + (("heatmaps", "rescaled") if return_heatmaps or overlay else ())
+                track = ops.gaze_track(preds, target, N, want=want)
+            else:                                             # the fill reads the sparse maps: they are dropped at the end
+                track = fill_track(ops.gaze_track(preds, target, N, want=("heatmaps", "count")), mode=fill, max_gap=max_gap,
+                                   plan=plan)
             if overlay:
                 track["points_source"] = points_to_source(track["points"], row, S)
                 track["overlay"] = self.render_track(frames_u8, track)
-                if not return_heatmaps:
-                    del track["heatmaps"], track["rescaled"]
+            if not return_heatmaps and "heatmaps" in track:
+                del track["heatmaps"], track["rescaled"]
         track["windows"] = nwin
         return track

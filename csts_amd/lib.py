@@ -267,6 +267,7 @@ SYMBOLS = {
     "csts_gaze_meter_update_host": (_I, [vp, vp, i64, i64, _I, _I, _I, i64, _I, vp]),
     "csts_gaze_decode": (_I, [vp, _I, i64, _I, _I, _F, vp, vp, vp, vp, vp]),
     "csts_gaze_track": (_I, [vp, vp, vp, i64, _I, _I, vp, vp, vp, vp, vp, vp]),
+    "csts_gaze_track_fill": (_I, [vp, vp, i64, _I, _I, _I, _I, vp, vp, vp, vp, vp, vp]),
     "csts_gaze_overlay": (_I, [vp, vp, vp, vp, vp, i64, _I, _I, _I, _I, _I, _F, _I, vp]),
 }
 

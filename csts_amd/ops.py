@@ -2500,6 +2500,47 @@ def gaze_track(preds, target_idx, n_frames, want=_TRACK_OUTPUTS):
     return out
 
 
+_FILL_OUTPUTS = ("heatmaps", "rescaled", "points", "peak", "neighbours")
+_FILL_MODES = ("hold", "linear")        # the kernel's mode is the position
+
+
+def gaze_track_fill(heatmaps, count, mode="linear", max_gap=9, want=_FILL_OUTPUTS):
+    """csts_gaze_track_fill: the sparse track of gaze_track -- heatmaps fp32 (F, H, W) and count int32 (F,) -- with every frame
+    between two neighbouring predictions filled.  A frame with count > 0 passes through bit for bit; a frame with count 0 whose
+    nearest predicted neighbours a < n < b lie at most max_gap frames apart gets H_a (mode "hold") or the time-linear blend
+    ((b - n) H_a + (n - a) H_b) / (b - a) (mode "linear"); any other frame stays unpredicted (maps 0, points NaN, peak 0).
+    rescaled, points and peak are decoded from the new map as gaze_track decodes them; neighbours int32 (F, 2) = (a, b),
+    (n, n) on a predicted frame, (-1, -1) on an unpredicted one.  Nothing is extrapolated outside the predicted span.
+    Returns a dict of the outputs named in `want` (new tensors: the inputs are not written).  One launch, no host sync: it can
+    be captured in a graph.  The rule is stated in include/csts_hip.h and restated on the host by infer.fill_plan."""
+    _need_gpu(heatmaps, count)
+    want = tuple(want)
+    unknown = [k for k in want if k not in _FILL_OUTPUTS]
+    if unknown or not want:
+        raise ValueError(f"want must name some of {_FILL_OUTPUTS}, got {want}")
+    if mode not in _FILL_MODES:
+        raise ValueError(f"mode must be one of {_FILL_MODES}, got {mode!r}")
+    if heatmaps.dim() != 3 or heatmaps.dtype != torch.float32:
+        raise ValueError(f"heatmaps must be fp32 (F, H, W), got {tuple(heatmaps.shape)} {heatmaps.dtype}")
+    F, H, W = heatmaps.shape
+    if count.dtype != torch.int32 or tuple(count.shape) != (F,):
+        raise ValueError(f"count must be int32 ({F},), got {tuple(count.shape)} {count.dtype}")
+    if F < 1:
+        raise ValueError(f"gaze_track_fill needs F >= 1 frames, got {F}")
+    x = heatmaps.detach().contiguous()
+    c = count.contiguous()
+    dev = x.device
+    out = {}
+    for k, shape, dt in (("heatmaps", (F, H, W), torch.float32), ("rescaled", (F, H, W), torch.float32),
+                         ("points", (F, 2), torch.float32), ("peak", (F,), torch.float32), ("neighbours", (F, 2), torch.int32)):
+        if k in want:
+            out[k] = torch.empty(shape, dtype=dt, device=dev)
+    L.check(_lib().csts_gaze_track_fill(_p(x), _p(c), F, H, W, _FILL_MODES.index(mode), int(max_gap), _p(out.get("heatmaps")),
+                                        _p(out.get("rescaled")), _p(out.get("points")), _p(out.get("peak")),
+                                        _p(out.get("neighbours")), _stream()), "csts_gaze_track_fill")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- gaze overlay
 def jet_table():
     """The heat colours of gaze_overlay on the host: uint8 numpy (256, 3) RGB, row q = the classic JET by the integer formula of

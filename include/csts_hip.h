@@ -607,6 +607,36 @@ int csts_gaze_decode(const void* logits, int dt, int64_t nframes, int H, int W, 
 int csts_gaze_track(const float* preds, const int* order, const int* offsets, int64_t F, int H, int W, float* heatmaps,
                     float* rescaled, float* points, float* peak, int* count, hipStream_t stream);
 
+/* ---- filling the gaze track between predictions (csts_amd/csrc/decode.hip): the model predicts T frames per window,
+ *      SAMPLING_RATE + 1 frames apart, so the track of csts_gaze_track is sparse.  This gives every frame between two
+ *      neighbouring predictions a map: what the num_repeat loops of slowfast/visualization/visualization.py (vis_video :105-127,
+ *      vis_video_forecasting :146-169) do by holding a map over the following frames.  heatmaps [F][H * W] fp32 and count [F]
+ *      int32 are the outputs of csts_gaze_track.  Rule, per frame n:
+ *        count[n] > 0 (predicted):  neighbours (n, n); the frame passes through, m = heatmaps[n].
+ *        count[n] == 0:  a = the largest predicted frame below n, b = the smallest predicted frame above n.
+ *                        both exist and b - a <= max_gap (filled):  neighbours (a, b);
+ *                          mode 0 (hold):    m = heatmaps[a]
+ *                          mode 1 (linear):  m = wa * heatmaps[a] + wb * heatmaps[b] in fp32 (two products, one sum, no
+ *                                            contraction), wa = (float)(b - n) / (float)(b - a), wb = (float)(n - a) / (float)(b - a):
+ *                                            a convex combination, so still a probability map
+ *                        otherwise (unpredicted):  neighbours (-1, -1); maps 0, points NaN, peak 0.
+ *        out_heatmaps = m;  out_rescaled, out_points, out_peak from m exactly as csts_gaze_track derives them from its mean
+ *        (min-max with + 1e-6, the lowest flat index of the maximum), by the same device function: a predicted frame comes out
+ *        with the bits csts_gaze_track wrote, a held frame with those of frame a.
+ *      Nothing is extrapolated before the first or after the last predicted frame.  Each workgroup finds a and b itself by
+ *      scanning count at most max_gap - 1 frames each way: no table from the host, no sort, nothing read back.  Outputs:
+ *      out_heatmaps and out_rescaled [F][H * W], out_points [F][2], out_peak [F] fp32, out_neighbours [F][2] int32; each may be
+ *      NULL and is then skipped; with all NULL nothing is launched.  No output may overlap heatmaps or count, in whole or in
+ *      part: a workgroup reads other frames' maps while their workgroups write.  An output that STARTS at heatmaps is
+ *      refused (-1); any other overlap is the caller's to avoid.  One workgroup per output frame keeps the map in registers: H * W <= CSTS_GAZE_DECODE_MAX_HW,
+ *      1 <= F < 2^31, 1 <= max_gap <= CSTS_GAZE_FILL_MAX_GAP.  128-bit accesses when H * W is a multiple of 4 and heatmaps,
+ *      out_heatmaps and out_rescaled are 16-byte aligned, scalar ones otherwise.  One launch; no allocation, no
+ *      synchronisation, no host read: graph-capturable. */
+#define CSTS_GAZE_FILL_MAX_GAP 1024
+int csts_gaze_track_fill(const float* heatmaps, const int* count, int64_t F, int H, int W, int mode, int max_gap,
+                         float* out_heatmaps, float* out_rescaled, float* out_points, float* out_peak, int* out_neighbours,
+                         hipStream_t stream);
+
 /* ---- gaze overlay (csts_amd/csrc/overlay.hip): the heat map of a gaze track blended onto the source frames and a disc at the
  *      gaze point, what slowfast/visualization/visualization.py (vis_inference, vis_video_forecasting) draws with cv2: map
  *      resized to the frame, JET colours, 0.6 frame + 0.4 heat, a filled green circle.  cv2 is not a dependency, so the rule

@@ -18,7 +18,11 @@ per-frame track: points (N, 2), peak (N,), count (N,), heatmaps and rescaled (N,
 "_type": "predict_video".  --video and --clip exclude each other.
 --overlay (with --video): --out also receives points_source (N, 2), the points normalised on the source frame, and overlay uint8
 (N, H, W, 3), the track drawn onto the recording (GazePredictor.render_track).  --overlay-dir DIR [--overlay-every K] additionally
-writes every K-th overlay frame as DIR/frame_000000.png through PIL; without PIL one line says so and no image is written."""
+writes every K-th overlay frame as DIR/frame_000000.png through PIL; without PIL one line says so and no image is written.
+--fill {hold,linear} (with --video): the frames between two neighbouring predictions are filled on the device
+(csts_amd.fill_track: the earlier map held, or the time-linear blend of the two), at most --max-gap N frames apart (default:
+csts_amd.default_max_gap of the plan).  --out also receives neighbours (N, 2) and filled (N,); the json_stats line gains "fill",
+"max_gap" and "filled_frames".  Without --fill the output and the record are what they were."""
 import argparse
 import json
 import os
@@ -47,6 +51,8 @@ def parse_args(argv=None):
     p.add_argument("--overlay", action="store_true", help="with --video: add points_source and the rendered overlay to --out")
     p.add_argument("--overlay-dir", default=None, type=str, help="with --video: also write overlay frames as PNGs here (implies --overlay)")
     p.add_argument("--overlay-every", default=1, type=int, help="write every K-th frame to --overlay-dir")
+    p.add_argument("--fill", default=None, choices=["hold", "linear"], help="with --video: fill the frames between predictions")
+    p.add_argument("--max-gap", default=None, type=int, help="with --fill: widest distance between two predictions that is filled")
     p.add_argument("--seed", default=2000, type=int, help="seed of the synthetic batch used without --clip")
     p.add_argument("--batch", default=2, type=int, help="clips in the synthetic batch used without --clip")
     p.add_argument("--no-graph", action="store_true", help="launch the kernels eagerly instead of replaying a HIP graph")
@@ -57,6 +63,12 @@ def parse_args(argv=None):
         p.error("--video and --clip exclude each other: a whole recording or one clip")
     if (args.overlay or args.overlay_dir) and args.video is None:
         p.error("--overlay and --overlay-dir draw onto a recording: they need --video")
+    if args.fill is not None and args.video is None:
+        p.error("--fill fills the track of a recording: it needs --video")
+    if args.max_gap is not None and args.fill is None:
+        p.error("--max-gap belongs to a fill mode: it needs --fill")
+    if args.max_gap is not None and args.max_gap < 1:
+        p.error("--max-gap must be positive")
     if args.overlay_every < 1:
         p.error("--overlay-every must be positive")
     return args
@@ -88,17 +100,22 @@ def main(argv=None):
                 raise SystemExit(f"{args.video} lacks {missing}: a video holds {list(VIDEO_KEYS)} and optionally fps")
             fps = args.fps if args.fps is not None else (float(z["fps"]) if "fps" in z.files else None)
             out = predictor.predict_video(torch.from_numpy(z["frames_u8"]).to(dev), torch.from_numpy(z["wav"]).float().to(dev),
-                                          fps=fps, stride=args.stride, overlay=bool(args.overlay or args.overlay_dir))
+                                          fps=fps, stride=args.stride, overlay=bool(args.overlay or args.overlay_dir),
+                                          fill=args.fill, max_gap=args.max_gap)
         keys = ("points", "peak", "count", "rescaled", "heatmaps") + (("points_source", "overlay") if "overlay" in out else ())
+        keys += ("neighbours", "filled") if args.fill is not None else ()
         arrays = {k: out[k].cpu().numpy() for k in keys}
         np.savez(args.out, **arrays)
         if args.overlay_dir is not None:
             write_pngs(arrays["overlay"], args.overlay_dir, args.overlay_every)
-        print("json_stats: " + json.dumps({"_type": "predict_video", "checkpoint": predictor.checkpoint_path, "source": args.video,
-                                           "graph": predictor.graph, "out": args.out, "windows": out["windows"],
-                                           "frames": int(arrays["count"].shape[0]),
-                                           "covered_frames": int((arrays["count"] > 0).sum()),
-                                           "shapes": {k: list(v.shape) for k, v in arrays.items()}}), flush=True)
+        record = {"_type": "predict_video", "checkpoint": predictor.checkpoint_path, "source": args.video,
+                  "graph": predictor.graph, "out": args.out, "windows": out["windows"],
+                  "frames": int(arrays["count"].shape[0]),
+                  "covered_frames": int((arrays["count"] > 0).sum()),
+                  "shapes": {k: list(v.shape) for k, v in arrays.items()}}
+        if args.fill is not None:
+            record.update({"fill": args.fill, "max_gap": int(out["max_gap"]), "filled_frames": int(arrays["filled"].sum())})
+        print("json_stats: " + json.dumps(record), flush=True)
         return
     if args.clip is not None:
         with np.load(args.clip) as z:

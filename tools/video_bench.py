@@ -5,14 +5,18 @@
                windows 16 frames apart as predict_video lays them out;
   (b) track    ops.gaze_track against its torch composition (index_add_ + divide + min / max / arg-max) at 64 x 64 on the maps
                of a 900-frame video (stride 16: 51 windows of 8 maps);
-  (c) video    GazePredictor.predict_video on 900 synthetic frames (360 x 480) with a 30 s waveform at stride 16: clips per second.
+  (c) video    GazePredictor.predict_video on 900 synthetic frames (360 x 480) with a 30 s waveform at stride 16: clips per second;
+  (d) fill     ops.gaze_track_fill in both modes against its torch composition (neighbour search with cummax / a reversed cummin: no host read, a
+               gather and blend, then min / max / arg-max) on the sparse track of the DEFAULT Ego4D plan at 900 frames, 64 x 64
+               (13 windows, 102 predicted frames); also, from plan_video on the host, how many windows a track made dense by a
+               small stride would need instead.
 
 After a warm-up the variants of (a) and of (b) are alternated over several rounds (clock and thermal drift hit both alike); a
 round times `--steps` calls between two device events.  Reports the median of the per-round times and their spread, checks
 that the variants agree, writes the JSON (with the build stamp) to --out and prints it on one line.
 
     python tools/video_bench.py                                    # -> profiles/video_bench.json
-    python tools/video_bench.py --skip-video                       # (a) and (b) only: no model is built
+    python tools/video_bench.py --skip-video                       # (a), (b) and (d) only: no model is built
 """
 import argparse
 import json
@@ -21,13 +25,14 @@ import statistics
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import build_stamp                                  # noqa: E402
-from csts_amd import GazePredictor, inputs, ops, plan_video     # noqa: E402
+from csts_amd import GazePredictor, default_max_gap, inputs, ops, plan_video     # noqa: E402
 from csts_amd.config import load_yaml               # noqa: E402
 
 YAML = os.path.join(ROOT, "configs/Ego4D/CSTS_Ego4D_Gaze_Forecast.yaml")
@@ -68,6 +73,31 @@ def track_torch(preds, target_idx, n_frames):
     resc = (heat - mn) / (mx - mn + 1e-6)
     points = torch.cat([(idx % W).float() / W, torch.div(idx, W, rounding_mode="floor").float() / H], dim=-1)
     return heat, resc, points, mx[:, 0], count
+
+
+def fill_torch(heatmaps, count, mode, max_gap):
+    """The torch composition gaze_track_fill replaces."""
+    N, H, W = heatmaps.shape
+    idx = torch.arange(N, device=heatmaps.device)
+    pred = count > 0
+    a = torch.cummax(torch.where(pred, idx, torch.full_like(idx, -1)), dim=0).values            # last predicted frame <= n, -1: none
+    b = torch.flip(torch.cummin(torch.flip(torch.where(pred, idx, torch.full_like(idx, N)), [0]), dim=0).values, [0])   # first predicted frame >= n, N: none
+    ok = pred | ((a >= 0) & (b < N) & (b - a <= max_gap))
+    ac, bc = a.clamp(min=0), b.clamp(max=N - 1)
+    flat = heatmaps.reshape(N, -1)
+    if mode == "hold":
+        heat = flat[ac]
+    else:
+        span = (bc - ac).clamp(min=1).float()
+        wa = torch.where(bc > ac, (bc - idx).float() / span, torch.ones_like(span))
+        wb = torch.where(bc > ac, (idx - ac).float() / span, torch.zeros_like(span))
+        heat = wa[:, None] * flat[ac] + wb[:, None] * flat[bc]
+    heat = torch.where(ok[:, None], heat, torch.zeros_like(heat))
+    mn, (mx, am) = heat.amin(dim=-1, keepdim=True), heat.max(dim=-1, keepdim=True)
+    resc = (heat - mn) / (mx - mn + 1e-6)
+    points = torch.cat([(am % W).float() / W, torch.div(am, W, rounding_mode="floor").float() / H], dim=-1)
+    nb = torch.where(ok[:, None], torch.stack([a, b], dim=-1), torch.full_like(idx, -1)[:, None])
+    return heat, resc, points, mx[:, 0], nb
 
 
 def main():
@@ -139,6 +169,38 @@ def main():
                         "batch": min(int(cfg.TEST.BATCH_SIZE), 8), "round_s": [round(v, 4) for v in secs], "median_s": round(med, 4),
                         "round_spread_s": round(max(secs) - min(secs), 4), "clips_per_s": round(r["windows"] / med, 1),
                         "video_frames_per_s": round(N / med, 1), "covered_frames": int((r["count"] > 0).sum())}
+    # ---- (d) the fill, on the sparse track of the default plan
+    dplan = plan_video(cfg, N)
+    gap = default_max_gap(dplan)
+    Pd = dplan["windows"] * T
+    dpreds = torch.softmax(torch.randn(Pd, 64 * 64, generator=g, device=dev) / 2, dim=-1).reshape(Pd, 64, 64)
+    sparse = ops.gaze_track(dpreds, torch.from_numpy(dplan["target_idx"].reshape(-1)).to(dev), N, want=("heatmaps", "count"))
+    heat, count = sparse["heatmaps"], sparse["count"]
+    predicted = int((count > 0).sum())
+    out["fill"] = {"frames": N, "grid": [64, 64], "stride": dplan["stride"], "windows": dplan["windows"], "max_gap": gap,
+                   "predicted_frames": predicted}
+    for mode in ("hold", "linear"):
+        variants = {"gaze_track_fill": lambda m=mode: ops.gaze_track_fill(heat, count, mode=m, max_gap=gap),
+                    "torch": lambda m=mode: fill_torch(heat, count, m, gap)}
+        a, b = variants["gaze_track_fill"](), variants["torch"]()
+        covered = a["neighbours"][:, 0] >= 0
+        agree = {"heatmaps_max_abs": float((a["heatmaps"].reshape(N, -1) - b[0]).abs().max()),
+                 "points_equal_on_covered": bool(torch.equal(a["points"][covered], b[2][covered])),
+                 "neighbours_equal": bool(torch.equal(a["neighbours"].long(), b[4]))}
+        res = alternate(variants, args.warmup, args.steps, args.rounds)
+        nfilled = int(covered.sum()) - predicted
+        maps_moved = predicted + (2 if mode == "linear" else 1) * nfilled + 2 * N      # maps read + heatmaps and rescaled written
+        out["fill"][mode] = {"covered_frames": int(covered.sum()), "filled_frames": nfilled, "agreement": agree,
+                             "model_MB": round(maps_moved * 64 * 64 * 4 / 1e6, 1),
+                             **res, "torch_over_fused": round(res["torch"]["median_us"] / res["gaze_track_fill"]["median_us"], 2)}
+    # what a track made dense by stride alone costs in forward passes (host arithmetic, nothing is run)
+    dense = plan_video(cfg, N, stride=7)
+    dt = dense["target_idx"].reshape(-1)
+    dcount = np.bincount(dt[dt < N], minlength=N)
+    span = np.nonzero(dcount)[0]
+    out["fill"]["dense_by_stride"] = {"stride": 7, "windows": int(dense["windows"]), "windows_with_fill": int(dplan["windows"]),
+                                      "empty_frames_in_span": int((dcount[span[0]:span[-1] + 1] == 0).sum())}
+
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     json.dump(out, open(args.out, "w"), indent=1)
     print(json.dumps(out))
