@@ -8,8 +8,8 @@ from .config import get_cfg, load_yaml, assert_and_infer_cfg  # noqa: F401
 from .build import build_model  # noqa: F401
 from .infer import GazePredictor, GraphedEvalStep, plan_video, points_to_source, marker_centers  # noqa: F401
 from .infer import fill_track, fill_plan, default_max_gap  # noqa: F401
-from .ops import gaze_overlay, jet_table  # noqa: F401
+from .ops import gaze_overlay, jet_table, audio_pixel_attn  # noqa: F401
 
 __all__ = ["MODEL_REGISTRY", "build_model", "get_cfg", "load_yaml", "assert_and_infer_cfg", "GazePredictor", "GraphedEvalStep",
            "plan_video", "fill_track", "fill_plan", "default_max_gap", "points_to_source", "marker_centers", "gaze_overlay",
-           "jet_table"]
+           "jet_table", "audio_pixel_attn"]

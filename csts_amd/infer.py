@@ -176,12 +176,23 @@ def _core(model):
     return model.module if hasattr(model, "module") else model
 
 
-def eval_forward(model, video, audio):
+# result name of predict(attention=True) -> entry of the model's fusion dict (CSTS.forward_head, return_fusion_maps)
+ATTENTION_OUTPUTS = {"audio_attention": "column", "audio_attention_mean": "column_mean", "attention_maps": "maps",
+                     "attention_range": "range", "temporal_attention": "temporal"}
+
+
+def eval_forward(model, video, audio, attention=False):
     """model([video], audio) -> gaze_decode, with the kernels the graph replays.  The caller holds eval mode and no_grad.
-    Returns {"logits", "preds", "rescaled"}: (B, 1, T, H/4, W/4); "points": (B, T, 2); "peak": (B, T)."""
-    logits = model([video], audio)
+    Returns {"logits", "preds", "rescaled"}: (B, 1, T, H/4, W/4); "points": (B, T, 2); "peak": (B, T).  attention=True runs the
+    forward with return_fusion_maps and adds the entries of ATTENTION_OUTPUTS; the logits are the same bits either way."""
+    if attention:
+        logits, fusion = model([video], audio, return_fusion_maps=True)
+    else:
+        logits = model([video], audio)
     out = ops.gaze_decode(logits, TEMPERATURE)
     out["logits"] = logits
+    if attention:
+        out.update({k: fusion[v] for k, v in ATTENTION_OUTPUTS.items()})
     return out
 
 
@@ -189,10 +200,12 @@ class GraphedEvalStep:
     """The forward-only step -- eval-mode model([video], audio), then gaze_decode -- captured ONCE into a HIP graph and replayed.
     The capture runs the model's own forward, so the second-stream trunks of CSTS_AMD.TWO_STREAMS are part of the graph as
     they are in the training capture.  Inputs are copied into static buffers; run() returns the graph's static outputs, which
-    the next run() overwrites.  The model's parameters are not touched and its training flag is put back."""
+    the next run() overwrites.  The model's parameters are not touched and its training flag is put back.  attention=True
+    captures the forward that also yields the fusion attention maps (eval_forward)."""
 
-    def __init__(self, cfg, model, example_batch, warmup: int = 2):
+    def __init__(self, cfg, model, example_batch, warmup: int = 2, attention: bool = False):
         self.cfg, self.model = cfg, _core(model)      # forward only: nothing for a data-parallel wrapper to reduce
+        self.attention = bool(attention)
         for k in ("video", "audio"):
             if not example_batch[k].is_cuda:
                 raise L.CstsError("GraphedEvalStep runs on MI355X only: the batch must hold GPU tensors")
@@ -217,11 +230,11 @@ class GraphedEvalStep:
             self.model.train(was_training)
 
     def _step(self):
-        return eval_forward(self.model, self.static["video"], self.static["audio"])
+        return eval_forward(self.model, self.static["video"], self.static["audio"], attention=self.attention)
 
     def run(self, video=None, audio=None):
         """Copy the inputs into the static buffers (None: keep what they hold) and replay.  Returns the static outputs
-        {"logits", "preds", "rescaled", "points", "peak"}."""
+        {"logits", "preds", "rescaled", "points", "peak"} (and the ATTENTION_OUTPUTS of a step captured with attention)."""
         for k, v in (("video", video), ("audio", audio)):
             if v is not None and v is not self.static[k]:
                 if v.shape != self.static[k].shape:
@@ -267,16 +280,17 @@ class GazePredictor:
                 ck.load_checkpoint(checkpoint_path, self.model)
         self.checkpoint_path = checkpoint_path if checkpoint_path is not None else (cfg.TEST.CHECKPOINT_FILE_PATH or None)
         self.model.eval()
-        self._steps = {}           # (B, T, S) -> GraphedEvalStep
+        self._steps = {}           # (B, T, S) or (B, T, S, "attention") -> GraphedEvalStep
 
     @torch.no_grad()
-    def predict(self, frames_u8, wav, frames_idx, frame_length, labels=None):
+    def predict(self, frames_u8, wav, frames_idx, frame_length, labels=None, attention=False):
         """frames_u8 uint8 (B, T, H, W, 3), wav fp32 (B, n) at 24 kHz, frames_idx (B, T) = the sampled frames' positions on the
         clip's time axis of `frame_length` frames -> {"points": (B, T, 2) (x, y) in [0, 1), "peak": (B, T),
         "heatmaps": (B, T, S/4, S/4), "rescaled": same shape} on the device, S = DATA.TEST_CROP_SIZE.
         Frames that come at S x S are normalised as they are; any other size goes through the test-mode spatial sampling (short
         side to S, centre crop: inputs.spatial_sampling(train=False, spatial_idx=1)), so the points are in the crop's
-        coordinates.  labels (optional, (B, T, L >= 2) gaze labels): carried through the same crop and returned as "labels"."""
+        coordinates.  labels (optional, (B, T, L >= 2) gaze labels): carried through the same crop and returned as "labels".
+        attention=True adds the fusion attention maps of predict_batch; the other entries keep their bits."""
         for t in (frames_u8, wav, frames_idx) + ((labels,) if labels is not None else ()):
             if not torch.is_tensor(t) or not t.is_cuda:
                 raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
@@ -300,15 +314,22 @@ class GazePredictor:
             if S != 256:       # S frequency bins x S columns around each frame, as train.synthetic_batch cuts them
                 o = (256 - S) // 2
                 audio = audio[:, :, :, :S, o:o + S].contiguous()
-            out = self.predict_batch({"video": video, "audio": audio})
+            out = self.predict_batch({"video": video, "audio": audio}, attention=attention)
         if labels is not None:
             out["labels"] = new_labels
         return out
 
     @torch.no_grad()
-    def predict_batch(self, batch):
+    def predict_batch(self, batch, attention=False):
         """batch: an assembled dict with "video" fp32 (B, 3, T, S, S) and "audio" fp32 (B, 1, T, F, F) (inputs.assemble_batch,
-        train.synthetic_batch) -> the dict of predict().  The tensors are the caller's: a later call does not overwrite them."""
+        train.synthetic_batch) -> the dict of predict().  The tensors are the caller's: a later call does not overwrite them.
+        attention=True adds what vis_av_st_fusion of the reference draws (ops.audio_pixel_attn, include/csts_hip.h), with Hh heads
+        and the grid (T', h, w) of the spatial fusion block: "audio_attention" (B, Hh, T', h, w) = the probability each image
+        region of frame t gives that frame's audio token, "audio_attention_mean" (B, T', h, w) = its head mean, "attention_maps"
+        (B, Hh + 1, T, h, w) = one rescaled map per input frame and head (index Hh: the head mean), ready for render_attention,
+        "attention_range" (B, Hh + 1, T, 2) = the (lo, hi) each was rescaled by, "temporal_attention" (B, n, n) = the temporal
+        fusion block's head-averaged probabilities.  Without the flag the launches are what they were."""
+        attention = bool(attention)
         video, audio = batch["video"], batch["audio"]
         for t in (video, audio):
             if not torch.is_tensor(t) or not t.is_cuda:
@@ -317,16 +338,20 @@ class GazePredictor:
             raise ValueError(f"video and audio must be 5-D, got {tuple(video.shape)} and {tuple(audio.shape)}")
         with torch.cuda.device(self.device):
             if self.graph:
-                key = (video.shape[0], video.shape[2], video.shape[-1])
+                key = (video.shape[0], video.shape[2], video.shape[-1]) + (("attention",) if attention else ())
                 step = self._steps.get(key)
                 if step is None or step.static["audio"].shape != audio.shape or step.static["video"].shape != video.shape:
-                    step = self._steps[key] = GraphedEvalStep(self.cfg, self.model, {"video": video, "audio": audio})
+                    step = self._steps[key] = GraphedEvalStep(self.cfg, self.model, {"video": video, "audio": audio},
+                                                              attention=attention)
                 out = step.run(video, audio)
-                out = {k: out[k].clone() for k in ("points", "peak", "preds", "rescaled")}
+                out = {k: out[k].clone() for k in ("points", "peak", "preds", "rescaled") + (tuple(ATTENTION_OUTPUTS) if attention else ())}
             else:
-                out = eval_forward(self.model, video.contiguous(), audio.contiguous())
-        return {"points": out["points"], "peak": out["peak"], "heatmaps": out["preds"].squeeze(1),
-                "rescaled": out["rescaled"].squeeze(1)}
+                out = eval_forward(self.model, video.contiguous(), audio.contiguous(), attention=attention)
+        res = {"points": out["points"], "peak": out["peak"], "heatmaps": out["preds"].squeeze(1),
+               "rescaled": out["rescaled"].squeeze(1)}
+        if attention:
+            res.update({k: out[k] for k in ATTENTION_OUTPUTS})
+        return res
 
     @torch.no_grad()
     def _video_params_row(self, H, W):
@@ -370,6 +395,47 @@ class GazePredictor:
                 sel = slice(a, min(a + step, N))
                 ops.gaze_overlay(frames_u8[sel], track["rescaled"][sel], params, S, centers=centers[sel], alpha=alpha,
                                  radius=radius, out=out[sel])
+        return out
+
+    @torch.no_grad()
+    def render_attention(self, frames_u8, result, head=None, alpha=0.4, radius=5, points=None, out=None):
+        """The fusion attention maps of predict(attention=True) drawn onto the clip: frames_u8 uint8 (B, T, H, W, 3) on the device
+        (the frames that were predicted) and the result dict (it must hold "attention_maps") -> uint8 (B, T, H, W, 3): the map
+        of `head` (None: the head mean) of every input frame blended over the crop the model saw -- one ops.gaze_overlay call
+        over the B * T frames.  The crop is predict()'s: identity for S x S frames, else short side to S and centre crop.
+        points (optional, (B, T, 2) on the crop, e.g. result["points"]): a disc of `radius` pixels at each (NaN: that frame comes
+        back untouched).  out=frames_u8 renders in place."""
+        if not torch.is_tensor(frames_u8) or not frames_u8.is_cuda:
+            raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
+        if "attention_maps" not in result:
+            raise ValueError("render_attention needs the result's \"attention_maps\": call predict with attention=True")
+        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 5 or frames_u8.shape[-1] != 3:
+            raise ValueError(f"frames must be uint8 (B, T, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
+        if not frames_u8.is_contiguous():
+            raise ValueError("frames must be contiguous (B, T, H, W, 3)")
+        B, T, H, W, _ = frames_u8.shape
+        maps = result["attention_maps"]
+        if maps.dim() != 5 or maps.shape[0] != B or maps.shape[2] != T:
+            raise ValueError(f"attention_maps {tuple(maps.shape)} do not belong to {B} clips of {T} frames")
+        nheads = maps.shape[1] - 1
+        g = nheads if head is None else int(head)
+        if head is not None and not 0 <= g < nheads:
+            raise ValueError(f"head must be None (the head mean) or lie in [0, {nheads}), got {head!r}")
+        if out is not None and (out.shape != frames_u8.shape or out.dtype != torch.uint8 or not out.is_contiguous()):
+            raise ValueError(f"out must be contiguous uint8 {tuple(frames_u8.shape)}, got {tuple(out.shape)} {out.dtype}")
+        S = int(self.cfg.DATA.TEST_CROP_SIZE)
+        with torch.cuda.device(self.device):
+            row = self._video_params_row(H, W)
+            params = torch.tensor(row, dtype=torch.int32, device=frames_u8.device)
+            centers = None
+            if points is not None:
+                if tuple(points.shape) != (B, T, 2):
+                    raise ValueError(f"points must be ({B}, {T}, 2), got {tuple(points.shape)}")
+                centers = marker_centers(points_to_source(points.reshape(B * T, 2), row, S), H, W)
+            if out is None:
+                out = torch.empty_like(frames_u8)
+            ops.gaze_overlay(frames_u8.view(B * T, H, W, 3), maps[:, g].reshape(B * T, maps.shape[3], maps.shape[4]), params, S,
+                             centers=centers, alpha=alpha, radius=radius, out=out.view(B * T, H, W, 3))
         return out
 
     @torch.no_grad()

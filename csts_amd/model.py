@@ -176,9 +176,11 @@ class Block(nn.Module):
             raise L.CstsError("Block dropout in train mode needs the per-forward key CSTS.forward draws")
         return ops.Dropout(self.rt.drop_key, self.dropout_site, self.drop_rate)
 
-    def forward(self, x, thw, keep_masks=None, want_attn=False, spatial_audio_attn=False, x_add=None):
+    def forward(self, x, thw, keep_masks=None, want_attn=False, spatial_audio_attn=False, x_add=None, fusion_maps=None):
         """x_add (optional): a skip tensor to be added to x first (the decoder's `feat + en_feat`,
-        custom_multimodal_builder.py:467-479): folded into norm1's kernel, which then also writes the sum."""
+        custom_multimodal_builder.py:467-479): folded into norm1's kernel, which then also writes the sum.
+        fusion_maps (optional, spatial fusion block only): (input frames, crop side); the return gains a fourth element, the dict
+        of ops.audio_pixel_attn computed from the qkv and lse this forward holds anyway (no gradient flows through it)."""
         rt = self.rt
         drop = self._dropout()
         a = self.attn
@@ -191,7 +193,7 @@ class Block(nn.Module):
         w16 = lambda lin: getattr(lin, "_w16", None)      # bf16 shadow maintained by CSTS._refresh_w16 (bf16 mode)
         w16t = lambda lin: getattr(lin, "_w16t", None)    # its [in][out] twin (training): the data gradients run as NT GEMMs
         kvc = None
-        if ops.kv_compact_ok(thw, self.stride_kv, self.has_pool_kv) and not spatial_audio_attn and not want_attn:
+        if ops.kv_compact_ok(thw, self.stride_kv, self.has_pool_kv) and not spatial_audio_attn and not want_attn and fusion_maps is None:
             # K/V pools with spatial stride >= 4 read (3/s)^2 of the token rows: k|v only for those (ops.QkvCompactFn)
             qkv, kvc = ops.qkv_compact(xn, a.qkv.weight, a.qkv.bias, thw, self.stride_kv, out_dt=rt.act_dt, compute=rt.compute,
                                        w16=w16(a.qkv), w16t=w16t(a.qkv))
@@ -249,6 +251,10 @@ class Block(nn.Module):
         elif want_attn:
             with torch.no_grad():
                 extra = ops.attention_probs(qkv.detach(), B, N, Cc, H, lse, mask_mode, mT, mHW)
+        if fusion_maps is not None:
+            with torch.no_grad():
+                fm = ops.audio_pixel_attn(qkv.detach(), lse, thw, H, fusion_maps[0], fusion_maps[1])
+            return out, q_thw, extra, fm
         return out, q_thw, extra
 
 
@@ -511,8 +517,9 @@ class CSTS(nn.Module):
 
     # ------------------------------------------------------------------ forward (custom_multimodal_builder.py:343-498)
     def forward(self, x, y, return_embed=False, return_spatial_attn=False, return_temporal_attn=False, keep_masks=None,
-                boundary=None):
-        """boundary (optional, csts_amd.train.SegmentedTrainStep): callable applied to the list of tensors that cross from
+                boundary=None, return_fusion_maps=False):
+        """return_fusion_maps: see forward_head.
+        boundary (optional, csts_amd.train.SegmentedTrainStep): callable applied to the list of tensors that cross from
         the encoder trunks to the fusion / decoder head [video tokens, audio tokens, the four encoder features the decoder
         re-uses]; it may return detached stand-ins, which cuts the autograd graph into a trunk part and a head part.  A
         boundary with an attribute `trunk_cut` = k > 0 and a method `inner(tensors)` is also applied to [video tokens] in front
@@ -528,7 +535,7 @@ class CSTS(nn.Module):
         feats, geo = self.forward_trunk(inpt, y, km, boundary, twins=twins)
         if boundary is not None:
             feats = boundary(feats)
-        return self.forward_head(feats, geo, km, return_embed, return_spatial_attn, return_temporal_attn)
+        return self.forward_head(feats, geo, km, return_embed, return_spatial_attn, return_temporal_attn, return_fusion_maps)
 
     def _run_halves(self, xt, thw, km, blocks, names, main):
         """blocks over the two halves of the batch, the second half on its own stream (autograd replays its backward there)."""
@@ -635,8 +642,14 @@ class CSTS(nn.Module):
             yt, thw_a = run(yt, thw_a, ab, an)
         return [xt, yt] + inter, (list(thw), list(thw_a), inter_thw)
 
-    def forward_head(self, feats, geo, km, return_embed=False, return_spatial_attn=False, return_temporal_attn=False):
-        """Spatial / temporal fusion, re-weighting, decoder, classifier, embeddings (custom_multimodal_builder.py:413-498)."""
+    def forward_head(self, feats, geo, km, return_embed=False, return_spatial_attn=False, return_temporal_attn=False,
+                     return_fusion_maps=False):
+        """Spatial / temporal fusion, re-weighting, decoder, classifier, embeddings (custom_multimodal_builder.py:413-498).
+        return_fusion_maps: the result becomes a list (as with the reference's three flags, whose entries keep their places) with
+        one more entry at its end, `fusion`: the dict of ops.audio_pixel_attn on the spatial fusion block -- "column",
+        "column_mean", "maps", "range": what vis_av_st_fusion of visualization.py:172-228 draws, per input frame of the S x S
+        crop -- plus "temporal" (B, n, n), the temporal fusion block's probabilities averaged over heads (:196).  Alone it gives
+        [logits, fusion].  The logits do not depend on the flag."""
         rt = self.rt
         xt, yt = feats[0], feats[1]
         thw, thw_a, inter_thw = geo
@@ -652,7 +665,7 @@ class CSTS(nn.Module):
                                     w16=c16(self.vision_pool))
             y_tmp = ops.fusion_conv(yt, self.audio_pool2.weight, self.audio_pool2.bias, thw_a[0], HWa, rt.act_dt, rt.compute,
                                     w16=c16(self.audio_pool2))
-            return self.temporal_fusion(ops.cat_tokens(x_tmp, y_tmp), (2, 2, 2), want_attn=return_temporal_attn)
+            return self.temporal_fusion(ops.cat_tokens(x_tmp, y_tmp), (2, 2, 2), want_attn=return_temporal_attn or return_fusion_maps)
 
         # The temporal fusion (16 tokens per clip: every kernel of it is one latency-bound round trip) does not depend on the spatial
         # one unless SPATIAL_AUDIO_ATTN re-weights its input (:438-440): it runs on the side stream beside the spatial fusion, and
@@ -668,8 +681,14 @@ class CSTS(nn.Module):
         y_sp = ops.fusion_conv(yt, self.audio_pool.weight, self.audio_pool.bias, thw_a[0], HWa, rt.act_dt, rt.compute,
                                w16=c16(self.audio_pool))
         av_sp = ops.cat_tokens(xt, y_sp)
-        av_sp, _, sp_extra = self.spatial_fusion(av_sp, thw, want_attn=return_spatial_attn,
-                                                 spatial_audio_attn=self.spatial_audio_attn)
+        fusion = None
+        if return_fusion_maps:
+            av_sp, _, sp_extra, fusion = self.spatial_fusion(av_sp, thw, want_attn=return_spatial_attn,
+                                                             spatial_audio_attn=self.spatial_audio_attn,
+                                                             fusion_maps=(self.input_dims[0], self.input_dims[1]))
+        else:
+            av_sp, _, sp_extra = self.spatial_fusion(av_sp, thw, want_attn=return_spatial_attn,
+                                                     spatial_audio_attn=self.spatial_audio_attn)
         x_spatial, _ = ops.split_tokens(av_sp, Nv)        # (y_spatial, the audio half, is unused in the reference too: :432)
         # ---- temporal fusion (:435-451)
         if side is not None:
@@ -711,18 +730,23 @@ class CSTS(nn.Module):
         en, en_thw = inter[0]
         logits = ops.classifier_head(feat, en, self.classifier.weight, self.classifier.bias, en_thw, rt.compute)
 
-        if not return_embed and not return_spatial_attn and not return_temporal_attn:
+        if not return_embed and not return_spatial_attn and not return_temporal_attn and not return_fusion_maps:
             return logits
+        if return_fusion_maps:
+            with torch.no_grad():
+                fusion["temporal"] = t_extra.mean(dim=1)          # visualization.py:196
         if not return_embed:
             out = [logits]
             if return_spatial_attn:     # with SPATIAL_AUDIO_ATTN the block yields the audio->pixel map instead (the reference
                 out.append(sp_extra[0] if isinstance(sp_extra, tuple) else sp_extra)   # raises NameError there, :485-491)
             if return_temporal_attn:
                 out.append(t_extra)
+            if return_fusion_maps:
+                out.append(fusion)
             return out
         v_emb, a_emb = emb
         if self.two_streams and HEAD_STREAMS:
             main.wait_stream(self._audio_stream())
             v_emb.record_stream(main)
             a_emb.record_stream(main)
-        return [logits, v_emb, a_emb]
+        return [logits, v_emb, a_emb] + ([fusion] if return_fusion_maps else [])

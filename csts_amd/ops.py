@@ -2603,3 +2603,47 @@ def gaze_overlay(frames_u8, rescaled, params, crop_size, centers=None, alpha=0.4
     L.check(_lib().csts_gaze_overlay(_p(frames_u8), _p(maps), _p(cen), _p(par), _p(out), N, H, W, S, maps.shape[1], maps.shape[2],
                                      alpha, radius, _stream()), "csts_gaze_overlay")
     return out
+
+
+# ----------------------------------------------------------------------------------------- fusion attention maps
+def audio_pixel_attn(qkv, lse, thw, heads, n_frames, crop_size):
+    """csts_audio_pixel_attn on what the spatial fusion block's forward holds: qkv (B, N, 3C) packed q | k | v rows (fp32 or the
+    library's 16-bit type), N = T' h w + T' for the grid thw = (T', h, w), and lse fp32 (B, heads, N), the rows' log-sum-exp in
+    the log2 domain (attention_inner) -> the audio-visual correlation map of visualization.py:172-228 without the (N, N) matrix:
+    {"column": (B, heads, T', h, w) = the probability each image region of frame t gives that frame's audio token,
+     "column_mean": (B, T', h, w) = its head mean,
+     "maps": (B, heads + 1, T, h, w) = per input frame (T = n_frames) the time-linear mix of the column, rescaled by the extrema its
+             bilinear upsample takes on the S x S crop lattice (S = crop_size) -- what gaze_overlay draws; index `heads` = the mean,
+     "range": (B, heads + 1, T, 2) = those extrema (lo, hi)}, all fp32.
+    Inference only: raises when an input carries a gradient.  Two launches, no host sync: it can be captured in a graph.  The
+    rule is stated in include/csts_hip.h."""
+    _need_gpu(qkv, lse)
+    if (qkv.requires_grad or lse.requires_grad) and torch.is_grad_enabled():
+        raise L.CstsError("audio_pixel_attn is an inference output: it has no backward (call it under torch.no_grad(), or use "
+                          "audio_attn for the differentiable MVIT.SPATIAL_AUDIO_ATTN map)")
+    thw = [int(v) for v in thw]
+    heads, T, S = int(heads), int(n_frames), int(crop_size)
+    if len(thw) != 3 or min(thw) < 1 or heads < 1:
+        raise ValueError(f"thw must be three positive sizes (T', h, w) and heads positive, got {thw} and {heads}")
+    if T < 1 or S < 1:
+        raise ValueError(f"audio_pixel_attn needs n_frames >= 1 and crop_size >= 1, got {T} and {S}")
+    Tp, h, w = thw
+    N = Tp * h * w + Tp
+    if qkv.dim() != 3 or qkv.shape[1] != N or qkv.shape[2] % (3 * heads) != 0:
+        raise ValueError(f"qkv must be (B, {N}, 3 * heads * head_dim) for the grid {tuple(thw)} and {heads} heads, got {tuple(qkv.shape)}")
+    B = qkv.shape[0]
+    hd = qkv.shape[2] // (3 * heads)
+    if lse.dtype != torch.float32 or tuple(lse.shape) != (B, heads, N):
+        raise ValueError(f"lse must be fp32 ({B}, {heads}, {N}), got {tuple(lse.shape)} {lse.dtype}")
+    if B < 1:
+        raise ValueError("audio_pixel_attn needs B >= 1 clips")
+    x, l = qkv.detach().contiguous(), lse.detach().contiguous()
+    dev = x.device
+    out = {"column": torch.empty(B, heads, Tp, h, w, dtype=torch.float32, device=dev),
+           "column_mean": torch.empty(B, Tp, h, w, dtype=torch.float32, device=dev),
+           "maps": torch.empty(B, heads + 1, T, h, w, dtype=torch.float32, device=dev),
+           "range": torch.empty(B, heads + 1, T, 2, dtype=torch.float32, device=dev)}
+    L.check(_lib().csts_audio_pixel_attn(_p(x), _dt(x), _p(l), B, heads, hd, Tp, h, w, T, S, hd ** -0.5, _p(out["column"]),
+                                         _p(out["column_mean"]), _p(out["maps"]), _p(out["range"]), _stream()),
+            "csts_audio_pixel_attn")
+    return out

@@ -32,10 +32,10 @@ enum { CSTS_EPI_NONE = 0, CSTS_EPI_GELU = 1, CSTS_EPI_DGELU = 2 };
 enum { CSTS_MASK_NONE = 0, CSTS_MASK_SPATIAL = 1 };
 
 /* Version of this header's struct layouts and call semantics.  Bumped whenever a struct grows or a field changes meaning
- * (2: csts_gemm_args.res_up; 3: compact k|v rows, 16-bit build, loss scaler in csts_opt_args; 4: csts_opt_args.extra_sq, factored AdamW; 5: grouped stencil weight gradients; 6: csts_copy_token_segments, csts_wgrad_grouped8_limited; 7: csts_wgrad_grouped5, csts_gemm algo 500; 8: csts_opt_rule, csts_opt_step, csts_opt_factored_step, csts_opt_factored.tensor replaces pad_).  csts_abi_version() returns the value the
+ * (2: csts_gemm_args.res_up; 3: compact k|v rows, 16-bit build, loss scaler in csts_opt_args; 4: csts_opt_args.extra_sq, factored AdamW; 5: grouped stencil weight gradients; 6: csts_copy_token_segments, csts_wgrad_grouped8_limited; 7: csts_wgrad_grouped5, csts_gemm algo 500; 8: csts_opt_rule, csts_opt_step, csts_opt_factored_step, csts_opt_factored.tensor replaces pad_; 10: csts_audio_pixel_attn).  csts_abi_version() returns the value the
  * LIBRARY was built with: a caller must compare it with the CSTS_ABI_VERSION it was compiled against and refuse a mismatch
  * (the Python binding does, csts_amd/lib.py::load). */
-#define CSTS_ABI_VERSION 9
+#define CSTS_ABI_VERSION 10
 const char* csts_last_error(void);
 int csts_abi_version(void);
 int csts_half_kind(void);   /* the 16-bit type behind CSTS_BF16 in THIS library: 0 bfloat16 (libcsts_hip.so), 1 IEEE half (libcsts_hip_f16.so) */
@@ -670,6 +670,47 @@ int csts_gaze_track_fill(const float* heatmaps, const int* count, int64_t F, int
  *      S <= 4096, N * ceil(H / 32) < 2^31. */
 int csts_gaze_overlay(const uint8_t* frames_nhwc, const float* rescaled, const int* centers, const int* params, uint8_t* out,
                       int64_t N, int H, int W, int S, int mh, int mw, float alpha, int radius, hipStream_t stream);
+
+/* ---- fusion attention maps (csts_amd/csrc/fusion_maps.hip): the audio-visual correlation map of the spatial fusion block, what
+ *      vis_av_st_fusion of slowfast/visualization/visualization.py:172-228 draws per head: for every frame, how strongly each image
+ *      region attends to that frame's audio token.  It reads what the block's forward already holds and forms no (N, N) matrix.
+ *      qkv (B, N, 3C) packed q | k | v rows of the block, fp32 (dt CSTS_F32) or the library's 16-bit type (dt CSTS_BF16), C =
+ *      heads * head_dim, N = T' h w + T' (the video tokens of the grid (T', h, w), then one audio token per frame); lse
+ *      (B, heads, N) fp32 = the log-sum-exp of every query row in the LOG2 domain, as csts_attn_fwd writes it (the spatial mask
+ *      is inside it; the mask never hides a frame's own audio token, so none is applied here); T = input frames, S = crop side.
+ *      Rule, all fp32, with c = y w + x, HW = h w:
+ *        column[b][k][t][c]   = exp2f(fl(fl(s * fl(scale * 1.4426950408889634f)) - lse[b][k][t HW + c])),
+ *                               s = <q[b][t HW + c][k][:], key[b][T' HW + t][k][:]> : lane l of a wave multiplies elements l, l + 64,
+ *                               ... and adds them in that order, then a 64-lane xor butterfly (offsets 32 .. 1) adds the lanes.
+ *                               This is attn[:, :, HW t : HW (t + 1), THW + t] of visualization.py:190.
+ *        column_mean[b][t][c] = ((0 + column[b][0][t][c]) + column[b][1][t][c] + ...) / heads   (heads ascending, one division)
+ *        index g of maps / range:  g < heads: head g of column;  g == heads: column_mean.
+ *        time, input frame j:   u = max((j + 0.5) T' / T - 0.5, 0) = max(A / D, 0) with A = (2j + 1) T' - T, D = 2T in integers;
+ *                               t0 = min(floor(u), T' - 1), t1 = min(t0 + 1, T' - 1), lambda = fl((A mod D) / D) (0 where A <= 0);
+ *                               m_j = fl(fl((1 - lambda) * col[t0]) + fl(lambda * col[t1]))   -- the temporal part of
+ *                               F.upsample(mode='trilinear', align_corners=False); T == T' gives lambda = 0, m_j = col[j].
+ *        space:                 lattice point p of the S x S crop sits on a map axis of n cells at max((p + 0.5) n / S - 0.5, 0),
+ *                               the same rational with (p, S, n) for (j, T, T'); neighbours clamped to n - 1; the sample is
+ *                               top = fma(lx, m[i0][j1] - m[i0][j0], m[i0][j0]), bot likewise on row i1, v = fma(ly, bot - top, top):
+ *                               exactly what csts_gaze_overlay evaluates at that pixel of an identity crop.
+ *        range[b][g][j]       = (lo, hi) = the minimum and maximum of v over the S x S lattice.  A bilinear patch is extremal at
+ *                               its corners, so only the first and last lattice point of every run that shares (i0) on an axis
+ *                               are evaluated: at most 2h x 2w points.  No lattice point sits on a cell centre, so (lo, hi) lie
+ *                               strictly inside the coarse map's own extrema.
+ *        maps[b][g][j][c]     = (m_j[c] - lo) / (hi - lo + 1e-6)
+ *      Bilinear weights sum to one, so upsampling this rescaled coarse map equals the reference's order (upsample, then per-frame
+ *      min-max) up to rounding: csts_gaze_overlay draws maps[b][g][j] (mh = h, mw = w) unchanged.  Cells between lattice points
+ *      may leave [0, 1] by what the patch overshoots; the overlay clamps its quantised value.
+ *      Outputs fp32: column (B, heads, T', h, w), column_mean (B, T', h, w), maps (B, heads + 1, T, h, w), range
+ *      (B, heads + 1, T, 2); none may be NULL.  Sizes: B, heads >= 1; 1 <= head_dim <= CSTS_AUDIO_PIXEL_MAX_HD; 1 <= h, w <=
+ *      CSTS_AUDIO_PIXEL_MAX_SIDE, h w <= CSTS_AUDIO_PIXEL_MAX_HW; 1 <= T, T', S <= 65536; B heads T', B (T (heads + 1) + T') and
+ *      N * 3C below 2^31.  Two launches on `stream` (the column, then everything derived from it); no allocation, no
+ *      synchronisation, no host read: graph-capturable.  No atomics: deterministic. */
+#define CSTS_AUDIO_PIXEL_MAX_HD 256
+#define CSTS_AUDIO_PIXEL_MAX_SIDE 128
+#define CSTS_AUDIO_PIXEL_MAX_HW 4096
+int csts_audio_pixel_attn(const void* qkv, int dt, const float* lse, int B, int heads, int head_dim, int Tp, int h, int w, int T,
+                          int S, float scale, float* column, float* column_mean, float* maps, float* range, hipStream_t stream);
 
 #ifdef __cplusplus
 }

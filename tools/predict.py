@@ -22,7 +22,13 @@ writes every K-th overlay frame as DIR/frame_000000.png through PIL; without PIL
 --fill {hold,linear} (with --video): the frames between two neighbouring predictions are filled on the device
 (csts_amd.fill_track: the earlier map held, or the time-linear blend of the two), at most --max-gap N frames apart (default:
 csts_amd.default_max_gap of the plan).  --out also receives neighbours (N, 2) and filled (N,); the json_stats line gains "fill",
-"max_gap" and "filled_frames".  Without --fill the output and the record are what they were."""
+"max_gap" and "filled_frames".  Without --fill the output and the record are what they were.
+--attention (one clip or the synthetic batch, not --video): --out also receives the fusion attention maps of
+GazePredictor.predict(attention=True): audio_attention, audio_attention_mean, attention_maps, attention_range and
+temporal_attention.  --attention-dir DIR (implies --attention; needs --clip, whose uint8 frames are drawn on) additionally writes,
+as the reference's vis_av_st_fusion does, DIR/spat_attn_<clip>_<frame>_head_<k>.png for every head and ..._head_mean.png
+(GazePredictor.render_attention, through PIL; without PIL one line says so and no image is written) and
+DIR/temporal_attn_<clip>.txt.  A whole-recording attention track is not defined yet: --attention with --video is an error."""
 import argparse
 import json
 import os
@@ -53,6 +59,9 @@ def parse_args(argv=None):
     p.add_argument("--overlay-every", default=1, type=int, help="write every K-th frame to --overlay-dir")
     p.add_argument("--fill", default=None, choices=["hold", "linear"], help="with --video: fill the frames between predictions")
     p.add_argument("--max-gap", default=None, type=int, help="with --fill: widest distance between two predictions that is filled")
+    p.add_argument("--attention", action="store_true", help="add the fusion attention maps to --out (one clip, not --video)")
+    p.add_argument("--attention-dir", default=None, type=str,
+                   help="with --clip: also write the attention overlays as PNGs and the temporal matrices as text here (implies --attention)")
     p.add_argument("--seed", default=2000, type=int, help="seed of the synthetic batch used without --clip")
     p.add_argument("--batch", default=2, type=int, help="clips in the synthetic batch used without --clip")
     p.add_argument("--no-graph", action="store_true", help="launch the kernels eagerly instead of replaying a HIP graph")
@@ -63,6 +72,11 @@ def parse_args(argv=None):
         p.error("--video and --clip exclude each other: a whole recording or one clip")
     if (args.overlay or args.overlay_dir) and args.video is None:
         p.error("--overlay and --overlay-dir draw onto a recording: they need --video")
+    if (args.attention or args.attention_dir) and args.video is not None:
+        p.error("--attention and --attention-dir show one clip's fusion attention: they do not work with --video (a whole-recording "
+                "attention track is not defined yet); use --clip")
+    if args.attention_dir is not None and args.clip is None:
+        p.error("--attention-dir draws onto a clip's uint8 frames: it needs --clip")
     if args.fill is not None and args.video is None:
         p.error("--fill fills the track of a recording: it needs --video")
     if args.max_gap is not None and args.fill is None:
@@ -85,8 +99,29 @@ def write_pngs(overlay, directory, every):
         Image.fromarray(overlay[i]).save(os.path.join(directory, f"frame_{i:06d}.png"))
 
 
+def write_attention(predictor, frames_u8, out, directory):
+    """spat_attn_<clip>_<frame>_head_<k>.png for every head and the head mean, temporal_attn_<clip>.txt."""
+    os.makedirs(directory, exist_ok=True)
+    temporal = out["temporal_attention"].cpu().numpy()
+    for b in range(temporal.shape[0]):
+        np.savetxt(os.path.join(directory, f"temporal_attn_{b}.txt"), temporal[b])
+    try:
+        from PIL import Image
+    except ImportError:
+        print(f"PIL is not installed: no PNG written to {directory}", flush=True)
+        return
+    heads = out["attention_maps"].shape[1] - 1
+    for k in list(range(heads)) + [None]:
+        drawn = predictor.render_attention(frames_u8, out, head=k).cpu().numpy()
+        name = "mean" if k is None else str(k)
+        for b in range(drawn.shape[0]):
+            for t in range(drawn.shape[1]):
+                Image.fromarray(drawn[b, t]).save(os.path.join(directory, f"spat_attn_{b}_{t}_head_{name}.png"))
+
+
 def main(argv=None):
     args = parse_args(argv)
+    attention = bool(args.attention or args.attention_dir)
     cfg = assert_and_infer_cfg(load_yaml(args.cfg_file, ["NUM_GPUS", 1] + list(args.opts or [])))
     if not torch.cuda.is_available():
         raise SystemExit("tools/predict.py needs an MI355X: there is no CPU fallback")
@@ -122,16 +157,22 @@ def main(argv=None):
             missing = [k for k in CLIP_KEYS if k not in z.files]
             if missing:
                 raise SystemExit(f"{args.clip} lacks {missing}: a clip holds {list(CLIP_KEYS)}")
-            out = predictor.predict(torch.from_numpy(z["frames_u8"]).to(dev), torch.from_numpy(z["wav"]).float().to(dev),
-                                    torch.from_numpy(z["frames_idx"]).float().to(dev), float(z["frame_length"]))
+            frames_u8 = torch.from_numpy(z["frames_u8"]).to(dev)
+            out = predictor.predict(frames_u8, torch.from_numpy(z["wav"]).float().to(dev),
+                                    torch.from_numpy(z["frames_idx"]).float().to(dev), float(z["frame_length"]), attention=attention)
+        if args.attention_dir is not None:
+            write_attention(predictor, frames_u8, out, args.attention_dir)
         source = args.clip
     else:
         from csts_amd import train as T
         batch = T.synthetic_batch(args.batch, cfg.DATA.NUM_FRAMES, cfg.DATA.TEST_CROP_SIZE, args.seed, dev,
                                   spatial=T.spatial_config(cfg, train=False))
-        out = predictor.predict_batch(batch)
+        out = predictor.predict_batch(batch, attention=attention)
         source = f"synthetic_batch(seed={args.seed})"
-    arrays = {k: out[k].cpu().numpy() for k in ("points", "peak", "rescaled", "heatmaps")}
+    keys = ("points", "peak", "rescaled", "heatmaps")
+    if attention:
+        keys += ("audio_attention", "audio_attention_mean", "attention_maps", "attention_range", "temporal_attention")
+    arrays = {k: out[k].cpu().numpy() for k in keys}
     np.savez(args.out, **arrays)
     print("json_stats: " + json.dumps({"_type": "predict", "checkpoint": predictor.checkpoint_path, "source": source,
                                        "graph": predictor.graph, "out": args.out,
