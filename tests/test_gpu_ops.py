@@ -492,6 +492,33 @@ def test_qkv_compact_equals_full_qkv(case, compute, monkeypatch):
         if k == "bk":        # exactly zero in exact arithmetic (softmax shift invariance): rounding noise on both sides
             continue
         assert rel_l2(g_c[k].float(), g_f[k].float()) < tol, (k, rel_l2(g_c[k].float(), g_f[k].float()))
+    # the compact path against torch autograd of the reference formulation (fp32 Linear -> the oracle's pools, LayerNorms and
+    # attention core), from the operands the kernels read (bf16 mode: x and the 16-bit copy of W), at test_attention_inner's bars
+    xr = rnd(B, N, Cc, seed=1).to(dt).float().requires_grad_(True)
+    W0 = rnd(3 * Cc, Cc, seed=2, scale=Cc ** -0.5)
+    Wr = (W0.to(torch.bfloat16).float() if compute == L.BF16 else W0).requires_grad_(True)
+    br = (0.1 * rnd(3 * Cc, seed=3)).requires_grad_(True)
+    Pr = {}
+    for i, s_ in enumerate("qkv"):
+        Pr["w" + s_] = rnd(HD, 1, 3, 3, 3, seed=10 + i, scale=0.2).requires_grad_(True)
+        Pr["g" + s_] = (1 + 0.1 * rnd(HD, seed=20 + i)).requires_grad_(True)
+        Pr["b" + s_] = (0.1 * rnd(HD, seed=30 + i)).requires_grad_(True)
+    orf = _ref_attn_inner(xr @ Wr.t() + br, Pr, B, N, Cc, H, list(thw), kind, sq, skv, kind != "dec" and use_q, True, False)
+    orf.backward(rnd(*orf.shape, seed=5).to(dt).float())
+    rtol = 3e-5 if compute == L.F32 else 3e-2
+    ref_g = {"x": xr.grad, "W": Wr.grad, "b": br.grad}
+    ref_g.update({k: v.grad for k, v in Pr.items() if v.grad is not None})
+    assert set(ref_g) == set(g_c)
+    figures = {"o": rel_l2(o_c.float(), orf)}
+    figures.update({k: rel_l2(g_c[k].float(), ref_g[k]) for k in g_c if k != "bk"})
+    print(f"\n[qkv_compact vs reference {name} {'f32' if compute == L.F32 else 'bf16'}] " + "  ".join(f"{k} {v:.2e}" for k, v in figures.items()))
+    assert figures["o"] < rtol, "o"
+    assert figures["x"] < rtol * 2, "dx"
+    for k in g_c:
+        if k == "bk":        # as in test_attention_inner: rounding noise on both sides, held against the scale of d(gamma_k)
+            assert float(g_c["bk"].norm()) < (1e-3 if compute == L.F32 else 0.5) * float(ref_g["gk"].norm()) + 1e-6
+        elif k not in ("x",):
+            assert figures[k] < rtol * 3, (k, figures[k])
 
 
 @pytest.mark.parametrize("compute", [L.F32, L.BF16])
