@@ -7,9 +7,10 @@ from .registry import MODEL_REGISTRY  # noqa: F401
 from .config import get_cfg, load_yaml, assert_and_infer_cfg  # noqa: F401
 from .build import build_model  # noqa: F401
 from .infer import GazePredictor, GraphedEvalStep, plan_video, points_to_source, marker_centers  # noqa: F401
-from .infer import fill_track, fill_plan, default_max_gap  # noqa: F401
-from .ops import gaze_overlay, jet_table, audio_pixel_attn  # noqa: F401
+from .infer import fill_track, fill_plan, default_max_gap, fill_attention_track, default_attention_gap  # noqa: F401
+from .ops import gaze_overlay, jet_table, audio_pixel_attn, attention_track, attention_rescale  # noqa: F401
 
 __all__ = ["MODEL_REGISTRY", "build_model", "get_cfg", "load_yaml", "assert_and_infer_cfg", "GazePredictor", "GraphedEvalStep",
            "plan_video", "fill_track", "fill_plan", "default_max_gap", "points_to_source", "marker_centers", "gaze_overlay",
-           "jet_table", "audio_pixel_attn"]
+           "jet_table", "audio_pixel_attn", "attention_track", "attention_rescale", "fill_attention_track",
+           "default_attention_gap"]

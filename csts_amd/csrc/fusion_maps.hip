@@ -9,6 +9,12 @@
 //                      extrema of its bilinear upsample over the S x S lattice from the end pixels of every cell interval (a
 //                      bilinear patch is extremal at its corners: 2h x 2w evaluations instead of S^2), the rescaled coarse map
 //                      out; B * T' further workgroups of the same launch write the head mean of the column.
+// The whole-recording track (csts_attention_track) reuses the pieces: the per-pair map is apa_pair_cell (time mix, head mean), the
+// extrema and the rescale are apa_lattice_range / apa_rescale_store, the very device functions apa_maps_kernel runs, so a frame
+// one pair hits carries that kernel's bits.
+//   apt_accumulate_kernel  one workgroup per (output frame f, head or head mean): walks the frame's pair list, the sum in LDS
+//                          cells each thread owns, then the mean;
+//   apa_rescale_kernel     one workgroup per (f, g): the map into LDS, lattice extrema, rescaled map and range out.
 #include "common.h"
 
 namespace {
@@ -84,43 +90,27 @@ __device__ inline void apa_end_pixels(ApaAxis* ends, int S, int m, int tid) {
   }
 }
 
-// grid B * T * (Hh + 1) + B * T', 256 threads
-__global__ __launch_bounds__(256) void apa_maps_kernel(const float* __restrict__ column, float* __restrict__ column_mean,
-                                                       float* __restrict__ maps, float* __restrict__ range, int B, int Hh, int Tp,
-                                                       int h, int w, int T, int S) {
-  __shared__ float m[APA_MAX_CELLS];
-  __shared__ ApaAxis ey[2 * APA_MAX_SIDE], ex[2 * APA_MAX_SIDE];
-  __shared__ float red[8];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int HW = h * w;
-  const int64_t head_stride = (int64_t)Tp * HW;
-  const int map_blocks = B * T * (Hh + 1);
-  if ((int)blockIdx.x >= map_blocks) {                          // the head mean of the column, frame (b, t)
-    const int r = blockIdx.x - map_blocks;
-    const int t = r % Tp;
-    const int64_t b = r / Tp;
-    const float* col = column + b * Hh * head_stride + (int64_t)t * HW;
-    float* out = column_mean + (b * Tp + t) * (int64_t)HW;
-    for (int c = tid; c < HW; c += 256) out[c] = apa_head_mean(col + c, Hh, head_stride);
-    return;
-  }
-  const int g = blockIdx.x % (Hh + 1);
-  const int j = (blockIdx.x / (Hh + 1)) % T;
-  const int64_t b = blockIdx.x / ((Hh + 1) * T);
-  const ApaAxis at = apa_axis(j, T, Tp);
+// cell c of the map of (clip cb, input frame axis `at`, index g): fl(fl((1 - lambda) col[t0]) + fl(lambda col[t1])), for the head
+// mean (g == Hh) on the head means of the two coarse maps.  Two products, one sum (no contraction).
+__device__ __forceinline__ float apa_pair_cell(const float* __restrict__ cb, int g, int Hh, int64_t head_stride, int HW,
+                                               const ApaAxis& at, int c) {
   const float w0 = 1.0f - at.lam, w1 = at.lam;
-  const float* cb = column + b * Hh * head_stride;
-  for (int c = tid; c < HW; c += 256) {
-    float a0, a1;
-    if (g < Hh) {
-      a0 = cb[g * head_stride + (int64_t)at.i0 * HW + c];
-      a1 = cb[g * head_stride + (int64_t)at.i1 * HW + c];
-    } else {
-      a0 = apa_head_mean(cb + (int64_t)at.i0 * HW + c, Hh, head_stride);
-      a1 = apa_head_mean(cb + (int64_t)at.i1 * HW + c, Hh, head_stride);
-    }
-    m[c] = w0 * a0 + w1 * a1;                                   // two products, one sum (no contraction)
+  float a0, a1;
+  if (g < Hh) {
+    a0 = cb[g * head_stride + (int64_t)at.i0 * HW + c];
+    a1 = cb[g * head_stride + (int64_t)at.i1 * HW + c];
+  } else {
+    a0 = apa_head_mean(cb + (int64_t)at.i0 * HW + c, Hh, head_stride);
+    a1 = apa_head_mean(cb + (int64_t)at.i1 * HW + c, Hh, head_stride);
   }
+  return w0 * a0 + w1 * a1;
+}
+
+// (lo, hi) of the bilinear upsample of the LDS map m (h x w, written by this workgroup's threads; the barrier is in here) over
+// the S x S lattice, from the end pixels.  Every thread returns the same pair.  256 threads.
+__device__ inline void apa_lattice_range(const float* m, ApaAxis* ey, ApaAxis* ex, float* red, int h, int w, int S, int tid,
+                                         float& lo_out, float& hi_out) {
+  const int lane = tid & 63, wv = tid >> 6;
   apa_end_pixels(ey, S, h, tid);
   apa_end_pixels(ex, S, w, tid);
   __syncthreads();
@@ -139,12 +129,97 @@ __global__ __launch_bounds__(256) void apa_maps_kernel(const float* __restrict__
   hi = wave_max(hi);
   if (lane == 0) { red[wv] = lo; red[4 + wv] = hi; }
   __syncthreads();
-  lo = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
-  hi = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
-  const int64_t o = (b * (Hh + 1) + g) * T + j;
+  lo_out = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
+  hi_out = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
+}
+
+// maps[o] = (m - lo) / (hi - lo + 1e-6), range[o] = (lo, hi)
+__device__ __forceinline__ void apa_rescale_store(const float* m, float lo, float hi, int HW, int64_t o, float* __restrict__ maps,
+                                                  float* __restrict__ range, int tid) {
   const float den = hi - lo + 1e-6f;
   for (int c = tid; c < HW; c += 256) maps[o * HW + c] = (m[c] - lo) / den;
   if (tid == 0) { range[2 * o] = lo; range[2 * o + 1] = hi; }
+}
+
+// grid B * T * (Hh + 1) + B * T', 256 threads
+__global__ __launch_bounds__(256) void apa_maps_kernel(const float* __restrict__ column, float* __restrict__ column_mean,
+                                                       float* __restrict__ maps, float* __restrict__ range, int B, int Hh, int Tp,
+                                                       int h, int w, int T, int S) {
+  __shared__ float m[APA_MAX_CELLS];
+  __shared__ ApaAxis ey[2 * APA_MAX_SIDE], ex[2 * APA_MAX_SIDE];
+  __shared__ float red[8];
+  const int tid = threadIdx.x;
+  const int HW = h * w;
+  const int64_t head_stride = (int64_t)Tp * HW;
+  const int map_blocks = B * T * (Hh + 1);
+  if ((int)blockIdx.x >= map_blocks) {                          // the head mean of the column, frame (b, t)
+    const int r = blockIdx.x - map_blocks;
+    const int t = r % Tp;
+    const int64_t b = r / Tp;
+    const float* col = column + b * Hh * head_stride + (int64_t)t * HW;
+    float* out = column_mean + (b * Tp + t) * (int64_t)HW;
+    for (int c = tid; c < HW; c += 256) out[c] = apa_head_mean(col + c, Hh, head_stride);
+    return;
+  }
+  const int g = blockIdx.x % (Hh + 1);
+  const int j = (blockIdx.x / (Hh + 1)) % T;
+  const int64_t b = blockIdx.x / ((Hh + 1) * T);
+  const ApaAxis at = apa_axis(j, T, Tp);
+  const float* cb = column + b * Hh * head_stride;
+  for (int c = tid; c < HW; c += 256) m[c] = apa_pair_cell(cb, g, Hh, head_stride, HW, at, c);
+  float lo, hi;
+  apa_lattice_range(m, ey, ex, red, h, w, S, tid, lo, hi);
+  apa_rescale_store(m, lo, hi, HW, (b * (Hh + 1) + g) * T + j, maps, range, tid);
+}
+
+// grid F * (Hh + 1), 256 threads: mixed[f][g] = the mean of the maps of the pairs order[offsets[f] .. offsets[f + 1]), count[f].
+// Thread tid owns cells tid, tid + 256, ... of the LDS sum: no barrier between pairs.  A list bound outside [0, P] is clamped
+// and a pair outside [0, P) skipped (neither happens with the lists ops.attention_track builds), so no read leaves column/order.
+__global__ __launch_bounds__(256) void apt_accumulate_kernel(const float* __restrict__ column, const int* __restrict__ order,
+                                                             const int* __restrict__ offsets, int Wn, int Hh, int Tp, int HW,
+                                                             int T, float* __restrict__ mixed, int* __restrict__ count) {
+  __shared__ float m[APA_MAX_CELLS];
+  const int tid = threadIdx.x;
+  const int g = blockIdx.x % (Hh + 1);
+  const int64_t f = blockIdx.x / (Hh + 1);
+  const int64_t head_stride = (int64_t)Tp * HW;
+  const int64_t P = (int64_t)Wn * T;
+  const int beg = max(offsets[f], 0);
+  const int end = (int)min((int64_t)offsets[f + 1], P);
+  const int n = max(end - beg, 0);
+  for (int c = tid; c < HW; c += 256) m[c] = 0.f;
+  for (int i = beg; i < end; ++i) {                             // workgroup-uniform
+    const int p = order[i];
+    if (p < 0 || p >= P) continue;
+    const ApaAxis at = apa_axis(p % T, T, Tp);
+    const float* cb = column + (int64_t)(p / T) * Hh * head_stride;
+    for (int c = tid; c < HW; c += 256) m[c] += apa_pair_cell(cb, g, Hh, head_stride, HW, at, c);
+  }
+  const float inv = n > 0 ? 1.f / (float)n : 0.f;
+  float* out = mixed + (f * (Hh + 1) + g) * (int64_t)HW;
+  for (int c = tid; c < HW; c += 256) out[c] = m[c] * inv;
+  if (g == 0 && tid == 0) count[f] = n;
+}
+
+// grid F * G, 256 threads: maps / range of mixed[f][g]; a frame with valid[f] <= 0 gets maps 0 and range NaN.
+__global__ __launch_bounds__(256) void apa_rescale_kernel(const float* __restrict__ mixed, const int* __restrict__ valid, int G,
+                                                          int h, int w, int S, float* __restrict__ maps,
+                                                          float* __restrict__ range) {
+  __shared__ float m[APA_MAX_CELLS];
+  __shared__ ApaAxis ey[2 * APA_MAX_SIDE], ex[2 * APA_MAX_SIDE];
+  __shared__ float red[8];
+  const int tid = threadIdx.x;
+  const int HW = h * w;
+  const int64_t o = blockIdx.x, f = o / G;
+  if (valid && valid[f] <= 0) {                                 // workgroup-uniform
+    for (int c = tid; c < HW; c += 256) maps[o * HW + c] = 0.f;
+    if (tid == 0) { range[2 * o] = NAN; range[2 * o + 1] = NAN; }
+    return;
+  }
+  for (int c = tid; c < HW; c += 256) m[c] = mixed[o * HW + c];
+  float lo, hi;
+  apa_lattice_range(m, ey, ex, red, h, w, S, tid, lo, hi);
+  apa_rescale_store(m, lo, hi, HW, o, maps, range, tid);
 }
 
 }  // namespace
@@ -170,4 +245,34 @@ extern "C" int csts_audio_pixel_attn(const void* qkv, int dt, const float* lse, 
                      range, B, heads, Tp, h, w, T, S);
   CSTS_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int csts_attention_rescale(const float* mixed, const int* valid, int nmaps_per_frame, int64_t F, int h, int w, int S,
+                                      float* maps, float* range, hipStream_t stream) {
+  CSTS_REQUIRE(mixed && maps && range, "bad args (only valid may be NULL)");
+  CSTS_REQUIRE(maps != mixed, "maps must not be mixed (the workgroup reads its map after others may have written theirs)");
+  CSTS_REQUIRE(h >= 1 && w >= 1 && h <= APA_MAX_SIDE && w <= APA_MAX_SIDE && (int64_t)h * w <= APA_MAX_CELLS,
+               "1 <= h, w <= CSTS_AUDIO_PIXEL_MAX_SIDE and h * w <= CSTS_AUDIO_PIXEL_MAX_HW (the map is staged in LDS)");
+  CSTS_REQUIRE(nmaps_per_frame >= 1 && F >= 1 && S >= 1 && S <= 65536, "nmaps_per_frame >= 1, F >= 1, 1 <= S <= 65536");
+  CSTS_REQUIRE(F < ((int64_t)1 << 31) && F * nmaps_per_frame < ((int64_t)1 << 31), "F * nmaps_per_frame must stay below 2^31");
+  hipLaunchKernelGGL(apa_rescale_kernel, dim3((unsigned)(F * nmaps_per_frame)), dim3(256), 0, stream, mixed, valid,
+                     nmaps_per_frame, h, w, S, maps, range);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_attention_track(const float* column, const int* order, const int* offsets, int64_t F, int Wn, int heads, int Tp,
+                                    int h, int w, int T, int S, float* mixed, float* maps, float* range, int* count,
+                                    hipStream_t stream) {
+  CSTS_REQUIRE(column && order && offsets && mixed && maps && range && count, "bad args (no pointer may be NULL)");
+  CSTS_REQUIRE(Wn >= 1 && heads >= 1 && F >= 1, "Wn >= 1, heads >= 1, F >= 1");
+  CSTS_REQUIRE(Tp >= 1 && h >= 1 && w >= 1 && h <= APA_MAX_SIDE && w <= APA_MAX_SIDE && (int64_t)h * w <= APA_MAX_CELLS,
+               "1 <= h, w <= CSTS_AUDIO_PIXEL_MAX_SIDE and h * w <= CSTS_AUDIO_PIXEL_MAX_HW (the map is staged in LDS)");
+  CSTS_REQUIRE(T >= 1 && T <= 65536 && Tp <= 65536 && S >= 1 && S <= 65536, "1 <= T, T', S <= 65536");
+  CSTS_REQUIRE((int64_t)Wn * T < ((int64_t)1 << 31) && F < ((int64_t)1 << 31) && F * (heads + 1) < ((int64_t)1 << 31),
+               "Wn * T and F * (heads + 1) must stay below 2^31");
+  hipLaunchKernelGGL(apt_accumulate_kernel, dim3((unsigned)(F * (heads + 1))), dim3(256), 0, stream, column, order, offsets, Wn,
+                     heads, Tp, h * w, T, mixed, count);
+  CSTS_LAUNCH_CHECK();
+  return csts_attention_rescale(mixed, count, heads + 1, F, h, w, S, maps, range, stream);
 }

@@ -145,6 +145,62 @@ def fill_track(track, mode="linear", max_gap=None, plan=None):
     return out
 
 
+def default_attention_gap(plan):
+    """The widest step between two consecutive INPUT frames of one window of `plan` (plan_video): max(diff(plan["inputs"])), at
+    least 1 -- 9 on the Ego4D forecast plan, 5 on the Aria one.  The attention track lands on the input frames (the frames the
+    audio was heard with), not on the predicted ones, so its fill has its own default gap: it fills inside a window's observed
+    span and leaves the stretch between two windows' observed spans empty."""
+    import numpy as np
+    inputs = np.asarray(plan["inputs"], dtype=np.int64)
+    if inputs.size < 2:
+        return 1
+    return max(1, int(np.diff(inputs).max()))
+
+
+ATTENTION_TRACK_KEYS = ("attention_maps", "attention_range", "attention_mixed", "attention_count")
+
+
+def fill_attention_track(track, mode="linear", max_gap=None, plan=None, crop_size=None):
+    """The attention track of predict_video(attention_track=True) with the frames between neighbouring hit frames filled, as
+    fill_track fills the gaze track.  track: a dict with "attention_mixed" fp32 (N, heads + 1, h, w) and "attention_count" int32
+    (N,) on the device.  The fill runs on the MIXED maps -- ops.gaze_track_fill on the frame's heads + 1 maps viewed as one
+    (heads + 1) h x w map, so hold / linear and the neighbour rule are the gaze track's, bit for bit -- and ops.attention_rescale
+    then gives every hit or filled frame its own extrema: a blend is rescaled by the range of the blend, a hit frame keeps its
+    bits.  max_gap: None takes default_attention_gap(plan) and needs plan=.  crop_size: the S of the lattice; None takes
+    track["attention_crop_size"] (predict_video stores it).  Returns a NEW dict: "attention_mixed", "attention_maps" and
+    "attention_range" filled, "attention_neighbours" int32 (N, 2), "attention_filled" bool (N,), "attention_max_gap" (a host
+    int); every other entry as it was.  The fill kernel holds a frame in registers: (heads + 1) h w <= CSTS_GAZE_DECODE_MAX_HW."""
+    if "attention_mixed" not in track or "attention_count" not in track:
+        raise ValueError("fill_attention_track needs the track's \"attention_mixed\" and \"attention_count\": call predict_video "
+                         "with attention_track=True")
+    if max_gap is None:
+        if plan is None:
+            raise ValueError("fill_attention_track needs max_gap, or plan= (the plan_video result) to take default_attention_gap from")
+        max_gap = default_attention_gap(plan)
+    if crop_size is None:
+        if "attention_crop_size" not in track:
+            raise ValueError("fill_attention_track needs crop_size= (DATA.TEST_CROP_SIZE) or the track's \"attention_crop_size\"")
+        crop_size = track["attention_crop_size"]
+    mixed, count = track["attention_mixed"], track["attention_count"]
+    if mixed.dim() != 4:
+        raise ValueError(f"attention_mixed must be (N, heads + 1, h, w), got {tuple(mixed.shape)}")
+    N, G, h, w = mixed.shape
+    if G * h * w > L.GAZE_DECODE_MAX_HW:
+        raise ValueError(f"the fill holds a frame's {G} maps of {h} x {w} in registers: (heads + 1) * h * w = {G * h * w} exceeds "
+                         f"CSTS_GAZE_DECODE_MAX_HW ({L.GAZE_DECODE_MAX_HW})")
+    out = dict(track)
+    filled = ops.gaze_track_fill(mixed.contiguous().view(N, G * h, w), count, mode=mode, max_gap=int(max_gap),
+                                 want=("heatmaps", "neighbours"))
+    out["attention_mixed"] = filled["heatmaps"].view(N, G, h, w)
+    out["attention_neighbours"] = filled["neighbours"]
+    out["attention_filled"] = (count == 0) & (filled["neighbours"][:, 0] >= 0)
+    rescaled = ops.attention_rescale(out["attention_mixed"], int(crop_size), valid=(count > 0) | out["attention_filled"])
+    out["attention_maps"], out["attention_range"] = rescaled["maps"], rescaled["range"]
+    out["attention_max_gap"] = int(max_gap)
+    out["attention_crop_size"] = int(crop_size)
+    return out
+
+
 def points_to_source(points, params_row, crop_size):
     """Gaze points (N, 2) = (x, y) normalised on the S x S crop -> the same points normalised on the SOURCE frame the crop was cut
     from: x_src = (x S + x0) / new w, y_src = (y S + y0) / new h, the inverse of the label rule of the spatial sampling.
@@ -439,8 +495,60 @@ class GazePredictor:
         return out
 
     @torch.no_grad()
+    def render_attention_track(self, frames_u8, track, head=None, alpha=0.4, radius=5, points=None, out=None, chunk=None):
+        """The attention track of predict_video(attention_track=True) drawn onto its recording: frames_u8 uint8 (N, H, W, 3) on
+        the device and the track (it must hold "attention_maps" and "attention_count") -> uint8 (N, H, W, 3): on every frame a
+        pair landed on, or the fill reached ("attention_filled"), the map of `head` (None: the head mean) blended over the crop
+        the model saw -- one ops.gaze_overlay call per chunk.  Every other frame comes back byte for byte.  points (optional,
+        (N, 2) on the crop, e.g. the gaze track's "points"): a disc of `radius` pixels where the point is finite; a drawn frame
+        without a point gets no disc (its marker centre lies radius + 1 pixels right of the frame).  chunk: frames per launch
+        (default: all).  out=frames_u8 renders in place."""
+        if not torch.is_tensor(frames_u8) or not frames_u8.is_cuda:
+            raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
+        if "attention_maps" not in track or "attention_count" not in track:
+            raise ValueError("render_attention_track needs the track's \"attention_maps\" and \"attention_count\": call predict_video "
+                             "with attention_track=True")
+        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
+            raise ValueError(f"frames must be uint8 (N, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
+        N, H, W, _ = frames_u8.shape
+        maps, count = track["attention_maps"], track["attention_count"]
+        if maps.dim() != 4 or maps.shape[0] != N or tuple(count.shape) != (N,):
+            raise ValueError(f"the attention track holds {maps.shape[0]} frames, the recording {N}")
+        nheads = maps.shape[1] - 1
+        g = nheads if head is None else int(head)
+        if head is not None and not 0 <= g < nheads:
+            raise ValueError(f"head must be None (the head mean) or lie in [0, {nheads}), got {head!r}")
+        if points is not None and tuple(points.shape) != (N, 2):
+            raise ValueError(f"points must be ({N}, 2), got {tuple(points.shape)}")
+        step = N if chunk is None else int(chunk)
+        if step < 1:
+            raise ValueError(f"chunk must be positive, got {chunk}")
+        radius = int(radius)
+        S = int(self.cfg.DATA.TEST_CROP_SIZE)
+        with torch.cuda.device(self.device):
+            row = self._video_params_row(H, W)
+            params = torch.tensor(row, dtype=torch.int32, device=frames_u8.device)
+            drawn = count > 0
+            if "attention_filled" in track:
+                drawn = drawn | track["attention_filled"]
+            # drawn, no point: a centre no pixel of the frame is within `radius` of; not drawn: X = -1, the frame passes through
+            centers = torch.tensor([W + max(radius, 0) + 1, 0], dtype=torch.int32, device=frames_u8.device).repeat(N, 1)
+            if points is not None:
+                marks = marker_centers(points_to_source(points, row, S), H, W)
+                centers = torch.where(marks[:, :1] >= 0, marks, centers)
+            centers = torch.where(drawn[:, None], centers, torch.full_like(centers, -1))
+            picture = maps[:, g].contiguous()
+            if out is None:
+                out = torch.empty_like(frames_u8)
+            for a in range(0, N, step):
+                sel = slice(a, min(a + step, N))
+                ops.gaze_overlay(frames_u8[sel], picture[sel], params, S, centers=centers[sel], alpha=alpha, radius=radius,
+                                 out=out[sel])
+        return out
+
+    @torch.no_grad()
     def predict_video(self, frames_u8, wav, fps=None, stride=None, batch=None, return_heatmaps=True, overlay=False, fill=None,
-                      max_gap=None):
+                      max_gap=None, attention_track=False):
         """A whole recording in, one gaze track out: frames_u8 uint8 (N, H, W, 3) and wav fp32 (n,) at 24 kHz, both resident on
         the device -> {"points": (N, 2), "peak": (N,), "count": (N,) int32 = windows that predicted the frame, "heatmaps" and
         "rescaled": (N, S/4, S/4) (left out with return_heatmaps=False), "windows": their number}, on the device.
@@ -458,7 +566,19 @@ class GazePredictor:
         fill: None (the sparse track above), "hold" or "linear": the track is fill_track of the sparse one, so every frame
         between two predictions at most max_gap frames apart (default: default_max_gap of the plan, SAMPLING_RATE + 1) carries
         a map and a point; "count" stays, "neighbours" (N, 2) int32, "filled" (N,) bool and "max_gap" (the gap applied, a host
-        int) are added, and overlay=True draws the filled track.  Still one forward pass per window."""
+        int) are added, and overlay=True draws the filled track.  Still one forward pass per window.
+
+        attention_track=True: every batch runs predict_batch(attention=True) and one ops.attention_track call over the plan's
+        "frames_idx" adds where the audio attends over the recording (include/csts_hip.h, csts_attention_track), with Hh heads on
+        the grid (h, w) of the spatial fusion block: "attention_maps" (N, Hh + 1, h, w) = per video frame and head (index Hh: the
+        head mean) the mean over the (window, input frame) pairs that show the frame of that pair's time-mixed map, rescaled by
+        its own lattice extrema -- render_attention_track draws it; "attention_range" (N, Hh + 1, 2) = those extrema (NaN where
+        no pair lands), "attention_mixed" = the mean before the rescale, "attention_count" (N,) int32 = pairs per frame,
+        "temporal_attention_windows" (windows, n, n) and "attention_crop_size" (a host int).  A frame one pair shows carries
+        predict(attention=True)'s maps of that window and input frame bit for bit.  The track lands on the INPUT frames, the gaze
+        track on the predicted ones.  With a fill mode the attention track is filled too (fill_attention_track; default gap
+        default_attention_gap of the plan, max_gap overrides it as well): "attention_neighbours", "attention_filled" and
+        "attention_max_gap" are added.  Every gaze entry keeps the bits it has without the flag."""
         if fill not in (None, "hold", "linear"):
             raise ValueError(f"fill must be None, \"hold\" or \"linear\", got {fill!r}")
         if fill is None and max_gap is not None:
@@ -490,6 +610,8 @@ class GazePredictor:
             centers = torch.from_numpy(plan["audio_centers"]).to(dev)
             o = (AUDIO_WIDTH - S) // 2
             preds = torch.empty(nwin * T, S // 4, S // 4, dtype=torch.float32, device=dev)
+            attention_track = bool(attention_track)
+            column = temporal = None
             for w0 in range(0, nwin, nb):
                 n = min(nb, nwin - w0)
                 sel = slice(w0, w0 + n)
@@ -501,8 +623,15 @@ class GazePredictor:
                 audio = inputs.audio_windows_at(spec, cen, AUDIO_WIDTH)
                 if S != AUDIO_WIDTH:   # S frequency bins x S columns around each frame, as predict() cuts them
                     audio = audio[:, :, :, :S, o:o + S].contiguous()
-                out = self.predict_batch({"video": video, "audio": audio})
+                out = self.predict_batch({"video": video, "audio": audio}, attention=attention_track)
                 preds[w0 * T:(w0 + n) * T] = out["heatmaps"][:n].reshape(n * T, S // 4, S // 4)
+                if attention_track:                           # the padded repeats are dropped here too
+                    if column is None:
+                        column = torch.empty((nwin,) + tuple(out["audio_attention"].shape[1:]), dtype=torch.float32, device=dev)
+                        temporal = torch.empty((nwin,) + tuple(out["temporal_attention"].shape[1:]),
+                                               dtype=out["temporal_attention"].dtype, device=dev)
+                    column[sel] = out["audio_attention"][:n]
+                    temporal[sel] = out["temporal_attention"][:n]
             target = torch.from_numpy(plan["target_idx"].reshape(-1)).to(dev)
             if fill is None:
                 want = ("points", "peak", "count") + (("heatmaps", "rescaled") if return_heatmaps or overlay else ())
@@ -510,6 +639,13 @@ class GazePredictor:
             else:                                             # the fill reads the sparse maps: they are dropped at the end
                 track = fill_track(ops.gaze_track(preds, target, N, want=("heatmaps", "count")), mode=fill, max_gap=max_gap,
                                    plan=plan)
+            if attention_track:
+                att = ops.attention_track(column, frames_idx, N, T, S)
+                track.update({"attention_maps": att["maps"], "attention_range": att["range"], "attention_mixed": att["mixed"],
+                              "attention_count": att["count"], "temporal_attention_windows": temporal,
+                              "attention_crop_size": S})
+                if fill is not None:
+                    track = fill_attention_track(track, mode=fill, max_gap=max_gap, plan=plan)
             if overlay:
                 track["points_source"] = points_to_source(track["points"], row, S)
                 track["overlay"] = self.render_track(frames_u8, track)

@@ -42,11 +42,14 @@ def half_dtype():
     return torch.float16 if HALF == "fp16" else torch.bfloat16
 
 
-ABI_VERSION = 10   # == CSTS_ABI_VERSION of include/csts_hip.h this binding mirrors (struct layouts below)
+ABI_VERSION = 11   # == CSTS_ABI_VERSION of include/csts_hip.h this binding mirrors (struct layouts below)
 F32, BF16 = 0, 1
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 EPI_NONE, EPI_GELU, EPI_DGELU = 0, 1, 2
 MASK_NONE, MASK_SPATIAL = 0, 1
+# size limits of include/csts_hip.h the Python side names in its own errors
+GAZE_DECODE_MAX_HW = 8192
+AUDIO_PIXEL_MAX_SIDE, AUDIO_PIXEL_MAX_HW = 128, 4096
 
 vp = C.c_void_p
 i64 = C.c_int64
@@ -270,6 +273,8 @@ SYMBOLS = {
     "csts_gaze_track_fill": (_I, [vp, vp, i64, _I, _I, _I, _I, vp, vp, vp, vp, vp, vp]),
     "csts_gaze_overlay": (_I, [vp, vp, vp, vp, vp, i64, _I, _I, _I, _I, _I, _F, _I, vp]),
     "csts_audio_pixel_attn": (_I, [vp, _I, vp, _I, _I, _I, _I, _I, _I, _I, _I, _F, vp, vp, vp, vp, vp]),
+    "csts_attention_track": (_I, [vp, vp, vp, i64, _I, _I, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp]),
+    "csts_attention_rescale": (_I, [vp, vp, _I, i64, _I, _I, _I, vp, vp, vp]),
 }
 
 

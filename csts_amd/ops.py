@@ -2462,6 +2462,17 @@ def gaze_decode(logits, temperature=2.0, want=_DECODE_OUTPUTS):
 _TRACK_OUTPUTS = ("heatmaps", "rescaled", "points", "peak", "count")
 
 
+def _target_lists(target_idx, n_frames):
+    """int64 (P,) target frames -> the device lists csts_gaze_track / csts_attention_track take: order int32 (P,) = the rows
+    sorted by target (stable: ascending row within a frame), offsets int32 (n_frames + 1,) = each frame's bounds in it.  Targets
+    outside [0, n_frames) go to a discard bucket behind the last frame.  No host sync."""
+    inside = (target_idx >= 0) & (target_idx < n_frames)
+    bucket = torch.where(inside, target_idx, torch.full_like(target_idx, n_frames))      # n_frames: the discard bucket
+    sorted_t, order = torch.sort(bucket, stable=True)
+    offsets = torch.searchsorted(sorted_t, torch.arange(n_frames + 1, device=target_idx.device, dtype=torch.int64))
+    return order.to(torch.int32), offsets.to(torch.int32)
+
+
 def gaze_track(preds, target_idx, n_frames, want=_TRACK_OUTPUTS):
     """csts_gaze_track: P per-window heat maps preds (P, H, W) fp32, each predicting video frame target_idx[p] (int64 (P,)), ->
     one entry per frame of the video: heatmaps (n_frames, H, W) = the mean of the maps that target the frame (added in
@@ -2484,11 +2495,7 @@ def gaze_track(preds, target_idx, n_frames, want=_TRACK_OUTPUTS):
         raise ValueError(f"gaze_track needs P >= 1 maps and n_frames >= 1, got {P} and {n_frames}")
     x = preds.detach().contiguous()
     dev = x.device
-    inside = (target_idx >= 0) & (target_idx < n_frames)
-    bucket = torch.where(inside, target_idx, torch.full_like(target_idx, n_frames))      # n_frames: the discard bucket
-    sorted_t, order = torch.sort(bucket, stable=True)
-    offsets = torch.searchsorted(sorted_t, torch.arange(n_frames + 1, device=dev, dtype=torch.int64)).to(torch.int32)
-    order = order.to(torch.int32)
+    order, offsets = _target_lists(target_idx, n_frames)
     out = {}
     for k, shape, dt in (("heatmaps", (n_frames, H, W), torch.float32), ("rescaled", (n_frames, H, W), torch.float32),
                          ("points", (n_frames, 2), torch.float32), ("peak", (n_frames,), torch.float32),
@@ -2646,4 +2653,73 @@ def audio_pixel_attn(qkv, lse, thw, heads, n_frames, crop_size):
     L.check(_lib().csts_audio_pixel_attn(_p(x), _dt(x), _p(l), B, heads, hd, Tp, h, w, T, S, hd ** -0.5, _p(out["column"]),
                                          _p(out["column_mean"]), _p(out["maps"]), _p(out["range"]), _stream()),
             "csts_audio_pixel_attn")
+    return out
+
+
+def _attention_grid(h, w, what):
+    if h < 1 or w < 1 or h > L.AUDIO_PIXEL_MAX_SIDE or w > L.AUDIO_PIXEL_MAX_SIDE or h * w > L.AUDIO_PIXEL_MAX_HW:
+        raise ValueError(f"{what} needs 1 <= h, w <= CSTS_AUDIO_PIXEL_MAX_SIDE ({L.AUDIO_PIXEL_MAX_SIDE}) and h * w <= "
+                         f"CSTS_AUDIO_PIXEL_MAX_HW ({L.AUDIO_PIXEL_MAX_HW}), got {h} x {w}")
+
+
+def attention_track(column, frames_idx, n_frames, n_input_frames, crop_size):
+    """csts_attention_track: the audio_attention of every window of a recording -- column fp32 (Wn, heads, T', h, w), windows
+    concatenated -- and frames_idx, an integer (Wn, T) device tensor = the video frame each window's input frame j shows (T =
+    n_input_frames, plan_video's "frames_idx") -> one attention map per video frame, head and head mean:
+    {"mixed": (F, heads + 1, h, w) = the mean over the (window, input frame) pairs that land on the frame (added in ascending
+              w T + j) of the map audio_pixel_attn mixes in time for that pair; index `heads` = the head mean,
+     "maps": same shape = mixed rescaled by the extrema its bilinear upsample takes on the S x S crop lattice (S = crop_size) --
+             what gaze_overlay draws,
+     "range": (F, heads + 1, 2) = those extrema (lo, hi),
+     "count": (F,) int32 = pairs that landed on the frame}, F = n_frames.  A frame no pair lands on: mixed and maps 0, range NaN.
+    Frames outside [0, F) are dropped.  A frame with one pair carries audio_pixel_attn's maps / range of that pair bit for bit.
+    The pair lists are built on the device as gaze_track builds its rows (stable sort, binary search): two launches of the
+    library, no host sync, graph-capturable.  The rule is stated in include/csts_hip.h."""
+    _need_gpu(column, frames_idx)
+    if column.requires_grad and torch.is_grad_enabled():
+        raise L.CstsError("attention_track is an inference output: it has no backward (call it under torch.no_grad())")
+    if column.dim() != 5 or column.dtype != torch.float32:
+        raise ValueError(f"column must be fp32 (Wn, heads, T', h, w), got {tuple(column.shape)} {column.dtype}")
+    Wn, heads, Tp, h, w = column.shape
+    F_, T, S = int(n_frames), int(n_input_frames), int(crop_size)
+    if frames_idx.dtype not in (torch.int32, torch.int64) or tuple(frames_idx.shape) != (Wn, T):
+        raise ValueError(f"frames_idx must be int32 or int64 ({Wn}, {T}), got {tuple(frames_idx.shape)} {frames_idx.dtype}")
+    if F_ < 1 or T < 1 or S < 1 or Wn < 1 or heads < 1 or Tp < 1:
+        raise ValueError(f"attention_track needs n_frames, n_input_frames, crop_size, Wn, heads and T' >= 1, got {F_}, {T}, {S}, "
+                         f"{Wn}, {heads} and {Tp}")
+    _attention_grid(h, w, "attention_track")
+    x = column.detach().contiguous()
+    dev = x.device
+    order, offsets = _target_lists(frames_idx.reshape(-1).to(torch.int64), F_)
+    out = {"mixed": torch.empty(F_, heads + 1, h, w, dtype=torch.float32, device=dev),
+           "maps": torch.empty(F_, heads + 1, h, w, dtype=torch.float32, device=dev),
+           "range": torch.empty(F_, heads + 1, 2, dtype=torch.float32, device=dev),
+           "count": torch.empty(F_, dtype=torch.int32, device=dev)}
+    L.check(_lib().csts_attention_track(_p(x), _p(order), _p(offsets), F_, Wn, heads, Tp, h, w, T, S, _p(out["mixed"]),
+                                        _p(out["maps"]), _p(out["range"]), _p(out["count"]), _stream()), "csts_attention_track")
+    return out
+
+
+def attention_rescale(mixed, crop_size, valid=None):
+    """csts_attention_rescale: coarse maps mixed fp32 (F, G, h, w) -> {"maps": (F, G, h, w) = (mixed - lo) / (hi - lo + 1e-6),
+    "range": (F, G, 2) = (lo, hi)}, the extrema of each map's bilinear upsample over the S x S crop lattice (S = crop_size) --
+    the second half of attention_track, for maps that changed after it (a filled track).  valid (optional, int32 or bool (F,)
+    on the device): a frame with valid <= 0 gets maps 0 and range NaN.  One launch, no host sync: graph-capturable."""
+    _need_gpu(mixed, valid)
+    if mixed.dim() != 4 or mixed.dtype != torch.float32:
+        raise ValueError(f"mixed must be fp32 (F, G, h, w), got {tuple(mixed.shape)} {mixed.dtype}")
+    F_, G, h, w = mixed.shape
+    S = int(crop_size)
+    if F_ < 1 or G < 1 or S < 1:
+        raise ValueError(f"attention_rescale needs F >= 1 frames, G >= 1 maps a frame and crop_size >= 1, got {F_}, {G} and {S}")
+    _attention_grid(h, w, "attention_rescale")
+    v = None
+    if valid is not None:
+        if valid.dtype not in (torch.int32, torch.bool) or tuple(valid.shape) != (F_,):
+            raise ValueError(f"valid must be int32 or bool ({F_},), got {tuple(valid.shape)} {valid.dtype}")
+        v = valid.to(torch.int32).contiguous()
+    x = mixed.detach().contiguous()
+    out = {"maps": torch.empty_like(x), "range": torch.empty(F_, G, 2, dtype=torch.float32, device=x.device)}
+    L.check(_lib().csts_attention_rescale(_p(x), _p(v), G, F_, h, w, S, _p(out["maps"]), _p(out["range"]), _stream()),
+            "csts_attention_rescale")
     return out

@@ -32,10 +32,10 @@ enum { CSTS_EPI_NONE = 0, CSTS_EPI_GELU = 1, CSTS_EPI_DGELU = 2 };
 enum { CSTS_MASK_NONE = 0, CSTS_MASK_SPATIAL = 1 };
 
 /* Version of this header's struct layouts and call semantics.  Bumped whenever a struct grows or a field changes meaning
- * (2: csts_gemm_args.res_up; 3: compact k|v rows, 16-bit build, loss scaler in csts_opt_args; 4: csts_opt_args.extra_sq, factored AdamW; 5: grouped stencil weight gradients; 6: csts_copy_token_segments, csts_wgrad_grouped8_limited; 7: csts_wgrad_grouped5, csts_gemm algo 500; 8: csts_opt_rule, csts_opt_step, csts_opt_factored_step, csts_opt_factored.tensor replaces pad_; 10: csts_audio_pixel_attn).  csts_abi_version() returns the value the
+ * (2: csts_gemm_args.res_up; 3: compact k|v rows, 16-bit build, loss scaler in csts_opt_args; 4: csts_opt_args.extra_sq, factored AdamW; 5: grouped stencil weight gradients; 6: csts_copy_token_segments, csts_wgrad_grouped8_limited; 7: csts_wgrad_grouped5, csts_gemm algo 500; 8: csts_opt_rule, csts_opt_step, csts_opt_factored_step, csts_opt_factored.tensor replaces pad_; 10: csts_audio_pixel_attn; 11: csts_attention_track, csts_attention_rescale).  csts_abi_version() returns the value the
  * LIBRARY was built with: a caller must compare it with the CSTS_ABI_VERSION it was compiled against and refuse a mismatch
  * (the Python binding does, csts_amd/lib.py::load). */
-#define CSTS_ABI_VERSION 10
+#define CSTS_ABI_VERSION 11
 const char* csts_last_error(void);
 int csts_abi_version(void);
 int csts_half_kind(void);   /* the 16-bit type behind CSTS_BF16 in THIS library: 0 bfloat16 (libcsts_hip.so), 1 IEEE half (libcsts_hip_f16.so) */
@@ -711,6 +711,45 @@ int csts_gaze_overlay(const uint8_t* frames_nhwc, const float* rescaled, const i
 #define CSTS_AUDIO_PIXEL_MAX_HW 4096
 int csts_audio_pixel_attn(const void* qkv, int dt, const float* lse, int B, int heads, int head_dim, int Tp, int h, int w, int T,
                           int S, float scale, float* column, float* column_mean, float* maps, float* range, hipStream_t stream);
+
+/* ---- whole-recording attention track (csts_amd/csrc/fusion_maps.hip): the fusion attention maps of every window of a recording
+ *      (csts_audio_pixel_attn's `column`, windows concatenated) become one map per video frame, head and head mean -- for the
+ *      attention what csts_gaze_track is for the heat maps.
+ *      column [Wn][heads][T'][h * w] fp32.  A pair is p = w * T + j: window w, input frame j of its T input frames; it lands on
+ *      the video frame frames_idx[w][j].  order[offsets[f] .. offsets[f + 1]) lists the pairs of output frame f in [0, F) in
+ *      ascending p (offsets int32 [F + 1], non-decreasing, order int32 with values in [0, Wn * T); both in DEVICE memory): the
+ *      lists csts_gaze_track takes, here of input frames.  A pair whose frame lies outside [0, F) is in no list: it is dropped.
+ *      Rule, all fp32, per output frame f and index g in [0, heads] (g == heads: the head mean), n = offsets[f + 1] - offsets[f]:
+ *        m_p          = the map csts_audio_pixel_attn mixes for (window w, input frame j, g) before it rescales it:
+ *                       fl(fl((1 - lambda) col[t0]) + fl(lambda col[t1])) with (t0, t1, lambda) of input frame j on the axis
+ *                       (T, T') as stated there; for g == heads col[t] is the head mean ((0 + c_0) + c_1 + ...) / heads of the
+ *                       coarse map t, taken BEFORE the mix.  One device function serves both entries: the bits are equal.
+ *        mixed[f][g]  = (((0 + m_p0) + m_p1) + ... ) * (1 / n), pairs added in list order: the mean of csts_gaze_track.
+ *        range[f][g]  = (lo, hi) = the extrema of the bilinear upsample of mixed[f][g] over the S x S crop lattice, from the end
+ *                       pixels of every cell interval, by the device function csts_audio_pixel_attn evaluates them with.
+ *        maps[f][g]   = (mixed[f][g] - lo) / (hi - lo + 1e-6)
+ *        count[f]     = n
+ *        n == 0 (no pair lands on the frame):  mixed and maps 0, range (NaN, NaN), count 0.
+ *      The mean comes before the rescale: the extrema of a mean are not the mean of the extrema, and a picture rescaled by its own
+ *      extrema is what csts_gaze_overlay draws.  A frame exactly one pair hits therefore carries, bit for bit, the maps and range
+ *      csts_audio_pixel_attn gives for that window and input frame ((0 + m) * 1 = m).
+ *      Outputs: mixed, maps [F][heads + 1][h * w], range [F][heads + 1][2] fp32, count [F] int32; none may be NULL.  Sizes: Wn,
+ *      heads, F >= 1; 1 <= h, w <= CSTS_AUDIO_PIXEL_MAX_SIDE, h w <= CSTS_AUDIO_PIXEL_MAX_HW; 1 <= T, T', S <= 65536; Wn T and
+ *      F (heads + 1) below 2^31.  Two launches on `stream`: one workgroup per (f, g) walks its pair list with the sum in LDS, then
+ *      csts_attention_rescale with valid = count.  No atomics (deterministic), no allocation, no synchronisation, no host read:
+ *      graph-capturable. */
+int csts_attention_track(const float* column, const int* order, const int* offsets, int64_t F, int Wn, int heads, int Tp, int h,
+                         int w, int T, int S, float* mixed, float* maps, float* range, int* count, hipStream_t stream);
+
+/* ---- extrema and rescale of coarse maps (csts_amd/csrc/fusion_maps.hip): mixed [F][G][h * w] fp32, G = nmaps_per_frame ->
+ *      range[f][g] = (lo, hi), the extrema of the bilinear upsample of mixed[f][g] over the S x S lattice, and maps[f][g] =
+ *      (mixed[f][g] - lo) / (hi - lo + 1e-6), exactly as csts_attention_track states them (it is that entry's second launch).
+ *      valid int32 [F] in DEVICE memory or NULL: a frame with valid[f] <= 0 gets maps 0 and range (NaN, NaN); NULL: every frame
+ *      is valid.  Called alone after a fill of `mixed` (csts_gaze_track_fill on the maps viewed as one tall map per frame), with
+ *      valid = predicted or filled.  maps must not be mixed.  Sizes as above; F G below 2^31.  One launch, one workgroup per
+ *      (f, g); no allocation, no synchronisation, no host read: graph-capturable. */
+int csts_attention_rescale(const float* mixed, const int* valid, int nmaps_per_frame, int64_t F, int h, int w, int S, float* maps,
+                           float* range, hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -28,7 +28,15 @@ GazePredictor.predict(attention=True): audio_attention, audio_attention_mean, at
 temporal_attention.  --attention-dir DIR (implies --attention; needs --clip, whose uint8 frames are drawn on) additionally writes,
 as the reference's vis_av_st_fusion does, DIR/spat_attn_<clip>_<frame>_head_<k>.png for every head and ..._head_mean.png
 (GazePredictor.render_attention, through PIL; without PIL one line says so and no image is written) and
-DIR/temporal_attn_<clip>.txt.  A whole-recording attention track is not defined yet: --attention with --video is an error."""
+DIR/temporal_attn_<clip>.txt.  These per-clip arrays are not defined yet for a whole recording: --attention with --video is an
+error; a recording has --attention-track.
+--attention-track (with --video): the fusion attention over the whole recording (GazePredictor.predict_video(attention_track=True),
+csts_attention_track): --out also receives attention_maps and attention_mixed (N, heads + 1, h, w), attention_range
+(N, heads + 1, 2), attention_count (N,) and temporal_attention_windows (windows, n, n); with --fill the attention track is filled
+too and attention_neighbours (N, 2) and attention_filled (N,) are added.  The json_stats line gains "attention_track" and
+"attention_frames" (frames a map was computed for).  --attention-overlay HEAD|mean (implies --attention-track): --out also
+receives attention_overlay uint8 (N, H, W, 3), that head's map (or the head mean) drawn onto the recording with the gaze track's
+points as discs (GazePredictor.render_attention_track).  Without these flags the output and the record are what they were."""
 import argparse
 import json
 import os
@@ -62,6 +70,9 @@ def parse_args(argv=None):
     p.add_argument("--attention", action="store_true", help="add the fusion attention maps to --out (one clip, not --video)")
     p.add_argument("--attention-dir", default=None, type=str,
                    help="with --clip: also write the attention overlays as PNGs and the temporal matrices as text here (implies --attention)")
+    p.add_argument("--attention-track", action="store_true", help="with --video: add the whole-recording attention track to --out")
+    p.add_argument("--attention-overlay", default=None, type=str, metavar="HEAD|mean",
+                   help="with --video: also draw that head's attention track onto the recording (implies --attention-track)")
     p.add_argument("--seed", default=2000, type=int, help="seed of the synthetic batch used without --clip")
     p.add_argument("--batch", default=2, type=int, help="clips in the synthetic batch used without --clip")
     p.add_argument("--no-graph", action="store_true", help="launch the kernels eagerly instead of replaying a HIP graph")
@@ -73,8 +84,16 @@ def parse_args(argv=None):
     if (args.overlay or args.overlay_dir) and args.video is None:
         p.error("--overlay and --overlay-dir draw onto a recording: they need --video")
     if (args.attention or args.attention_dir) and args.video is not None:
-        p.error("--attention and --attention-dir show one clip's fusion attention: they do not work with --video (a whole-recording "
-                "attention track is not defined yet); use --clip")
+        p.error("--attention and --attention-dir show one clip's fusion attention: they do not work with --video (the per-clip "
+                "arrays are not defined yet for a whole recording); use --clip, or --attention-track for the recording's track")
+    if (args.attention_track or args.attention_overlay is not None) and args.video is None:
+        p.error("--attention-track and --attention-overlay follow the attention over a recording: they need --video")
+    if args.attention_overlay is not None and args.attention_overlay != "mean":
+        try:
+            if int(args.attention_overlay) < 0:
+                raise ValueError
+        except ValueError:
+            p.error("--attention-overlay takes a head index (0, 1, ...) or mean")
     if args.attention_dir is not None and args.clip is None:
         p.error("--attention-dir draws onto a clip's uint8 frames: it needs --clip")
     if args.fill is not None and args.video is None:
@@ -129,6 +148,7 @@ def main(argv=None):
     torch.manual_seed(cfg.RNG_SEED)
     predictor = GazePredictor(cfg, args.checkpoint, device=dev, graph=not args.no_graph)
     if args.video is not None:
+        attention_track = bool(args.attention_track or args.attention_overlay is not None)
         with np.load(args.video) as z:
             missing = [k for k in VIDEO_KEYS if k not in z.files]
             if missing:
@@ -136,9 +156,17 @@ def main(argv=None):
             fps = args.fps if args.fps is not None else (float(z["fps"]) if "fps" in z.files else None)
             out = predictor.predict_video(torch.from_numpy(z["frames_u8"]).to(dev), torch.from_numpy(z["wav"]).float().to(dev),
                                           fps=fps, stride=args.stride, overlay=bool(args.overlay or args.overlay_dir),
-                                          fill=args.fill, max_gap=args.max_gap)
+                                          fill=args.fill, max_gap=args.max_gap, attention_track=attention_track)
+            if args.attention_overlay is not None:
+                head = None if args.attention_overlay == "mean" else int(args.attention_overlay)
+                out["attention_overlay"] = predictor.render_attention_track(torch.from_numpy(z["frames_u8"]).to(dev), out, head=head,
+                                                                            points=out["points"])
         keys = ("points", "peak", "count", "rescaled", "heatmaps") + (("points_source", "overlay") if "overlay" in out else ())
         keys += ("neighbours", "filled") if args.fill is not None else ()
+        if attention_track:
+            keys += ("attention_maps", "attention_range", "attention_mixed", "attention_count", "temporal_attention_windows")
+            keys += ("attention_neighbours", "attention_filled") if args.fill is not None else ()
+            keys += ("attention_overlay",) if args.attention_overlay is not None else ()
         arrays = {k: out[k].cpu().numpy() for k in keys}
         np.savez(args.out, **arrays)
         if args.overlay_dir is not None:
@@ -150,6 +178,11 @@ def main(argv=None):
                   "shapes": {k: list(v.shape) for k, v in arrays.items()}}
         if args.fill is not None:
             record.update({"fill": args.fill, "max_gap": int(out["max_gap"]), "filled_frames": int(arrays["filled"].sum())})
+        if attention_track:
+            frames = arrays["attention_count"] > 0
+            if args.fill is not None:
+                frames = frames | arrays["attention_filled"]
+            record.update({"attention_track": True, "attention_frames": int(frames.sum())})
         print("json_stats: " + json.dumps(record), flush=True)
         return
     if args.clip is not None:
