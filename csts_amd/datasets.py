@@ -5,7 +5,9 @@ Layout under CSTS_AMD.DATA_ROOT (decoding is out of scope; tools/make_toy_datase
   train.csv, test.csv                         one clip per line, `<video>/<video>_t<start>_t<end>.mp4` (the reference's lists; the
                                               extension is ignored; val reads test.csv as the reference does)
   clips/<video>/<clip>.npz                    frames_u8 uint8 (N, H, W, 3), wav fp32 (n,) at 24 kHz [, fps]: what
-                                              tools/predict.py --video reads
+                                              tools/predict.py --video reads.  [sample_rate]: the rate wav was recorded at;
+                                              wav, floating or int16, (n,) or (C, n), is then brought to 24 kHz mono on the
+                                              device (inputs.resample_audio) before the spectrogram
   gaze_frame_label/<video>_frame_label.csv    a header row, then one row per video frame; Ego4D keeps columns [1:] = x, y, type
                                               (ego4d_avgaze_forecast.py:121-122), Aria columns [2:] (aria_avgaze_forecast.py:115)
 A clip's first label row is start * DATA.TARGET_FPS.
@@ -204,11 +206,20 @@ class ClipStore:
                 if missing:
                     raise ValueError(f"{path} lacks {missing}: a clip holds frames_u8, wav and optionally fps")
                 frames, wav = z["frames_u8"], z["wav"]
+                rate = np.asarray(z["sample_rate"]).reshape(-1) if "sample_rate" in z.files else None
             if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[-1] != 3 or frames.shape[0] <= self.observed:
                 raise ValueError(f"{path}: frames_u8 must be uint8 (N > {self.observed}, H, W, 3), got {frames.shape} {frames.dtype}")
             self.n_frames[i], self.hw[i] = frames.shape[0], frames.shape[1:3]
             self.frames_host.append(np.ascontiguousarray(frames[:self.observed]))
-            spec = inputs.stft_logpower(torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)).reshape(1, -1).to(self.device))
+            if rate is None:
+                wav = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)).reshape(1, -1).to(self.device)
+            else:
+                if rate.size != 1 or float(rate[0]) != int(rate[0]) or int(rate[0]) < 1 or wav.ndim not in (1, 2):
+                    raise ValueError(f"{path}: sample_rate must be one positive integer and wav (n,) or (C, n), got {rate.tolist()} "
+                                     f"and {wav.shape}")
+                wav = np.ascontiguousarray(wav, dtype=None if wav.dtype == np.int16 else np.float32)
+                wav = inputs.resample_audio(torch.from_numpy(wav).reshape(1, -1, wav.shape[-1]).to(self.device), int(rate[0]))
+            spec = inputs.stft_logpower(wav)
             self.spec_host.append(spec[0].cpu().numpy())
             self.cols[i] = spec.shape[2]
             self.usable[i] = self.observed * self.cols[i] // self.n_frames[i]

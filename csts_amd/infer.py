@@ -308,6 +308,24 @@ class GraphedEvalStep:
         return self.out
 
 
+def _check_rate(sample_rate):
+    from .inputs import check_sample_rate
+    return check_sample_rate(sample_rate)
+
+
+def _check_video_wav(wav, sample_rate):
+    """predict_video's waveform: floating (n,) at 24 kHz, or with a sample rate floating / int16 (n,) or (C, n)."""
+    if sample_rate is None:
+        if wav.dim() != 1 or not wav.is_floating_point():
+            raise ValueError(f"wav must be a floating (n,) waveform, got {tuple(wav.shape)} {wav.dtype} (a (C, n) waveform needs "
+                             "its sample_rate)")
+        return
+    _check_rate(sample_rate)
+    if wav.dim() not in (1, 2) or not (wav.is_floating_point() or wav.dtype == torch.int16):
+        raise ValueError(f"with a sample rate wav must be a floating or int16 (n,) or (C, n) waveform, got {tuple(wav.shape)} "
+                         f"{wav.dtype}")
+
+
 class GazePredictor:
     """Gaze prediction with trained weights on one GPU.
 
@@ -339,14 +357,18 @@ class GazePredictor:
         self._steps = {}           # (B, T, S) or (B, T, S, "attention") -> GraphedEvalStep
 
     @torch.no_grad()
-    def predict(self, frames_u8, wav, frames_idx, frame_length, labels=None, attention=False):
+    def predict(self, frames_u8, wav, frames_idx, frame_length, labels=None, attention=False, sample_rate=None):
         """frames_u8 uint8 (B, T, H, W, 3), wav fp32 (B, n) at 24 kHz, frames_idx (B, T) = the sampled frames' positions on the
         clip's time axis of `frame_length` frames -> {"points": (B, T, 2) (x, y) in [0, 1), "peak": (B, T),
         "heatmaps": (B, T, S/4, S/4), "rescaled": same shape} on the device, S = DATA.TEST_CROP_SIZE.
         Frames that come at S x S are normalised as they are; any other size goes through the test-mode spatial sampling (short
         side to S, centre crop: inputs.spatial_sampling(train=False, spatial_idx=1)), so the points are in the crop's
         coordinates.  labels (optional, (B, T, L >= 2) gaze labels): carried through the same crop and returned as "labels".
-        attention=True adds the fusion attention maps of predict_batch; the other entries keep their bits."""
+        attention=True adds the fusion attention maps of predict_batch; the other entries keep their bits.
+        sample_rate: None (wav is at 24 kHz: today's path, no extra launch), or the rate wav was recorded at: wav, floating or
+        int16, (B, n) or (B, C, n), is first brought to 24 kHz mono on the device (inputs.resample_audio)."""
+        if sample_rate is not None:
+            sample_rate = _check_rate(sample_rate)
         for t in (frames_u8, wav, frames_idx) + ((labels,) if labels is not None else ()):
             if not torch.is_tensor(t) or not t.is_cuda:
                 raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
@@ -354,6 +376,11 @@ class GazePredictor:
         if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 5 or frames_u8.shape[-1] != 3:
             raise ValueError(f"frames must be uint8 (B, T, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
         B, T, H, W, _ = frames_u8.shape
+        if sample_rate is not None:
+            if wav.dim() not in (2, 3) or wav.shape[0] != B:
+                raise ValueError(f"with a sample rate wav must be ({B}, n) or ({B}, C, n), got {tuple(wav.shape)}")
+            with torch.cuda.device(self.device):
+                wav = inputs.resample_audio(wav, sample_rate)
         if wav.dim() != 2 or wav.shape[0] != B or tuple(frames_idx.shape) != (B, T):
             raise ValueError(f"wav must be ({B}, n) and frames_idx ({B}, {T}), got {tuple(wav.shape)} and {tuple(frames_idx.shape)}")
         cfg = self.cfg
@@ -548,7 +575,7 @@ class GazePredictor:
 
     @torch.no_grad()
     def predict_video(self, frames_u8, wav, fps=None, stride=None, batch=None, return_heatmaps=True, overlay=False, fill=None,
-                      max_gap=None, attention_track=False):
+                      max_gap=None, attention_track=False, sample_rate=None):
         """A whole recording in, one gaze track out: frames_u8 uint8 (N, H, W, 3) and wav fp32 (n,) at 24 kHz, both resident on
         the device -> {"points": (N, 2), "peak": (N,), "count": (N,) int32 = windows that predicted the frame, "heatmaps" and
         "rescaled": (N, S/4, S/4) (left out with return_heatmaps=False), "windows": their number}, on the device.
@@ -578,7 +605,12 @@ class GazePredictor:
         predict(attention=True)'s maps of that window and input frame bit for bit.  The track lands on the INPUT frames, the gaze
         track on the predicted ones.  With a fill mode the attention track is filled too (fill_attention_track; default gap
         default_attention_gap of the plan, max_gap overrides it as well): "attention_neighbours", "attention_filled" and
-        "attention_max_gap" are added.  Every gaze entry keeps the bits it has without the flag."""
+        "attention_max_gap" are added.  Every gaze entry keeps the bits it has without the flag.
+
+        sample_rate: None (wav is at 24 kHz: today's path bit for bit, no extra launch), or the rate the audio was recorded
+        at, a positive integer: wav, floating or int16, (n,) or (C, n), is first brought to 24 kHz mono on the device
+        (inputs.resample_audio: channel mean, band-limited polyphase resampling), and the result is what this call would give
+        for that waveform.  Without a rate a 2-D wav stays an error."""
         if fill not in (None, "hold", "linear"):
             raise ValueError(f"fill must be None, \"hold\" or \"linear\", got {fill!r}")
         if fill is None and max_gap is not None:
@@ -589,8 +621,11 @@ class GazePredictor:
         from . import inputs
         if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
             raise ValueError(f"frames must be uint8 (N, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
-        if wav.dim() != 1 or not wav.is_floating_point():
-            raise ValueError(f"wav must be a floating (n,) waveform, got {tuple(wav.shape)} {wav.dtype}")
+        _check_video_wav(wav, sample_rate)
+        if sample_rate is not None:
+            with torch.cuda.device(self.device):
+                wav = inputs.resample_audio(wav[None] if wav.dim() == 2 else wav, sample_rate)
+                wav = wav[0] if wav.dim() == 2 else wav
         N, H, W, _ = frames_u8.shape
         cfg = self.cfg
         S = int(cfg.DATA.TEST_CROP_SIZE)

@@ -47,6 +47,97 @@ def stft_logpower(wav: torch.Tensor, n_fft: int = 511, hop: int = 120, win: int 
     return spec
 
 
+AUDIO_RATE = 24000          # the rate the model's spectrogram is defined at (data/preprocess.py::extract_audio, -ar 24000)
+_RULES, _TABLES = {}, {}    # (rate, target, zeros, beta) -> host rule; (..., device) -> fp32 device table
+
+
+def check_sample_rate(rate, what: str = "sample_rate") -> int:
+    """A sample rate is a positive integer (int or numpy integer; no bool, no float): ValueError otherwise."""
+    import numbers
+    if isinstance(rate, bool) or not isinstance(rate, numbers.Integral) or int(rate) <= 0:
+        raise ValueError(f"{what} must be a positive integer number of samples per second, got {rate!r}")
+    return int(rate)
+
+
+def resample_lds_floats(up: int, down: int, half: int) -> int:
+    """The LDS floats csts_resample_wav needs (include/csts_hip.h): the phase-major filter table and one run's input span."""
+    span = ((L.RESAMPLE_RUN - 1) * down + 2 * half) // up + 2
+    return up * (((2 * half + up) // up) | 1) + span + span // 32 + 1
+
+
+def resample_rule(sample_rate, target_rate=AUDIO_RATE, zeros: int = 10, beta: float = 5.0):
+    """The host side of resample_audio, fp64, cached: (h float64 (2 * half + 1,), up, down, half) with up / down = target_rate /
+    sample_rate reduced by their gcd, half = zeros * max(up, down) and h the windowed sinc scipy.signal.resample_poly designs,
+    h = sinc(k / mx) / mx * kaiser(2 half + 1, beta), k = -half .. half, scaled to sum to up.  A ratio whose table does not fit
+    csts_resample_wav is a ValueError naming the reduced ratio."""
+    import math
+    import numpy as np
+    sample_rate, target_rate = check_sample_rate(sample_rate), check_sample_rate(target_rate, "target_rate")
+    zeros, beta = int(zeros), float(beta)
+    if zeros < 1 or not beta >= 0.0:
+        raise ValueError(f"zeros must be positive and beta non-negative, got {zeros} and {beta}")
+    key = (sample_rate, target_rate, zeros, beta)
+    if key not in _RULES:
+        g = math.gcd(sample_rate, target_rate)
+        up, down = target_rate // g, sample_rate // g
+        mx = max(up, down)
+        half = zeros * mx
+        if mx > L.RESAMPLE_MAX_RATIO or half > L.RESAMPLE_MAX_RATIO or resample_lds_floats(up, down, half) > L.RESAMPLE_MAX_LDS_FLOATS:
+            raise ValueError(f"{sample_rate} Hz -> {target_rate} Hz reduces to the ratio {up}/{down}: its filter of {2 * half + 1} taps "
+                             "is beyond the table the resampling kernel supports (there is no fallback)")
+        k = np.arange(-half, half + 1, dtype=np.float64)
+        h = np.sinc(k / mx) / mx * np.kaiser(2 * half + 1, beta)
+        h = h / h.sum() * up
+        h.setflags(write=False)
+        _RULES[key] = (h, up, down, half)
+    return _RULES[key]
+
+
+def resample_filter(sample_rate, target_rate=AUDIO_RATE, zeros: int = 10, beta: float = 5.0, device=None):
+    """(taps fp32 (2 * half + 1,) on `device` (default: the current GPU), up, down, half): resample_rule's table as
+    csts_resample_wav reads it, cached per (sample_rate, target_rate, zeros, beta, device)."""
+    h, up, down, half = resample_rule(sample_rate, target_rate, zeros, beta)
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise L.CstsError("csts_amd.inputs runs on MI355X only: the filter table lives on a GPU device")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(sample_rate), int(target_rate), int(zeros), float(beta), device)
+    if key not in _TABLES:
+        _TABLES[key] = torch.from_numpy(h.astype("float32")).to(device)
+    return _TABLES[key], up, down, half
+
+
+def resample_audio(wav: torch.Tensor, sample_rate, target_rate=AUDIO_RATE, zeros: int = 10, beta: float = 5.0) -> torch.Tensor:
+    """A waveform at any sample rate -> fp32 at target_rate (24 kHz, what stft_logpower expects), on the device in one launch
+    (csts_resample_wav): wav (n,), (B, n) or (B, C, n), floating or int16 (scaled by 1 / 32768) -> (n_out,) or (B, n_out),
+    n_out = ceil(n * up / down).  The C channels are averaged as the samples are read (ffmpeg's -ac 1) and the mono signal is
+    resampled by resample_rule's filter with zero extension at both ends: scipy.signal.resample_poly(x, up, down).
+    sample_rate == target_rate with a mono fp32 waveform returns the argument itself and launches nothing."""
+    h, up, down, half = resample_rule(sample_rate, target_rate, zeros, beta)
+    if not torch.is_tensor(wav) or wav.dim() not in (1, 2, 3) or not (wav.is_floating_point() or wav.dtype == torch.int16):
+        raise ValueError("wav must be a floating or int16 tensor (n,), (B, n) or (B, C, n), got "
+                         f"{tuple(wav.shape) if torch.is_tensor(wav) else type(wav)} {getattr(wav, 'dtype', '')}")
+    if wav.numel() == 0:
+        raise ValueError(f"wav holds no sample: {tuple(wav.shape)}")
+    _gpu(wav)
+    if up == down and wav.dim() < 3 and wav.dtype == torch.float32:
+        return wav
+    x = wav if wav.dtype in (torch.float32, torch.int16) else wav.float()
+    x = (x.reshape(1, 1, -1) if x.dim() == 1 else x.unsqueeze(1) if x.dim() == 2 else x).contiguous()
+    B, Cn, n = x.shape
+    if B > 65535 or Cn > 64 or n > L.RESAMPLE_MAX_N:
+        raise ValueError(f"resample_audio takes B <= 65535 waveforms of C <= 64 channels, got {tuple(wav.shape)}")
+    lib = L.load()
+    taps = resample_filter(sample_rate, target_rate, zeros, beta, x.device)[0]
+    n_out = lib.csts_resample_len(n, up, down)
+    out = torch.empty(B, n_out, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        L.check(lib.csts_resample_wav(x.data_ptr(), L.WAV_I16 if x.dtype == torch.int16 else L.WAV_F32, B, Cn, n, taps.data_ptr(), up,
+                                      down, half, out.data_ptr(), _s()), "csts_resample_wav")
+    return out[0] if wav.dim() == 1 else out
+
+
 def audio_windows(spec: torch.Tensor, frames_idx: torch.Tensor, frame_length: float, width: int = 256) -> torch.Tensor:
     """(B, nbins, cols) spectrogram + per-clip frame indices (B, T) -> (B, 1, T, nbins, width) windows centred at
     round(idx / frame_length * cols), clipped to the valid range (ego4d_avgaze_forecast.py:216-219)."""

@@ -32,10 +32,10 @@ enum { CSTS_EPI_NONE = 0, CSTS_EPI_GELU = 1, CSTS_EPI_DGELU = 2 };
 enum { CSTS_MASK_NONE = 0, CSTS_MASK_SPATIAL = 1 };
 
 /* Version of this header's struct layouts and call semantics.  Bumped whenever a struct grows or a field changes meaning
- * (2: csts_gemm_args.res_up; 3: compact k|v rows, 16-bit build, loss scaler in csts_opt_args; 4: csts_opt_args.extra_sq, factored AdamW; 5: grouped stencil weight gradients; 6: csts_copy_token_segments, csts_wgrad_grouped8_limited; 7: csts_wgrad_grouped5, csts_gemm algo 500; 8: csts_opt_rule, csts_opt_step, csts_opt_factored_step, csts_opt_factored.tensor replaces pad_; 10: csts_audio_pixel_attn; 11: csts_attention_track, csts_attention_rescale).  csts_abi_version() returns the value the
+ * (2: csts_gemm_args.res_up; 3: compact k|v rows, 16-bit build, loss scaler in csts_opt_args; 4: csts_opt_args.extra_sq, factored AdamW; 5: grouped stencil weight gradients; 6: csts_copy_token_segments, csts_wgrad_grouped8_limited; 7: csts_wgrad_grouped5, csts_gemm algo 500; 8: csts_opt_rule, csts_opt_step, csts_opt_factored_step, csts_opt_factored.tensor replaces pad_; 10: csts_audio_pixel_attn; 11: csts_attention_track, csts_attention_rescale; 12: csts_resample_wav, csts_resample_len).  csts_abi_version() returns the value the
  * LIBRARY was built with: a caller must compare it with the CSTS_ABI_VERSION it was compiled against and refuse a mismatch
  * (the Python binding does, csts_amd/lib.py::load). */
-#define CSTS_ABI_VERSION 11
+#define CSTS_ABI_VERSION 12
 const char* csts_last_error(void);
 int csts_abi_version(void);
 int csts_half_kind(void);   /* the 16-bit type behind CSTS_BF16 in THIS library: 0 bfloat16 (libcsts_hip.so), 1 IEEE half (libcsts_hip_f16.so) */
@@ -569,6 +569,30 @@ int csts_batch_sample(const uint8_t* arena_u8, int64_t arena_bytes, const int64_
                       float* out, int B, int T, int S, int max_W, const float mean[3], const float std[3], hipStream_t stream);
 int csts_audio_gather(const float* spec_arena, const int64_t* specs, const int* centers, float* out, int B, int T, int nbins,
                       int width, hipStream_t stream);
+
+/* ---- audio at any sample rate (csts_amd/csrc/resample.hip, csts_amd/inputs.py::resample_audio): band-limited resampling by the
+ *      rational ratio up / down (reduced: gcd 1), the step the reference does offline with ffmpeg (data/preprocess.py::
+ *      extract_audio, -ar 24000 -ac 1).  Rule, per waveform x of n samples and a filter h of 2 * half + 1 taps (taps, DEVICE
+ *      memory, fp32; inputs.resample_filter designs the windowed sinc scipy.signal.resample_poly uses):
+ *        n_out = ceil(n * up / down)                                             = csts_resample_len(n, up, down)
+ *        y[m]  = sum_i x[i] * h[half + m * down - i * up]   over 0 <= i < n with the h index in [0, 2 * half],
+ *      i.e. zero extension at both ends and zero phase: scipy.signal.resample_poly(x, up, down) for that h.  The products are
+ *      accumulated in fp32 in the order of i.  wav: (B, C, n) contiguous, fp32 (CSTS_WAV_F32) or int16 (CSTS_WAV_I16, scaled by
+ *      1 / 32768); x is the mean of the C channels (summed in the order of c, divided by C), taken while the samples are staged:
+ *      the downmix has no pass of its own.  out fp32 (B, n_out).  Positions are 64-bit.  No host sync, no allocation, no atomics:
+ *      graph-capturable.  Limits: B <= 65535, C <= 64, n <= CSTS_RESAMPLE_MAX_N, up, down, half <= CSTS_RESAMPLE_MAX_RATIO, and
+ *      the phase-major filter table with the input span of one run of CSTS_RESAMPLE_RUN outputs must fit the kernel's LDS:
+ *        up * (ceil((2 half + 1) / up) | 1) + s + s / 32 + 1 <= CSTS_RESAMPLE_MAX_LDS_FLOATS,
+ *        s = ((CSTS_RESAMPLE_RUN - 1) * down + 2 * half) / up + 2   (integer divisions).
+ *      A call outside them, or with a null pointer, returns -1 and launches nothing (csts_resample_len returns -1). */
+enum { CSTS_WAV_F32 = 0, CSTS_WAV_I16 = 1 };
+#define CSTS_RESAMPLE_RUN 256
+#define CSTS_RESAMPLE_MAX_LDS_FLOATS 16384
+#define CSTS_RESAMPLE_MAX_RATIO (1 << 20)
+#define CSTS_RESAMPLE_MAX_N ((int64_t)1 << 40)
+int64_t csts_resample_len(int64_t n, int up, int down);
+int csts_resample_wav(const void* wav, int in_kind, int B, int C, int64_t n, const float* taps, int up, int down, int half,
+                      float* out, hipStream_t stream);
 
 /* ---- gaze head of the inference path (csts_amd/csrc/decode.hip): one read of a frame's logits gives every consumer of a
  *      prediction what it needs.  logits: nframes = B * T frames of H * W cells each, the (B, 1, T, H, W) model output, fp32

@@ -11,7 +11,8 @@
                                               frame, time, x, y, type (Aria)
 
 --dataset picks the clip length (Ego4D forecast: 150 frames of 5 s; Aria forecast: 100 frames of 5 s at 20 fps).  train.csv lists
-every clip, test.csv the last --test-clips of them.  Pure numpy: no GPU needed."""
+every clip, test.csv the last --test-clips of them.  --sample-rate R writes the waveforms at R Hz instead, with a sample_rate entry
+beside them (csts_amd/datasets.py resamples such clips to 24 kHz on the device).  Pure numpy: no GPU needed."""
 import argparse
 import os
 
@@ -22,9 +23,10 @@ CLIP = {"ego4d_av_gaze_forecast": (150, 30, ("frame", "x", "y", "type")),
 
 
 def write_dataset(out, dataset="ego4d_av_gaze_forecast", clips_per_video=(3, 2), sizes=((36, 48), (40, 44)), seconds=5,
-                  test_clips=2, seed=0, label_rows=None):
+                  test_clips=2, seed=0, label_rows=None, sample_rate=None):
     """-> the list of clip lines written to train.csv.  clips_per_video[v] clips of sizes[v % len(sizes)] = (H, W) for video v;
-    label_rows (optional): rows of every video's label table (default: enough for every clip), to make a table run out."""
+    label_rows (optional): rows of every video's label table (default: enough for every clip), to make a table run out.
+    sample_rate (optional): the waveforms are noise at that rate and every clip carries a sample_rate entry."""
     n_frames, fps, header = CLIP[dataset]
     rng = np.random.default_rng(seed)
     lines = []
@@ -35,9 +37,11 @@ def write_dataset(out, dataset="ego4d_av_gaze_forecast", clips_per_video=(3, 2),
         os.makedirs(os.path.join(out, "clips", video), exist_ok=True)
         for c in range(nclips):
             name = f"{video}_t{c * seconds}_t{(c + 1) * seconds}"
+            rate = {} if sample_rate is None else {"sample_rate": np.int64(sample_rate)}
             np.savez(os.path.join(out, "clips", video, name + ".npz"),
                      frames_u8=rng.integers(0, 256, (n_frames, H, W, 3), dtype=np.uint8),
-                     wav=(0.1 * rng.standard_normal(24000 * seconds)).astype(np.float32), fps=np.float32(fps))
+                     wav=(0.1 * rng.standard_normal((24000 if sample_rate is None else int(sample_rate)) * seconds)).astype(np.float32),
+                     fps=np.float32(fps), **rate)
             lines.append(f"{video}/{name}.mp4")
         # a clip's first label row is start * DATA.TARGET_FPS (30 in both configurations), whatever rate the clip runs at
         rows = (nclips - 1) * seconds * 30 + n_frames if label_rows is None else int(label_rows)
@@ -64,8 +68,12 @@ def main(argv=None):
     p.add_argument("--width", default=80, type=int)
     p.add_argument("--test-clips", default=2, type=int)
     p.add_argument("--seed", default=0, type=int)
+    p.add_argument("--sample-rate", default=None, type=int, help="write the waveforms at this rate with a sample_rate entry")
     a = p.parse_args(argv)
-    lines = write_dataset(a.out, a.dataset, (a.clips,) * a.videos, ((a.height, a.width),), test_clips=a.test_clips, seed=a.seed)
+    if a.sample_rate is not None and a.sample_rate < 1:
+        p.error("--sample-rate must be positive")
+    lines = write_dataset(a.out, a.dataset, (a.clips,) * a.videos, ((a.height, a.width),), test_clips=a.test_clips, seed=a.seed,
+                          sample_rate=a.sample_rate)
     print(f"wrote {len(lines)} clips of {a.dataset} to {a.out}")
 
 

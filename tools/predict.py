@@ -36,7 +36,12 @@ csts_attention_track): --out also receives attention_maps and attention_mixed (N
 too and attention_neighbours (N, 2) and attention_filled (N,) are added.  The json_stats line gains "attention_track" and
 "attention_frames" (frames a map was computed for).  --attention-overlay HEAD|mean (implies --attention-track): --out also
 receives attention_overlay uint8 (N, H, W, 3), that head's map (or the head mean) drawn onto the recording with the gaze track's
-points as discs (GazePredictor.render_attention_track).  Without these flags the output and the record are what they were."""
+points as discs (GazePredictor.render_attention_track).  Without these flags the output and the record are what they were.
+Audio at another rate (--clip and --video): an optional npz entry sample_rate (integer scalar) says what rate wav was recorded at,
+--sample-rate R overrides it; wav, floating or int16, may then carry a channel axis in front of its samples ((B, C, n) / (C, n)),
+and is brought to 24 kHz mono on the device first (csts_amd.inputs.resample_audio).  --out then also records sample_rate (what
+came in) and audio_rate (24000), and the json_stats line carries both.  Without either the output and the record are what they
+were."""
 import argparse
 import json
 import os
@@ -49,6 +54,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from csts_amd.config import assert_and_infer_cfg, load_yaml      # noqa: E402
 from csts_amd.infer import GazePredictor                         # noqa: E402
+from csts_amd.inputs import AUDIO_RATE                           # noqa: E402
 
 CLIP_KEYS = ("frames_u8", "wav", "frames_idx", "frame_length")
 VIDEO_KEYS = ("frames_u8", "wav")
@@ -73,6 +79,8 @@ def parse_args(argv=None):
     p.add_argument("--attention-track", action="store_true", help="with --video: add the whole-recording attention track to --out")
     p.add_argument("--attention-overlay", default=None, type=str, metavar="HEAD|mean",
                    help="with --video: also draw that head's attention track onto the recording (implies --attention-track)")
+    p.add_argument("--sample-rate", default=None, type=int,
+                   help="rate wav was recorded at (default: the npz entry sample_rate, else 24000): resampled on the device")
     p.add_argument("--seed", default=2000, type=int, help="seed of the synthetic batch used without --clip")
     p.add_argument("--batch", default=2, type=int, help="clips in the synthetic batch used without --clip")
     p.add_argument("--no-graph", action="store_true", help="launch the kernels eagerly instead of replaying a HIP graph")
@@ -104,7 +112,29 @@ def parse_args(argv=None):
         p.error("--max-gap must be positive")
     if args.overlay_every < 1:
         p.error("--overlay-every must be positive")
+    if args.sample_rate is not None and args.sample_rate < 1:
+        p.error("--sample-rate must be positive")
+    if args.sample_rate is not None and args.video is None and args.clip is None:
+        p.error("--sample-rate is the rate of a recorded waveform: it needs --clip or --video")
     return args
+
+
+def source_rate(z, args, path):
+    """The rate the waveform of an opened npz was recorded at: --sample-rate, else its sample_rate entry, else None (24 kHz)."""
+    if args.sample_rate is not None:
+        return int(args.sample_rate)
+    if "sample_rate" not in z.files:
+        return None
+    rate = np.asarray(z["sample_rate"]).reshape(-1)
+    if rate.size != 1 or float(rate[0]) != int(rate[0]) or int(rate[0]) < 1:
+        raise SystemExit(f"{path}: sample_rate must be one positive integer, got {z['sample_rate']!r}")
+    return int(rate[0])
+
+
+def waveform(z, rate, dev):
+    """wav of an opened npz on the device: fp32 as before without a rate; with one, int16 stays int16 (the kernel scales it)."""
+    wav = torch.from_numpy(z["wav"])
+    return (wav if rate is not None and wav.dtype == torch.int16 else wav.float()).to(dev)
 
 
 def write_pngs(overlay, directory, every):
@@ -154,7 +184,8 @@ def main(argv=None):
             if missing:
                 raise SystemExit(f"{args.video} lacks {missing}: a video holds {list(VIDEO_KEYS)} and optionally fps")
             fps = args.fps if args.fps is not None else (float(z["fps"]) if "fps" in z.files else None)
-            out = predictor.predict_video(torch.from_numpy(z["frames_u8"]).to(dev), torch.from_numpy(z["wav"]).float().to(dev),
+            rate = source_rate(z, args, args.video)
+            out = predictor.predict_video(torch.from_numpy(z["frames_u8"]).to(dev), waveform(z, rate, dev), sample_rate=rate,
                                           fps=fps, stride=args.stride, overlay=bool(args.overlay or args.overlay_dir),
                                           fill=args.fill, max_gap=args.max_gap, attention_track=attention_track)
             if args.attention_overlay is not None:
@@ -168,7 +199,8 @@ def main(argv=None):
             keys += ("attention_neighbours", "attention_filled") if args.fill is not None else ()
             keys += ("attention_overlay",) if args.attention_overlay is not None else ()
         arrays = {k: out[k].cpu().numpy() for k in keys}
-        np.savez(args.out, **arrays)
+        rates = {} if rate is None else {"sample_rate": np.int64(rate), "audio_rate": np.int64(AUDIO_RATE)}
+        np.savez(args.out, **arrays, **rates)
         if args.overlay_dir is not None:
             write_pngs(arrays["overlay"], args.overlay_dir, args.overlay_every)
         record = {"_type": "predict_video", "checkpoint": predictor.checkpoint_path, "source": args.video,
@@ -176,6 +208,7 @@ def main(argv=None):
                   "frames": int(arrays["count"].shape[0]),
                   "covered_frames": int((arrays["count"] > 0).sum()),
                   "shapes": {k: list(v.shape) for k, v in arrays.items()}}
+        record.update({k: int(v) for k, v in rates.items()})
         if args.fill is not None:
             record.update({"fill": args.fill, "max_gap": int(out["max_gap"]), "filled_frames": int(arrays["filled"].sum())})
         if attention_track:
@@ -191,8 +224,9 @@ def main(argv=None):
             if missing:
                 raise SystemExit(f"{args.clip} lacks {missing}: a clip holds {list(CLIP_KEYS)}")
             frames_u8 = torch.from_numpy(z["frames_u8"]).to(dev)
-            out = predictor.predict(frames_u8, torch.from_numpy(z["wav"]).float().to(dev),
-                                    torch.from_numpy(z["frames_idx"]).float().to(dev), float(z["frame_length"]), attention=attention)
+            rate = source_rate(z, args, args.clip)
+            out = predictor.predict(frames_u8, waveform(z, rate, dev), torch.from_numpy(z["frames_idx"]).float().to(dev),
+                                    float(z["frame_length"]), attention=attention, sample_rate=rate)
         if args.attention_dir is not None:
             write_attention(predictor, frames_u8, out, args.attention_dir)
         source = args.clip
@@ -202,14 +236,17 @@ def main(argv=None):
                                   spatial=T.spatial_config(cfg, train=False))
         out = predictor.predict_batch(batch, attention=attention)
         source = f"synthetic_batch(seed={args.seed})"
+        rate = None
     keys = ("points", "peak", "rescaled", "heatmaps")
     if attention:
         keys += ("audio_attention", "audio_attention_mean", "attention_maps", "attention_range", "temporal_attention")
     arrays = {k: out[k].cpu().numpy() for k in keys}
-    np.savez(args.out, **arrays)
-    print("json_stats: " + json.dumps({"_type": "predict", "checkpoint": predictor.checkpoint_path, "source": source,
-                                       "graph": predictor.graph, "out": args.out,
-                                       "shapes": {k: list(v.shape) for k, v in arrays.items()}}), flush=True)
+    rates = {} if rate is None else {"sample_rate": np.int64(rate), "audio_rate": np.int64(AUDIO_RATE)}
+    np.savez(args.out, **arrays, **rates)
+    record = {"_type": "predict", "checkpoint": predictor.checkpoint_path, "source": source, "graph": predictor.graph,
+              "out": args.out, "shapes": {k: list(v.shape) for k, v in arrays.items()}}
+    record.update({k: int(v) for k, v in rates.items()})
+    print("json_stats: " + json.dumps(record), flush=True)
 
 
 if __name__ == "__main__":
