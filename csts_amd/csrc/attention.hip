@@ -1684,7 +1684,8 @@ extern "C" int csts_attn_fwd(const csts_attn_args* a, hipStream_t stream) {
 }
 
 extern "C" size_t csts_attn_bwd_workspace(const csts_attn_args* a) {
-  if (!a) return 0;
+  // a problem ATTN_COMMON_CHECKS refuses needs no workspace (and dkv_plan divides by B * H * cdiv(Nk, 128))
+  if (!a || a->B <= 0 || a->H <= 0 || a->Nq <= 0 || a->Nk <= 0 || (a->head_dim != 96 && a->head_dim != 192)) return 0;
   int nsplit, q_chunk;
   dkv_plan(a, nsplit, q_chunk);
   return nsplit > 1 ? (size_t)2 * nsplit * a->B * a->H * a->Nk * a->head_dim * sizeof(float) : 16;
@@ -1698,12 +1699,13 @@ extern "C" int csts_attn_bwd(const csts_attn_args* a, void* workspace, size_t ws
                    strides_ok(a->dk_strides, a->dtype) && strides_ok(a->dv_strides, a->dtype) &&
                    strides_ok(a->o_strides, a->dtype), "strides must keep 16-byte row alignment");
   AttnP p; fill(a, p);
+  // the query splits are planned and the workspace is checked before the first launch: a refused call writes nothing
+  dkv_plan(a, p.nsplit, p.q_chunk);
+  if (p.nsplit > 1) {
+    CSTS_REQUIRE(workspace != nullptr && ws_bytes >= csts_attn_bwd_workspace(a), "workspace too small");
+    p.ws = reinterpret_cast<float*>(workspace);
+  }
   if (fused_bwd_ok(a)) {   // delta, dQ, dK, dV in one pass over Q / dO / O
-    dkv_plan(a, p.nsplit, p.q_chunk);
-    if (p.nsplit > 1) {
-      CSTS_REQUIRE(workspace != nullptr && ws_bytes >= csts_attn_bwd_workspace(a), "workspace too small");
-      p.ws = reinterpret_cast<float*>(workspace);
-    }
     hipLaunchKernelGGL((attn_bwd_fused_kernel<96>), dim3((unsigned)p.nsplit, (unsigned)(a->B * a->H)), dim3(256), 0, stream, p);
     CSTS_LAUNCH_CHECK();
     if (p.nsplit > 1) {
@@ -1722,11 +1724,6 @@ extern "C" int csts_attn_bwd(const csts_attn_args* a, void* workspace, size_t ws
   }
   // 3. dK, dV (query-split, deterministic reduce)
   {
-    dkv_plan(a, p.nsplit, p.q_chunk);
-    if (p.nsplit > 1) {
-      CSTS_REQUIRE(workspace != nullptr && ws_bytes >= csts_attn_bwd_workspace(a), "workspace too small");
-      p.ws = reinterpret_cast<float*>(workspace);
-    }
     dim3 grid((unsigned)cdiv(a->Nk, 128), p.nsplit, a->B * a->H);
     CSTS_REQUIRE(attn_dispatch(K_DKV, a, p, grid, stream), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on this device");
     CSTS_LAUNCH_CHECK();

@@ -223,7 +223,13 @@ int csts_trilinear_bwd(const csts_pool_geom* g, const void* dy, int dy_dt, void*
 
 /* ---- fused attention core softmax(q k^T scale [same-frame mask]) v  (attention.py:154-158,384-388;
  *      av_attention.py:137-141,334-350).  q/k/v/o are (B, N, H, hd) views given by element strides
- *      {batch, token, head}; hd contiguous.  LSE/delta are fp32 (B, H, Nq); LSE is in the log2 domain. */
+ *      {batch, token, head}; hd contiguous.  LSE/delta are fp32 (B, H, Nq); LSE is in the log2 domain.
+ *      delta is SCRATCH of csts_attn_bwd, not a result: the two-kernel backward writes rowsum(dO * O) into it (the dQ kernel
+ *      leaves it for the dK/dV kernel), the one-pass backward (16-bit, head_dim 96, no mask, Nk <= 128, Nq >= 1024) keeps the
+ *      sums in LDS and leaves the buffer untouched.  It must be given either way; read nothing back from it.
+ *      Every argument, the query-split plan and the workspace size are checked before the first launch: a call that returns
+ *      non-zero has written nothing.  csts_attn_bwd_workspace returns 0 for a problem the calls refuse (a non-positive
+ *      B / H / Nq / Nk, a head_dim other than 96 / 192, NULL). */
 typedef struct {
   const void* Q; const void* K; const void* V; void* O; float* LSE;
   const void* dO; float* delta; void* dQ; void* dK; void* dV;
