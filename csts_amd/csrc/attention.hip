@@ -1583,41 +1583,57 @@ bool strides_ok(const int64_t* s, int dt) {
   return s[0] % a == 0 && s[1] % a == 0 && s[2] % a == 0;
 }
 
-// one-pass backward (attn_bwd_fused_kernel): bf16, head_dim 96, all keys in one LDS tile, no mask, enough queries to split
-bool fused_bwd_ok(const csts_attn_args* a) {
-  static const bool off = [] { const char* e = getenv("CSTS_ATTN_FUSED_BWD"); return e && atoi(e) == 0; }();
-  return !off && a->dtype == CSTS_BF16 && a->head_dim == 96 && a->Nk <= 128 && a->mask_mode == 0 && a->Nq >= 1024;
+// The four switches, read once per process (atoi): 0 turns a fast form off; CSTS_ATTN_DQ_FAST = 4 selects the 128-key dQ form.
+struct AttnSwitches { bool fwd_fast, dkv_fast, fused; int dq; };
+const AttnSwitches& attn_switches() {
+  static const AttnSwitches s = [] {
+    auto num = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : -1; };
+    return AttnSwitches{num("CSTS_ATTN_FWD_FAST") != 0, num("CSTS_ATTN_DKV_FAST") != 0, num("CSTS_ATTN_FUSED_BWD") != 0, num("CSTS_ATTN_DQ_FAST")};
+  }();
+  return s;
 }
 
-// attn_dkv_kernel's FAST form: hd 96, bf16, no mask, every query tile whole (128 queries)
-bool dkv_fast(int dt, int hd, int mask_mode, int Nq) {
-  static const bool off = [] { const char* e = getenv("CSTS_ATTN_DKV_FAST"); return e && atoi(e) == 0; }();
-  return !off && dt == CSTS_BF16 && hd == 96 && mask_mode == 0 && Nq % 128 == 0;
-}
+// Which kernels run a problem and with which query splits, decided ONCE: csts_attn_fwd and csts_attn_bwd launch what attn_route
+// answers, csts_attn_bwd_workspace returns its ws_bytes and csts_attn_route spells it.
+enum { FWD_GENERIC, FWD_FAST };
+enum { DQ_NONE, DQ_GENERIC, DQ_FAST64, DQ_FAST128 };             // DQ_NONE: the one-pass kernel computes dQ itself
+enum { DKV_ONE_PASS, DKV_FAST, DKV_SLOW, DKV_PLAIN };            // attn_bwd_fused_kernel, <96,false,false>, <HD,F32,true>, <192,false,false>
+struct AttnRoute { int fwd, dq, dkv, nsplit, q_chunk; size_t ws_bytes; };
 
-// attn_dq_fast_kernel: hd 96, bf16, no mask, every key tile whole.  Returns the 32-key units per tile (0: generic kernel).
-// 2 (64-key tiles, two workgroups per CU) is the library's choice: 128-key tiles at one workgroup per CU measured 3-17 %
-// slower per call (profiles/r3_attn_backward_ab.txt).  CSTS_ATTN_DQ_FAST = 0 / 4 forces the generic kernel / the 128-key form.
-int dq_fast(int dt, int hd, int mask_mode, int Nk) {
-  static const int force = [] { const char* e = getenv("CSTS_ATTN_DQ_FAST"); return e ? atoi(e) : -1; }();
-  if (force == 0 || dt != CSTS_BF16 || hd != 96 || mask_mode != 0 || Nk % 64 != 0) return 0;
-  return (force == 4 && Nk % 128 == 0) ? 4 : 2;
-}
-
-void dkv_plan(const csts_attn_args* a, int& nsplit, int& q_chunk) {
-  if (fused_bwd_ok(a)) {      // one workgroup per CU (its LDS holds K, V and the Q / dO tile): aim at two rounds of the chip
-    const int64_t want = std::max<int64_t>(1, std::min<int64_t>(256 / ((int64_t)a->B * a->H), cdiv(a->Nq, 256)));
-    q_chunk = (int)(cdiv(cdiv(a->Nq, want), 128) * 128);
-    nsplit = (int)cdiv(a->Nq, q_chunk);
-    return;
+// false: a problem the entry points refuse (NULL, a non-positive B / H / Nq / Nk, a head_dim other than 96 / 192); the plan
+// below divides by B * H * cdiv(Nk, 128).  Reads dtype, head_dim, B, H, Nq, Nk, mask_mode and the switches, nothing else.
+bool attn_route(const csts_attn_args* a, AttnRoute* r) {
+  if (!a || a->B <= 0 || a->H <= 0 || a->Nq <= 0 || a->Nk <= 0 || (a->head_dim != 96 && a->head_dim != 192)) return false;
+  const AttnSwitches& sw = attn_switches();
+  const int Nq = a->Nq, Nk = a->Nk, hd = a->head_dim;
+  const bool h16 = a->dtype == CSTS_BF16, open = a->mask_mode == 0;
+  const bool fast96 = h16 && hd == 96 && open;      // what every fast form needs: 16-bit, hd 96, no mask; then its tiles whole
+  r->fwd = sw.fwd_fast && fast96 && Nk % 64 == 0 ? FWD_FAST : FWD_GENERIC;
+  int qblk;                                         // queries per tile of the kernel that produces dK / dV
+  int64_t want;                                     // query splits aimed at
+  if (sw.fused && fast96 && Nk <= 128 && Nq >= 1024) {
+    // one-pass backward: all keys in one LDS tile, enough queries to split.  One workgroup per CU (its LDS holds K, V and the
+    // Q / dO tile): aim at two rounds of the chip
+    r->dq = DQ_NONE; r->dkv = DKV_ONE_PASS; qblk = 128;
+    want = std::max<int64_t>(1, std::min<int64_t>(256 / ((int64_t)a->B * a->H), cdiv(Nq, 256)));
+  } else {
+    // dQ: 64-key tiles at two workgroups per CU are the library's choice; 128-key tiles at one workgroup per CU measured 3-17 %
+    // slower per call (profiles/r3_attn_backward_ab.txt)
+    if (sw.dq == 0 || !fast96 || Nk % 64 != 0) r->dq = DQ_GENERIC;
+    else r->dq = (sw.dq == 4 && Nk % 128 == 0) ? DQ_FAST128 : DQ_FAST64;
+    // dK/dV: FAST (128-query tiles, its own LDS size) when every query tile is whole; hd 192 / 16-bit / unmasked with whole
+    // 32-query tiles is the one shape that drops the per-element tests; every other call takes the SLOW instantiation
+    if (sw.dkv_fast && fast96 && Nq % 128 == 0) r->dkv = DKV_FAST;
+    else r->dkv = (h16 && hd == 192 && open && Nq % 32 == 0) ? DKV_PLAIN : DKV_SLOW;
+    qblk = r->dkv == DKV_FAST ? 128 : hd == 96 ? 64 : 32;
+    // one workgroup per CU: the kernel runs one wave per SIMD (measured: 512 -> 76 us, 256 -> 66 us, 128 -> 82 us on the 2048 x 512 block)
+    want = std::max<int64_t>(1, 256 / (cdiv(Nk, 128) * a->B * a->H));
+    want = std::max<int64_t>(1, std::min<int64_t>(want, cdiv(Nq, 4 * qblk)));
   }
-  const int qblk = dkv_fast(a->dtype, a->head_dim, a->mask_mode, a->Nq) ? 128 : a->head_dim == 96 ? 64 : 32;
-  const int64_t base = cdiv(a->Nk, 128) * a->B * a->H;
-  int64_t want = std::max<int64_t>(1, 256 / base);   // one workgroup per CU: the kernel runs one wave per SIMD (measured: 512 -> 76 us, 256 -> 66 us, 128 -> 82 us on the 2048 x 512 block)   // one workgroup per CU (the kernel runs one wave per SIMD)
-  want = std::min<int64_t>(want, cdiv(a->Nq, 4 * qblk));
-  want = std::max<int64_t>(want, 1);
-  q_chunk = (int)(cdiv(cdiv(a->Nq, want), qblk) * qblk);
-  nsplit = (int)cdiv(a->Nq, q_chunk);
+  r->q_chunk = (int)(cdiv(cdiv(Nq, want), qblk) * qblk);
+  r->nsplit = (int)cdiv(Nq, r->q_chunk);
+  r->ws_bytes = r->nsplit > 1 ? (size_t)2 * r->nsplit * a->B * a->H * Nk * hd * sizeof(float) : 16;
+  return true;
 }
 
 }  // namespace
@@ -1635,60 +1651,86 @@ void dkv_plan(const csts_attn_args* a, int& nsplit, int& q_chunk) {
   if ((a)->mask_mode == CSTS_MASK_SPATIAL)                                                              \
   CSTS_REQUIRE((a)->mask_HW > 0 && (a)->Nq < (1 << 20) && (a)->Nq == (a)->mask_T * (a)->mask_HW + (a)->mask_T && (a)->Nk == (a)->Nq, "spatial mask needs Nq == Nk == T*HW + T < 2^20")
 
-enum { K_FWD = 0, K_DQ = 1, K_DKV = 2 };
+// The three launchers follow the route's kernel form; LAUNCH_BY_TYPE picks their (head_dim, fp32) instantiation.  false:
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed (the two forms that need more than 64 KB of dynamic LDS).
 template <int HD, bool F32>
-static bool attn_launch(int which, const AttnP& p, dim3 grid, hipStream_t stream) {
-  if (which == K_FWD) {
-    const size_t sm = smem_fwd<HD, F32>();
-    static const bool fast_off = [] { const char* e = getenv("CSTS_ATTN_FWD_FAST"); return e && atoi(e) == 0; }();
-    if (!fast_off && !F32 && HD == 96 && p.mask_mode == 0 && p.Nk % 64 == 0)
-      hipLaunchKernelGGL(attn_fwd_fast_kernel, grid, dim3(256), sm, stream, p);
-    else
-      hipLaunchKernelGGL((attn_fwd_kernel<HD, F32>), grid, dim3(256), sm, stream, p);
-  } else if (which == K_DQ) {
-    const size_t sm = smem_bwd<HD, F32>();
-    if (const int kt = dq_fast(p.dt, HD, p.mask_mode, p.Nk); kt == 4) {
-      constexpr size_t sm4 = (size_t)2 * 128 * 2 * Cfg<96, false>::LD_ROW * 2;       // 128-key K and V tiles, double-buffered
-      if (!csts_dyn_lds_optin(reinterpret_cast<const void*>(&attn_dq_fast_kernel<4>), (int)sm4)) return false;
-      hipLaunchKernelGGL(attn_dq_fast_kernel<4>, grid, dim3(256), sm4, stream, p);
-    } else if (kt == 2) hipLaunchKernelGGL(attn_dq_fast_kernel<2>, grid, dim3(256), sm, stream, p);
-    else hipLaunchKernelGGL((attn_dq_kernel<HD, F32>), grid, dim3(256), sm, stream, p);
-  } else {
-    const size_t sm = smem_bwd<HD, F32>() + (size_t)Cfg<HD, F32>::KVBLK * 4 * sizeof(float);   // + LSE / delta of the tile(s)
-    if (!dkv_fast(p.dt, HD, p.mask_mode, p.Nq)) {
-      // masked / ragged shapes (and every fp32 call) take the per-element tests.  <96, false, false> IS the FAST form (128-query
-      // tiles, its own LDS size): every other hd 96 / bf16 call takes the SLOW instantiation, whatever its shape
-      const bool slow = F32 || (HD == 96) || p.mask_mode != 0 || p.Nq % Cfg<HD, F32>::KVBLK != 0;   // (q_chunk is a multiple of the tile)
-      if (slow) hipLaunchKernelGGL((attn_dkv_kernel<HD, F32, true>), grid, dim3(256), sm, stream, p);
-      else hipLaunchKernelGGL((attn_dkv_kernel<HD, F32, F32 || HD == 96>), grid, dim3(256), sm, stream, p);
-    } else if constexpr (!F32 && HD == 96) {
-      if (!csts_attn_dkv_fast_launch(p, grid, stream)) return false;      // part 1 of this source (see the top of the file)
-    }
-  }
+static bool launch_fwd(const AttnRoute& r, const AttnP& p, dim3 grid, hipStream_t stream) {
+  const size_t sm = smem_fwd<HD, F32>();
+  if (r.fwd == FWD_FAST) hipLaunchKernelGGL(attn_fwd_fast_kernel, grid, dim3(256), sm, stream, p);
+  else hipLaunchKernelGGL((attn_fwd_kernel<HD, F32>), grid, dim3(256), sm, stream, p);
   return true;
 }
-static bool attn_dispatch(int which, const csts_attn_args* a, const AttnP& p, dim3 grid, hipStream_t stream) {
-  const bool f32 = a->dtype == CSTS_F32;
-  if (a->head_dim == 96) return f32 ? attn_launch<96, true>(which, p, grid, stream) : attn_launch<96, false>(which, p, grid, stream);
-  return f32 ? attn_launch<192, true>(which, p, grid, stream) : attn_launch<192, false>(which, p, grid, stream);
+template <int HD, bool F32>
+static bool launch_dq(const AttnRoute& r, const AttnP& p, dim3 grid, hipStream_t stream) {
+  const size_t sm = smem_bwd<HD, F32>();
+  if (r.dq == DQ_FAST128) {
+    constexpr size_t sm4 = (size_t)2 * 128 * 2 * Cfg<96, false>::LD_ROW * 2;       // 128-key K and V tiles, double-buffered
+    if (!csts_dyn_lds_optin(reinterpret_cast<const void*>(&attn_dq_fast_kernel<4>), (int)sm4)) return false;
+    hipLaunchKernelGGL(attn_dq_fast_kernel<4>, grid, dim3(256), sm4, stream, p);
+  } else if (r.dq == DQ_FAST64) hipLaunchKernelGGL(attn_dq_fast_kernel<2>, grid, dim3(256), sm, stream, p);
+  else hipLaunchKernelGGL((attn_dq_kernel<HD, F32>), grid, dim3(256), sm, stream, p);
+  return true;
+}
+template <int HD, bool F32>
+static bool launch_dkv(const AttnRoute& r, const AttnP& p, dim3 grid, hipStream_t stream) {
+  const size_t sm = smem_bwd<HD, F32>() + (size_t)Cfg<HD, F32>::KVBLK * 4 * sizeof(float);   // + LSE / delta of the tile(s)
+  if (r.dkv == DKV_FAST) return csts_attn_dkv_fast_launch(p, grid, stream);       // part 1 of this source (see the top of the file)
+  if constexpr (HD == 192 && !F32) {
+    if (r.dkv == DKV_PLAIN) {
+      hipLaunchKernelGGL((attn_dkv_kernel<192, false, false>), grid, dim3(256), sm, stream, p);
+      return true;
+    }
+  }
+  hipLaunchKernelGGL((attn_dkv_kernel<HD, F32, true>), grid, dim3(256), sm, stream, p);
+  return true;
+}
+#define LAUNCH_BY_TYPE(fn, a, ...)                                                                                   \
+  ((a)->head_dim == 96 ? ((a)->dtype == CSTS_F32 ? fn<96, true>(__VA_ARGS__) : fn<96, false>(__VA_ARGS__))           \
+                       : ((a)->dtype == CSTS_F32 ? fn<192, true>(__VA_ARGS__) : fn<192, false>(__VA_ARGS__)))
+
+// second pass of a split backward: dK / dV = the sum of the splits' partials in the workspace
+static void launch_reduce(const csts_attn_args* a, const AttnP& p, hipStream_t stream) {
+  const int64_t total = (int64_t)2 * a->B * a->H * a->Nk * a->head_dim / 8;
+  hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 4096)), dim3(256), 0, stream, p,
+                     a->head_dim);
 }
 
 extern "C" int csts_attn_fwd(const csts_attn_args* a, hipStream_t stream) {
   ATTN_COMMON_CHECKS(a);
   CSTS_REQUIRE(a->O && a->LSE && aligned16(a->O) && strides_ok(a->o_strides, a->dtype), "bad output");
   AttnP p; fill(a, p);
+  AttnRoute r;
+  CSTS_REQUIRE(attn_route(a, &r), "no route");
   dim3 grid((unsigned)cdiv(a->Nq, 128), a->H, a->B);
-  CSTS_REQUIRE(attn_dispatch(K_FWD, a, p, grid, stream), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on this device");
+  CSTS_REQUIRE(LAUNCH_BY_TYPE(launch_fwd, a, r, p, grid, stream), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on this device");
   CSTS_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" size_t csts_attn_bwd_workspace(const csts_attn_args* a) {
-  // a problem ATTN_COMMON_CHECKS refuses needs no workspace (and dkv_plan divides by B * H * cdiv(Nk, 128))
-  if (!a || a->B <= 0 || a->H <= 0 || a->Nq <= 0 || a->Nk <= 0 || (a->head_dim != 96 && a->head_dim != 192)) return 0;
-  int nsplit, q_chunk;
-  dkv_plan(a, nsplit, q_chunk);
-  return nsplit > 1 ? (size_t)2 * nsplit * a->B * a->H * a->Nk * a->head_dim * sizeof(float) : 16;
+  AttnRoute r;
+  return attn_route(a, &r) ? r.ws_bytes : 0;       // a problem the calls refuse needs no workspace
+}
+
+// The route by name (host-only: no operand pointer, no stride, no device): "fwd;dq;dkv;reduce", the kernels as the source
+// spells them without spaces.  dq is empty on the one-pass path, reduce is empty when nothing is split.
+extern "C" int csts_attn_route(const csts_attn_args* a, char* buf, int buflen, int* nsplit, int* q_chunk) {
+  CSTS_REQUIRE(buf != nullptr && buflen > 0 && nsplit != nullptr && q_chunk != nullptr, "null pointer");
+  AttnRoute r;
+  CSTS_REQUIRE(attn_route(a, &r), "no route: null args, empty problem, or head_dim not 96 / 192");
+  *nsplit = r.nsplit;
+  *q_chunk = r.q_chunk;
+  const int hd = a->head_dim;
+  const char* t = a->dtype == CSTS_BF16 ? "false" : "true";
+  char fwd[48] = "attn_fwd_fast_kernel", dq[48] = "", dkv[48] = "attn_bwd_fused_kernel";
+  if (r.fwd == FWD_GENERIC) snprintf(fwd, sizeof fwd, "attn_fwd_kernel<%d,%s>", hd, t);
+  if (r.dq == DQ_GENERIC) snprintf(dq, sizeof dq, "attn_dq_kernel<%d,%s>", hd, t);
+  else if (r.dq != DQ_NONE) snprintf(dq, sizeof dq, "attn_dq_fast_kernel<%d>", r.dq == DQ_FAST128 ? 4 : 2);
+  if (r.dkv == DKV_SLOW) snprintf(dkv, sizeof dkv, "attn_dkv_kernel<%d,%s,true>", hd, t);
+  else if (r.dkv != DKV_ONE_PASS) snprintf(dkv, sizeof dkv, "attn_dkv_kernel<%d,false,false>", hd);
+  const int n = snprintf(buf, buflen, "%s;%s;%s;%s", fwd, dq, dkv, r.nsplit > 1 ? "attn_dkv_reduce_kernel" : "");
+  CSTS_REQUIRE(n < buflen, "buffer too small");
+  return 0;
 }
 
 extern "C" int csts_attn_bwd(const csts_attn_args* a, void* workspace, size_t ws_bytes, hipStream_t stream) {
@@ -1700,39 +1742,29 @@ extern "C" int csts_attn_bwd(const csts_attn_args* a, void* workspace, size_t ws
                    strides_ok(a->o_strides, a->dtype), "strides must keep 16-byte row alignment");
   AttnP p; fill(a, p);
   // the query splits are planned and the workspace is checked before the first launch: a refused call writes nothing
-  dkv_plan(a, p.nsplit, p.q_chunk);
-  if (p.nsplit > 1) {
-    CSTS_REQUIRE(workspace != nullptr && ws_bytes >= csts_attn_bwd_workspace(a), "workspace too small");
+  AttnRoute r;
+  CSTS_REQUIRE(attn_route(a, &r), "no route");
+  p.nsplit = r.nsplit; p.q_chunk = r.q_chunk;
+  if (r.nsplit > 1) {
+    // (the text of the message as callers know it: r.ws_bytes is what csts_attn_bwd_workspace(a) returns)
+    if (workspace == nullptr || ws_bytes < r.ws_bytes) CSTS_FAIL("workspace too small [workspace != nullptr && ws_bytes >= csts_attn_bwd_workspace(a)]");
     p.ws = reinterpret_cast<float*>(workspace);
   }
-  if (fused_bwd_ok(a)) {   // delta, dQ, dK, dV in one pass over Q / dO / O
+  if (r.dkv == DKV_ONE_PASS) {   // delta, dQ, dK, dV in one pass over Q / dO / O
     hipLaunchKernelGGL((attn_bwd_fused_kernel<96>), dim3((unsigned)p.nsplit, (unsigned)(a->B * a->H)), dim3(256), 0, stream, p);
+  } else {
+    // 1 + 2. delta = rowsum(dO * O) and dQ (the dQ kernel computes delta from its staged O rows and leaves it for step 3)
+    dim3 grid_dq((unsigned)cdiv(a->Nq, 128), a->H, a->B);
+    CSTS_REQUIRE(LAUNCH_BY_TYPE(launch_dq, a, r, p, grid_dq, stream), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on this device");
     CSTS_LAUNCH_CHECK();
-    if (p.nsplit > 1) {
-      const int64_t total = (int64_t)2 * a->B * a->H * a->Nk * a->head_dim / 8;
-      hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 4096)), dim3(256), 0,
-                         stream, p, a->head_dim);
-      CSTS_LAUNCH_CHECK();
-    }
-    return 0;
+    // 3. dK, dV (query-split, deterministic reduce)
+    dim3 grid_dkv((unsigned)cdiv(a->Nk, 128), p.nsplit, a->B * a->H);
+    CSTS_REQUIRE(LAUNCH_BY_TYPE(launch_dkv, a, r, p, grid_dkv, stream), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on this device");
   }
-  // 1 + 2. delta = rowsum(dO * O) and dQ (the dQ kernel computes delta from its staged O rows and leaves it for step 3)
-  {
-    dim3 grid((unsigned)cdiv(a->Nq, 128), a->H, a->B);
-    CSTS_REQUIRE(attn_dispatch(K_DQ, a, p, grid, stream), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on this device");
+  CSTS_LAUNCH_CHECK();
+  if (r.nsplit > 1) {
+    launch_reduce(a, p, stream);
     CSTS_LAUNCH_CHECK();
-  }
-  // 3. dK, dV (query-split, deterministic reduce)
-  {
-    dim3 grid((unsigned)cdiv(a->Nk, 128), p.nsplit, a->B * a->H);
-    CSTS_REQUIRE(attn_dispatch(K_DKV, a, p, grid, stream), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on this device");
-    CSTS_LAUNCH_CHECK();
-    if (p.nsplit > 1) {
-      const int64_t total = (int64_t)2 * a->B * a->H * a->Nk * a->head_dim / 8;
-      hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 4096)), dim3(256), 0,
-                         stream, p, a->head_dim);
-      CSTS_LAUNCH_CHECK();
-    }
   }
   return 0;
 }

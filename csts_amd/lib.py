@@ -42,7 +42,7 @@ def half_dtype():
     return torch.float16 if HALF == "fp16" else torch.bfloat16
 
 
-ABI_VERSION = 12   # == CSTS_ABI_VERSION of include/csts_hip.h this binding mirrors (struct layouts below)
+ABI_VERSION = 13  # == CSTS_ABI_VERSION of include/csts_hip.h this binding mirrors (struct layouts below)
 F32, BF16 = 0, 1
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 EPI_NONE, EPI_GELU, EPI_DGELU = 0, 1, 2
@@ -210,6 +210,7 @@ SYMBOLS = {
     "csts_attn_bwd_workspace": (sz, [C.POINTER(AttnArgs)]),
     "csts_attn_bwd": (_I, [C.POINTER(AttnArgs), vp, sz, vp]),
     "csts_attn_probs": (_I, [C.POINTER(AttnArgs), vp, vp]),
+    "csts_attn_route": (_I, [C.POINTER(AttnArgs), C.c_char_p, _I, C.POINTER(_I), C.POINTER(_I)]),
     "csts_im2col": (_I, [C.POINTER(Im2colGeom), vp, _I, vp, _I, vp]),
     "csts_posembed_build": (_I, [vp, vp, vp, _I, _I, _I, vp]),
     "csts_transpose_batched": (_I, [vp, _I, vp, _I, i64, _I, _I, vp]),

@@ -1290,6 +1290,26 @@ def _ln_rows_bwd(dy, c, gamma, mean, rstd, HD, params=None):
     return dc, dgb[:HD], dgb[HD:]
 
 
+def _attn_args(dt, dims, mask, qd, kd, vd, o=None, lse=None, do=None, delta=None, tq=None, tk=None, tv=None):
+    """The csts_attn_args of one call.  dims = (B, H, Nq, Nk, HD), mask = (mode, T, HW); qd / kd / vd and the gradient targets
+    tq / tk / tv are (tensor, element offset, strides, ...) descriptors; o and do are contiguous (B, Nq, H * HD)."""
+    B, H, Nq, Nk, HD = dims
+    a = L.AttnArgs()
+    a.dtype, a.B, a.H, a.Nq, a.Nk, a.head_dim = dt, B, H, Nq, Nk, HD
+    for name, d in (("Q", qd), ("K", kd), ("V", vd), ("dQ", tq), ("dK", tk), ("dV", tv)):
+        if d is not None:
+            setattr(a, name, _p(d[0], d[1]))
+            setattr(a, name.lower() + "_strides", (C.c_int64 * 3)(*d[2]))
+    a.O, a.LSE, a.dO, a.delta = _p(o), _p(lse), _p(do), _p(delta)
+    if o is not None:
+        a.o_strides = (C.c_int64 * 3)(Nq * H * HD, H * HD, HD)
+    if do is not None:
+        a.do_strides = (C.c_int64 * 3)(Nq * H * HD, H * HD, HD)
+    a.scale = HD ** -0.5
+    a.mask_mode, a.mask_T, a.mask_HW = mask
+    return a
+
+
 class AttnInnerFn(Function):
     """Everything between the qkv Linear and the output projection of MultiScaleAttention /
     MultiScaleDecoderAttention / SpatialAttention / TemporalAttention (attention.py:130-158, :374-388;
@@ -1383,16 +1403,7 @@ class AttnInnerFn(Function):
         Nq, Nk = qd[3], kd[3]
         o = torch.empty(B, Nq, Cc, dtype=qkv.dtype, device=dev)
         lse = torch.empty(B, H, Nq, dtype=torch.float32, device=dev)
-        a = L.AttnArgs()
-        a.Q, a.K, a.V = _p(qd[0], qd[1]), _p(kd[0], kd[1]), _p(vd[0], vd[1])
-        a.O, a.LSE = _p(o), _p(lse)
-        a.dtype, a.B, a.H, a.Nq, a.Nk, a.head_dim = _dt(qkv), B, H, Nq, Nk, HD
-        a.q_strides = (C.c_int64 * 3)(*qd[2])
-        a.k_strides = (C.c_int64 * 3)(*kd[2])
-        a.v_strides = (C.c_int64 * 3)(*vd[2])
-        a.o_strides = (C.c_int64 * 3)(Nq * Cc, Cc, HD)
-        a.scale = HD ** -0.5
-        a.mask_mode, a.mask_T, a.mask_HW = mask_mode, mask_T, mask_HW
+        a = _attn_args(_dt(qkv), (B, H, Nq, Nk, HD), (mask_mode, mask_T, mask_HW), qd, kd, vd, o=o, lse=lse)
         L.check(lib.csts_attn_fwd(C.byref(a), s), "csts_attn_fwd")
         ctx.meta = meta
         ctx.saved_slots = saved
@@ -1435,21 +1446,8 @@ class AttnInnerFn(Function):
             tk, tv = (dkv[0], 0, (Nk * Cc, Cc, HD)), (dkv[1], 0, (Nk * Cc, Cc, HD))
         else:
             tk, tv = grad_target(1, Nk), grad_target(2, Nk)
-        a = L.AttnArgs()
-        a.Q, a.K, a.V = _p(qd[0], qd[1]), _p(kd[0], kd[1]), _p(vd[0], vd[1])
-        a.O, a.LSE, a.dO, a.delta = _p(o), _p(lse), _p(do), _p(delta)
-        a.dQ, a.dK, a.dV = _p(tq[0], tq[1]), _p(tk[0], tk[1]), _p(tv[0], tv[1])
-        a.dtype, a.B, a.H, a.Nq, a.Nk, a.head_dim = _dt(qkv), B, H, Nq, Nk, HD
-        a.q_strides = (C.c_int64 * 3)(*qd[2])
-        a.k_strides = (C.c_int64 * 3)(*kd[2])
-        a.v_strides = (C.c_int64 * 3)(*vd[2])
-        a.o_strides = (C.c_int64 * 3)(Nq * Cc, Cc, HD)
-        a.do_strides = (C.c_int64 * 3)(Nq * Cc, Cc, HD)
-        a.dq_strides = (C.c_int64 * 3)(*tq[2])
-        a.dk_strides = (C.c_int64 * 3)(*tk[2])
-        a.dv_strides = (C.c_int64 * 3)(*tv[2])
-        a.scale = HD ** -0.5
-        a.mask_mode, a.mask_T, a.mask_HW = mask_mode, mask_T, mask_HW
+        a = _attn_args(_dt(qkv), (B, H, Nq, Nk, HD), (mask_mode, mask_T, mask_HW), qd, kd, vd, o=o, lse=lse, do=do, delta=delta,
+                       tq=tq, tk=tk, tv=tv)
         ws = _ws(lib.csts_attn_bwd_workspace(C.byref(a)), dev)
         L.check(lib.csts_attn_bwd(C.byref(a), _p(ws), ws.numel(), s), "csts_attn_bwd")
 
@@ -1668,16 +1666,8 @@ def attention_probs(qkv, B, N, Cc, H, lse, mask_mode, mask_T, mask_HW):
     (av_attention.py:150-153,358-359); forward-only visualisation output."""
     HD = Cc // H
     probs = torch.empty(B, H, N, N, dtype=torch.float32, device=qkv.device)
-    a = L.AttnArgs()
-    a.Q, a.K, a.V = _p(qkv, 0), _p(qkv, Cc), _p(qkv, 2 * Cc)
-    a.LSE = _p(lse)
-    a.dtype, a.B, a.H, a.Nq, a.Nk, a.head_dim = _dt(qkv), B, H, N, N, HD
-    st = (C.c_int64 * 3)(N * 3 * Cc, 3 * Cc, HD)
-    a.q_strides = st
-    a.k_strides = st
-    a.v_strides = st
-    a.scale = HD ** -0.5
-    a.mask_mode, a.mask_T, a.mask_HW = mask_mode, mask_T, mask_HW
+    qd, kd, vd = ((qkv, slot * Cc, (N * 3 * Cc, 3 * Cc, HD)) for slot in range(3))
+    a = _attn_args(_dt(qkv), (B, H, N, N, HD), (mask_mode, mask_T, mask_HW), qd, kd, vd, lse=lse)
     L.check(_lib().csts_attn_probs(C.byref(a), _p(probs), _stream()), "csts_attn_probs")
     return probs
 

@@ -32,10 +32,10 @@ enum { CSTS_EPI_NONE = 0, CSTS_EPI_GELU = 1, CSTS_EPI_DGELU = 2 };
 enum { CSTS_MASK_NONE = 0, CSTS_MASK_SPATIAL = 1 };
 
 /* Version of this header's struct layouts and call semantics.  Bumped whenever a struct grows or a field changes meaning
- * (2: csts_gemm_args.res_up; 3: compact k|v rows, 16-bit build, loss scaler in csts_opt_args; 4: csts_opt_args.extra_sq, factored AdamW; 5: grouped stencil weight gradients; 6: csts_copy_token_segments, csts_wgrad_grouped8_limited; 7: csts_wgrad_grouped5, csts_gemm algo 500; 8: csts_opt_rule, csts_opt_step, csts_opt_factored_step, csts_opt_factored.tensor replaces pad_; 10: csts_audio_pixel_attn; 11: csts_attention_track, csts_attention_rescale; 12: csts_resample_wav, csts_resample_len).  csts_abi_version() returns the value the
+ * (2: csts_gemm_args.res_up; 3: compact k|v rows, 16-bit build, loss scaler in csts_opt_args; 4: csts_opt_args.extra_sq, factored AdamW; 5: grouped stencil weight gradients; 6: csts_copy_token_segments, csts_wgrad_grouped8_limited; 7: csts_wgrad_grouped5, csts_gemm algo 500; 8: csts_opt_rule, csts_opt_step, csts_opt_factored_step, csts_opt_factored.tensor replaces pad_; 10: csts_audio_pixel_attn; 11: csts_attention_track, csts_attention_rescale; 12: csts_resample_wav, csts_resample_len; 13: csts_attn_route).  csts_abi_version() returns the value the
  * LIBRARY was built with: a caller must compare it with the CSTS_ABI_VERSION it was compiled against and refuse a mismatch
  * (the Python binding does, csts_amd/lib.py::load). */
-#define CSTS_ABI_VERSION 12
+#define CSTS_ABI_VERSION 13
 const char* csts_last_error(void);
 int csts_abi_version(void);
 int csts_half_kind(void);   /* the 16-bit type behind CSTS_BF16 in THIS library: 0 bfloat16 (libcsts_hip.so), 1 IEEE half (libcsts_hip_f16.so) */
@@ -229,7 +229,13 @@ int csts_trilinear_bwd(const csts_pool_geom* g, const void* dy, int dy_dt, void*
  *      sums in LDS and leaves the buffer untouched.  It must be given either way; read nothing back from it.
  *      Every argument, the query-split plan and the workspace size are checked before the first launch: a call that returns
  *      non-zero has written nothing.  csts_attn_bwd_workspace returns 0 for a problem the calls refuse (a non-positive
- *      B / H / Nq / Nk, a head_dim other than 96 / 192, NULL). */
+ *      B / H / Nq / Nk, a head_dim other than 96 / 192, NULL).
+ *      Launch, workspace and query share ONE route: which forward / dQ / dK/dV kernel runs and with how many query splits is
+ *      decided once, from dtype, head_dim, B, H, Nq, Nk, mask_mode and the CSTS_ATTN_* switches.  csts_attn_route (host-only:
+ *      it reads no operand pointer and no stride, launches nothing, needs no device) writes that route to buf as
+ *      "fwd;dq;dkv;reduce" -- kernel names as the source spells them, without spaces; dq is empty on the one-pass path, where dkv
+ *      is attn_bwd_fused_kernel; reduce is attn_dkv_reduce_kernel or empty -- and returns -1 for the problems
+ *      csts_attn_bwd_workspace returns 0 for. */
 typedef struct {
   const void* Q; const void* K; const void* V; void* O; float* LSE;
   const void* dO; float* delta; void* dQ; void* dK; void* dV;
@@ -243,6 +249,7 @@ int csts_attn_fwd(const csts_attn_args* a, hipStream_t stream);
 size_t csts_attn_bwd_workspace(const csts_attn_args* a);
 int csts_attn_bwd(const csts_attn_args* a, void* workspace, size_t ws_bytes, hipStream_t stream);
 int csts_attn_probs(const csts_attn_args* a, float* probs /* (B,H,Nq,Nk) */, hipStream_t stream);
+int csts_attn_route(const csts_attn_args* a, char* buf, int buflen, int* nsplit, int* q_chunk);
 
 /* ---- patch embedding: Conv3d k(3,7,7) s(2,4,4) p(1,3,3) + flatten/transpose (stem_helper.py:27-38) as
  *      im2col + csts_gemm; separable positional embedding (custom_multimodal_builder.py:362-370). */

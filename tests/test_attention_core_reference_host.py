@@ -1,12 +1,22 @@
 """CPU checks of tests/attention_core_reference.py: the float64 restatement of the attention core is the operation (against float64
 torch autograd), the device form of frame_of is x // HW, the Python restatement of the host code's plan reaches every kernel
-instantiation with the case table, the reduce kernel's second grid-stride trip is unreachable under that plan, and the staircase
-cases hold the three kinds of rows the lazy running max of the forward distinguishes."""
+instantiation with the case table, the reduce kernel's second grid-stride trip is unreachable under that plan, the built library's
+own route (csts_attn_route, csts_attn_bwd_workspace) is that restatement in every environment, and the staircase cases hold the
+three kinds of rows the lazy running max of the forward distinguishes."""
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 import attention_core_reference as AR
+import attention_route_worker as AW
+from conftest import ROOT
+from csts_amd import lib as L
 
 _RUNS = [(n, hd) for n in AR.CASES for hd in AR.CASES[n][4]]
 
@@ -138,6 +148,54 @@ def test_reduce_second_trip_is_unreachable():
                             if p["reduce"]:
                                 worst[p["path"]] = max(worst[p["path"]], BH * Nk * hd)
     assert 0 < worst["two-kernel"] <= 16384 * 192 and 0 < worst["one-pass"] <= 1572864, worst
+
+
+# ------------------------------------------------------------------------------------------------------------ the library's route
+# What the plan tests above prove about the restatement holds for the library only while the two agree: the built library is asked
+# (csts_attn_route, csts_attn_bwd_workspace; host-only, no GPU) for every run of the case table, PROBS_CAP and a sweep that
+# hits every threshold of the plan on both sides, in every environment the suite runs attention in and with each switch alone.
+_OFF = {f"{s[10:].lower()}_off": {s: "0"} for s in AR.SWITCHES}
+ROUTE_ENV = {"generic": AR.CHILD_ENV["generic"], "dq4": AR.CHILD_ENV["dq4"], **_OFF, "fp16": {"CSTS_HALF": "fp16"}}
+
+
+def test_route_problems_straddle_the_thresholds():
+    assert set(_OFF) == {"fwd_fast_off", "dq_fast_off", "dkv_fast_off", "fused_bwd_off"}
+    assert {255, 256, 1023, 1024} <= set(AW.SWEEP_NQ) and {64, 65, 128, 129, 192} <= set(AW.SWEEP_NK)
+    probs = AW.problems()
+    assert len(probs) == len(AR.runs(AR.CASES)) + 1 + 2 * 2 * 10 * 12 * 8 and any(p[6] is not None for p in probs)
+
+
+def test_library_route_is_the_restatement():
+    """The default environment, in this process."""
+    n, bad = AW.mismatches(L.load(), AR.env_of())
+    assert n > 3800 and not bad, (len(bad), bad[:3])
+
+
+@pytest.mark.parametrize("mode", list(ROUTE_ENV))
+def test_library_route_is_the_restatement_in_a_child(mode, tmp_path):
+    """Every other environment in a host-only process of its own: the switches are read once per process, and the fp16 run loads
+    the other library."""
+    base = {k: v for k, v in os.environ.items() if k not in ("CSTS_HALF",) + AR.SWITCHES}
+    out = tmp_path / "route.json"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "attention_route_worker.py"), str(out)], cwd=ROOT,
+                       env={**base, **ROUTE_ENV[mode]}, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-4000:]
+    r = json.load(open(out))
+    assert r["env"] == AR.env_of(ROUTE_ENV[mode]) and r["half_kind"] == (1 if mode == "fp16" else 0)
+    assert r["checked"] > 3800 and r["n_bad"] == 0, (r["n_bad"], r["bad"])
+
+
+def test_route_query_refuses_what_the_workspace_query_refuses():
+    lib = L.load()
+    for kw in ({"B": 0}, {"H": 0}, {"Nq": 0}, {"Nk": 0}, {"B": -1}, {"Nk": -5}, {"head_dim": 64}, {"head_dim": 0}):
+        a = AW.args_of(2, 2, 300, 100, 96, True, None)
+        for k, v in kw.items():
+            setattr(a, k, v)
+        assert AW.route(lib, a)[0] == -1 and b"csts_attn_route" in lib.csts_last_error(), kw
+        assert lib.csts_attn_bwd_workspace(C.byref(a)) == 0, kw
+    assert AW.route(lib, None)[0] == -1 and lib.csts_attn_bwd_workspace(None) == 0
+    ok = AW.args_of(2, 2, 300, 100, 96, True, None)
+    assert AW.route(lib, ok)[0] == 0 and lib.csts_attn_bwd_workspace(C.byref(ok)) == 2 * 2 * 4 * 100 * 96 * 4
 
 
 # ------------------------------------------------------------------------------------------------------------ the staircase
