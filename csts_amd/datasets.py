@@ -7,7 +7,10 @@ Layout under CSTS_AMD.DATA_ROOT (decoding is out of scope; tools/make_toy_datase
   clips/<video>/<clip>.npz                    frames_u8 uint8 (N, H, W, 3), wav fp32 (n,) at 24 kHz [, fps]: what
                                               tools/predict.py --video reads.  [sample_rate]: the rate wav was recorded at;
                                               wav, floating or int16, (n,) or (C, n), is then brought to 24 kHz mono on the
-                                              device (inputs.resample_audio) before the spectrogram
+                                              device (inputs.resample_audio) before the spectrogram.  Instead of frames_u8 a
+                                              clip may hold frames_yuv uint8 (N, H * 3 / 2, W) with pixel_format "nv12" | "i420"
+                                              [, yuv_matrix "bt601" | "bt709", yuv_full_range]: 4:2:0 pictures, kept and sampled
+                                              in that format (half the bytes); a split is uniform in format, matrix and range
   gaze_frame_label/<video>_frame_label.csv    a header row, then one row per video frame; Ego4D keeps columns [1:] = x, y, type
                                               (ego4d_avgaze_forecast.py:121-122), Aria columns [2:] (aria_avgaze_forecast.py:115)
 A clip's first label row is start * DATA.TARGET_FPS.
@@ -154,6 +157,46 @@ def plan_epoch(n_clips: int, batch: int, world: int, rank: int, seed: int, epoch
     return groups
 
 
+def clip_pictures(z, path: str, pixel_format=None, matrix=None, full_range=None, lead: int = 1):
+    """The pictures of one clip npz (an open numpy.load, or a dict of arrays) -> (frames, H, W, (pixel_format, matrix,
+    full_range)): frames_u8 uint8 (N, H, W, 3) as ("rgb24", "bt601", False), or frames_yuv uint8 (N, H * 3 / 2, W) with the entry
+    pixel_format "nv12" | "i420" and the optional entries yuv_matrix (default "bt601") and yuv_full_range (default False).  The
+    three arguments override the entries.  lead: the leading dimensions in front of a picture (1: (N, ...), 2: (B, T, ...)).
+    ValueError for an npz holding both kinds or neither, or a bad entry."""
+    dims = "(N" if lead == 1 else "(B, T"
+    names = z.files if hasattr(z, "files") else list(z)
+    if "frames_u8" in names and "frames_yuv" in names:
+        raise ValueError(f"{path} holds both frames_u8 and frames_yuv: a clip holds its pictures once, in one format")
+    if "frames_yuv" not in names:
+        if "frames_u8" not in names:
+            raise ValueError(f"{path} lacks frames_u8 (or frames_yuv with pixel_format): a clip holds its pictures")
+        if pixel_format not in (None, "rgb24"):
+            raise ValueError(f"{path} holds frames_u8, packed RGB: pixel format {pixel_format!r} needs frames_yuv")
+        frames = z["frames_u8"]
+        if frames.dtype != np.uint8 or frames.ndim != lead + 3 or frames.shape[-1] != 3:
+            raise ValueError(f"{path}: frames_u8 must be uint8 {dims}, H, W, 3), got {frames.shape} {frames.dtype}")
+        return frames, int(frames.shape[-3]), int(frames.shape[-2]), ("rgb24", "bt601", False)
+    if pixel_format is None:
+        if "pixel_format" not in names:
+            raise ValueError(f"{path} holds frames_yuv without a pixel_format entry (\"nv12\" or \"i420\")")
+        pixel_format = str(np.asarray(z["pixel_format"]).reshape(-1)[0])
+    if matrix is None:
+        matrix = str(np.asarray(z["yuv_matrix"]).reshape(-1)[0]) if "yuv_matrix" in names else "bt601"
+    if full_range is None:
+        full_range = bool(np.asarray(z["yuv_full_range"]).reshape(-1)[0]) if "yuv_full_range" in names else False
+    if pixel_format == "rgb24":
+        raise ValueError(f"{path}: frames_yuv holds 4:2:0 pictures, pixel_format must be \"nv12\" or \"i420\"")
+    inputs.check_pixel_format(pixel_format, matrix, full_range)
+    frames = z["frames_yuv"]
+    if frames.dtype != np.uint8 or frames.ndim != lead + 2:
+        raise ValueError(f"{path}: frames_yuv must be uint8 {dims}, H * 3 / 2, W), got {frames.shape} {frames.dtype}")
+    try:
+        H, W = inputs._yuv_hw(frames.shape, pixel_format, "frames_yuv")
+    except ValueError as e:
+        raise ValueError(f"{path}: {e}")
+    return frames, H, W, (pixel_format, matrix, bool(full_range))
+
+
 def _align(n: int, a: int) -> int:
     return (n + a - 1) // a * a
 
@@ -161,7 +204,7 @@ def _align(n: int, a: int) -> int:
 class ClipStore:
     """One split of a data set, read once: the observed frames, one spectrogram and the label rows of every listed clip.
 
-    Host side: per clip the uint8 frames (observed part), the fp32 spectrogram (nbins, cols), and the tables n_frames, H, W,
+    Host side: per clip the uint8 frames (observed part; packed RGB, or 4:2:0 as the split's pixel_format says), the fp32 spectrogram (nbins, cols), and the tables n_frames, H, W,
     cols, usable, first label row (in the label arena) and label rows of its video.  Device side: the label arena fp64 (rows, L)
     (always resident) and, after upload(ids), the frame arena (uint8, recordings back to back at any byte) and the spectrogram
     arena (fp32) of those clips with their tables {byte offset, N, H, W} and {float offset, row stride, usable columns}."""
@@ -197,19 +240,30 @@ class ClipStore:
         self.n_frames, self.hw = np.zeros(n, np.int64), np.zeros((n, 2), np.int64)
         self.cols, self.usable = np.zeros(n, np.int64), np.zeros(n, np.int64)
         self.label_first, self.label_end = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        self.pixel_format, self.yuv_matrix, self.yuv_full_range = "rgb24", "bt601", False      # the first clip's, below
         for i, (video, name, t0, _) in enumerate(self.clips):
             path = os.path.join(root, "clips", video, name + ".npz")
             if not os.path.exists(path):
                 raise FileNotFoundError(f"{path} not found: clip {video}/{name} is listed in the {split} split")
             with np.load(path) as z:
-                missing = [k for k in ("frames_u8", "wav") if k not in z.files]
+                missing = [k for k in ("frames_u8", "wav") if k not in z.files and (k == "wav" or "frames_yuv" not in z.files)]
                 if missing:
-                    raise ValueError(f"{path} lacks {missing}: a clip holds frames_u8, wav and optionally fps")
-                frames, wav = z["frames_u8"], z["wav"]
+                    raise ValueError(f"{path} lacks {missing}: a clip holds frames_u8 (or frames_yuv with pixel_format), wav and "
+                                     "optionally fps")
+                frames, H, W, fmt = clip_pictures(z, path)
+                wav = z["wav"]
                 rate = np.asarray(z["sample_rate"]).reshape(-1) if "sample_rate" in z.files else None
-            if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[-1] != 3 or frames.shape[0] <= self.observed:
-                raise ValueError(f"{path}: frames_u8 must be uint8 (N > {self.observed}, H, W, 3), got {frames.shape} {frames.dtype}")
-            self.n_frames[i], self.hw[i] = frames.shape[0], frames.shape[1:3]
+            if frames.shape[0] <= self.observed:
+                what = "frames_u8 must be uint8 (N" if fmt[0] == "rgb24" else f"frames_yuv ({fmt[0]}) must be uint8 (N"
+                tail = "H, W, 3)" if fmt[0] == "rgb24" else "H * 3 / 2, W)"
+                raise ValueError(f"{path}: {what} > {self.observed}, {tail}, got {frames.shape} {frames.dtype}")
+            if i == 0:
+                self.pixel_format, self.yuv_matrix, self.yuv_full_range = fmt
+            elif fmt != (self.pixel_format, self.yuv_matrix, self.yuv_full_range):
+                raise ValueError(f"{path}: clip {video}/{name} holds {fmt[0]} pictures (matrix {fmt[1]}, full range {fmt[2]}), the "
+                                 f"split {self.pixel_format} (matrix {self.yuv_matrix}, full range {self.yuv_full_range}): a split is "
+                                 "uniform in pixel format, matrix and range")
+            self.n_frames[i], self.hw[i] = frames.shape[0], (H, W)
             self.frames_host.append(np.ascontiguousarray(frames[:self.observed]))
             if rate is None:
                 wav = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)).reshape(1, -1).to(self.device)
@@ -239,6 +293,12 @@ class ClipStore:
 
     def __len__(self):
         return len(self.clips)
+
+    def format_args(self):
+        """The keywords that tell inputs.batch_sample the split's pixel format: {} for packed RGB."""
+        if self.pixel_format == "rgb24":
+            return {}
+        return dict(pixel_format=self.pixel_format, matrix=self.yuv_matrix, full_range=self.yuv_full_range)
 
     def budget_bytes(self):
         """CSTS_AMD.DATA_RESIDENT_GB in bytes, or None when 0: the whole split is resident."""
@@ -274,7 +334,7 @@ class ClipStore:
             f, s = self.frames_host[i], self.spec_host[i]
             hv[off:off + f.nbytes] = f.reshape(-1)
             sv[soff:soff + s.size] = s.reshape(-1)
-            self.clips_host[i] = (off, f.shape[0], f.shape[1], f.shape[2])
+            self.clips_host[i] = (off, f.shape[0], self.hw[i, 0], self.hw[i, 1])
             self.specs_host[i] = (soff, s.shape[1], self.usable[i])
             self.slot[i] = k
             off += f.nbytes
@@ -391,7 +451,7 @@ class ClipLoader:
         labels = st.labels[rows]                                              # (B, T, L) fp64
         params, new_labels = inputs.batch_params(labels, clips, S, key=key, clips_host=tab_host[:, 0:4], **self.spatial_args())
         video = inputs.batch_sample(st.arena, clips, frames_idx, params, S, tab_host[:, 0:4], mean=tuple(cfg.DATA.MEAN),
-                                    std=tuple(cfg.DATA.STD))
+                                    std=tuple(cfg.DATA.STD), **st.format_args())
         audio = inputs.audio_gather(st.spec_arena, specs, centers, st.nbins, tab_host[:, 4:7], AUDIO_WIDTH)
         if S != AUDIO_WIDTH or st.nbins != S:      # S frequency bins x S columns around each frame, as train.synthetic_batch cuts them
             o = (AUDIO_WIDTH - S) // 2

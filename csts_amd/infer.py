@@ -308,6 +308,36 @@ class GraphedEvalStep:
         return self.out
 
 
+def _picture_hw(frames, lead, pixel_format, matrix, full_range):
+    """H, W and the format keywords of a picture argument with `lead` leading dimensions: packed RGB uint8 (..., H, W, 3) -> (H,
+    W, {}), or with pixel_format "nv12" | "i420" 4:2:0 uint8 (..., H * 3 / 2, W) -> (H, W, the three keywords to pass on).
+    ValueError for an unknown format or matrix, a shape of the other kind, odd H or W."""
+    from . import inputs
+    names = "(B, T" if lead == 2 else "(N"
+    if inputs.check_pixel_format(pixel_format, matrix, full_range)[0] == 0:
+        if frames.dtype != torch.uint8 or frames.dim() != lead + 3 or frames.shape[-1] != 3:
+            raise ValueError(f"frames must be uint8 {names}, H, W, 3), got {tuple(frames.shape)} {frames.dtype}")
+        return int(frames.shape[-3]), int(frames.shape[-2]), {}
+    if frames.dtype != torch.uint8 or frames.dim() != lead + 2:
+        raise ValueError(f"{pixel_format} frames must be uint8 {names}, H * 3 / 2, W), got {tuple(frames.shape)} {frames.dtype}")
+    H, W = inputs._yuv_hw(frames.shape, pixel_format)
+    return H, W, {"pixel_format": pixel_format, "matrix": matrix, "full_range": bool(full_range)}
+
+
+def _render_out(frames, out, H, W, fmt):
+    """The uint8 (..., H, W, 3) tensor a renderer of 4:2:0 frames draws into: a fresh one unless `out` is given, and `out` must not
+    share memory with the input (the RGB pictures are converted into it, then drawn over in place)."""
+    shape = tuple(frames.shape[:-2]) + (H, W, 3)
+    if out is not None and (not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != torch.uint8 or
+                            not out.is_contiguous() or not out.is_cuda):
+        raise ValueError(f"out must be a contiguous uint8 {shape} GPU tensor")
+    if out is not None:
+        a, b = frames.data_ptr(), out.data_ptr()
+        if a < b + out.numel() and b < a + frames.numel() * frames.element_size():
+            raise ValueError(f"out must not share memory with {fmt['pixel_format']} frames: the overlay is RGB, (N, H, W, 3)")
+    return torch.empty(shape, dtype=torch.uint8, device=frames.device) if out is None else out
+
+
 def _check_rate(sample_rate):
     from .inputs import check_sample_rate
     return check_sample_rate(sample_rate)
@@ -357,7 +387,8 @@ class GazePredictor:
         self._steps = {}           # (B, T, S) or (B, T, S, "attention") -> GraphedEvalStep
 
     @torch.no_grad()
-    def predict(self, frames_u8, wav, frames_idx, frame_length, labels=None, attention=False, sample_rate=None):
+    def predict(self, frames_u8, wav, frames_idx, frame_length, labels=None, attention=False, sample_rate=None, *,
+                pixel_format="rgb24", matrix="bt601", full_range=False):
         """frames_u8 uint8 (B, T, H, W, 3), wav fp32 (B, n) at 24 kHz, frames_idx (B, T) = the sampled frames' positions on the
         clip's time axis of `frame_length` frames -> {"points": (B, T, 2) (x, y) in [0, 1), "peak": (B, T),
         "heatmaps": (B, T, S/4, S/4), "rescaled": same shape} on the device, S = DATA.TEST_CROP_SIZE.
@@ -366,16 +397,17 @@ class GazePredictor:
         coordinates.  labels (optional, (B, T, L >= 2) gaze labels): carried through the same crop and returned as "labels".
         attention=True adds the fusion attention maps of predict_batch; the other entries keep their bits.
         sample_rate: None (wav is at 24 kHz: today's path, no extra launch), or the rate wav was recorded at: wav, floating or
-        int16, (B, n) or (B, C, n), is first brought to 24 kHz mono on the device (inputs.resample_audio)."""
+        int16, (B, n) or (B, C, n), is first brought to 24 kHz mono on the device (inputs.resample_audio).
+        pixel_format "nv12" | "i420" (with matrix "bt601" | "bt709", full_range): frames_u8 is uint8 (B, T, H * 3 / 2, W), 4:2:0
+        pictures sampled in place (inputs.spatial_sample); the result is that of the converted RGB frames, bit for bit."""
         if sample_rate is not None:
             sample_rate = _check_rate(sample_rate)
         for t in (frames_u8, wav, frames_idx) + ((labels,) if labels is not None else ()):
             if not torch.is_tensor(t) or not t.is_cuda:
                 raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
         from . import inputs
-        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 5 or frames_u8.shape[-1] != 3:
-            raise ValueError(f"frames must be uint8 (B, T, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
-        B, T, H, W, _ = frames_u8.shape
+        H, W, fmt = _picture_hw(frames_u8, 2, pixel_format, matrix, full_range)
+        B, T = frames_u8.shape[:2]
         if sample_rate is not None:
             if wav.dim() not in (2, 3) or wav.shape[0] != B:
                 raise ValueError(f"with a sample rate wav must be ({B}, n) or ({B}, C, n), got {tuple(wav.shape)}")
@@ -390,7 +422,11 @@ class GazePredictor:
             new_labels = labels
             if (H, W) != (S, S):
                 lab = labels if labels is not None else torch.zeros(B, T, 2, dtype=torch.float64, device=frames_u8.device)
-                video, new_labels = inputs.spatial_sampling(frames_u8, lab, S, train=False, spatial_idx=1, mean=mean, std=std)
+                video, new_labels = inputs.spatial_sampling(frames_u8, lab, S, train=False, spatial_idx=1, mean=mean, std=std,
+                                                            **fmt)
+            elif fmt:          # the identity crop of the sampling pass equals normalize_frames of the converted frames bit for bit
+                ident = torch.tensor([[S, S, 0, 0, 0]], dtype=torch.int32, device=frames_u8.device).repeat(B, 1)
+                video = inputs.spatial_sample(frames_u8, ident, S, mean=mean, std=std, **fmt)
             else:
                 video = inputs.normalize_frames(frames_u8, mean=mean, std=std)
             audio = inputs.audio_windows(inputs.stft_logpower(wav), frames_idx, frame_length)
@@ -448,20 +484,23 @@ class GazePredictor:
         return inputs.spatial_rule_host(np.zeros((1, T, 2)), H, W, S, train=False, spatial_idx=1)[0][0].tolist()
 
     @torch.no_grad()
-    def render_track(self, frames_u8, track, alpha=0.4, radius=5, out=None, chunk=None):
+    def render_track(self, frames_u8, track, alpha=0.4, radius=5, out=None, chunk=None, *, pixel_format="rgb24", matrix="bt601",
+                     full_range=False):
         """The track of predict_video drawn onto its recording: frames_u8 uint8 (N, H, W, 3) on the device and the dict
         predict_video returned (it must hold "rescaled" and "points") -> uint8 (N, H, W, 3): the heat map of every predicted
         frame blended over the crop the model saw and a disc at the gaze point (ops.gaze_overlay, csts_gaze_overlay); frames no
         window predicts (NaN points) come back as they are.  The crop is the one predict_video sampled: identity for S x S
         sources, else short side to S and centre crop.  chunk: frames per kernel launch (default: all).  out=frames_u8 renders
-        in place."""
+        in place.  pixel_format "nv12" | "i420": frames_u8 is the 4:2:0 recording uint8 (N, H * 3 / 2, W); each chunk is converted
+        into `out` (inputs.yuv_to_rgb) and drawn over there, so the result is RGB as above and out must not alias the input."""
         if not torch.is_tensor(frames_u8) or not frames_u8.is_cuda:
             raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
         if "rescaled" not in track or "points" not in track:
             raise ValueError("render_track needs the track's \"rescaled\" and \"points\": call predict_video with return_heatmaps=True")
-        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
-            raise ValueError(f"frames must be uint8 (N, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
-        N, H, W, _ = frames_u8.shape
+        H, W, fmt = _picture_hw(frames_u8, 1, pixel_format, matrix, full_range)
+        N = frames_u8.shape[0]
+        if fmt:
+            out = _render_out(frames_u8, out, H, W, fmt)
         if track["rescaled"].shape[0] != N or tuple(track["points"].shape) != (N, 2):
             raise ValueError(f"the track holds {track['rescaled'].shape[0]} frames, the recording {N}")
         step = N if chunk is None else int(chunk)
@@ -474,29 +513,32 @@ class GazePredictor:
             centers = marker_centers(points_to_source(track["points"], row, S), H, W)
             if out is None:
                 out = torch.empty_like(frames_u8)
+            from . import inputs
             for a in range(0, N, step):
                 sel = slice(a, min(a + step, N))
-                ops.gaze_overlay(frames_u8[sel], track["rescaled"][sel], params, S, centers=centers[sel], alpha=alpha,
+                src = inputs.yuv_to_rgb(frames_u8[sel], out=out[sel], **fmt) if fmt else frames_u8[sel]
+                ops.gaze_overlay(src, track["rescaled"][sel], params, S, centers=centers[sel], alpha=alpha,
                                  radius=radius, out=out[sel])
         return out
 
     @torch.no_grad()
-    def render_attention(self, frames_u8, result, head=None, alpha=0.4, radius=5, points=None, out=None):
+    def render_attention(self, frames_u8, result, head=None, alpha=0.4, radius=5, points=None, out=None, *, pixel_format="rgb24",
+                         matrix="bt601", full_range=False):
         """The fusion attention maps of predict(attention=True) drawn onto the clip: frames_u8 uint8 (B, T, H, W, 3) on the device
         (the frames that were predicted) and the result dict (it must hold "attention_maps") -> uint8 (B, T, H, W, 3): the map
         of `head` (None: the head mean) of every input frame blended over the crop the model saw -- one ops.gaze_overlay call
         over the B * T frames.  The crop is predict()'s: identity for S x S frames, else short side to S and centre crop.
         points (optional, (B, T, 2) on the crop, e.g. result["points"]): a disc of `radius` pixels at each (NaN: that frame comes
-        back untouched).  out=frames_u8 renders in place."""
+        back untouched).  out=frames_u8 renders in place.  pixel_format "nv12" | "i420": frames_u8 is uint8 (B, T, H * 3 / 2, W); the
+        frames are converted into `out` (inputs.yuv_to_rgb) and drawn over there: out must not alias the input."""
         if not torch.is_tensor(frames_u8) or not frames_u8.is_cuda:
             raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
         if "attention_maps" not in result:
             raise ValueError("render_attention needs the result's \"attention_maps\": call predict with attention=True")
-        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 5 or frames_u8.shape[-1] != 3:
-            raise ValueError(f"frames must be uint8 (B, T, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
+        H, W, fmt = _picture_hw(frames_u8, 2, pixel_format, matrix, full_range)
         if not frames_u8.is_contiguous():
-            raise ValueError("frames must be contiguous (B, T, H, W, 3)")
-        B, T, H, W, _ = frames_u8.shape
+            raise ValueError("frames must be contiguous")
+        B, T = frames_u8.shape[:2]
         maps = result["attention_maps"]
         if maps.dim() != 5 or maps.shape[0] != B or maps.shape[2] != T:
             raise ValueError(f"attention_maps {tuple(maps.shape)} do not belong to {B} clips of {T} frames")
@@ -504,7 +546,9 @@ class GazePredictor:
         g = nheads if head is None else int(head)
         if head is not None and not 0 <= g < nheads:
             raise ValueError(f"head must be None (the head mean) or lie in [0, {nheads}), got {head!r}")
-        if out is not None and (out.shape != frames_u8.shape or out.dtype != torch.uint8 or not out.is_contiguous()):
+        if fmt:
+            out = _render_out(frames_u8, out, H, W, fmt)
+        elif out is not None and (out.shape != frames_u8.shape or out.dtype != torch.uint8 or not out.is_contiguous()):
             raise ValueError(f"out must be contiguous uint8 {tuple(frames_u8.shape)}, got {tuple(out.shape)} {out.dtype}")
         S = int(self.cfg.DATA.TEST_CROP_SIZE)
         with torch.cuda.device(self.device):
@@ -517,27 +561,35 @@ class GazePredictor:
                 centers = marker_centers(points_to_source(points.reshape(B * T, 2), row, S), H, W)
             if out is None:
                 out = torch.empty_like(frames_u8)
-            ops.gaze_overlay(frames_u8.view(B * T, H, W, 3), maps[:, g].reshape(B * T, maps.shape[3], maps.shape[4]), params, S,
+            if fmt:
+                from . import inputs
+                src = inputs.yuv_to_rgb(frames_u8, out=out, **fmt)
+            else:
+                src = frames_u8
+            ops.gaze_overlay(src.view(B * T, H, W, 3), maps[:, g].reshape(B * T, maps.shape[3], maps.shape[4]), params, S,
                              centers=centers, alpha=alpha, radius=radius, out=out.view(B * T, H, W, 3))
         return out
 
     @torch.no_grad()
-    def render_attention_track(self, frames_u8, track, head=None, alpha=0.4, radius=5, points=None, out=None, chunk=None):
+    def render_attention_track(self, frames_u8, track, head=None, alpha=0.4, radius=5, points=None, out=None, chunk=None, *,
+                               pixel_format="rgb24", matrix="bt601", full_range=False):
         """The attention track of predict_video(attention_track=True) drawn onto its recording: frames_u8 uint8 (N, H, W, 3) on
         the device and the track (it must hold "attention_maps" and "attention_count") -> uint8 (N, H, W, 3): on every frame a
         pair landed on, or the fill reached ("attention_filled"), the map of `head` (None: the head mean) blended over the crop
         the model saw -- one ops.gaze_overlay call per chunk.  Every other frame comes back byte for byte.  points (optional,
         (N, 2) on the crop, e.g. the gaze track's "points"): a disc of `radius` pixels where the point is finite; a drawn frame
         without a point gets no disc (its marker centre lies radius + 1 pixels right of the frame).  chunk: frames per launch
-        (default: all).  out=frames_u8 renders in place."""
+        (default: all).  out=frames_u8 renders in place.  pixel_format "nv12" | "i420": frames_u8 is the 4:2:0 recording uint8
+        (N, H * 3 / 2, W); each chunk is converted into `out` (inputs.yuv_to_rgb) and drawn over there: out must not alias it."""
         if not torch.is_tensor(frames_u8) or not frames_u8.is_cuda:
             raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
         if "attention_maps" not in track or "attention_count" not in track:
             raise ValueError("render_attention_track needs the track's \"attention_maps\" and \"attention_count\": call predict_video "
                              "with attention_track=True")
-        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
-            raise ValueError(f"frames must be uint8 (N, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
-        N, H, W, _ = frames_u8.shape
+        H, W, fmt = _picture_hw(frames_u8, 1, pixel_format, matrix, full_range)
+        N = frames_u8.shape[0]
+        if fmt:
+            out = _render_out(frames_u8, out, H, W, fmt)
         maps, count = track["attention_maps"], track["attention_count"]
         if maps.dim() != 4 or maps.shape[0] != N or tuple(count.shape) != (N,):
             raise ValueError(f"the attention track holds {maps.shape[0]} frames, the recording {N}")
@@ -567,15 +619,18 @@ class GazePredictor:
             picture = maps[:, g].contiguous()
             if out is None:
                 out = torch.empty_like(frames_u8)
+            from . import inputs
             for a in range(0, N, step):
                 sel = slice(a, min(a + step, N))
-                ops.gaze_overlay(frames_u8[sel], picture[sel], params, S, centers=centers[sel], alpha=alpha, radius=radius,
+                src = inputs.yuv_to_rgb(frames_u8[sel], out=out[sel], **fmt) if fmt else frames_u8[sel]
+                ops.gaze_overlay(src, picture[sel], params, S, centers=centers[sel], alpha=alpha, radius=radius,
                                  out=out[sel])
         return out
 
     @torch.no_grad()
     def predict_video(self, frames_u8, wav, fps=None, stride=None, batch=None, return_heatmaps=True, overlay=False, fill=None,
-                      max_gap=None, attention_track=False, sample_rate=None):
+                      max_gap=None, attention_track=False, sample_rate=None, *, pixel_format="rgb24", matrix="bt601",
+                      full_range=False):
         """A whole recording in, one gaze track out: frames_u8 uint8 (N, H, W, 3) and wav fp32 (n,) at 24 kHz, both resident on
         the device -> {"points": (N, 2), "peak": (N,), "count": (N,) int32 = windows that predicted the frame, "heatmaps" and
         "rescaled": (N, S/4, S/4) (left out with return_heatmaps=False), "windows": their number}, on the device.
@@ -610,7 +665,12 @@ class GazePredictor:
         sample_rate: None (wav is at 24 kHz: today's path bit for bit, no extra launch), or the rate the audio was recorded
         at, a positive integer: wav, floating or int16, (n,) or (C, n), is first brought to 24 kHz mono on the device
         (inputs.resample_audio: channel mean, band-limited polyphase resampling), and the result is what this call would give
-        for that waveform.  Without a rate a 2-D wav stays an error."""
+        for that waveform.  Without a rate a 2-D wav stays an error.
+
+        pixel_format "nv12" | "i420" (with matrix "bt601" | "bt709", full_range): frames_u8 is the 4:2:0 recording uint8
+        (N, H * 3 / 2, W), half the bytes of RGB; the windows are sampled straight out of it (inputs.clip_sample in that format,
+        no RGB copy of the recording) and every entry equals, bit for bit, that of the converted recording.  "overlay" stays
+        RGB uint8 (N, H, W, 3)."""
         if fill not in (None, "hold", "linear"):
             raise ValueError(f"fill must be None, \"hold\" or \"linear\", got {fill!r}")
         if fill is None and max_gap is not None:
@@ -619,14 +679,13 @@ class GazePredictor:
             if not torch.is_tensor(t) or not t.is_cuda:
                 raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
         from . import inputs
-        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
-            raise ValueError(f"frames must be uint8 (N, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
+        H, W, fmt = _picture_hw(frames_u8, 1, pixel_format, matrix, full_range)
         _check_video_wav(wav, sample_rate)
         if sample_rate is not None:
             with torch.cuda.device(self.device):
                 wav = inputs.resample_audio(wav[None] if wav.dim() == 2 else wav, sample_rate)
                 wav = wav[0] if wav.dim() == 2 else wav
-        N, H, W, _ = frames_u8.shape
+        N = frames_u8.shape[0]
         cfg = self.cfg
         S = int(cfg.DATA.TEST_CROP_SIZE)
         T = int(cfg.DATA.NUM_FRAMES)
@@ -654,7 +713,7 @@ class GazePredictor:
                 if n < nb:                                    # pad by repeating the last window: one graph shape per video
                     idx = torch.cat([idx, idx[-1:].expand(nb - n, T)])
                     cen = torch.cat([cen, cen[-1:].expand(nb - n, T)])
-                video = inputs.clip_sample(frames_u8, idx, params, S, mean=mean, std=std)
+                video = inputs.clip_sample(frames_u8, idx, params, S, mean=mean, std=std, **fmt)
                 audio = inputs.audio_windows_at(spec, cen, AUDIO_WIDTH)
                 if S != AUDIO_WIDTH:   # S frequency bins x S columns around each frame, as predict() cuts them
                     audio = audio[:, :, :, :S, o:o + S].contiguous()
@@ -683,7 +742,7 @@ class GazePredictor:
                     track = fill_attention_track(track, mode=fill, max_gap=max_gap, plan=plan)
             if overlay:
                 track["points_source"] = points_to_source(track["points"], row, S)
-                track["overlay"] = self.render_track(frames_u8, track)
+                track["overlay"] = self.render_track(frames_u8, track, **fmt)
             if not return_heatmaps and "heatmaps" in track:
                 del track["heatmaps"], track["rescaled"]
         track["windows"] = nwin

@@ -214,10 +214,107 @@ def gaze_heatmaps(labels: torch.Tensor, H: int = 64, W: int = 64, ksize: int = 1
     return out
 
 
+PIXEL_FORMATS = ("rgb24", "nv12", "i420")     # packed RGB, and the two 4:2:0 layouts of include/csts_hip.h
+YUV_MATRICES = ("bt601", "bt709")
+# {CY, CRV, CGU, CGV, CBU} = round(c * 2^20) of (matrix, full_range): the tables of include/csts_hip.h, restated
+YUV_TABLES = {("bt601", False): (1220945, 1673555, -410793, -852458, 2115221),
+              ("bt601", True): (1048576, 1470104, -360853, -748826, 1858077),
+              ("bt709", False): (1220945, 1879825, -223607, -558796, 2215014),
+              ("bt709", True): (1048576, 1651297, -196424, -490864, 1945738)}
+
+
+def yuv_frame_shape(H: int, W: int):
+    """The shape of one 4:2:0 frame of H x W pixels (H, W even): (H * 3 // 2, W) bytes, the Y plane then the chroma."""
+    H, W = int(H), int(W)
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError(f"4:2:0 frames need even H, W >= 2, got {H} x {W}")
+    return H * 3 // 2, W
+
+
+def check_pixel_format(pixel_format, matrix="bt601", full_range=False):
+    """(layout, matrix, full_range) as the C ABI takes them; layout 0 for rgb24.  ValueError for an unknown format or matrix."""
+    if pixel_format not in PIXEL_FORMATS:
+        raise ValueError(f"pixel_format must be one of {PIXEL_FORMATS}, got {pixel_format!r}")
+    if matrix not in YUV_MATRICES:
+        raise ValueError(f"matrix must be one of {YUV_MATRICES}, got {matrix!r}")
+    return PIXEL_FORMATS.index(pixel_format), YUV_MATRICES.index(matrix), int(bool(full_range))
+
+
+def _yuv_hw(shape, pixel_format, what="frames"):
+    """H, W of 4:2:0 pictures whose last two dimensions are (H * 3 / 2, W): ValueError for rows no multiple of 3, odd H or W,
+    or a trailing dimension of 3 (packed RGB passed as 4:2:0)."""
+    if len(shape) < 2:
+        raise ValueError(f"{what} in {pixel_format} must be uint8 (..., H * 3 / 2, W), got {tuple(shape)}")
+    rows, W = int(shape[-2]), int(shape[-1])
+    if W == 3 and len(shape) >= 3:
+        raise ValueError(f"{what} of shape {tuple(shape)} look like packed RGB (..., H, W, 3), not {pixel_format}: pass "
+                         "pixel_format='rgb24'")
+    if rows < 3 or rows % 3:
+        raise ValueError(f"{what} in {pixel_format} hold H * 3 / 2 rows per picture: {rows} is not a multiple of 3")
+    H = rows // 3 * 2
+    if W < 2 or W % 2 or H % 2:
+        raise ValueError(f"{what} in {pixel_format} need even H and W, got H {H}, W {W}")
+    return H, W
+
+
+def yuv_to_rgb(frames_yuv: torch.Tensor, pixel_format: str, matrix: str = "bt601", full_range: bool = False,
+               out: torch.Tensor = None) -> torch.Tensor:
+    """4:2:0 pictures uint8 (..., H * 3 / 2, W) in `pixel_format` ("nv12" | "i420") -> packed RGB uint8 (..., H, W, 3) by the
+    integer rule of include/csts_hip.h (nearest chroma, `matrix` "bt601" | "bt709", limited range unless full_range), one
+    streaming launch (csts_yuv_to_rgb).  The input may start at any byte.  out: a contiguous uint8 (..., H, W, 3) GPU tensor to
+    write into, at any byte as well (a slice of a larger tensor); it must not share memory with the input."""
+    layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
+    if layout == 0:
+        raise ValueError("yuv_to_rgb converts 'nv12' or 'i420' pictures; rgb24 needs no conversion")
+    if not torch.is_tensor(frames_yuv) or frames_yuv.dtype != torch.uint8:
+        raise ValueError(f"frames must be a uint8 tensor (..., H * 3 / 2, W), got {getattr(frames_yuv, 'dtype', type(frames_yuv))}")
+    H, W = _yuv_hw(frames_yuv.shape, pixel_format)
+    lead = tuple(frames_yuv.shape[:-2])
+    N = 1
+    for d in lead:
+        N *= int(d)
+    if N < 1:
+        raise ValueError(f"frames hold no picture: {tuple(frames_yuv.shape)}")
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != lead + (H, W, 3) or
+                            not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous uint8 {lead + (H, W, 3)} tensor")
+    _gpu(frames_yuv)
+    x = frames_yuv.contiguous()
+    if out is None:
+        out = torch.empty(lead + (H, W, 3), dtype=torch.uint8, device=x.device)
+    else:
+        _gpu(out)
+        a, b = x.data_ptr(), out.data_ptr()
+        if out.device != x.device or (a < b + out.numel() and b < a + x.numel()):
+            raise ValueError("out must be on the frames' device and must not share memory with them")
+    with torch.cuda.device(x.device):
+        L.check(L.load().csts_yuv_to_rgb(x.data_ptr(), out.data_ptr(), N, H, W, layout, mat, fr, _s()), "csts_yuv_to_rgb")
+    return out
+
+
+def yuv_to_rgb_host(frames_yuv, pixel_format: str, matrix: str = "bt601", full_range: bool = False):
+    """yuv_to_rgb on the CPU (csts_yuv_to_rgb_host, the same pixel function): numpy uint8 (..., H * 3 / 2, W) -> (..., H, W, 3)."""
+    import numpy as np
+    layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
+    if layout == 0:
+        raise ValueError("yuv_to_rgb_host converts 'nv12' or 'i420' pictures; rgb24 needs no conversion")
+    x = np.ascontiguousarray(frames_yuv)
+    if x.dtype != np.uint8:
+        raise ValueError(f"frames must be uint8, got {x.dtype}")
+    H, W = _yuv_hw(x.shape, pixel_format)
+    lead = tuple(x.shape[:-2])
+    N = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    if N < 1:
+        raise ValueError(f"frames hold no picture: {x.shape}")
+    out = np.empty(lead + (H, W, 3), dtype=np.uint8)
+    L.check(L.load().csts_yuv_to_rgb_host(x.ctypes.data, out.ctypes.data, N, H, W, layout, mat, fr), "csts_yuv_to_rgb_host")
+    return out
+
+
 def spatial_sampling(frames_u8: torch.Tensor, labels: torch.Tensor, crop_size: int, *, train: bool, min_scale: int = 0,
                      max_scale: int = 0, spatial_idx: int = 1, random_flip: bool = True, inverse_uniform: bool = False,
                      mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225), generator=None, return_params: bool = False,
-                     key: torch.Tensor = None):
+                     key: torch.Tensor = None, pixel_format: str = "rgb24", matrix: str = "bt601", full_range: bool = False):
     """slowfast/datasets/utils.py::spatial_sampling(..., gaze_loc=labels) on the device, fused with frame normalisation.
 
     frames_u8 uint8 (B, T, H, W, 3), labels (B, T, L >= 2) with x, y in columns 0, 1 -> video fp32 (B, 3, T, S, S) and the
@@ -226,10 +323,18 @@ def spatial_sampling(frames_u8: torch.Tensor, labels: torch.Tensor, crop_size: i
     (DATA.RANDOM_FLIP); the clip variates come from a 64-bit key drawn once per call from `generator` (torch's default
     device generator when None), so the call needs no host sync, can be captured in a graph and follows torch.manual_seed.
     train=False: short side resized to crop_size and the uniform crop `spatial_idx` (0, 1, 2); no draw.  key: an int64 (1,)
-    device tensor to use instead of the draw (the kernel reads it when it runs).  include/csts_hip.h states the rule."""
-    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 5 or frames_u8.shape[-1] != 3:
-        raise ValueError(f"frames must be uint8 (B, T, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
-    B, T, H, W, _ = frames_u8.shape
+    device tensor to use instead of the draw (the kernel reads it when it runs).  include/csts_hip.h states the rule.
+    pixel_format "nv12" | "i420": frames_u8 is uint8 (B, T, H * 3 / 2, W), 4:2:0 pictures sampled in place (spatial_sample)."""
+    yuv = check_pixel_format(pixel_format, matrix, full_range)[0] != 0
+    if yuv:
+        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4:
+            raise ValueError(f"{pixel_format} frames must be uint8 (B, T, H * 3 / 2, W), got {tuple(frames_u8.shape)} "
+                             f"{frames_u8.dtype}")
+        (B, T), (H, W) = frames_u8.shape[:2], _yuv_hw(frames_u8.shape, pixel_format)
+    else:
+        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 5 or frames_u8.shape[-1] != 3:
+            raise ValueError(f"frames must be uint8 (B, T, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
+        B, T, H, W, _ = frames_u8.shape
     if labels.dim() != 3 or tuple(labels.shape[:2]) != (B, T) or labels.shape[2] < 2 or not labels.is_floating_point():
         raise ValueError(f"labels must be floating (B, T, L >= 2) = ({B}, {T}, L), got {tuple(labels.shape)} {labels.dtype}")
     S = int(crop_size)
@@ -267,17 +372,27 @@ def spatial_sampling(frames_u8: torch.Tensor, labels: torch.Tensor, crop_size: i
     L.check(lib.csts_spatial_params(key.data_ptr() if key is not None else None, lab.data_ptr(), B, T, ncol, H, W, S, min_scale,
                                      max_scale, idx, int(bool(random_flip)), int(bool(inverse_uniform)), params.data_ptr(),
                                      new_labels.data_ptr(), _s()), "csts_spatial_params")
-    video = spatial_sample(x, params, S, mean=mean, std=std)
+    video = spatial_sample(x, params, S, mean=mean, std=std, pixel_format=pixel_format, matrix=matrix, full_range=full_range)
     return (video, new_labels, params) if return_params else (video, new_labels)
 
 
 def spatial_sample(frames_u8: torch.Tensor, params: torch.Tensor, crop_size: int, mean=(0.45, 0.45, 0.45),
-                   std=(0.225, 0.225, 0.225)) -> torch.Tensor:
+                   std=(0.225, 0.225, 0.225), *, pixel_format: str = "rgb24", matrix: str = "bt601",
+                   full_range: bool = False) -> torch.Tensor:
     """The pixel pass of spatial_sampling alone: uint8 (B, T, H, W, 3) + int32 params (B, 5) = new h, new w, y0, x0, flip ->
-    fp32 (B, 3, T, S, S) = normalised bilinear resize (F.interpolate, align_corners=False) + crop + horizontal flip."""
-    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 5 or frames_u8.shape[-1] != 3:
-        raise ValueError(f"frames must be uint8 (B, T, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
-    B, T, H, W, _ = frames_u8.shape
+    fp32 (B, 3, T, S, S) = normalised bilinear resize (F.interpolate, align_corners=False) + crop + horizontal flip.
+    pixel_format "nv12" | "i420": frames_u8 is uint8 (B, T, H * 3 / 2, W), 4:2:0 pictures read in place
+    (csts_spatial_sample_yuv); the result is, bit for bit, spatial_sample(yuv_to_rgb(frames, ...), params, S)."""
+    layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
+    if layout:
+        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4:
+            raise ValueError(f"{pixel_format} frames must be uint8 (B, T, H * 3 / 2, W), got {tuple(frames_u8.shape)} "
+                             f"{frames_u8.dtype}")
+        (B, T), (H, W) = frames_u8.shape[:2], _yuv_hw(frames_u8.shape, pixel_format)
+    else:
+        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 5 or frames_u8.shape[-1] != 3:
+            raise ValueError(f"frames must be uint8 (B, T, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
+        B, T, H, W, _ = frames_u8.shape
     if params.dtype != torch.int32 or tuple(params.shape) != (B, 5):
         raise ValueError(f"params must be int32 ({B}, 5), got {tuple(params.shape)} {params.dtype}")
     _gpu(frames_u8, params)
@@ -288,20 +403,33 @@ def spatial_sample(frames_u8: torch.Tensor, params: torch.Tensor, crop_size: int
     out = torch.empty(B, 3, T, S, S, dtype=torch.float32, device=x.device)
     f3 = C.c_float * 3
     par = params.contiguous()
+    if layout:
+        L.check(L.load().csts_spatial_sample_yuv(x.data_ptr(), par.data_ptr(), out.data_ptr(), B, T, H, W, S, f3(*mean), f3(*std),
+                                                 layout, mat, fr, _s()), "csts_spatial_sample_yuv")
+        return out
     L.check(L.load().csts_spatial_sample(x.data_ptr(), par.data_ptr(), out.data_ptr(), B, T, H, W, S, f3(*mean), f3(*std), _s()),
             "csts_spatial_sample")
     return out
 
 
 def clip_sample(video_u8: torch.Tensor, frames_idx: torch.Tensor, params: torch.Tensor, crop_size: int,
-                mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225)) -> torch.Tensor:
+                mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225), *, pixel_format: str = "rgb24", matrix: str = "bt601",
+                full_range: bool = False) -> torch.Tensor:
     """spatial_sample of clips that are windows of ONE resident video, without gathering them first: video uint8 (N, H, W, 3),
     frames_idx int32 (B, T) frame numbers (clamped to [0, N - 1] on the device, as the reference's temporal_sampling clamps),
     params int32 (B, 5) -> fp32 (B, 3, T, S, S), bit for bit spatial_sample(video[frames_idx], params, S).  The table is read
-    by the kernel when it runs: no host sync, graph-capturable (csts_clip_sample)."""
-    if video_u8.dtype != torch.uint8 or video_u8.dim() != 4 or video_u8.shape[-1] != 3 or video_u8.shape[0] < 1:
-        raise ValueError(f"video must be uint8 (N >= 1, H, W, 3), got {tuple(video_u8.shape)} {video_u8.dtype}")
-    N, H, W, _ = video_u8.shape
+    by the kernel when it runs: no host sync, graph-capturable (csts_clip_sample).  pixel_format "nv12" | "i420": the video is
+    uint8 (N, H * 3 / 2, W), 4:2:0 pictures read in place (csts_clip_sample_yuv), bit for bit clip_sample of yuv_to_rgb(video)."""
+    layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
+    if layout:
+        if video_u8.dtype != torch.uint8 or video_u8.dim() != 3 or video_u8.shape[0] < 1:
+            raise ValueError(f"{pixel_format} video must be uint8 (N >= 1, H * 3 / 2, W), got {tuple(video_u8.shape)} "
+                             f"{video_u8.dtype}")
+        N, (H, W) = video_u8.shape[0], _yuv_hw(video_u8.shape, pixel_format, "video")
+    else:
+        if video_u8.dtype != torch.uint8 or video_u8.dim() != 4 or video_u8.shape[-1] != 3 or video_u8.shape[0] < 1:
+            raise ValueError(f"video must be uint8 (N >= 1, H, W, 3), got {tuple(video_u8.shape)} {video_u8.dtype}")
+        N, H, W, _ = video_u8.shape
     if frames_idx.dtype != torch.int32 or frames_idx.dim() != 2:
         raise ValueError(f"frames_idx must be int32 (B, T), got {tuple(frames_idx.shape)} {frames_idx.dtype}")
     B, T = frames_idx.shape
@@ -319,6 +447,10 @@ def clip_sample(video_u8: torch.Tensor, frames_idx: torch.Tensor, params: torch.
     out = torch.empty(B, 3, T, S, S, dtype=torch.float32, device=x.device)
     f3 = C.c_float * 3
     idx, par = frames_idx.contiguous(), params.contiguous()
+    if layout:
+        L.check(L.load().csts_clip_sample_yuv(x.data_ptr(), N, idx.data_ptr(), par.data_ptr(), out.data_ptr(), B, T, H, W, S,
+                                              f3(*mean), f3(*std), layout, mat, fr, _s()), "csts_clip_sample_yuv")
+        return out
     L.check(L.load().csts_clip_sample(x.data_ptr(), N, idx.data_ptr(), par.data_ptr(), out.data_ptr(), B, T, H, W, S, f3(*mean),
                                       f3(*std), _s()), "csts_clip_sample")
     return out
@@ -384,14 +516,18 @@ def batch_params(labels: torch.Tensor, clips: torch.Tensor, crop_size: int, *, t
 
 
 def batch_sample(arena_u8: torch.Tensor, clips: torch.Tensor, frames_idx: torch.Tensor, params: torch.Tensor, crop_size: int,
-                 clips_host, mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225), out: torch.Tensor = None) -> torch.Tensor:
+                 clips_host, mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225), out: torch.Tensor = None, *,
+                 pixel_format: str = "rgb24", matrix: str = "bt601", full_range: bool = False) -> torch.Tensor:
     """clip_sample for clips of B different recordings in ONE launch (csts_batch_sample): arena_u8 uint8 (bytes,) holds the
     recordings back to back at any byte, clips int64 (B, 4) = {byte offset, N, H, W} on the device, frames_idx int32 (B, T)
     (clamped to [0, N_b - 1] on the device), params int32 (B, 5) -> fp32 (B, 3, T, S, S); clip b is, bit for bit,
     clip_sample(recording_b, frames_idx[b:b+1], params[b:b+1], S).  clips_host: the table on the host; every row must lie inside
     the arena with N, H, W >= 1 (ValueError) -- the device reads the tables when the kernel runs and gives a NaN clip for a row
-    that does not, so a captured launch stays safe when the tables are rewritten."""
+    that does not, so a captured launch stays safe when the tables are rewritten.  pixel_format "nv12" | "i420": the recordings
+    are 4:2:0 pictures (csts_batch_sample_yuv); the table keeps its columns with H the luma height (H, W even), a recording
+    occupies N H W 3 / 2 bytes and clip b is clip_sample of it in that format."""
     import numpy as np
+    layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
     if arena_u8.dtype != torch.uint8 or arena_u8.dim() != 1 or arena_u8.numel() < 3:
         raise ValueError(f"the arena must be uint8 (bytes,), got {tuple(arena_u8.shape)} {arena_u8.dtype}")
     if frames_idx.dtype != torch.int32 or frames_idx.dim() != 2:
@@ -410,7 +546,9 @@ def batch_sample(arena_u8: torch.Tensor, clips: torch.Tensor, frames_idx: torch.
         raise ValueError(f"the host clip table has {host.shape[0]} rows, the batch {B}")
     nbytes = arena_u8.numel()
     for b, (off, n, h, w) in enumerate(host.tolist()):
-        if n < 1 or h < 1 or w < 1 or w > 6000 or off < 0 or off + n * h * w * 3 > nbytes:
+        if layout and (h % 2 or w % 2):
+            raise ValueError(f"clip {b}: {pixel_format} recordings need even H and W, got H {h}, W {w}")
+        if n < 1 or h < 1 or w < 1 or w > 6000 or off < 0 or off + (n * h * w * 3 // 2 if layout else n * h * w * 3) > nbytes:
             raise ValueError(f"clip {b}: recording (offset {off}, N {n}, H {h}, W {w}) does not lie inside the arena of {nbytes} "
                              "bytes (or W > 6000)")
     _gpu(arena_u8, tab, frames_idx, params)
@@ -422,6 +560,11 @@ def batch_sample(arena_u8: torch.Tensor, clips: torch.Tensor, frames_idx: torch.
         raise ValueError(f"out must be a contiguous fp32 ({B}, 3, {T}, {S}, {S}) GPU tensor")
     f3 = C.c_float * 3
     idx, par = frames_idx.contiguous(), params.contiguous()
+    if layout:
+        L.check(L.load().csts_batch_sample_yuv(arena_u8.data_ptr(), nbytes, tab.data_ptr(), idx.data_ptr(), par.data_ptr(),
+                                               out.data_ptr(), B, T, S, int(host[:, 3].max()), f3(*mean), f3(*std), layout, mat, fr,
+                                               _s()), "csts_batch_sample_yuv")
+        return out
     L.check(L.load().csts_batch_sample(arena_u8.data_ptr(), nbytes, tab.data_ptr(), idx.data_ptr(), par.data_ptr(), out.data_ptr(),
                                        B, T, S, int(host[:, 3].max()), f3(*mean), f3(*std), _s()), "csts_batch_sample")
     return out
@@ -502,18 +645,27 @@ def spatial_uniforms_host(key: int, first: int, count: int):
     return out
 
 
-def assemble_batch(frames_u8, wav, frames_idx, frame_length, labels, spatial=None):
+def assemble_batch(frames_u8, wav, frames_idx, frame_length, labels, spatial=None, *, pixel_format: str = "rgb24",
+                   matrix: str = "bt601", full_range: bool = False):
     """uint8 frames (B, T, H, W, 3), waveform (B, n), sampled frame indices (B, T), gaze labels (B, T, 3) -> the batch
     dict the training step takes (video, audio, labels_hm, labels).  spatial: None (frames normalised at the size they
     come in), or the keyword arguments of spatial_sampling (crop_size, train, ...): the video is spatially sampled, and
-    the heat maps ((S/4)^2) and the returned labels are the transformed ones (ego4d_avgaze_forecast.py:302-326)."""
+    the heat maps ((S/4)^2) and the returned labels are the transformed ones (ego4d_avgaze_forecast.py:302-326).
+    pixel_format "nv12" | "i420": the frames are 4:2:0 pictures uint8 (B, T, H * 3 / 2, W); with spatial they are sampled in
+    place, without it they are converted (yuv_to_rgb) and normalised."""
+    yuv = check_pixel_format(pixel_format, matrix, full_range)[0] != 0
+    fmt = dict(pixel_format=pixel_format, matrix=matrix, full_range=full_range) if yuv else {}
+    if yuv:
+        if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4:
+            raise ValueError(f"{pixel_format} frames must be uint8 (B, T, H * 3 / 2, W), got {tuple(frames_u8.shape)}")
+        _yuv_hw(frames_u8.shape, pixel_format)
     if spatial is None:
-        return {"video": normalize_frames(frames_u8),
+        return {"video": normalize_frames(yuv_to_rgb(frames_u8, **fmt) if yuv else frames_u8),
                 "audio": audio_windows(stft_logpower(wav), frames_idx, frame_length),
                 "labels_hm": gaze_heatmaps(labels), "labels": labels}
     kw = dict(spatial)
     S = int(kw.pop("crop_size"))
-    video, new_labels = spatial_sampling(frames_u8, labels, S, **kw)
+    video, new_labels = spatial_sampling(frames_u8, labels, S, **kw, **fmt)
     return {"video": video,
             "audio": audio_windows(stft_logpower(wav), frames_idx, frame_length),
             "labels_hm": gaze_heatmaps(new_labels, H=S // 4, W=S // 4), "labels": new_labels}

@@ -42,7 +42,7 @@ def half_dtype():
     return torch.float16 if HALF == "fp16" else torch.bfloat16
 
 
-ABI_VERSION = 13  # == CSTS_ABI_VERSION of include/csts_hip.h this binding mirrors (struct layouts below)
+ABI_VERSION = 14  # == CSTS_ABI_VERSION of include/csts_hip.h this binding mirrors (struct layouts below)
 F32, BF16 = 0, 1
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 EPI_NONE, EPI_GELU, EPI_DGELU = 0, 1, 2
@@ -52,6 +52,8 @@ GAZE_DECODE_MAX_HW = 8192
 AUDIO_PIXEL_MAX_SIDE, AUDIO_PIXEL_MAX_HW = 128, 4096
 WAV_F32, WAV_I16 = 0, 1
 RESAMPLE_RUN, RESAMPLE_MAX_LDS_FLOATS, RESAMPLE_MAX_RATIO, RESAMPLE_MAX_N = 256, 16384, 1 << 20, 1 << 40
+YUV_NV12, YUV_I420 = 1, 2
+YUV_BT601, YUV_BT709 = 0, 1
 
 vp = C.c_void_p
 i64 = C.c_int64
@@ -266,6 +268,11 @@ SYMBOLS = {
     "csts_audio_gather": (_I, [vp, vp, vp, vp, _I, _I, _I, _I, vp]),
     "csts_resample_len": (i64, [i64, _I, _I]),
     "csts_resample_wav": (_I, [vp, _I, _I, _I, i64, vp, _I, _I, _I, vp, vp]),
+    "csts_yuv_to_rgb": (_I, [vp, vp, i64, _I, _I, _I, _I, _I, vp]),
+    "csts_yuv_to_rgb_host": (_I, [vp, vp, i64, _I, _I, _I, _I, _I]),
+    "csts_spatial_sample_yuv": (_I, [vp, vp, vp, _I, _I, _I, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),
+    "csts_clip_sample_yuv": (_I, [vp, i64, vp, vp, vp, _I, _I, _I, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),
+    "csts_batch_sample_yuv": (_I, [vp, i64, vp, vp, vp, vp, _I, _I, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),
     "csts_adaptive_f1_workspace": (sz, [i64, _I]),
     "csts_adaptive_f1": (_I, [vp, vp, vp, vp, _I, i64, _I, _I, vp, vp, sz, vp]),
     "csts_f1_counts": (_I, [vp, vp, vp, _I, i64, _I, _I, vp, vp]),

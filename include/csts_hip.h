@@ -32,10 +32,10 @@ enum { CSTS_EPI_NONE = 0, CSTS_EPI_GELU = 1, CSTS_EPI_DGELU = 2 };
 enum { CSTS_MASK_NONE = 0, CSTS_MASK_SPATIAL = 1 };
 
 /* Version of this header's struct layouts and call semantics.  Bumped whenever a struct grows or a field changes meaning
- * (2: csts_gemm_args.res_up; 3: compact k|v rows, 16-bit build, loss scaler in csts_opt_args; 4: csts_opt_args.extra_sq, factored AdamW; 5: grouped stencil weight gradients; 6: csts_copy_token_segments, csts_wgrad_grouped8_limited; 7: csts_wgrad_grouped5, csts_gemm algo 500; 8: csts_opt_rule, csts_opt_step, csts_opt_factored_step, csts_opt_factored.tensor replaces pad_; 10: csts_audio_pixel_attn; 11: csts_attention_track, csts_attention_rescale; 12: csts_resample_wav, csts_resample_len; 13: csts_attn_route).  csts_abi_version() returns the value the
+ * (2: csts_gemm_args.res_up; 3: compact k|v rows, 16-bit build, loss scaler in csts_opt_args; 4: csts_opt_args.extra_sq, factored AdamW; 5: grouped stencil weight gradients; 6: csts_copy_token_segments, csts_wgrad_grouped8_limited; 7: csts_wgrad_grouped5, csts_gemm algo 500; 8: csts_opt_rule, csts_opt_step, csts_opt_factored_step, csts_opt_factored.tensor replaces pad_; 10: csts_audio_pixel_attn; 11: csts_attention_track, csts_attention_rescale; 12: csts_resample_wav, csts_resample_len; 13: csts_attn_route; 14: 4:2:0 frames, csts_yuv_to_rgb, csts_*_sample_yuv).  csts_abi_version() returns the value the
  * LIBRARY was built with: a caller must compare it with the CSTS_ABI_VERSION it was compiled against and refuse a mismatch
  * (the Python binding does, csts_amd/lib.py::load). */
-#define CSTS_ABI_VERSION 13
+#define CSTS_ABI_VERSION 14
 const char* csts_last_error(void);
 int csts_abi_version(void);
 int csts_half_kind(void);   /* the 16-bit type behind CSTS_BF16 in THIS library: 0 bfloat16 (libcsts_hip.so), 1 IEEE half (libcsts_hip_f16.so) */
@@ -582,6 +582,51 @@ int csts_batch_sample(const uint8_t* arena_u8, int64_t arena_bytes, const int64_
                       float* out, int B, int T, int S, int max_W, const float mean[3], const float std[3], hipStream_t stream);
 int csts_audio_gather(const float* spec_arena, const int64_t* specs, const int* centers, float* out, int B, int T, int nbins,
                       int width, hipStream_t stream);
+
+/* ---- 4:2:0 YUV frames (csts_amd/csrc/yuv.hip, yuv_shared.h; csts_amd/inputs.py): pictures the way video sources deliver them --
+ *      NV12 from hardware decoders, I420 (yuv420p) from software ones -- 1.5 bytes per pixel, converted where they are read.
+ *      Layouts.  One frame is H * 3 / 2 rows of W bytes, H and W even, rows unpadded:
+ *        CSTS_YUV_NV12: the Y plane H x W, then H / 2 rows of interleaved U V U V ...
+ *        CSTS_YUV_I420: the Y plane H x W, then the U plane (H/2) x (W/2), then the V plane (H/2) x (W/2), each contiguous.
+ *      Pixel (y, x) uses Y[y][x] and the chroma sample (y >> 1, x >> 1): nearest replication, no chroma interpolation.
+ *      Arithmetic, all int32 (>> is the arithmetic shift), so a pixel is an exact function of three bytes:
+ *        y' = Y - yoff, u' = U - 128, v' = V - 128          yoff = 16 (limited range) or 0 (full_range != 0)
+ *        R = clamp((CY y' + CRV v' + 2^19) >> 20, 0, 255)
+ *        G = clamp((CY y' + CGU u' + CGV v' + 2^19) >> 20, 0, 255)
+ *        B = clamp((CY y' + CBU u' + 2^19) >> 20, 0, 255)
+ *      {CY, CRV, CGU, CGV, CBU} = round(c 2^20) of the rationals c = {sy, 2 sc (1 - Kr), -2 sc Kb (1 - Kb) / Kg,
+ *      -2 sc Kr (1 - Kr) / Kg, 2 sc (1 - Kb)}, Kg = 1 - Kr - Kb, sy = 255/219 and sc = 255/224 (limited) or 1 (full);
+ *      CSTS_YUV_BT601: Kr 0.299, Kb 0.114; CSTS_YUV_BT709: Kr 0.2126, Kb 0.0722:
+ *        bt601 limited {1220945, 1673555, -410793, -852458, 2115221}    bt601 full {1048576, 1470104, -360853, -748826, 1858077}
+ *        bt709 limited {1220945, 1879825, -223607, -558796, 2215014}    bt709 full {1048576, 1651297, -196424, -490864, 1945738}
+ *      The accumulators stay below 5.74e8 in magnitude and the result is within 1 of clip(rint(real-valued matrix)) for every
+ *      byte triple.  The rule is this library's own statement (the reference decodes with PyAV's to_rgb(), whose swscale
+ *      arithmetic is not restated here).
+ *      yuv_to_rgb: frames (N, H * 3 / 2, W) -> out (N, H, W, 3) RGB, one streaming pass with 16-byte loads and stores.  frames_yuv
+ *        may start at any byte and a frame of H W 3 / 2 bytes at any byte of it; out may start at any byte too (a chunk of a
+ *        larger tensor) and must not overlap the input.  H <= 131070.  yuv_to_rgb_host: the same pixel function over HOST memory.
+ *      *_sample_yuv: csts_spatial_sample / csts_clip_sample / csts_batch_sample with 4:2:0 pictures in place of RGB ones: frames
+ *        (B, T, H * 3 / 2, W), a video (N, H * 3 / 2, W), or an arena whose clip table stays {byte offset, N, H, W} with H the luma
+ *        height, a recording occupying N H W 3 / 2 bytes.  Each of the four taps of an output pixel is converted to integer R, G,
+ *        B by the rule above and the fp32 expressions of the RGB pass follow in the same order: the result equals, bit for bit,
+ *        the RGB function on yuv_to_rgb of the pictures.  Every guarantee of the RGB functions holds: tables read on the DEVICE
+ *        when the kernel runs, no host sync, no allocation, graph-capturable, bad params or a bad clip row give a NaN clip and
+ *        read nothing, no byte at or past the end of the source is read, W <= 6000, source and out 16-byte aligned.  Odd H or W
+ *        is refused (-1) where it is an argument and gives a NaN clip where it stands in a device table. */
+enum { CSTS_YUV_NV12 = 1, CSTS_YUV_I420 = 2 };
+enum { CSTS_YUV_BT601 = 0, CSTS_YUV_BT709 = 1 };
+int csts_yuv_to_rgb(const uint8_t* frames_yuv, uint8_t* out_nhwc, int64_t N, int H, int W, int layout, int matrix, int full_range,
+                    hipStream_t stream);
+int csts_yuv_to_rgb_host(const uint8_t* frames_yuv, uint8_t* out_nhwc, int64_t N, int H, int W, int layout, int matrix,
+                         int full_range);
+int csts_spatial_sample_yuv(const uint8_t* frames_yuv, const int* params, float* out, int B, int T, int H, int W, int S,
+                            const float mean[3], const float std[3], int layout, int matrix, int full_range, hipStream_t stream);
+int csts_clip_sample_yuv(const uint8_t* video_yuv, int64_t N, const int* frames_idx, const int* params, float* out, int B, int T,
+                         int H, int W, int S, const float mean[3], const float std[3], int layout, int matrix, int full_range,
+                         hipStream_t stream);
+int csts_batch_sample_yuv(const uint8_t* arena_u8, int64_t arena_bytes, const int64_t* clips, const int* frames_idx,
+                          const int* params, float* out, int B, int T, int S, int max_W, const float mean[3], const float std[3],
+                          int layout, int matrix, int full_range, hipStream_t stream);
 
 /* ---- audio at any sample rate (csts_amd/csrc/resample.hip, csts_amd/inputs.py::resample_audio): band-limited resampling by the
  *      rational ratio up / down (reduced: gcd 1), the step the reference does offline with ffmpeg (data/preprocess.py::

@@ -12,7 +12,9 @@
 
 --dataset picks the clip length (Ego4D forecast: 150 frames of 5 s; Aria forecast: 100 frames of 5 s at 20 fps).  train.csv lists
 every clip, test.csv the last --test-clips of them.  --sample-rate R writes the waveforms at R Hz instead, with a sample_rate entry
-beside them (csts_amd/datasets.py resamples such clips to 24 kHz on the device).  Pure numpy: no GPU needed."""
+beside them (csts_amd/datasets.py resamples such clips to 24 kHz on the device).  --pixel-format nv12|i420 writes the pictures as
+random 4:2:0 frames instead: frames_yuv uint8 (N, H * 3 / 2, W) with a pixel_format entry (H and W must be even).  Pure numpy: no
+GPU needed."""
 import argparse
 import os
 
@@ -23,10 +25,13 @@ CLIP = {"ego4d_av_gaze_forecast": (150, 30, ("frame", "x", "y", "type")),
 
 
 def write_dataset(out, dataset="ego4d_av_gaze_forecast", clips_per_video=(3, 2), sizes=((36, 48), (40, 44)), seconds=5,
-                  test_clips=2, seed=0, label_rows=None, sample_rate=None):
+                  test_clips=2, seed=0, label_rows=None, sample_rate=None, pixel_format="rgb24"):
     """-> the list of clip lines written to train.csv.  clips_per_video[v] clips of sizes[v % len(sizes)] = (H, W) for video v;
     label_rows (optional): rows of every video's label table (default: enough for every clip), to make a table run out.
-    sample_rate (optional): the waveforms are noise at that rate and every clip carries a sample_rate entry."""
+    sample_rate (optional): the waveforms are noise at that rate and every clip carries a sample_rate entry.
+    pixel_format "nv12" | "i420": every clip holds frames_yuv uint8 (N, H * 3 / 2, W) noise and a pixel_format entry."""
+    if pixel_format not in ("rgb24", "nv12", "i420"):
+        raise ValueError(f"pixel_format must be rgb24, nv12 or i420, got {pixel_format!r}")
     n_frames, fps, header = CLIP[dataset]
     rng = np.random.default_rng(seed)
     lines = []
@@ -38,8 +43,14 @@ def write_dataset(out, dataset="ego4d_av_gaze_forecast", clips_per_video=(3, 2),
         for c in range(nclips):
             name = f"{video}_t{c * seconds}_t{(c + 1) * seconds}"
             rate = {} if sample_rate is None else {"sample_rate": np.int64(sample_rate)}
-            np.savez(os.path.join(out, "clips", video, name + ".npz"),
-                     frames_u8=rng.integers(0, 256, (n_frames, H, W, 3), dtype=np.uint8),
+            if pixel_format == "rgb24":
+                pictures = {"frames_u8": rng.integers(0, 256, (n_frames, H, W, 3), dtype=np.uint8)}
+            else:
+                if H % 2 or W % 2:
+                    raise ValueError(f"4:2:0 frames need even H and W, got {H} x {W}")
+                pictures = {"frames_yuv": rng.integers(0, 256, (n_frames, H * 3 // 2, W), dtype=np.uint8),
+                            "pixel_format": np.array(pixel_format)}
+            np.savez(os.path.join(out, "clips", video, name + ".npz"), **pictures,
                      wav=(0.1 * rng.standard_normal((24000 if sample_rate is None else int(sample_rate)) * seconds)).astype(np.float32),
                      fps=np.float32(fps), **rate)
             lines.append(f"{video}/{name}.mp4")
@@ -69,11 +80,13 @@ def main(argv=None):
     p.add_argument("--test-clips", default=2, type=int)
     p.add_argument("--seed", default=0, type=int)
     p.add_argument("--sample-rate", default=None, type=int, help="write the waveforms at this rate with a sample_rate entry")
+    p.add_argument("--pixel-format", default="rgb24", choices=("rgb24", "nv12", "i420"),
+                   help="nv12 / i420: write frames_yuv (N, H * 3 / 2, W) with a pixel_format entry instead of frames_u8")
     a = p.parse_args(argv)
     if a.sample_rate is not None and a.sample_rate < 1:
         p.error("--sample-rate must be positive")
     lines = write_dataset(a.out, a.dataset, (a.clips,) * a.videos, ((a.height, a.width),), test_clips=a.test_clips, seed=a.seed,
-                          sample_rate=a.sample_rate)
+                          sample_rate=a.sample_rate, pixel_format=a.pixel_format)
     print(f"wrote {len(lines)} clips of {a.dataset} to {a.out}")
 
 

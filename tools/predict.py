@@ -41,7 +41,12 @@ Audio at another rate (--clip and --video): an optional npz entry sample_rate (i
 --sample-rate R overrides it; wav, floating or int16, may then carry a channel axis in front of its samples ((B, C, n) / (C, n)),
 and is brought to 24 kHz mono on the device first (csts_amd.inputs.resample_audio).  --out then also records sample_rate (what
 came in) and audio_rate (24000), and the json_stats line carries both.  Without either the output and the record are what they
-were."""
+were.
+4:2:0 pictures (--clip and --video): instead of frames_u8 the npz may hold frames_yuv uint8 (B, T, H * 3 / 2, W) / (N, H * 3 / 2, W)
+with a pixel_format entry ("nv12" or "i420") and optionally yuv_matrix ("bt601", the default, or "bt709") and yuv_full_range;
+--pixel-format, --yuv-matrix and --yuv-full-range override the entries.  The pictures are uploaded and sampled in that format
+(half the bytes of RGB); overlays stay RGB uint8 (N, H, W, 3).  An npz holding both frames_u8 and frames_yuv is an error.  The
+json_stats line then carries "pixel_format"."""
 import argparse
 import json
 import os
@@ -81,6 +86,12 @@ def parse_args(argv=None):
                    help="with --video: also draw that head's attention track onto the recording (implies --attention-track)")
     p.add_argument("--sample-rate", default=None, type=int,
                    help="rate wav was recorded at (default: the npz entry sample_rate, else 24000): resampled on the device")
+    p.add_argument("--pixel-format", default=None, choices=["nv12", "i420"],
+                   help="layout of the npz entry frames_yuv (default: its pixel_format entry)")
+    p.add_argument("--yuv-matrix", default=None, choices=["bt601", "bt709"],
+                   help="colour matrix of frames_yuv (default: the npz entry yuv_matrix, else bt601)")
+    p.add_argument("--yuv-full-range", default=None, type=int, choices=[0, 1],
+                   help="1: frames_yuv is full range, 0: limited (default: the npz entry yuv_full_range, else limited)")
     p.add_argument("--seed", default=2000, type=int, help="seed of the synthetic batch used without --clip")
     p.add_argument("--batch", default=2, type=int, help="clips in the synthetic batch used without --clip")
     p.add_argument("--no-graph", action="store_true", help="launch the kernels eagerly instead of replaying a HIP graph")
@@ -114,6 +125,8 @@ def parse_args(argv=None):
         p.error("--overlay-every must be positive")
     if args.sample_rate is not None and args.sample_rate < 1:
         p.error("--sample-rate must be positive")
+    if (args.pixel_format or args.yuv_matrix or args.yuv_full_range is not None) and args.video is None and args.clip is None:
+        p.error("--pixel-format, --yuv-matrix and --yuv-full-range describe recorded pictures: they need --clip or --video")
     if args.sample_rate is not None and args.video is None and args.clip is None:
         p.error("--sample-rate is the rate of a recorded waveform: it needs --clip or --video")
     return args
@@ -129,6 +142,21 @@ def source_rate(z, args, path):
     if rate.size != 1 or float(rate[0]) != int(rate[0]) or int(rate[0]) < 1:
         raise SystemExit(f"{path}: sample_rate must be one positive integer, got {z['sample_rate']!r}")
     return int(rate[0])
+
+
+def pictures(z, args, path, lead):
+    """The pictures of an opened npz (numpy) and the keywords that name their format ({} for frames_u8, packed RGB): frames_yuv
+    with pixel_format [, yuv_matrix, yuv_full_range], each overridden by its flag.  lead: 1 for a video (N, ...), 2 for a clip."""
+    from csts_amd.datasets import clip_pictures
+    if "frames_yuv" not in z.files and (args.pixel_format or args.yuv_matrix or args.yuv_full_range is not None):
+        raise SystemExit(f"{path} holds no frames_yuv: --pixel-format, --yuv-matrix and --yuv-full-range describe 4:2:0 pictures")
+    try:
+        frames, _, _, fmt = clip_pictures(z, path, args.pixel_format, args.yuv_matrix,
+                                          None if args.yuv_full_range is None else bool(args.yuv_full_range), lead=lead)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    kw = {} if fmt[0] == "rgb24" else {"pixel_format": fmt[0], "matrix": fmt[1], "full_range": fmt[2]}
+    return frames, kw
 
 
 def waveform(z, rate, dev):
@@ -148,7 +176,7 @@ def write_pngs(overlay, directory, every):
         Image.fromarray(overlay[i]).save(os.path.join(directory, f"frame_{i:06d}.png"))
 
 
-def write_attention(predictor, frames_u8, out, directory):
+def write_attention(predictor, frames_u8, out, directory, fmt):
     """spat_attn_<clip>_<frame>_head_<k>.png for every head and the head mean, temporal_attn_<clip>.txt."""
     os.makedirs(directory, exist_ok=True)
     temporal = out["temporal_attention"].cpu().numpy()
@@ -161,7 +189,7 @@ def write_attention(predictor, frames_u8, out, directory):
         return
     heads = out["attention_maps"].shape[1] - 1
     for k in list(range(heads)) + [None]:
-        drawn = predictor.render_attention(frames_u8, out, head=k).cpu().numpy()
+        drawn = predictor.render_attention(frames_u8, out, head=k, **fmt).cpu().numpy()
         name = "mean" if k is None else str(k)
         for b in range(drawn.shape[0]):
             for t in range(drawn.shape[1]):
@@ -171,6 +199,11 @@ def write_attention(predictor, frames_u8, out, directory):
 def main(argv=None):
     args = parse_args(argv)
     attention = bool(args.attention or args.attention_dir)
+    npz, pics = args.video or args.clip, None
+    if npz is not None and os.path.exists(npz):  # the pictures are read, and a bad npz refused, before the model is built
+        with np.load(npz) as z:
+            if "frames_u8" in z.files or "frames_yuv" in z.files:
+                pics = pictures(z, args, npz, lead=1 if args.video is not None else 2)
     cfg = assert_and_infer_cfg(load_yaml(args.cfg_file, ["NUM_GPUS", 1] + list(args.opts or [])))
     if not torch.cuda.is_available():
         raise SystemExit("tools/predict.py needs an MI355X: there is no CPU fallback")
@@ -180,18 +213,18 @@ def main(argv=None):
     if args.video is not None:
         attention_track = bool(args.attention_track or args.attention_overlay is not None)
         with np.load(args.video) as z:
-            missing = [k for k in VIDEO_KEYS if k not in z.files]
+            missing = [k for k in VIDEO_KEYS if k not in z.files and (k != "frames_u8" or "frames_yuv" not in z.files)]
             if missing:
                 raise SystemExit(f"{args.video} lacks {missing}: a video holds {list(VIDEO_KEYS)} and optionally fps")
             fps = args.fps if args.fps is not None else (float(z["fps"]) if "fps" in z.files else None)
             rate = source_rate(z, args, args.video)
-            out = predictor.predict_video(torch.from_numpy(z["frames_u8"]).to(dev), waveform(z, rate, dev), sample_rate=rate,
+            frames, fmt = torch.from_numpy(pics[0]).to(dev), pics[1]
+            out = predictor.predict_video(frames, waveform(z, rate, dev), sample_rate=rate,
                                           fps=fps, stride=args.stride, overlay=bool(args.overlay or args.overlay_dir),
-                                          fill=args.fill, max_gap=args.max_gap, attention_track=attention_track)
+                                          fill=args.fill, max_gap=args.max_gap, attention_track=attention_track, **fmt)
             if args.attention_overlay is not None:
                 head = None if args.attention_overlay == "mean" else int(args.attention_overlay)
-                out["attention_overlay"] = predictor.render_attention_track(torch.from_numpy(z["frames_u8"]).to(dev), out, head=head,
-                                                                            points=out["points"])
+                out["attention_overlay"] = predictor.render_attention_track(frames, out, head=head, points=out["points"], **fmt)
         keys = ("points", "peak", "count", "rescaled", "heatmaps") + (("points_source", "overlay") if "overlay" in out else ())
         keys += ("neighbours", "filled") if args.fill is not None else ()
         if attention_track:
@@ -209,6 +242,8 @@ def main(argv=None):
                   "covered_frames": int((arrays["count"] > 0).sum()),
                   "shapes": {k: list(v.shape) for k, v in arrays.items()}}
         record.update({k: int(v) for k, v in rates.items()})
+        if fmt:
+            record["pixel_format"] = fmt["pixel_format"]
         if args.fill is not None:
             record.update({"fill": args.fill, "max_gap": int(out["max_gap"]), "filled_frames": int(arrays["filled"].sum())})
         if attention_track:
@@ -220,15 +255,15 @@ def main(argv=None):
         return
     if args.clip is not None:
         with np.load(args.clip) as z:
-            missing = [k for k in CLIP_KEYS if k not in z.files]
+            missing = [k for k in CLIP_KEYS if k not in z.files and (k != "frames_u8" or "frames_yuv" not in z.files)]
             if missing:
                 raise SystemExit(f"{args.clip} lacks {missing}: a clip holds {list(CLIP_KEYS)}")
-            frames_u8 = torch.from_numpy(z["frames_u8"]).to(dev)
+            frames_u8, fmt = torch.from_numpy(pics[0]).to(dev), pics[1]
             rate = source_rate(z, args, args.clip)
             out = predictor.predict(frames_u8, waveform(z, rate, dev), torch.from_numpy(z["frames_idx"]).float().to(dev),
-                                    float(z["frame_length"]), attention=attention, sample_rate=rate)
+                                    float(z["frame_length"]), attention=attention, sample_rate=rate, **fmt)
         if args.attention_dir is not None:
-            write_attention(predictor, frames_u8, out, args.attention_dir)
+            write_attention(predictor, frames_u8, out, args.attention_dir, fmt)
         source = args.clip
     else:
         from csts_amd import train as T
@@ -236,7 +271,7 @@ def main(argv=None):
                                   spatial=T.spatial_config(cfg, train=False))
         out = predictor.predict_batch(batch, attention=attention)
         source = f"synthetic_batch(seed={args.seed})"
-        rate = None
+        rate, fmt = None, {}
     keys = ("points", "peak", "rescaled", "heatmaps")
     if attention:
         keys += ("audio_attention", "audio_attention_mean", "attention_maps", "attention_range", "temporal_attention")
@@ -246,6 +281,8 @@ def main(argv=None):
     record = {"_type": "predict", "checkpoint": predictor.checkpoint_path, "source": source, "graph": predictor.graph,
               "out": args.out, "shapes": {k: list(v.shape) for k, v in arrays.items()}}
     record.update({k: int(v) for k, v in rates.items()})
+    if fmt:
+        record["pixel_format"] = fmt["pixel_format"]
     print("json_stats: " + json.dumps(record), flush=True)
 
 
