@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <vector>
 
 namespace {
@@ -46,35 +47,6 @@ __device__ __forceinline__ void st4(void* p, int dt, int64_t i, const float (&o)
     a[0] = (bf16)o[0]; a[1] = (bf16)o[1]; a[2] = (bf16)o[2]; a[3] = (bf16)o[3];
     *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16*>(p) + i) = a;
   }
-}
-
-// 8 consecutive channels (16-byte bf16 / 2 x 16-byte f32 accesses); offsets are 32-bit inside one batch element
-__device__ __forceinline__ void ld8v(const void* p, int dt, int i, float (&o)[8]) {
-  if (dt == CSTS_F32) {
-    const float4* q = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p) + i);
-    const float4 a = q[0], b = q[1];
-    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-  } else {
-    const bf16x8 v = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const bf16*>(p) + i);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (float)v[j];
-  }
-}
-__device__ __forceinline__ const void* batch_ptr(const void* p, int dt, int64_t off) {
-  return dt == CSTS_F32 ? (const void*)(reinterpret_cast<const float*>(p) + off) : (const void*)(reinterpret_cast<const bf16*>(p) + off);
-}
-__device__ __forceinline__ void* batch_ptr(void* p, int dt, int64_t off) {
-  return dt == CSTS_F32 ? (void*)(reinterpret_cast<float*>(p) + off) : (void*)(reinterpret_cast<bf16*>(p) + off);
-}
-
-// weights staged as wl[tap][HD] (fp32) so that lanes read consecutive channels
-__device__ __forceinline__ void stage_weights(const float* __restrict__ w, float* wl, int HD) {
-  const int nthr = blockDim.x * blockDim.y, tid = threadIdx.y * blockDim.x + threadIdx.x;
-  for (int i = tid; i < HD * 27; i += nthr) {   // consecutive LDS addresses (conflict-free), strided L2-cached reads
-    const int k = i / HD, c = i - k * HD;
-    wl[i] = w[c * 27 + k];
-  }
-  __syncthreads();
 }
 
 // The depthwise kernels keep their tap loads free of control flow AND of dtype conversion: a batch of raw loads
@@ -113,30 +85,6 @@ __device__ __forceinline__ void decomp(int bt, int ntok, int H, int W, int& b, i
   t = o / H;
 }
 
-template <bool F32> struct Raw4;                       // 4 consecutive channels, unconverted
-template <> struct Raw4<true> { float4 v; };
-template <> struct Raw4<false> { uint2 v; };
-template <bool F32> __device__ __forceinline__ Raw4<F32> raw4_load(const void* base, int i) {
-  Raw4<F32> r;
-  if constexpr (F32) r.v = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(base) + i);
-  else r.v = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16*>(base) + i);
-  return r;
-}
-template <bool F32> __device__ __forceinline__ void raw4_cvt(const Raw4<F32>& r, float (&o)[4]) {
-  if constexpr (F32) { o[0] = r.v.x; o[1] = r.v.y; o[2] = r.v.z; o[3] = r.v.w; }
-  else {
-    o[0] = h16_lo(r.v.x); o[1] = h16_hi(r.v.x);
-    o[2] = h16_lo(r.v.y); o[3] = h16_hi(r.v.y);
-  }
-}
-template <bool F32> __device__ __forceinline__ void st4t(void* base, int i, const float (&o)[4]) {
-  if constexpr (F32) *reinterpret_cast<float4*>(reinterpret_cast<float*>(base) + i) = make_float4(o[0], o[1], o[2], o[3]);
-  else {
-    bf16x4 a;
-    a[0] = (bf16)o[0]; a[1] = (bf16)o[1]; a[2] = (bf16)o[2]; a[3] = (bf16)o[3];
-    *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16*>(base) + i) = a;
-  }
-}
 template <bool F32> __device__ __forceinline__ const void* bptr(const void* p, int64_t off) {
   if constexpr (F32) return reinterpret_cast<const float*>(p) + off;
   else return reinterpret_cast<const bf16*>(p) + off;
@@ -146,58 +94,52 @@ template <bool F32> __device__ __forceinline__ void* bptr(void* p, int64_t off) 
   else return reinterpret_cast<bf16*>(p) + off;
 }
 
-template <bool F32> struct Raw8;
-template <> struct Raw8<true> { float4 a, b; };
-template <> struct Raw8<false> { uint4 a; };
-template <bool F32> __device__ __forceinline__ Raw8<F32> raw8_load(const void* base, int i) {
-  Raw8<F32> r;
+// V = 4, 8 or 12 consecutive channels of one token as the raw words of the loads (16-bit: two channels per word), converted
+// only after a whole batch of them is in flight.  fp32: V / 4 16-byte accesses.  16-bit: ONE 16-byte access for 8 channels
+// (the 8-byte form kept the vector-memory path at about half rate -- 18..27 tap loads per output make these kernels bound
+// by the L1/TA path, not by HBM), 8-byte pieces for 4 and 12 (a lane's 12 channels start at a multiple of 24 bytes).
+template <int V, bool F32> struct Raw { unsigned w[F32 ? V : V / 2]; };
+template <int V, bool F32> __device__ __forceinline__ Raw<V, F32> raw_load(const void* base, int i) {
+  Raw<V, F32> r;
   if constexpr (F32) {
-    const float4* q = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(base) + i);
-    r.a = q[0]; r.b = q[1];
+    const uint4* q = reinterpret_cast<const uint4*>(reinterpret_cast<const float*>(base) + i);
+#pragma unroll
+    for (int k = 0; k < V / 4; ++k) { const uint4 a = q[k]; r.w[4 * k] = a.x; r.w[4 * k + 1] = a.y; r.w[4 * k + 2] = a.z; r.w[4 * k + 3] = a.w; }
+  } else if constexpr (V == 8) {
+    const uint4 a = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(base) + i);
+    r.w[0] = a.x; r.w[1] = a.y; r.w[2] = a.z; r.w[3] = a.w;
   } else {
-    r.a = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(base) + i);
+    const uint2* q = reinterpret_cast<const uint2*>(reinterpret_cast<const bf16*>(base) + i);
+#pragma unroll
+    for (int k = 0; k < V / 4; ++k) { const uint2 a = q[k]; r.w[2 * k] = a.x; r.w[2 * k + 1] = a.y; }
   }
   return r;
 }
-template <bool F32> __device__ __forceinline__ void raw8_cvt(const Raw8<F32>& r, float (&o)[8]) {
-  if constexpr (F32) {
-    o[0] = r.a.x; o[1] = r.a.y; o[2] = r.a.z; o[3] = r.a.w; o[4] = r.b.x; o[5] = r.b.y; o[6] = r.b.z; o[7] = r.b.w;
-  } else {
-    o[0] = h16_lo(r.a.x); o[1] = h16_hi(r.a.x);
-    o[2] = h16_lo(r.a.y); o[3] = h16_hi(r.a.y);
-    o[4] = h16_lo(r.a.z); o[5] = h16_hi(r.a.z);
-    o[6] = h16_lo(r.a.w); o[7] = h16_hi(r.a.w);
+template <int V, bool F32> __device__ __forceinline__ void raw_cvt(const Raw<V, F32>& r, float (&o)[V]) {
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    if constexpr (F32) o[j] = __uint_as_float(r.w[j]);
+    else o[j] = (j & 1) ? h16_hi(r.w[j >> 1]) : h16_lo(r.w[j >> 1]);
   }
 }
-template <bool F32> __device__ __forceinline__ void st8t(void* base, int64_t i, const float (&o)[8]) {
+template <int V, bool F32> __device__ __forceinline__ void raw_store(void* base, int64_t i, const float (&o)[V]) {
   if constexpr (F32) {
     float4* q = reinterpret_cast<float4*>(reinterpret_cast<float*>(base) + i);
-    q[0] = make_float4(o[0], o[1], o[2], o[3]);
-    q[1] = make_float4(o[4], o[5], o[6], o[7]);
-  } else {
+#pragma unroll
+    for (int k = 0; k < V / 4; ++k) q[k] = make_float4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
+  } else if constexpr (V == 8) {
     bf16x8 v;
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = (bf16)o[j];
     *reinterpret_cast<bf16x8*>(reinterpret_cast<bf16*>(base) + i) = v;
+  } else {
+    bf16x4 v[V / 4];
+#pragma unroll
+    for (int j = 0; j < V; ++j) v[j >> 2][j & 3] = (bf16)o[j];
+    bf16x4* q = reinterpret_cast<bf16x4*>(reinterpret_cast<bf16*>(base) + i);
+#pragma unroll
+    for (int k = 0; k < V / 4; ++k) q[k] = v[k];
   }
-}
-
-// V consecutive channels per thread: 4 (fp32 tensors: 16-byte accesses) or 8 (bf16 tensors: 16-byte accesses; the 8-byte
-// bf16x4 form kept the vector-memory path at about half rate -- 18..27 tap loads per output make these kernels bound by
-// the L1/TA path, not by HBM)
-template <int V, bool F32> struct RawV { typedef Raw4<F32> T; };
-template <bool F32> struct RawV<8, F32> { typedef Raw8<F32> T; };
-template <int V, bool F32> __device__ __forceinline__ typename RawV<V, F32>::T rawv_load(const void* base, int i) {
-  if constexpr (V == 8) return raw8_load<F32>(base, i);
-  else return raw4_load<F32>(base, i);
-}
-template <int V, bool F32> __device__ __forceinline__ void rawv_cvt(const typename RawV<V, F32>::T& r, float (&o)[V]) {
-  if constexpr (V == 8) raw8_cvt<F32>(r, o);
-  else raw4_cvt<F32>(r, o);
-}
-template <int V, bool F32> __device__ __forceinline__ void stvt(void* base, int i, const float (&o)[V]) {
-  if constexpr (V == 8) st8t<F32>(base, i, o);
-  else st4t<F32>(base, i, o);
 }
 // acc[j] += v[j] * wl[j]  for V channels (wl: 16-byte aligned row of the staged weights)
 template <int V> __device__ __forceinline__ void fmav(float (&acc)[V], const float (&v)[V], const float* wrow) {
@@ -218,12 +160,11 @@ constexpr int WPAD = 4;
 // Coalesced global reads, 12 per thread IN FLIGHT before the first LDS store (a plain load -> store loop waits for every
 // load on its own: 11 round trips in a row for a 96-channel table on 256 threads, and this table is the first thing every
 // workgroup of the stencil kernels needs); the (conflicting) transposition is paid in LDS.
-// SPLIT8 (pool_ln_fwd_kernel: a lane owns 8 consecutive channels and reads them as two 16-byte pieces): inside a tap row the
-// FIRST four channels of every 8-channel group are stored next to each other, then all the second fours -- channel 8 i + j sits
-// at 4 i + j (j < 4) or HD / 2 + 4 i + j - 4 -- so that each of the two ds_read_b128 of a tap is one contiguous run over the
-// lanes (the straight layout put consecutive lanes 32 bytes apart: two lanes per bank pair on every read, 3.6 conflict cycles
-// per LDS instruction by SQ_LDS_BANK_CONFLICT / SQ_INSTS_LDS).
-template <bool SPLIT8 = false>
+// The rows keep the channels in their natural order although a lane of the pool + LayerNorm kernel that reads its 8 or 12
+// channels as 16-byte pieces then conflicts with its neighbour (3.6 conflict cycles per LDS instruction): a row layout that
+// made every ds_read_b128 one contiguous run over the lanes took that to 0.5 and the kernel 8-10 % SLOWER (17.4 -> 19.1 us
+// at the 384-channel stage, tools/pool_ln_bench.py) -- the kernel is bound by its dependent global-load rounds, and the
+// permuted staging costs every workgroup more than the conflicts did.
 __device__ __forceinline__ void stage_weight_rows(const float* __restrict__ w, float* wl, int HD, int nthr, int tid) {
   const int n = HD * 27;
   // (channel, tap) of element i = tid + u * nthr WITHOUT a division per element (the stencil kernels are bound by VALU
@@ -240,7 +181,7 @@ __device__ __forceinline__ void stage_weight_rows(const float* __restrict__ w, f
     }
 #pragma unroll
     for (int u = 0; u < 12; ++u) {
-      if (base + u * nthr < n) wl[k * (HD + WPAD) + (SPLIT8 ? ((c & 4) ? (HD >> 1) + ((c >> 3) << 2) + (c & 3) : ((c >> 3) << 2) + (c & 3)) : c)] = v[u];
+      if (base + u * nthr < n) wl[k * (HD + WPAD) + c] = v[u];
       k += dr; c += dq;
       if (k >= 27) { k -= 27; ++c; }
     }
@@ -250,6 +191,14 @@ __device__ __forceinline__ void stage_weight_rows(const float* __restrict__ w, f
 __device__ __forceinline__ void stage_weights_z(const float* __restrict__ w, float* wl, int HD) {
   stage_weight_rows(w, wl, HD, blockDim.x * blockDim.y, threadIdx.y * blockDim.x + threadIdx.x);
   __syncthreads();
+}
+constexpr size_t staged_bytes(int HD, int tables = 1) { return (size_t)tables * (HD + WPAD) * 28 * sizeof(float); }
+
+// Tap i = o * s - 1 + k of an axis of n positions: whether it lies inside the grid, and its position CLAMPED into the grid
+// (the load goes ahead either way, from an address of the tensor itself, and meets the zero weight row).
+__device__ __forceinline__ int tap_at(int i, int n, bool& ok) {
+  ok = (unsigned)i < (unsigned)n;
+  return min(max(i, 0), n - 1);
 }
 
 // coarse[b,o,c] = sum_k fine[b, o*s-1+k, c] * w[c%HD][k]          (V channels per thread)
@@ -275,10 +224,9 @@ __global__ __launch_bounds__(256, CSTS_DW_WAVES) void dwconv_strided_kernel(RowG
     bool tv[3], hv[3], xv[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      const int t = ot * g.st - 1 + k, h = oh * g.sh - 1 + k, x = ow * g.sw - 1 + k;
-      tv[k] = (unsigned)t < (unsigned)g.Tf; tof[k] = min(max(t, 0), g.Tf - 1) * g.Hf * g.Wf * fts;
-      hv[k] = (unsigned)h < (unsigned)g.Hf; hof[k] = min(max(h, 0), g.Hf - 1) * g.Wf * fts;
-      xv[k] = (unsigned)x < (unsigned)g.Wf; xof[k] = min(max(x, 0), g.Wf - 1) * fts + c;
+      tof[k] = tap_at(ot * g.st - 1 + k, g.Tf, tv[k]) * g.Hf * g.Wf * fts;
+      hof[k] = tap_at(oh * g.sh - 1 + k, g.Hf, hv[k]) * g.Wf * fts;
+      xof[k] = tap_at(ow * g.sw - 1 + k, g.Wf, xv[k]) * fts + c;
     }
     const void* fb = bptr<FF32>(fine, (int64_t)b * g.f_bs);
     float acc[V];
@@ -286,35 +234,37 @@ __global__ __launch_bounds__(256, CSTS_DW_WAVES) void dwconv_strided_kernel(RowG
     for (int j = 0; j < V; ++j) acc[j] = 0.f;
 #pragma unroll
     for (int kt = 0; kt < 3; ++kt) {
-      typename RawV<V, FF32>::T raw[9];
+      Raw<V, FF32> raw[9];
 #pragma unroll
       for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
-        for (int kw = 0; kw < 3; ++kw) raw[kh * 3 + kw] = rawv_load<V, FF32>(fb, tof[kt] + hof[kh] + xof[kw]);
+        for (int kw = 0; kw < 3; ++kw) raw[kh * 3 + kw] = raw_load<V, FF32>(fb, tof[kt] + hof[kh] + xof[kw]);
 #pragma unroll
       for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw) {
           const int tap = (tv[kt] && hv[kh] && xv[kw]) ? kt * 9 + kh * 3 + kw : 27;
           float v[V];
-          rawv_cvt<V, FF32>(raw[kh * 3 + kw], v);
+          raw_cvt<V, FF32>(raw[kh * 3 + kw], v);
           fmav<V>(acc, v, &wl[tap * (g.HD + WPAD) + cw]);
         }
     }
-    stvt<V, CF32>(bptr<CF32>(coarse, (int64_t)b * g.c_bs), (bt - b * ntok) * cts + c, acc);
+    raw_store<V, CF32>(bptr<CF32>(coarse, (int64_t)b * g.c_bs), (bt - b * ntok) * cts + c, acc);
   }
 }
 
 // Fused pooling: depthwise conv (as dwconv_strided) + LayerNorm(hd) of the result, for up to two tensors that share the
 // geometry (k and v of one attention: attention.py:104-116 -> pool_k + norm_k, pool_v + norm_v), in ONE launch.
-// A group of GL lanes owns one (batch, out-token, head, slot) item, 8 channels per lane (HD/8 lanes active), so the
-// LayerNorm statistics are a shuffle reduction inside the group and the pooled row never leaves registers before it is
-// normalised.  Writes the pre-LN row (saved for backward), the normalised row, mean and rstd.
-#ifdef CSTS_POOLLN_SPLIT8
-constexpr bool POOLLN_SPLIT8 = true;
-#else
-constexpr bool POOLLN_SPLIT8 = false;
-#endif
+// A group of GL lanes owns one (batch, out-token, head, slot) item, V channels per lane, so the LayerNorm statistics are a
+// shuffle reduction inside the group and the pooled row never leaves registers before it is normalised.  Writes the pre-LN
+// row (saved for backward), the normalised row, mean and rstd.
+//   V = 8 : any head dim; the HD / 8 first lanes of a group of 16 (HD <= 128) or 32 are active, the others shadow the last
+//           active one (their loads stay in range) and are masked out of the sums and the stores.
+//   V = 12: head dims 96 / 192 = 8 / 16 lanes per item, every lane active and no mask (with 8 channels per lane a 96-wide head
+//           keeps 12 of its 16 lanes busy), and 32 / 16 items per workgroup instead of 16 / 8: the 384-channel stage's launches
+//           are 512 workgroups, ONE round at three workgroups per CU, instead of 1024 = 1.33 rounds.
+// Same arithmetic per channel and the same order of taps in both: bit-identical conv rows; the LayerNorm sums run over a
+// different lane tree (8 / 16 lanes of 12 instead of 16 / 32 of 8): equal to rounding.
 #ifndef POOL_LN_WGS
 #define POOL_LN_WGS 3      // workgroups per CU the register budget is set for.  Round 5: 3 (168 registers, ~no spills) instead of 4 (128 registers,
                            // 8-12 spilled): -0.19 ms per step once the index arithmetic had shrunk (profiles/r5_stencil_ab.txt); 2: -0.14 ms
@@ -329,291 +279,120 @@ struct PoolLnSlots {
   float* mean[2];
   float* rstd[2];
 };
-template <int GL, bool F32>
-__global__ __launch_bounds__(256, POOL_LN_WGS) void pool_ln_fwd_kernel(RowGeom rg, PoolLnSlots sl, int nslots, float eps) {
-  extern __shared__ __attribute__((aligned(16))) float wl[];   // [nslots][28][HD]
+// Taps in flight: one temporal slice (9) at a time at POOL_LN_WGS workgroups per CU, or ALL27 -- one memory round trip per
+// item instead of three -- which needs the registers of TWO workgroups per CU (fp32 operands: 27 x 12 registers of taps do
+// not fit at all) and is therefore offered only where the launch is at most 512 workgroups, one round either way.
+// Measured alike on the large launches, 10-30 % faster on the small ones (profiles/r2_pool_ln_ab.txt).
+template <int GL, int V, bool F32, bool ALL27>
+__global__ __launch_bounds__(256, (ALL27 ? 2 : POOL_LN_WGS)) void pool_ln_fwd_kernel(RowGeom rg, PoolLnSlots sl, int nslots, float eps) {
+  extern __shared__ __attribute__((aligned(16))) float wl[];   // [nslots][28][HD + WPAD]
+  constexpr bool MASKED = V == 8;                              // V == 12: HD == 12 GL (host-checked)
+  constexpr int groups_per_block = 256 / GL;
   const Geom& g = rg.g;
   const int HD = g.HD, H = g.C / HD;
   const int lane_in = threadIdx.x % GL;
-  const bool active = lane_in * 8 < HD;
-  const int c8 = min(lane_in * 8, HD - 8);                    // idle lanes shadow the last active one (loads stay in range)
-  const int groups_per_block = blockDim.x / GL;
+  const bool active = !MASKED || lane_in * V < HD;
+  const int cl = MASKED ? min(lane_in * V, HD - V) : lane_in * V;
   const int ntok = g.Tc * g.Hc * g.Wc;
   const int per_slot = g.B * ntok * H;
   const int total = per_slot * nslots;
   const int fts = (int)g.f_ts, cts = (int)g.c_ts;
   const float invHD = 1.f / HD;
-  // -DCSTS_POOLLN_EARLY_LOADS (round 5, measured and NOT kept): the tap loads of the workgroup's first items in flight while the weight
-  // tables are staged (the loads do not depend on the weights).  With the staging inside the item loop the kernel spills 30-36 registers
-  // instead of 8-12 at its 128-register budget and runs 25-35 % SLOWER per launch, +0.37 ms per step (profiles/r5_stencil_ab.txt).
-  bool staged = false;
-  auto stage = [&]() {   // both slots' weights (tap-major, one zero row each)
-    // POOLLN_SPLIT8 (round 4, -DCSTS_POOLLN_SPLIT8): the conflict-free row layout took SQ_LDS_BANK_CONFLICT / SQ_INSTS_LDS from 3.56
-    // to 0.53 and made the kernel 8-10 % SLOWER (tools/pool_ln_bench.py: 17.4 -> 19.1 us at the 384-channel stage): the kernel is
-    // bound by its dependent global-load rounds, and the permuted staging costs every workgroup more than the conflicts did.  Off.
-    for (int s2 = 0; s2 < nslots; ++s2) stage_weight_rows<POOLLN_SPLIT8>(sl.w[s2], wl + s2 * 28 * (HD + WPAD), HD, blockDim.x, threadIdx.x);
-    __syncthreads();
-    staged = true;
-  };
-#ifndef CSTS_POOLLN_EARLY_LOADS               // default: tables staged in front of the first tap loads
-  stage();
-#endif
-  const int item0 = blockIdx.x * groups_per_block + threadIdx.x / GL;
-  // every thread runs the first pass (an item past the end is clamped and only not stored): the barrier inside stage() is then reached
-  // by the whole workgroup at the same place
-  for (int item_raw = item0, pass = 0; pass == 0 || item_raw < total; item_raw += gridDim.x * groups_per_block, ++pass) {
-    const bool live = item_raw < total;
-    const int item = min(item_raw, total - 1);
-    const int slot = item >= per_slot ? 1 : 0;            // (nslots <= 2)
-    int r = item - slot * per_slot;
-    const int bt = fdiv(r, rg.dHeads);
-    const int head = r - bt * H;
-    int b, ot, oh, ow;
-    decompf(bt, rg.dNc, rg.dHc, rg.dWc, b, ot, oh, ow);
-    const int c = head * HD + c8;
-    int hof[3], xof[3];
-    bool hv[3], xv[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-#ifdef CSTS_POOLLN_SHIFT
-      const int h = (oh << rg.lh) - 1 + k, x = (ow << rg.lw) - 1 + k;
-#else
-      const int h = oh * g.sh - 1 + k, x = ow * g.sw - 1 + k;
-#endif
-      hv[k] = (unsigned)h < (unsigned)g.Hf; hof[k] = min(max(h, 0), g.Hf - 1) * g.Wf * fts;
-      xv[k] = (unsigned)x < (unsigned)g.Wf; xof[k] = min(max(x, 0), g.Wf - 1) * fts + c;
-    }
-    const void* fb = bptr<F32>(sl.fine[slot], (int64_t)b * g.f_bs);
-    const float* wls = wl + slot * 28 * (HD + WPAD) + (POOLLN_SPLIT8 ? (c8 >> 1) : c8);      // SPLIT8 layout: first fours at 4 i, second fours at HD / 2 + 4 i
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    // 9 taps (one temporal slice) in flight at a time: a 128-register budget, FOUR workgroups per CU, so the 1024-workgroup
-    // launches of the 384-channel stages are resident at once.  (All 27 taps at once -- one memory round trip per item
-    // instead of three -- needs 176 registers = two workgroups per CU = two rounds.  Measured alike: 27.9 vs 28.2 us for
-    // those launches, 10-30 % faster for the smaller ones; rocprofv3 kernel trace, profiles/r2_pool_ln_ab.txt.)
-#pragma unroll 1
-    for (int kt = 0; kt < 3; ++kt) {           // a real loop: unrolled, the scheduler hoists all 27 loads again and spills
-#ifdef CSTS_POOLLN_SHIFT
-      const int t = (ot << rg.lt) - 1 + kt;
-#else
-      const int t = ot * g.st - 1 + kt;
-#endif
-      const bool tvk = (unsigned)t < (unsigned)g.Tf;
-      const int tofk = min(max(t, 0), g.Tf - 1) * g.Hf * g.Wf * fts;
-      Raw8<F32> raw[9];
-#pragma unroll
-      for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw) raw[kh * 3 + kw] = raw8_load<F32>(fb, tofk + hof[kh] + xof[kw]);
-      if (!staged) stage();                    // first pass, first round: the tables arrive under these loads
-#pragma unroll
-      for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw) {
-          const int tap = (tvk && hv[kh] && xv[kw]) ? kt * 9 + kh * 3 + kw : 27;
-          const float4 w0 = *reinterpret_cast<const float4*>(&wls[tap * (HD + WPAD)]);
-          const float4 w1 = *reinterpret_cast<const float4*>(&wls[tap * (HD + WPAD) + (POOLLN_SPLIT8 ? (HD >> 1) : 4)]);
-          float v[8];
-          raw8_cvt<F32>(raw[kh * 3 + kw], v);
-          acc[0] += v[0] * w0.x; acc[1] += v[1] * w0.y; acc[2] += v[2] * w0.z; acc[3] += v[3] * w0.w;
-          acc[4] += v[4] * w1.x; acc[5] += v[5] * w1.y; acc[6] += v[6] * w1.z; acc[7] += v[7] * w1.w;
-        }
-    }
-    // the pre-LN row is stored in the activation dtype and the statistics are taken from the STORED values, exactly
-    // like the two-kernel path (conv -> round -> LayerNorm) and the reference (attention.py:37-47)
-    if constexpr (!F32) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] = (float)(bf16)acc[j];
-    }
-    float s1 = 0.f;
-    if (active) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s1 += acc[j];
-    }
-#pragma unroll
-    for (int o = GL / 2; o > 0; o >>= 1) s1 += __shfl_xor(s1, o, 64);
-    const float mu = s1 * invHD;
-    float s2 = 0.f;
-    if (active) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { const float d = acc[j] - mu; s2 += d * d; }
-    }
-#pragma unroll
-    for (int o = GL / 2; o > 0; o >>= 1) s2 += __shfl_xor(s2, o, 64);
-    const float rs = rsqrtf(s2 * invHD + eps);
-    if (active && live) {
-      const int64_t off = (int64_t)b * g.c_bs + (int64_t)(bt - b * ntok) * cts + c;
-      st8t<F32>(sl.conv[slot], off, acc);
-      const float4 g0 = *reinterpret_cast<const float4*>(sl.gamma[slot] + c8), g1 = *reinterpret_cast<const float4*>(sl.gamma[slot] + c8 + 4);
-      const float4 b0 = *reinterpret_cast<const float4*>(sl.beta[slot] + c8), b1 = *reinterpret_cast<const float4*>(sl.beta[slot] + c8 + 4);
-      float y[8];
-      y[0] = (acc[0] - mu) * rs * g0.x + b0.x; y[1] = (acc[1] - mu) * rs * g0.y + b0.y;
-      y[2] = (acc[2] - mu) * rs * g0.z + b0.z; y[3] = (acc[3] - mu) * rs * g0.w + b0.w;
-      y[4] = (acc[4] - mu) * rs * g1.x + b1.x; y[5] = (acc[5] - mu) * rs * g1.y + b1.y;
-      y[6] = (acc[6] - mu) * rs * g1.z + b1.z; y[7] = (acc[7] - mu) * rs * g1.w + b1.w;
-      st8t<F32>(sl.y[slot], off, y);
-      if (lane_in == 0) {
-        const int64_t row = (int64_t)bt * H + head;       // row index of the (B*N, H) x HD LayerNorm
-        sl.mean[slot][row] = mu;
-        sl.rstd[slot][row] = rs;
-      }
-    }
-  }
-}
-
-// Round 5: the same kernel with TWELVE channels per lane (head dims 96 / 192: 8 / 16 lanes per item, every lane active -- with 8 channels per lane
-// a 96-wide head keeps 12 of its 16 lanes busy -- and 32 / 16 items per workgroup instead of 16 / 8: the 384-channel stage's launches become 512
-// workgroups, ONE round at three workgroups per CU instead of 1024 = 1.33 rounds).  Same arithmetic per channel, same order of taps: bit-identical
-// conv rows; the LayerNorm sums run over a different lane tree (8 / 16 lanes of 12 instead of 16 / 32 of 8): equal to rounding.
-template <bool F32> struct Raw12;
-template <> struct Raw12<true> { float4 a, b, c; };
-template <> struct Raw12<false> { uint4 a; uint2 b; };
-template <bool F32> __device__ __forceinline__ Raw12<F32> raw12_load(const void* base, int i) {
-  Raw12<F32> r;
-  if constexpr (F32) {
-    const float4* q = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(base) + i);
-    r.a = q[0]; r.b = q[1]; r.c = q[2];
-  } else {
-    const char* q = reinterpret_cast<const char*>(reinterpret_cast<const bf16*>(base) + i);      // 24 k bytes: 8-byte aligned
-    uint2 lo = *reinterpret_cast<const uint2*>(q), mid = *reinterpret_cast<const uint2*>(q + 8);
-    r.a = make_uint4(lo.x, lo.y, mid.x, mid.y);
-    r.b = *reinterpret_cast<const uint2*>(q + 16);
-  }
-  return r;
-}
-template <bool F32> __device__ __forceinline__ void raw12_cvt(const Raw12<F32>& r, float (&o)[12]) {
-  if constexpr (F32) {
-    o[0] = r.a.x; o[1] = r.a.y; o[2] = r.a.z; o[3] = r.a.w; o[4] = r.b.x; o[5] = r.b.y; o[6] = r.b.z; o[7] = r.b.w;
-    o[8] = r.c.x; o[9] = r.c.y; o[10] = r.c.z; o[11] = r.c.w;
-  } else {
-    o[0] = h16_lo(r.a.x); o[1] = h16_hi(r.a.x); o[2] = h16_lo(r.a.y); o[3] = h16_hi(r.a.y);
-    o[4] = h16_lo(r.a.z); o[5] = h16_hi(r.a.z); o[6] = h16_lo(r.a.w); o[7] = h16_hi(r.a.w);
-    o[8] = h16_lo(r.b.x); o[9] = h16_hi(r.b.x); o[10] = h16_lo(r.b.y); o[11] = h16_hi(r.b.y);
-  }
-}
-template <bool F32> __device__ __forceinline__ void st12t(void* base, int64_t i, const float (&o)[12]) {
-  if constexpr (F32) {
-    float4* q = reinterpret_cast<float4*>(reinterpret_cast<float*>(base) + i);
-    q[0] = make_float4(o[0], o[1], o[2], o[3]);
-    q[1] = make_float4(o[4], o[5], o[6], o[7]);
-    q[2] = make_float4(o[8], o[9], o[10], o[11]);
-  } else {
-    bf16x4 v[3];
-#pragma unroll
-    for (int j = 0; j < 12; ++j) v[j >> 2][j & 3] = (bf16)o[j];
-    uint2* q = reinterpret_cast<uint2*>(reinterpret_cast<bf16*>(base) + i);                        // 8-byte aligned
-    q[0] = __builtin_bit_cast(uint2, v[0]); q[1] = __builtin_bit_cast(uint2, v[1]); q[2] = __builtin_bit_cast(uint2, v[2]);
-  }
-}
-
-// ALL27: all 27 taps of an item in flight at once (one memory round trip per item instead of three) at TWO workgroups per CU -- every launch of
-// this form is at most 512 workgroups, one round either way.
-template <int GL, bool F32, bool ALL27>
-__global__ __launch_bounds__(256, (ALL27 ? 2 : POOL_LN_WGS)) void pool_ln_fwd12_kernel(RowGeom rg, PoolLnSlots sl, int nslots, float eps) {
-  extern __shared__ __attribute__((aligned(16))) float wl[];   // [nslots][28][HD + WPAD]
-  const Geom& g = rg.g;
-  const int HD = g.HD, H = g.C / HD;                          // HD == 12 GL (host-checked)
-  const int lane_in = threadIdx.x % GL;
-  const int c12 = lane_in * 12;
-  constexpr int groups_per_block = 256 / GL;
-  const int ntok = g.Tc * g.Hc * g.Wc;
-  const int per_slot = g.B * ntok * H;
-  const int total = per_slot * nslots;
-  const int fts = (int)g.f_ts, cts = (int)g.c_ts;
-  const float invHD = 1.f / HD;
-  for (int s2 = 0; s2 < nslots; ++s2) stage_weight_rows<false>(sl.w[s2], wl + s2 * 28 * (HD + WPAD), HD, blockDim.x, threadIdx.x);
+  for (int s2 = 0; s2 < nslots; ++s2) stage_weight_rows(sl.w[s2], wl + s2 * 28 * (HD + WPAD), HD, blockDim.x, threadIdx.x);
   __syncthreads();
-  const int item0 = blockIdx.x * groups_per_block + threadIdx.x / GL;
-  for (int item = item0; item < total; item += gridDim.x * groups_per_block) {
+  // the lanes of a group share one item, so a group leaves the loop as a whole and the shuffles below stay inside it
+  for (int item = blockIdx.x * groups_per_block + threadIdx.x / GL; item < total; item += gridDim.x * groups_per_block) {
     const int slot = item >= per_slot ? 1 : 0;            // (nslots <= 2)
-    int r = item - slot * per_slot;
+    const int r = item - slot * per_slot;
     const int bt = fdiv(r, rg.dHeads);
     const int head = r - bt * H;
     int b, ot, oh, ow;
     decompf(bt, rg.dNc, rg.dHc, rg.dWc, b, ot, oh, ow);
-    const int c = head * HD + c12;
+    const int c = head * HD + cl;
     int hof[3], xof[3];
     bool hv[3], xv[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      const int h = oh * g.sh - 1 + k, x = ow * g.sw - 1 + k;
-      hv[k] = (unsigned)h < (unsigned)g.Hf; hof[k] = min(max(h, 0), g.Hf - 1) * g.Wf * fts;
-      xv[k] = (unsigned)x < (unsigned)g.Wf; xof[k] = min(max(x, 0), g.Wf - 1) * fts + c;
+      hof[k] = tap_at(oh * g.sh - 1 + k, g.Hf, hv[k]) * g.Wf * fts;
+      xof[k] = tap_at(ow * g.sw - 1 + k, g.Wf, xv[k]) * fts + c;
     }
     const void* fb = bptr<F32>(sl.fine[slot], (int64_t)b * g.f_bs);
-    const float* wls = wl + slot * 28 * (HD + WPAD) + c12;
-    float acc[12];
+    const float* wls = wl + slot * 28 * (HD + WPAD) + cl;
+    float acc[V];
 #pragma unroll
-    for (int j = 0; j < 12; ++j) acc[j] = 0.f;
-    auto slice_load = [&](int kt, Raw12<F32> (&raw)[9], bool& tvk) {
-      const int t = ot * g.st - 1 + kt;
-      tvk = (unsigned)t < (unsigned)g.Tf;
-      const int tofk = min(max(t, 0), g.Tf - 1) * g.Hf * g.Wf * fts;
+    for (int j = 0; j < V; ++j) acc[j] = 0.f;
+    auto slice_load = [&](int kt, Raw<V, F32> (&raw)[9], bool& tvk) {
+      const int tofk = tap_at(ot * g.st - 1 + kt, g.Tf, tvk) * g.Hf * g.Wf * fts;
 #pragma unroll
       for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
-        for (int kw = 0; kw < 3; ++kw) raw[kh * 3 + kw] = raw12_load<F32>(fb, tofk + hof[kh] + xof[kw]);
+        for (int kw = 0; kw < 3; ++kw) raw[kh * 3 + kw] = raw_load<V, F32>(fb, tofk + hof[kh] + xof[kw]);
     };
-    auto slice_mac = [&](int kt, const Raw12<F32> (&raw)[9], bool tvk) {
+    auto slice_mac = [&](int kt, const Raw<V, F32> (&raw)[9], bool tvk) {
 #pragma unroll
       for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw) {
           const int tap = (tvk && hv[kh] && xv[kw]) ? kt * 9 + kh * 3 + kw : 27;
-          const float* wr = &wls[tap * (HD + WPAD)];
-          const float4 w0 = *reinterpret_cast<const float4*>(wr), w1 = *reinterpret_cast<const float4*>(wr + 4), w2 = *reinterpret_cast<const float4*>(wr + 8);
-          float v[12];
-          raw12_cvt<F32>(raw[kh * 3 + kw], v);
-          acc[0] += v[0] * w0.x; acc[1] += v[1] * w0.y; acc[2] += v[2] * w0.z; acc[3] += v[3] * w0.w;
-          acc[4] += v[4] * w1.x; acc[5] += v[5] * w1.y; acc[6] += v[6] * w1.z; acc[7] += v[7] * w1.w;
-          acc[8] += v[8] * w2.x; acc[9] += v[9] * w2.y; acc[10] += v[10] * w2.z; acc[11] += v[11] * w2.w;
+          float v[V];
+          raw_cvt<V, F32>(raw[kh * 3 + kw], v);
+          fmav<V>(acc, v, &wls[tap * (HD + WPAD)]);
         }
     };
     if constexpr (ALL27) {
-      Raw12<F32> r0[9], r1[9], r2[9];
+      Raw<V, F32> r0[9], r1[9], r2[9];
       bool t0, t1, t2;
       slice_load(0, r0, t0); slice_load(1, r1, t1); slice_load(2, r2, t2);
       slice_mac(0, r0, t0); slice_mac(1, r1, t1); slice_mac(2, r2, t2);
     } else {
 #pragma unroll 1
-      for (int kt = 0; kt < 3; ++kt) {           // a real loop: one temporal slice (9 taps) in flight at a time, as in pool_ln_fwd_kernel
-        Raw12<F32> raw[9];
+      for (int kt = 0; kt < 3; ++kt) {           // a real loop: unrolled, the scheduler hoists all 27 loads again and spills
+        Raw<V, F32> raw[9];
         bool tvk;
         slice_load(kt, raw, tvk);
         slice_mac(kt, raw, tvk);
       }
     }
+    // the pre-LN row is stored in the activation dtype and the statistics are taken from the STORED values, exactly
+    // like the two-kernel path (conv -> round -> LayerNorm) and the reference (attention.py:37-47)
     if constexpr (!F32) {
 #pragma unroll
-      for (int j = 0; j < 12; ++j) acc[j] = (float)(bf16)acc[j];
+      for (int j = 0; j < V; ++j) acc[j] = (float)(bf16)acc[j];
     }
     float s1 = 0.f;
+    if (active) {
 #pragma unroll
-    for (int j = 0; j < 12; ++j) s1 += acc[j];
+      for (int j = 0; j < V; ++j) s1 += acc[j];
+    }
 #pragma unroll
     for (int o = GL / 2; o > 0; o >>= 1) s1 += __shfl_xor(s1, o, 64);
     const float mu = s1 * invHD;
     float s2 = 0.f;
+    if (active) {
 #pragma unroll
-    for (int j = 0; j < 12; ++j) { const float d = acc[j] - mu; s2 += d * d; }
+      for (int j = 0; j < V; ++j) { const float d = acc[j] - mu; s2 += d * d; }
+    }
 #pragma unroll
     for (int o = GL / 2; o > 0; o >>= 1) s2 += __shfl_xor(s2, o, 64);
     const float rs = rsqrtf(s2 * invHD + eps);
-    const int64_t off = (int64_t)b * g.c_bs + (int64_t)(bt - b * ntok) * cts + c;
-    st12t<F32>(sl.conv[slot], off, acc);
-    const float* gp = sl.gamma[slot] + c12;
-    const float* bp = sl.beta[slot] + c12;
-    float y[12];
+    if (active) {
+      const int64_t off = (int64_t)b * g.c_bs + (int64_t)(bt - b * ntok) * cts + c;
+      raw_store<V, F32>(sl.conv[slot], off, acc);
+      const float* gp = sl.gamma[slot] + cl;
+      const float* bp = sl.beta[slot] + cl;
+      float y[V];
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const float4 gq = *reinterpret_cast<const float4*>(gp + 4 * q), bq = *reinterpret_cast<const float4*>(bp + 4 * q);
-      y[4 * q + 0] = (acc[4 * q + 0] - mu) * rs * gq.x + bq.x; y[4 * q + 1] = (acc[4 * q + 1] - mu) * rs * gq.y + bq.y;
-      y[4 * q + 2] = (acc[4 * q + 2] - mu) * rs * gq.z + bq.z; y[4 * q + 3] = (acc[4 * q + 3] - mu) * rs * gq.w + bq.w;
-    }
-    st12t<F32>(sl.y[slot], off, y);
-    if (lane_in == 0) {
-      const int64_t row = (int64_t)bt * H + head;       // row index of the (B*N, H) x HD LayerNorm
-      sl.mean[slot][row] = mu;
-      sl.rstd[slot][row] = rs;
+      for (int q = 0; q < V / 4; ++q) {
+        const float4 gq = *reinterpret_cast<const float4*>(gp + 4 * q), bq = *reinterpret_cast<const float4*>(bp + 4 * q);
+        y[4 * q + 0] = (acc[4 * q + 0] - mu) * rs * gq.x + bq.x; y[4 * q + 1] = (acc[4 * q + 1] - mu) * rs * gq.y + bq.y;
+        y[4 * q + 2] = (acc[4 * q + 2] - mu) * rs * gq.z + bq.z; y[4 * q + 3] = (acc[4 * q + 3] - mu) * rs * gq.w + bq.w;
+      }
+      raw_store<V, F32>(sl.y[slot], off, y);
+      if (lane_in == 0) {
+        const int64_t row = (int64_t)bt * H + head;       // row index of the (B*N, H) x HD LayerNorm
+        sl.mean[slot][row] = mu;
+        sl.rstd[slot][row] = rs;
+      }
     }
   }
 }
@@ -678,22 +457,22 @@ __global__ __launch_bounds__(256, CSTS_DW_WAVES) void dwconv_transposed_kernel(R
     for (int j = 0; j < V; ++j) acc[j] = 0.f;
 #pragma unroll
     for (int a = 0; a < NT; ++a) {
-      typename RawV<V, CF32>::T raw[NH * NW];
+      Raw<V, CF32> raw[NH * NW];
 #pragma unroll
       for (int e = 0; e < NH; ++e)
 #pragma unroll
-        for (int f = 0; f < NW; ++f) raw[e * NW + f] = rawv_load<V, CF32>(cb, ot[a] + oh[e] + ow[f]);
+        for (int f = 0; f < NW; ++f) raw[e * NW + f] = raw_load<V, CF32>(cb, ot[a] + oh[e] + ow[f]);
 #pragma unroll
       for (int e = 0; e < NH; ++e)
 #pragma unroll
         for (int f = 0; f < NW; ++f) {
           const int tap = (vt[a] && vh[e] && vw[f]) ? kt[a] * 9 + kh[e] * 3 + kw[f] : 27;
           float v[V];
-          rawv_cvt<V, CF32>(raw[e * NW + f], v);
+          raw_cvt<V, CF32>(raw[e * NW + f], v);
           fmav<V>(acc, v, &wl[tap * (g.HD + WPAD) + cw]);
         }
     }
-    stvt<V, FF32>(bptr<FF32>(fine, (int64_t)b * g.f_bs), (bt - b * ntok) * fts + c, acc);
+    raw_store<V, FF32>(bptr<FF32>(fine, (int64_t)b * g.f_bs), (bt - b * ntok) * fts + c, acc);
   }
 }
 
@@ -730,22 +509,22 @@ __global__ __launch_bounds__(256, CSTS_DW_WAVES) void dwconv_transposed_s22_kern
     float o00[8], o01[8], o10[8], o11[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { o00[j] = 0.f; o01[j] = 0.f; o10[j] = 0.f; o11[j] = 0.f; }
-    Raw8<false> raw[NT][4];
+    Raw<8, false> raw[NT][4];
 #pragma unroll
     for (int a = 0; a < NT; ++a) {
       const int tb = ot[a] * g.Hc * g.Wc * cts;
-      raw[a][0] = raw8_load<false>(cb, tb + oh0 + ow0);
-      raw[a][1] = raw8_load<false>(cb, tb + oh0 + ow1);
-      raw[a][2] = raw8_load<false>(cb, tb + oh1 + ow0);
-      raw[a][3] = raw8_load<false>(cb, tb + oh1 + ow1);
+      raw[a][0] = raw_load<8, false>(cb, tb + oh0 + ow0);
+      raw[a][1] = raw_load<8, false>(cb, tb + oh0 + ow1);
+      raw[a][2] = raw_load<8, false>(cb, tb + oh1 + ow0);
+      raw[a][3] = raw_load<8, false>(cb, tb + oh1 + ow1);
     }
 #pragma unroll
     for (int a = 0; a < NT; ++a) {
       float i00[8], i01[8], i10[8], i11[8];
-      raw8_cvt<false>(raw[a][0], i00);
-      raw8_cvt<false>(raw[a][1], i01);
-      raw8_cvt<false>(raw[a][2], i10);
-      raw8_cvt<false>(raw[a][3], i11);
+      raw_cvt<8, false>(raw[a][0], i00);
+      raw_cvt<8, false>(raw[a][1], i01);
+      raw_cvt<8, false>(raw[a][2], i10);
+      raw_cvt<8, false>(raw[a][3], i11);
       // weight row of tap (kt, kh, kw); taps that do not exist read the all-zero row 27
       const int t9 = kt[a] * 9;
       auto wrow = [&](bool ok, int kh, int kw) { return &wl[(ok ? t9 + kh * 3 + kw : 27) * (g.HD + WPAD) + cw]; };
@@ -762,10 +541,10 @@ __global__ __launch_bounds__(256, CSTS_DW_WAVES) void dwconv_transposed_s22_kern
     }
     bf16* fb = fine + (int64_t)b * g.f_bs;
     const int f00 = ((ft * g.Hf + 2 * mh) * g.Wf + 2 * mw) * fts + c;
-    st8t<false>(fb, f00, o00);
-    st8t<false>(fb, f00 + fts, o01);
-    st8t<false>(fb, f00 + g.Wf * fts, o10);
-    st8t<false>(fb, f00 + g.Wf * fts + fts, o11);
+    raw_store<8, false>(fb, f00, o00);
+    raw_store<8, false>(fb, f00 + fts, o01);
+    raw_store<8, false>(fb, f00 + g.Wf * fts, o10);
+    raw_store<8, false>(fb, f00 + g.Wf * fts + fts, o11);
   }
 }
 
@@ -860,13 +639,8 @@ __device__ __forceinline__ void dwconv_wgrad_body(const Geom& g, const void* __r
         for (int j = 0; j < 9; ++j) {
           const int tap = kt * 9 + j;
           const unsigned r = (tv[kt] && hxv[j]) ? raw[tap] : 0u;
-#ifdef CSTS_SWG_FMA            // A/B build: fused multiply-add (one rounding less per tap; NOT bit-identical to the shipped form)
-          a0[tap] = __builtin_fmaf(h16_lo(r), c0, a0[tap]);
-          a1[tap] = __builtin_fmaf(h16_hi(r), c1, a1[tap]);
-#else
           a0[tap] += h16_lo(r) * c0;
           a1[tap] += h16_hi(r) * c1;
-#endif
         }
     }
     ow += tstep;
@@ -1286,6 +1060,10 @@ int grid_for(int64_t total) { return (int)std::min<int64_t>(cdiv(total, 256), 25
 // 2048 / 4096 -> 25.27, 1024 / 2048 -> 25.27: 4 staged workgroups per CU, the element-wise kernels effectively uncapped.
 int grid_for_staged(int64_t total) { return (int)std::min<int64_t>(cdiv(total, 256), 256 * 4); }
 
+// the pointer checks of every entry (per slot of the two-slot ones): all given, tensor bases 16-byte aligned
+bool all_set(std::initializer_list<const void*> ps) { return std::all_of(ps.begin(), ps.end(), [](const void* p) { return p != nullptr; }); }
+bool aligned16(std::initializer_list<const void*> ps) { return std::all_of(ps.begin(), ps.end(), [](const void* p) { return ((uintptr_t)p & 15) == 0; }); }
+
 int ilog2(int v) { if (v <= 0 || (v & (v - 1)) != 0) return -1; int l = 0; while ((1 << l) < v) ++l; return l; }   // -1: not a power of two
 bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
@@ -1338,14 +1116,14 @@ int fill_geom(const csts_dwconv_geom* a, RowGeom& rg) {
 extern "C" int csts_dwconv_strided(const csts_dwconv_geom* a, const void* fine, int fine_dt, const float* weight,
                                    void* coarse, int coarse_dt, hipStream_t stream) {
   CHECK_GEOM(a);
-  CSTS_REQUIRE(fine && weight && coarse, "null pointer");
-  CSTS_REQUIRE(((uintptr_t)fine & 15) == 0 && ((uintptr_t)coarse & 15) == 0, "tensors must be 16-byte aligned");
+  CSTS_REQUIRE(all_set({fine, weight, coarse}), "null pointer");
+  CSTS_REQUIRE(aligned16({fine, coarse}), "tensors must be 16-byte aligned");
   RowGeom rg; fill_geom(a, rg);
   const bool ff = fine_dt == CSTS_F32, cf = coarse_dt == CSTS_F32;
   const int vec = (!ff && !cf) ? 8 : VEC;     // bf16 on both sides: 8 channels (16 bytes) per thread
   const int64_t total = (int64_t)a->B * a->Tc * a->Hc * a->Wc * (a->C / vec);
   const dim3 grid(grid_for_staged(total)), block(256);
-  const size_t sm = (size_t)(a->HD + WPAD) * 28 * 4;
+  const size_t sm = staged_bytes(a->HD);
   if (ff && cf) hipLaunchKernelGGL((dwconv_strided_kernel<true, true, 4>), grid, block, sm, stream, rg, fine, weight, coarse);
   else if (!ff && !cf) hipLaunchKernelGGL((dwconv_strided_kernel<false, false, 8>), grid, block, sm, stream, rg, fine, weight, coarse);
   else if (ff) hipLaunchKernelGGL((dwconv_strided_kernel<true, false, 4>), grid, block, sm, stream, rg, fine, weight, coarse);
@@ -1360,8 +1138,8 @@ static int transposed_launch(const csts_dwconv_geom* a, int nslots, const void* 
   CSTS_REQUIRE(nslots == 1 || nslots == 2, "nslots must be 1 or 2");
   Slots2 sl{};
   for (int i = 0; i < nslots; ++i) {
-    CSTS_REQUIRE(fine[i] && weight[i] && coarse[i], "null pointer");
-    CSTS_REQUIRE(((uintptr_t)fine[i] & 15) == 0 && ((uintptr_t)coarse[i] & 15) == 0, "tensors must be 16-byte aligned");
+    CSTS_REQUIRE(all_set({fine[i], weight[i], coarse[i]}), "null pointer");
+    CSTS_REQUIRE(aligned16({fine[i], coarse[i]}), "tensors must be 16-byte aligned");
     sl.src[i] = coarse[i]; sl.dst[i] = fine[i]; sl.w[i] = weight[i];
   }
   RowGeom rg; fill_geom(a, rg);
@@ -1369,7 +1147,7 @@ static int transposed_launch(const csts_dwconv_geom* a, int nslots, const void* 
   const bool f32 = fine_dt == CSTS_F32;
   const int64_t total = (int64_t)a->B * a->Tf * a->Hf * a->Wf * (a->C / (f32 ? VEC : 8));   // bf16: 8 channels per thread
   const dim3 grid(grid_for_staged(total), nslots), block(256);
-  const size_t sm = (size_t)(a->HD + WPAD) * 28 * 4;
+  const size_t sm = staged_bytes(a->HD);
   auto nc = [](int st) { return st == 1 ? 3 : (st == 2 ? 2 : 1); };
   if (!f32 && a->sh == 2 && a->sw == 2 && a->Hf % 2 == 0 && a->Wf % 2 == 0) {   // 2 x 2 output blocks (see the kernel)
     const int64_t items = (int64_t)a->B * a->Tf * (a->Hf / 2) * (a->Wf / 2) * (a->C / 8);
@@ -1443,7 +1221,7 @@ static int wgrad_launch(const csts_dwconv_geom* a, int nslots, const void* const
   RowGeom rg; fill_geom(a, rg);
   WgSlots2 sl{};
   for (int i = 0; i < nslots; ++i) {
-    CSTS_REQUIRE(fine[i] && coarse[i], "null pointer");
+    CSTS_REQUIRE(all_set({fine[i], coarse[i]}), "null pointer");
     sl.fine[i] = fine[i]; sl.coarse[i] = coarse[i];
     sl.ws[i] = reinterpret_cast<float*>(workspace) + per_slot * i;
   }
@@ -1548,11 +1326,8 @@ extern "C" int csts_pool_ln_fwd(const csts_pool_ln_args* a, hipStream_t stream) 
   CSTS_REQUIRE(a->dt == CSTS_F32 || a->dt == CSTS_BF16, "bad dtype");
   PoolLnSlots sl{};
   for (int i = 0; i < a->nslots; ++i) {
-    CSTS_REQUIRE(a->fine[i] && a->weight[i] && a->gamma[i] && a->beta[i] && a->conv_out[i] && a->y[i] && a->mean[i] && a->rstd[i],
-                 "null pointer");
-    CSTS_REQUIRE(((uintptr_t)a->fine[i] & 15) == 0 && ((uintptr_t)a->conv_out[i] & 15) == 0 && ((uintptr_t)a->y[i] & 15) == 0 &&
-                     ((uintptr_t)a->gamma[i] & 15) == 0 && ((uintptr_t)a->beta[i] & 15) == 0,
-                 "tensors must be 16-byte aligned");
+    CSTS_REQUIRE(all_set({a->fine[i], a->weight[i], a->gamma[i], a->beta[i], a->conv_out[i], a->y[i], a->mean[i], a->rstd[i]}), "null pointer");
+    CSTS_REQUIRE(aligned16({a->fine[i], a->conv_out[i], a->y[i], a->gamma[i], a->beta[i]}), "tensors must be 16-byte aligned");
     sl.fine[i] = a->fine[i]; sl.w[i] = a->weight[i]; sl.gamma[i] = a->gamma[i]; sl.beta[i] = a->beta[i];
     sl.conv[i] = a->conv_out[i]; sl.y[i] = a->y[i]; sl.mean[i] = a->mean[i]; sl.rstd[i] = a->rstd[i];
   }
@@ -1561,36 +1336,19 @@ extern "C" int csts_pool_ln_fwd(const csts_pool_ln_args* a, hipStream_t stream) 
   // twelve channels per lane for the 96- / 192-wide heads (CSTS_POOLLN_CPL12=0: the 8-channel form for every head dim; 1, default: nine taps
   // in flight; 2: all 27).  Whole step, same box, 3 rounds: 19.92 -> 19.75 (1) / 19.77 (2) ms; another box 19.54 -> 19.46 (gpurun_out/r5ao, r5ap)
   static const int cpl12 = [] { const char* e = getenv("CSTS_POOLLN_CPL12"); return e ? atoi(e) : 1; }();
-  if (cpl12 > 0 && (gm->HD == 96 || gm->HD == 192) && (((uintptr_t)a->fine[0] | (uintptr_t)a->conv_out[0] | (uintptr_t)a->y[0]) & 7) == 0) {
-    const int gl12 = gm->HD / 12, gpb12 = 256 / gl12;
-    const dim3 grid12((unsigned)std::min<int64_t>(cdiv(items, gpb12), grid_for_staged((int64_t)1 << 40))), block12(256);
-    const size_t sm12 = (size_t)a->nslots * (gm->HD + WPAD) * 28 * 4;
-    const bool f32_12 = a->dt == CSTS_F32;
-#define CSTS_PL12(GLv, F32v, ALLv) hipLaunchKernelGGL((pool_ln_fwd12_kernel<GLv, F32v, ALLv>), grid12, block12, sm12, stream, rg, sl, a->nslots, a->eps)
-    const bool all27 = cpl12 >= 2 && grid12.x <= 512 && !f32_12;       // (fp32 operands: 27 x 12 registers of taps do not fit)
-    if (gl12 == 8) {
-      if (f32_12) { if (all27) CSTS_PL12(8, true, true); else CSTS_PL12(8, true, false); }
-      else { if (all27) CSTS_PL12(8, false, true); else CSTS_PL12(8, false, false); }
-    } else {
-      if (f32_12) { if (all27) CSTS_PL12(16, true, true); else CSTS_PL12(16, true, false); }
-      else { if (all27) CSTS_PL12(16, false, true); else CSTS_PL12(16, false, false); }
-    }
-#undef CSTS_PL12
-    CSTS_LAUNCH_CHECK();
-    return 0;
-  }
-  const int gl = gm->HD <= 128 ? 16 : 32;
-  const int gpb = 256 / gl;
-  const dim3 grid((unsigned)std::min<int64_t>(cdiv(items, gpb), grid_for_staged((int64_t)1 << 40))), block(256);
-  const size_t sm = (size_t)a->nslots * (gm->HD + WPAD) * 28 * 4;
   const bool f32 = a->dt == CSTS_F32;
-  if (gl == 16) {
-    if (f32) hipLaunchKernelGGL((pool_ln_fwd_kernel<16, true>), grid, block, sm, stream, rg, sl, a->nslots, a->eps);
-    else hipLaunchKernelGGL((pool_ln_fwd_kernel<16, false>), grid, block, sm, stream, rg, sl, a->nslots, a->eps);
-  } else {
-    if (f32) hipLaunchKernelGGL((pool_ln_fwd_kernel<32, true>), grid, block, sm, stream, rg, sl, a->nslots, a->eps);
-    else hipLaunchKernelGGL((pool_ln_fwd_kernel<32, false>), grid, block, sm, stream, rg, sl, a->nslots, a->eps);
-  }
+  const bool v12 = cpl12 > 0 && (gm->HD == 96 || gm->HD == 192);   // (its 8-byte pieces: bases and strides were checked above)
+  const int gl = v12 ? gm->HD / 12 : (gm->HD <= 128 ? 16 : 32);                  // lanes per item; 256 / gl items per workgroup
+  const dim3 grid(grid_for_staged(items * gl)), block(256);
+  const bool all27 = v12 && cpl12 >= 2 && grid.x <= 512 && !f32;
+  // exactly the forms that can be launched: (16 | 32 lanes) x 8 channels and (8 | 16 lanes) x 12 in both dtypes, ALL27 in 16 bits only
+#define POOL_LN_BOTH(GL, V) (f32 ? pool_ln_fwd_kernel<GL, V, true, false> : pool_ln_fwd_kernel<GL, V, false, false>)
+  void (*const kernel)(RowGeom, PoolLnSlots, int, float) =
+      all27 ? (gl == 8 ? pool_ln_fwd_kernel<8, 12, false, true> : pool_ln_fwd_kernel<16, 12, false, true>)
+      : v12 ? (gl == 8 ? POOL_LN_BOTH(8, 12) : POOL_LN_BOTH(16, 12))
+            : (gl == 16 ? POOL_LN_BOTH(16, 8) : POOL_LN_BOTH(32, 8));
+#undef POOL_LN_BOTH
+  hipLaunchKernelGGL(kernel, grid, block, staged_bytes(gm->HD, a->nslots), stream, rg, sl, a->nslots, a->eps);
   CSTS_LAUNCH_CHECK();
   return 0;
 }

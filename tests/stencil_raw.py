@@ -142,6 +142,14 @@ def weights(HD, seed, dev, scale=0.25):
     return (torch.randn(HD, 27, generator=torch.Generator().manual_seed(seed)) * scale).to(dev).contiguous()
 
 
+OUTPUTS = None                                   # a list (tools/stencil_digest.py): every run_* appends (name, output Region)
+
+
+def _record(name, *regions):
+    if OUTPUTS is not None:
+        OUTPUTS.extend((f"{name}[{i}]", r) for i, r in enumerate(regions))
+
+
 def _ratio(err, bar):
     """Worst |err| / bar; an error where the bar is zero counts as infinite."""
     r = torch.where(bar > 0, err / bar, torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
@@ -177,6 +185,7 @@ def run_strided(sp, f_dt, c_dt, dev, seed=1, fine_layout=("slot", 1), out_layout
     L.check(L.load().csts_dwconv_strided(C.byref(g), fine.ptr(), dt_code(f_dt), w.data_ptr(), out.ptr(), dt_code(c_dt), stream()),
             "csts_dwconv_strided")
     torch.cuda.synchronize()
+    _record("strided", out)
     ref, A = SR.conv_strided(sp.f5(fine.view().double()), w.double(), sp.stride)
     return [_conv_result(f"strided {sp}", out, ref, A)]
 
@@ -199,6 +208,7 @@ def run_transposed(sp, dt, dev, nslots=1, seed=2, coarse_layout=("slot", 1), out
                                          vp2(outs[0].ptr(), outs[1].ptr()), code, stream())
     L.check(rc, "csts_dwconv_transposed")
     torch.cuda.synchronize()
+    _record("transposed", *outs)
     res = []
     for i in range(nslots):
         ref, A = SR.conv_transposed(sp.c5(srcs[i].view().double()), ws[i].double(), sp.fthw, sp.stride)
@@ -230,6 +240,8 @@ def run_pool_ln(sp, dt, dev, nslots=1, seed=3, fine_slots=True, **kw):
         pa.conv_out[i], pa.y[i], pa.mean[i], pa.rstd[i] = convs[i].ptr(), ys[i].ptr(), means[i].ptr(), rstds[i].ptr()
     L.check(lib.csts_pool_ln_fwd(C.byref(pa), stream()), "csts_pool_ln_fwd")
     torch.cuda.synchronize()
+    for name, regions in (("conv_out", convs), ("y", ys), ("mean", means), ("rstd", rstds)):
+        _record(f"pool_ln {name}", *regions)
     res = []
     for i in range(nslots):
         ref, A = SR.conv_strided(sp.f5(fines[i].view().double()), ws[i].double(), sp.stride)
@@ -302,6 +314,8 @@ def run_wgrad(probs, mode, dev):
                                        dws[0].ptr() if mode == "dweight" else None, ws.ptr(), wsz, stream())
         L.check(rc, "csts_dwconv_wgrad")
         torch.cuda.synchronize()
+        _record(f"wgrad/{mode} workspace", ws)
+        _record(f"wgrad/{mode} dweight", *dws)
         for i, q in enumerate(pair):
             given = mode == "dweight" or (mode == "two" and i == 0)
             ok = ws.finite() and ws.guards_ok() and dws[i].guards_ok()
@@ -332,6 +346,7 @@ def run_wgrad_grouped(probs, dev, keep=None):
     table = torch.frombuffer(bytearray(bytes(image)), dtype=torch.uint8).to(dev)
     L.check(lib.csts_dwconv_wgrad_grouped(table.data_ptr(), len(probs), nblocks.value, code, stream()), "csts_dwconv_wgrad_grouped")
     torch.cuda.synchronize()
+    _record("wgrad/grouped workspace", *wss)
     if keep is not None:
         keep.extend(wss)
     return [p.result("wgrad/grouped", ws.view().flatten().double().view(-1, p.sp.HD * 27).sum(0), ws.finite() and ws.guards_ok())
@@ -388,3 +403,20 @@ def pool_cases(dt, dev, HD, **kw):
         for ns in (1, 2):
             res += run_pool_ln(Spec(2, HD * heads, HD, (3, 7, 5), (1, 2, 2)), dt, dev, nslots=ns, **kw)
     return res
+
+
+def wgrad_specs():
+    """HD 8 / 32 / 64 / 64 / 96 / 160 / 192: the 192-channel slab holds 24 / 6 / 3 / 2 / 2 / 1 / 1 heads.  (3, 7, 5) by (1, 2, 2), B = 2:
+    72 coarse tokens in 5 chunks of 15 (the last holds 12); one coarse token in total and two (lanes == 1); the (1, 3, 3) stride."""
+    g = ((3, 7, 5), (1, 2, 2))
+    return [Spec(2, 192, 8, *g), Spec(2, 192, 32, *g), Spec(2, 192, 64, *g), Spec(2, 128, 64, *g), Spec(2, 192, 96, *g),
+            Spec(2, 320, 160, *g), Spec(2, 384, 192, *g), Spec(1, 192, 96, (1, 1, 1), (1, 1, 1)), Spec(1, 96, 96, (2, 3, 3), (1, 8, 8)),
+            Spec(2, 64, 32, (3, 11, 8), (1, 3, 3))]
+
+
+def pool_tiny(dt, dev, HD, **kw):
+    """csts_pool_ln_fwd on one almost-empty workgroup (B = 1, one head, stride 1): a single item -- one token with 26 of its 27
+    taps outside the grid, one slot -- and six (fine (1, 1, 3), two slots), against 8 to 32 lane groups per workgroup: most
+    groups have no item at all."""
+    return (run_pool_ln(Spec(1, HD, HD, (1, 1, 1), (1, 1, 1)), dt, dev, nslots=1, **kw)
+            + run_pool_ln(Spec(1, HD, HD, (1, 1, 3), (1, 1, 1)), dt, dev, nslots=2, **kw))

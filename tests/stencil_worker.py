@@ -1,7 +1,7 @@
 """Child process of tests/test_gpu_stencil.py: the raw stencil checks of tests/stencil_raw.py in a process of its own, because
 what it varies is fixed per process -- csts_pool_ln_fwd reads CSTS_POOLLN_CPL12 once, and one process runs one 16-bit type.
-  argv[1] = "cpl0": the parent set CSTS_POOLLN_CPL12=0 -- head dims 96 and 192 through the generic pool_ln_fwd_kernel<16 / 32>;
-            "cpl2": CSTS_POOLLN_CPL12=2 -- the ALL27 form of the 12-lane kernel (16-bit operands only; fp32 stays on nine taps);
+  argv[1] = "cpl0": the parent set CSTS_POOLLN_CPL12=0 -- head dims 96 and 192 on 8 channels per lane, pool_ln_fwd_kernel<16 / 32, 8, ...>;
+            "cpl2": CSTS_POOLLN_CPL12=2 -- the ALL27 form of the 12-channel kernel (16-bit operands only; fp32 stays on nine taps);
             "fp16": libcsts_hip_f16.so (IEEE half) -- the ragged table and the stride-(., 2, 2) block cases with ordinary values,
                     values near the top of the fp16 range and channels in its subnormal range.
 Writes {case: {"conv": [results], "wgrad": [results]}} as JSON to argv[2]; the parent applies the bars."""
