@@ -8,6 +8,7 @@
 //   gaze_heatmaps    : 19x19 OpenCV-Gaussian gaze maps, clipped and renormalised      (ego4d_avgaze_forecast.py:318-326,404-422)
 // All HBM/latency-bound byte shuffling except the STFT, a 240-tap direct DFT per (frame, bin) from a twiddle table in LDS.
 #include "common.h"
+#include "stft_shared.h"
 
 namespace {
 
@@ -22,39 +23,16 @@ __global__ __launch_bounds__(256) void frames_normalize_kernel(const uint8_t* __
   }
 }
 
-// one workgroup per (frame, batch): the window's samples (times the periodic Hann window) in LDS, one thread per bin
+// one workgroup per (frame, batch): the window's samples (times the periodic Hann window) in LDS, one thread per bin.  The column
+// body is stft_logpower_column (stft_shared.h), which stream.hip runs too.
 __global__ __launch_bounds__(256) void stft_logpower_kernel(const float* __restrict__ wav, float* __restrict__ spec, int n,
                                                             int n_fft, int hop, int win, int nframes, float eps) {
   extern __shared__ float sm[];          // [win] windowed samples, [n_fft] cos, [n_fft] sin
-  float* xs = sm;
-  float* ct = sm + win;
-  float* st = ct + n_fft;
-  const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const int lpad = (n_fft - win) / 2;     // librosa.util.pad_center of the window inside n_fft
-  const int64_t s0 = (int64_t)f * hop + lpad - n_fft / 2;      // first waveform sample under the window (center=True)
-  for (int k = tid; k < win; k += 256) {
-    const int64_t s = s0 + k;
-    const float w = 0.5f - 0.5f * cospif(2.0f * (float)k / (float)win);     // scipy hann, fftbins=True
-    xs[k] = (s >= 0 && s < n) ? wav[(int64_t)b * n + s] * w : 0.f;
-  }
-  for (int m = tid; m < n_fft; m += 256) {
-    float sv, cv;
-    sincospif(2.0f * (float)m / (float)n_fft, &sv, &cv);
-    ct[m] = cv; st[m] = sv;
-  }
-  __syncthreads();
+  const int f = blockIdx.x, b = blockIdx.y;
   const int nbins = n_fft / 2 + 1;
-  for (int bin = tid; bin < nbins; bin += 256) {
-    float re = 0.f, im = 0.f;
-    int idx = (int)(((int64_t)bin * lpad) % n_fft);            // phase index (bin * j) mod n_fft, j = lpad + k
-    for (int k = 0; k < win; ++k) {
-      re += xs[k] * ct[idx];
-      im -= xs[k] * st[idx];
-      idx += bin;
-      if (idx >= n_fft) idx -= n_fft;
-    }
-    spec[((int64_t)b * nbins + bin) * nframes + f] = logf(re * re + im * im + eps);
-  }
+  const float* x = wav + (int64_t)b * n;
+  stft_logpower_column(sm, f, n_fft, hop, win, eps, [n](int64_t s) { return s >= 0 && s < n; }, [x](int64_t s) { return x[s]; },
+                       spec + (int64_t)b * nbins * nframes + f, nframes);
 }
 
 // out[b][0][t][bin][j] = spec[b][bin][center[b][t] - 128 + j]
@@ -133,7 +111,7 @@ extern "C" int csts_stft_logpower(const float* wav, float* spec, int B, int n, i
   CSTS_REQUIRE(wav && spec && B > 0 && n > 0 && n_fft > 0 && hop > 0 && win > 0 && win <= n_fft && n_fft <= 2048, "bad args");
   const int nframes = csts_stft_frames(n, n_fft, hop);
   CSTS_REQUIRE(nframes > 0, "signal shorter than one frame");
-  const size_t sm = (size_t)(win + 2 * n_fft) * sizeof(float);
+  const size_t sm = (size_t)stft_lds_floats(n_fft, win) * sizeof(float);
   hipLaunchKernelGGL(stft_logpower_kernel, dim3(nframes, B), dim3(256), sm, stream, wav, spec, n, n_fft, hop, win, nframes, eps);
   CSTS_LAUNCH_CHECK();
   return 0;

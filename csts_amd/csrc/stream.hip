@@ -1,0 +1,200 @@
+// Live-stream input (csts_amd/stream.py): frames and audio arrive in pieces of any size and the recording never ends, so what the
+// windows read lives in two device rings whose size does not depend on the length of the stream.
+//   stream_stft          : columns [f0, f1) of the log-power STFT of the endless signal, from the buffer that holds the samples they
+//                          need, into a spectrogram ring at column f mod ring_cols.  The column body is stft_logpower_column
+//                          (stft_shared.h), the one csts_stft_logpower runs: a column has the bits it has offline.
+//   stream_audio_windows : the T windows of 256 columns around global centre columns, read out of the ring across its wrap.
+//   stream_ingest(_yuv)  : the frames of one pushed chunk some window will read, sampled ONCE into a ring of normalised crops by
+//                          sample_rows / sample_rows_yuv (the pixel pass of csts_clip_sample) under one test-mode parameter row.
+//   stream_gather        : (B, 3, T, S, S) clips out of the crop ring by a slot table.
+// Every table is DEVICE memory read when the kernel runs; no atomics, no allocation, no synchronisation.
+#include "stft_shared.h"
+#include "yuv_shared.h"
+
+namespace {
+
+// grid (f1 - f0), 256 threads; dynamic LDS stft_lds_floats.  buf holds the samples [s_base, s_base + m); samples below 0, and with
+// n_total >= 0 those at or past n_total, are zero.  A sample the buffer does not hold reads nothing (the host refuses the launch).
+__global__ __launch_bounds__(256) void stream_stft_kernel(const float* __restrict__ buf, int64_t s_base, int64_t m, int64_t n_total,
+                                                          int64_t f0, float* __restrict__ ring, int ring_cols, int n_fft, int hop,
+                                                          int win, float eps) {
+  extern __shared__ float sm[];
+  const int64_t f = f0 + blockIdx.x;
+  const int64_t s_end = s_base + m;
+  stft_logpower_column(sm, f, n_fft, hop, win, eps,
+                       [=](int64_t s) { return s >= 0 && (n_total < 0 || s < n_total) && s >= s_base && s < s_end; },
+                       [=](int64_t s) { return buf[s - s_base]; }, ring + (int)(f % ring_cols), ring_cols);
+}
+
+// grid (blocks over nbins * width / V, B * T), 256 threads.  out[bt][bin][j] = ring[bin][(centers[bt] - width / 2 + j) mod ring_cols];
+// a window not wholly inside the live span [max(newest - ring_cols + 1, 0), newest] is NaN and reads nothing.
+// VEC: width % 4 == 0 and out 16-byte aligned, one float4 store per lane.
+template <bool VEC>
+__global__ __launch_bounds__(256) void stream_audio_windows_kernel(const float* __restrict__ ring, int ring_cols, int64_t newest,
+                                                                   const int64_t* __restrict__ centers, float* __restrict__ out,
+                                                                   int nbins, int width) {
+  const int bt = blockIdx.y;
+  const int64_t lo = centers[bt] - width / 2, hi = lo + width - 1;
+  const int64_t oldest = newest - ring_cols + 1 > 0 ? newest - ring_cols + 1 : 0;
+  const bool ok = lo >= oldest && hi <= newest;            // uniform over the workgroup (one window)
+  const int start = ok ? (int)(lo % ring_cols) : 0;
+  const int64_t total = (int64_t)nbins * width;
+  float* o = out + (int64_t)bt * total;
+  constexpr int V = VEC ? 4 : 1;
+  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V; i < total; i += (int64_t)gridDim.x * 256 * V) {
+    const int bin = (int)(i / width), j = (int)(i - (int64_t)bin * width);
+    const float* row = ring + (int64_t)bin * ring_cols;
+    float v[V];
+#pragma unroll
+    for (int q = 0; q < V; ++q) {
+      int c = start + j + q;                               // < 2 ring_cols: width <= ring_cols
+      if (c >= ring_cols) c -= ring_cols;
+      v[q] = ok ? row[c] : __builtin_nanf("");
+    }
+    if constexpr (VEC) {
+      *reinterpret_cast<float4*>(o + i) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+      o[i] = v[0];
+    }
+  }
+}
+
+// one row of the (frame in chunk, slot) table: inside the chunk and the ring, or the workgroup writes nothing
+__device__ __forceinline__ bool ingest_pair_ok(const int* __restrict__ pairs, int p, int K, int R, int* frame, int* slot) {
+  *frame = pairs[2 * p];
+  *slot = pairs[2 * p + 1];
+  return *frame >= 0 && *frame < K && *slot >= 0 && *slot < R;
+}
+
+// grid (ceil(S / 4), pairs), 256 threads; dynamic LDS sample_lds_bytes(W).  The ring is (R, 3, S, S): slot r is "clip" r of one frame
+__global__ __launch_bounds__(256) void stream_ingest_kernel(const uint8_t* __restrict__ chunk, int K, int H, int W,
+                                                            const int* __restrict__ pairs, const int* __restrict__ params,
+                                                            float* __restrict__ ring, int R, int S, int64_t chunk_bytes, int rowcap,
+                                                            float3 mean, float3 inv_std) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  int frame, slot;
+  if (!ingest_pair_ok(pairs, blockIdx.y, K, R, &frame, &slot)) return;      // uniform over the workgroup (one pair)
+  sample_rows(chunk, chunk_bytes, 0, frame, H, W, params, false, ring, slot, 0, 1, S, rowcap, mean, inv_std, lds);
+}
+
+// the same for a chunk of 4:2:0 frames; dynamic LDS sample_yuv_lds_bytes(W)
+__global__ __launch_bounds__(256) void stream_ingest_yuv_kernel(const uint8_t* __restrict__ chunk, int K, int H, int W,
+                                                                const int* __restrict__ pairs, const int* __restrict__ params,
+                                                                float* __restrict__ ring, int R, int S, int64_t chunk_bytes, int lcap,
+                                                                int ccap, int layout, YuvCoef k, float3 mean, float3 inv_std) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  int frame, slot;
+  if (!ingest_pair_ok(pairs, blockIdx.y, K, R, &frame, &slot)) return;
+  sample_rows_yuv(chunk, chunk_bytes, 0, frame, H, W, params, false, ring, slot, 0, 1, S, lcap, ccap, layout, k, mean, inv_std, lds);
+}
+
+// grid (blocks over S * S / V, 3 * T, B), 256 threads.  out[b][c][t] = ring[slots[b][t]][c]; a slot outside [0, R) gives NaN.
+// VEC: S * S % 4 == 0 and both 16-byte aligned, one float4 per lane each way.
+template <bool VEC>
+__global__ __launch_bounds__(256) void stream_gather_kernel(const float* __restrict__ ring, int R, const int* __restrict__ slots,
+                                                            float* __restrict__ out, int T, int64_t plane) {
+  const int c = blockIdx.y / T, t = blockIdx.y - c * T, b = blockIdx.z;
+  const int slot = slots[(int64_t)b * T + t];
+  const bool ok = slot >= 0 && slot < R;                   // uniform over the workgroup
+  const float* src = ring + ((int64_t)(ok ? slot : 0) * 3 + c) * plane;
+  float* dst = out + (((int64_t)b * 3 + c) * T + t) * plane;
+  constexpr int V = VEC ? 4 : 1;
+  const float nan = __builtin_nanf("");
+  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V; i < plane; i += (int64_t)gridDim.x * 256 * V) {
+    if constexpr (VEC)
+      *reinterpret_cast<float4*>(dst + i) = ok ? *reinterpret_cast<const float4*>(src + i) : make_float4(nan, nan, nan, nan);
+    else
+      dst[i] = ok ? src[i] : nan;
+  }
+}
+
+int ingest_check(const void* chunk, const void* pairs, const void* params, const void* ring, const float* mean, const float* std,
+                 int K, int H, int W, int npairs, int R, int S) {
+  CSTS_REQUIRE(chunk && pairs && params && ring && mean && std, "bad args");
+  CSTS_REQUIRE(K > 0 && H > 0 && W > 0 && W <= 6000 && npairs > 0 && npairs <= 65535 && R > 0 && S > 0 && S <= 4096 &&
+                   (int64_t)R * 3 * S * S < ((int64_t)1 << 40), "bad sizes (W <= 6000, S <= 4096, pairs <= 65535)");
+  CSTS_REQUIRE(aligned16(chunk) && aligned16(ring), "chunk and ring must be 16-byte aligned");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int csts_stream_stft(const float* buf, int64_t s_base, int64_t m, int64_t n_total, int64_t f0, int64_t f1, float* ring,
+                                int ring_cols, int n_fft, int hop, int win, float eps, hipStream_t stream) {
+  CSTS_REQUIRE(ring && (buf || m == 0) && m >= 0 && s_base >= 0 && n_fft > 0 && hop > 0 && win > 0 && win <= n_fft && n_fft <= 2048,
+               "bad args");
+  CSTS_REQUIRE(f0 >= 0 && f1 > f0 && ring_cols > 0 && f1 - f0 <= ring_cols && f1 <= ((int64_t)1 << 40),
+               "columns [f0, f1) must be non-empty and at most one turn of the ring");
+  CSTS_REQUIRE(n_total < 0 || n_total <= s_base + m, "n_total lies past the samples pushed");
+  // every sample a column reads is zero by rule (before 0, at or past n_total) or inside the buffer
+  const int64_t first = std::max<int64_t>(stft_first_sample(f0, n_fft, hop, win), 0);
+  int64_t last = stft_first_sample(f1 - 1, n_fft, hop, win) + win;          // one past the last sample read
+  if (n_total >= 0) last = std::min(last, n_total);
+  CSTS_REQUIRE(last <= first || (first >= s_base && last <= s_base + m), "a column needs a sample the buffer does not hold");
+  const size_t sm = (size_t)stft_lds_floats(n_fft, win) * sizeof(float);
+  hipLaunchKernelGGL(stream_stft_kernel, dim3((unsigned)(f1 - f0)), dim3(256), sm, stream, buf, s_base, m, n_total, f0, ring,
+                     ring_cols, n_fft, hop, win, eps);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_stream_audio_windows(const float* ring, int ring_cols, int64_t newest, const int64_t* centers, float* out, int B,
+                                         int T, int nbins, int width, hipStream_t stream) {
+  CSTS_REQUIRE(ring && centers && out && B > 0 && T > 0 && nbins > 0 && width > 0 && (int64_t)B * T <= 65535,
+               "bad args (B * T <= 65535)");
+  CSTS_REQUIRE((width & 1) == 0 && width <= ring_cols, "width must be even and at most ring_cols");
+  const bool vec = (width & 3) == 0 && aligned16(out);
+  const dim3 grid((unsigned)std::min<int64_t>(cdiv((int64_t)nbins * width, vec ? 1024 : 256), 1024), B * T);
+  if (vec)
+    hipLaunchKernelGGL(stream_audio_windows_kernel<true>, grid, dim3(256), 0, stream, ring, ring_cols, newest, centers, out, nbins,
+                       width);
+  else
+    hipLaunchKernelGGL(stream_audio_windows_kernel<false>, grid, dim3(256), 0, stream, ring, ring_cols, newest, centers, out, nbins,
+                       width);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_stream_ingest(const uint8_t* chunk_khwc, int K, int H, int W, const int* pairs, int npairs, const int* params,
+                                  float* ring, int R, int S, const float mean[3], const float std[3], hipStream_t stream) {
+  if (ingest_check(chunk_khwc, pairs, params, ring, mean, std, K, H, W, npairs, R, S)) return -1;
+  int rowcap;
+  const int lds = sample_lds_bytes(W, &rowcap);
+  if (lds > 65536) CSTS_REQUIRE(csts_dyn_lds_optin(reinterpret_cast<const void*>(&stream_ingest_kernel), lds), "LDS opt-in");
+  const float3 m = make_float3(mean[0], mean[1], mean[2]), is = make_float3(1.f / std[0], 1.f / std[1], 1.f / std[2]);
+  hipLaunchKernelGGL(stream_ingest_kernel, dim3((unsigned)cdiv(S, SAMPLE_ROWS), npairs), dim3(256), lds, stream, chunk_khwc, K, H, W,
+                     pairs, params, ring, R, S, (int64_t)K * H * W * 3, rowcap, m, is);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_stream_ingest_yuv(const uint8_t* chunk_yuv, int K, int H, int W, const int* pairs, int npairs, const int* params,
+                                      float* ring, int R, int S, const float mean[3], const float std[3], int layout, int matrix,
+                                      int full_range, hipStream_t stream) {
+  if (ingest_check(chunk_yuv, pairs, params, ring, mean, std, K, H, W, npairs, R, S)) return -1;
+  CSTS_REQUIRE(yuv_args_ok(layout, matrix), "layout must be CSTS_YUV_NV12 or CSTS_YUV_I420, matrix CSTS_YUV_BT601 or CSTS_YUV_BT709");
+  CSTS_REQUIRE(H >= 2 && W >= 2 && (H & 1) == 0 && (W & 1) == 0, "4:2:0 frames need even H, W >= 2");
+  int lcap, ccap;
+  const int lds = sample_yuv_lds_bytes(W, &lcap, &ccap);
+  if (lds > 65536) CSTS_REQUIRE(csts_dyn_lds_optin(reinterpret_cast<const void*>(&stream_ingest_yuv_kernel), lds), "LDS opt-in");
+  const float3 m = make_float3(mean[0], mean[1], mean[2]), is = make_float3(1.f / std[0], 1.f / std[1], 1.f / std[2]);
+  hipLaunchKernelGGL(stream_ingest_yuv_kernel, dim3((unsigned)cdiv(S, SAMPLE_ROWS), npairs), dim3(256), lds, stream, chunk_yuv, K, H, W,
+                     pairs, params, ring, R, S, (int64_t)K * yuv_frame_bytes(H, W), lcap, ccap, layout, yuv_coef(matrix, full_range), m,
+                     is);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_stream_gather(const float* ring, int R, const int* slots, float* out, int B, int T, int S, hipStream_t stream) {
+  CSTS_REQUIRE(ring && slots && out && R > 0 && B > 0 && B <= 65535 && T > 0 && T <= SPATIAL_MAX_T && S > 0 && S <= 4096,
+               "bad args (B <= 65535, T <= 64, S <= 4096)");
+  const int64_t plane = (int64_t)S * S;
+  const bool vec = (plane & 3) == 0 && aligned16(ring) && aligned16(out);
+  const dim3 grid((unsigned)std::min<int64_t>(cdiv(plane, vec ? 1024 : 256), 1024), 3 * T, B);
+  if (vec)
+    hipLaunchKernelGGL(stream_gather_kernel<true>, grid, dim3(256), 0, stream, ring, R, slots, out, T, plane);
+  else
+    hipLaunchKernelGGL(stream_gather_kernel<false>, grid, dim3(256), 0, stream, ring, R, slots, out, T, plane);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}

@@ -18,32 +18,13 @@ TEMPERATURE = 2.0          # frame_softmax temperature of the train / val / test
 AUDIO_WIDTH = 256          # spectrogram columns per audio window (ego4d_avgaze_forecast.py:218-219)
 
 
-def plan_video(cfg, n_frames, fps=None, stride=None, segment=None, cols=None):
-    """The windows predict_video cuts a recording of n_frames frames into, on the host (numpy arrays).
-
-    A window is one clip of the dataset cfg.TEST.DATASET names: `segment` frames from its origin o_w = w * stride, of which
-    the first `observed` are seen.  Its T input frames follow the reference's temporal rule on the observed part
-    (inputs.temporal_indices) and its T predictions target
-      forecast, not aria: 150 / 86 frames, inputs clip 1 of TEST.NUM_ENSEMBLE_VIEWS, targets linspace(86, 149, T)
-                          (ego4d_avgaze_forecast.py:197,234-235);
-      forecast and aria:  100 / 60 frames, same inputs, targets linspace(60 + rate, 99, T) (aria_avgaze_forecast.py:192,230-231);
-      estimation:         round(5 fps) frames, all observed, inputs clip 0, targets = the input frames (ego4d_avgaze.py:263-267),
-    all local to the origin.  Default stride: segment - observed (forecast: the predicted spans tile the video) or
-    ceil(clip size) (estimation).  `segment` overrides the table; the forecast rows then scale observed and the targets by
-    segment / table segment, floored.  windows = floor((n_frames - observed) / stride) + 1; fewer than `observed` frames is an
-    error.  Targets >= n_frames stay in the plan (gaze_track drops them).  fps defaults to DATA.TARGET_FPS.
-
-    cols (optional): the columns of ONE spectrogram of the whole waveform.  The plan then holds the audio window centres by the
-    rule of ego4d_avgaze_forecast.py:215-219 applied to the window's slice [c0, c1) = [floor(o cols / n), floor((o + observed)
-    cols / n)): centre = c0 + round(local / observed * (c1 - c0)) clipped to [c0 + 128, c1 - 1 - 128]; a slice narrower than
-    257 columns is an error.
-
-    Returns {"windows", "segment", "observed", "stride", "clip_size", "origins" (windows,), "inputs" and "targets" (T,) local,
-    "frames_idx" int32 and "target_idx" int64 (windows, T) absolute [, "audio_centers" int32 (windows, T)]}."""
+def window_rule(cfg, fps=None, stride=None, segment=None):
+    """The part of plan_video that does not need the recording's length (plan_stream shares it): the table of the dataset
+    cfg.TEST.DATASET names -> {"segment", "observed", "stride", "clip_size", "inputs" and "targets" int64 (T,) local to a window's
+    origin}, as plan_video's docstring states them."""
     import math
     import numpy as np
     from .inputs import temporal_indices
-    n_frames = int(n_frames)
     T, rate, target_fps = int(cfg.DATA.NUM_FRAMES), int(cfg.DATA.SAMPLING_RATE), cfg.DATA.TARGET_FPS
     fps = target_fps if fps is None else fps
     views = int(cfg.TEST.NUM_ENSEMBLE_VIEWS)
@@ -71,6 +52,37 @@ def plan_video(cfg, n_frames, fps=None, stride=None, segment=None, cols=None):
     stride = default_stride if stride is None else int(stride)
     if stride < 1:
         raise ValueError(f"stride must be positive, got {stride}")
+    return {"segment": seg, "observed": observed, "stride": stride, "clip_size": clip_size,
+            "inputs": inputs_local.astype(np.int64), "targets": targets.astype(np.int64)}
+
+
+def plan_video(cfg, n_frames, fps=None, stride=None, segment=None, cols=None):
+    """The windows predict_video cuts a recording of n_frames frames into, on the host (numpy arrays).
+
+    A window is one clip of the dataset cfg.TEST.DATASET names: `segment` frames from its origin o_w = w * stride, of which
+    the first `observed` are seen.  Its T input frames follow the reference's temporal rule on the observed part
+    (inputs.temporal_indices) and its T predictions target
+      forecast, not aria: 150 / 86 frames, inputs clip 1 of TEST.NUM_ENSEMBLE_VIEWS, targets linspace(86, 149, T)
+                          (ego4d_avgaze_forecast.py:197,234-235);
+      forecast and aria:  100 / 60 frames, same inputs, targets linspace(60 + rate, 99, T) (aria_avgaze_forecast.py:192,230-231);
+      estimation:         round(5 fps) frames, all observed, inputs clip 0, targets = the input frames (ego4d_avgaze.py:263-267),
+    all local to the origin.  Default stride: segment - observed (forecast: the predicted spans tile the video) or
+    ceil(clip size) (estimation).  `segment` overrides the table; the forecast rows then scale observed and the targets by
+    segment / table segment, floored.  windows = floor((n_frames - observed) / stride) + 1; fewer than `observed` frames is an
+    error.  Targets >= n_frames stay in the plan (gaze_track drops them).  fps defaults to DATA.TARGET_FPS.
+
+    cols (optional): the columns of ONE spectrogram of the whole waveform.  The plan then holds the audio window centres by the
+    rule of ego4d_avgaze_forecast.py:215-219 applied to the window's slice [c0, c1) = [floor(o cols / n), floor((o + observed)
+    cols / n)): centre = c0 + round(local / observed * (c1 - c0)) clipped to [c0 + 128, c1 - 1 - 128]; a slice narrower than
+    257 columns is an error.
+
+    Returns {"windows", "segment", "observed", "stride", "clip_size", "origins" (windows,), "inputs" and "targets" (T,) local,
+    "frames_idx" int32 and "target_idx" int64 (windows, T) absolute [, "audio_centers" int32 (windows, T)]}."""
+    import numpy as np
+    n_frames = int(n_frames)
+    rule = window_rule(cfg, fps=fps, stride=stride, segment=segment)
+    seg, observed, stride, clip_size = rule["segment"], rule["observed"], rule["stride"], rule["clip_size"]
+    inputs_local, targets = rule["inputs"], rule["targets"]
     if n_frames < observed:
         raise ValueError(f"the video has {n_frames} frames, one window observes {observed}")
     windows = (n_frames - observed) // stride + 1
@@ -471,6 +483,17 @@ class GazePredictor:
         if attention:
             res.update({k: out[k] for k in ATTENTION_OUTPUTS})
         return res
+
+    def stream(self, fps=None, stride=None, segment=None, batch=1, max_chunk=32, pixel_format="rgb24", matrix="bt601",
+               full_range=False, sample_rate=None):
+        """A live stream on this predictor (csts_amd.stream.GazeStream): push(frames, wav) takes frames and 24 kHz audio in whatever
+        pieces they arrive and returns the windows each piece completes; close() ends it.  The windows are plan_stream's (fps an
+        int or a Fraction, stride in frames); `batch` windows run per predict_batch call; `max_chunk` sizes the two device rings,
+        which do not grow with the stream (GazeStream states the capacities).  pixel_format "nv12" | "i420": the pushed frames
+        are 4:2:0 pictures.  sample_rate: None or 24000; another rate is a ValueError (chunk-wise resampling needs filter state)."""
+        from .stream import GazeStream
+        return GazeStream(self, fps=fps, stride=stride, segment=segment, batch=batch, max_chunk=max_chunk,
+                          pixel_format=pixel_format, matrix=matrix, full_range=full_range, sample_rate=sample_rate)
 
     @torch.no_grad()
     def _video_params_row(self, H, W):

@@ -456,6 +456,143 @@ def clip_sample(video_u8: torch.Tensor, frames_idx: torch.Tensor, params: torch.
     return out
 
 
+STFT_N_FFT, STFT_HOP, STFT_WIN, STFT_EPS = 511, 120, 240, 1e-6     # stft_logpower's defaults: the model's spectrogram
+
+
+def stream_stft(buf: torch.Tensor, s_base: int, f0: int, f1: int, ring: torch.Tensor, n_total: int = -1, n_fft: int = STFT_N_FFT,
+                hop: int = STFT_HOP, win: int = STFT_WIN, eps: float = STFT_EPS) -> torch.Tensor:
+    """Columns [f0, f1) of stft_logpower's spectrogram of an endless signal, written into a spectrogram ring (csts_stream_stft):
+    buf fp32 (m,) holds the samples [s_base, s_base + m) of the signal, ring fp32 (n_fft // 2 + 1, ring_cols) receives column f at
+    ring[:, f % ring_cols].  Column f reads the samples [f * hop + (n_fft - win) // 2 - n_fft // 2, + win) -- [120 f - 120,
+    120 f + 120) with the defaults; samples before 0 are zero and, with n_total >= 0 (the signal ended after n_total samples), so
+    are those at or past n_total, as at the two ends of an offline waveform.  A column that needs any other sample the buffer
+    does not hold, or more than ring_cols columns at once, is a ValueError.  Column f equals stft_logpower(whole signal)[:, f]
+    bit for bit (one device function computes both).  Returns the ring."""
+    _gpu(buf, ring)
+    s_base, f0, f1, n_total = int(s_base), int(f0), int(f1), int(n_total)
+    if buf.dtype != torch.float32 or buf.dim() != 1 or not buf.is_contiguous():
+        raise ValueError(f"buf must be a contiguous fp32 (m,) waveform, got {tuple(buf.shape)} {buf.dtype}")
+    nbins = n_fft // 2 + 1
+    if ring.dtype != torch.float32 or ring.dim() != 2 or ring.shape[0] != nbins or not ring.is_contiguous():
+        raise ValueError(f"the ring must be contiguous fp32 ({nbins}, ring_cols), got {tuple(ring.shape)} {ring.dtype}")
+    m, ring_cols = buf.numel(), ring.shape[1]
+    if s_base < 0 or f0 < 0 or f1 <= f0 or f1 - f0 > ring_cols:
+        raise ValueError(f"columns [{f0}, {f1}) must be non-empty and at most one turn of the ring ({ring_cols} columns); s_base "
+                         f"{s_base} >= 0")
+    if n_total >= 0 and n_total > s_base + m:
+        raise ValueError(f"n_total {n_total} lies past the {s_base + m} samples pushed")
+    first = max(f0 * hop + (n_fft - win) // 2 - n_fft // 2, 0)
+    last = (f1 - 1) * hop + (n_fft - win) // 2 - n_fft // 2 + win
+    if n_total >= 0:
+        last = min(last, n_total)
+    if last > first and (first < s_base or last > s_base + m):
+        raise ValueError(f"columns [{f0}, {f1}) read the samples [{first}, {last}), the buffer holds [{s_base}, {s_base + m})")
+    with torch.cuda.device(ring.device):
+        L.check(L.load().csts_stream_stft(buf.data_ptr() if m else None, s_base, m, n_total, f0, f1, ring.data_ptr(), ring_cols,
+                                          n_fft, hop, win, eps, _s()), "csts_stream_stft")
+    return ring
+
+
+def stream_audio_windows(ring: torch.Tensor, newest: int, centers: torch.Tensor, centers_host, width: int = 256) -> torch.Tensor:
+    """audio_windows_at on a spectrogram ring (csts_stream_audio_windows): ring fp32 (nbins, ring_cols) holds column f of an endless
+    spectrogram at ring[:, f % ring_cols] (stream_stft), newest is the last column written, centers int64 (B, T) on the device are
+    GLOBAL centre columns -> (B, 1, T, nbins, width), window (b, t) = columns [c - width/2, c + width/2) read across the wrap.
+    Nothing is clamped: centers_host, the same table on the host (anything numpy.asarray takes), is checked first and a window
+    that is not wholly inside the live span [max(newest - ring_cols + 1, 0), newest] is a ValueError; the device applies the same
+    test when the kernel runs and gives such a window NaN, so a replayed launch stays safe."""
+    import numpy as np
+    _gpu(ring, centers)
+    if ring.dtype != torch.float32 or ring.dim() != 2 or not ring.is_contiguous():
+        raise ValueError(f"the ring must be contiguous fp32 (nbins, ring_cols), got {tuple(ring.shape)} {ring.dtype}")
+    if centers.dtype != torch.int64 or centers.dim() != 2:
+        raise ValueError(f"centers must be int64 (B, T), got {tuple(centers.shape)} {centers.dtype}")
+    nbins, ring_cols = ring.shape
+    B, T = centers.shape
+    width, newest = int(width), int(newest)
+    if width < 2 or width % 2 or width > ring_cols or B < 1 or T < 1 or B * T > 65535:
+        raise ValueError(f"bad sizes: width {width} (even, <= ring_cols {ring_cols}), B {B}, T {T} (B * T <= 65535)")
+    host = np.asarray(centers_host, dtype=np.int64)
+    if host.shape != (B, T):
+        raise ValueError(f"the host centre table is {host.shape}, the device one ({B}, {T})")
+    oldest = max(newest - ring_cols + 1, 0)
+    if int(host.min()) - width // 2 < oldest or int(host.max()) + width // 2 - 1 > newest:
+        raise ValueError(f"an audio window reaches outside the ring's live columns [{oldest}, {newest}] ({ring_cols} columns): "
+                         f"centres {int(host.min())} .. {int(host.max())}, width {width}")
+    out = torch.empty(B, 1, T, nbins, width, dtype=torch.float32, device=ring.device)
+    with torch.cuda.device(ring.device):
+        L.check(L.load().csts_stream_audio_windows(ring.data_ptr(), ring_cols, newest, centers.contiguous().data_ptr(), out.data_ptr(),
+                                                   B, T, nbins, width, _s()), "csts_stream_audio_windows")
+    return out
+
+
+def stream_ingest(chunk_u8: torch.Tensor, pairs: torch.Tensor, params_row: torch.Tensor, ring: torch.Tensor,
+                  mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225), *, pixel_format: str = "rgb24", matrix: str = "bt601",
+                  full_range: bool = False) -> torch.Tensor:
+    """The used frames of one pushed chunk, sampled once into a ring of normalised crops (csts_stream_ingest): chunk uint8
+    (K, H, W, 3), pairs int32 (P, 2) = (frame in chunk, slot) on the device, params_row int32 (5,) = new h, new w, y0, x0, flip
+    (one test-mode row for the stream), ring fp32 (R, 3, S, S) -> ring[slot] = clip_sample(chunk, [[frame]], params_row[None],
+    S)[0, :, 0], bit for bit.  A chunk frame no pair names is not read, and no other slot is written.  The table is read by the
+    kernel when it runs; a pair outside the chunk or the ring writes nothing.  P == 0 launches nothing.  pixel_format "nv12" |
+    "i420": the chunk is uint8 (K, H * 3 / 2, W), read in place (csts_stream_ingest_yuv).  Returns the ring."""
+    layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
+    if layout:
+        if chunk_u8.dtype != torch.uint8 or chunk_u8.dim() != 3 or chunk_u8.shape[0] < 1:
+            raise ValueError(f"{pixel_format} chunk must be uint8 (K >= 1, H * 3 / 2, W), got {tuple(chunk_u8.shape)} "
+                             f"{chunk_u8.dtype}")
+        K, (H, W) = chunk_u8.shape[0], _yuv_hw(chunk_u8.shape, pixel_format, "chunk")
+    else:
+        if chunk_u8.dtype != torch.uint8 or chunk_u8.dim() != 4 or chunk_u8.shape[-1] != 3 or chunk_u8.shape[0] < 1:
+            raise ValueError(f"chunk must be uint8 (K >= 1, H, W, 3), got {tuple(chunk_u8.shape)} {chunk_u8.dtype}")
+        K, H, W, _ = chunk_u8.shape
+    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.shape[0] > 65535:
+        raise ValueError(f"pairs must be int32 (P <= 65535, 2) = frame in chunk, slot, got {tuple(pairs.shape)} {pairs.dtype}")
+    if params_row.dtype != torch.int32 or tuple(params_row.shape) != (5,):
+        raise ValueError(f"params_row must be int32 (5,), got {tuple(params_row.shape)} {params_row.dtype}")
+    if ring.dtype != torch.float32 or ring.dim() != 4 or ring.shape[1] != 3 or ring.shape[2] != ring.shape[3] or \
+            not ring.is_contiguous() or ring.data_ptr() % 16:
+        raise ValueError(f"the ring must be contiguous, 16-byte aligned fp32 (R, 3, S, S), got {tuple(ring.shape)} {ring.dtype}")
+    if W > 6000:
+        raise ValueError(f"frames wider than 6000 pixels are not supported, got W {W}")
+    _gpu(chunk_u8, pairs, params_row, ring)
+    P, R, S = pairs.shape[0], ring.shape[0], ring.shape[2]
+    if P == 0:
+        return ring
+    x = chunk_u8.contiguous()
+    if x.data_ptr() % 16:
+        x = x.clone()
+    f3 = C.c_float * 3
+    tab, par = pairs.contiguous(), params_row.contiguous()
+    with torch.cuda.device(ring.device):
+        if layout:
+            L.check(L.load().csts_stream_ingest_yuv(x.data_ptr(), K, H, W, tab.data_ptr(), P, par.data_ptr(), ring.data_ptr(), R, S,
+                                                    f3(*mean), f3(*std), layout, mat, fr, _s()), "csts_stream_ingest_yuv")
+        else:
+            L.check(L.load().csts_stream_ingest(x.data_ptr(), K, H, W, tab.data_ptr(), P, par.data_ptr(), ring.data_ptr(), R, S,
+                                                f3(*mean), f3(*std), _s()), "csts_stream_ingest")
+    return ring
+
+
+def stream_gather(ring: torch.Tensor, slots: torch.Tensor) -> torch.Tensor:
+    """Clips out of the crop ring (csts_stream_gather): ring fp32 (R, 3, S, S), slots int32 (B, T) on the device -> fp32
+    (B, 3, T, S, S), out[b, :, t] = ring[slots[b, t]].  The table is read by the kernel when it runs; a slot outside [0, R) gives
+    a NaN frame."""
+    _gpu(ring, slots)
+    if ring.dtype != torch.float32 or ring.dim() != 4 or ring.shape[1] != 3 or ring.shape[2] != ring.shape[3] or \
+            not ring.is_contiguous():
+        raise ValueError(f"the ring must be contiguous fp32 (R, 3, S, S), got {tuple(ring.shape)} {ring.dtype}")
+    if slots.dtype != torch.int32 or slots.dim() != 2:
+        raise ValueError(f"slots must be int32 (B, T), got {tuple(slots.shape)} {slots.dtype}")
+    B, T = slots.shape
+    if not 1 <= T <= 64 or not 1 <= B <= 65535:
+        raise ValueError(f"the gather takes 1 <= B <= 65535 clips of 1 <= T <= 64 frames, got B {B}, T {T}")
+    R, S = ring.shape[0], ring.shape[2]
+    out = torch.empty(B, 3, T, S, S, dtype=torch.float32, device=ring.device)
+    with torch.cuda.device(ring.device):
+        L.check(L.load().csts_stream_gather(ring.data_ptr(), R, slots.contiguous().data_ptr(), out.data_ptr(), B, T, S, _s()),
+                "csts_stream_gather")
+    return out
+
+
 def _clip_table(clips, B=None):
     """The clip table {byte offset, N, H, W} as a contiguous int64 (B, 4) tensor; the caller validates its rows."""
     if clips.dtype != torch.int64 or clips.dim() != 2 or clips.shape[1] != 4 or clips.shape[0] < 1 or \

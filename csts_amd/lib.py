@@ -273,6 +273,11 @@ SYMBOLS = {
     "csts_spatial_sample_yuv": (_I, [vp, vp, vp, _I, _I, _I, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),
     "csts_clip_sample_yuv": (_I, [vp, i64, vp, vp, vp, _I, _I, _I, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),
     "csts_batch_sample_yuv": (_I, [vp, i64, vp, vp, vp, vp, _I, _I, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),
+    "csts_stream_stft": (_I, [vp, i64, i64, i64, i64, i64, vp, _I, _I, _I, _I, _F, vp]),
+    "csts_stream_audio_windows": (_I, [vp, _I, i64, vp, vp, _I, _I, _I, _I, vp]),
+    "csts_stream_ingest": (_I, [vp, _I, _I, _I, vp, _I, vp, vp, _I, _I, C.c_float * 3, C.c_float * 3, vp]),
+    "csts_stream_ingest_yuv": (_I, [vp, _I, _I, _I, vp, _I, vp, vp, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),
+    "csts_stream_gather": (_I, [vp, _I, vp, vp, _I, _I, _I, vp]),
     "csts_adaptive_f1_workspace": (sz, [i64, _I]),
     "csts_adaptive_f1": (_I, [vp, vp, vp, vp, _I, i64, _I, _I, vp, vp, sz, vp]),
     "csts_f1_counts": (_I, [vp, vp, vp, _I, i64, _I, _I, vp, vp]),

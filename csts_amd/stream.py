@@ -1,0 +1,383 @@
+"""Gaze prediction on a live stream: ``plan_video`` without a length, and ``GazeStream``.
+
+``GazePredictor.predict_video`` needs the finished recording resident on the device.  Here the user pushes frames and audio in
+whatever pieces they arrive; every window is emitted by the push that completes it, and what the windows read lives in two device
+rings (normalised crops, spectrogram columns) whose size does not depend on how long the stream runs.  The host side -- which
+window reads which frames and columns, and when it is ready -- is pure arithmetic (``plan_stream``, ``stream_window``,
+``stream_schedule``); the device side is the four kernels of csts_amd/csrc/stream.hip behind inputs.stream_stft,
+inputs.stream_audio_windows, inputs.stream_ingest and inputs.stream_gather."""
+from __future__ import annotations
+
+import numbers
+from fractions import Fraction
+
+from .infer import AUDIO_WIDTH, window_rule
+from .inputs import AUDIO_RATE, STFT_HOP, STFT_N_FFT, STFT_WIN
+
+HALF_WIDTH = AUDIO_WIDTH // 2
+
+
+def check_stream_rate(sample_rate):
+    """The sample rate of a stream's audio: None or 24000.  Any other rate is a ValueError: resampling chunk by chunk needs the
+    filter's state carried from push to push, which inputs.resample_audio (one whole waveform per call) does not keep."""
+    if sample_rate is None:
+        return AUDIO_RATE
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, numbers.Integral) or int(sample_rate) != AUDIO_RATE:
+        raise ValueError(f"a stream takes its audio at {AUDIO_RATE} Hz, got sample_rate {sample_rate!r}: resampling chunk by chunk "
+                         "needs filter state carried between pushes, which is not implemented; resample the pieces yourself or use "
+                         "predict_video(sample_rate=...) on a finished recording")
+    return AUDIO_RATE
+
+
+def _exact_fps(fps, default):
+    """fps as an exact Fraction: an int, a Fraction, or an integral float; anything else is a ValueError."""
+    if fps is None:
+        fps = default
+    if isinstance(fps, bool):
+        raise ValueError(f"fps must be an int or a Fraction, got {fps!r}")
+    if isinstance(fps, numbers.Integral):
+        f = Fraction(int(fps))
+    elif isinstance(fps, Fraction):
+        f = fps
+    elif isinstance(fps, float) and fps == int(fps):
+        f = Fraction(int(fps))
+    else:
+        raise ValueError(f"a stream places its audio windows by the exact ratio of columns to frames: fps must be an int or a "
+                         f"fractions.Fraction, e.g. Fraction(30000, 1001), got {fps!r}")
+    if f <= 0:
+        raise ValueError(f"fps must be positive, got {fps!r}")
+    return f
+
+
+def plan_stream(cfg, fps=None, stride=None, segment=None):
+    """plan_video without a length: the window rule of a stream, on the host.
+
+    Returns {"segment", "observed", "stride", "clip_size", "inputs" and "targets" int64 (T,) local to a window's origin} exactly as
+    plan_video(cfg, n, fps, stride, segment) has them (infer.window_rule is the one table behind both), plus "fps" and
+    "cols_per_frame", both exact fractions.Fraction: cols_per_frame = AUDIO_RATE / (hop * fps) = 200 / fps spectrogram columns per
+    video frame.  fps: an int or a Fraction (an integral float is accepted); anything else is a ValueError -- the audio windows of
+    an open-ended stream are placed by this ratio alone, so it has to be exact.  fps defaults to DATA.TARGET_FPS.  A ratio that
+    leaves the observed span fewer than 257 columns is the error plan_video raises for such a recording."""
+    f = _exact_fps(fps, cfg.DATA.TARGET_FPS)
+    rule = window_rule(cfg, fps=int(f) if f.denominator == 1 else float(f), stride=stride, segment=segment)
+    plan = dict(rule)
+    plan["fps"] = f
+    plan["cols_per_frame"] = Fraction(AUDIO_RATE, STFT_HOP) / f
+    if plan["observed"] * plan["cols_per_frame"] < AUDIO_WIDTH + 1:
+        raise ValueError(f"the spectrogram slice of a window has {float(plan['observed'] * plan['cols_per_frame']):.1f} columns "
+                         f"({float(plan['cols_per_frame']):.3f} per frame), an audio window needs {AUDIO_WIDTH + 1}")
+    return plan
+
+
+def stream_window(plan, w):
+    """Window w of a stream (plan: plan_stream's), o = w * stride:
+
+      frames_idx    = o + inputs, target_idx = o + targets (int64 (T,), absolute frame numbers);
+      audio_centers = plan_video's rule with the whole-recording ratio cols / n replaced by rho = cols_per_frame:
+                      c0 = floor(o rho), c1 = floor((o + observed) rho), centre = c0 + rint(local / observed * (c1 - c0)) clipped
+                      to [c0 + 128, c1 - 1 - 128] (int64 (T,), global column numbers); a slice narrower than 257 columns is the
+                      error it is there;
+      ready_frames  = o + inputs[-1] + 1: the window needs this many frames pushed;
+      ready_samples = hop * (max(audio_centers) + 128): and this many 24 kHz samples -- column f of the STFT reads the samples
+                      [120 f - 120, 120 f + 120), so the last column the window reads is final once they are in.
+
+    Where cols * den == num * n for rho = num / den (e.g. 300 frames, 2000 columns, 30 fps) the centres are plan_video's."""
+    import numpy as np
+    w = int(w)
+    if w < 0:
+        raise ValueError(f"window numbers start at 0, got {w}")
+    rho = plan["cols_per_frame"]
+    observed = int(plan["observed"])
+    o = w * int(plan["stride"])
+    inputs = np.asarray(plan["inputs"], dtype=np.int64)
+    c0 = o * rho.numerator // rho.denominator
+    c1 = (o + observed) * rho.numerator // rho.denominator
+    if c1 - c0 < AUDIO_WIDTH + 1:
+        raise ValueError(f"the spectrogram slice of window {w} has {c1 - c0} columns ({float(rho):.3f} per frame), an audio window "
+                         f"needs {AUDIO_WIDTH + 1}")
+    centers = c0 + np.rint(inputs.astype(np.float64) / observed * (c1 - c0)).astype(np.int64)
+    centers = np.clip(centers, c0 + HALF_WIDTH, c1 - 1 - HALF_WIDTH).astype(np.int64)
+    return {"window": w, "origin": o, "frames_idx": o + inputs, "target_idx": o + np.asarray(plan["targets"], dtype=np.int64),
+            "audio_centers": centers, "first_column": int(c0), "ready_frames": int(o + inputs[-1] + 1),
+            "ready_samples": int(STFT_HOP * (int(centers.max()) + HALF_WIDTH))}
+
+
+def stream_schedule(plan, pushes):
+    """Which windows each push completes.  pushes: a list of (frames, samples) counts, one pair per push; returns one list of
+    window numbers per push.  Window w is ready in the first push after which ready_frames(w) frames and ready_samples(w) samples
+    have been pushed in total; windows are emitted in order, every window once."""
+    frames = samples = 0
+    w = 0
+    nxt = stream_window(plan, 0)
+    out = []
+    for k, m in pushes:
+        k, m = int(k), int(m)
+        if k < 0 or m < 0:
+            raise ValueError(f"a push holds counts >= 0, got ({k}, {m})")
+        frames += k
+        samples += m
+        ready = []
+        while nxt["ready_frames"] <= frames and nxt["ready_samples"] <= samples:
+            ready.append(w)
+            w += 1
+            nxt = stream_window(plan, w)
+        out.append(ready)
+    return out
+
+
+def used_frames(plan, a, b):
+    """The frames of [a, b) some window reads: f is used iff f - w * stride is one of the plan's inputs for some w >= 0."""
+    stride = int(plan["stride"])
+    inputs = [int(i) for i in plan["inputs"]]
+    return [f for f in range(int(a), int(b)) if any(f >= i and (f - i) % stride == 0 for i in inputs)]
+
+
+def ring_sizes(plan, max_chunk, crop_size, nbins=STFT_N_FFT // 2 + 1):
+    """The two capacities of a GazeStream and their bytes: {"slots": R = observed + max_chunk crops, "crop_bytes": R * 3 * S * S * 4,
+    "ring_cols": one observed span of columns plus the audio of max_chunk frames plus the column close() adds, rounded up to a
+    multiple of 64, "spec_bytes": nbins * ring_cols * 4}."""
+    import math
+    rho = plan["cols_per_frame"]
+    slots = int(plan["observed"]) + int(max_chunk)
+    cols = math.ceil(plan["observed"] * rho) + 1 + math.ceil(int(max_chunk) * rho) + 1
+    cols = (cols + 63) // 64 * 64
+    S = int(crop_size)
+    return {"slots": slots, "crop_bytes": slots * 3 * S * S * 4, "ring_cols": cols, "spec_bytes": int(nbins) * cols * 4}
+
+
+def track_from_windows(results, n_frames, want=("points", "peak", "count", "heatmaps", "rescaled")):
+    """The windows a GazeStream emitted, folded into predict_video's track format by ONE ops.gaze_track call: results (a list of
+    push() / close() results, in any grouping) -> {"points" (n_frames, 2), "peak", "count", "heatmaps", "rescaled", ...} as `want`
+    names them, plus "windows".  fill_track and render_track work on it unchanged.  Targets at or past n_frames are dropped."""
+    import numpy as np
+    import torch
+    from . import ops
+    results = list(results)
+    if not results:
+        raise ValueError("track_from_windows needs at least one emitted window")
+    preds = torch.cat([r["heatmaps"] for r in results], dim=0)
+    target = torch.from_numpy(np.concatenate([np.asarray(r["target_idx"], dtype=np.int64) for r in results])).to(preds.device)
+    track = ops.gaze_track(preds, target, int(n_frames), want=want)
+    track["windows"] = len(results)
+    return track
+
+
+class GazeStream:
+    """Gaze prediction while the recording is still running (reach it through GazePredictor.stream).
+
+    push(frames, wav) takes the next frames and the next 24 kHz samples, in pieces of any size and in any proportion, and returns
+    the windows that piece completes; close() ends the stream.  The windows are plan_stream's: window w starts at frame
+    w * stride, reads the T input frames stream_window names and the audio windows around its centre columns, and runs once both
+    have arrived -- through predictor.predict_batch in groups of `batch` (a short group is padded by repeating its last window,
+    as predict_video pads, so one graph shape serves the stream).  Each result is a dict: "window" (int), "frames_idx" and
+    "target_idx" int64 (T,) numpy, and on the device "points" (T, 2), "peak" (T,), "heatmaps" and "rescaled" (T, S/4, S/4).
+    The points are in the crop's coordinates (short side to S, centre crop; S x S sources as they are), as predict_video's.
+
+    Device memory is two rings, neither of which depends on how long the stream runs (ring_sizes; `capacity` holds the numbers):
+      crops     fp32 (R, 3, S, S), R = observed + max_chunk slots; frame f lives in slot f mod R.  A frame some window reads is
+                resized and normalised ONCE, when it arrives (inputs.stream_ingest); frames no window reads are not touched.
+                Ego4D forecast plan, max_chunk 32, S 256: R = 118, 92.8 MB (a 1088 x 1080 source frame is 3.5 MB: 26 frames).
+      spectrum  fp32 (256, ring_cols), ring_cols = one observed span of columns + the audio of max_chunk frames + 1, rounded up
+                to 64; column f lives at f mod ring_cols.  Ego4D at 30 fps: 832 columns, 852 KB (4.2 s of audio).
+    and the waveform tail the unfinished columns still need (fewer than 240 samples) plus the piece being pushed.
+
+    Frames and audio may run ahead of each other by what the rings hold: a push is worked off in steps -- as many samples as the
+    spectrum ring takes, at most max_chunk frames as the crop ring takes them, then every window that is ready -- so no slot or
+    column is overwritten before the last window that reads it has run, and a push far longer than max_chunk is fine.  When
+    neither ring can take more and no window is ready, the push raises a ValueError that names the capacity, BEFORE anything of
+    that push is consumed; nothing is ever overwritten silently.  The windows that become ready in one step form that step's groups.
+
+    Difference from predict_video: predict_video scales audio positions by the whole recording's cols / n, which a stream cannot
+    know; the stream uses cols_per_frame = 200 / fps, so the centres may differ by a column or two (they agree exactly when
+    cols * den == num * n).  Equality with predict_video is therefore not claimed; each window equals, bit for bit, the
+    composition clip_sample + stft_logpower + audio_windows_at + predict_batch at stream_window's indices and the same batch.
+
+    Out of scope: sample_rate other than 24 kHz (chunk-wise resampling needs filter state: ValueError), attention maps, and fill /
+    overlay inside the stream (fold the results with track_from_windows, then fill_track / render_track)."""
+
+    def __init__(self, predictor, fps=None, stride=None, segment=None, batch=1, max_chunk=32, pixel_format="rgb24",
+                 matrix="bt601", full_range=False, sample_rate=None):
+        check_stream_rate(sample_rate)
+        from . import inputs
+        self.fmt = {}
+        if inputs.check_pixel_format(pixel_format, matrix, full_range)[0]:
+            self.fmt = {"pixel_format": pixel_format, "matrix": matrix, "full_range": bool(full_range)}
+        self.batch, self.max_chunk = int(batch), int(max_chunk)
+        if self.batch < 1 or self.max_chunk < 1:
+            raise ValueError(f"batch and max_chunk must be positive, got {batch} and {max_chunk}")
+        self.predictor = predictor
+        cfg = predictor.cfg
+        self.plan = plan_stream(cfg, fps=fps, stride=stride, segment=segment)
+        self.S, self.T = int(cfg.DATA.TEST_CROP_SIZE), int(cfg.DATA.NUM_FRAMES)
+        self.mean, self.std = tuple(cfg.DATA.MEAN), tuple(cfg.DATA.STD)
+        self.capacity = ring_sizes(self.plan, self.max_chunk, self.S)
+        self.R, self.ring_cols = self.capacity["slots"], self.capacity["ring_cols"]
+        self.frames = self.samples = self.cols = 0          # pushed so far; columns [0, cols) are final
+        self.next_window, self.dropped, self.closed = 0, 0, False
+        self.hw = None
+        self._next = stream_window(self.plan, 0)
+        self._crops = self._spec = self._tail = self._params = None
+        self._tail_base = 0                                  # the stream position of _tail[0]
+
+    # ---- host arithmetic -------------------------------------------------------------------------------------------------------
+    def _limits(self, nxt):
+        """(frames, samples) the rings take while window `nxt` is the oldest one that has not run."""
+        frames_max = int(nxt["frames_idx"][0]) + self.R                   # frame f overwrites f - R < the window's first input
+        cols_max = nxt["first_column"] + self.ring_cols - 1               # one column is kept free for close()
+        return frames_max, STFT_HOP * cols_max + STFT_HOP - 1
+
+    def _steps(self, k, m):
+        """The steps a push of k frames and m samples is worked off in: [(frames, samples, [windows])]; ValueError when stuck."""
+        frames, samples, w, nxt = self.frames, self.samples, self.next_window, self._next
+        steps = []
+        while True:
+            frames_max, samples_max = self._limits(nxt)
+            dm = max(0, min(m, samples_max - samples))
+            dk = max(0, min(k, self.max_chunk, frames_max - frames))
+            frames, samples, k, m = frames + dk, samples + dm, k - dk, m - dm
+            ready = []
+            while nxt["ready_frames"] <= frames and nxt["ready_samples"] <= samples:
+                ready.append(w)
+                w += 1
+                nxt = stream_window(self.plan, w)
+            if dk or dm or ready:
+                steps.append((dk, dm, ready))
+            if not k and not m:
+                return steps
+            if not (dk or dm or ready):
+                if m:
+                    raise ValueError(f"the audio runs further ahead of the frames than the spectrum ring holds ({self.ring_cols} "
+                                     f"columns = {self.ring_cols * STFT_HOP} samples): window {w} still waits for frame "
+                                     f"{nxt['ready_frames'] - 1}, {frames} pushed; nothing of this push was consumed")
+                raise ValueError(f"the frames run further ahead of the audio than the crop ring holds ({self.R} slots): window {w} "
+                                 f"still waits for sample {nxt['ready_samples'] - 1}, {samples} pushed; nothing of this push was "
+                                 "consumed")
+
+    # ---- device work -----------------------------------------------------------------------------------------------------------
+    def _setup(self, H, W, device):
+        import torch
+        self.hw = (H, W)
+        self._params = torch.tensor(self.predictor._video_params_row(H, W), dtype=torch.int32, device=device)
+        self._crops = torch.zeros(self.R, 3, self.S, self.S, dtype=torch.float32, device=device)
+
+    def _audio(self, piece, n_total=-1):
+        """Take the next samples (a device tensor, possibly empty) and compute the columns they complete."""
+        import torch
+        from . import inputs
+        if self._spec is None:
+            self._spec = torch.zeros(STFT_N_FFT // 2 + 1, self.ring_cols, dtype=torch.float32, device=piece.device)
+        buf = piece if self._tail is None else torch.cat([self._tail, piece])
+        self.samples += piece.numel()
+        cols = self.samples // STFT_HOP                     # column f is final once sample 120 f + 119 is in
+        if n_total >= 0:                                    # the signal ended: the columns of the offline STFT (csts_stft_frames)
+            cols = max(cols, 1 + (self.samples + 2 * (STFT_N_FFT // 2) - STFT_N_FFT) // STFT_HOP)
+        for f0 in range(self.cols, cols, self.ring_cols):   # at most one turn of the ring per launch
+            inputs.stream_stft(buf.contiguous(), self._tail_base, f0, min(f0 + self.ring_cols, cols), self._spec, n_total=n_total)
+        self.cols = max(self.cols, cols)
+        keep = max(0, STFT_HOP * self.cols + (STFT_N_FFT - STFT_WIN) // 2 - STFT_N_FFT // 2)      # first sample column `cols` reads
+        keep = max(keep, self._tail_base)
+        self._tail = buf[keep - self._tail_base:].clone()
+        self._tail_base = keep
+
+    def _ingest(self, chunk):
+        import torch
+        from . import inputs
+        a = self.frames
+        used = used_frames(self.plan, a, a + chunk.shape[0])
+        if used:
+            pairs = torch.tensor([[f - a, f % self.R] for f in used], dtype=torch.int32, device=chunk.device)
+            inputs.stream_ingest(chunk, pairs, self._params, self._crops, mean=self.mean, std=self.std, **self.fmt)
+        self.frames += chunk.shape[0]
+
+    def _run(self, windows):
+        import numpy as np
+        import torch
+        from . import inputs
+        dev = self._crops.device
+        S, T, nb = self.S, self.T, self.batch
+        results = []
+        for g in range(0, len(windows), nb):
+            group = [stream_window(self.plan, w) for w in windows[g:g + nb]]
+            rows = group + [group[-1]] * (nb - len(group))              # pad by repeating the last window
+            slots = np.stack([r["frames_idx"] % self.R for r in rows]).astype(np.int32)
+            centers = np.stack([r["audio_centers"] for r in rows]).astype(np.int64)
+            video = inputs.stream_gather(self._crops, torch.from_numpy(slots).to(dev))
+            audio = inputs.stream_audio_windows(self._spec, self.cols - 1, torch.from_numpy(centers).to(dev), centers, AUDIO_WIDTH)
+            if S != AUDIO_WIDTH:   # S frequency bins x S columns around each frame, as predict_video cuts them
+                o = (AUDIO_WIDTH - S) // 2
+                audio = audio[:, :, :, :S, o:o + S].contiguous()
+            out = self.predictor.predict_batch({"video": video, "audio": audio})
+            for i, r in enumerate(group):
+                results.append({"window": r["window"], "frames_idx": r["frames_idx"], "target_idx": r["target_idx"],
+                                "points": out["points"][i], "peak": out["peak"][i], "heatmaps": out["heatmaps"][i],
+                                "rescaled": out["rescaled"][i]})
+        self.next_window = windows[-1] + 1
+        self._next = stream_window(self.plan, self.next_window)
+        return results
+
+    # ---- the interface ---------------------------------------------------------------------------------------------------------
+    def push(self, frames=None, wav=None):
+        """The next frames -- uint8 (K, H, W, 3), or (K, H * 3 / 2, W) in the stream's pixel format -- and / or the next samples --
+        fp32 (m,) at 24 kHz -- both on the device -> the list (possibly empty) of the windows this push completes, in order."""
+        import torch
+        from . import lib as L
+        from .infer import _picture_hw
+        if self.closed:
+            raise ValueError("the stream is closed: push() after close()")
+        for t in (frames, wav):
+            if t is not None and (not torch.is_tensor(t) or not t.is_cuda):
+                raise L.CstsError("GazeStream runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
+        k = m = 0
+        if frames is not None:
+            H, W, _ = _picture_hw(frames, 1, self.fmt.get("pixel_format", "rgb24"), self.fmt.get("matrix", "bt601"),
+                                  self.fmt.get("full_range", False))
+            if self.hw is not None and (H, W) != self.hw:
+                raise ValueError(f"the stream's frames are {self.hw[0]} x {self.hw[1]} (fixed by the first push), got {H} x {W}")
+            k = frames.shape[0]
+        if wav is not None:
+            if wav.dim() != 1 or wav.dtype != torch.float32:
+                raise ValueError(f"wav must be an fp32 (m,) waveform at {AUDIO_RATE} Hz, got {tuple(wav.shape)} {wav.dtype}")
+            m = wav.numel()
+        steps = self._steps(k, m)                            # raises before anything is consumed
+        results = []
+        fa = sa = 0
+        with torch.no_grad(), torch.cuda.device(self.predictor.device):
+            if k and self.hw is None:
+                self._setup(H, W, frames.device)
+            for dk, dm, ready in steps:
+                if dm:
+                    self._audio(wav[sa:sa + dm])
+                    sa += dm
+                if dk:
+                    self._ingest(frames[fa:fa + dk])
+                    fa += dk
+                if ready:
+                    results += self._run(ready)
+        return results
+
+    def close(self, wav_pad=True):
+        """End the stream.  wav_pad: the column the offline STFT adds at the end of a waveform whose length is no multiple of the
+        hop -- zeros past the last sample -- is computed, and the windows it completes are returned.  Windows that began (their
+        first input frame was pushed) but still miss frames or audio are dropped and counted in `dropped`.  After close(), push()
+        is an error."""
+        import torch
+        if self.closed:
+            raise ValueError("the stream is closed already")
+        self.closed = True
+        results = []
+        with torch.no_grad(), torch.cuda.device(self.predictor.device):
+            if wav_pad and self._tail is not None:
+                self._audio(self._tail[:0], n_total=self.samples)
+            ready, w, nxt = [], self.next_window, self._next
+            while self._crops is not None and nxt["ready_frames"] <= self.frames and \
+                    int(nxt["audio_centers"].max()) + HALF_WIDTH <= self.cols:
+                ready.append(w)
+                w += 1
+                nxt = stream_window(self.plan, w)
+            if ready:
+                results = self._run(ready)
+        w = self.next_window
+        while int(stream_window(self.plan, w)["frames_idx"][0]) < self.frames:
+            self.dropped += 1
+            w += 1
+        return results

@@ -32,7 +32,7 @@ enum { CSTS_EPI_NONE = 0, CSTS_EPI_GELU = 1, CSTS_EPI_DGELU = 2 };
 enum { CSTS_MASK_NONE = 0, CSTS_MASK_SPATIAL = 1 };
 
 /* Version of this header's struct layouts and call semantics.  Bumped whenever a struct grows or a field changes meaning
- * (2: csts_gemm_args.res_up; 3: compact k|v rows, 16-bit build, loss scaler in csts_opt_args; 4: csts_opt_args.extra_sq, factored AdamW; 5: grouped stencil weight gradients; 6: csts_copy_token_segments, csts_wgrad_grouped8_limited; 7: csts_wgrad_grouped5, csts_gemm algo 500; 8: csts_opt_rule, csts_opt_step, csts_opt_factored_step, csts_opt_factored.tensor replaces pad_; 10: csts_audio_pixel_attn; 11: csts_attention_track, csts_attention_rescale; 12: csts_resample_wav, csts_resample_len; 13: csts_attn_route; 14: 4:2:0 frames, csts_yuv_to_rgb, csts_*_sample_yuv).  csts_abi_version() returns the value the
+ * (2: csts_gemm_args.res_up; 3: compact k|v rows, 16-bit build, loss scaler in csts_opt_args; 4: csts_opt_args.extra_sq, factored AdamW; 5: grouped stencil weight gradients; 6: csts_copy_token_segments, csts_wgrad_grouped8_limited; 7: csts_wgrad_grouped5, csts_gemm algo 500; 8: csts_opt_rule, csts_opt_step, csts_opt_factored_step, csts_opt_factored.tensor replaces pad_; 10: csts_audio_pixel_attn; 11: csts_attention_track, csts_attention_rescale; 12: csts_resample_wav, csts_resample_len; 13: csts_attn_route; 14: 4:2:0 frames, csts_yuv_to_rgb, csts_*_sample_yuv; still 14: csts_stream_* (new entry points only, no struct or call changed)).  csts_abi_version() returns the value the
  * LIBRARY was built with: a caller must compare it with the CSTS_ABI_VERSION it was compiled against and refuse a mismatch
  * (the Python binding does, csts_amd/lib.py::load). */
 #define CSTS_ABI_VERSION 14
@@ -832,6 +832,40 @@ int csts_attention_track(const float* column, const int* order, const int* offse
  *      (f, g); no allocation, no synchronisation, no host read: graph-capturable. */
 int csts_attention_rescale(const float* mixed, const int* valid, int nmaps_per_frame, int64_t F, int h, int w, int S, float* maps,
                            float* range, hipStream_t stream);
+
+/* ---- live stream (csts_amd/csrc/stream.hip, csts_amd/stream.py): frames and audio of an endless recording arrive in pieces; what
+ *      the windows read lives in two device rings whose size does not depend on the length of the stream.  Every table below is
+ *      DEVICE memory read when the kernel runs; no atomics, no allocation, no synchronisation.
+ *      stream_stft: columns [f0, f1) of csts_stft_logpower's spectrogram of the endless signal, column f written to
+ *        ring[bin][f mod ring_cols]; ring fp32 (n_fft / 2 + 1, ring_cols).  buf holds the samples [s_base, s_base + m) of the signal.
+ *        Column f reads the samples [f hop + (n_fft - win) / 2 - n_fft / 2, + win) (= [120 f - 120, 120 f + 120) for 511 / 120 / 240);
+ *        samples before 0 are zero and, with n_total >= 0 (the signal ended after n_total samples), so are those at or past n_total,
+ *        which is what csts_stft_logpower does at the two ends of a waveform; n_total < 0: the signal goes on.  A column that needs
+ *        any other sample outside the buffer is refused (-1) before launch, as are f1 - f0 > ring_cols and n_total > s_base + m.
+ *        The arithmetic of a column is csts_stft_logpower's, term for term (one device function, stft_shared.h): column f equals
+ *        column f of the spectrogram of the whole signal bit for bit.
+ *      stream_audio_windows: out (B, 1, T, nbins, width), window (b, t) = ring columns (centers[b][t] - width / 2 + j) mod ring_cols,
+ *        j in [0, width); centers int64 [B][T] are GLOBAL column numbers and newest is the last column written.  A window that does
+ *        not lie wholly inside the live span [max(newest - ring_cols + 1, 0), newest] is NaN and reads nothing.  width even and
+ *        <= ring_cols, B * T <= 65535.
+ *      stream_ingest / stream_ingest_yuv: pairs int32 [npairs][2] = (frame in chunk, slot): frame pairs[p][0] of the chunk -- uint8
+ *        (K, H, W, 3), or (K, H * 3 / 2, W) in a 4:2:0 layout -- is sampled into ring[slot] of the crop ring fp32 (R, 3, S, S) by the
+ *        pixel rule of csts_clip_sample / csts_clip_sample_yuv under the ONE parameter row params int32 [5]: ring[slot] equals
+ *        csts_clip_sample(...)[0, :, 0] of that frame bit for bit.  A chunk frame no pair names is not read and no other slot is
+ *        written.  A pair with the frame outside [0, K) or the slot outside [0, R) writes nothing; bad params give a NaN slot.  No
+ *        byte at or past the end of the chunk is read; chunk and ring 16-byte aligned, W <= 6000, 1 <= npairs <= 65535.
+ *      stream_gather: out fp32 (B, 3, T, S, S), out[b][:, t] = ring[slots[b][t]]; slots int32 [B][T]; a slot outside [0, R) gives
+ *        a NaN frame and reads nothing.  T <= 64, B <= 65535. */
+int csts_stream_stft(const float* buf, int64_t s_base, int64_t m, int64_t n_total, int64_t f0, int64_t f1, float* ring, int ring_cols,
+                     int n_fft, int hop, int win, float eps, hipStream_t stream);
+int csts_stream_audio_windows(const float* ring, int ring_cols, int64_t newest, const int64_t* centers, float* out, int B, int T,
+                              int nbins, int width, hipStream_t stream);
+int csts_stream_ingest(const uint8_t* chunk_khwc, int K, int H, int W, const int* pairs, int npairs, const int* params, float* ring,
+                       int R, int S, const float mean[3], const float std[3], hipStream_t stream);
+int csts_stream_ingest_yuv(const uint8_t* chunk_yuv, int K, int H, int W, const int* pairs, int npairs, const int* params, float* ring,
+                           int R, int S, const float mean[3], const float std[3], int layout, int matrix, int full_range,
+                           hipStream_t stream);
+int csts_stream_gather(const float* ring, int R, const int* slots, float* out, int B, int T, int S, hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -46,7 +46,13 @@ were.
 with a pixel_format entry ("nv12" or "i420") and optionally yuv_matrix ("bt601", the default, or "bt709") and yuv_full_range;
 --pixel-format, --yuv-matrix and --yuv-full-range override the entries.  The pictures are uploaded and sampled in that format
 (half the bytes of RGB); overlays stay RGB uint8 (N, H, W, 3).  An npz holding both frames_u8 and frames_yuv is an error.  The
-json_stats line then carries "pixel_format"."""
+json_stats line then carries "pixel_format".
+--stream [--chunk K] (with --video): the recording is replayed through csts_amd.GazeStream (GazePredictor.stream) in pushes of K
+frames (default 8) with the matching audio -- the samples up to frame_end * 24000 / fps, the rest with the last push -- as a live
+source would deliver it, and closed.  --out receives the same entries as --video, the track folded from the emitted windows by
+csts_amd.track_from_windows, plus stream_windows (the window numbers, in the order they were emitted) and stream_dropped; the
+json_stats line gains "stream", "chunk" and "dropped".  --fps must then be integral (a stream places its audio by the exact ratio of
+columns to frames) and the audio at 24 kHz; --overlay, --fill and the attention flags are not part of the stream."""
 import argparse
 import json
 import os
@@ -92,6 +98,8 @@ def parse_args(argv=None):
                    help="colour matrix of frames_yuv (default: the npz entry yuv_matrix, else bt601)")
     p.add_argument("--yuv-full-range", default=None, type=int, choices=[0, 1],
                    help="1: frames_yuv is full range, 0: limited (default: the npz entry yuv_full_range, else limited)")
+    p.add_argument("--stream", action="store_true", help="with --video: replay the recording through GazePredictor.stream")
+    p.add_argument("--chunk", default=None, type=int, help="with --stream: frames per push (default 8)")
     p.add_argument("--seed", default=2000, type=int, help="seed of the synthetic batch used without --clip")
     p.add_argument("--batch", default=2, type=int, help="clips in the synthetic batch used without --clip")
     p.add_argument("--no-graph", action="store_true", help="launch the kernels eagerly instead of replaying a HIP graph")
@@ -123,6 +131,15 @@ def parse_args(argv=None):
         p.error("--max-gap must be positive")
     if args.overlay_every < 1:
         p.error("--overlay-every must be positive")
+    if args.stream and args.video is None:
+        p.error("--stream replays a recording as a live stream: it needs --video")
+    if args.chunk is not None and not args.stream:
+        p.error("--chunk is the push size of --stream")
+    if args.chunk is not None and args.chunk < 1:
+        p.error("--chunk must be positive")
+    if args.stream and (args.overlay or args.overlay_dir or args.fill or args.attention_track or args.attention_overlay is not None):
+        p.error("--stream emits windows as they complete: --overlay, --fill and the attention flags are not part of it (fold the "
+                "windows with csts_amd.track_from_windows, then fill_track / render_track)")
     if args.sample_rate is not None and args.sample_rate < 1:
         p.error("--sample-rate must be positive")
     if (args.pixel_format or args.yuv_matrix or args.yuv_full_range is not None) and args.video is None and args.clip is None:
@@ -163,6 +180,27 @@ def waveform(z, rate, dev):
     """wav of an opened npz on the device: fp32 as before without a rate; with one, int16 stays int16 (the kernel scales it)."""
     wav = torch.from_numpy(z["wav"])
     return (wav if rate is not None and wav.dtype == torch.int16 else wav.float()).to(dev)
+
+
+def replay_stream(predictor, frames, wav, fps, stride, chunk, fmt):
+    """The recording pushed through GazePredictor.stream in pushes of `chunk` frames with the matching audio, then closed ->
+    (the track by track_from_windows with "windows" = their number, the window numbers in emission order, the dropped count)."""
+    from fractions import Fraction
+    from csts_amd import track_from_windows
+    stream = predictor.stream(fps=fps, stride=stride, **fmt)
+    N, n = frames.shape[0], wav.shape[0]
+    per = Fraction(AUDIO_RATE) / stream.plan["fps"]                  # samples per frame
+    results, sent = [], 0
+    for a in range(0, N, chunk):
+        b = min(a + chunk, N)
+        upto = n if b == N else min(n, int(b * per))
+        results += stream.push(frames[a:b], wav[sent:upto] if upto > sent else None)
+        sent = max(sent, upto)
+    results += stream.close()
+    if not results:
+        raise SystemExit(f"the stream of {N} frames and {n} samples completed no window (one window observes "
+                         f"{stream.plan['observed']} frames)")
+    return track_from_windows(results, N), [r["window"] for r in results], stream.dropped
 
 
 def write_pngs(overlay, directory, every):
@@ -219,9 +257,19 @@ def main(argv=None):
             fps = args.fps if args.fps is not None else (float(z["fps"]) if "fps" in z.files else None)
             rate = source_rate(z, args, args.video)
             frames, fmt = torch.from_numpy(pics[0]).to(dev), pics[1]
-            out = predictor.predict_video(frames, waveform(z, rate, dev), sample_rate=rate,
-                                          fps=fps, stride=args.stride, overlay=bool(args.overlay or args.overlay_dir),
-                                          fill=args.fill, max_gap=args.max_gap, attention_track=attention_track, **fmt)
+            if args.stream:
+                if rate is not None and rate != AUDIO_RATE:
+                    raise SystemExit(f"--stream takes the audio at {AUDIO_RATE} Hz, {args.video} is at {rate} Hz: resampling chunk by "
+                                     "chunk needs filter state carried between pushes")
+                try:
+                    out, stream_windows, dropped = replay_stream(predictor, frames, waveform(z, None, dev), fps, args.stride,
+                                                                 8 if args.chunk is None else args.chunk, fmt)
+                except ValueError as e:
+                    raise SystemExit(str(e))
+            else:
+                out = predictor.predict_video(frames, waveform(z, rate, dev), sample_rate=rate,
+                                              fps=fps, stride=args.stride, overlay=bool(args.overlay or args.overlay_dir),
+                                              fill=args.fill, max_gap=args.max_gap, attention_track=attention_track, **fmt)
             if args.attention_overlay is not None:
                 head = None if args.attention_overlay == "mean" else int(args.attention_overlay)
                 out["attention_overlay"] = predictor.render_attention_track(frames, out, head=head, points=out["points"], **fmt)
@@ -233,6 +281,9 @@ def main(argv=None):
             keys += ("attention_overlay",) if args.attention_overlay is not None else ()
         arrays = {k: out[k].cpu().numpy() for k in keys}
         rates = {} if rate is None else {"sample_rate": np.int64(rate), "audio_rate": np.int64(AUDIO_RATE)}
+        if args.stream:
+            arrays["stream_windows"] = np.asarray(stream_windows, dtype=np.int64)
+            arrays["stream_dropped"] = np.int64(dropped)
         np.savez(args.out, **arrays, **rates)
         if args.overlay_dir is not None:
             write_pngs(arrays["overlay"], args.overlay_dir, args.overlay_every)
@@ -246,6 +297,8 @@ def main(argv=None):
             record["pixel_format"] = fmt["pixel_format"]
         if args.fill is not None:
             record.update({"fill": args.fill, "max_gap": int(out["max_gap"]), "filled_frames": int(arrays["filled"].sum())})
+        if args.stream:
+            record.update({"stream": True, "chunk": 8 if args.chunk is None else args.chunk, "dropped": int(dropped)})
         if attention_track:
             frames = arrays["attention_count"] > 0
             if args.fill is not None:
