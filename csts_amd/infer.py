@@ -485,15 +485,19 @@ class GazePredictor:
         return res
 
     def stream(self, fps=None, stride=None, segment=None, batch=1, max_chunk=32, pixel_format="rgb24", matrix="bt601",
-               full_range=False, sample_rate=None):
+               full_range=False, sample_rate=None, input_rate=None):
         """A live stream on this predictor (csts_amd.stream.GazeStream): push(frames, wav) takes frames and 24 kHz audio in whatever
         pieces they arrive and returns the windows each piece completes; close() ends it.  The windows are plan_stream's (fps an
         int or a Fraction, stride in frames); `batch` windows run per predict_batch call; `max_chunk` sizes the two device rings,
         which do not grow with the stream (GazeStream states the capacities).  pixel_format "nv12" | "i420": the pushed frames
-        are 4:2:0 pictures.  sample_rate: None or 24000; another rate is a ValueError (chunk-wise resampling needs filter state)."""
+        are 4:2:0 pictures.  input_rate=R: the audio is pushed at R Hz, (m,) or (C, m), floating or int16, and resampled to 24 kHz
+        mono on the device with the filter state carried from push to push (inputs.StreamResampler): the track of
+        inputs.resample_audio on the whole waveform, bit for bit.  sample_rate: None or 24000, the audio as it is; another rate
+        there is a ValueError (it keeps no filter state), and so are both keywords together."""
         from .stream import GazeStream
         return GazeStream(self, fps=fps, stride=stride, segment=segment, batch=batch, max_chunk=max_chunk,
-                          pixel_format=pixel_format, matrix=matrix, full_range=full_range, sample_rate=sample_rate)
+                          pixel_format=pixel_format, matrix=matrix, full_range=full_range, sample_rate=sample_rate,
+                          input_rate=input_rate)
 
     @torch.no_grad()
     def _video_params_row(self, H, W):

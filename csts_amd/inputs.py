@@ -138,6 +138,129 @@ def resample_audio(wav: torch.Tensor, sample_rate, target_rate=AUDIO_RATE, zeros
     return out[0] if wav.dim() == 1 else out
 
 
+def resample_ready(n_in: int, up: int, down: int, half: int, closed: bool = False) -> int:
+    """The outputs of resample_audio's rule that are final after n_in inputs (csts_resample_ready): output m reads the inputs up
+    to floor((m down + half) / up), so an open stream has max(0, floor((n_in up - half - 1) / down) + 1) of them; a stream that
+    ended at n_in has them all, ceil(n_in up / down)."""
+    n_in, up, down, half = int(n_in), int(up), int(down), int(half)
+    if closed:
+        return -(-n_in * up // down)
+    return max(0, (n_in * up - half - 1) // down + 1)
+
+
+def resample_first_input(m: int, up: int, down: int, half: int) -> int:
+    """The first input output m reads (csts_resample_first_input): max(ceil((m down - half) / up), 0)."""
+    return max(-(-(int(m) * int(down) - int(half)) // int(up)), 0)
+
+
+def resample_inputs_for(m_out: int, up: int, down: int, half: int) -> int:
+    """The least n_in with resample_ready(n_in) >= m_out: how many source samples an open stream needs before its first m_out
+    outputs are final (a window's ready_samples at 24 kHz -> the source samples it waits for).  0 for m_out <= 0."""
+    m_out = int(m_out)
+    return 0 if m_out <= 0 else ((m_out - 1) * int(down) + int(half)) // int(up) + 1
+
+
+class StreamResampler:
+    """resample_audio on a stream that arrives in pieces: push(piece) returns the 24 kHz samples that piece makes final, close()
+    the rest, and torch.cat([*pushes, close()]) equals resample_audio of the whole waveform bit for bit, however it was cut
+    (csts_resample_stream runs csts_resample_wav's kernel on the kept tail + the piece, at the stream's positions).
+
+    Pieces are (m,) or (C, m), floating or int16, on the device, m >= 0; the first push fixes `channels` and `dtype`.  The state
+    carried between pushes is the tail of the input the unfinished outputs still read, (C, tail) in the input's type with
+    tail <= 2 half / up + 2 (42 samples at 48 kHz, 162 at 192 kHz): int16 stays int16 and the downmix happens in the kernel.  A
+    push is one torch.cat and one launch, with no host synchronisation.  `consumed` / `produced` count inputs and outputs so far;
+    produced == resample_ready(consumed) until close().  sample_rate == target_rate with (m,) fp32 pieces hands the pieces
+    through untouched and without delay, as resample_audio returns its argument; any other form at that rate goes through the
+    1/1 filter like the offline path."""
+
+    def __init__(self, sample_rate, target_rate=AUDIO_RATE, zeros: int = 10, beta: float = 5.0):
+        _, self.up, self.down, self.half = resample_rule(sample_rate, target_rate, zeros, beta)
+        self._key = (int(sample_rate), int(target_rate), int(zeros), float(beta))
+        self.consumed = self.produced = 0
+        self.channels = self.dtype = None
+        self.closed = False
+        self._mono = self._device = None          # the rank of the pieces, (m,) or (C, m), and their device: the first push's
+        self._tail, self._tail_base = None, 0     # (C, tail) of the input and the stream position of its first sample
+
+    def _through(self, wav=None):
+        """Pieces pass through untouched: the ratio is 1/1 and they are (m,) fp32."""
+        if self.up != self.down:
+            return False
+        if self.dtype is not None:
+            return self._mono and self.dtype == torch.float32
+        return wav is not None and wav.dim() == 1 and wav.dtype == torch.float32
+
+    def check(self, wav) -> int:
+        """The samples per channel of a piece push() would take; ValueError / CstsError otherwise.  Changes nothing."""
+        if self.closed:
+            raise ValueError("the resampler is closed: push() after close()")
+        if not torch.is_tensor(wav) or wav.dim() not in (1, 2) or not (wav.is_floating_point() or wav.dtype == torch.int16):
+            raise ValueError("a piece must be a floating or int16 tensor (m,) or (C, m), got "
+                             f"{tuple(wav.shape) if torch.is_tensor(wav) else type(wav)} {getattr(wav, 'dtype', '')}")
+        _gpu(wav)
+        C = 1 if wav.dim() == 1 else wav.shape[0]
+        if C < 1 or C > 64:
+            raise ValueError(f"a piece holds 1 <= C <= 64 channels, got {tuple(wav.shape)}")
+        if self.dtype is not None and (wav.dtype != self.dtype or C != self.channels or (wav.dim() == 1) != self._mono):
+            raise ValueError(f"the stream's pieces are {'(m,)' if self._mono else f'({self.channels}, m)'} {self.dtype} (fixed by "
+                             f"the first push), got {tuple(wav.shape)} {wav.dtype}")
+        if self.consumed + wav.shape[-1] > L.RESAMPLE_MAX_N:
+            raise ValueError(f"a stream holds at most {L.RESAMPLE_MAX_N} samples")
+        return int(wav.shape[-1])
+
+    def count(self, m: int, like=None) -> int:
+        """How many outputs a push of m more samples would return: host arithmetic, no device work, no state change.  like: the
+        piece itself, which a 1/1 stream needs before its first push to tell whether pieces pass through."""
+        m = int(m)
+        if m < 0:
+            raise ValueError(f"a piece holds m >= 0 samples, got {m}")
+        if self._through(like):
+            return m
+        return resample_ready(self.consumed + m, self.up, self.down, self.half) - self.produced
+
+    def _launch(self, buf, n_total, m1):
+        out = torch.empty(m1 - self.produced, dtype=torch.float32, device=buf.device)
+        if m1 > self.produced:
+            taps = resample_filter(*self._key, buf.device)[0]
+            with torch.cuda.device(buf.device):
+                L.check(L.load().csts_resample_stream(buf.data_ptr(), L.WAV_I16 if buf.dtype == torch.int16 else L.WAV_F32,
+                                                      buf.shape[0], buf.shape[1], self._tail_base, n_total, taps.data_ptr(), self.up,
+                                                      self.down, self.half, self.produced, m1, out.data_ptr(), _s()),
+                        "csts_resample_stream")
+        self.produced = m1
+        return out
+
+    def push(self, wav: torch.Tensor) -> torch.Tensor:
+        """The next piece -> the fp32 (count(m),) outputs it makes final (possibly none)."""
+        m = self.check(wav)
+        if self.dtype is None:
+            self.dtype, self.channels, self._mono = wav.dtype, 1 if wav.dim() == 1 else wav.shape[0], wav.dim() == 1
+            self._device = wav.device
+        if self._through():
+            self.consumed += m
+            self.produced += m
+            return wav
+        x = wav if wav.dtype in (torch.float32, torch.int16) else wav.float()
+        x = x.reshape(1, -1) if x.dim() == 1 else x
+        buf = torch.cat([self._tail, x], dim=1) if self._tail is not None else torch.cat([x], dim=1)
+        self.consumed += m
+        out = self._launch(buf, -1, resample_ready(self.consumed, self.up, self.down, self.half))
+        keep = max(resample_first_input(self.produced, self.up, self.down, self.half), self._tail_base)
+        self._tail, self._tail_base = buf[:, keep - self._tail_base:], keep      # a view: the next push copies it into its buffer
+        return out
+
+    def close(self) -> torch.Tensor:
+        """End the stream -> the remaining outputs, up to ceil(consumed up / down) (none for a stream that never got a sample)."""
+        if self.closed:
+            raise ValueError("the resampler is closed already")
+        self.closed = True
+        if self._tail is None or self._tail.shape[1] == 0:                        # no sample yet, or pieces that pass through
+            return torch.empty(0, dtype=torch.float32, device=self._device)
+        out = self._launch(self._tail.contiguous(), self.consumed, resample_ready(self.consumed, self.up, self.down, self.half, True))
+        self._tail = None
+        return out
+
+
 def audio_windows(spec: torch.Tensor, frames_idx: torch.Tensor, frame_length: float, width: int = 256) -> torch.Tensor:
     """(B, nbins, cols) spectrogram + per-clip frame indices (B, T) -> (B, 1, T, nbins, width) windows centred at
     round(idx / frame_length * cols), clipped to the valid range (ego4d_avgaze_forecast.py:216-219)."""

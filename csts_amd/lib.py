@@ -268,6 +268,9 @@ SYMBOLS = {
     "csts_audio_gather": (_I, [vp, vp, vp, vp, _I, _I, _I, _I, vp]),
     "csts_resample_len": (i64, [i64, _I, _I]),
     "csts_resample_wav": (_I, [vp, _I, _I, _I, i64, vp, _I, _I, _I, vp, vp]),
+    "csts_resample_ready": (i64, [i64, _I, _I, _I, _I]),
+    "csts_resample_first_input": (i64, [i64, _I, _I, _I]),
+    "csts_resample_stream": (_I, [vp, _I, _I, i64, i64, i64, vp, _I, _I, _I, i64, i64, vp, vp]),
     "csts_yuv_to_rgb": (_I, [vp, vp, i64, _I, _I, _I, _I, _I, vp]),
     "csts_yuv_to_rgb_host": (_I, [vp, vp, i64, _I, _I, _I, _I, _I]),
     "csts_spatial_sample_yuv": (_I, [vp, vp, vp, _I, _I, _I, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),

@@ -18,13 +18,15 @@ HALF_WIDTH = AUDIO_WIDTH // 2
 
 
 def check_stream_rate(sample_rate):
-    """The sample rate of a stream's audio: None or 24000.  Any other rate is a ValueError: resampling chunk by chunk needs the
-    filter's state carried from push to push, which inputs.resample_audio (one whole waveform per call) does not keep."""
+    """The sample_rate= of a stream, the rate its audio is pushed at as it is: None or 24000.  Any other rate is a ValueError:
+    resampling chunk by chunk needs the filter's state carried from push to push, which sample_rate= does not do; input_rate=
+    (inputs.StreamResampler) does."""
     if sample_rate is None:
         return AUDIO_RATE
     if isinstance(sample_rate, bool) or not isinstance(sample_rate, numbers.Integral) or int(sample_rate) != AUDIO_RATE:
         raise ValueError(f"a stream takes its audio at {AUDIO_RATE} Hz, got sample_rate {sample_rate!r}: resampling chunk by chunk "
-                         "needs filter state carried between pushes, which is not implemented; resample the pieces yourself or use "
+                         "needs filter state carried between pushes, which sample_rate= does not keep: open the stream with "
+                         f"input_rate={sample_rate!r} instead (inputs.StreamResampler carries the state), or use "
                          "predict_video(sample_rate=...) on a finished recording")
     return AUDIO_RATE
 
@@ -102,10 +104,23 @@ def stream_window(plan, w):
             "ready_samples": int(STFT_HOP * (int(centers.max()) + HALF_WIDTH))}
 
 
-def stream_schedule(plan, pushes):
+def stream_schedule(plan, pushes, input_rate=None):
     """Which windows each push completes.  pushes: a list of (frames, samples) counts, one pair per push; returns one list of
     window numbers per push.  Window w is ready in the first push after which ready_frames(w) frames and ready_samples(w) samples
-    have been pushed in total; windows are emitted in order, every window once."""
+    have been pushed in total; windows are emitted in order, every window once.  input_rate: the sample counts are at that rate,
+    as a GazeStream(input_rate=...) takes them; each is first converted to the 24 kHz samples the push makes final (differences
+    of inputs.resample_ready over the running total; at 24000 Hz the pieces count as mono fp32, which pass through)."""
+    if input_rate is not None:
+        from .inputs import check_sample_rate, resample_ready, resample_rule
+        _, up, down, half = resample_rule(check_sample_rate(input_rate, "input_rate"))
+        total, converted = 0, []
+        for k, m in pushes:
+            if int(m) < 0:
+                raise ValueError(f"a push holds counts >= 0, got ({k}, {m})")
+            before = total
+            total += int(m)
+            converted.append((k, int(m) if up == down else resample_ready(total, up, down, half) - resample_ready(before, up, down, half)))
+        pushes = converted
     frames = samples = 0
     w = 0
     nxt = stream_window(plan, 0)
@@ -166,8 +181,13 @@ class GazeStream:
     """Gaze prediction while the recording is still running (reach it through GazePredictor.stream).
 
     push(frames, wav) takes the next frames and the next 24 kHz samples, in pieces of any size and in any proportion, and returns
-    the windows that piece completes; close() ends the stream.  The windows are plan_stream's: window w starts at frame
-    w * stride, reads the T input frames stream_window names and the audio windows around its centre columns, and runs once both
+    the windows that piece completes; close() ends the stream.  With input_rate=R the samples are pushed at R Hz instead, (m,)
+    or (C, m), floating or int16, and brought to 24 kHz mono on the device by an inputs.StreamResampler the stream owns: its
+    state is carried from push to push, so the 24 kHz track is that of inputs.resample_audio on the whole waveform, bit for bit,
+    however it was cut.  `samples` counts the 24 kHz samples taken, `input_samples` the source samples; the resampler holds back
+    10 to 30 outputs (at most 1.25 ms) until the inputs they read have arrived, and close() flushes them.
+
+    The windows are plan_stream's: window w starts at frame w * stride, reads the T input frames stream_window names and the audio windows around its centre columns, and runs once both
     have arrived -- through predictor.predict_batch in groups of `batch` (a short group is padded by repeating its last window,
     as predict_video pads, so one graph shape serves the stream).  Each result is a dict: "window" (int), "frames_idx" and
     "target_idx" int64 (T,) numpy, and on the device "points" (T, 2), "peak" (T,), "heatmaps" and "rescaled" (T, S/4, S/4).
@@ -190,15 +210,22 @@ class GazeStream:
     Difference from predict_video: predict_video scales audio positions by the whole recording's cols / n, which a stream cannot
     know; the stream uses cols_per_frame = 200 / fps, so the centres may differ by a column or two (they agree exactly when
     cols * den == num * n).  Equality with predict_video is therefore not claimed; each window equals, bit for bit, the
-    composition clip_sample + stft_logpower + audio_windows_at + predict_batch at stream_window's indices and the same batch.
+    composition clip_sample + stft_logpower + audio_windows_at + predict_batch at stream_window's indices and the same batch
+    (with input_rate: stft_logpower of resample_audio of the whole waveform).
 
-    Out of scope: sample_rate other than 24 kHz (chunk-wise resampling needs filter state: ValueError), attention maps, and fill /
-    overlay inside the stream (fold the results with track_from_windows, then fill_track / render_track)."""
+    Out of scope: attention maps, and fill / overlay inside the stream (fold the results with track_from_windows, then
+    fill_track / render_track).  sample_rate= still names the rate the audio is pushed at as it is, 24 kHz only."""
 
     def __init__(self, predictor, fps=None, stride=None, segment=None, batch=1, max_chunk=32, pixel_format="rgb24",
-                 matrix="bt601", full_range=False, sample_rate=None):
+                 matrix="bt601", full_range=False, sample_rate=None, input_rate=None):
         check_stream_rate(sample_rate)
         from . import inputs
+        if input_rate is not None and sample_rate is not None:
+            raise ValueError(f"sample_rate={sample_rate!r} says the audio is pushed at {AUDIO_RATE} Hz as it is, input_rate="
+                             f"{input_rate!r} that it is resampled from that rate: pass one of them")
+        self.input_rate = None if input_rate is None else inputs.check_sample_rate(input_rate, "input_rate")
+        self.resampler = None if input_rate is None else inputs.StreamResampler(self.input_rate)
+        self.input_samples = 0                               # source samples consumed (= samples without input_rate)
         self.fmt = {}
         if inputs.check_pixel_format(pixel_format, matrix, full_range)[0]:
             self.fmt = {"pixel_format": pixel_format, "matrix": matrix, "full_range": bool(full_range)}
@@ -318,7 +345,8 @@ class GazeStream:
     # ---- the interface ---------------------------------------------------------------------------------------------------------
     def push(self, frames=None, wav=None):
         """The next frames -- uint8 (K, H, W, 3), or (K, H * 3 / 2, W) in the stream's pixel format -- and / or the next samples --
-        fp32 (m,) at 24 kHz -- both on the device -> the list (possibly empty) of the windows this push completes, in order."""
+        fp32 (m,) at 24 kHz, or with input_rate (m,) / (C, m), floating or int16, at that rate -- both on the device -> the list
+        (possibly empty) of the windows this push completes, in order."""
         import torch
         from . import lib as L
         from .infer import _picture_hw
@@ -334,16 +362,23 @@ class GazeStream:
             if self.hw is not None and (H, W) != self.hw:
                 raise ValueError(f"the stream's frames are {self.hw[0]} x {self.hw[1]} (fixed by the first push), got {H} x {W}")
             k = frames.shape[0]
-        if wav is not None:
+        if wav is not None and self.resampler is not None:
+            m_in = self.resampler.check(wav)
+            m = self.resampler.count(m_in, wav)              # the 24 kHz samples this piece makes final
+        elif wav is not None:
             if wav.dim() != 1 or wav.dtype != torch.float32:
                 raise ValueError(f"wav must be an fp32 (m,) waveform at {AUDIO_RATE} Hz, got {tuple(wav.shape)} {wav.dtype}")
-            m = wav.numel()
-        steps = self._steps(k, m)                            # raises before anything is consumed
+            m_in = m = wav.numel()
+        steps = self._steps(k, m)                            # raises before anything is consumed, the resampler included
         results = []
         fa = sa = 0
         with torch.no_grad(), torch.cuda.device(self.predictor.device):
             if k and self.hw is None:
                 self._setup(H, W, frames.device)
+            if wav is not None:
+                self.input_samples += m_in
+                if self.resampler is not None:
+                    wav = self.resampler.push(wav)           # the whole piece once; the steps slice the 24 kHz samples
             for dk, dm, ready in steps:
                 if dm:
                     self._audio(wav[sa:sa + dm])
@@ -366,6 +401,11 @@ class GazeStream:
         self.closed = True
         results = []
         with torch.no_grad(), torch.cuda.device(self.predictor.device):
+            if self.resampler is not None:                   # the outputs held back; as many of them as the spectrum ring takes
+                rest = self.resampler.close()
+                rest = rest[:max(0, min(rest.numel(), self._limits(self._next)[1] - self.samples))]
+                if rest.numel():
+                    self._audio(rest)
             if wav_pad and self._tail is not None:
                 self._audio(self._tail[:0], n_total=self.samples)
             ready, w, nxt = [], self.next_window, self._next

@@ -32,7 +32,7 @@ enum { CSTS_EPI_NONE = 0, CSTS_EPI_GELU = 1, CSTS_EPI_DGELU = 2 };
 enum { CSTS_MASK_NONE = 0, CSTS_MASK_SPATIAL = 1 };
 
 /* Version of this header's struct layouts and call semantics.  Bumped whenever a struct grows or a field changes meaning
- * (2: csts_gemm_args.res_up; 3: compact k|v rows, 16-bit build, loss scaler in csts_opt_args; 4: csts_opt_args.extra_sq, factored AdamW; 5: grouped stencil weight gradients; 6: csts_copy_token_segments, csts_wgrad_grouped8_limited; 7: csts_wgrad_grouped5, csts_gemm algo 500; 8: csts_opt_rule, csts_opt_step, csts_opt_factored_step, csts_opt_factored.tensor replaces pad_; 10: csts_audio_pixel_attn; 11: csts_attention_track, csts_attention_rescale; 12: csts_resample_wav, csts_resample_len; 13: csts_attn_route; 14: 4:2:0 frames, csts_yuv_to_rgb, csts_*_sample_yuv; still 14: csts_stream_* (new entry points only, no struct or call changed)).  csts_abi_version() returns the value the
+ * (2: csts_gemm_args.res_up; 3: compact k|v rows, 16-bit build, loss scaler in csts_opt_args; 4: csts_opt_args.extra_sq, factored AdamW; 5: grouped stencil weight gradients; 6: csts_copy_token_segments, csts_wgrad_grouped8_limited; 7: csts_wgrad_grouped5, csts_gemm algo 500; 8: csts_opt_rule, csts_opt_step, csts_opt_factored_step, csts_opt_factored.tensor replaces pad_; 10: csts_audio_pixel_attn; 11: csts_attention_track, csts_attention_rescale; 12: csts_resample_wav, csts_resample_len; 13: csts_attn_route; 14: 4:2:0 frames, csts_yuv_to_rgb, csts_*_sample_yuv; still 14: csts_stream_*, then csts_resample_stream, csts_resample_ready, csts_resample_first_input (new entry points only, no struct or call changed)).  csts_abi_version() returns the value the
  * LIBRARY was built with: a caller must compare it with the CSTS_ABI_VERSION it was compiled against and refuse a mismatch
  * (the Python binding does, csts_amd/lib.py::load). */
 #define CSTS_ABI_VERSION 14
@@ -651,6 +651,31 @@ enum { CSTS_WAV_F32 = 0, CSTS_WAV_I16 = 1 };
 int64_t csts_resample_len(int64_t n, int up, int down);
 int csts_resample_wav(const void* wav, int in_kind, int B, int C, int64_t n, const float* taps, int up, int down, int half,
                       float* out, hipStream_t stream);
+
+/* ---- the same resampling on a live stream (csts_amd/csrc/resample.hip, csts_amd/inputs.py::StreamResampler): a range of the
+ *      outputs of a stream from a buffer that holds only part of it.  Output m of the rule above reads the inputs
+ *        csts_resample_first_input(m) = max(ceil((m * down - half) / up), 0)  ..  floor((m * down + half) / up),
+ *      so it is final once the latter is in.  After n_in inputs the final outputs are [0, csts_resample_ready(n_in, ...)):
+ *        open stream   (closed = 0):  max(0, floor((n_in * up - half - 1) / down) + 1)
+ *        ended stream  (closed = 1):  ceil(n_in * up / down)                   (the offline zero extension past the last sample)
+ *      Both return -1 outside the limits above (n_in in [0, CSTS_RESAMPLE_MAX_N], m >= 0).  An open stream holds back between
+ *      10 and 30 outputs for the filters of inputs.resample_rule, and must keep n_in - first_input(ready(n_in)) <=
+ *      2 * half / up + 2 input samples per channel from one call to the next.
+ *      csts_resample_stream: buf (C, len) contiguous, fp32 or int16 as csts_resample_wav's wav, holds the stream samples
+ *      [x_base, x_base + len); out[m - m0] receives output m for m in [m0, m1), by the kernel and the arithmetic of
+ *      csts_resample_wav (B = 1): the same products in the same order, so the bits are those of csts_resample_wav on the whole
+ *      waveform, however the stream was cut (runs of CSTS_RESAMPLE_RUN outputs start at m0; a sum does not depend on its run).
+ *        n_total < 0   the stream is open: every input an output reads is in the buffer, m1 <= csts_resample_ready(x_base + len, 0);
+ *        n_total >= 0  the stream ended at that length: x_base + len == n_total and m1 <= ceil(n_total * up / down); the sums are
+ *                      cut at n_total - 1.
+ *      In both, csts_resample_first_input(m0) >= x_base, 0 <= m0 <= m1, len >= 1, x_base + len <= CSTS_RESAMPLE_MAX_N, and the
+ *      limits of csts_resample_wav on C, the ratio and the LDS table hold.  m0 == m1 returns 0 and launches nothing.  A call
+ *      outside these conditions returns -1, sets csts_last_error and launches nothing; the kernel additionally keeps every read
+ *      inside [0, len) of the buffer.  No host sync, no allocation, no atomics: graph-capturable. */
+int64_t csts_resample_ready(int64_t n_in, int up, int down, int half, int closed);
+int64_t csts_resample_first_input(int64_t m, int up, int down, int half);
+int csts_resample_stream(const void* buf, int in_kind, int C, int64_t len, int64_t x_base, int64_t n_total, const float* taps, int up,
+                         int down, int half, int64_t m0, int64_t m1, float* out, hipStream_t stream);
 
 /* ---- gaze head of the inference path (csts_amd/csrc/decode.hip): one read of a frame's logits gives every consumer of a
  *      prediction what it needs.  logits: nframes = B * T frames of H * W cells each, the (B, 1, T, H, W) model output, fp32

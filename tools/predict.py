@@ -51,8 +51,11 @@ json_stats line then carries "pixel_format".
 frames (default 8) with the matching audio -- the samples up to frame_end * 24000 / fps, the rest with the last push -- as a live
 source would deliver it, and closed.  --out receives the same entries as --video, the track folded from the emitted windows by
 csts_amd.track_from_windows, plus stream_windows (the window numbers, in the order they were emitted) and stream_dropped; the
-json_stats line gains "stream", "chunk" and "dropped".  --fps must then be integral (a stream places its audio by the exact ratio of
-columns to frames) and the audio at 24 kHz; --overlay, --fill and the attention flags are not part of the stream."""
+json_stats line gains "stream", "chunk" and "dropped".  A recording at another rate (sample_rate entry or --sample-rate) is pushed
+at that rate, int16 and (C, n) as stored -- the samples up to frame_end * rate / fps -- and resampled inside the stream with the
+filter state carried from push to push (GazePredictor.stream(input_rate=rate)); --out records sample_rate and audio_rate as the
+offline path does.  --fps must then be integral (a stream places its audio by the exact ratio of columns to frames); --overlay,
+--fill and the attention flags are not part of the stream."""
 import argparse
 import json
 import os
@@ -182,19 +185,20 @@ def waveform(z, rate, dev):
     return (wav if rate is not None and wav.dtype == torch.int16 else wav.float()).to(dev)
 
 
-def replay_stream(predictor, frames, wav, fps, stride, chunk, fmt):
+def replay_stream(predictor, frames, wav, fps, stride, chunk, fmt, rate=None):
     """The recording pushed through GazePredictor.stream in pushes of `chunk` frames with the matching audio, then closed ->
-    (the track by track_from_windows with "windows" = their number, the window numbers in emission order, the dropped count)."""
+    (the track by track_from_windows with "windows" = their number, the window numbers in emission order, the dropped count).
+    rate: the rate wav, (n,) or (C, n), was recorded at; the stream resamples it (input_rate)."""
     from fractions import Fraction
     from csts_amd import track_from_windows
-    stream = predictor.stream(fps=fps, stride=stride, **fmt)
-    N, n = frames.shape[0], wav.shape[0]
-    per = Fraction(AUDIO_RATE) / stream.plan["fps"]                  # samples per frame
+    stream = predictor.stream(fps=fps, stride=stride, input_rate=rate, **fmt)
+    N, n = frames.shape[0], wav.shape[-1]
+    per = Fraction(AUDIO_RATE if rate is None else rate) / stream.plan["fps"]     # samples per frame
     results, sent = [], 0
     for a in range(0, N, chunk):
         b = min(a + chunk, N)
         upto = n if b == N else min(n, int(b * per))
-        results += stream.push(frames[a:b], wav[sent:upto] if upto > sent else None)
+        results += stream.push(frames[a:b], wav[..., sent:upto] if upto > sent else None)
         sent = max(sent, upto)
     results += stream.close()
     if not results:
@@ -258,12 +262,9 @@ def main(argv=None):
             rate = source_rate(z, args, args.video)
             frames, fmt = torch.from_numpy(pics[0]).to(dev), pics[1]
             if args.stream:
-                if rate is not None and rate != AUDIO_RATE:
-                    raise SystemExit(f"--stream takes the audio at {AUDIO_RATE} Hz, {args.video} is at {rate} Hz: resampling chunk by "
-                                     "chunk needs filter state carried between pushes")
                 try:
-                    out, stream_windows, dropped = replay_stream(predictor, frames, waveform(z, None, dev), fps, args.stride,
-                                                                 8 if args.chunk is None else args.chunk, fmt)
+                    out, stream_windows, dropped = replay_stream(predictor, frames, waveform(z, rate, dev), fps, args.stride,
+                                                                 8 if args.chunk is None else args.chunk, fmt, rate)
                 except ValueError as e:
                     raise SystemExit(str(e))
             else:
