@@ -22,7 +22,8 @@ template <bool F32> __device__ __forceinline__ void stt(void* p, int64_t i, floa
 
 // one wave handles R rows per iteration (R*NV independent loads), two-pass statistics in registers
 // optional input of the forward kernels: x + addend is what gets normalised, and the sum is written to `sum` (dtype of x):
-// the decoder's `feat + en_feat` skip (custom_multimodal_builder.py:467-479) folded into the next block's norm1
+// the decoder's `feat + en_feat` skip (custom_multimodal_builder.py:467-479) folded into the next block's norm1.  What is normalised
+// is the sum AS STORED (a 16-bit sum is rounded first): mean / rstd are those of `sum`, the x the backward reads with them
 struct FwdAdd {
   const void* addend = nullptr;
   void* sum = nullptr;
@@ -54,6 +55,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const void* __restrict__ x,
         v[r][j] = ldt<XF32>(x, row * C + min(c, C - 1));
         if (fa.addend) {                                         // wave-uniform
           v[r][j] += ldt<XF32>(fa.addend, row * C + min(c, C - 1));
+          if constexpr (!XF32) v[r][j] = (float)(bf16)v[r][j];   // normalise the sum as stored: the x the backward reads with this mean / rstd
           if (c < C && row0 + r < rows) stt<XF32>(fa.sum, row * C + c, v[r][j]);
         }
       }
@@ -268,7 +270,10 @@ __global__ __launch_bounds__(256) void ln_fwd_vec_kernel(const void* __restrict_
           float a2[8];
           ld8t<XF32>(fa.addend, row * C + c0[i], a2);
 #pragma unroll
-          for (int j = 0; j < 8; ++j) v[r][i][j] += a2[j];
+          for (int j = 0; j < 8; ++j) {
+            v[r][i][j] += a2[j];
+            if constexpr (!XF32) v[r][i][j] = (float)(bf16)v[r][i][j];   // the sum as stored (see ln_fwd_kernel)
+          }
           if (act[i] && row0 + r < rows) st8t<XF32>(fa.sum, row * C + c0[i], v[r][i]);
         }
       }
