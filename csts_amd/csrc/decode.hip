@@ -9,23 +9,9 @@
 // video frame several times; the track is the mean heat map per frame, decoded again (rescale, arg-max point, peak).  One
 // workgroup per OUTPUT frame walks the list of prediction rows that target it and keeps the running sum in registers in the
 // layout of gaze_decode, so every row is read once, nothing is re-read and no atomics are needed: the sum has one fixed order.
-#include "common.h"
+#include "track_shared.h"
 
 namespace {
-
-constexpr int DEC_MAX_NCH = CSTS_GAZE_DECODE_MAX_HW / 1024;      // 4-value chunks per lane at the largest frame
-
-// Element r of chunk c of lane tid.  VEC: 4 consecutive cells per chunk (128-bit stores, 64- / 128-bit loads); otherwise the
-// cells of a chunk are 256 apart (frames whose size or address does not allow vector access).
-template <bool VEC>
-__device__ __forceinline__ int cell_of(int c, int r, int tid) {
-  return VEC ? (c * 256 + tid) * 4 + r : (c * 4 + r) * 256 + tid;
-}
-
-// (value, index) pair with "larger value wins, lowest index on ties"
-__device__ __forceinline__ void take_max(float& v, int& i, float ov, int oi) {
-  if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-}
 
 template <int NCH, bool VEC>
 __global__ __launch_bounds__(256) void gaze_decode_kernel(const void* __restrict__ logits, int dt, int H, int W, float inv_temp,
@@ -150,73 +136,6 @@ void launch_decode(bool vec, unsigned nframes, hipStream_t stream, const void* l
                           rescaled, points, peak);
 }
 
-// The tail gaze_track and gaze_track_fill share: the frame's map m (registers, layout of cell_of) -> its max + arg-max (a lane
-// walks its cells in ascending index order) and its min, then heatmaps = m, rescaled, points and peak of frame blockIdx.x.
-// live = false (nobody predicts the frame; the caller passes m = 0): maps 0, points NaN, peak 0.
-template <int NCH, bool VEC>
-__device__ __forceinline__ void track_tail(const float (&m)[NCH * 4], bool live, int H, int W, float* __restrict__ heatmaps,
-                                           float* __restrict__ rescaled, float* __restrict__ points, float* __restrict__ peak) {
-  __shared__ float red_v[2][4];
-  __shared__ int red_i[4];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int hw = H * W;
-  const int64_t frame = blockIdx.x, base = frame * hw;
-  float bv = -INFINITY, mn = INFINITY;
-  int bi = 0x7fffffff;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int at = cell_of<VEC>(c, r, tid);
-      if (at < hw) {
-        take_max(bv, bi, m[c * 4 + r], at);
-        mn = fminf(mn, m[c * 4 + r]);
-      }
-    }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) take_max(bv, bi, __shfl_xor(bv, o, 64), __shfl_xor(bi, o, 64));
-  mn = -wave_max(-mn);
-  if (lane == 0) { red_v[0][w] = bv; red_i[w] = bi; red_v[1][w] = mn; }
-  __syncthreads();
-  bv = red_v[0][0]; bi = red_i[0];
-#pragma unroll
-  for (int k = 1; k < 4; ++k) take_max(bv, bi, red_v[0][k], red_i[k]);
-  if (bi >= hw) bi = 0;                 // a frame without a comparable value (all NaN): still a cell of the frame
-  mn = fminf(fminf(red_v[1][0], red_v[1][1]), fminf(red_v[1][2], red_v[1][3]));
-  const float denom = bv - mn + 1e-6f;
-  // ---- writes (an uncovered frame: m = 0 everywhere, so the maps below are 0)
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    if (VEC) {
-      const int at = (c * 256 + tid) * 4;
-      if (at < hw) {
-        f32x4 p, q;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { p[r] = m[c * 4 + r]; q[r] = (p[r] - mn) / denom; }
-        if (heatmaps) *reinterpret_cast<f32x4*>(heatmaps + base + at) = p;
-        if (rescaled) *reinterpret_cast<f32x4*>(rescaled + base + at) = q;
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int at = cell_of<false>(c, r, tid);
-        if (at < hw) {
-          if (heatmaps) heatmaps[base + at] = m[c * 4 + r];
-          if (rescaled) rescaled[base + at] = (m[c * 4 + r] - mn) / denom;
-        }
-      }
-    }
-  }
-  if (tid == 0) {
-    if (points) {
-      const int row = bi / W, col = bi - row * W;
-      points[frame * 2] = live ? (float)col / (float)W : __builtin_nanf("");
-      points[frame * 2 + 1] = live ? (float)row / (float)H : __builtin_nanf("");
-    }
-    if (peak) peak[frame] = live ? bv : 0.f;
-  }
-}
-
 // One workgroup per output frame f: order[offsets[f] .. offsets[f + 1]) are its prediction rows, added in that order.
 template <int NCH, bool VEC>
 __global__ __launch_bounds__(256) void gaze_track_kernel(const float* __restrict__ preds, const int* __restrict__ order,
@@ -272,26 +191,6 @@ void launch_track(bool vec, unsigned nframes, hipStream_t stream, const float* p
 // addresses), and takes H_a (hold) or wa H_a + wb H_b (linear) when b - a <= max_gap.  The map then goes through track_tail,
 // so a predicted frame leaves with the bits gaze_track wrote for it.
 template <int NCH, bool VEC>
-__device__ __forceinline__ void load_map(float (&m)[NCH * 4], const float* __restrict__ row, int hw, int tid) {
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    if (VEC) {
-      const int at = (c * 256 + tid) * 4;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (at < hw) v = *reinterpret_cast<const f32x4*>(row + at);       // hw % 4 == 0 on this path
-#pragma unroll
-      for (int r = 0; r < 4; ++r) m[c * 4 + r] = v[r];
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int at = cell_of<false>(c, r, tid);
-        m[c * 4 + r] = at < hw ? row[at] : 0.f;
-      }
-    }
-  }
-}
-
-template <int NCH, bool VEC>
 __global__ __launch_bounds__(256) void gaze_fill_kernel(const float* __restrict__ maps, const int* __restrict__ count, int F, int H,
                                                         int W, int mode, int max_gap, float* __restrict__ heatmaps,
                                                         float* __restrict__ rescaled, float* __restrict__ points,
@@ -322,10 +221,7 @@ __global__ __launch_bounds__(256) void gaze_fill_kernel(const float* __restrict_
     if (mode == 1 && b != a) {
       float hb[NCH * 4];
       load_map<NCH, VEC>(hb, maps + (int64_t)b * hw, hw, tid);
-      const float span = (float)(b - a);
-      const float wa = (float)(b - n) / span, wb = (float)(n - a) / span;
-#pragma unroll
-      for (int k = 0; k < NCH * 4; ++k) m[k] = wa * m[k] + wb * hb[k];
+      blend_maps<NCH>(m, hb, a, b, n);
     }
   }
   track_tail<NCH, VEC>(m, a >= 0, H, W, heatmaps, rescaled, points, peak);

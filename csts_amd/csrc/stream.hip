@@ -7,9 +7,13 @@
 //   stream_ingest(_yuv)  : the frames of one pushed chunk some window will read, sampled ONCE into a ring of normalised crops by
 //                          sample_rows / sample_rows_yuv (the pixel pass of csts_clip_sample) under one test-mode parameter row.
 //   stream_gather        : (B, 3, T, S, S) clips out of the crop ring by a slot table.
+//   live_track_add       : the maps of newly run windows folded into a ring of per-frame sums (frame t in slot t mod Rt).
+//   live_track_rows      : the rows of a gaze track for the frames just pushed, out of that ring: mean, neighbours, hold or blend,
+//                          decode -- the device functions of csts_gaze_track / csts_gaze_track_fill (track_shared.h).
 // Every table is DEVICE memory read when the kernel runs; no atomics, no allocation, no synchronisation.
 #include "stft_shared.h"
 #include "yuv_shared.h"
+#include "track_shared.h"
 
 namespace {
 
@@ -108,6 +112,149 @@ __global__ __launch_bounds__(256) void stream_gather_kernel(const float* __restr
   }
 }
 
+// ---- live track ring (GazeStream(live=...)): frame t lives in slot t mod Rt of sum (Rt, hw) / count (Rt) / tag (Rt), the tag
+// being the frame number the slot holds (-1: empty).  A slot is written by ONE workgroup of ONE launch at a time and read by a
+// later launch on the same stream: plain loads and stores, no atomics.  Inside that workgroup every lane reads the slot's tag and
+// count before a workgroup barrier and lane 0 writes them after it; a lane reads and writes only its own cells of the sum.
+
+// grid (Rt), 256 threads.  Workgroup s walks target[0 .. P) in ascending p (uniform loads) and takes the rows whose target
+// t >= 0 has t mod Rt == s:  tag != t -> the slot restarts (sum = 0 + row, count = 1, tag = t);  tag == t -> sum += row, count += 1.
+// The walk is done twice: once on the tags alone, which finds the slot's last restart (`start`, -1: none: the sum in the ring is
+// carried on), its final tag and count; then per 4-cell chunk over the rows from there on, so that a cell is read once per row
+// that counts and written once.  The additions of one cell are ((0 + row_0) + row_1) + ..., in window order across calls and in
+// ascending p inside one: the order of csts_gaze_track.  A slot no row names is not touched.
+template <bool VEC>
+__global__ __launch_bounds__(256) void live_track_add_kernel(const float* __restrict__ maps, const int64_t* __restrict__ target, int P,
+                                                             int hw, float* __restrict__ sum, int* __restrict__ count,
+                                                             int64_t* __restrict__ tag, int Rt) {
+  const int slot = blockIdx.x, tid = threadIdx.x;
+  int64_t cur = tag[slot];
+  int cnt = count[slot], start = -1, hits = 0;
+  for (int p = 0; p < P; ++p) {
+    const int64_t t = target[p];
+    if (t < 0 || (int)(t % Rt) != slot) continue;
+    ++hits;
+    if (t != cur) { cur = t; cnt = 1; start = p; } else { ++cnt; }
+  }
+  if (hits == 0) return;                                     // uniform over the workgroup: it depends on target alone
+  // Every lane has read the slot's tag and count by here; lane 0 replaces them at the end.  Without this barrier a wave that
+  // started late could read the NEW tag of a restarted slot, take the restart for a carry-on and add to the old frame's sum.
+  __syncthreads();
+  float* dst = sum + (int64_t)slot * hw;
+  const int first = start < 0 ? 0 : start;
+  constexpr int V = VEC ? 4 : 1;
+  for (int at = tid * V; at < hw; at += 256 * V) {
+    float acc[V];
+#pragma unroll
+    for (int q = 0; q < V; ++q) acc[q] = 0.f;
+    if (start < 0) {
+      if constexpr (VEC) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(dst + at);
+#pragma unroll
+        for (int q = 0; q < V; ++q) acc[q] = v[q];
+      } else {
+        acc[0] = dst[at];
+      }
+    }
+    for (int p = first; p < P; ++p) {
+      const int64_t t = target[p];
+      if (t != cur) continue;                                // from `start` on, the slot's rows all carry its final tag
+      const float* row = maps + (int64_t)p * hw + at;
+      if constexpr (VEC) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(row);
+#pragma unroll
+        for (int q = 0; q < V; ++q) acc[q] += v[q];
+      } else {
+        acc[0] += row[0];
+      }
+    }
+    if constexpr (VEC) {
+      f32x4 o;
+#pragma unroll
+      for (int q = 0; q < V; ++q) o[q] = acc[q];
+      *reinterpret_cast<f32x4*>(dst + at) = o;
+    } else {
+      dst[at] = acc[0];
+    }
+  }
+  if (tid == 0) { count[slot] = cnt; tag[slot] = cur; }
+}
+
+// how many maps frame t holds in the ring: its slot's count when the slot's tag is t, else 0 (never written, or recycled)
+__device__ __forceinline__ int live_count_of(const int* __restrict__ count, const int64_t* __restrict__ tag, int Rt, int64_t t) {
+  if (t < 0) return 0;
+  const int s = (int)(t % Rt);
+  return tag[s] == t ? count[s] : 0;
+}
+
+// frame t's mean map out of the ring, in registers: sum * (1 / count), csts_gaze_track's mean
+template <int NCH, bool VEC>
+__device__ __forceinline__ void live_mean(float (&m)[NCH * 4], const float* __restrict__ sum, const int* __restrict__ count, int Rt,
+                                          int64_t t, int hw, int tid) {
+  const int s = (int)(t % Rt);
+  load_map<NCH, VEC>(m, sum + (int64_t)s * hw, hw, tid);
+  const float inv = 1.f / (float)count[s];
+#pragma unroll
+  for (int k = 0; k < NCH * 4; ++k) m[k] *= inv;
+}
+
+// grid (K), 256 threads: workgroup k answers frame n = f0 + k by the rule of csts_gaze_track_fill on a track of n + max_gap + 1
+// frames whose count is live_count_of: a, b as gaze_fill_kernel finds them (all uniform over the workgroup), the map by
+// live_mean / blend_maps, the outputs by track_tail.
+template <int NCH, bool VEC>
+__global__ __launch_bounds__(256) void live_track_rows_kernel(const float* __restrict__ sum, const int* __restrict__ count,
+                                                              const int64_t* __restrict__ tag, int Rt, int64_t f0, int H, int W,
+                                                              int mode, int max_gap, float* __restrict__ heatmaps,
+                                                              float* __restrict__ rescaled, float* __restrict__ points,
+                                                              float* __restrict__ peak, int* __restrict__ out_count,
+                                                              int* __restrict__ neighbours) {
+  const int tid = threadIdx.x;
+  const int hw = H * W;
+  const int64_t n = f0 + blockIdx.x;
+  const int own = live_count_of(count, tag, Rt, n);
+  int64_t a = -1, b = -1;
+  if (own > 0) {
+    a = b = n;
+  } else {
+    const int64_t lo = n - (max_gap - 1) > 0 ? n - (max_gap - 1) : 0;
+    for (int64_t j = n - 1; j >= lo; --j)
+      if (live_count_of(count, tag, Rt, j) > 0) { a = j; break; }
+    if (a >= 0) {
+      const int64_t hi = a + max_gap;                        // b - a <= max_gap; the track ends at n + max_gap > hi
+      for (int64_t j = n + 1; j <= hi; ++j)
+        if (live_count_of(count, tag, Rt, j) > 0) { b = j; break; }
+    }
+    if (b < 0) a = -1;
+  }
+  float m[NCH * 4];
+  if (a < 0) {
+#pragma unroll
+    for (int k = 0; k < NCH * 4; ++k) m[k] = 0.f;
+  } else {
+    live_mean<NCH, VEC>(m, sum, count, Rt, a, hw, tid);
+    if (mode == 1 && b != a) {
+      float hb[NCH * 4];
+      live_mean<NCH, VEC>(hb, sum, count, Rt, b, hw, tid);
+      blend_maps<NCH>(m, hb, a, b, n);
+    }
+  }
+  track_tail<NCH, VEC>(m, a >= 0, H, W, heatmaps, rescaled, points, peak);
+  if (tid == 0) {
+    if (out_count) out_count[blockIdx.x] = own;
+    if (neighbours) { neighbours[2 * (int64_t)blockIdx.x] = (int)a; neighbours[2 * (int64_t)blockIdx.x + 1] = (int)b; }
+  }
+}
+
+template <int NCH>
+void launch_live_rows(bool vec, unsigned K, hipStream_t stream, const float* sum, const int* count, const int64_t* tag, int Rt,
+                      int64_t f0, int H, int W, int mode, int max_gap, float* heatmaps, float* rescaled, float* points, float* peak,
+                      int* out_count, int* neighbours) {
+  if (vec) hipLaunchKernelGGL((live_track_rows_kernel<NCH, true>), dim3(K), dim3(256), 0, stream, sum, count, tag, Rt, f0, H, W, mode,
+                              max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
+  else hipLaunchKernelGGL((live_track_rows_kernel<NCH, false>), dim3(K), dim3(256), 0, stream, sum, count, tag, Rt, f0, H, W, mode,
+                          max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
+}
+
 int ingest_check(const void* chunk, const void* pairs, const void* params, const void* ring, const float* mean, const float* std,
                  int K, int H, int W, int npairs, int R, int S) {
   CSTS_REQUIRE(chunk && pairs && params && ring && mean && std, "bad args");
@@ -195,6 +342,46 @@ extern "C" int csts_stream_gather(const float* ring, int R, const int* slots, fl
     hipLaunchKernelGGL(stream_gather_kernel<true>, grid, dim3(256), 0, stream, ring, R, slots, out, T, plane);
   else
     hipLaunchKernelGGL(stream_gather_kernel<false>, grid, dim3(256), 0, stream, ring, R, slots, out, T, plane);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_live_track_add(const float* maps, const int64_t* target_idx, int P, int H, int W, float* sum, int* count,
+                                   int64_t* frame, int Rt, hipStream_t stream) {
+  CSTS_REQUIRE(maps && target_idx && sum && count && frame, "null maps, target_idx or ring");
+  CSTS_REQUIRE(P >= 1 && P <= 65535 && Rt >= 1 && Rt <= 65535, "1 <= P <= 65535 maps, 1 <= Rt <= 65535 slots");
+  CSTS_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W <= CSTS_GAZE_DECODE_MAX_HW, "1 <= H * W <= CSTS_GAZE_DECODE_MAX_HW");
+  CSTS_REQUIRE((const void*)maps != (const void*)sum, "maps must not be the ring");
+  const int hw = H * W;
+  const bool vec = hw % 4 == 0 && aligned16(maps) && aligned16(sum);
+  if (vec) hipLaunchKernelGGL(live_track_add_kernel<true>, dim3((unsigned)Rt), dim3(256), 0, stream, maps, target_idx, P, hw, sum, count,
+                              frame, Rt);
+  else hipLaunchKernelGGL(live_track_add_kernel<false>, dim3((unsigned)Rt), dim3(256), 0, stream, maps, target_idx, P, hw, sum, count,
+                          frame, Rt);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_live_track_rows(const float* sum, const int* count, const int64_t* frame, int Rt, int64_t f0, int K, int H, int W,
+                                    int mode, int max_gap, float* heatmaps, float* rescaled, float* points, float* peak,
+                                    int* out_count, int* neighbours, hipStream_t stream) {
+  CSTS_REQUIRE(sum && count && frame, "null ring");
+  CSTS_REQUIRE(Rt >= 1 && Rt <= 65535 && K >= 1 && K <= 65535, "1 <= Rt <= 65535 slots, 1 <= K <= 65535 frames");
+  CSTS_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W <= CSTS_GAZE_DECODE_MAX_HW, "1 <= H * W <= CSTS_GAZE_DECODE_MAX_HW (the frame is held in registers)");
+  CSTS_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (hold) or 1 (linear)");
+  CSTS_REQUIRE(max_gap >= 1 && max_gap <= CSTS_GAZE_FILL_MAX_GAP, "1 <= max_gap <= CSTS_GAZE_FILL_MAX_GAP");
+  CSTS_REQUIRE(f0 >= 0 && f0 + K + max_gap < ((int64_t)1 << 31), "0 <= f0 and f0 + K + max_gap < 2^31 (neighbours are int32)");
+  CSTS_REQUIRE(heatmaps != sum && rescaled != sum, "no output may be the ring");
+  if (!heatmaps && !rescaled && !points && !peak && !out_count && !neighbours) return 0;
+  const int hw = H * W;
+  const bool vec = hw % 4 == 0 && aligned16(sum) && aligned16(heatmaps) && aligned16(rescaled);
+  const int nch = (int)cdiv(hw, 1024);
+  static_assert(DEC_MAX_NCH == 8, "the dispatch below covers 1, 2, 4 and 8 chunks per lane");
+  const unsigned n = (unsigned)K;
+  if (nch <= 1) launch_live_rows<1>(vec, n, stream, sum, count, frame, Rt, f0, H, W, mode, max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
+  else if (nch <= 2) launch_live_rows<2>(vec, n, stream, sum, count, frame, Rt, f0, H, W, mode, max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
+  else if (nch <= 4) launch_live_rows<4>(vec, n, stream, sum, count, frame, Rt, f0, H, W, mode, max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
+  else launch_live_rows<8>(vec, n, stream, sum, count, frame, Rt, f0, H, W, mode, max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
   CSTS_LAUNCH_CHECK();
   return 0;
 }

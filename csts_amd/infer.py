@@ -485,7 +485,7 @@ class GazePredictor:
         return res
 
     def stream(self, fps=None, stride=None, segment=None, batch=1, max_chunk=32, pixel_format="rgb24", matrix="bt601",
-               full_range=False, sample_rate=None, input_rate=None):
+               full_range=False, sample_rate=None, input_rate=None, live=None, max_gap=None, overlay=False, alpha=0.4, radius=5):
         """A live stream on this predictor (csts_amd.stream.GazeStream): push(frames, wav) takes frames and 24 kHz audio in whatever
         pieces they arrive and returns the windows each piece completes; close() ends it.  The windows are plan_stream's (fps an
         int or a Fraction, stride in frames); `batch` windows run per predict_batch call; `max_chunk` sizes the two device rings,
@@ -493,11 +493,15 @@ class GazePredictor:
         are 4:2:0 pictures.  input_rate=R: the audio is pushed at R Hz, (m,) or (C, m), floating or int16, and resampled to 24 kHz
         mono on the device with the filter state carried from push to push (inputs.StreamResampler): the track of
         inputs.resample_audio on the whole waveform, bit for bit.  sample_rate: None or 24000, the audio as it is; another rate
-        there is a ValueError (it keeps no filter state), and so are both keywords together."""
+        there is a ValueError (it keeps no filter state), and so are both keywords together.
+        live="hold" | "linear" (forecast plans): push_live(frames, wav) also answers every pushed frame with its row of a gaze
+        track computed from the windows that have run by then -- the forecast drawn on the frame it was made for, when that frame
+        arrives -- filled at most max_gap frames apart (default: default_max_gap of the plan); overlay=True (needs live) adds
+        the frames drawn over with `alpha` and `radius` as render_track takes them.  GazeStream states the causal rule."""
         from .stream import GazeStream
         return GazeStream(self, fps=fps, stride=stride, segment=segment, batch=batch, max_chunk=max_chunk,
                           pixel_format=pixel_format, matrix=matrix, full_range=full_range, sample_rate=sample_rate,
-                          input_rate=input_rate)
+                          input_rate=input_rate, live=live, max_gap=max_gap, overlay=overlay, alpha=alpha, radius=radius)
 
     @torch.no_grad()
     def _video_params_row(self, H, W):

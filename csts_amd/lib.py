@@ -49,6 +49,7 @@ EPI_NONE, EPI_GELU, EPI_DGELU = 0, 1, 2
 MASK_NONE, MASK_SPATIAL = 0, 1
 # size limits of include/csts_hip.h the Python side names in its own errors
 GAZE_DECODE_MAX_HW = 8192
+GAZE_FILL_MAX_GAP = 1024   # == CSTS_GAZE_FILL_MAX_GAP
 AUDIO_PIXEL_MAX_SIDE, AUDIO_PIXEL_MAX_HW = 128, 4096
 WAV_F32, WAV_I16 = 0, 1
 RESAMPLE_RUN, RESAMPLE_MAX_LDS_FLOATS, RESAMPLE_MAX_RATIO, RESAMPLE_MAX_N = 256, 16384, 1 << 20, 1 << 40
@@ -281,6 +282,8 @@ SYMBOLS = {
     "csts_stream_ingest": (_I, [vp, _I, _I, _I, vp, _I, vp, vp, _I, _I, C.c_float * 3, C.c_float * 3, vp]),
     "csts_stream_ingest_yuv": (_I, [vp, _I, _I, _I, vp, _I, vp, vp, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),
     "csts_stream_gather": (_I, [vp, _I, vp, vp, _I, _I, _I, vp]),
+    "csts_live_track_add": (_I, [vp, vp, _I, _I, _I, vp, vp, vp, _I, vp]),
+    "csts_live_track_rows": (_I, [vp, vp, vp, _I, i64, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, vp, vp]),
     "csts_adaptive_f1_workspace": (sz, [i64, _I]),
     "csts_adaptive_f1": (_I, [vp, vp, vp, vp, _I, i64, _I, _I, vp, vp, sz, vp]),
     "csts_f1_counts": (_I, [vp, vp, vp, _I, i64, _I, _I, vp, vp]),

@@ -2538,6 +2538,111 @@ def gaze_track_fill(heatmaps, count, mode="linear", max_gap=9, want=_FILL_OUTPUT
     return out
 
 
+# ----------------------------------------------------------------------------------------- live gaze track
+_LIVE_OUTPUTS = ("heatmaps", "rescaled", "points", "peak", "count", "neighbours")
+
+
+def live_track_ring(slots, h, w, device):
+    """An empty track ring of `slots` frames of h x w maps on `device`: {"sum" fp32 (slots, h, w) zeros, "count" int32 (slots,)
+    zeros, "frame" int64 (slots,) -1}.  Frame t lives in slot t mod slots (include/csts_hip.h, live gaze track)."""
+    slots, h, w = int(slots), int(h), int(w)
+    if slots < 1 or slots > 65535 or h < 1 or w < 1 or h * w > L.GAZE_DECODE_MAX_HW:
+        raise ValueError(f"a track ring holds 1..65535 slots of maps with h * w <= {L.GAZE_DECODE_MAX_HW}, got {slots} of {h} x {w}")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.CstsError("the track ring lives on MI355X only (there is no CPU fallback)")
+    return {"sum": torch.zeros(slots, h, w, dtype=torch.float32, device=device),
+            "count": torch.zeros(slots, dtype=torch.int32, device=device),
+            "frame": torch.full((slots,), -1, dtype=torch.int64, device=device)}
+
+
+def _check_live_ring(ring):
+    """The three tensors of a track ring, checked: (sum, count, frame, Rt, h, w)."""
+    try:
+        s, c, f = ring["sum"], ring["count"], ring["frame"]
+    except (KeyError, TypeError, IndexError):
+        raise ValueError("ring must be a dict with \"sum\", \"count\" and \"frame\" (ops.live_track_ring)")
+    _need_gpu(s, c, f)
+    if s.dim() != 3 or s.dtype != torch.float32 or not s.is_contiguous():
+        raise ValueError(f"ring[\"sum\"] must be contiguous fp32 (Rt, h, w), got {tuple(s.shape)} {s.dtype}")
+    Rt, h, w = s.shape
+    if c.dtype != torch.int32 or tuple(c.shape) != (Rt,) or not c.is_contiguous():
+        raise ValueError(f"ring[\"count\"] must be contiguous int32 ({Rt},), got {tuple(c.shape)} {c.dtype}")
+    if f.dtype != torch.int64 or tuple(f.shape) != (Rt,) or not f.is_contiguous():
+        raise ValueError(f"ring[\"frame\"] must be contiguous int64 ({Rt},), got {tuple(f.shape)} {f.dtype}")
+    if Rt < 1 or Rt > 65535 or h * w < 1 or h * w > L.GAZE_DECODE_MAX_HW:
+        raise ValueError(f"a track ring holds 1..65535 slots of maps with h * w <= {L.GAZE_DECODE_MAX_HW}, got {Rt} of {h} x {w}")
+    return s, c, f, Rt, h, w
+
+
+def live_track_add(maps, target_idx, targets, ring, live_from=0):
+    """csts_live_track_add: the maps of newly run windows, fp32 (P, h, w), each predicting frame target_idx[p] (int64 (P,) on the
+    device), folded into the track ring (ops.live_track_ring) in place.  A slot whose frame tag differs from the target restarts
+    (sum = the map, count 1, retagged: stale slots are recycled without a clearing pass); a slot whose tag matches is added to in
+    ascending p and its count bumped -- the order and the arithmetic of ops.gaze_track, when the windows come in the order they ran.
+    targets: the same P targets on the HOST (a sequence or numpy array of ints; the stream has them from stream_window), so
+    that what cannot be written is refused before the launch and without a host sync: a negative target, and a target
+    t >= live_from + Rt, which would overwrite the slot of frame t - Rt >= live_from.  live_from: the lowest frame whose row may
+    still be asked for, minus max_gap - 1 (a row reads that far back).  One launch, no atomics, no host sync."""
+    import numpy as np
+    _need_gpu(maps, target_idx)
+    s, c, f, Rt, h, w = _check_live_ring(ring)
+    if maps.dim() != 3 or maps.dtype != torch.float32 or tuple(maps.shape[1:]) != (h, w):
+        raise ValueError(f"maps must be fp32 (P, {h}, {w}), got {tuple(maps.shape)} {maps.dtype}")
+    P = maps.shape[0]
+    if target_idx.dtype != torch.int64 or tuple(target_idx.shape) != (P,):
+        raise ValueError(f"target_idx must be int64 ({P},), got {tuple(target_idx.shape)} {target_idx.dtype}")
+    if P < 1 or P > 65535:
+        raise ValueError(f"live_track_add takes 1..65535 maps a call, got {P}")
+    if torch.is_tensor(targets):
+        raise ValueError("targets are the host copy of target_idx: a sequence or numpy array of ints, not a tensor")
+    host = np.asarray(targets)
+    if host.shape != (P,) or not np.issubdtype(host.dtype, np.integer):
+        raise ValueError(f"targets must hold the {P} targets as integers on the host, got shape {host.shape} {host.dtype}")
+    live_from = int(live_from)
+    if int(host.min()) < 0:
+        raise ValueError(f"targets must be frame numbers >= 0, got {int(host.min())}")
+    if int(host.max()) >= live_from + Rt:
+        t = int(host.max())
+        raise ValueError(f"the track ring holds {Rt} frames: target {t} would overwrite the slot of frame {t - Rt}, which is still "
+                         f"inside the live span (it starts at frame {live_from}); nothing was written")
+    x = maps.detach().contiguous()
+    L.check(_lib().csts_live_track_add(_p(x), _p(target_idx.contiguous()), P, h, w, _p(s), _p(c), _p(f), Rt, _stream()),
+            "csts_live_track_add")
+
+
+def live_track_rows(ring, f0, K, mode="linear", max_gap=9, want=_LIVE_OUTPUTS):
+    """csts_live_track_rows: the track rows of frames f0 .. f0 + K - 1 out of the track ring.  Row n is row n of
+    ops.gaze_track_fill(mode, max_gap) of ops.gaze_track(everything added so far, n_frames = n + max_gap + 1), bit for bit, as long
+    as the frames in [n - max_gap + 1, n + max_gap - 1] have not been recycled (live_track_add's live_from): heatmaps and rescaled
+    (K, h, w), points (K, 2), peak (K,), count int32 (K,) (0 on a filled or unpredicted frame) and neighbours int32 (K, 2).  A
+    slot that holds another frame counts as empty.  Returns the outputs named in `want`; the others are not computed.  The ring
+    is only read.  One launch, no host sync: it can be captured in a graph."""
+    s, c, f, Rt, h, w = _check_live_ring(ring)
+    want = tuple(want)
+    unknown = [k for k in want if k not in _LIVE_OUTPUTS]
+    if unknown or not want:
+        raise ValueError(f"want must name some of {_LIVE_OUTPUTS}, got {want}")
+    if mode not in _FILL_MODES:
+        raise ValueError(f"mode must be one of {_FILL_MODES}, got {mode!r}")
+    f0, K, max_gap = int(f0), int(K), int(max_gap)
+    if f0 < 0 or K < 1 or K > 65535 or f0 + K + max_gap >= 2 ** 31:
+        raise ValueError(f"live_track_rows answers 1..65535 frames from f0 >= 0 with f0 + K + max_gap < 2^31, got f0 {f0}, K {K}")
+    if max_gap < 1 or max_gap > L.GAZE_FILL_MAX_GAP:
+        raise ValueError(f"max_gap must lie in 1..{L.GAZE_FILL_MAX_GAP}, got {max_gap}")
+    dev = s.device
+    out = {}
+    for k, shape, dt in (("heatmaps", (K, h, w), torch.float32), ("rescaled", (K, h, w), torch.float32),
+                         ("points", (K, 2), torch.float32), ("peak", (K,), torch.float32), ("count", (K,), torch.int32),
+                         ("neighbours", (K, 2), torch.int32)):
+        if k in want:
+            out[k] = torch.empty(shape, dtype=dt, device=dev)
+    L.check(_lib().csts_live_track_rows(_p(s), _p(c), _p(f), Rt, f0, K, h, w, _FILL_MODES.index(mode), max_gap,
+                                        _p(out.get("heatmaps")), _p(out.get("rescaled")), _p(out.get("points")), _p(out.get("peak")),
+                                        _p(out.get("count")), _p(out.get("neighbours")), _stream()), "csts_live_track_rows")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- gaze overlay
 def jet_table():
     """The heat colours of gaze_overlay on the host: uint8 numpy (256, 3) RGB, row q = the classic JET by the integer formula of

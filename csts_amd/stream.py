@@ -5,7 +5,9 @@ whatever pieces they arrive; every window is emitted by the push that completes 
 rings (normalised crops, spectrogram columns) whose size does not depend on how long the stream runs.  The host side -- which
 window reads which frames and columns, and when it is ready -- is pure arithmetic (``plan_stream``, ``stream_window``,
 ``stream_schedule``); the device side is the four kernels of csts_amd/csrc/stream.hip behind inputs.stream_stft,
-inputs.stream_audio_windows, inputs.stream_ingest and inputs.stream_gather."""
+inputs.stream_audio_windows, inputs.stream_ingest and inputs.stream_gather.  With ``live=`` a forecast stream also answers
+every pushed frame with its row of a gaze track, out of a third ring (``stream_live_schedule``, ``live_ring_slots``;
+ops.live_track_add and ops.live_track_rows, the last two kernels of stream.hip)."""
 from __future__ import annotations
 
 import numbers
@@ -104,23 +106,30 @@ def stream_window(plan, w):
             "ready_samples": int(STFT_HOP * (int(centers.max()) + HALF_WIDTH))}
 
 
+def _pushes_at_24k(pushes, input_rate):
+    """(frames, samples) counts whose samples are at input_rate -> the same pushes counted in the 24 kHz samples each makes final
+    (differences of inputs.resample_ready over the running total; at 24000 Hz, or with input_rate None, they pass through)."""
+    if input_rate is None:
+        return pushes
+    from .inputs import check_sample_rate, resample_ready, resample_rule
+    _, up, down, half = resample_rule(check_sample_rate(input_rate, "input_rate"))
+    total, converted = 0, []
+    for k, m in pushes:
+        if int(m) < 0:
+            raise ValueError(f"a push holds counts >= 0, got ({k}, {m})")
+        before = total
+        total += int(m)
+        converted.append((k, int(m) if up == down else resample_ready(total, up, down, half) - resample_ready(before, up, down, half)))
+    return converted
+
+
 def stream_schedule(plan, pushes, input_rate=None):
     """Which windows each push completes.  pushes: a list of (frames, samples) counts, one pair per push; returns one list of
     window numbers per push.  Window w is ready in the first push after which ready_frames(w) frames and ready_samples(w) samples
     have been pushed in total; windows are emitted in order, every window once.  input_rate: the sample counts are at that rate,
     as a GazeStream(input_rate=...) takes them; each is first converted to the 24 kHz samples the push makes final (differences
     of inputs.resample_ready over the running total; at 24000 Hz the pieces count as mono fp32, which pass through)."""
-    if input_rate is not None:
-        from .inputs import check_sample_rate, resample_ready, resample_rule
-        _, up, down, half = resample_rule(check_sample_rate(input_rate, "input_rate"))
-        total, converted = 0, []
-        for k, m in pushes:
-            if int(m) < 0:
-                raise ValueError(f"a push holds counts >= 0, got ({k}, {m})")
-            before = total
-            total += int(m)
-            converted.append((k, int(m) if up == down else resample_ready(total, up, down, half) - resample_ready(before, up, down, half)))
-        pushes = converted
+    pushes = _pushes_at_24k(pushes, input_rate)
     frames = samples = 0
     w = 0
     nxt = stream_window(plan, 0)
@@ -158,6 +167,104 @@ def ring_sizes(plan, max_chunk, crop_size, nbins=STFT_N_FFT // 2 + 1):
     cols = (cols + 63) // 64 * 64
     S = int(crop_size)
     return {"slots": slots, "crop_bytes": slots * 3 * S * S * 4, "ring_cols": cols, "spec_bytes": int(nbins) * cols * 4}
+
+
+def ring_limits(nxt, slots, ring_cols):
+    """(frames, samples) the two rings take while window `nxt` (a stream_window result) is the oldest one that has not run."""
+    frames_max = int(nxt["frames_idx"][0]) + int(slots)                   # frame f overwrites f - R < the window's first input
+    cols_max = nxt["first_column"] + int(ring_cols) - 1                   # one column is kept free for close()
+    return frames_max, STFT_HOP * cols_max + STFT_HOP - 1
+
+
+def stream_steps(plan, slots, ring_cols, max_chunk, frames, samples, w, k, m):
+    """The steps a push of k frames and m samples is worked off in by a stream that has taken `frames` frames and `samples`
+    samples and run the windows below w: [(frames, samples, [windows])], each step being as many samples as the spectrum ring
+    takes, at most max_chunk frames as the crop ring takes them, then every window that is ready.  ValueError when neither ring
+    can take more and no window is ready.  The one statement of the step rule: GazeStream.push works a push off by it and
+    stream_live_schedule replays it."""
+    nxt = stream_window(plan, w)
+    steps = []
+    while True:
+        frames_max, samples_max = ring_limits(nxt, slots, ring_cols)
+        dm = max(0, min(m, samples_max - samples))
+        dk = max(0, min(k, max_chunk, frames_max - frames))
+        frames, samples, k, m = frames + dk, samples + dm, k - dk, m - dm
+        ready = []
+        while nxt["ready_frames"] <= frames and nxt["ready_samples"] <= samples:
+            ready.append(w)
+            w += 1
+            nxt = stream_window(plan, w)
+        if dk or dm or ready:
+            steps.append((dk, dm, ready))
+        if not k and not m:
+            return steps
+        if not (dk or dm or ready):
+            if m:
+                raise ValueError(f"the audio runs further ahead of the frames than the spectrum ring holds ({ring_cols} "
+                                 f"columns = {ring_cols * STFT_HOP} samples): window {w} still waits for frame "
+                                 f"{nxt['ready_frames'] - 1}, {frames} pushed; nothing of this push was consumed")
+            raise ValueError(f"the frames run further ahead of the audio than the crop ring holds ({slots} slots): window {w} "
+                             f"still waits for sample {nxt['ready_samples'] - 1}, {samples} pushed; nothing of this push was "
+                             "consumed")
+
+
+LIVE_MODES = ("hold", "linear")
+
+
+def check_live_plan(plan):
+    """A live track shows the forecast of a frame when the frame arrives, so every target of a window must lie past the window's
+    last input; a plan that predicts frames it has already seen (the estimation configs) is a ValueError."""
+    first_target, last_input = int(min(plan["targets"])), int(max(plan["inputs"]))
+    if first_target <= last_input:
+        raise ValueError(f"live= draws the forecast of a frame when that frame arrives, but this plan predicts frames the window "
+                         f"has already seen (its first target is frame {first_target} of the window, its last input frame "
+                         f"{last_input}): there is nothing to show on an arriving frame.  Fold the emitted windows with "
+                         "track_from_windows (then fill_track / render_track) instead")
+
+
+def live_ring_slots(plan, max_chunk, max_gap):
+    """The capacity Rt of the live track ring (frame t in slot t mod Rt): a ring in which, however the recording is pushed, no
+    window's targets recycle a slot some row still reads.
+
+    Take a step after which F frames are in; it pushed dk <= max_chunk of them, frames F - dk .. F - 1, and their rows are
+    computed after the step's windows have been added.
+      reads   row n looks for neighbours a in [n - max_gap + 1, n) and b in (n, a + max_gap], so it reads frames
+              n - max_gap + 1 .. n + max_gap - 1.  The rows of this step and of every later one belong to frames >= F - dk, so the
+              lowest frame still read is  L = F - dk - max_gap + 1 >= F - max_chunk - max_gap + 1.
+      writes  a window runs once its last input frame is in: o + inputs[-1] + 1 <= F, so the largest target written so far is
+              t_max = o + targets[-1] <= F - 1 - inputs[-1] + targets[-1].
+    Writing target t recycles the slot of frame t - Rt; that is harmless iff t - Rt < L for every t written before the read:
+              F - 1 - inputs[-1] + targets[-1] - Rt < F - max_chunk - max_gap + 1
+        <=>   Rt >= (targets[-1] - inputs[-1]) + max_chunk + max_gap - 1.
+    Targets ascend with the windows, so a slot never holds a NEWER frame than the one being written, and a row that finds an
+    OLDER frame in a slot treats it as empty, which it is: nothing has been predicted for the frame the row asks about.  The
+    audio does not enter: a window that waits for audio only runs later, with F larger.  Ego4D forecast plan, max_chunk 32,
+    max_gap 9: 64 + 32 + 9 - 1 = 104 slots, 1.7 MB of 64 x 64 sums."""
+    check_live_plan(plan)
+    max_chunk, max_gap = int(max_chunk), int(max_gap)
+    if max_chunk < 1 or max_gap < 1:
+        raise ValueError(f"max_chunk and max_gap must be positive, got {max_chunk} and {max_gap}")
+    return int(max(plan["targets"])) - int(max(plan["inputs"])) + max_chunk + max_gap - 1
+
+
+def stream_live_schedule(plan, pushes, max_chunk=32, input_rate=None):
+    """The companion of stream_schedule for a live track: known(f) for every frame f of the given pushes, in frame order (a list of
+    ints, one per frame).  known(f) is the number of windows that have run when the step that takes frame f in finishes -- the
+    steps of stream_steps, which GazeStream.push works a push off by: audio, frames, then the ready windows.  The live row of f
+    is computed from windows 0 .. known(f) - 1; every frame of one step has the same known, and known never decreases.  It
+    depends on how the recording is pushed: the same frame pushed later, or with more audio, may know more windows.  pushes
+    and input_rate as stream_schedule takes them; a push the rings cannot take is the ValueError GazeStream.push raises."""
+    sizes = ring_sizes(plan, max_chunk, 1)
+    frames = samples = w = 0
+    known = []
+    for k, m in _pushes_at_24k(pushes, input_rate):
+        k, m = int(k), int(m)
+        if k < 0 or m < 0:
+            raise ValueError(f"a push holds counts >= 0, got ({k}, {m})")
+        for dk, dm, ready in stream_steps(plan, sizes["slots"], sizes["ring_cols"], int(max_chunk), frames, samples, w, k, m):
+            frames, samples, w = frames + dk, samples + dm, w + len(ready)
+            known += [w] * dk
+    return known
 
 
 def track_from_windows(results, n_frames, want=("points", "peak", "count", "heatmaps", "rescaled")):
@@ -213,12 +320,36 @@ class GazeStream:
     composition clip_sample + stft_logpower + audio_windows_at + predict_batch at stream_window's indices and the same batch
     (with input_rate: stft_logpower of resample_audio of the whole waveform).
 
-    Out of scope: attention maps, and fill / overlay inside the stream (fold the results with track_from_windows, then
-    fill_track / render_track).  sample_rate= still names the rate the audio is pushed at as it is, 24 kHz only."""
+    Live track (live="hold" | "linear", forecast plans only): a forecast window predicts frames the camera has not delivered
+    yet, so push_live(frames, wav) answers every pushed frame f with its row of a gaze track, and with overlay=True with the
+    frame drawn over.  The causal rule: the row is computed from the windows that have run when f's step finishes (audio,
+    frames, ready windows, then the rows of the step's frames); with known(f) their number (stream_live_schedule),
+
+      live row of f == row f of fill_track(track_from_windows(results[:known(f)], n_frames=f + max_gap + 1), mode=live, max_gap)
+
+    bit for bit: a predicted frame carries the mean of its maps, added in window order; a frame between two predictions at most
+    max_gap apart the earlier map ("hold") or the time-linear blend ("linear"); any other frame is unpredicted (zero maps, NaN
+    points, peak 0, count 0, neighbours (-1, -1)).  max_gap defaults to default_max_gap(plan).  The track lives in a third ring,
+    fp32 sums (Rt, S/4, S/4) with a count and a frame tag per slot, Rt = live_ring_slots(plan, max_chunk, max_gap) (104 slots,
+    1.7 MB on the Ego4D forecast plan): ops.live_track_add folds each step's windows in, ops.live_track_rows reads the rows out.
+    What a row knows depends on how the recording is pushed -- a frame pushed in a larger piece, or with more audio, may know one
+    window more -- so live rows are reproducible for the same pushes, not across different cuts.  The emitted windows do not
+    change by a bit with live on.  An estimation plan (targets inside the observed span) is refused: it has nothing to show on
+    an arriving frame.
+
+    Out of scope: attention maps per streamed window, a delayed display for estimation plans, and equality with predict_video.
+    sample_rate= still names the rate the audio is pushed at as it is, 24 kHz only."""
 
     def __init__(self, predictor, fps=None, stride=None, segment=None, batch=1, max_chunk=32, pixel_format="rgb24",
-                 matrix="bt601", full_range=False, sample_rate=None, input_rate=None):
+                 matrix="bt601", full_range=False, sample_rate=None, input_rate=None, live=None, max_gap=None, overlay=False,
+                 alpha=0.4, radius=5):
         check_stream_rate(sample_rate)
+        if live is not None and live not in LIVE_MODES:
+            raise ValueError(f"live must be None or one of {LIVE_MODES}, got {live!r}")
+        if overlay and live is None:
+            raise ValueError("overlay=True draws the live track onto the pushed frames: it needs live=\"hold\" or live=\"linear\"")
+        if max_gap is not None and live is None:
+            raise ValueError("max_gap is the gap the live track fills: it needs live=\"hold\" or live=\"linear\"")
         from . import inputs
         if input_rate is not None and sample_rate is not None:
             raise ValueError(f"sample_rate={sample_rate!r} says the audio is pushed at {AUDIO_RATE} Hz as it is, input_rate="
@@ -245,40 +376,29 @@ class GazeStream:
         self._next = stream_window(self.plan, 0)
         self._crops = self._spec = self._tail = self._params = None
         self._tail_base = 0                                  # the stream position of _tail[0]
+        self.live, self.overlay, self.alpha, self.radius = live, bool(overlay), float(alpha), int(radius)
+        self.max_gap, self.track_slots, self._track = None, 0, None
+        if live is not None:
+            from .infer import default_max_gap
+            check_live_plan(self.plan)
+            self.max_gap = default_max_gap(self.plan) if max_gap is None else int(max_gap)
+            if self.max_gap < 1:
+                raise ValueError(f"max_gap must be positive, got {max_gap}")
+            if not 0.0 <= self.alpha <= 1.0 or self.radius < 0:
+                raise ValueError(f"alpha must lie in [0, 1] and radius be >= 0, got {alpha} and {radius}")
+            self.track_slots = live_ring_slots(self.plan, self.max_chunk, self.max_gap)
+            side = self.S // 4                               # the model's heat maps are S/4 x S/4
+            self.capacity = dict(self.capacity, track_slots=self.track_slots,
+                                 track_bytes=self.track_slots * (side * side * 4 + 4 + 8))
 
     # ---- host arithmetic -------------------------------------------------------------------------------------------------------
     def _limits(self, nxt):
         """(frames, samples) the rings take while window `nxt` is the oldest one that has not run."""
-        frames_max = int(nxt["frames_idx"][0]) + self.R                   # frame f overwrites f - R < the window's first input
-        cols_max = nxt["first_column"] + self.ring_cols - 1               # one column is kept free for close()
-        return frames_max, STFT_HOP * cols_max + STFT_HOP - 1
+        return ring_limits(nxt, self.R, self.ring_cols)
 
     def _steps(self, k, m):
         """The steps a push of k frames and m samples is worked off in: [(frames, samples, [windows])]; ValueError when stuck."""
-        frames, samples, w, nxt = self.frames, self.samples, self.next_window, self._next
-        steps = []
-        while True:
-            frames_max, samples_max = self._limits(nxt)
-            dm = max(0, min(m, samples_max - samples))
-            dk = max(0, min(k, self.max_chunk, frames_max - frames))
-            frames, samples, k, m = frames + dk, samples + dm, k - dk, m - dm
-            ready = []
-            while nxt["ready_frames"] <= frames and nxt["ready_samples"] <= samples:
-                ready.append(w)
-                w += 1
-                nxt = stream_window(self.plan, w)
-            if dk or dm or ready:
-                steps.append((dk, dm, ready))
-            if not k and not m:
-                return steps
-            if not (dk or dm or ready):
-                if m:
-                    raise ValueError(f"the audio runs further ahead of the frames than the spectrum ring holds ({self.ring_cols} "
-                                     f"columns = {self.ring_cols * STFT_HOP} samples): window {w} still waits for frame "
-                                     f"{nxt['ready_frames'] - 1}, {frames} pushed; nothing of this push was consumed")
-                raise ValueError(f"the frames run further ahead of the audio than the crop ring holds ({self.R} slots): window {w} "
-                                 f"still waits for sample {nxt['ready_samples'] - 1}, {samples} pushed; nothing of this push was "
-                                 "consumed")
+        return stream_steps(self.plan, self.R, self.ring_cols, self.max_chunk, self.frames, self.samples, self.next_window, k, m)
 
     # ---- device work -----------------------------------------------------------------------------------------------------------
     def _setup(self, H, W, device):
@@ -346,7 +466,67 @@ class GazeStream:
     def push(self, frames=None, wav=None):
         """The next frames -- uint8 (K, H, W, 3), or (K, H * 3 / 2, W) in the stream's pixel format -- and / or the next samples --
         fp32 (m,) at 24 kHz, or with input_rate (m,) / (C, m), floating or int16, at that rate -- both on the device -> the list
-        (possibly empty) of the windows this push completes, in order."""
+        (possibly empty) of the windows this push completes, in order.  On a live stream the windows are folded into the track
+        ring as well, so push and push_live may be mixed; a frame is only answered by the push_live that takes it in."""
+        return self._push(frames, wav, False)[0]
+
+    def push_live(self, frames=None, wav=None):
+        """push() on a stream opened with live=: -> (windows, live).  windows is what push returns.  live answers the K frames of
+        this push, in order, on the device: "frame_idx" int64 (K,), "known" int32 (K,) = the windows the row was computed from
+        (stream_live_schedule), "points" (K, 2) on the crop, "peak" (K,), "count" int32 (K,), "neighbours" int32 (K, 2), "filled"
+        bool (K,), "rescaled" (K, S/4, S/4), "points_source" float64 (K, 2) on the source frame, and with overlay=True "overlay"
+        uint8 (K, H, W, 3), the frames drawn over as render_track draws a track (an unpredicted frame comes back as it is).  A
+        push longer than max_chunk is worked off in steps and its rows are concatenated; a push without frames has K = 0."""
+        if self.live is None:
+            raise ValueError("push_live answers frames with the live track: open the stream with live=\"hold\" or live=\"linear\"")
+        return self._push(frames, wav, True)
+
+    def _live_add(self, results, f_start):
+        """Fold the windows a step ran into the track ring; f_start: the first frame whose row is still to come."""
+        import numpy as np
+        import torch
+        from . import ops
+        maps = torch.cat([r["heatmaps"] for r in results], dim=0)
+        if self._track is None:
+            self._track = ops.live_track_ring(self.track_slots, maps.shape[1], maps.shape[2], maps.device)
+        targets = np.concatenate([np.asarray(r["target_idx"], dtype=np.int64) for r in results])
+        ops.live_track_add(maps, torch.from_numpy(targets).to(maps.device), targets, self._track,
+                           live_from=max(0, f_start - self.max_gap + 1))
+
+    def _live_rows(self, f0, chunk):
+        """The live rows of the step's frames f0 .. f0 + K - 1 (chunk: those frames as they were pushed)."""
+        import torch
+        from . import ops
+        from .infer import points_to_source
+        K, dev = chunk.shape[0], chunk.device
+        if self._track is None:                              # no window has run yet: every row is the unpredicted one
+            side = self.S // 4
+            self._track = ops.live_track_ring(self.track_slots, side, side, dev)
+        rows = ops.live_track_rows(self._track, f0, K, mode=self.live, max_gap=self.max_gap,
+                                   want=("rescaled", "points", "peak", "count", "neighbours"))
+        rows["filled"] = (rows["count"] == 0) & (rows["neighbours"][:, 0] >= 0)
+        rows["frame_idx"] = torch.arange(f0, f0 + K, dtype=torch.int64, device=dev)
+        rows["known"] = torch.full((K,), self.next_window, dtype=torch.int32, device=dev)
+        rows["points_source"] = points_to_source(rows["points"], self.predictor._video_params_row(*self.hw), self.S)
+        if self.overlay:
+            rows["overlay"] = self.predictor.render_track(chunk, rows, alpha=self.alpha, radius=self.radius, **self.fmt)
+        return rows
+
+    def _live_empty(self, device):
+        """The live dict of a push without frames."""
+        import torch
+        side = self.S // 4
+        shapes = {"frame_idx": ((0,), torch.int64), "known": ((0,), torch.int32), "points": ((0, 2), torch.float32),
+                  "peak": ((0,), torch.float32), "count": ((0,), torch.int32), "neighbours": ((0, 2), torch.int32),
+                  "filled": ((0,), torch.bool), "rescaled": ((0, side, side), torch.float32),
+                  "points_source": ((0, 2), torch.float64)}
+        out = {k: torch.empty(shape, dtype=dt, device=device) for k, (shape, dt) in shapes.items()}
+        if self.overlay:
+            H, W = self.hw if self.hw is not None else (0, 0)
+            out["overlay"] = torch.empty((0, H, W, 3), dtype=torch.uint8, device=device)
+        return out
+
+    def _push(self, frames, wav, want_live):
         import torch
         from . import lib as L
         from .infer import _picture_hw
@@ -370,7 +550,7 @@ class GazeStream:
                 raise ValueError(f"wav must be an fp32 (m,) waveform at {AUDIO_RATE} Hz, got {tuple(wav.shape)} {wav.dtype}")
             m_in = m = wav.numel()
         steps = self._steps(k, m)                            # raises before anything is consumed, the resampler included
-        results = []
+        results, rows = [], []
         fa = sa = 0
         with torch.no_grad(), torch.cuda.device(self.predictor.device):
             if k and self.hw is None:
@@ -387,8 +567,19 @@ class GazeStream:
                     self._ingest(frames[fa:fa + dk])
                     fa += dk
                 if ready:
-                    results += self._run(ready)
-        return results
+                    ran = self._run(ready)
+                    results += ran
+                    if self.live is not None:                # before the rows of this step's frames, which come last
+                        self._live_add(ran, self.frames - dk)
+                if dk and want_live:
+                    rows.append(self._live_rows(self.frames - dk, frames[fa - dk:fa]))
+            if not want_live:
+                return results, None
+            if not rows:
+                dev = frames.device if frames is not None else (wav.device if wav is not None else self.predictor.device)
+                return results, self._live_empty(dev)
+            live = rows[0] if len(rows) == 1 else {key: torch.cat([r[key] for r in rows], dim=0) for key in rows[0]}
+        return results, live
 
     def close(self, wav_pad=True):
         """End the stream.  wav_pad: the column the offline STFT adds at the end of a waveform whose length is no multiple of the

@@ -892,6 +892,41 @@ int csts_stream_ingest_yuv(const uint8_t* chunk_yuv, int K, int H, int W, const 
                            hipStream_t stream);
 int csts_stream_gather(const float* ring, int R, const int* slots, float* out, int B, int T, int S, hipStream_t stream);
 
+/* ---- live gaze track (csts_amd/csrc/stream.hip, GazeStream(live=...)): a forecast window predicts frames the camera has not
+ *      delivered yet, so the track row of a frame can be had the moment the frame arrives.  The track lives in a ring of Rt slots
+ *      whose size does not depend on the length of the stream: sum fp32 [Rt][H * W], count int32 [Rt], frame int64 [Rt] = the
+ *      frame number a slot holds, -1 when empty; frame t lives in slot t mod Rt.  All in DEVICE memory.
+ *      live_track_add: maps [P][H * W] fp32 (the preds of newly run windows) and target_idx int64 [P], walked in ascending p:
+ *        t = target_idx[p] < 0:           the row is skipped
+ *        frame[t mod Rt] != t:            the slot restarts: sum = 0 + maps[p], count = 1, frame = t (a stale slot is recycled
+ *                                         here; there is no clearing pass)
+ *        frame[t mod Rt] == t:            sum += maps[p], count += 1
+ *      so a slot's sum is (((0 + row_0) + row_1) + ...) over the rows that target its frame, in the order of the calls and in
+ *      ascending p inside a call: the sum of csts_gaze_track when the windows are added in the order they ran.  One workgroup
+ *      per slot takes the rows of its slot: no atomics, one launch, a slot no row names is not touched.  The caller keeps
+ *      targets in window order and never names a target t while frame t - Rt is still to be read (csts_amd.ops.live_track_add
+ *      refuses that on the host).  1 <= P <= 65535, 1 <= Rt <= 65535, H * W <= CSTS_GAZE_DECODE_MAX_HW.
+ *      live_track_rows: the K frames n = f0 .. f0 + K - 1, one workgroup each.  With c(t) = count[t mod Rt] when t >= 0 and
+ *      frame[t mod Rt] == t, else 0 (a slot that holds another frame is empty for t), row n is row n of
+ *      csts_gaze_track_fill(mode, max_gap) on the track whose frame t has count c(t) and heatmaps sum * (1 / count), i.e.
+ *        c(n) > 0:   neighbours (n, n), m = the mean of frame n
+ *        c(n) == 0:  a = the largest t in [n - max_gap + 1, n) with c(t) > 0, b = the smallest t in (n, a + max_gap] with
+ *                    c(t) > 0; both exist: neighbours (a, b), m = mean_a (mode 0) or wa * mean_a + wb * mean_b (mode 1, the
+ *                    weights and the arithmetic of csts_gaze_track_fill); otherwise neighbours (-1, -1), maps 0, points NaN,
+ *                    peak 0
+ *        heatmaps = m; rescaled, points, peak from m by the device function csts_gaze_track and csts_gaze_track_fill use;
+ *        out_count = c(n).
+ *      Outputs heatmaps and rescaled [K][H * W], points [K][2], peak [K] fp32, out_count [K] and neighbours [K][2] int32; each
+ *      may be NULL and is then skipped; with all NULL nothing is launched.  The ring is only read.  0 <= f0,
+ *      f0 + K + max_gap < 2^31, 1 <= K <= 65535, 1 <= max_gap <= CSTS_GAZE_FILL_MAX_GAP.  128-bit accesses when H * W is a
+ *      multiple of 4 and the maps are 16-byte aligned.  One launch each; no allocation, no synchronisation, no host read:
+ *      graph-capturable (f0 is a launch argument). */
+int csts_live_track_add(const float* maps, const int64_t* target_idx, int P, int H, int W, float* sum, int* count, int64_t* frame,
+                        int Rt, hipStream_t stream);
+int csts_live_track_rows(const float* sum, const int* count, const int64_t* frame, int Rt, int64_t f0, int K, int H, int W, int mode,
+                         int max_gap, float* heatmaps, float* rescaled, float* points, float* peak, int* out_count, int* neighbours,
+                         hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

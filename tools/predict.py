@@ -55,7 +55,14 @@ json_stats line gains "stream", "chunk" and "dropped".  A recording at another r
 at that rate, int16 and (C, n) as stored -- the samples up to frame_end * rate / fps -- and resampled inside the stream with the
 filter state carried from push to push (GazePredictor.stream(input_rate=rate)); --out records sample_rate and audio_rate as the
 offline path does.  --fps must then be integral (a stream places its audio by the exact ratio of columns to frames); --overlay,
---fill and the attention flags are not part of the stream."""
+--fill and the attention flags are not part of the stream.
+--live {hold,linear} (with --stream, forecast configurations): every pushed frame is answered with its row of the live gaze track
+(GazeStream.push_live: the forecast shown on the frame it was made for, when that frame arrives, from the windows that had run by
+then; the frames between two predictions at most --max-gap apart, default csts_amd.default_max_gap of the plan, hold the earlier
+map or blend the two).  --out also receives live_points (N, 2), live_peak, live_count, live_known (the windows each row was
+computed from), live_filled and live_points_source (N, 2), and with --overlay live_overlay uint8 (N, H, W, 3), the frames drawn over
+as they arrived; --overlay-dir writes those frames as PNGs.  The entries written without --live stay as they are; the json_stats
+line gains "live", "max_gap" and "live_filled_frames".  --fill stays an offline flag: the mode of a live track is --live's."""
 import argparse
 import json
 import os
@@ -103,6 +110,8 @@ def parse_args(argv=None):
                    help="1: frames_yuv is full range, 0: limited (default: the npz entry yuv_full_range, else limited)")
     p.add_argument("--stream", action="store_true", help="with --video: replay the recording through GazePredictor.stream")
     p.add_argument("--chunk", default=None, type=int, help="with --stream: frames per push (default 8)")
+    p.add_argument("--live", default=None, choices=["hold", "linear"],
+                   help="with --stream: answer every pushed frame with its row of the live gaze track (honours --max-gap, --overlay)")
     p.add_argument("--seed", default=2000, type=int, help="seed of the synthetic batch used without --clip")
     p.add_argument("--batch", default=2, type=int, help="clips in the synthetic batch used without --clip")
     p.add_argument("--no-graph", action="store_true", help="launch the kernels eagerly instead of replaying a HIP graph")
@@ -128,7 +137,7 @@ def parse_args(argv=None):
         p.error("--attention-dir draws onto a clip's uint8 frames: it needs --clip")
     if args.fill is not None and args.video is None:
         p.error("--fill fills the track of a recording: it needs --video")
-    if args.max_gap is not None and args.fill is None:
+    if args.max_gap is not None and args.fill is None and args.live is None:
         p.error("--max-gap belongs to a fill mode: it needs --fill")
     if args.max_gap is not None and args.max_gap < 1:
         p.error("--max-gap must be positive")
@@ -140,9 +149,13 @@ def parse_args(argv=None):
         p.error("--chunk is the push size of --stream")
     if args.chunk is not None and args.chunk < 1:
         p.error("--chunk must be positive")
-    if args.stream and (args.overlay or args.overlay_dir or args.fill or args.attention_track or args.attention_overlay is not None):
+    if args.live is not None and not args.stream:
+        p.error("--live answers the frames of a replayed stream: it needs --stream")
+    offline_extras = args.fill or args.attention_track or args.attention_overlay is not None
+    if args.stream and (offline_extras or ((args.overlay or args.overlay_dir) and args.live is None)):
         p.error("--stream emits windows as they complete: --overlay, --fill and the attention flags are not part of it (fold the "
-                "windows with csts_amd.track_from_windows, then fill_track / render_track)")
+                "windows with csts_amd.track_from_windows, then fill_track / render_track; --live hold|linear draws the live "
+                "track, with --overlay onto the frames as they arrive)")
     if args.sample_rate is not None and args.sample_rate < 1:
         p.error("--sample-rate must be positive")
     if (args.pixel_format or args.yuv_matrix or args.yuv_full_range is not None) and args.video is None and args.clip is None:
@@ -185,26 +198,37 @@ def waveform(z, rate, dev):
     return (wav if rate is not None and wav.dtype == torch.int16 else wav.float()).to(dev)
 
 
-def replay_stream(predictor, frames, wav, fps, stride, chunk, fmt, rate=None):
+def replay_stream(predictor, frames, wav, fps, stride, chunk, fmt, rate=None, live=None, max_gap=None, overlay=False):
     """The recording pushed through GazePredictor.stream in pushes of `chunk` frames with the matching audio, then closed ->
     (the track by track_from_windows with "windows" = their number, the window numbers in emission order, the dropped count).
-    rate: the rate wav, (n,) or (C, n), was recorded at; the stream resamples it (input_rate)."""
+    rate: the rate wav, (n,) or (C, n), was recorded at; the stream resamples it (input_rate).  live "hold" | "linear": the pushes
+    go through push_live and the track gains "live" = the rows of all N frames (GazeStream.push_live's dict) and "live_max_gap"."""
     from fractions import Fraction
     from csts_amd import track_from_windows
-    stream = predictor.stream(fps=fps, stride=stride, input_rate=rate, **fmt)
+    stream = predictor.stream(fps=fps, stride=stride, input_rate=rate, live=live, max_gap=max_gap, overlay=overlay, **fmt)
     N, n = frames.shape[0], wav.shape[-1]
     per = Fraction(AUDIO_RATE if rate is None else rate) / stream.plan["fps"]     # samples per frame
-    results, sent = [], 0
+    results, rows, sent = [], [], 0
     for a in range(0, N, chunk):
         b = min(a + chunk, N)
         upto = n if b == N else min(n, int(b * per))
-        results += stream.push(frames[a:b], wav[..., sent:upto] if upto > sent else None)
+        piece = wav[..., sent:upto] if upto > sent else None
+        if live is None:
+            results += stream.push(frames[a:b], piece)
+        else:
+            done, answered = stream.push_live(frames[a:b], piece)
+            results += done
+            rows.append(answered)
         sent = max(sent, upto)
     results += stream.close()
     if not results:
         raise SystemExit(f"the stream of {N} frames and {n} samples completed no window (one window observes "
                          f"{stream.plan['observed']} frames)")
-    return track_from_windows(results, N), [r["window"] for r in results], stream.dropped
+    track = track_from_windows(results, N)
+    if live is not None:
+        track["live"] = {k: torch.cat([r[k] for r in rows], dim=0) for k in rows[0]}
+        track["live_max_gap"] = stream.max_gap
+    return track, [r["window"] for r in results], stream.dropped
 
 
 def write_pngs(overlay, directory, every):
@@ -264,7 +288,8 @@ def main(argv=None):
             if args.stream:
                 try:
                     out, stream_windows, dropped = replay_stream(predictor, frames, waveform(z, rate, dev), fps, args.stride,
-                                                                 8 if args.chunk is None else args.chunk, fmt, rate)
+                                                                 8 if args.chunk is None else args.chunk, fmt, rate, live=args.live,
+                                                                 max_gap=args.max_gap, overlay=bool(args.overlay or args.overlay_dir))
                 except ValueError as e:
                     raise SystemExit(str(e))
             else:
@@ -285,9 +310,12 @@ def main(argv=None):
         if args.stream:
             arrays["stream_windows"] = np.asarray(stream_windows, dtype=np.int64)
             arrays["stream_dropped"] = np.int64(dropped)
+        if args.live is not None:
+            live_keys = ("points", "peak", "count", "known", "filled", "points_source") + (("overlay",) if "overlay" in out["live"] else ())
+            arrays.update({"live_" + k: out["live"][k].cpu().numpy() for k in live_keys})
         np.savez(args.out, **arrays, **rates)
         if args.overlay_dir is not None:
-            write_pngs(arrays["overlay"], args.overlay_dir, args.overlay_every)
+            write_pngs(arrays["live_overlay" if args.live is not None else "overlay"], args.overlay_dir, args.overlay_every)
         record = {"_type": "predict_video", "checkpoint": predictor.checkpoint_path, "source": args.video,
                   "graph": predictor.graph, "out": args.out, "windows": out["windows"],
                   "frames": int(arrays["count"].shape[0]),
@@ -300,6 +328,8 @@ def main(argv=None):
             record.update({"fill": args.fill, "max_gap": int(out["max_gap"]), "filled_frames": int(arrays["filled"].sum())})
         if args.stream:
             record.update({"stream": True, "chunk": 8 if args.chunk is None else args.chunk, "dropped": int(dropped)})
+        if args.live is not None:
+            record.update({"live": args.live, "max_gap": int(out["live_max_gap"]), "live_filled_frames": int(arrays["live_filled"].sum())})
         if attention_track:
             frames = arrays["attention_count"] > 0
             if args.fill is not None:
