@@ -217,7 +217,7 @@ __host__ __device__ __forceinline__ bool spatial_hw_ok(int64_t H, int64_t W, int
 }
 
 // dynamic LDS of a sample launch for source rows of up to W pixels
-inline int sample_lds_bytes(int W, int* rowcap) {
+__host__ __device__ inline int sample_lds_bytes(int W, int* rowcap) {
   *rowcap = (3 * W + 30 + 15) / 16 * 16;
   return SAMPLE_ROWS * 2 * *rowcap;
 }

@@ -10,7 +10,12 @@
 //   live_track_add       : the maps of newly run windows folded into a ring of per-frame sums (frame t in slot t mod Rt).
 //   live_track_rows      : the rows of a gaze track for the frames just pushed, out of that ring: mean, neighbours, hold or blend,
 //                          decode -- the device functions of csts_gaze_track / csts_gaze_track_fill (track_shared.h).
+//   group_stft, group_audio_windows, group_ingest(_yuv) : stream_stft, stream_audio_windows and stream_ingest(_yuv) for the
+//                          streams of a GazeStreamGroup, which share one arena of rings: one launch takes what several streams
+//                          pushed, from a job table; the column, the window and the crop are computed by the same device functions.
 // Every table is DEVICE memory read when the kernel runs; no atomics, no allocation, no synchronisation.
+#include <vector>
+
 #include "stft_shared.h"
 #include "yuv_shared.h"
 #include "track_shared.h"
@@ -264,6 +269,151 @@ int ingest_check(const void* chunk, const void* pairs, const void* params, const
   return 0;
 }
 
+// ---- stream group (GazeStreamGroup): N streams share one arena of crop rings (streams * R, 3, S, S) and one of spectrum rings
+// (streams, nbins, ring_cols); what several streams pushed in one tick goes in with ONE launch per stage, from a job table in
+// device memory.  A workgroup finds its job from blockIdx alone, so every table read is a uniform (scalar) load, and then runs
+// the device function the single-stream kernel runs: a column, a crop, a window has the bits it has there.
+
+constexpr int GROUP_STFT_JOB = 8;      // int64 per row: sample buffer, s_base, m, n_total, f0, f1, stream, first workgroup
+constexpr int GROUP_INGEST_JOB = 6;    // int64 per row: chunk, chunk bytes, K, H, W, LDS row capacity
+
+// grid (total columns), 256 threads; dynamic LDS stft_lds_floats.  The rows are ordered by their first workgroup (a running sum
+// of f1 - f0, which the host checks): the job of workgroup g is the LAST row whose first workgroup is <= g, which skips the rows
+// without columns.  A row whose stream lies outside [0, streams) writes nothing.
+__global__ __launch_bounds__(256) void group_stft_kernel(const int64_t* __restrict__ jobs, int njobs, float* __restrict__ rings,
+                                                         int streams, int nbins, int ring_cols, int n_fft, int hop, int win,
+                                                         float eps) {
+  extern __shared__ float sm[];
+  const int64_t g = blockIdx.x;
+  int lo = 0, hi = njobs - 1;                                 // uniform over the workgroup: blockIdx and the table alone
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (jobs[(int64_t)mid * GROUP_STFT_JOB + 7] <= g) lo = mid; else hi = mid - 1;
+  }
+  const int64_t* job = jobs + (int64_t)lo * GROUP_STFT_JOB;
+  const float* buf = reinterpret_cast<const float*>(job[0]);
+  const int64_t s_base = job[1], s_end = s_base + job[2], n_total = job[3], f0 = job[4], f1 = job[5], slot = job[6];
+  const int64_t f = f0 + (g - job[7]);
+  if (slot < 0 || slot >= streams || f < f0 || f >= f1) return;
+  float* ring = rings + slot * (int64_t)nbins * ring_cols;
+  stft_logpower_column(sm, f, n_fft, hop, win, eps,
+                       [=](int64_t s) { return s >= 0 && (n_total < 0 || s < n_total) && s >= s_base && s < s_end; },
+                       [=](int64_t s) { return buf[s - s_base]; }, ring + (int)(f % ring_cols), ring_cols);
+}
+
+// grid (blocks over nbins * width / V, B * T), 256 threads: stream_audio_windows_kernel with the ring and its newest column
+// looked up per batch row: row b reads ring stream_of[b] under newest[stream_of[b]]; a stream outside [0, streams) is NaN.
+template <bool VEC>
+__global__ __launch_bounds__(256) void group_audio_windows_kernel(const float* __restrict__ rings, int streams, int ring_cols,
+                                                                  const int* __restrict__ stream_of,
+                                                                  const int64_t* __restrict__ newest_of,
+                                                                  const int64_t* __restrict__ centers, float* __restrict__ out, int T,
+                                                                  int nbins, int width) {
+  const int bt = blockIdx.y;
+  const int s = stream_of[bt / T];
+  const bool known = s >= 0 && s < streams;                // uniform over the workgroup (one window)
+  const int64_t newest = known ? newest_of[s] : -1;
+  const int64_t lo = centers[bt] - width / 2, hi = lo + width - 1;
+  const int64_t oldest = newest - ring_cols + 1 > 0 ? newest - ring_cols + 1 : 0;
+  const bool ok = known && lo >= oldest && hi <= newest;
+  const int start = ok ? (int)(lo % ring_cols) : 0;
+  const int64_t total = (int64_t)nbins * width;
+  const float* ring = rings + (int64_t)(ok ? s : 0) * nbins * ring_cols;
+  float* o = out + (int64_t)bt * total;
+  constexpr int V = VEC ? 4 : 1;
+  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V; i < total; i += (int64_t)gridDim.x * 256 * V) {
+    const int bin = (int)(i / width), j = (int)(i - (int64_t)bin * width);
+    const float* row = ring + (int64_t)bin * ring_cols;
+    float v[V];
+#pragma unroll
+    for (int q = 0; q < V; ++q) {
+      int c = start + j + q;                               // < 2 ring_cols: width <= ring_cols
+      if (c >= ring_cols) c -= ring_cols;
+      v[q] = ok ? row[c] : __builtin_nanf("");
+    }
+    if constexpr (VEC) {
+      *reinterpret_cast<float4*>(o + i) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+      o[i] = v[0];
+    }
+  }
+}
+
+// one row of the (job, frame in chunk, arena slot) table and its job: inside the table, the chunk and the arena, or the workgroup
+// writes nothing.  All of it is uniform over the workgroup (one pair).
+__device__ __forceinline__ const int64_t* group_pair_job(const int64_t* __restrict__ jobs, int njobs, const int* __restrict__ pairs,
+                                                         int p, int arena_slots, int* j, int* frame, int* slot) {
+  *j = pairs[3 * p];
+  *frame = pairs[3 * p + 1];
+  *slot = pairs[3 * p + 2];
+  if (*j < 0 || *j >= njobs || *slot < 0 || *slot >= arena_slots) return nullptr;
+  const int64_t* job = jobs + (int64_t)*j * GROUP_INGEST_JOB;
+  return *frame >= 0 && *frame < job[2] ? job : nullptr;
+}
+
+// grid (ceil(S / 4), pairs), 256 threads; dynamic LDS lds_bytes = sample_lds_bytes of the widest job.  A job whose row capacity is
+// not the one its W asks for, or does not fit the launch's LDS, writes nothing.
+__global__ __launch_bounds__(256) void group_ingest_kernel(const int64_t* __restrict__ jobs, int njobs, const int* __restrict__ params,
+                                                           const int* __restrict__ pairs, float* __restrict__ arena, int arena_slots,
+                                                           int S, int lds_bytes, float3 mean, float3 inv_std) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  int j, frame, slot;
+  const int64_t* job = group_pair_job(jobs, njobs, pairs, blockIdx.y, arena_slots, &j, &frame, &slot);
+  if (!job) return;
+  const int H = (int)job[3], W = (int)job[4];
+  int rowcap;
+  if (sample_lds_bytes(W, &rowcap) > lds_bytes || job[5] != rowcap) return;
+  sample_rows(reinterpret_cast<const uint8_t*>(job[0]), job[1], 0, frame, H, W, params + 5 * j, false, arena, slot, 0, 1, S, rowcap,
+              mean, inv_std, lds);
+}
+
+// the same for chunks of 4:2:0 frames; the job's row capacity is the luma one, lcap of sample_yuv_lds_bytes
+__global__ __launch_bounds__(256) void group_ingest_yuv_kernel(const int64_t* __restrict__ jobs, int njobs,
+                                                               const int* __restrict__ params, const int* __restrict__ pairs,
+                                                               float* __restrict__ arena, int arena_slots, int S, int lds_bytes,
+                                                               int layout, YuvCoef k, float3 mean, float3 inv_std) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  int j, frame, slot;
+  const int64_t* job = group_pair_job(jobs, njobs, pairs, blockIdx.y, arena_slots, &j, &frame, &slot);
+  if (!job) return;
+  const int H = (int)job[3], W = (int)job[4];
+  int lcap, ccap;
+  if (sample_yuv_lds_bytes(W, &lcap, &ccap) > lds_bytes || job[5] != lcap) return;
+  sample_rows_yuv(reinterpret_cast<const uint8_t*>(job[0]), job[1], 0, frame, H, W, params + 5 * j, false, arena, slot, 0, 1, S, lcap,
+                  ccap, layout, k, mean, inv_std, lds);
+}
+
+// the host copy of an ingest job table: every row as csts_stream_ingest asks it of its chunk -> the widest row's LDS bytes, or -1
+int group_ingest_check(const int64_t* jobs_host, int njobs, const void* jobs, const void* params, const void* pairs, int npairs,
+                       const void* arena, int64_t arena_slots, int S, const float* mean, const float* std, bool yuv) {
+  CSTS_REQUIRE(jobs_host && njobs > 0 && njobs <= 65535, "the host copy of the job table is missing, or 1 <= njobs <= 65535 fails");
+  CSTS_REQUIRE(npairs > 0 && npairs <= 65535 && arena_slots > 0 && S > 0 && S <= 4096 &&
+                   arena_slots * 3 * S * S < ((int64_t)1 << 40) && arena_slots < ((int64_t)1 << 31),
+               "bad sizes (S <= 4096, 1 <= pairs <= 65535)");
+  int lds = 0;
+  for (int j = 0; j < njobs; ++j) {
+    const int64_t* job = jobs_host + (int64_t)j * GROUP_INGEST_JOB;
+    const int64_t bytes = job[1], K = job[2], H = job[3], W = job[4];
+    CSTS_REQUIRE(job[0] != 0 && K > 0 && K < ((int64_t)1 << 31) && H > 0 && H < ((int64_t)1 << 31) && W > 0 && W <= 6000,
+                 "a job has a null chunk or bad sizes (K, H >= 1, 1 <= W <= 6000)");
+    CSTS_REQUIRE((job[0] & 15) == 0, "every chunk must be 16-byte aligned");
+    int cap, ccap, need;
+    if (yuv) {
+      CSTS_REQUIRE(H >= 2 && W >= 2 && (H & 1) == 0 && (W & 1) == 0, "4:2:0 frames need even H, W >= 2");
+      CSTS_REQUIRE(bytes == K * yuv_frame_bytes((int)H, (int)W), "a job's chunk bytes are not K * H * 3 / 2 * W");
+      need = sample_yuv_lds_bytes((int)W, &cap, &ccap);
+    } else {
+      CSTS_REQUIRE(bytes == K * H * W * 3, "a job's chunk bytes are not K * H * W * 3");
+      need = sample_lds_bytes((int)W, &cap);
+    }
+    CSTS_REQUIRE(job[5] == cap, "a job's LDS row capacity is not the one its W asks for");
+    lds = std::max(lds, need);
+  }
+  CSTS_REQUIRE(jobs && params && pairs && arena && mean && std, "bad args");
+  CSTS_REQUIRE(aligned16(arena), "the arena must be 16-byte aligned");
+  return lds;
+}
+
 }  // namespace
 
 extern "C" int csts_stream_stft(const float* buf, int64_t s_base, int64_t m, int64_t n_total, int64_t f0, int64_t f1, float* ring,
@@ -382,6 +532,85 @@ extern "C" int csts_live_track_rows(const float* sum, const int* count, const in
   else if (nch <= 2) launch_live_rows<2>(vec, n, stream, sum, count, frame, Rt, f0, H, W, mode, max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
   else if (nch <= 4) launch_live_rows<4>(vec, n, stream, sum, count, frame, Rt, f0, H, W, mode, max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
   else launch_live_rows<8>(vec, n, stream, sum, count, frame, Rt, f0, H, W, mode, max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_group_stft(const int64_t* jobs, const int64_t* jobs_host, int njobs, float* rings, int streams, int ring_cols,
+                               int n_fft, int hop, int win, float eps, hipStream_t stream) {
+  CSTS_REQUIRE(jobs_host && njobs > 0 && njobs <= 65535, "the host copy of the job table is missing, or 1 <= njobs <= 65535 fails");
+  CSTS_REQUIRE(streams > 0 && ring_cols > 0 && n_fft > 0 && hop > 0 && win > 0 && win <= n_fft && n_fft <= 2048, "bad args");
+  std::vector<char> named((size_t)streams, 0);
+  int64_t total = 0;
+  for (int j = 0; j < njobs; ++j) {
+    const int64_t* job = jobs_host + (int64_t)j * GROUP_STFT_JOB;
+    const int64_t s_base = job[1], m = job[2], n_total = job[3], f0 = job[4], f1 = job[5], slot = job[6];
+    CSTS_REQUIRE(slot >= 0 && slot < streams, "a job names a stream outside [0, streams)");
+    CSTS_REQUIRE(!named[(size_t)slot], "two jobs name one stream");
+    named[(size_t)slot] = 1;
+    CSTS_REQUIRE((job[0] != 0 || m == 0) && m >= 0 && s_base >= 0, "a job has a null sample buffer or bad sizes");
+    CSTS_REQUIRE(f0 >= 0 && f1 >= f0 && f1 - f0 <= ring_cols && f1 <= ((int64_t)1 << 40),
+                 "a job's columns [f0, f1) must be at most one turn of the ring");
+    CSTS_REQUIRE(n_total < 0 || n_total <= s_base + m, "n_total lies past the samples pushed");
+    CSTS_REQUIRE(job[7] == total, "a job's first workgroup is not the number of columns before it");
+    if (f1 > f0) {   // every sample a column reads is zero by rule (before 0, at or past n_total) or inside the job's buffer
+      const int64_t first = std::max<int64_t>(stft_first_sample(f0, n_fft, hop, win), 0);
+      int64_t last = stft_first_sample(f1 - 1, n_fft, hop, win) + win;        // one past the last sample read
+      if (n_total >= 0) last = std::min(last, n_total);
+      CSTS_REQUIRE(last <= first || (first >= s_base && last <= s_base + m), "a column needs a sample the buffer does not hold");
+    }
+    total += f1 - f0;
+  }
+  CSTS_REQUIRE(total < ((int64_t)1 << 31), "too many columns in one launch");
+  if (total == 0) return 0;
+  CSTS_REQUIRE(jobs && rings, "bad args");
+  const size_t sm = (size_t)stft_lds_floats(n_fft, win) * sizeof(float);
+  hipLaunchKernelGGL(group_stft_kernel, dim3((unsigned)total), dim3(256), sm, stream, jobs, njobs, rings, streams, n_fft / 2 + 1,
+                     ring_cols, n_fft, hop, win, eps);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_group_audio_windows(const float* rings, int streams, int ring_cols, const int* stream_of, const int64_t* newest,
+                                        const int64_t* centers, float* out, int B, int T, int nbins, int width, hipStream_t stream) {
+  CSTS_REQUIRE(rings && stream_of && newest && centers && out && streams > 0 && B > 0 && T > 0 && nbins > 0 && width > 0 &&
+                   (int64_t)B * T <= 65535, "bad args (B * T <= 65535)");
+  CSTS_REQUIRE((width & 1) == 0 && width <= ring_cols, "width must be even and at most ring_cols");
+  const bool vec = (width & 3) == 0 && aligned16(out);
+  const dim3 grid((unsigned)std::min<int64_t>(cdiv((int64_t)nbins * width, vec ? 1024 : 256), 1024), B * T);
+  if (vec)
+    hipLaunchKernelGGL(group_audio_windows_kernel<true>, grid, dim3(256), 0, stream, rings, streams, ring_cols, stream_of, newest,
+                       centers, out, T, nbins, width);
+  else
+    hipLaunchKernelGGL(group_audio_windows_kernel<false>, grid, dim3(256), 0, stream, rings, streams, ring_cols, stream_of, newest,
+                       centers, out, T, nbins, width);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_group_ingest(const int64_t* jobs, const int64_t* jobs_host, int njobs, const int* params, const int* pairs,
+                                 int npairs, float* arena, int64_t arena_slots, int S, const float mean[3], const float std[3],
+                                 hipStream_t stream) {
+  const int lds = group_ingest_check(jobs_host, njobs, jobs, params, pairs, npairs, arena, arena_slots, S, mean, std, false);
+  if (lds < 0) return -1;
+  if (lds > 65536) CSTS_REQUIRE(csts_dyn_lds_optin(reinterpret_cast<const void*>(&group_ingest_kernel), lds), "LDS opt-in");
+  const float3 m = make_float3(mean[0], mean[1], mean[2]), is = make_float3(1.f / std[0], 1.f / std[1], 1.f / std[2]);
+  hipLaunchKernelGGL(group_ingest_kernel, dim3((unsigned)cdiv(S, SAMPLE_ROWS), npairs), dim3(256), lds, stream, jobs, njobs, params,
+                     pairs, arena, (int)arena_slots, S, lds, m, is);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_group_ingest_yuv(const int64_t* jobs, const int64_t* jobs_host, int njobs, const int* params, const int* pairs,
+                                     int npairs, float* arena, int64_t arena_slots, int S, const float mean[3], const float std[3],
+                                     int layout, int matrix, int full_range, hipStream_t stream) {
+  CSTS_REQUIRE(yuv_args_ok(layout, matrix), "layout must be CSTS_YUV_NV12 or CSTS_YUV_I420, matrix CSTS_YUV_BT601 or CSTS_YUV_BT709");
+  const int lds = group_ingest_check(jobs_host, njobs, jobs, params, pairs, npairs, arena, arena_slots, S, mean, std, true);
+  if (lds < 0) return -1;
+  if (lds > 65536) CSTS_REQUIRE(csts_dyn_lds_optin(reinterpret_cast<const void*>(&group_ingest_yuv_kernel), lds), "LDS opt-in");
+  const float3 m = make_float3(mean[0], mean[1], mean[2]), is = make_float3(1.f / std[0], 1.f / std[1], 1.f / std[2]);
+  hipLaunchKernelGGL(group_ingest_yuv_kernel, dim3((unsigned)cdiv(S, SAMPLE_ROWS), npairs), dim3(256), lds, stream, jobs, njobs, params,
+                     pairs, arena, (int)arena_slots, S, lds, layout, yuv_coef(matrix, full_range), m, is);
   CSTS_LAUNCH_CHECK();
   return 0;
 }

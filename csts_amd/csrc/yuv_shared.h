@@ -55,7 +55,7 @@ __device__ __forceinline__ int yuv_stage(uint8_t* __restrict__ dst, const uint8_
 // dynamic LDS of a 4:2:0 sample launch for source rows of up to W pixels.  Per wave: two luma rows of lcap bytes, then the chroma of
 // both rows: two interleaved rows of lcap bytes (nv12) or U, U, V, V rows of ccap bytes (i420); 2 lcap <= 4 ccap.  About
 // 4 W + 200 bytes against the RGB pass's 2 (3 W + 30).
-inline int sample_yuv_lds_bytes(int W, int* lcap, int* ccap) {
+__host__ __device__ inline int sample_yuv_lds_bytes(int W, int* lcap, int* ccap) {
   *lcap = (W + 30 + 15) / 16 * 16;
   *ccap = (W / 2 + 30 + 15) / 16 * 16;
   return SAMPLE_ROWS * (2 * *lcap + 4 * *ccap);

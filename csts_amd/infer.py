@@ -503,6 +503,18 @@ class GazePredictor:
                           pixel_format=pixel_format, matrix=matrix, full_range=full_range, sample_rate=sample_rate,
                           input_rate=input_rate, live=live, max_gap=max_gap, overlay=overlay, alpha=alpha, radius=radius)
 
+    def stream_group(self, streams, fps=None, stride=None, segment=None, batch=4, max_chunk=32, pixel_format="rgb24",
+                     matrix="bt601", full_range=False, input_rate=None):
+        """`streams` live streams on this predictor, served together (csts_amd.stream.GazeStreamGroup): push({slot: (frames,
+        wav)}) is one tick -- what all the slots pushed goes into one arena of rings with one launch per stage, and the windows
+        that become ready in the same tick are predicted together, `batch` per predict_batch call, whichever slot they belong
+        to; close(slot) / close() end a slot / all of them, reset(slot) reopens one.  The keywords are stream()'s and hold for
+        every slot; each slot has its own source size.  live=, overlay= and attention are not part of a group.
+        GazeStreamGroup states the tick rule and the contract; group_schedule is the rule on the host."""
+        from .stream import GazeStreamGroup
+        return GazeStreamGroup(self, streams, fps=fps, stride=stride, segment=segment, batch=batch, max_chunk=max_chunk,
+                               pixel_format=pixel_format, matrix=matrix, full_range=full_range, input_rate=input_rate)
+
     @torch.no_grad()
     def _video_params_row(self, H, W):
         """The one row of test-mode spatial parameters a whole video is sampled under: (new h, new w, y0, x0, flip)."""

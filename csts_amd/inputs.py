@@ -716,6 +716,175 @@ def stream_gather(ring: torch.Tensor, slots: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _upload(device, *tables):
+    """Host tables (numpy, any integer types) -> their device copies, by ONE host-to-device copy: the tables are laid out one
+    after the other at 16-byte boundaries of one byte buffer and handed back as views of its device copy."""
+    import numpy as np
+    tables = [np.ascontiguousarray(t) for t in tables]
+    offs, total = [], 0
+    for t in tables:
+        offs.append(total)
+        total += (t.nbytes + 15) // 16 * 16
+    host = np.zeros(max(total, 16), dtype=np.uint8)
+    for t, o in zip(tables, offs):
+        host[o:o + t.nbytes] = t.reshape(-1).view(np.uint8)
+    dev = torch.from_numpy(host).to(device)
+    return [dev[o:o + t.nbytes].view(getattr(torch, t.dtype.name)).reshape(t.shape) for t, o in zip(tables, offs)]
+
+
+def _group_rings(rings, nbins=None):
+    if rings.dtype != torch.float32 or rings.dim() != 3 or not rings.is_contiguous() or (nbins and rings.shape[1] != nbins):
+        raise ValueError(f"the rings must be contiguous fp32 (streams, {nbins or 'nbins'}, ring_cols), got {tuple(rings.shape)} "
+                         f"{rings.dtype}")
+    return rings.shape
+
+
+def group_stft(jobs, rings: torch.Tensor, n_fft: int = STFT_N_FFT, hop: int = STFT_HOP, win: int = STFT_WIN,
+               eps: float = STFT_EPS) -> torch.Tensor:
+    """stream_stft for several streams in ONE launch (csts_group_stft): jobs is a list of (buf, s_base, f0, f1, stream, n_total),
+    each as stream_stft takes them -- buf fp32 (m,) on the device holds the samples [s_base, s_base + m) of that stream's signal,
+    n_total -1 while it goes on -- and rings fp32 (streams, n_fft // 2 + 1, ring_cols) receives column f of stream i at
+    rings[i, :, f % ring_cols], with stream_stft's bits.  A job may have f1 == f0 (it writes nothing); two jobs naming one
+    stream, a stream outside the arena, a column that needs a sample its buffer does not hold or more than ring_cols columns
+    in one job are a ValueError before anything is launched.  The job table goes up in one copy.  Returns the rings."""
+    import numpy as np
+    _gpu(rings)
+    streams, _, ring_cols = _group_rings(rings, n_fft // 2 + 1)
+    jobs = list(jobs)
+    if not jobs:
+        return rings
+    table = np.zeros((len(jobs), 8), dtype=np.int64)
+    keep, seen, total = [], set(), 0
+    for j, (buf, s_base, f0, f1, slot, n_total) in enumerate(jobs):
+        _gpu(buf)
+        if buf.dtype != torch.float32 or buf.dim() != 1:
+            raise ValueError(f"job {j}: buf must be an fp32 (m,) waveform, got {tuple(buf.shape)} {buf.dtype}")
+        buf = buf.contiguous()
+        keep.append(buf)
+        s_base, f0, f1, slot, n_total, m = int(s_base), int(f0), int(f1), int(slot), int(n_total), buf.numel()
+        if not 0 <= slot < streams or slot in seen:
+            raise ValueError(f"job {j}: stream {slot} lies outside [0, {streams}) or is named by two jobs")
+        seen.add(slot)
+        if s_base < 0 or f0 < 0 or f1 < f0 or f1 - f0 > ring_cols:
+            raise ValueError(f"job {j}: columns [{f0}, {f1}) must be at most one turn of the ring ({ring_cols} columns); s_base "
+                             f"{s_base} >= 0")
+        if n_total >= 0 and n_total > s_base + m:
+            raise ValueError(f"job {j}: n_total {n_total} lies past the {s_base + m} samples pushed")
+        first = max(f0 * hop + (n_fft - win) // 2 - n_fft // 2, 0)
+        last = (f1 - 1) * hop + (n_fft - win) // 2 - n_fft // 2 + win
+        if n_total >= 0:
+            last = min(last, n_total)
+        if f1 > f0 and last > first and (first < s_base or last > s_base + m):
+            raise ValueError(f"job {j}: columns [{f0}, {f1}) read the samples [{first}, {last}), the buffer holds "
+                             f"[{s_base}, {s_base + m})")
+        table[j] = (buf.data_ptr() if m else 0, s_base, m, n_total, f0, f1, slot, total)
+        total += f1 - f0
+    if total == 0:
+        return rings
+    (dev,) = _upload(rings.device, table)
+    with torch.cuda.device(rings.device):
+        L.check(L.load().csts_group_stft(dev.data_ptr(), table.ctypes.data, len(jobs), rings.data_ptr(), streams, ring_cols, n_fft,
+                                         hop, win, eps, _s()), "csts_group_stft")
+    return rings
+
+
+def group_audio_windows(rings: torch.Tensor, stream_of, newest, centers, width: int = 256, check: bool = True) -> torch.Tensor:
+    """stream_audio_windows over the spectrum rings of a stream group (csts_group_audio_windows): rings fp32 (streams, nbins,
+    ring_cols); stream_of (B,), newest (streams,) = the last column written of every stream (-1: none) and centers (B, T), GLOBAL
+    centre columns, are HOST tables (anything numpy.asarray takes), which go up in one copy -> (B, 1, T, nbins, width): row b
+    holds the windows of stream stream_of[b], read across that ring's wrap.  check: a row whose stream lies outside the arena, or
+    a window not wholly inside its stream's live span [max(newest - ring_cols + 1, 0), newest], is a ValueError; with check=False
+    it is left to the device, which applies the same test when the kernel runs and gives such a window NaN."""
+    import numpy as np
+    _gpu(rings)
+    streams, nbins, ring_cols = _group_rings(rings)
+    stream_of = np.asarray(stream_of, dtype=np.int32)
+    newest = np.asarray(newest, dtype=np.int64)
+    centers = np.asarray(centers, dtype=np.int64)
+    width = int(width)
+    if centers.ndim != 2 or stream_of.shape != centers.shape[:1] or newest.shape != (streams,):
+        raise ValueError(f"stream_of must be (B,), newest ({streams},) and centers (B, T), got {stream_of.shape}, {newest.shape} and "
+                         f"{centers.shape}")
+    B, T = centers.shape
+    if width < 2 or width % 2 or width > ring_cols or B < 1 or T < 1 or B * T > 65535:
+        raise ValueError(f"bad sizes: width {width} (even, <= ring_cols {ring_cols}), B {B}, T {T} (B * T <= 65535)")
+    if check:
+        if int(stream_of.min()) < 0 or int(stream_of.max()) >= streams:
+            raise ValueError(f"stream_of names a stream outside [0, {streams}): {stream_of.tolist()}")
+        new = newest[stream_of][:, None]
+        bad = (centers - width // 2 < np.maximum(new - ring_cols + 1, 0)) | (centers + width // 2 - 1 > new)
+        if bad.any():
+            b = int(np.argwhere(bad)[0][0])
+            raise ValueError(f"an audio window of row {b} (stream {int(stream_of[b])}) reaches outside the ring's live columns "
+                             f"[{max(int(new[b, 0]) - ring_cols + 1, 0)}, {int(new[b, 0])}] ({ring_cols} columns): centres "
+                             f"{int(centers[b].min())} .. {int(centers[b].max())}, width {width}")
+    d_new, d_cen, d_of = _upload(rings.device, newest, centers, stream_of)
+    out = torch.empty(B, 1, T, nbins, width, dtype=torch.float32, device=rings.device)
+    with torch.cuda.device(rings.device):
+        L.check(L.load().csts_group_audio_windows(rings.data_ptr(), streams, ring_cols, d_of.data_ptr(), d_new.data_ptr(),
+                                                  d_cen.data_ptr(), out.data_ptr(), B, T, nbins, width, _s()),
+                "csts_group_audio_windows")
+    return out
+
+
+def group_ingest(jobs, pairs, arena: torch.Tensor, mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225), *,
+                 pixel_format: str = "rgb24", matrix: str = "bt601", full_range: bool = False) -> torch.Tensor:
+    """stream_ingest for several streams in ONE launch (csts_group_ingest / _yuv): jobs is a list of (chunk, params_row) -- chunk
+    uint8 (K, H, W, 3) on the device, or (K, H * 3 / 2, W) in the one pixel_format of the call, each job of its own size;
+    params_row the five test-mode integers new h, new w, y0, x0, flip of that job, on the HOST -- and pairs a HOST table (P, 3) =
+    (job, frame in chunk, arena slot): arena fp32 (slots, 3, S, S) receives arena[slot] = clip_sample(chunk of the job,
+    [[frame]], params_row[None], S)[0, :, 0], bit for bit.  A chunk frame no pair names is not read and no other slot is
+    written; a pair whose job, frame or slot is out of range writes nothing; the tables go up in one copy and are read by the
+    kernel when it runs.  A chunk that does not start at a 16-byte boundary is copied first, as stream_ingest does.  P == 0
+    launches nothing.  Returns the arena."""
+    import numpy as np
+    layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
+    if arena.dtype != torch.float32 or arena.dim() != 4 or arena.shape[1] != 3 or arena.shape[2] != arena.shape[3] or \
+            not arena.is_contiguous() or arena.data_ptr() % 16:
+        raise ValueError(f"the arena must be contiguous, 16-byte aligned fp32 (slots, 3, S, S), got {tuple(arena.shape)} {arena.dtype}")
+    _gpu(arena)
+    jobs = list(jobs)
+    pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 3)
+    if pairs.shape[0] > 65535 or len(jobs) > 65535:
+        raise ValueError(f"a launch takes at most 65535 jobs and pairs, got {len(jobs)} and {pairs.shape[0]}")
+    if pairs.shape[0] == 0 or not jobs:
+        return arena
+    table = np.zeros((len(jobs), 6), dtype=np.int64)
+    params = np.zeros((len(jobs), 5), dtype=np.int32)
+    keep = []
+    for j, (chunk, row) in enumerate(jobs):
+        _gpu(chunk)
+        if layout:
+            if chunk.dtype != torch.uint8 or chunk.dim() != 3 or chunk.shape[0] < 1:
+                raise ValueError(f"job {j}: {pixel_format} chunk must be uint8 (K >= 1, H * 3 / 2, W), got {tuple(chunk.shape)} "
+                                 f"{chunk.dtype}")
+            K, (H, W) = chunk.shape[0], _yuv_hw(chunk.shape, pixel_format, "chunk")
+            cap = (W + 30 + 15) // 16 * 16
+        else:
+            if chunk.dtype != torch.uint8 or chunk.dim() != 4 or chunk.shape[-1] != 3 or chunk.shape[0] < 1:
+                raise ValueError(f"job {j}: chunk must be uint8 (K >= 1, H, W, 3), got {tuple(chunk.shape)} {chunk.dtype}")
+            K, H, W, _ = chunk.shape
+            cap = (3 * W + 30 + 15) // 16 * 16
+        if W > 6000:
+            raise ValueError(f"job {j}: frames wider than 6000 pixels are not supported, got W {W}")
+        x = chunk.contiguous()
+        if x.data_ptr() % 16:
+            x = x.clone()
+        keep.append(x)
+        table[j] = (x.data_ptr(), x.numel(), K, H, W, cap)
+        params[j] = np.asarray(row, dtype=np.int32).reshape(5)
+    d_jobs, d_params, d_pairs = _upload(arena.device, table, params, pairs)
+    f3 = C.c_float * 3
+    args = (d_jobs.data_ptr(), table.ctypes.data, len(jobs), d_params.data_ptr(), d_pairs.data_ptr(), pairs.shape[0], arena.data_ptr(),
+            arena.shape[0], arena.shape[2], f3(*mean), f3(*std))
+    with torch.cuda.device(arena.device):
+        if layout:
+            L.check(L.load().csts_group_ingest_yuv(*args, layout, mat, fr, _s()), "csts_group_ingest_yuv")
+        else:
+            L.check(L.load().csts_group_ingest(*args, _s()), "csts_group_ingest")
+    return arena
+
+
 def _clip_table(clips, B=None):
     """The clip table {byte offset, N, H, W} as a contiguous int64 (B, 4) tensor; the caller validates its rows."""
     if clips.dtype != torch.int64 or clips.dim() != 2 or clips.shape[1] != 4 or clips.shape[0] < 1 or \

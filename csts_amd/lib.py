@@ -282,6 +282,10 @@ SYMBOLS = {
     "csts_stream_ingest": (_I, [vp, _I, _I, _I, vp, _I, vp, vp, _I, _I, C.c_float * 3, C.c_float * 3, vp]),
     "csts_stream_ingest_yuv": (_I, [vp, _I, _I, _I, vp, _I, vp, vp, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),
     "csts_stream_gather": (_I, [vp, _I, vp, vp, _I, _I, _I, vp]),
+    "csts_group_stft": (_I, [vp, vp, _I, vp, _I, _I, _I, _I, _I, _F, vp]),
+    "csts_group_audio_windows": (_I, [vp, _I, _I, vp, vp, vp, vp, _I, _I, _I, _I, vp]),
+    "csts_group_ingest": (_I, [vp, vp, _I, vp, vp, _I, vp, i64, _I, C.c_float * 3, C.c_float * 3, vp]),
+    "csts_group_ingest_yuv": (_I, [vp, vp, _I, vp, vp, _I, vp, i64, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),
     "csts_live_track_add": (_I, [vp, vp, _I, _I, _I, vp, vp, vp, _I, vp]),
     "csts_live_track_rows": (_I, [vp, vp, vp, _I, i64, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, vp, vp]),
     "csts_adaptive_f1_workspace": (sz, [i64, _I]),

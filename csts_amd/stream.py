@@ -7,7 +7,10 @@ window reads which frames and columns, and when it is ready -- is pure arithmeti
 ``stream_schedule``); the device side is the four kernels of csts_amd/csrc/stream.hip behind inputs.stream_stft,
 inputs.stream_audio_windows, inputs.stream_ingest and inputs.stream_gather.  With ``live=`` a forecast stream also answers
 every pushed frame with its row of a gaze track, out of a third ring (``stream_live_schedule``, ``live_ring_slots``;
-ops.live_track_add and ops.live_track_rows, the last two kernels of stream.hip)."""
+ops.live_track_add and ops.live_track_rows, the live-track kernels of stream.hip).  ``GazeStreamGroup`` serves several
+recordings at once: its slots share one arena of rings, a tick's frames and samples go in with one launch per stage
+(inputs.group_stft, inputs.group_ingest) and the windows of different slots that are ready together share a forward;
+``group_schedule`` states on the host which windows share a batch."""
 from __future__ import annotations
 
 import numbers
@@ -612,3 +615,318 @@ class GazeStream:
             self.dropped += 1
             w += 1
         return results
+
+
+# ---- stream group: N streams on one predictor, their windows batched together -------------------------------------------------------
+
+def _tick_rounds(steps, batch):
+    """The rounds of one tick.  steps: {slot: that slot's stream_steps}.  Round r takes step r of every slot that has one, in slot
+    order; its ready windows over all slots, ordered by (slot, window), are cut into consecutive groups of `batch`.  Returns
+    [({slot: (frames, samples, [windows])}, [[(slot, window), ...], ...])], one pair per round.  The one statement of the tick
+    rule: GazeStreamGroup.push works a tick off by it and group_schedule replays it."""
+    rounds = []
+    for r in range(max((len(s) for s in steps.values()), default=0)):
+        part = {i: steps[i][r] for i in sorted(steps) if r < len(steps[i])}
+        rows = [(i, w) for i, (_, _, ready) in part.items() for w in ready]
+        rounds.append((part, [rows[g:g + batch] for g in range(0, len(rows), batch)]))
+    return rounds
+
+
+def group_schedule(plan, ticks, batch, max_chunk=32, input_rate=None):
+    """The batches a GazeStreamGroup runs, on the host.  ticks: a list of {slot: (frames, samples)} counts, one dict per
+    GazeStreamGroup.push; returns, per tick, the list of its batches, each a list of (slot, window) pairs in the order of the
+    batch's rows (a batch shorter than `batch` is padded by repeating its last row when it runs).
+
+    One tick: every slot's steps are computed by stream_steps on that slot's counters, in slot order, before anything is
+    consumed; a slot that is stuck raises stream_steps' ValueError prefixed with "slot i: " and nothing of the tick counts for
+    any slot.  Then the tick runs in rounds: round r takes step r of every slot that has one -- their samples, then their
+    frames, then the windows that are ready, ordered by (slot, window) and cut into consecutive groups of `batch`.  Batches
+    never mix rounds.  input_rate: the sample counts are at that rate, as stream_schedule takes them."""
+    batch, max_chunk = int(batch), int(max_chunk)
+    if batch < 1 or max_chunk < 1:
+        raise ValueError(f"batch and max_chunk must be positive, got {batch} and {max_chunk}")
+    sizes = ring_sizes(plan, max_chunk, 1)
+    ratio = None
+    if input_rate is not None:
+        from .inputs import check_sample_rate, resample_ready, resample_rule
+        _, up, down, half = resample_rule(check_sample_rate(input_rate, "input_rate"))
+        ratio = None if up == down else (up, down, half)
+    state, out = {}, []                                      # slot -> (frames, 24 kHz samples, next window, source samples)
+    for tick in ticks:
+        steps, after = {}, {}
+        for i in sorted(tick):
+            k, m = (int(v) for v in tick[i])
+            if k < 0 or m < 0:
+                raise ValueError(f"slot {i}: a push holds counts >= 0, got ({k}, {m})")
+            frames, samples, w, source = state.get(i, (0, 0, 0, 0))
+            m24 = m if ratio is None else resample_ready(source + m, *ratio) - resample_ready(source, *ratio)
+            try:
+                steps[i] = stream_steps(plan, sizes["slots"], sizes["ring_cols"], max_chunk, frames, samples, w, k, m24)
+            except ValueError as e:
+                raise ValueError(f"slot {i}: {e}") from None
+            after[i] = (frames + k, samples + m24, w + sum(len(ready) for _, _, ready in steps[i]), source + m)
+        state.update(after)
+        out.append([rows for _, batches in _tick_rounds(steps, batch) for rows in batches])
+    return out
+
+
+class GazeStreamGroup:
+    """Several live streams on one predictor, their windows predicted together (reach it through GazePredictor.stream_group).
+
+    `streams` slots, each one recording: its own source size H x W, fixed by its first push, and its own counters, the lists
+    `frames`, `samples`, `input_samples`, `cols`, `next_window`, `dropped`, `closed`, one entry per slot, as a GazeStream has
+    them; `batches` holds the batches the last push() or close() ran, as group_schedule lists them.  All slots share one plan (plan_stream), one pixel format, matrix and range, and one input_rate.
+
+    push(pieces) is one TICK: pieces is {slot: (frames or None, wav or None)} -- or a list of (slot, frames, wav) with distinct
+    slots -- with frames and samples as GazeStream.push takes them, and the answer is {slot: [window dicts]} for the slots of
+    pieces, each dict a GazeStream result plus "stream": slot.  A tick is worked off by the rule group_schedule states:
+      1. every slot's steps are computed by stream_steps on that slot's counters, in slot order, before anything is consumed
+         (the resampler's check / count included);
+      2. a slot that is stuck, or any input that is invalid (wrong device, wrong shape, H x W differing from the slot's, a closed
+         slot) raises the ValueError / CstsError GazeStream raises, prefixed with "slot i: ", and nothing of the tick is consumed
+         for any slot;
+      3. the tick runs in rounds; round r takes step r of every slot that has one: all their samples go in with ONE STFT launch
+         (inputs.group_stft), then all their frames with ONE ingest launch (inputs.group_ingest), then the ready windows of the
+         round over all slots, ordered by (slot, window), are cut into consecutive groups of `batch`, the last one padded by
+         repeating its last row; each group is one predict_batch call, so one graph shape serves the group;
+      4. a round's windows run before the next round's ingest, so no slot or column is overwritten before its last reader has
+         run: GazeStream's argument, per slot.
+
+    Device memory is two arenas, allocated once, when the group is made (a GazeStream allocates its spectrum ring on the first
+    audio; here both are there from the start): crops fp32 (streams, R, 3, S, S) and spectrum fp32 (streams, 256, ring_cols),
+    R and ring_cols from ring_sizes(plan, max_chunk, S), so a slot's ring is exactly a GazeStream's.  `capacity` holds the
+    per-slot numbers, "streams" and "total_bytes".
+
+    close(slot) ends one slot as GazeStream.close(wav_pad=True) does -- the resampler is flushed, the padded last column computed,
+    the windows that completes run, the begun-but-incomplete ones counted in dropped[slot]; close() does so for every open slot and
+    batches the last windows of all of them together in (slot, window) order.  Both return {slot: [window dicts]}.  reset(slot)
+    reopens a closed slot as a fresh stream: counters zero, H x W free again, a fresh resampler.  It writes nothing to the
+    rings: an audio window is NaN unless it lies inside the columns the slot's new counters have written, and a window runs only
+    after every frame it reads has been ingested over what the slots held.
+
+    The contract: every emitted window equals, bit for bit, its row of predict_batch on the batch group_schedule names, each row
+    of which is built from that slot's own whole recording by clip_sample at stream_window's frames and audio_windows_at on
+    stft_logpower of its whole waveform (with input_rate: of resample_audio of the whole waveform).  A group of one slot equals
+    a GazeStream with the same batch, bit for bit.  Nothing is claimed about a row's bits when its batch neighbours change.
+
+    Out of scope, and not accepted as keywords: live=, overlay= (the live track of GazeStream) and attention maps; different
+    plans per slot; equality with predict_video."""
+
+    def __init__(self, predictor, streams, fps=None, stride=None, segment=None, batch=4, max_chunk=32, pixel_format="rgb24",
+                 matrix="bt601", full_range=False, input_rate=None):
+        import torch
+        from . import inputs
+        self.streams, self.batch, self.max_chunk = int(streams), int(batch), int(max_chunk)
+        if self.streams < 1 or self.batch < 1 or self.max_chunk < 1:
+            raise ValueError(f"streams, batch and max_chunk must be positive, got {streams}, {batch} and {max_chunk}")
+        self.input_rate = None if input_rate is None else inputs.check_sample_rate(input_rate, "input_rate")
+        self.fmt = {}
+        if inputs.check_pixel_format(pixel_format, matrix, full_range)[0]:
+            self.fmt = {"pixel_format": pixel_format, "matrix": matrix, "full_range": bool(full_range)}
+        self.predictor = predictor
+        cfg = predictor.cfg
+        self.plan = plan_stream(cfg, fps=fps, stride=stride, segment=segment)
+        self.S, self.T = int(cfg.DATA.TEST_CROP_SIZE), int(cfg.DATA.NUM_FRAMES)
+        self.mean, self.std = tuple(cfg.DATA.MEAN), tuple(cfg.DATA.STD)
+        sizes = ring_sizes(self.plan, self.max_chunk, self.S)
+        self.R, self.ring_cols = sizes["slots"], sizes["ring_cols"]
+        self.capacity = dict(sizes, streams=self.streams, total_bytes=self.streams * (sizes["crop_bytes"] + sizes["spec_bytes"]))
+        n = self.streams
+        self.frames, self.samples, self.input_samples, self.cols = [0] * n, [0] * n, [0] * n, [0] * n
+        self.next_window, self.dropped, self.closed, self.hw = [0] * n, [0] * n, [False] * n, [None] * n
+        self._rows, self._tail, self._tail_base = [None] * n, [None] * n, [0] * n
+        self._resamplers = [None if input_rate is None else inputs.StreamResampler(self.input_rate) for _ in range(n)]
+        self.batches = []                                    # the batches the last push() / close() ran: [[(slot, window), ...]]
+        self._crops = torch.zeros(n, self.R, 3, self.S, self.S, dtype=torch.float32, device=predictor.device)
+        self._spec = torch.zeros(n, STFT_N_FFT // 2 + 1, self.ring_cols, dtype=torch.float32, device=predictor.device)
+
+    # ---- host arithmetic -------------------------------------------------------------------------------------------------------
+    def _slot(self, slot):
+        if isinstance(slot, bool) or not isinstance(slot, numbers.Integral) or not 0 <= int(slot) < self.streams:
+            raise ValueError(f"a slot is an integer in [0, {self.streams}), got {slot!r}")
+        return int(slot)
+
+    def _plan_slot(self, i, frames, wav):
+        """What GazeStream._push checks and counts before it consumes anything, on slot i: (k, (H, W), m_in, m, steps)."""
+        import torch
+        from . import lib as L
+        from .infer import _picture_hw
+        if self.closed[i]:
+            raise ValueError("the stream is closed: push() after close()")
+        for t in (frames, wav):
+            if t is not None and (not torch.is_tensor(t) or not t.is_cuda):
+                raise L.CstsError("GazeStreamGroup runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
+        k = m = m_in = 0
+        hw = self.hw[i]
+        if frames is not None:
+            H, W, _ = _picture_hw(frames, 1, self.fmt.get("pixel_format", "rgb24"), self.fmt.get("matrix", "bt601"),
+                                  self.fmt.get("full_range", False))
+            if hw is not None and (H, W) != hw:
+                raise ValueError(f"the stream's frames are {hw[0]} x {hw[1]} (fixed by the first push), got {H} x {W}")
+            k, hw = frames.shape[0], (H, W)
+        if wav is not None and self._resamplers[i] is not None:
+            m_in = self._resamplers[i].check(wav)
+            m = self._resamplers[i].count(m_in, wav)
+        elif wav is not None:
+            if wav.dim() != 1 or wav.dtype != torch.float32:
+                raise ValueError(f"wav must be an fp32 (m,) waveform at {AUDIO_RATE} Hz, got {tuple(wav.shape)} {wav.dtype}")
+            m_in = m = wav.numel()
+        steps = stream_steps(self.plan, self.R, self.ring_cols, self.max_chunk, self.frames[i], self.samples[i],
+                             self.next_window[i], k, m)
+        return k, hw, m_in, m, steps
+
+    # ---- device work -----------------------------------------------------------------------------------------------------------
+    def _audio(self, jobs):
+        """jobs: [(slot, the next samples of that slot, n_total)], distinct slots: the columns they complete, in one launch."""
+        import torch
+        from . import inputs
+        pending = []
+        for i, piece, n_total in jobs:
+            buf = piece if self._tail[i] is None else torch.cat([self._tail[i], piece])
+            self.samples[i] += piece.numel()
+            cols = self.samples[i] // STFT_HOP               # column f is final once sample 120 f + 119 is in
+            if n_total >= 0:                                 # the signal ended: the columns of the offline STFT
+                cols = max(cols, 1 + (self.samples[i] + 2 * (STFT_N_FFT // 2) - STFT_N_FFT) // STFT_HOP)
+            pending.append([buf.contiguous(), self._tail_base[i], self.cols[i], cols, i, n_total])
+            self.cols[i] = max(self.cols[i], cols)
+            keep = max(0, STFT_HOP * self.cols[i] + (STFT_N_FFT - STFT_WIN) // 2 - STFT_N_FFT // 2)
+            keep = max(keep, self._tail_base[i])
+            self._tail[i] = buf[keep - self._tail_base[i]:].clone()
+            self._tail_base[i] = keep
+        while any(p[2] < p[3] for p in pending):             # at most one turn of a ring per launch
+            turn = [(buf, base, f0, min(f0 + self.ring_cols, f1), i, n_total) for buf, base, f0, f1, i, n_total in pending if f0 < f1]
+            inputs.group_stft(turn, self._spec)
+            for p in pending:
+                p[2] = min(p[2] + self.ring_cols, p[3])
+
+    def _ingest(self, jobs):
+        """jobs: [(slot, the next frames of that slot)]: the frames of them some window reads, sampled in one launch."""
+        from . import inputs
+        table, pairs = [], []
+        for i, chunk in jobs:
+            a = self.frames[i]
+            used = used_frames(self.plan, a, a + chunk.shape[0])
+            if used:
+                pairs += [(len(table), f - a, i * self.R + f % self.R) for f in used]
+                table.append((chunk, self._rows[i]))
+            self.frames[i] += chunk.shape[0]
+        if pairs:
+            inputs.group_ingest(table, pairs, self._crops.view(-1, 3, self.S, self.S), mean=self.mean, std=self.std, **self.fmt)
+
+    def _run(self, rows):
+        """One batch: rows [(slot, window)], at most `batch` of them, padded by repeating the last."""
+        import numpy as np
+        import torch
+        from . import inputs
+        S = self.S
+        self.batches.append(list(rows))
+        group = [(i, stream_window(self.plan, w)) for i, w in rows]
+        padded = group + [group[-1]] * (self.batch - len(group))
+        slots = np.stack([i * self.R + r["frames_idx"] % self.R for i, r in padded]).astype(np.int32)
+        centers = np.stack([r["audio_centers"] for _, r in padded]).astype(np.int64)
+        video = inputs.stream_gather(self._crops.view(-1, 3, S, S), torch.from_numpy(slots).to(self._crops.device))
+        audio = inputs.group_audio_windows(self._spec, [i for i, _ in padded], [c - 1 for c in self.cols], centers, AUDIO_WIDTH)
+        if S != AUDIO_WIDTH:   # S frequency bins x S columns around each frame, as predict_video cuts them
+            o = (AUDIO_WIDTH - S) // 2
+            audio = audio[:, :, :, :S, o:o + S].contiguous()
+        out = self.predictor.predict_batch({"video": video, "audio": audio})
+        results = []
+        for b, (i, r) in enumerate(group):
+            results.append({"stream": i, "window": r["window"], "frames_idx": r["frames_idx"], "target_idx": r["target_idx"],
+                            "points": out["points"][b], "peak": out["peak"][b], "heatmaps": out["heatmaps"][b],
+                            "rescaled": out["rescaled"][b]})
+            self.next_window[i] = r["window"] + 1
+        return results
+
+    # ---- the interface ---------------------------------------------------------------------------------------------------------
+    def push(self, pieces):
+        """One tick: {slot: (frames or None, wav or None)}, or a list of (slot, frames, wav) with distinct slots -> {slot: [the
+        windows this tick completes for that slot, in order]} for the slots of pieces."""
+        import torch
+        from . import lib as L
+        items = [(i, *v) for i, v in pieces.items()] if isinstance(pieces, dict) else [tuple(p) for p in pieces]
+        if any(len(p) != 3 for p in items):
+            raise ValueError("a piece is (frames or None, wav or None) under its slot, or (slot, frames, wav) in a list")
+        items = sorted(((self._slot(i), frames, wav) for i, frames, wav in items), key=lambda p: p[0])
+        if len({p[0] for p in items}) != len(items):
+            raise ValueError(f"a tick names every slot at most once, got {[p[0] for p in items]}")
+        planned = {}
+        for i, frames, wav in items:                         # everything that can refuse the tick, before anything is consumed
+            try:
+                planned[i] = self._plan_slot(i, frames, wav)
+            except L.CstsError as e:
+                raise L.CstsError(f"slot {i}: {e}") from None
+            except ValueError as e:
+                raise ValueError(f"slot {i}: {e}") from None
+        self.batches = []
+        out = {i: [] for i, _, _ in items}
+        given = {i: [frames, wav] for i, frames, wav in items}
+        fa, sa = dict.fromkeys(out, 0), dict.fromkeys(out, 0)
+        with torch.no_grad(), torch.cuda.device(self.predictor.device):
+            for i, (k, hw, m_in, _, _) in planned.items():
+                if k and self.hw[i] is None:
+                    self.hw[i], self._rows[i] = hw, self.predictor._video_params_row(*hw)
+                if given[i][1] is not None:
+                    self.input_samples[i] += m_in
+                    if self._resamplers[i] is not None:      # the whole piece once; the rounds slice the 24 kHz samples
+                        given[i][1] = self._resamplers[i].push(given[i][1])
+            for part, batches in _tick_rounds({i: p[4] for i, p in planned.items()}, self.batch):
+                self._audio([(i, given[i][1][sa[i]:sa[i] + dm], -1) for i, (_, dm, _) in part.items() if dm])
+                self._ingest([(i, given[i][0][fa[i]:fa[i] + dk]) for i, (dk, _, _) in part.items() if dk])
+                for i, (dk, dm, _) in part.items():
+                    fa[i], sa[i] = fa[i] + dk, sa[i] + dm
+                for rows in batches:
+                    for r in self._run(rows):
+                        out[r["stream"]].append(r)
+        return out
+
+    def close(self, slot=None):
+        """End slot `slot`, or with None every slot that is still open -> {slot: [the windows the padded last column completes]}.
+        The closing windows of all the slots are batched together, ordered by (slot, window)."""
+        import torch
+        slots = [i for i in range(self.streams) if not self.closed[i]] if slot is None else [self._slot(slot)]
+        if slot is not None and self.closed[slots[0]]:
+            raise ValueError(f"slot {slots[0]}: the stream is closed already")
+        self.batches = []
+        out = {i: [] for i in slots}
+        with torch.no_grad(), torch.cuda.device(self.predictor.device):
+            flush = []
+            for i in slots:
+                self.closed[i] = True
+                if self._resamplers[i] is not None:          # the outputs held back; as many of them as the spectrum ring takes
+                    rest = self._resamplers[i].close()
+                    limit = ring_limits(stream_window(self.plan, self.next_window[i]), self.R, self.ring_cols)[1]
+                    rest = rest[:max(0, min(rest.numel(), limit - self.samples[i]))]
+                    if rest.numel():
+                        flush.append((i, rest, -1))
+            self._audio(flush)
+            self._audio([(i, self._tail[i][:0], self.samples[i]) for i in slots if self._tail[i] is not None])
+            rows = []
+            for i in slots:
+                w = self.next_window[i]
+                nxt = stream_window(self.plan, w)
+                while self.hw[i] is not None and nxt["ready_frames"] <= self.frames[i] and \
+                        int(nxt["audio_centers"].max()) + HALF_WIDTH <= self.cols[i]:
+                    rows.append((i, w))
+                    w += 1
+                    nxt = stream_window(self.plan, w)
+            for g in range(0, len(rows), self.batch):
+                for r in self._run(rows[g:g + self.batch]):
+                    out[r["stream"]].append(r)
+        for i in slots:
+            w = self.next_window[i]
+            while int(stream_window(self.plan, w)["frames_idx"][0]) < self.frames[i]:
+                self.dropped[i] += 1
+                w += 1
+        return out
+
+    def reset(self, slot):
+        """Reopen the closed slot `slot` as a fresh stream.  Nothing is written to the rings."""
+        from . import inputs
+        i = self._slot(slot)
+        if not self.closed[i]:
+            raise ValueError(f"slot {i}: reset() reopens a closed slot; close({i}) first")
+        self.frames[i] = self.samples[i] = self.input_samples[i] = self.cols[i] = self.next_window[i] = self.dropped[i] = 0
+        self.closed[i], self.hw[i], self._rows[i], self._tail[i], self._tail_base[i] = False, None, None, None, 0
+        if self.input_rate is not None:
+            self._resamplers[i] = inputs.StreamResampler(self.input_rate)

@@ -892,6 +892,45 @@ int csts_stream_ingest_yuv(const uint8_t* chunk_yuv, int K, int H, int W, const 
                            hipStream_t stream);
 int csts_stream_gather(const float* ring, int R, const int* slots, float* out, int B, int T, int S, hipStream_t stream);
 
+/* ---- stream group (csts_amd/csrc/stream.hip, csts_amd.GazeStreamGroup): N streams share one arena of crop rings, fp32
+ *      (streams * R, 3, S, S) -- ring slot r of stream i is arena slot i * R + r -- and one of spectrum rings, fp32
+ *      (streams, n_fft / 2 + 1, ring_cols); what several streams pushed in one tick goes in with ONE launch per stage, from a job
+ *      table.  Every table is DEVICE memory read when the kernel runs (a workgroup finds its job from its block index alone, so
+ *      the reads are uniform); no atomics, no allocation, no synchronisation, no host read of device memory.  jobs_host is the
+ *      HOST copy of the same job table: the entry validates it and sizes the launch from it before anything is launched.  The
+ *      arithmetic is the single-stream kernels' (one device function each): a column, a crop, a window has the bits it has there.
+ *      group_stft: jobs int64 [njobs][8] = {address of the job's fp32 sample buffer, s_base, m, n_total, f0, f1, stream, first
+ *        workgroup of the job = the number of columns of the jobs before it}, each as csts_stream_stft takes them; column f of
+ *        stream i goes to rings[i][bin][f mod ring_cols].  The grid is the total column count.  Refused (-1) before launch: a
+ *        column that needs a sample outside its job's buffer, f1 - f0 > ring_cols, n_total > s_base + m, a stream outside
+ *        [0, streams), two jobs naming one stream, a first workgroup that is not the running column count.  A job with f1 == f0
+ *        is legal and writes nothing; a table of such jobs launches nothing.  1 <= njobs <= 65535.
+ *      group_audio_windows: csts_stream_audio_windows with the ring looked up per batch row: rings (streams, nbins, ring_cols),
+ *        stream_of int32 [B], newest int64 [streams] = the last column written of every stream (-1: none), centers int64 [B][T] ->
+ *        out (B, 1, T, nbins, width).  Row b reads the ring of stream_of[b] under that stream's live span
+ *        [max(newest - ring_cols + 1, 0), newest]; a window outside it, or a stream_of outside [0, streams), is NaN and reads
+ *        nothing.  width even and <= ring_cols, B * T <= 65535.
+ *      group_ingest / group_ingest_yuv: jobs int64 [njobs][6] = {chunk address, chunk bytes, K, H, W, LDS row capacity for that
+ *        W}: the chunks several streams pushed, each uint8 (K, H, W, 3) -- or (K, H * 3 / 2, W) in a 4:2:0 layout, the same
+ *        layout, matrix and range for all -- of its own size; the row capacity is (3 W + 30) rounded up to 16 (for 4:2:0 the luma
+ *        one, (W + 30) rounded up to 16).  params int32 [njobs][5]: the parameter row of each job.  pairs int32 [npairs][3] =
+ *        (job, frame in chunk, arena slot): that frame is sampled into arena[slot] by the pixel rule of csts_stream_ingest under
+ *        the job's row.  The grid is (ceil(S / 4), npairs), the dynamic LDS that of the widest job (144 KB at W = 6000).  A pair
+ *        whose job, frame or arena slot is out of range writes nothing; bad params give a NaN slot; no byte at or past a job's
+ *        chunk end is read.  Refused (-1) before launch, per job: a chunk that is null or not 16-byte aligned, W > 6000, chunk
+ *        bytes that are not K frames, a row capacity that is not the one W asks for, odd H or W in a 4:2:0 layout.
+ *        1 <= njobs, npairs <= 65535, the arena 16-byte aligned.
+ *      The clip gather of a group is csts_stream_gather on the arena, R = streams * R, with arena slots. */
+int csts_group_stft(const int64_t* jobs, const int64_t* jobs_host, int njobs, float* rings, int streams, int ring_cols, int n_fft,
+                    int hop, int win, float eps, hipStream_t stream);
+int csts_group_audio_windows(const float* rings, int streams, int ring_cols, const int* stream_of, const int64_t* newest,
+                             const int64_t* centers, float* out, int B, int T, int nbins, int width, hipStream_t stream);
+int csts_group_ingest(const int64_t* jobs, const int64_t* jobs_host, int njobs, const int* params, const int* pairs, int npairs,
+                      float* arena, int64_t arena_slots, int S, const float mean[3], const float std[3], hipStream_t stream);
+int csts_group_ingest_yuv(const int64_t* jobs, const int64_t* jobs_host, int njobs, const int* params, const int* pairs, int npairs,
+                          float* arena, int64_t arena_slots, int S, const float mean[3], const float std[3], int layout, int matrix,
+                          int full_range, hipStream_t stream);
+
 /* ---- live gaze track (csts_amd/csrc/stream.hip, GazeStream(live=...)): a forecast window predicts frames the camera has not
  *      delivered yet, so the track row of a frame can be had the moment the frame arrives.  The track lives in a ring of Rt slots
  *      whose size does not depend on the length of the stream: sum fp32 [Rt][H * W], count int32 [Rt], frame int64 [Rt] = the

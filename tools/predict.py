@@ -56,6 +56,14 @@ at that rate, int16 and (C, n) as stored -- the samples up to frame_end * rate /
 filter state carried from push to push (GazePredictor.stream(input_rate=rate)); --out records sample_rate and audio_rate as the
 offline path does.  --fps must then be integral (a stream places its audio by the exact ratio of columns to frames); --overlay,
 --fill and the attention flags are not part of the stream.
+--videos A.npz B.npz ... --stream [--chunk K] [--batch B]: the recordings are replayed as the slots of ONE csts_amd.GazeStreamGroup
+(GazePredictor.stream_group(len(videos), batch=B)): every tick pushes the next K frames of every recording that still has some,
+with the samples that belong to them, cut exactly as --video --stream cuts one recording; a recording that ends is closed.  The
+windows of different recordings that become ready in the same tick are predicted together, B per forward.  The recordings share
+one plan: the same fps, sample rate and pixel format.  --out OUT names one file per recording, OUT with _<slot> before its
+extension, each with the entries --video --stream writes plus stream_slot and stream_batches int64 (batches, B, 2): the (slot,
+window) rows of every batch this slot took part in, rows a short batch lacks as (-1, -1); one json_stats line per recording.
+--videos without --stream, or with --live, --overlay or the attention flags, is refused.
 --live {hold,linear} (with --stream, forecast configurations): every pushed frame is answered with its row of the live gaze track
 (GazeStream.push_live: the forecast shown on the frame it was made for, when that frame arrives, from the windows that had run by
 then; the frames between two predictions at most --max-gap apart, default csts_amd.default_max_gap of the plan, hold the earlier
@@ -87,6 +95,8 @@ def parse_args(argv=None):
     p.add_argument("--checkpoint", default=None, type=str, help=".pyth file (default: TEST.CHECKPOINT_FILE_PATH)")
     p.add_argument("--clip", default=None, type=str, help=".npz with " + ", ".join(CLIP_KEYS))
     p.add_argument("--video", default=None, type=str, help=".npz with " + ", ".join(VIDEO_KEYS) + " [, fps]: a whole recording")
+    p.add_argument("--videos", default=None, nargs="+", type=str, metavar="NPZ",
+                   help="with --stream: several recordings replayed as the slots of one stream group (--batch windows per forward)")
     p.add_argument("--stride", default=None, type=int, help="frames between windows of --video (default: csts_amd.plan_video's)")
     p.add_argument("--fps", default=None, type=float, help="frame rate of --video (default: its fps entry, else DATA.TARGET_FPS)")
     p.add_argument("--overlay", action="store_true", help="with --video: add points_source and the rendered overlay to --out")
@@ -113,13 +123,26 @@ def parse_args(argv=None):
     p.add_argument("--live", default=None, choices=["hold", "linear"],
                    help="with --stream: answer every pushed frame with its row of the live gaze track (honours --max-gap, --overlay)")
     p.add_argument("--seed", default=2000, type=int, help="seed of the synthetic batch used without --clip")
-    p.add_argument("--batch", default=2, type=int, help="clips in the synthetic batch used without --clip")
+    p.add_argument("--batch", default=2, type=int,
+                   help="clips in the synthetic batch used without --clip; with --videos: windows per forward of the stream group")
     p.add_argument("--no-graph", action="store_true", help="launch the kernels eagerly instead of replaying a HIP graph")
     p.add_argument("--out", required=True, type=str, help=".npz to write")
     p.add_argument("opts", default=None, nargs=argparse.REMAINDER, help="KEY VALUE overrides")
     args = p.parse_args(argv)
     if args.video is not None and args.clip is not None:
         p.error("--video and --clip exclude each other: a whole recording or one clip")
+    if args.videos is not None:
+        if args.video is not None or args.clip is not None:
+            p.error("--videos, --video and --clip exclude each other: several recordings, a whole recording or one clip")
+        if not args.stream:
+            p.error("--videos replays several recordings as the slots of one stream group: it needs --stream (predict one "
+                    "recording offline with --video)")
+        if args.live is not None or args.overlay or args.overlay_dir or args.attention or args.attention_dir or \
+                args.attention_track or args.attention_overlay is not None or args.fill is not None:
+            p.error("--videos serves the windows of several recordings together: --live, --overlay, --fill and the attention flags "
+                    "are not part of a stream group (use --video --stream for one recording)")
+        if args.batch < 1:
+            p.error("--batch must be positive")
     if (args.overlay or args.overlay_dir) and args.video is None:
         p.error("--overlay and --overlay-dir draw onto a recording: they need --video")
     if (args.attention or args.attention_dir) and args.video is not None:
@@ -143,7 +166,7 @@ def parse_args(argv=None):
         p.error("--max-gap must be positive")
     if args.overlay_every < 1:
         p.error("--overlay-every must be positive")
-    if args.stream and args.video is None:
+    if args.stream and args.video is None and args.videos is None:
         p.error("--stream replays a recording as a live stream: it needs --video")
     if args.chunk is not None and not args.stream:
         p.error("--chunk is the push size of --stream")
@@ -158,9 +181,10 @@ def parse_args(argv=None):
                 "track, with --overlay onto the frames as they arrive)")
     if args.sample_rate is not None and args.sample_rate < 1:
         p.error("--sample-rate must be positive")
-    if (args.pixel_format or args.yuv_matrix or args.yuv_full_range is not None) and args.video is None and args.clip is None:
+    if (args.pixel_format or args.yuv_matrix or args.yuv_full_range is not None) and args.video is None and args.clip is None \
+            and args.videos is None:
         p.error("--pixel-format, --yuv-matrix and --yuv-full-range describe recorded pictures: they need --clip or --video")
-    if args.sample_rate is not None and args.video is None and args.clip is None:
+    if args.sample_rate is not None and args.video is None and args.clip is None and args.videos is None:
         p.error("--sample-rate is the rate of a recorded waveform: it needs --clip or --video")
     return args
 
@@ -231,6 +255,93 @@ def replay_stream(predictor, frames, wav, fps, stride, chunk, fmt, rate=None, li
     return track, [r["window"] for r in results], stream.dropped
 
 
+def replay_group(predictor, recordings, fps, stride, chunk, batch, fmt, rate=None):
+    """The recordings [(frames, wav)] replayed as the slots of one GazePredictor.stream_group: every tick pushes the next `chunk`
+    frames of every recording that still has some with the matching audio (replay_stream's cut), and a recording that ends is
+    closed -> per slot (the track by track_from_windows, the window numbers in emission order, the dropped count, the batches the
+    slot took part in as lists of (slot, window) rows)."""
+    from fractions import Fraction
+    from csts_amd import track_from_windows
+    group = predictor.stream_group(len(recordings), fps=fps, stride=stride, batch=batch, input_rate=rate, **fmt)
+    per = Fraction(AUDIO_RATE if rate is None else rate) / group.plan["fps"]      # samples per frame
+    results, sent, batches = [[] for _ in recordings], [0] * len(recordings), []
+    for a in range(0, max(frames.shape[0] for frames, _ in recordings), chunk):
+        pieces, ending = {}, []
+        for i, (frames, wav) in enumerate(recordings):
+            N, n = frames.shape[0], wav.shape[-1]
+            if a >= N:
+                continue
+            b = min(a + chunk, N)
+            upto = n if b == N else min(n, int(b * per))
+            pieces[i] = (frames[a:b], wav[..., sent[i]:upto] if upto > sent[i] else None)
+            sent[i] = max(sent[i], upto)
+            if b == N:
+                ending.append(i)
+        done = [group.push(pieces)]
+        batches += group.batches
+        for i in ending:
+            done.append(group.close(i))
+            batches += group.batches
+        for res in done:
+            for i, rs in res.items():
+                results[i] += rs
+    out = []
+    for i, (frames, wav) in enumerate(recordings):
+        if not results[i]:
+            raise SystemExit(f"recording {i} of {frames.shape[0]} frames and {wav.shape[-1]} samples completed no window (one "
+                             f"window observes {group.plan['observed']} frames)")
+        out.append((track_from_windows(results[i], frames.shape[0]), [r["window"] for r in results[i]], group.dropped[i],
+                    [rows for rows in batches if any(slot == i for slot, _ in rows)]))
+    return out
+
+
+def predict_group(args, predictor, dev):
+    """--videos: load the recordings, replay them through one stream group, write one file per recording."""
+    recordings, shared = [], None
+    for path in args.videos:
+        if not os.path.exists(path):
+            raise SystemExit(f"{path}: no such file")
+        with np.load(path) as z:
+            missing = [k for k in VIDEO_KEYS if k not in z.files and (k != "frames_u8" or "frames_yuv" not in z.files)]
+            if missing:
+                raise SystemExit(f"{path} lacks {missing}: a video holds {list(VIDEO_KEYS)} and optionally fps")
+            pics, fmt = pictures(z, args, path, lead=1)
+            fps = args.fps if args.fps is not None else (float(z["fps"]) if "fps" in z.files else None)
+            rate = source_rate(z, args, path)
+            if shared is None:
+                shared = (fps, rate, fmt)
+            elif shared != (fps, rate, fmt):
+                raise SystemExit(f"{path}: the slots of a stream group share one plan: fps, sample rate and pixel format "
+                                 f"{(fps, rate, fmt)} differ from {args.videos[0]}'s {shared}")
+            recordings.append((torch.from_numpy(pics).to(dev), waveform(z, rate, dev)))
+    fps, rate, fmt = shared
+    chunk = 8 if args.chunk is None else args.chunk
+    try:
+        done = replay_group(predictor, recordings, fps, args.stride, chunk, args.batch, fmt, rate)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    stem, ext = os.path.splitext(args.out)
+    rates = {} if rate is None else {"sample_rate": np.int64(rate), "audio_rate": np.int64(AUDIO_RATE)}
+    for i, (track, windows, dropped, batches) in enumerate(done):
+        arrays = {k: track[k].cpu().numpy() for k in ("points", "peak", "count", "rescaled", "heatmaps")}
+        rows = np.full((len(batches), args.batch, 2), -1, dtype=np.int64)
+        for j, batch in enumerate(batches):
+            rows[j, :len(batch)] = batch
+        arrays.update(stream_windows=np.asarray(windows, dtype=np.int64), stream_dropped=np.int64(dropped), stream_slot=np.int64(i),
+                      stream_batches=rows)
+        out = f"{stem}_{i}{ext}"
+        np.savez(out, **arrays, **rates)
+        record = {"_type": "predict_video", "checkpoint": predictor.checkpoint_path, "source": args.videos[i],
+                  "graph": predictor.graph, "out": out, "windows": track["windows"], "frames": int(arrays["count"].shape[0]),
+                  "covered_frames": int((arrays["count"] > 0).sum()), "shapes": {k: list(v.shape) for k, v in arrays.items()},
+                  "stream": True, "chunk": chunk, "dropped": int(dropped), "stream_slot": i, "streams": len(done),
+                  "batch": args.batch, "batches": len(batches)}
+        record.update({k: int(v) for k, v in rates.items()})
+        if fmt:
+            record["pixel_format"] = fmt["pixel_format"]
+        print("json_stats: " + json.dumps(record), flush=True)
+
+
 def write_pngs(overlay, directory, every):
     try:
         from PIL import Image
@@ -276,6 +387,9 @@ def main(argv=None):
     dev = torch.device("cuda", torch.cuda.current_device())
     torch.manual_seed(cfg.RNG_SEED)
     predictor = GazePredictor(cfg, args.checkpoint, device=dev, graph=not args.no_graph)
+    if args.videos is not None:
+        predict_group(args, predictor, dev)
+        return
     if args.video is not None:
         attention_track = bool(args.attention_track or args.attention_overlay is not None)
         with np.load(args.video) as z:
