@@ -13,6 +13,10 @@
 //   group_stft, group_audio_windows, group_ingest(_yuv) : stream_stft, stream_audio_windows and stream_ingest(_yuv) for the
 //                          streams of a GazeStreamGroup, which share one arena of rings: one launch takes what several streams
 //                          pushed, from a job table; the column, the window and the crop are computed by the same device functions.
+//   group_live_add, group_live_rows : live_track_add and live_track_rows for the slots of a GazeLiveGroup, whose track rings share
+//                          one arena: one launch folds the windows of all slots, one answers the frames of all slots, from a
+//                          (stream, target) and a (stream, frame) table; the slot and the row are live_add_slot and live_row, the
+//                          device functions the single-stream kernels run.
 // Every table is DEVICE memory read when the kernel runs; no atomics, no allocation, no synchronisation.
 #include <vector>
 
@@ -122,30 +126,33 @@ __global__ __launch_bounds__(256) void stream_gather_kernel(const float* __restr
 // later launch on the same stream: plain loads and stores, no atomics.  Inside that workgroup every lane reads the slot's tag and
 // count before a workgroup barrier and lane 0 writes them after it; a lane reads and writes only its own cells of the sum.
 
-// grid (Rt), 256 threads.  Workgroup s walks target[0 .. P) in ascending p (uniform loads) and takes the rows whose target
-// t >= 0 has t mod Rt == s:  tag != t -> the slot restarts (sum = 0 + row, count = 1, tag = t);  tag == t -> sum += row, count += 1.
-// The walk is done twice: once on the tags alone, which finds the slot's last restart (`start`, -1: none: the sum in the ring is
-// carried on), its final tag and count; then per 4-cell chunk over the rows from there on, so that a cell is read once per row
-// that counts and written once.  The additions of one cell are ((0 + row_0) + row_1) + ..., in window order across calls and in
-// ascending p inside one: the order of csts_gaze_track.  A slot no row names is not touched.
-template <bool VEC>
-__global__ __launch_bounds__(256) void live_track_add_kernel(const float* __restrict__ maps, const int64_t* __restrict__ target, int P,
-                                                             int hw, float* __restrict__ sum, int* __restrict__ count,
-                                                             int64_t* __restrict__ tag, int Rt) {
-  const int slot = blockIdx.x, tid = threadIdx.x;
-  int64_t cur = tag[slot];
-  int cnt = count[slot], start = -1, hits = 0;
+// One track slot (`slot` of a ring of Rt; dst its sum, cnt_at and tag_at its count and tag) takes the rows of maps [P][hw] that
+// target it.  row_target(p) is the frame row p predicts, or a negative number when the row is not for this ring; it must depend
+// on p and device tables alone, so that every read of it is uniform over the workgroup.  The rows are walked in ascending p and
+// those whose target t >= 0 has t mod Rt == slot are taken:  tag != t -> the slot restarts (sum = 0 + row, count = 1, tag = t);
+// tag == t -> sum += row, count += 1.  The walk is done twice: once on the tags alone, which finds the slot's last restart
+// (`start`, -1: none: the sum in the ring is carried on), its final tag and count; then per 4-cell chunk over the rows from there
+// on, so that a cell is read once per row that counts and written once.  The additions of one cell are ((0 + row_0) + row_1) +
+// ..., in window order across calls and in ascending p inside one: the order of csts_gaze_track.  A slot no row names is not
+// touched.  The one statement of the rule: live_track_add_kernel and group_live_add_kernel both run it, so a track slot has the
+// bits it has in a single stream.
+template <bool VEC, class RowTarget>
+__device__ __forceinline__ void live_add_slot(const float* __restrict__ maps, int P, int hw, float* __restrict__ dst,
+                                              int* __restrict__ cnt_at, int64_t* __restrict__ tag_at, int slot, int Rt,
+                                              RowTarget row_target) {
+  const int tid = threadIdx.x;
+  int64_t cur = *tag_at;
+  int cnt = *cnt_at, start = -1, hits = 0;
   for (int p = 0; p < P; ++p) {
-    const int64_t t = target[p];
+    const int64_t t = row_target(p);
     if (t < 0 || (int)(t % Rt) != slot) continue;
     ++hits;
     if (t != cur) { cur = t; cnt = 1; start = p; } else { ++cnt; }
   }
-  if (hits == 0) return;                                     // uniform over the workgroup: it depends on target alone
+  if (hits == 0) return;                                     // uniform over the workgroup: it depends on the tables alone
   // Every lane has read the slot's tag and count by here; lane 0 replaces them at the end.  Without this barrier a wave that
   // started late could read the NEW tag of a restarted slot, take the restart for a carry-on and add to the old frame's sum.
   __syncthreads();
-  float* dst = sum + (int64_t)slot * hw;
   const int first = start < 0 ? 0 : start;
   constexpr int V = VEC ? 4 : 1;
   for (int at = tid * V; at < hw; at += 256 * V) {
@@ -162,8 +169,7 @@ __global__ __launch_bounds__(256) void live_track_add_kernel(const float* __rest
       }
     }
     for (int p = first; p < P; ++p) {
-      const int64_t t = target[p];
-      if (t != cur) continue;                                // from `start` on, the slot's rows all carry its final tag
+      if (row_target(p) != cur) continue;                    // from `start` on, the slot's rows all carry its final tag (>= 0)
       const float* row = maps + (int64_t)p * hw + at;
       if constexpr (VEC) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(row);
@@ -182,7 +188,31 @@ __global__ __launch_bounds__(256) void live_track_add_kernel(const float* __rest
       dst[at] = acc[0];
     }
   }
-  if (tid == 0) { count[slot] = cnt; tag[slot] = cur; }
+  if (tid == 0) { *cnt_at = cnt; *tag_at = cur; }
+}
+
+// grid (Rt), 256 threads.  Workgroup s is slot s of the ring and takes the rows of target[0 .. P) by live_add_slot.
+template <bool VEC>
+__global__ __launch_bounds__(256) void live_track_add_kernel(const float* __restrict__ maps, const int64_t* __restrict__ target, int P,
+                                                             int hw, float* __restrict__ sum, int* __restrict__ count,
+                                                             int64_t* __restrict__ tag, int Rt) {
+  const int slot = blockIdx.x;
+  live_add_slot<VEC>(maps, P, hw, sum + (int64_t)slot * hw, count + slot, tag + slot, slot, Rt, [=](int p) { return target[p]; });
+}
+
+// grid (Rt, streams), 256 threads: the track rings of a GazeLiveGroup lie in one arena, sum (streams, Rt, hw), count and tag
+// (streams, Rt).  Workgroup (s, i) is live_track_add_kernel's workgroup s on the ring of stream i, restricted to the rows with
+// stream_of[p] == i; a row whose stream lies outside [0, streams) belongs to no workgroup.  Both tables are read by blockIdx and
+// p alone: uniform loads.
+template <bool VEC>
+__global__ __launch_bounds__(256) void group_live_add_kernel(const float* __restrict__ maps, const int64_t* __restrict__ target,
+                                                             const int* __restrict__ stream_of, int P, int hw,
+                                                             float* __restrict__ sum, int* __restrict__ count,
+                                                             int64_t* __restrict__ tag, int Rt) {
+  const int slot = blockIdx.x, i = blockIdx.y;
+  const int64_t at = (int64_t)i * Rt + slot;
+  live_add_slot<VEC>(maps, P, hw, sum + at * hw, count + at, tag + at, slot, Rt,
+                     [=](int p) { return stream_of[p] == i ? target[p] : (int64_t)-1; });
 }
 
 // how many maps frame t holds in the ring: its slot's count when the slot's tag is t, else 0 (never written, or recycled)
@@ -203,19 +233,16 @@ __device__ __forceinline__ void live_mean(float (&m)[NCH * 4], const float* __re
   for (int k = 0; k < NCH * 4; ++k) m[k] *= inv;
 }
 
-// grid (K), 256 threads: workgroup k answers frame n = f0 + k by the rule of csts_gaze_track_fill on a track of n + max_gap + 1
-// frames whose count is live_count_of: a, b as gaze_fill_kernel finds them (all uniform over the workgroup), the map by
-// live_mean / blend_maps, the outputs by track_tail.
+// Workgroup blockIdx.x answers frame n of the ring (sum, count, tag) by the rule of csts_gaze_track_fill on a track of
+// n + max_gap + 1 frames whose count is live_count_of: a, b as gaze_fill_kernel finds them (all uniform over the workgroup), the
+// map by live_mean / blend_maps, the outputs by track_tail, into row blockIdx.x.  n < 0 finds nothing: the unpredicted row.
 template <int NCH, bool VEC>
-__global__ __launch_bounds__(256) void live_track_rows_kernel(const float* __restrict__ sum, const int* __restrict__ count,
-                                                              const int64_t* __restrict__ tag, int Rt, int64_t f0, int H, int W,
-                                                              int mode, int max_gap, float* __restrict__ heatmaps,
-                                                              float* __restrict__ rescaled, float* __restrict__ points,
-                                                              float* __restrict__ peak, int* __restrict__ out_count,
-                                                              int* __restrict__ neighbours) {
+__device__ __forceinline__ void live_row(const float* __restrict__ sum, const int* __restrict__ count, const int64_t* __restrict__ tag,
+                                         int Rt, int64_t n, int H, int W, int mode, int max_gap, float* __restrict__ heatmaps,
+                                         float* __restrict__ rescaled, float* __restrict__ points, float* __restrict__ peak,
+                                         int* __restrict__ out_count, int* __restrict__ neighbours) {
   const int tid = threadIdx.x;
   const int hw = H * W;
-  const int64_t n = f0 + blockIdx.x;
   const int own = live_count_of(count, tag, Rt, n);
   int64_t a = -1, b = -1;
   if (own > 0) {
@@ -250,6 +277,36 @@ __global__ __launch_bounds__(256) void live_track_rows_kernel(const float* __res
   }
 }
 
+// grid (K), 256 threads: workgroup k answers frame f0 + k
+template <int NCH, bool VEC>
+__global__ __launch_bounds__(256) void live_track_rows_kernel(const float* __restrict__ sum, const int* __restrict__ count,
+                                                              const int64_t* __restrict__ tag, int Rt, int64_t f0, int H, int W,
+                                                              int mode, int max_gap, float* __restrict__ heatmaps,
+                                                              float* __restrict__ rescaled, float* __restrict__ points,
+                                                              float* __restrict__ peak, int* __restrict__ out_count,
+                                                              int* __restrict__ neighbours) {
+  live_row<NCH, VEC>(sum, count, tag, Rt, f0 + blockIdx.x, H, W, mode, max_gap, heatmaps, rescaled, points, peak, out_count,
+                     neighbours);
+}
+
+// grid (K), 256 threads: workgroup k answers frame frame_of[k] of the ring of stream stream_of[k] in the arena of
+// group_live_add_kernel, by live_row.  Both table reads depend on blockIdx alone: uniform.  A stream outside [0, streams), or
+// a negative frame, gives the unpredicted row and reads no ring.
+template <int NCH, bool VEC>
+__global__ __launch_bounds__(256) void group_live_rows_kernel(const float* __restrict__ sum, const int* __restrict__ count,
+                                                              const int64_t* __restrict__ tag, int streams, int Rt,
+                                                              const int* __restrict__ stream_of, const int64_t* __restrict__ frame_of,
+                                                              int H, int W, int mode, int max_gap, float* __restrict__ heatmaps,
+                                                              float* __restrict__ rescaled, float* __restrict__ points,
+                                                              float* __restrict__ peak, int* __restrict__ out_count,
+                                                              int* __restrict__ neighbours) {
+  const int i = stream_of[blockIdx.x];
+  const bool known = i >= 0 && i < streams;
+  const int64_t ring = (int64_t)(known ? i : 0) * Rt;
+  live_row<NCH, VEC>(sum + ring * (H * W), count + ring, tag + ring, Rt, known ? frame_of[blockIdx.x] : (int64_t)-1, H, W, mode,
+                     max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
+}
+
 template <int NCH>
 void launch_live_rows(bool vec, unsigned K, hipStream_t stream, const float* sum, const int* count, const int64_t* tag, int Rt,
                       int64_t f0, int H, int W, int mode, int max_gap, float* heatmaps, float* rescaled, float* points, float* peak,
@@ -258,6 +315,16 @@ void launch_live_rows(bool vec, unsigned K, hipStream_t stream, const float* sum
                               max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
   else hipLaunchKernelGGL((live_track_rows_kernel<NCH, false>), dim3(K), dim3(256), 0, stream, sum, count, tag, Rt, f0, H, W, mode,
                           max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
+}
+
+template <int NCH>
+void launch_group_live_rows(bool vec, unsigned K, hipStream_t stream, const float* sum, const int* count, const int64_t* tag,
+                            int streams, int Rt, const int* stream_of, const int64_t* frame_of, int H, int W, int mode, int max_gap,
+                            float* heatmaps, float* rescaled, float* points, float* peak, int* out_count, int* neighbours) {
+  if (vec) hipLaunchKernelGGL((group_live_rows_kernel<NCH, true>), dim3(K), dim3(256), 0, stream, sum, count, tag, streams, Rt,
+                              stream_of, frame_of, H, W, mode, max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
+  else hipLaunchKernelGGL((group_live_rows_kernel<NCH, false>), dim3(K), dim3(256), 0, stream, sum, count, tag, streams, Rt,
+                          stream_of, frame_of, H, W, mode, max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
 }
 
 int ingest_check(const void* chunk, const void* pairs, const void* params, const void* ring, const float* mean, const float* std,
@@ -532,6 +599,51 @@ extern "C" int csts_live_track_rows(const float* sum, const int* count, const in
   else if (nch <= 2) launch_live_rows<2>(vec, n, stream, sum, count, frame, Rt, f0, H, W, mode, max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
   else if (nch <= 4) launch_live_rows<4>(vec, n, stream, sum, count, frame, Rt, f0, H, W, mode, max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
   else launch_live_rows<8>(vec, n, stream, sum, count, frame, Rt, f0, H, W, mode, max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_group_live_add(const float* maps, const int64_t* target_idx, const int* stream_of, int P, int H, int W, float* sum,
+                                   int* count, int64_t* frame, int streams, int Rt, hipStream_t stream) {
+  CSTS_REQUIRE(P >= 1 && P <= 65535 && Rt >= 1 && Rt <= 65535, "1 <= P <= 65535 maps, 1 <= Rt <= 65535 slots");
+  CSTS_REQUIRE(streams >= 1 && streams <= 65535 && (int64_t)streams * Rt < ((int64_t)1 << 31),
+               "1 <= streams <= 65535 and streams * Rt < 2^31");
+  CSTS_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W <= CSTS_GAZE_DECODE_MAX_HW, "1 <= H * W <= CSTS_GAZE_DECODE_MAX_HW");
+  CSTS_REQUIRE(maps && target_idx && stream_of && sum && count && frame, "null maps, target_idx, stream_of or arena");
+  CSTS_REQUIRE((const void*)maps != (const void*)sum, "maps must not be the arena");
+  const int hw = H * W;
+  const bool vec = hw % 4 == 0 && aligned16(maps) && aligned16(sum);
+  const dim3 grid((unsigned)Rt, (unsigned)streams);
+  if (vec) hipLaunchKernelGGL(group_live_add_kernel<true>, grid, dim3(256), 0, stream, maps, target_idx, stream_of, P, hw, sum, count,
+                              frame, Rt);
+  else hipLaunchKernelGGL(group_live_add_kernel<false>, grid, dim3(256), 0, stream, maps, target_idx, stream_of, P, hw, sum, count,
+                          frame, Rt);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_group_live_rows(const float* sum, const int* count, const int64_t* frame, int streams, int Rt, const int* stream_of,
+                                    const int64_t* frame_of, int K, int H, int W, int mode, int max_gap, float* heatmaps,
+                                    float* rescaled, float* points, float* peak, int* out_count, int* neighbours, hipStream_t stream) {
+  CSTS_REQUIRE(Rt >= 1 && Rt <= 65535 && K >= 1 && K <= 65535, "1 <= Rt <= 65535 slots, 1 <= K <= 65535 frames");
+  CSTS_REQUIRE(streams >= 1 && (int64_t)streams * Rt < ((int64_t)1 << 31), "1 <= streams and streams * Rt < 2^31");
+  CSTS_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W <= CSTS_GAZE_DECODE_MAX_HW, "1 <= H * W <= CSTS_GAZE_DECODE_MAX_HW (the frame is held in registers)");
+  CSTS_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (hold) or 1 (linear)");
+  CSTS_REQUIRE(max_gap >= 1 && max_gap <= CSTS_GAZE_FILL_MAX_GAP, "1 <= max_gap <= CSTS_GAZE_FILL_MAX_GAP");
+  CSTS_REQUIRE(sum && count && frame && stream_of && frame_of, "null arena, stream_of or frame_of");
+  CSTS_REQUIRE(heatmaps != sum && rescaled != sum && (const void*)out_count != (const void*)count &&
+                   (const void*)points != (const void*)sum && (const void*)peak != (const void*)sum,
+               "no output may be the arena");
+  if (!heatmaps && !rescaled && !points && !peak && !out_count && !neighbours) return 0;
+  const int hw = H * W;
+  const bool vec = hw % 4 == 0 && aligned16(sum) && aligned16(heatmaps) && aligned16(rescaled);
+  const int nch = (int)cdiv(hw, 1024);
+  static_assert(DEC_MAX_NCH == 8, "the dispatch below covers 1, 2, 4 and 8 chunks per lane");
+  const unsigned n = (unsigned)K;
+  if (nch <= 1) launch_group_live_rows<1>(vec, n, stream, sum, count, frame, streams, Rt, stream_of, frame_of, H, W, mode, max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
+  else if (nch <= 2) launch_group_live_rows<2>(vec, n, stream, sum, count, frame, streams, Rt, stream_of, frame_of, H, W, mode, max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
+  else if (nch <= 4) launch_group_live_rows<4>(vec, n, stream, sum, count, frame, streams, Rt, stream_of, frame_of, H, W, mode, max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
+  else launch_group_live_rows<8>(vec, n, stream, sum, count, frame, streams, Rt, stream_of, frame_of, H, W, mode, max_gap, heatmaps, rescaled, points, peak, out_count, neighbours);
   CSTS_LAUNCH_CHECK();
   return 0;
 }

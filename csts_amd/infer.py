@@ -509,11 +509,26 @@ class GazePredictor:
         wav)}) is one tick -- what all the slots pushed goes into one arena of rings with one launch per stage, and the windows
         that become ready in the same tick are predicted together, `batch` per predict_batch call, whichever slot they belong
         to; close(slot) / close() end a slot / all of them, reset(slot) reopens one.  The keywords are stream()'s and hold for
-        every slot; each slot has its own source size.  live=, overlay= and attention are not part of a group.
-        GazeStreamGroup states the tick rule and the contract; group_schedule is the rule on the host."""
+        every slot; each slot has its own source size.  live=, overlay= and attention are not part of a group (the live
+        track of a group is live_group()).  GazeStreamGroup states the tick rule and the contract; group_schedule is the rule
+        on the host."""
         from .stream import GazeStreamGroup
         return GazeStreamGroup(self, streams, fps=fps, stride=stride, segment=segment, batch=batch, max_chunk=max_chunk,
                                pixel_format=pixel_format, matrix=matrix, full_range=full_range, input_rate=input_rate)
+
+    def live_group(self, streams, live, fps=None, stride=None, segment=None, batch=4, max_chunk=32, pixel_format="rgb24",
+                   matrix="bt601", full_range=False, input_rate=None, max_gap=None, overlay=False, alpha=0.4, radius=5):
+        """stream_group() with the live track of stream(live=...) on every slot (csts_amd.stream.GazeLiveGroup, forecast plans):
+        push_live({slot: (frames, wav)}) is one tick and returns (windows, {slot: the push_live dict of that slot's frames}) --
+        every pushed frame of every slot answered with its row of a gaze track computed from the windows of its own slot that
+        have run by then, filled at most max_gap frames apart; overlay=True adds the frames drawn over.  live: "hold" or
+        "linear", required.  The tracks of all slots live in one arena and a round folds and answers them with one launch each
+        (ops.group_live_add, ops.group_live_rows), whatever the number of slots.  The other keywords are stream_group()'s and
+        stream()'s.  GazeLiveGroup states the order of work and the contract; group_live_schedule is the rule on the host."""
+        from .stream import GazeLiveGroup
+        return GazeLiveGroup(self, streams, live, fps=fps, stride=stride, segment=segment, batch=batch, max_chunk=max_chunk,
+                             pixel_format=pixel_format, matrix=matrix, full_range=full_range, input_rate=input_rate,
+                             max_gap=max_gap, overlay=overlay, alpha=alpha, radius=radius)
 
     @torch.no_grad()
     def _video_params_row(self, H, W):

@@ -288,6 +288,8 @@ SYMBOLS = {
     "csts_group_ingest_yuv": (_I, [vp, vp, _I, vp, vp, _I, vp, i64, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),
     "csts_live_track_add": (_I, [vp, vp, _I, _I, _I, vp, vp, vp, _I, vp]),
     "csts_live_track_rows": (_I, [vp, vp, vp, _I, i64, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, vp, vp]),
+    "csts_group_live_add": (_I, [vp, vp, vp, _I, _I, _I, vp, vp, vp, _I, _I, vp]),
+    "csts_group_live_rows": (_I, [vp, vp, vp, _I, _I, vp, vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, vp, vp]),
     "csts_adaptive_f1_workspace": (sz, [i64, _I]),
     "csts_adaptive_f1": (_I, [vp, vp, vp, vp, _I, i64, _I, _I, vp, vp, sz, vp]),
     "csts_f1_counts": (_I, [vp, vp, vp, _I, i64, _I, _I, vp, vp]),

@@ -2643,6 +2643,144 @@ def live_track_rows(ring, f0, K, mode="linear", max_gap=9, want=_LIVE_OUTPUTS):
     return out
 
 
+# ----------------------------------------------------------------------------------------- live gaze track of a stream group
+def group_live_ring(streams, slots, h, w, device):
+    """An empty arena of `streams` track rings of `slots` frames of h x w maps on `device`: {"sum" fp32 (streams, slots, h, w)
+    zeros, "count" int32 (streams, slots) zeros, "frame" int64 (streams, slots) -1}.  Frame t of slot i lives at [i, t mod slots];
+    the ring of slot i is the ring live_track_ring(slots, h, w) describes (include/csts_hip.h, live track of a stream group)."""
+    streams, slots, h, w = int(streams), int(slots), int(h), int(w)
+    if slots < 1 or slots > 65535 or h < 1 or w < 1 or h * w > L.GAZE_DECODE_MAX_HW:
+        raise ValueError(f"a track ring holds 1..65535 slots of maps with h * w <= {L.GAZE_DECODE_MAX_HW}, got {slots} of {h} x {w}")
+    if streams < 1 or streams > 65535 or streams * slots >= 2 ** 31:
+        raise ValueError(f"a track arena holds 1..65535 rings and fewer than 2^31 slots, got {streams} rings of {slots}")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.CstsError("the track arena lives on MI355X only (there is no CPU fallback)")
+    return {"sum": torch.zeros(streams, slots, h, w, dtype=torch.float32, device=device),
+            "count": torch.zeros(streams, slots, dtype=torch.int32, device=device),
+            "frame": torch.full((streams, slots), -1, dtype=torch.int64, device=device)}
+
+
+def _check_group_live_ring(ring):
+    """The three tensors of a track arena, checked: (sum, count, frame, streams, Rt, h, w)."""
+    try:
+        s, c, f = ring["sum"], ring["count"], ring["frame"]
+    except (KeyError, TypeError, IndexError):
+        raise ValueError("ring must be a dict with \"sum\", \"count\" and \"frame\" (ops.group_live_ring)")
+    _need_gpu(s, c, f)
+    if s.dim() != 4 or s.dtype != torch.float32 or not s.is_contiguous():
+        raise ValueError(f"ring[\"sum\"] must be contiguous fp32 (streams, Rt, h, w), got {tuple(s.shape)} {s.dtype}")
+    n, Rt, h, w = s.shape
+    if c.dtype != torch.int32 or tuple(c.shape) != (n, Rt) or not c.is_contiguous():
+        raise ValueError(f"ring[\"count\"] must be contiguous int32 ({n}, {Rt}), got {tuple(c.shape)} {c.dtype}")
+    if f.dtype != torch.int64 or tuple(f.shape) != (n, Rt) or not f.is_contiguous():
+        raise ValueError(f"ring[\"frame\"] must be contiguous int64 ({n}, {Rt}), got {tuple(f.shape)} {f.dtype}")
+    if Rt < 1 or Rt > 65535 or h * w < 1 or h * w > L.GAZE_DECODE_MAX_HW:
+        raise ValueError(f"a track ring holds 1..65535 slots of maps with h * w <= {L.GAZE_DECODE_MAX_HW}, got {Rt} of {h} x {w}")
+    if n < 1 or n > 65535 or n * Rt >= 2 ** 31:
+        raise ValueError(f"a track arena holds 1..65535 rings and fewer than 2^31 slots, got {n} rings of {Rt}")
+    return s, c, f, n, Rt, h, w
+
+
+def _live_host_table(values, n, name, of):
+    """The host copy of a device table of n integers, as an int64 numpy array."""
+    import numpy as np
+    if torch.is_tensor(values):
+        raise ValueError(f"{name} is the host copy of {of}: a sequence or numpy array of ints, not a tensor")
+    host = np.asarray(values)
+    if host.shape != (n,) or not np.issubdtype(host.dtype, np.integer):
+        raise ValueError(f"{name} must hold the {n} entries of {of} as integers on the host, got shape {host.shape} {host.dtype}")
+    return host.astype(np.int64)
+
+
+def group_live_add(maps, target_idx, stream_of, targets, streams_host, ring, live_from):
+    """csts_group_live_add: live_track_add for the slots of a track arena (ops.group_live_ring), in ONE launch.  maps fp32 (P, h, w),
+    row p predicting frame target_idx[p] (int64 (P,) on the device) of slot stream_of[p] (int32 (P,) on the device); the ring of
+    slot i takes the rows with stream_of[p] == i in ascending p by live_track_add's rule -- restart or carry on, the same
+    arithmetic -- so it ends as live_track_add leaves it on those rows alone.  A ring slot no row names is not touched.
+    targets, streams_host: the same two tables on the HOST (sequences or numpy arrays of ints), so that what cannot be written is
+    refused before the launch and without a host sync: a negative target, a stream outside [0, streams), and a target
+    t >= live_from[i] + Rt on its slot i, which would overwrite the slot of frame t - Rt >= live_from[i].  live_from: one entry
+    per slot of the arena, the lowest frame of that slot whose row may still be asked for, minus max_gap - 1.  A refusal leaves
+    the arena untouched.  One launch, no atomics, no host sync."""
+    import numpy as np
+    _need_gpu(maps, target_idx, stream_of)
+    s, c, f, n, Rt, h, w = _check_group_live_ring(ring)
+    if maps.dim() != 3 or maps.dtype != torch.float32 or tuple(maps.shape[1:]) != (h, w):
+        raise ValueError(f"maps must be fp32 (P, {h}, {w}), got {tuple(maps.shape)} {maps.dtype}")
+    P = maps.shape[0]
+    if target_idx.dtype != torch.int64 or tuple(target_idx.shape) != (P,):
+        raise ValueError(f"target_idx must be int64 ({P},), got {tuple(target_idx.shape)} {target_idx.dtype}")
+    if stream_of.dtype != torch.int32 or tuple(stream_of.shape) != (P,):
+        raise ValueError(f"stream_of must be int32 ({P},), got {tuple(stream_of.shape)} {stream_of.dtype}")
+    if P < 1 or P > 65535:
+        raise ValueError(f"group_live_add takes 1..65535 maps a call, got {P}")
+    host_t = _live_host_table(targets, P, "targets", "target_idx")
+    host_s = _live_host_table(streams_host, P, "streams_host", "stream_of")
+    if torch.is_tensor(live_from):
+        raise ValueError("live_from is a sequence of ints on the host, one per slot, not a tensor")
+    start = np.asarray(live_from)
+    if start.shape != (n,) or not np.issubdtype(start.dtype, np.integer):
+        raise ValueError(f"live_from must hold one integer per slot of the arena ({n}), got shape {start.shape} {start.dtype}")
+    if int(host_t.min()) < 0:
+        raise ValueError(f"targets must be frame numbers >= 0, got {int(host_t.min())}")
+    if int(host_s.min()) < 0 or int(host_s.max()) >= n:
+        bad = int(host_s.min()) if int(host_s.min()) < 0 else int(host_s.max())
+        raise ValueError(f"the arena holds the rings of streams 0..{n - 1}, a row names stream {bad}; nothing was written")
+    over = host_t >= start.astype(np.int64)[host_s] + Rt
+    if over.any():
+        p = int(np.argmax(over))
+        t, i = int(host_t[p]), int(host_s[p])
+        raise ValueError(f"a track ring holds {Rt} frames: target {t} of stream {i} would overwrite the slot of frame {t - Rt}, which "
+                         f"is still inside the live span (it starts at frame {int(start[i])}); nothing was written")
+    x = maps.detach().contiguous()
+    L.check(_lib().csts_group_live_add(_p(x), _p(target_idx.contiguous()), _p(stream_of.contiguous()), P, h, w, _p(s), _p(c), _p(f),
+                                       n, Rt, _stream()), "csts_group_live_add")
+
+
+def group_live_rows(ring, stream_of, frame_of, mode="linear", max_gap=9, want=_LIVE_OUTPUTS):
+    """csts_group_live_rows: live_track_rows over a track arena, in ONE launch: row k answers frame frame_of[k] of slot
+    stream_of[k] by live_track_rows' rule on that slot's ring, bit for bit.  stream_of, frame_of: the tables on the HOST
+    (sequences or numpy arrays of K ints); they are checked -- frames >= 0 and frame + max_gap < 2^31 -- and uploaded as int32
+    and int64.  A stream outside the arena is not refused: its row is the unpredicted one (zero maps, NaN points, peak 0, count
+    0, neighbours (-1, -1)).  The outputs are live_track_rows', K rows in the order of the tables, those named in `want`.  The
+    arena is only read.  One launch, no host sync."""
+    import numpy as np
+    s, c, f, n, Rt, h, w = _check_group_live_ring(ring)
+    want = tuple(want)
+    unknown = [k for k in want if k not in _LIVE_OUTPUTS]
+    if unknown or not want:
+        raise ValueError(f"want must name some of {_LIVE_OUTPUTS}, got {want}")
+    if mode not in _FILL_MODES:
+        raise ValueError(f"mode must be one of {_FILL_MODES}, got {mode!r}")
+    max_gap = int(max_gap)
+    if max_gap < 1 or max_gap > L.GAZE_FILL_MAX_GAP:
+        raise ValueError(f"max_gap must lie in 1..{L.GAZE_FILL_MAX_GAP}, got {max_gap}")
+    K = len(frame_of)
+    if K < 1 or K > 65535:
+        raise ValueError(f"group_live_rows answers 1..65535 frames a call, got {K}")
+    host_f = _live_host_table(frame_of, K, "frame_of", "the frame table")
+    host_s = _live_host_table(stream_of, K, "stream_of", "the stream table")
+    if int(host_f.min()) < 0 or int(host_f.max()) + max_gap >= 2 ** 31:
+        raise ValueError(f"group_live_rows answers frames >= 0 with frame + max_gap < 2^31, got {int(host_f.min())}..{int(host_f.max())}")
+    if int(host_s.min()) < -2 ** 31 or int(host_s.max()) >= 2 ** 31:
+        raise ValueError("stream_of holds int32 stream numbers")
+    dev = s.device
+    streams_dev = torch.from_numpy(host_s.astype(np.int32)).to(dev)
+    frames_dev = torch.from_numpy(host_f).to(dev)
+    out = {}
+    for k, shape, dt in (("heatmaps", (K, h, w), torch.float32), ("rescaled", (K, h, w), torch.float32),
+                         ("points", (K, 2), torch.float32), ("peak", (K,), torch.float32), ("count", (K,), torch.int32),
+                         ("neighbours", (K, 2), torch.int32)):
+        if k in want:
+            out[k] = torch.empty(shape, dtype=dt, device=dev)
+    L.check(_lib().csts_group_live_rows(_p(s), _p(c), _p(f), n, Rt, _p(streams_dev), _p(frames_dev), K, h, w,
+                                        _FILL_MODES.index(mode), max_gap, _p(out.get("heatmaps")), _p(out.get("rescaled")),
+                                        _p(out.get("points")), _p(out.get("peak")), _p(out.get("count")), _p(out.get("neighbours")),
+                                        _stream()), "csts_group_live_rows")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- gaze overlay
 def jet_table():
     """The heat colours of gaze_overlay on the host: uint8 numpy (256, 3) RGB, row q = the classic JET by the integer formula of

@@ -10,7 +10,9 @@ every pushed frame with its row of a gaze track, out of a third ring (``stream_l
 ops.live_track_add and ops.live_track_rows, the live-track kernels of stream.hip).  ``GazeStreamGroup`` serves several
 recordings at once: its slots share one arena of rings, a tick's frames and samples go in with one launch per stage
 (inputs.group_stft, inputs.group_ingest) and the windows of different slots that are ready together share a forward;
-``group_schedule`` states on the host which windows share a batch."""
+``group_schedule`` states on the host which windows share a batch.  ``GazeLiveGroup`` adds the live track to a group: the track
+rings of all slots share one arena, and a round folds its windows and answers its frames with one launch each
+(ops.group_live_add, ops.group_live_rows; ``group_live_schedule`` is the rule on the host)."""
 from __future__ import annotations
 
 import numbers
@@ -709,8 +711,8 @@ class GazeStreamGroup:
     stft_logpower of its whole waveform (with input_rate: of resample_audio of the whole waveform).  A group of one slot equals
     a GazeStream with the same batch, bit for bit.  Nothing is claimed about a row's bits when its batch neighbours change.
 
-    Out of scope, and not accepted as keywords: live=, overlay= (the live track of GazeStream) and attention maps; different
-    plans per slot; equality with predict_video."""
+    Not accepted as keywords here: live= and overlay=.  The live track of a group is GazeLiveGroup, a subclass (reach it through
+    GazePredictor.live_group).  Out of scope: attention maps; different plans per slot; equality with predict_video."""
 
     def __init__(self, predictor, streams, fps=None, stride=None, segment=None, batch=4, max_chunk=32, pixel_format="rgb24",
                  matrix="bt601", full_range=False, input_rate=None):
@@ -872,13 +874,21 @@ class GazeStreamGroup:
                         given[i][1] = self._resamplers[i].push(given[i][1])
             for part, batches in _tick_rounds({i: p[4] for i, p in planned.items()}, self.batch):
                 self._audio([(i, given[i][1][sa[i]:sa[i] + dm], -1) for i, (_, dm, _) in part.items() if dm])
-                self._ingest([(i, given[i][0][fa[i]:fa[i] + dk]) for i, (dk, _, _) in part.items() if dk])
+                chunks = [(i, given[i][0][fa[i]:fa[i] + dk]) for i, (dk, _, _) in part.items() if dk]
+                self._ingest(chunks)
                 for i, (dk, dm, _) in part.items():
                     fa[i], sa[i] = fa[i] + dk, sa[i] + dm
+                ran = []
                 for rows in batches:
-                    for r in self._run(rows):
-                        out[r["stream"]].append(r)
+                    ran += self._run(rows)
+                for r in ran:
+                    out[r["stream"]].append(r)
+                self._round_done(ran, chunks)
         return out
+
+    def _round_done(self, ran, chunks):
+        """The end of a round of push(): `ran`, the windows the round ran over all slots in (slot, window) order, and `chunks`,
+        [(slot, the frames that slot took in this round)] in slot order.  Nothing here; GazeLiveGroup folds and answers."""
 
     def close(self, slot=None):
         """End slot `slot`, or with None every slot that is still open -> {slot: [the windows the padded last column completes]}.
@@ -930,3 +940,180 @@ class GazeStreamGroup:
         self.closed[i], self.hw[i], self._rows[i], self._tail[i], self._tail_base[i] = False, None, None, None, 0
         if self.input_rate is not None:
             self._resamplers[i] = inputs.StreamResampler(self.input_rate)
+
+
+# ---- live group: the live track of GazeStream on every slot of a group ----------------------------------------------------------------
+
+def group_live_schedule(plan, ticks, max_chunk=32, input_rate=None):
+    """The companion of group_schedule for a GazeLiveGroup: {slot: [known(f) for every frame f that slot pushed, in frame order]}.
+    ticks: a list of {slot: (frames, samples)} counts, one dict per push, as group_schedule takes them.  Round r of a tick takes
+    step r of every slot, and a slot's steps come from stream_steps on that slot's own counters, so what a frame knows does not
+    depend on the other slots: this is stream_live_schedule on each slot's own pushes, and it is computed as that.  A slot that
+    is stuck raises stream_steps' ValueError prefixed with "slot i: ", as group_schedule does."""
+    pushes = {}
+    for tick in ticks:
+        for i in sorted(tick):
+            k, m = (int(v) for v in tick[i])
+            pushes.setdefault(i, []).append((k, m))
+    out = {}
+    for i in sorted(pushes):
+        try:
+            out[i] = stream_live_schedule(plan, pushes[i], max_chunk=max_chunk, input_rate=input_rate)
+        except ValueError as e:
+            raise ValueError(f"slot {i}: {e}") from None
+    return out
+
+
+class GazeLiveGroup(GazeStreamGroup):
+    """A GazeStreamGroup whose slots also answer every pushed frame with its row of a gaze track: GazeStream(live=...) for many
+    recordings at once (reach it through GazePredictor.live_group).  live: "hold" or "linear", required; forecast plans only
+    (check_live_plan); max_gap defaults to default_max_gap(plan); overlay, alpha and radius as GazeStream takes them.
+    Everything a GazeStreamGroup does it does unchanged: the emitted windows are those of a GazeStreamGroup with the same
+    arguments on the same ticks, bit for bit.
+
+    The tracks live in one arena, allocated once, when the group is made: sums fp32 (streams, Rt, S/4, S/4) with a count and a
+    frame tag per ring slot, Rt = live_ring_slots(plan, max_chunk, max_gap), so the ring of slot i is exactly a GazeStream's
+    (ops.group_live_ring).  `capacity` gains "track_slots" and "track_bytes" (per slot), and "total_bytes" includes the arena.
+
+    A round of a tick works in this order, whatever the number of slots:
+      1. the samples of all slots (one launch, inputs.group_stft);
+      2. their frames (one launch, inputs.group_ingest);
+      3. the round's batches (one predict_batch each);
+      4. ONE ops.group_live_add: all the windows the round ran, over all slots, in (slot, window) order -- the rows a batch was
+         padded with are not among them;
+      5. ONE ops.group_live_rows: the frames the round took in, over all slots, in (slot, frame) order; the result is split per
+         slot.
+    That is GazeStream._push's order -- audio, frames, ready windows, fold, rows -- for every slot, so with results_i the windows
+    the group emitted for slot i and known_i = group_live_schedule(plan, ticks, max_chunk, input_rate)[i],
+
+      live row of frame f of slot i == row f of fill_track(track_from_windows(results_i[:known_i[f]], f + max_gap + 1), mode=live,
+                                                           max_gap=max_gap)
+
+    bit for bit, and the unpredicted row for known 0.  A group of one slot equals a GazeStream with the same batch, live, max_gap
+    and overlay on the same pushes: windows, rows and overlay.
+
+    push_live(pieces) -> (windows, live): windows is what push returns, live is {slot: dict} for the slots of pieces, each dict
+    exactly a GazeStream.push_live dict ("frame_idx", "known", "points", "peak", "count", "neighbours", "filled", "rescaled",
+    "points_source", and "overlay" with overlay=True); the rows of different rounds are concatenated in frame order, and a slot
+    that pushed no frames gets the K = 0 dict.  push() folds the windows it runs as well, so push and push_live may be mixed; a
+    frame is only answered by the push_live that takes it in.  "points_source" and "overlay" are computed per slot, since each
+    slot has its own H x W: the overlay is predictor.render_track on that slot's frames of the round in the group's pixel
+    format, i.e. csts_gaze_overlay, one launch per slot and round.  A single overlay launch over slots of different sizes is
+    a follow-up.
+
+    close() behaves as in the base class; the closing windows are not folded, as in GazeStream.close (no frame arrives after
+    them).  reset(slot) reopens a closed slot and, unlike the base class's, writes to the device: see there.
+
+    Out of scope: live attention maps, one overlay launch for all slots, different plans per slot, and the command line
+    (tools/predict.py --videos still refuses --live and --overlay)."""
+
+    def __init__(self, predictor, streams, live, fps=None, stride=None, segment=None, batch=4, max_chunk=32, pixel_format="rgb24",
+                 matrix="bt601", full_range=False, input_rate=None, max_gap=None, overlay=False, alpha=0.4, radius=5):
+        from . import ops
+        from .infer import default_max_gap
+        if live not in LIVE_MODES:
+            raise ValueError(f"live must be one of {LIVE_MODES}, got {live!r}")
+        plan = plan_stream(predictor.cfg, fps=fps, stride=stride, segment=segment)
+        check_live_plan(plan)
+        self.live, self.overlay, self.alpha, self.radius = live, bool(overlay), float(alpha), int(radius)
+        self.max_gap = default_max_gap(plan) if max_gap is None else int(max_gap)
+        if self.max_gap < 1:
+            raise ValueError(f"max_gap must be positive, got {max_gap}")
+        if not 0.0 <= self.alpha <= 1.0 or self.radius < 0:
+            raise ValueError(f"alpha must lie in [0, 1] and radius be >= 0, got {alpha} and {radius}")
+        super().__init__(predictor, streams, fps=fps, stride=stride, segment=segment, batch=batch, max_chunk=max_chunk,
+                         pixel_format=pixel_format, matrix=matrix, full_range=full_range, input_rate=input_rate)
+        self.track_slots = live_ring_slots(self.plan, self.max_chunk, self.max_gap)
+        side = self.S // 4                                   # the model's heat maps are S/4 x S/4
+        track_bytes = self.track_slots * (side * side * 4 + 4 + 8)
+        self.capacity = dict(self.capacity, track_slots=self.track_slots, track_bytes=track_bytes,
+                             total_bytes=self.capacity["total_bytes"] + self.streams * track_bytes)
+        self._track = ops.group_live_ring(self.streams, self.track_slots, side, side, predictor.device)
+        self._answers = None                                 # {slot: [row dicts]} while a push_live runs
+
+    # ---- device work -----------------------------------------------------------------------------------------------------------
+    def _round_done(self, ran, chunks):
+        """Steps 4 and 5 of a round: fold the windows it ran, then answer the frames it took in."""
+        import numpy as np
+        import torch
+        from . import ops
+        took = dict.fromkeys(range(self.streams), 0)
+        took.update({i: chunk.shape[0] for i, chunk in chunks})
+        if ran:
+            dev = ran[0]["heatmaps"].device
+            maps = torch.cat([r["heatmaps"] for r in ran], dim=0)
+            targets = np.concatenate([np.asarray(r["target_idx"], dtype=np.int64) for r in ran])
+            streams = np.concatenate([np.full(len(r["target_idx"]), r["stream"], dtype=np.int32) for r in ran])
+            # per slot: the first frame whose row is still to come, minus what a row reads back
+            live_from = [max(0, self.frames[i] - took[i] - self.max_gap + 1) for i in range(self.streams)]
+            ops.group_live_add(maps, torch.from_numpy(targets).to(dev), torch.from_numpy(streams).to(dev), targets, streams,
+                               self._track, live_from)
+        if self._answers is None or not chunks:
+            return
+        first = {i: self.frames[i] - took[i] for i, _ in chunks}
+        stream_of = np.concatenate([np.full(took[i], i, dtype=np.int32) for i, _ in chunks])
+        frame_of = np.concatenate([np.arange(first[i], first[i] + took[i], dtype=np.int64) for i, _ in chunks])
+        rows = ops.group_live_rows(self._track, stream_of, frame_of, mode=self.live, max_gap=self.max_gap,
+                                   want=("rescaled", "points", "peak", "count", "neighbours"))
+        dev = rows["count"].device
+        # what GazeStream._live_rows adds to its rows, for all slots at once; the slots take views of it
+        rows["filled"] = (rows["count"] == 0) & (rows["neighbours"][:, 0] >= 0)
+        rows["frame_idx"] = torch.from_numpy(frame_of).to(dev)
+        known = np.concatenate([np.full(took[i], self.next_window[i], dtype=np.int32) for i, _ in chunks])
+        rows["known"] = torch.from_numpy(known).to(dev)
+        at = 0
+        for i, chunk in chunks:
+            self._answers[i].append(self._slot_rows({k: v[at:at + took[i]] for k, v in rows.items()}, i, chunk))
+            at += took[i]
+
+    def _slot_rows(self, rows, i, chunk):
+        """What depends on slot i's H x W, added to its rows of one round: "points_source", and "overlay" on `chunk`, the frames."""
+        from .infer import points_to_source
+        rows["points_source"] = points_to_source(rows["points"], self._rows[i], self.S)
+        if self.overlay:
+            rows["overlay"] = self.predictor.render_track(chunk, rows, alpha=self.alpha, radius=self.radius, **self.fmt)
+        return rows
+
+    def _live_empty(self, i):
+        """The live dict of a slot that pushed no frames."""
+        import torch
+        side, dev = self.S // 4, self.predictor.device
+        shapes = {"frame_idx": ((0,), torch.int64), "known": ((0,), torch.int32), "points": ((0, 2), torch.float32),
+                  "peak": ((0,), torch.float32), "count": ((0,), torch.int32), "neighbours": ((0, 2), torch.int32),
+                  "filled": ((0,), torch.bool), "rescaled": ((0, side, side), torch.float32),
+                  "points_source": ((0, 2), torch.float64)}
+        out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
+        if self.overlay:
+            H, W = self.hw[i] if self.hw[i] is not None else (0, 0)
+            out["overlay"] = torch.empty((0, H, W, 3), dtype=torch.uint8, device=dev)
+        return out
+
+    # ---- the interface ---------------------------------------------------------------------------------------------------------
+    def push_live(self, pieces):
+        """push(pieces) -> (windows, live): windows is what push returns; live is {slot: the GazeStream.push_live dict of the frames
+        that slot pushed in this tick, in frame order} for the slots of pieces (K = 0 for a slot without frames).  A tick that is
+        refused answers nothing and consumes nothing, as push's."""
+        import torch
+        self._answers = {i: [] for i in range(self.streams)}
+        try:
+            windows = self.push(pieces)
+            answers = self._answers
+        finally:
+            self._answers = None
+        live = {}
+        for i in windows:
+            rows = answers[i]
+            if not rows:
+                live[i] = self._live_empty(i)
+            else:
+                live[i] = rows[0] if len(rows) == 1 else {key: torch.cat([r[key] for r in rows], dim=0) for key in rows[0]}
+        return windows, live
+
+    def reset(self, slot):
+        """Reopen the closed slot `slot` as a fresh stream.  Unlike the base class's, this reset writes to the device: it sets the
+        slot's ring to empty (count 0, frame tag -1).  Frame numbers restart at 0 after a reset, so a tag left by the previous
+        recording would be taken for a prediction of the new one; the sums need no clearing, a slot restarts when it is retagged."""
+        super().reset(slot)
+        i = self._slot(slot)
+        self._track["count"][i].zero_()
+        self._track["frame"][i].fill_(-1)

@@ -32,7 +32,7 @@ enum { CSTS_EPI_NONE = 0, CSTS_EPI_GELU = 1, CSTS_EPI_DGELU = 2 };
 enum { CSTS_MASK_NONE = 0, CSTS_MASK_SPATIAL = 1 };
 
 /* Version of this header's struct layouts and call semantics.  Bumped whenever a struct grows or a field changes meaning
- * (2: csts_gemm_args.res_up; 3: compact k|v rows, 16-bit build, loss scaler in csts_opt_args; 4: csts_opt_args.extra_sq, factored AdamW; 5: grouped stencil weight gradients; 6: csts_copy_token_segments, csts_wgrad_grouped8_limited; 7: csts_wgrad_grouped5, csts_gemm algo 500; 8: csts_opt_rule, csts_opt_step, csts_opt_factored_step, csts_opt_factored.tensor replaces pad_; 10: csts_audio_pixel_attn; 11: csts_attention_track, csts_attention_rescale; 12: csts_resample_wav, csts_resample_len; 13: csts_attn_route; 14: 4:2:0 frames, csts_yuv_to_rgb, csts_*_sample_yuv; still 14: csts_stream_*, then csts_resample_stream, csts_resample_ready, csts_resample_first_input (new entry points only, no struct or call changed)).  csts_abi_version() returns the value the
+ * (2: csts_gemm_args.res_up; 3: compact k|v rows, 16-bit build, loss scaler in csts_opt_args; 4: csts_opt_args.extra_sq, factored AdamW; 5: grouped stencil weight gradients; 6: csts_copy_token_segments, csts_wgrad_grouped8_limited; 7: csts_wgrad_grouped5, csts_gemm algo 500; 8: csts_opt_rule, csts_opt_step, csts_opt_factored_step, csts_opt_factored.tensor replaces pad_; 10: csts_audio_pixel_attn; 11: csts_attention_track, csts_attention_rescale; 12: csts_resample_wav, csts_resample_len; 13: csts_attn_route; 14: 4:2:0 frames, csts_yuv_to_rgb, csts_*_sample_yuv; still 14: csts_stream_*, then csts_resample_stream, csts_resample_ready, csts_resample_first_input, csts_live_track_*, csts_group_*, csts_group_live_* (new entry points only, no struct or call changed)).  csts_abi_version() returns the value the
  * LIBRARY was built with: a caller must compare it with the CSTS_ABI_VERSION it was compiled against and refuse a mismatch
  * (the Python binding does, csts_amd/lib.py::load). */
 #define CSTS_ABI_VERSION 14
@@ -965,6 +965,31 @@ int csts_live_track_add(const float* maps, const int64_t* target_idx, int P, int
 int csts_live_track_rows(const float* sum, const int* count, const int64_t* frame, int Rt, int64_t f0, int K, int H, int W, int mode,
                          int max_gap, float* heatmaps, float* rescaled, float* points, float* peak, int* out_count, int* neighbours,
                          hipStream_t stream);
+
+/* ---- live track of a stream group (csts_amd/csrc/stream.hip, csts_amd.GazeLiveGroup): the track rings of `streams` slots in one
+ *      arena, sum fp32 [streams][Rt][H * W], count int32 [streams][Rt], frame int64 [streams][Rt] (-1: empty); frame t of slot i
+ *      lives at [i][t mod Rt], and the ring of slot i is exactly the ring csts_live_track_add / csts_live_track_rows work on.  One
+ *      launch serves every slot; the tables are DEVICE memory read when the kernel runs, by block index alone (uniform reads); no
+ *      atomics, no allocation, no synchronisation, no host read.  The arithmetic is the single-stream kernels' (one device function
+ *      each for the slot and for the row): a track slot and a row have the bits they have there.
+ *      group_live_add: maps [P][H * W] fp32, target_idx int64 [P], stream_of int32 [P].  Grid (Rt, streams): workgroup (s, i) is
+ *        csts_live_track_add's workgroup s on the ring of slot i, restricted to the rows with stream_of[p] == i -- the same two
+ *        walks, the same restart / carry-on rule, additions in ascending p.  A row whose stream lies outside [0, streams) or whose
+ *        target is negative is ignored; a ring slot no row names is not touched.  The caller never names a target t on slot i
+ *        while frame t - Rt of that slot is still to be read (csts_amd.ops.group_live_add refuses that on the host).
+ *        1 <= P, Rt, streams <= 65535, streams * Rt < 2^31, H * W <= CSTS_GAZE_DECODE_MAX_HW, maps must not be sum.
+ *      group_live_rows: stream_of int32 [K], frame_of int64 [K].  Grid (K): workgroup k answers frame frame_of[k] of slot
+ *        stream_of[k] by the rule of csts_live_track_rows on that slot's ring, into row k of the outputs (shapes, NULL outputs and
+ *        128-bit accesses as there).  A row whose stream lies outside [0, streams), or whose frame is negative, is the unpredicted
+ *        row: maps 0, points NaN, peak 0, count 0, neighbours (-1, -1).  The caller keeps frame_of[k] + max_gap < 2^31
+ *        (neighbours are int32; csts_amd.ops.group_live_rows checks the host copy).  1 <= K, Rt <= 65535, 1 <= streams,
+ *        streams * Rt < 2^31, mode 0 | 1, 1 <= max_gap <= CSTS_GAZE_FILL_MAX_GAP; no output may be the arena.
+ *      Both refuse (-1) before the launch and need no GPU to do so.  Graph-capturable. */
+int csts_group_live_add(const float* maps, const int64_t* target_idx, const int* stream_of, int P, int H, int W, float* sum,
+                        int* count, int64_t* frame, int streams, int Rt, hipStream_t stream);
+int csts_group_live_rows(const float* sum, const int* count, const int64_t* frame, int streams, int Rt, const int* stream_of,
+                         const int64_t* frame_of, int K, int H, int W, int mode, int max_gap, float* heatmaps, float* rescaled,
+                         float* points, float* peak, int* out_count, int* neighbours, hipStream_t stream);
 
 #ifdef __cplusplus
 }
