@@ -11,10 +11,11 @@ from .infer import fill_track, fill_plan, default_max_gap, fill_attention_track,
 from .stream import GazeStream, plan_stream, stream_window, stream_schedule, track_from_windows  # noqa: F401
 from .stream import stream_live_schedule, live_ring_slots, GazeStreamGroup, group_schedule  # noqa: F401
 from .stream import GazeLiveGroup, group_live_schedule  # noqa: F401
-from .ops import gaze_overlay, jet_table, audio_pixel_attn, attention_track, attention_rescale  # noqa: F401
+from .ops import gaze_overlay, gaze_overlay_yuv, jet_table, audio_pixel_attn, attention_track, attention_rescale  # noqa: F401
 
 __all__ = ["MODEL_REGISTRY", "build_model", "get_cfg", "load_yaml", "assert_and_infer_cfg", "GazePredictor", "GraphedEvalStep",
            "plan_video", "fill_track", "fill_plan", "default_max_gap", "points_to_source", "marker_centers", "gaze_overlay",
+           "gaze_overlay_yuv",
            "jet_table", "audio_pixel_attn", "attention_track", "attention_rescale", "fill_attention_track",
            "default_attention_gap", "GazeStream", "plan_stream", "stream_window", "stream_schedule", "track_from_windows",
            "stream_live_schedule", "live_ring_slots", "GazeStreamGroup", "group_schedule",

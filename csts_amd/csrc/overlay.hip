@@ -10,7 +10,9 @@
 // per row and column, never per pixel.  Then a wave walks one row at a time: on the vector path a lane owns 4 pixels = 12 bytes =
 // one 96-bit load and one 96-bit store (W % 4 == 0 keeps every row dword-aligned), on the byte path one pixel.  Both paths call
 // the same ov_shade(), so their bytes agree.  Rows that neither touch the crop nor the marker are copied (or skipped in place).
-#include "common.h"
+// gaze_overlay_yuv_kernel (below) draws the same picture onto 4:2:0 frames and writes 4:2:0 frames, through the same ov_axis and
+// ov_shade.
+#include "yuv_shared.h"
 
 namespace {
 
@@ -167,6 +169,317 @@ __global__ __launch_bounds__(256) void gaze_overlay_kernel(const uint8_t* frames
   }
 }
 
+// ---- the same picture drawn in 4:2:0 (NV12 / I420 in, the same layout out; include/csts_hip.h states the rule) ----------------------
+// 1.5 bytes in and 1.5 bytes out per pixel; the RGB picture exists only in registers.  A workgroup owns OVY_BAND pairs of luma rows
+// of one frame and the chroma rows those pairs share (nv12: chroma row cy belongs to row pair cy; i420: row cy of U and row cy of
+// V), so no workgroup reads a byte another one writes and in place is legal.  It stages map, alpha * JET, row and column entries as
+// gaze_overlay_kernel does (ovy_tables).  The unit of work is one 2 x 2 block (ovy_block): yuv_pixel on its four pixels, ov_shade /
+// the disc on the drawn ones, rgb_luma on the drawn ones, rgb_chroma on the sums if any is drawn.  Two kernels feed it:
+//   gaze_overlay_yuv_vec_kernel   W % 4 == 0, frames and out 4-byte aligned (what a decoder delivers): every luma row, every nv12
+//       chroma row starts on a dword and every i420 chroma row on a 2-byte word, so, like the vector path of gaze_overlay_kernel,
+//       a wave walks one row pair and a lane owns 4 pixels of both rows and their two chroma pairs: three 4-byte loads, two blocks,
+//       three 4-byte stores (i420: 2 + 2 bytes of chroma), no LDS traffic for the pixels and no barrier after the tables;
+//   gaze_overlay_yuv_kernel       any byte alignment (a recording inside a larger buffer, W = 2 mod 4): OVY_PAIRS row pairs of a
+//       tile at a time, the source bytes staged in LDS (yuv_stage: 16-byte chunks from any byte), a thread per block, the output
+//       bytes built in LDS images laid out from the output addresses and written back as 16-byte chunks (yuv_unstage; the ragged
+//       first and last chunk byte by byte, only bytes the workgroup owns).  All reads of a pass come before its barrier, all its
+//       writes after.
+// Both give the same bytes.  Row pairs that touch neither crop nor disc are copied, or skipped in place.
+// (Measured on 16 nv12 frames of 1088 x 1080: the staged kernel alone took 150 us against 114 us of yuv_to_rgb + gaze_overlay,
+// bound by its barrier phases at two workgroups a CU, not by bytes; hence the vector kernel.  tools/overlay_yuv_bench.py.)
+constexpr int OVY_BAND = 16;                     // row pairs per workgroup: OV_ROWS luma rows
+constexpr int OVY_PAIRS = 2;                     // row pairs per pass of the staged kernel
+constexpr int OVY_TW = 2048;                     // pixels of the widest tile of the staged kernel
+
+// what a workgroup knows about its frame: marker, crop (as gaze_overlay_kernel derives them from centers and params)
+struct OvyFrame {
+  int cX, cY, nh, nw, y0, x0;
+  bool marked, crop;
+};
+
+__device__ __forceinline__ OvyFrame ovy_frame(const int* __restrict__ centers, const int* __restrict__ params, int64_t n, int S) {
+  OvyFrame f;
+  f.cX = centers ? centers[2 * n] : 0;
+  f.cY = centers ? centers[2 * n + 1] : 0;
+  f.marked = centers && f.cX >= 0;
+  f.nh = params[0], f.nw = params[1], f.y0 = params[2], f.x0 = params[3];
+  f.crop = (!centers || f.cX >= 0) && f.nh >= S && f.nw >= S && f.nh <= (1 << 24) && f.nw <= (1 << 24) && f.y0 >= 0 && f.x0 >= 0 &&
+           f.y0 <= f.nh - S && f.x0 <= f.nw - S;
+  return f;
+}
+
+// The tables of a workgroup, staged by its 256 threads (no barrier inside): the frame's map m, alpha * JET(q), one entry per luma
+// row [Y0, Y0 + nrows) and one per column [X0, X0 + tw).  map, lut and cols are written only when the frame has a crop.
+__device__ __forceinline__ void ovy_tables(OvRow* rows, float* lut, float* map, uint2* cols, const float* __restrict__ m,
+                                           const OvyFrame& f, float alpha, int Y0, int nrows, int X0, int tw, int H, int W, int S,
+                                           int mh, int mw, int tid) {
+  if (f.crop) {                                                 // uniform over the workgroup
+    const int cells = mh * mw;
+    if ((cells & 3) == 0 && (reinterpret_cast<uintptr_t>(m) & 15) == 0) {
+      for (int k = tid * 4; k < cells; k += 256 * 4) *reinterpret_cast<float4*>(map + k) = *reinterpret_cast<const float4*>(m + k);
+    } else {
+      for (int k = tid; k < cells; k += 256) map[k] = m[k];
+    }
+    {                                                           // alpha * JET(q), q = tid
+      const int q4 = 4 * tid;
+      lut[3 * tid] = alpha * (float)min(max(383 - abs(q4 - 765), 0), 255);
+      lut[3 * tid + 1] = alpha * (float)min(max(383 - abs(q4 - 510), 0), 255);
+      lut[3 * tid + 2] = alpha * (float)min(max(383 - abs(q4 - 255), 0), 255);
+    }
+    for (int j = tid; j < tw; j += 256) {
+      const OvAxis a = ov_axis(X0 + j, W, f.nw, f.x0, S, mw);
+      cols[j] = a.inside ? make_uint2((uint32_t)a.i0 | ((uint32_t)a.i1 << 16), __float_as_uint(a.lam)) : make_uint2(OV_OUTSIDE, 0u);
+    }
+  }
+  if (tid < nrows) {
+    OvRow r = {OV_OUTSIDE, 0u, 0.f, 0};
+    if (f.crop) {
+      const OvAxis a = ov_axis(Y0 + tid, H, f.nh, f.y0, S, mh);
+      if (a.inside) r = {(uint32_t)(a.i0 * mw), (uint32_t)(a.i1 * mw), a.lam, 0};
+    }
+    rows[tid] = r;
+  }
+}
+
+// one pair of luma rows: uniform over whoever walks it
+struct OvyPair {
+  OvRow rw[2];
+  bool heat[2], disc[2], drawn;
+  int64_t dxm[2];                                               // the disc covers (X - cX)^2 <= dxm on that row
+};
+
+// rows: the entries of luma rows 2 cy and 2 cy + 1
+__device__ __forceinline__ OvyPair ovy_pair(const OvRow* rows, int cy, const OvyFrame& f, int radius) {
+  OvyPair p;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    p.rw[r] = rows[r];
+    p.heat[r] = p.rw[r].o0 != OV_OUTSIDE;
+    const int64_t dy = (int64_t)(2 * cy + r) - f.cY;
+    p.disc[r] = f.marked && dy >= -(int64_t)radius && dy <= (int64_t)radius;
+    p.dxm[r] = (int64_t)radius * radius - dy * dy;
+  }
+  p.drawn = p.heat[0] || p.heat[1] || p.disc[0] || p.disc[1];
+  return p;
+}
+
+// The 2 x 2 block at columns X, X + 1 (X even) of a drawn pair: Y[r][e], U, V come in as the source bytes and go out as the bytes to
+// write.  cols: the column entries, cols[0] that of column X (read only where a row has heat).
+__device__ __forceinline__ void ovy_block(int (&Y)[2][2], int& U, int& V, int X, const OvyPair& p, const uint2* cols, int cX,
+                                          int radius, const float* map, const float* lut, float oma, const YuvCoef& kf,
+                                          const RgbCoef& kr) {
+  uint2 col[2] = {make_uint2(OV_OUTSIDE, 0u), make_uint2(OV_OUTSIDE, 0u)};
+  if (p.heat[0] || p.heat[1]) {
+    col[0] = cols[0];
+    col[1] = cols[1];
+  }
+  bool dot[2][2], m[2][2];
+  bool any = false;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int64_t dx = (int64_t)(X + e) - cX;
+      dot[r][e] = p.disc[r] && dx >= -(int64_t)radius && dx <= (int64_t)radius && dx * dx <= p.dxm[r];
+      m[r][e] = dot[r][e] || (p.heat[r] && col[e].x != OV_OUTSIDE);
+      any = any || m[r][e];
+    }
+  }
+  if (!any) return;
+  int SR = 0, SG = 0, SB = 0;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      int R, G, B;
+      yuv_pixel(kf, Y[r][e], U, V, R, G, B);
+      if (m[r][e]) {
+        uint32_t px = (uint32_t)R | ((uint32_t)G << 8) | ((uint32_t)B << 16);
+        if (p.heat[r] && col[e].x != OV_OUTSIDE) px = ov_shade(px, p.rw[r], col[e], map, lut, oma);
+        if (dot[r][e]) px = 0x00ff00u;
+        R = (int)(px & 0xffu);
+        G = (int)((px >> 8) & 0xffu);
+        B = (int)((px >> 16) & 0xffu);
+        Y[r][e] = rgb_luma(kr, R, G, B);
+      }
+      SR += R;
+      SG += G;
+      SB += B;
+    }
+  }
+  rgb_chroma(kr, SR, SG, SB, U, V);
+}
+
+// grid N * bands, 256 threads; W % 4 == 0, frames and out 4-byte aligned.  Dynamic LDS: 2 OVY_BAND row entries, the JET table, the
+// map, W column entries.
+template <bool NV12>
+__global__ __launch_bounds__(256) void gaze_overlay_yuv_vec_kernel(const uint8_t* frames, uint8_t* out, const float* __restrict__ rescaled,
+                                                                   const int* __restrict__ centers, const int* __restrict__ params,
+                                                                   int bands, int H, int W, int S, int mh, int mw, float alpha,
+                                                                   int radius, YuvCoef kf, RgbCoef kr) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  OvRow* rows = reinterpret_cast<OvRow*>(lds);
+  float* lut = reinterpret_cast<float*>(rows + 2 * OVY_BAND);
+  float* map = lut + 256 * 3;                                   // 16-byte aligned
+  uint2* cols = reinterpret_cast<uint2*>(map + ((mh * mw + 3) & ~3));
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int64_t n = blockIdx.x / bands;
+  const int P0 = (blockIdx.x % bands) * OVY_BAND, npairs = min(OVY_BAND, (H >> 1) - P0);
+  const int hw = W >> 1;
+  const bool in_place = frames == out;
+  const OvyFrame f = ovy_frame(centers, params, n, S);
+  if (!f.crop && !f.marked && in_place) return;                 // uniform: nothing of this frame is drawn
+  ovy_tables(rows, lut, map, cols, rescaled + n * mh * mw, f, alpha, 2 * P0, 2 * npairs, 0, W, H, W, S, mh, mw, tid);
+  __syncthreads();
+
+  const float oma = 1.0f - alpha;
+  const int64_t f0 = n * yuv_frame_bytes(H, W), c0 = f0 + (int64_t)H * W, vplane = (int64_t)(H >> 1) * hw;
+  for (int pr = wv; pr < npairs; pr += 4) {                     // everything about the row pair is wave-uniform
+    const int cy = P0 + pr;
+    const OvyPair p = ovy_pair(rows + 2 * pr, cy, f, radius);
+    if (!p.drawn && in_place) continue;
+    const int64_t l0 = f0 + (int64_t)(2 * cy) * W, q0 = c0 + (int64_t)cy * (NV12 ? W : hw);
+    for (int g = lane; g < (W >> 2); g += 64) {
+      uint32_t a = *reinterpret_cast<const uint32_t*>(frames + l0 + 4 * g);
+      uint32_t b = *reinterpret_cast<const uint32_t*>(frames + l0 + W + 4 * g);
+      uint32_t c;                                               // U0 | V0 << 8 | U1 << 16 | V1 << 24
+      if (NV12) {
+        c = *reinterpret_cast<const uint32_t*>(frames + q0 + 4 * g);
+      } else {
+        const uint32_t u = *reinterpret_cast<const uint16_t*>(frames + q0 + 2 * g);
+        const uint32_t v = *reinterpret_cast<const uint16_t*>(frames + q0 + vplane + 2 * g);
+        c = (u & 0xffu) | ((v & 0xffu) << 8) | ((u >> 8) << 16) | ((v >> 8) << 24);
+      }
+      if (p.drawn) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          const int s = 16 * k;
+          int Y[2][2] = {{(int)((a >> s) & 0xffu), (int)((a >> (s + 8)) & 0xffu)}, {(int)((b >> s) & 0xffu), (int)((b >> (s + 8)) & 0xffu)}};
+          int U = (int)((c >> s) & 0xffu), V = (int)((c >> (s + 8)) & 0xffu);
+          ovy_block(Y, U, V, 4 * g + 2 * k, p, cols + 4 * g + 2 * k, f.cX, radius, map, lut, oma, kf, kr);
+          const uint32_t keep = ~(0xffffu << s);
+          a = (a & keep) | (((uint32_t)Y[0][0] | ((uint32_t)Y[0][1] << 8)) << s);
+          b = (b & keep) | (((uint32_t)Y[1][0] | ((uint32_t)Y[1][1] << 8)) << s);
+          c = (c & keep) | (((uint32_t)U | ((uint32_t)V << 8)) << s);
+        }
+      }
+      *reinterpret_cast<uint32_t*>(out + l0 + 4 * g) = a;
+      *reinterpret_cast<uint32_t*>(out + l0 + W + 4 * g) = b;
+      if (NV12) {
+        *reinterpret_cast<uint32_t*>(out + q0 + 4 * g) = c;
+      } else {
+        *reinterpret_cast<uint16_t*>(out + q0 + 2 * g) = (uint16_t)((c & 0xffu) | ((c >> 8) & 0xff00u));
+        *reinterpret_cast<uint16_t*>(out + q0 + vplane + 2 * g) = (uint16_t)(((c >> 8) & 0xffu) | ((c >> 16) & 0xff00u));
+      }
+    }
+  }
+}
+
+// LDS spans of one row pair of a tile of tw pixels: two luma rows of *lcap bytes, then the chroma: one interleaved row (nv12) or a
+// U and a V row of *ccap bytes each (i420), 2 * *ccap >= *lcap; returns the bytes of the pair
+__host__ __device__ inline int ovy_pair_bytes(int tw, int* lcap, int* ccap) {
+  *lcap = (tw + 30 + 15) / 16 * 16;
+  *ccap = (tw / 2 + 30 + 15) / 16 * 16;
+  return 2 * *lcap + 2 * *ccap;
+}
+
+// grid N * bands * xtiles, 256 threads.  src / dst: the addresses of frames / out rounded DOWN to 16 bytes, the tensors are the
+// bytes [lo, hi) / from olo on.  twn: pixels of a full tile (a multiple of 16).  Dynamic LDS: 2 OVY_BAND row entries, the JET table,
+// the map, twn column entries, OVY_PAIRS source spans and OVY_PAIRS images.
+__global__ __launch_bounds__(256) void gaze_overlay_yuv_kernel(const uint8_t* src, int64_t lo, int64_t hi, uint8_t* dst, int64_t olo,
+                                                               const float* __restrict__ rescaled, const int* __restrict__ centers,
+                                                               const int* __restrict__ params, int bands, int xtiles, int twn, int H,
+                                                               int W, int S, int mh, int mw, float alpha, int radius, int layout,
+                                                               YuvCoef kf, RgbCoef kr) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  OvRow* rows = reinterpret_cast<OvRow*>(lds);
+  float* lut = reinterpret_cast<float*>(rows + 2 * OVY_BAND);
+  float* map = lut + 256 * 3;                                   // 16-byte aligned
+  uint2* cols = reinterpret_cast<uint2*>(map + ((mh * mw + 3) & ~3));
+  int lcap, ccap;
+  const int pair_bytes = ovy_pair_bytes(twn, &lcap, &ccap);
+  uint8_t* in = reinterpret_cast<uint8_t*>(cols + twn);        // twn is even: 16-byte aligned
+  uint8_t* img = in + OVY_PAIRS * pair_bytes;
+  const int tid = threadIdx.x;
+  const int xt = blockIdx.x % xtiles, band = (blockIdx.x / xtiles) % bands;
+  const int64_t n = blockIdx.x / xtiles / bands;
+  const int x0 = xt * twn, tw = min(twn, W - x0), hw = W >> 1, ht = tw >> 1;
+  const int P0 = band * OVY_BAND, npairs = min(OVY_BAND, (H >> 1) - P0);
+  const bool nv12 = layout == CSTS_YUV_NV12;
+  const bool in_place = src == dst && lo == olo;
+  const int nspans = nv12 ? 3 : 4, cstep = nv12 ? 2 : 1;
+  const OvyFrame f = ovy_frame(centers, params, n, S);
+  if (!f.crop && !f.marked && in_place) return;                 // uniform: nothing of this frame is drawn
+  ovy_tables(rows, lut, map, cols, rescaled + n * mh * mw, f, alpha, 2 * P0, 2 * npairs, x0, tw, H, W, S, mh, mw, tid);
+  __syncthreads();
+
+  const float oma = 1.0f - alpha;
+  const int64_t fin = lo + n * yuv_frame_bytes(H, W), fout = olo + n * yuv_frame_bytes(H, W);
+  const int base[4] = {0, lcap, 2 * lcap, 2 * lcap + ccap};    // where the four spans of a pair lie in its LDS bytes
+  const int len[4] = {tw, tw, nv12 ? tw : ht, ht};
+  for (int pp = 0; pp < npairs; pp += OVY_PAIRS) {
+    const int nq = min(OVY_PAIRS, npairs - pp);
+    OvyPair pair[OVY_PAIRS];
+    bool live[OVY_PAIRS];
+    int sh[OVY_PAIRS][4];                                       // where the first byte of each staged span lies in in[]
+    int64_t o[OVY_PAIRS][4];                                    // where each output span starts, counted from dst
+#pragma unroll
+    for (int q = 0; q < OVY_PAIRS; ++q) {                       // everything about a row pair is uniform over the workgroup
+      live[q] = false;
+      if (q >= nq) continue;
+      const int cy = P0 + pp + q;
+      pair[q] = ovy_pair(rows + 2 * (pp + q), cy, f, radius);
+      live[q] = !in_place || pair[q].drawn;
+      if (!live[q]) continue;
+      const int64_t lum = (int64_t)(2 * cy) * W + x0, chr = (int64_t)H * W + (nv12 ? (int64_t)cy * W + x0 : (int64_t)cy * hw + (x0 >> 1));
+      const int64_t off[4] = {lum, lum + W, chr, chr + (int64_t)(H >> 1) * hw};
+      uint8_t* d = in + q * pair_bytes;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        o[q][k] = fout + off[k];
+        if (k < nspans) sh[q][k] = base[k] + yuv_stage(d + base[k], src, fin + off[k], fin + off[k] + len[k], lo, hi, tid, 256);
+      }
+      if (nv12) sh[q][3] = sh[q][2] + 1;                        // V follows U
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < OVY_PAIRS; ++q) {
+      if (!live[q]) continue;
+      const uint8_t* s = in + q * pair_bytes;
+      uint8_t* im = img + q * pair_bytes;
+      int os[4];                                                // where the first byte of each output span lies in its image
+#pragma unroll
+      for (int k = 0; k < 4; ++k) os[k] = base[k] + (int)(o[q][k] & 15);
+      if (nv12) os[3] = os[2] + 1;
+      for (int b = tid; b < ht; b += 256) {
+        int Y[2][2] = {{s[sh[q][0] + 2 * b], s[sh[q][0] + 2 * b + 1]}, {s[sh[q][1] + 2 * b], s[sh[q][1] + 2 * b + 1]}};
+        int U = s[sh[q][2] + b * cstep], V = s[sh[q][3] + b * cstep];
+        if (pair[q].drawn) ovy_block(Y, U, V, x0 + 2 * b, pair[q], cols + 2 * b, f.cX, radius, map, lut, oma, kf, kr);
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          im[os[r] + 2 * b] = (uint8_t)Y[r][0];
+          im[os[r] + 2 * b + 1] = (uint8_t)Y[r][1];
+        }
+        im[os[2] + b * cstep] = (uint8_t)U;
+        im[os[3] + b * cstep] = (uint8_t)V;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < OVY_PAIRS; ++q) {
+      if (!live[q]) continue;
+      const uint8_t* im = img + q * pair_bytes;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int b = (int)(o[q][k] & 15);
+        if (k < nspans) yuv_unstage(dst + (o[q][k] - b), im + base[k], b, b + len[k], tid, 256);
+      }
+    }
+    // no barrier here: the next pass stages into in[] (last read before the barrier above) and writes img[] only after its own
+    // barrier, which every thread reaches after it has finished this pass's write-back
+  }
+}
+
 }  // namespace
 
 extern "C" int csts_gaze_overlay(const uint8_t* frames_nhwc, const float* rescaled, const int* centers, const int* params,
@@ -188,6 +501,51 @@ extern "C" int csts_gaze_overlay(const uint8_t* frames_nhwc, const float* rescal
                               centers, params, out, (int)bands, H, W, S, mh, mw, alpha, radius);
   else hipLaunchKernelGGL(gaze_overlay_kernel<false>, dim3((unsigned)(N * bands)), dim3(256), lds, stream, frames_nhwc, rescaled,
                           centers, params, out, (int)bands, H, W, S, mh, mw, alpha, radius);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_gaze_overlay_yuv(const uint8_t* frames_yuv, const float* rescaled, const int* centers, const int* params,
+                                     uint8_t* out, int64_t N, int H, int W, int S, int mh, int mw, float alpha, int radius, int layout,
+                                     int matrix, int full_range, hipStream_t stream) {
+  CSTS_REQUIRE(frames_yuv && rescaled && params && out, "bad args (frames, rescaled, params and out must not be NULL)");
+  CSTS_REQUIRE(yuv_args_ok(layout, matrix), "layout must be CSTS_YUV_NV12 or CSTS_YUV_I420, matrix CSTS_YUV_BT601 or CSTS_YUV_BT709");
+  CSTS_REQUIRE(H >= 2 && W >= 2 && (H & 1) == 0 && (W & 1) == 0, "4:2:0 frames need even H, W >= 2");
+  CSTS_REQUIRE(N >= 1 && H <= 65534 && W <= OV_MAX_W && S >= 1 && S <= 4096, "bad sizes (N >= 1, H <= 65534, W <= 8192, S <= 4096)");
+  CSTS_REQUIRE(mh >= 1 && mw >= 1 && (int64_t)mh * mw <= CSTS_GAZE_DECODE_MAX_HW, "1 <= mh * mw <= CSTS_GAZE_DECODE_MAX_HW (the map is staged in LDS)");
+  CSTS_REQUIRE(alpha >= 0.f && alpha <= 1.f, "0 <= alpha <= 1");
+  CSTS_REQUIRE(radius >= 0, "radius >= 0");
+  const int64_t fb = yuv_frame_bytes(H, W);
+  CSTS_REQUIRE(N <= ((int64_t)1 << 62) / fb, "bad sizes (N H W 3 / 2 overflows)");
+  const int64_t bytes = N * fb;
+  CSTS_REQUIRE(out == frames_yuv || frames_yuv + bytes <= out || out + bytes <= frames_yuv,
+               "out must be the frames themselves (in place) or not overlap them");
+  const int64_t bands = cdiv(H / 2, OVY_BAND), xtiles = cdiv(W, OVY_TW);
+  CSTS_REQUIRE(N * bands * xtiles < ((int64_t)1 << 31), "N * ceil(H / 32) * ceil(W / 2048) must stay below 2^31");
+  const int tables = 2 * OVY_BAND * (int)sizeof(OvRow) + 256 * 3 * (int)sizeof(float) + ((mh * mw + 3) & ~3) * (int)sizeof(float);
+  const YuvCoef kf = yuv_coef(matrix, full_range);
+  const RgbCoef kr = rgb_coef(matrix, full_range);
+  if ((W & 3) == 0 && (reinterpret_cast<uintptr_t>(frames_yuv) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0) {
+    const int lds = tables + W * (int)sizeof(uint2);
+    const bool nv12 = layout == CSTS_YUV_NV12;
+    const void* fn = nv12 ? reinterpret_cast<const void*>(&gaze_overlay_yuv_vec_kernel<true>)
+                          : reinterpret_cast<const void*>(&gaze_overlay_yuv_vec_kernel<false>);
+    if (lds > 65536) CSTS_REQUIRE(csts_dyn_lds_optin(fn, lds), "LDS opt-in");
+    if (nv12) hipLaunchKernelGGL(gaze_overlay_yuv_vec_kernel<true>, dim3((unsigned)(N * bands)), dim3(256), lds, stream, frames_yuv,
+                                 out, rescaled, centers, params, (int)bands, H, W, S, mh, mw, alpha, radius, kf, kr);
+    else hipLaunchKernelGGL(gaze_overlay_yuv_vec_kernel<false>, dim3((unsigned)(N * bands)), dim3(256), lds, stream, frames_yuv, out,
+                            rescaled, centers, params, (int)bands, H, W, S, mh, mw, alpha, radius, kf, kr);
+    CSTS_LAUNCH_CHECK();
+    return 0;
+  }
+  const int twn = (int)((cdiv(W, xtiles) + 15) / 16 * 16);      // an even split of the row, <= OVY_TW
+  int lcap, ccap;
+  const int lds = tables + twn * (int)sizeof(uint2) + 2 * OVY_PAIRS * ovy_pair_bytes(twn, &lcap, &ccap);
+  if (lds > 65536) CSTS_REQUIRE(csts_dyn_lds_optin(reinterpret_cast<const void*>(&gaze_overlay_yuv_kernel), lds), "LDS opt-in");
+  const int64_t lo = (int64_t)(reinterpret_cast<uintptr_t>(frames_yuv) & 15), olo = (int64_t)(reinterpret_cast<uintptr_t>(out) & 15);
+  hipLaunchKernelGGL(gaze_overlay_yuv_kernel, dim3((unsigned)(N * bands * xtiles)), dim3(256), lds, stream, frames_yuv - lo, lo,
+                     lo + bytes, out - olo, olo, rescaled, centers, params, (int)bands, (int)xtiles, twn, H, W, S, mh, mw, alpha, radius,
+                     layout, kf, kr);
   CSTS_LAUNCH_CHECK();
   return 0;
 }

@@ -1,7 +1,7 @@
 // 4:2:0 YUV frames on the device: pictures the way video sources deliver them (NV12 from hardware decoders, I420 from software
 // ones), 1.5 bytes per pixel instead of the 3 of packed RGB.  include/csts_hip.h states the layouts and the integer colour rule;
 // yuv_pixel (yuv_shared.h) is its one implementation, run on the device by every kernel here and on the host by
-// csts_yuv_to_rgb_host.
+// csts_yuv_to_rgb_host; rgb_luma / rgb_chroma are the inverse rule, run by rgb_to_yuv here and by the 4:2:0 overlay (overlay.hip).
 //
 // yuv_to_rgb: the streaming converter (N, H * 3 / 2, W) -> (N, H, W, 3) for the consumers that draw RGB (the overlay renderers).
 // A workgroup owns one pair of luma rows of one tile of YUV_TW pixels and the chroma they share: it stages those source bytes in
@@ -9,6 +9,9 @@
 // LDS image of the two output rows laid out from the output address (any byte as well: a renderer converts into a chunk of its
 // output), and writes that image back as 16-byte chunks (the ragged first and last chunk of a row segment byte by byte: the
 // neighbouring workgroup owns the rest of them).
+//
+// rgb_to_yuv: the way back for the consumers that want 4:2:0 again (an encoder behind the overlay), by the inverse rule of the
+// header (rgb_luma / rgb_chroma, yuv_shared.h): the same tiles and the same staging, (N, H, W, 3) -> (N, H * 3 / 2, W).
 //
 // spatial / clip / batch_sample_yuv: the pixel pass of spatial.hip and batch.hip reading 4:2:0 pictures in place
 // (sample_rows_yuv, yuv_shared.h): bit for bit the RGB pass on the converted pictures, without the converted pictures.
@@ -89,6 +92,65 @@ __global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const uint8_t* __restri
         }
       }
     }
+    __syncthreads();                                            // the next frame reuses in[] and img[]
+  }
+}
+
+// rgb_to_yuv, the way back (rgb_luma / rgb_chroma, yuv_shared.h), with the staging of yuv_to_rgb_kernel turned round: a workgroup
+// owns the same row pair of the same tile, stages its 2 x 3 tw RGB bytes, and builds LDS images of the two luma segments and of
+// the chroma segment(s) (nv12: one interleaved, i420: one of U and one of V), each laid out from its output address.
+// grid (ceil(W / YUV_TW), H / 2, min(N, 65535)), 256 threads; src, lo, hi, out, olo as above.
+__global__ __launch_bounds__(256) void rgb_to_yuv_kernel(const uint8_t* __restrict__ src, int64_t lo, int64_t hi,
+                                                         uint8_t* __restrict__ out, int64_t olo, int64_t N, int H, int W, int layout,
+                                                         RgbCoef k) {
+  __shared__ __align__(16) uint8_t in[2][YUV_OUTCAP];
+  __shared__ __align__(16) uint8_t img[4][YUV_INCAP];
+  const int tid = threadIdx.x;
+  const int x0 = blockIdx.x * YUV_TW, tw = min(YUV_TW, W - x0), cy = blockIdx.y, hw = W >> 1;
+  const bool nv12 = layout == CSTS_YUV_NV12;
+  const int nspans = nv12 ? 3 : 4;
+  for (int64_t n = blockIdx.z; n < N; n += gridDim.z) {
+    const int64_t r0 = lo + (((int64_t)n * H + 2 * cy) * W + x0) * 3;
+    int sh[2];
+    sh[0] = yuv_stage(in[0], src, r0, r0 + 3 * tw, lo, hi, tid, 256);
+    sh[1] = yuv_stage(in[1], src, r0 + (int64_t)W * 3, r0 + (int64_t)W * 3 + 3 * tw, lo, hi, tid, 256);
+    __syncthreads();
+    // the four output segments: where each starts in out, how long it is, and where its first byte lies in its image
+    const int64_t f0 = olo + n * yuv_frame_bytes(H, W), c0 = f0 + (int64_t)H * W;
+    int64_t o[4];
+    int os[4], len[4];
+    o[0] = f0 + (int64_t)(2 * cy) * W + x0;
+    o[1] = o[0] + W;
+    o[2] = nv12 ? c0 + (int64_t)cy * W + x0 : c0 + (int64_t)cy * hw + (x0 >> 1);
+    o[3] = o[2] + (int64_t)(H >> 1) * hw;
+    len[0] = len[1] = tw;
+    len[2] = nv12 ? tw : tw >> 1;
+    len[3] = tw >> 1;
+    for (int s = 0; s < 4; ++s) os[s] = (int)(o[s] & 15);
+    for (int p = tid; p < (tw >> 1); p += 256) {
+      int SR = 0, SG = 0, SB = 0;
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const uint8_t* s = in[r] + sh[r] + 6 * p;
+        const int R0 = s[0], G0 = s[1], B0 = s[2], R1 = s[3], G1 = s[4], B1 = s[5];
+        img[r][os[r] + 2 * p] = (uint8_t)rgb_luma(k, R0, G0, B0);
+        img[r][os[r] + 2 * p + 1] = (uint8_t)rgb_luma(k, R1, G1, B1);
+        SR += R0 + R1;
+        SG += G0 + G1;
+        SB += B0 + B1;
+      }
+      int U, V;
+      rgb_chroma(k, SR, SG, SB, U, V);
+      if (nv12) {
+        img[2][os[2] + 2 * p] = (uint8_t)U;
+        img[2][os[2] + 2 * p + 1] = (uint8_t)V;
+      } else {
+        img[2][os[2] + p] = (uint8_t)U;
+        img[3][os[3] + p] = (uint8_t)V;
+      }
+    }
+    __syncthreads();
+    for (int s = 0; s < nspans; ++s) yuv_unstage(out + (o[s] - os[s]), img[s], os[s], os[s] + len[s], tid, 256);
     __syncthreads();                                            // the next frame reuses in[] and img[]
   }
 }
@@ -191,6 +253,59 @@ extern "C" int csts_yuv_to_rgb_host(const uint8_t* frames_yuv, uint8_t* out_nhwc
         d[0] = (uint8_t)R;
         d[1] = (uint8_t)G;
         d[2] = (uint8_t)B;
+      }
+    }
+  }
+  return 0;
+}
+
+extern "C" int csts_rgb_to_yuv(const uint8_t* frames_nhwc, uint8_t* out_yuv, int64_t N, int H, int W, int layout, int matrix,
+                               int full_range, hipStream_t stream) {
+  CSTS_REQUIRE(frames_nhwc && out_yuv, "bad args");
+  if (yuv_frame_check(N, H, W, layout, matrix)) return -1;
+  CSTS_REQUIRE(H <= 131070 && N <= ((int64_t)1 << 62) / ((int64_t)H * W * 3), "bad sizes (H <= 131070)");
+  const int64_t lo = (int64_t)(reinterpret_cast<uintptr_t>(frames_nhwc) & 15), bytes = N * H * W * 3;
+  const int64_t olo = (int64_t)(reinterpret_cast<uintptr_t>(out_yuv) & 15);
+  const uint8_t* a = frames_nhwc, *o = out_yuv;
+  CSTS_REQUIRE(a + bytes <= o || o + N * yuv_frame_bytes(H, W) <= a, "the output must not overlap the input");
+  hipLaunchKernelGGL(rgb_to_yuv_kernel, dim3((unsigned)cdiv(W, YUV_TW), H / 2, (unsigned)std::min<int64_t>(N, 65535)), dim3(256), 0,
+                     stream, frames_nhwc - lo, lo, lo + bytes, out_yuv - olo, olo, N, H, W, layout, rgb_coef(matrix, full_range));
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_rgb_to_yuv_host(const uint8_t* frames_nhwc, uint8_t* out_yuv, int64_t N, int H, int W, int layout, int matrix,
+                                    int full_range) {
+  CSTS_REQUIRE(frames_nhwc && out_yuv, "bad args");
+  if (yuv_frame_check(N, H, W, layout, matrix)) return -1;
+  const RgbCoef k = rgb_coef(matrix, full_range);
+  const int64_t fb = yuv_frame_bytes(H, W), hw = W / 2;
+  for (int64_t n = 0; n < N; ++n) {
+    const uint8_t* f = frames_nhwc + n * H * W * 3;
+    uint8_t* o = out_yuv + n * fb;
+    uint8_t* c = o + (int64_t)H * W;
+    for (int cy = 0; cy < H / 2; ++cy) {
+      for (int cx = 0; cx < hw; ++cx) {
+        int SR = 0, SG = 0, SB = 0;
+        for (int dy = 0; dy < 2; ++dy) {
+          for (int dx = 0; dx < 2; ++dx) {
+            const int64_t px = (int64_t)(2 * cy + dy) * W + 2 * cx + dx;
+            const int R = f[3 * px], G = f[3 * px + 1], B = f[3 * px + 2];
+            o[px] = (uint8_t)rgb_luma(k, R, G, B);
+            SR += R;
+            SG += G;
+            SB += B;
+          }
+        }
+        int U, V;
+        rgb_chroma(k, SR, SG, SB, U, V);
+        if (layout == CSTS_YUV_NV12) {
+          c[(int64_t)cy * W + 2 * cx] = (uint8_t)U;
+          c[(int64_t)cy * W + 2 * cx + 1] = (uint8_t)V;
+        } else {
+          c[cy * hw + cx] = (uint8_t)U;
+          c[(H / 2) * hw + cy * hw + cx] = (uint8_t)V;
+        }
       }
     }
   }

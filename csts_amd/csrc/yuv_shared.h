@@ -32,6 +32,31 @@ __host__ __device__ __forceinline__ void yuv_pixel(const YuvCoef& k, int Y, int 
   B = yuv_clamp8((y + k.cbu * u) >> 20);
 }
 
+// rgb_to_yuv, the inverse rule of include/csts_hip.h: {yr, yg, yb | ur, ug, ub | vr, vg, vb} = round(c * 2^20) of the real-valued
+// matrix of one (matrix, range) and the luma offset
+struct RgbCoef {
+  int yr, yg, yb, ur, ug, ub, vr, vg, vb, yoff;
+};
+
+inline RgbCoef rgb_coef(int matrix, int full_range) {
+  if (matrix == CSTS_YUV_BT709)
+    return full_range ? RgbCoef{222927, 749942, 75707, -120138, -404150, 524288, 524288, -476214, -48074, 0}
+                      : RgbCoef{191455, 644067, 65019, -105533, -355018, 460551, 460551, -418321, -42230, 16};
+  return full_range ? RgbCoef{313524, 615514, 119538, -176932, -347356, 524288, 524288, -439026, -85262, 0}
+                    : RgbCoef{269262, 528618, 102662, -155423, -305128, 460551, 460551, -385654, -74897, 16};
+}
+
+// luma of one pixel, R, G, B in [0, 255]; int32 throughout, >> arithmetic
+__host__ __device__ __forceinline__ int rgb_luma(const RgbCoef& k, int R, int G, int B) {
+  return yuv_clamp8(((k.yr * R + k.yg * G + k.yb * B + (1 << 19)) >> 20) + k.yoff);
+}
+
+// chroma of one 2 x 2 block from the sums of its four pixels, SR, SG, SB in [0, 1020] (|accumulator| <= 2^29 = 524288 * 1020 + 2^21)
+__host__ __device__ __forceinline__ void rgb_chroma(const RgbCoef& k, int SR, int SG, int SB, int& U, int& V) {
+  U = yuv_clamp8(((k.ur * SR + k.ug * SG + k.ub * SB + (1 << 21)) >> 22) + 128);
+  V = yuv_clamp8(((k.vr * SR + k.vg * SG + k.vb * SB + (1 << 21)) >> 22) + 128);
+}
+
 // bytes of one frame; H, W even
 __host__ __device__ __forceinline__ int64_t yuv_frame_bytes(int64_t H, int64_t W) { return H * W / 2 * 3; }
 
@@ -50,6 +75,20 @@ __device__ __forceinline__ int yuv_stage(uint8_t* __restrict__ dst, const uint8_
     }
   }
   return (int)(beg - a0);
+}
+
+// The way back: the bytes [beg, end) of img, an LDS image laid out from a 16-byte aligned global address g (byte c of img belongs
+// at g + c), written as 16-byte chunks; the ragged first and last chunk go byte by byte, so no byte outside [beg, end) is written
+// (a neighbouring workgroup owns those).  Called by `nthr` threads numbered `tid`.
+__device__ __forceinline__ void yuv_unstage(uint8_t* g, const uint8_t* img, int beg, int end, int tid, int nthr) {
+  for (int c = tid * 16; c < end; c += nthr * 16) {
+    if (c >= beg && c + 16 <= end) {
+      *reinterpret_cast<uint4*>(g + c) = *reinterpret_cast<const uint4*>(img + c);
+    } else {
+      for (int q = 0; q < 16; ++q)
+        if (c + q >= beg && c + q < end) g[c + q] = img[c + q];
+    }
+  }
 }
 
 // dynamic LDS of a 4:2:0 sample launch for source rows of up to W pixels.  Per wave: two luma rows of lcap bytes, then the chroma of

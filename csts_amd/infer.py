@@ -350,6 +350,41 @@ def _render_out(frames, out, H, W, fmt):
     return torch.empty(shape, dtype=torch.uint8, device=frames.device) if out is None else out
 
 
+OVERLAY_FORMATS = (None, "rgb24", "nv12", "i420")
+
+
+def _overlay_yuv(out_format, fmt, what="out_format"):
+    """Whether a renderer draws in 4:2:0 (ops.gaze_overlay_yuv): False for None / "rgb24", True for "nv12" / "i420" on frames of
+    that very layout (fmt: the format keywords of _picture_hw, {} for packed RGB).  ValueError for anything else."""
+    if out_format is None or out_format == "rgb24":
+        return False
+    if out_format not in OVERLAY_FORMATS:
+        raise ValueError(f"{what} must be None, 'rgb24', 'nv12' or 'i420', got {out_format!r}")
+    if not fmt:
+        raise ValueError(f"{what}={out_format!r} needs frames in that layout (pixel_format={out_format!r}), these are packed RGB: "
+                         "RGB in with 4:2:0 out is inputs.rgb_to_yuv of the RGB overlay")
+    if fmt["pixel_format"] != out_format:
+        raise ValueError(f"{what}={out_format!r} must be the layout of the frames, pixel_format={fmt['pixel_format']!r}: the overlay "
+                         "is drawn in the format the frames came in, mixed layouts are not supported")
+    return True
+
+
+def _render_out_yuv(frames, out):
+    """The tensor a 4:2:0 renderer draws into: a fresh one of the frames' shape unless `out` is given; `out` may be the frames
+    themselves (in place) and must otherwise share no memory with them."""
+    if not frames.is_contiguous():
+        raise ValueError("frames must be contiguous")
+    if out is None:
+        return torch.empty_like(frames)
+    if (not torch.is_tensor(out) or out.shape != frames.shape or out.dtype != torch.uint8 or not out.is_contiguous() or
+            not out.is_cuda):
+        raise ValueError(f"out must be a contiguous uint8 {tuple(frames.shape)} GPU tensor")
+    a, b, n = frames.data_ptr(), out.data_ptr(), frames.numel()
+    if a != b and a < b + n and b < a + n:
+        raise ValueError("out must be the frames themselves (in place) or share no memory with them")
+    return out
+
+
 def _check_rate(sample_rate):
     from .inputs import check_sample_rate
     return check_sample_rate(sample_rate)
@@ -485,7 +520,8 @@ class GazePredictor:
         return res
 
     def stream(self, fps=None, stride=None, segment=None, batch=1, max_chunk=32, pixel_format="rgb24", matrix="bt601",
-               full_range=False, sample_rate=None, input_rate=None, live=None, max_gap=None, overlay=False, alpha=0.4, radius=5):
+               full_range=False, sample_rate=None, input_rate=None, live=None, max_gap=None, overlay=False, alpha=0.4, radius=5,
+               overlay_format=None):
         """A live stream on this predictor (csts_amd.stream.GazeStream): push(frames, wav) takes frames and 24 kHz audio in whatever
         pieces they arrive and returns the windows each piece completes; close() ends it.  The windows are plan_stream's (fps an
         int or a Fraction, stride in frames); `batch` windows run per predict_batch call; `max_chunk` sizes the two device rings,
@@ -501,7 +537,8 @@ class GazePredictor:
         from .stream import GazeStream
         return GazeStream(self, fps=fps, stride=stride, segment=segment, batch=batch, max_chunk=max_chunk,
                           pixel_format=pixel_format, matrix=matrix, full_range=full_range, sample_rate=sample_rate,
-                          input_rate=input_rate, live=live, max_gap=max_gap, overlay=overlay, alpha=alpha, radius=radius)
+                          input_rate=input_rate, live=live, max_gap=max_gap, overlay=overlay, alpha=alpha, radius=radius,
+                          overlay_format=overlay_format)
 
     def stream_group(self, streams, fps=None, stride=None, segment=None, batch=4, max_chunk=32, pixel_format="rgb24",
                      matrix="bt601", full_range=False, input_rate=None):
@@ -517,7 +554,8 @@ class GazePredictor:
                                pixel_format=pixel_format, matrix=matrix, full_range=full_range, input_rate=input_rate)
 
     def live_group(self, streams, live, fps=None, stride=None, segment=None, batch=4, max_chunk=32, pixel_format="rgb24",
-                   matrix="bt601", full_range=False, input_rate=None, max_gap=None, overlay=False, alpha=0.4, radius=5):
+                   matrix="bt601", full_range=False, input_rate=None, max_gap=None, overlay=False, alpha=0.4, radius=5,
+                   overlay_format=None):
         """stream_group() with the live track of stream(live=...) on every slot (csts_amd.stream.GazeLiveGroup, forecast plans):
         push_live({slot: (frames, wav)}) is one tick and returns (windows, {slot: the push_live dict of that slot's frames}) --
         every pushed frame of every slot answered with its row of a gaze track computed from the windows of its own slot that
@@ -528,7 +566,7 @@ class GazePredictor:
         from .stream import GazeLiveGroup
         return GazeLiveGroup(self, streams, live, fps=fps, stride=stride, segment=segment, batch=batch, max_chunk=max_chunk,
                              pixel_format=pixel_format, matrix=matrix, full_range=full_range, input_rate=input_rate,
-                             max_gap=max_gap, overlay=overlay, alpha=alpha, radius=radius)
+                             max_gap=max_gap, overlay=overlay, alpha=alpha, radius=radius, overlay_format=overlay_format)
 
     @torch.no_grad()
     def _video_params_row(self, H, W):
@@ -543,21 +581,28 @@ class GazePredictor:
 
     @torch.no_grad()
     def render_track(self, frames_u8, track, alpha=0.4, radius=5, out=None, chunk=None, *, pixel_format="rgb24", matrix="bt601",
-                     full_range=False):
+                     full_range=False, out_format=None):
         """The track of predict_video drawn onto its recording: frames_u8 uint8 (N, H, W, 3) on the device and the dict
         predict_video returned (it must hold "rescaled" and "points") -> uint8 (N, H, W, 3): the heat map of every predicted
         frame blended over the crop the model saw and a disc at the gaze point (ops.gaze_overlay, csts_gaze_overlay); frames no
         window predicts (NaN points) come back as they are.  The crop is the one predict_video sampled: identity for S x S
         sources, else short side to S and centre crop.  chunk: frames per kernel launch (default: all).  out=frames_u8 renders
         in place.  pixel_format "nv12" | "i420": frames_u8 is the 4:2:0 recording uint8 (N, H * 3 / 2, W); each chunk is converted
-        into `out` (inputs.yuv_to_rgb) and drawn over there, so the result is RGB as above and out must not alias the input."""
+        into `out` (inputs.yuv_to_rgb) and drawn over there, so the result is RGB as above and out must not alias the input.
+        out_format: None / "rgb24" (the RGB result above), or the frames' own 4:2:0 layout ("nv12" | "i420", equal to
+        pixel_format; matrix and range are the input's): the overlay is drawn in that format (ops.gaze_overlay_yuv), the result
+        is uint8 (N, H * 3 / 2, W) -- where(drawn, rgb_to_yuv(the RGB result), frames), see include/csts_hip.h -- and
+        out=frames_u8 renders in place."""
         if not torch.is_tensor(frames_u8) or not frames_u8.is_cuda:
             raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
         if "rescaled" not in track or "points" not in track:
             raise ValueError("render_track needs the track's \"rescaled\" and \"points\": call predict_video with return_heatmaps=True")
         H, W, fmt = _picture_hw(frames_u8, 1, pixel_format, matrix, full_range)
         N = frames_u8.shape[0]
-        if fmt:
+        yuv_out = _overlay_yuv(out_format, fmt)
+        if yuv_out:
+            out = _render_out_yuv(frames_u8, out)
+        elif fmt:
             out = _render_out(frames_u8, out, H, W, fmt)
         if track["rescaled"].shape[0] != N or tuple(track["points"].shape) != (N, 2):
             raise ValueError(f"the track holds {track['rescaled'].shape[0]} frames, the recording {N}")
@@ -574,6 +619,10 @@ class GazePredictor:
             from . import inputs
             for a in range(0, N, step):
                 sel = slice(a, min(a + step, N))
+                if yuv_out:
+                    ops.gaze_overlay_yuv(frames_u8[sel], track["rescaled"][sel], params, S, centers=centers[sel], alpha=alpha,
+                                         radius=radius, out=out[sel], **fmt)
+                    continue
                 src = inputs.yuv_to_rgb(frames_u8[sel], out=out[sel], **fmt) if fmt else frames_u8[sel]
                 ops.gaze_overlay(src, track["rescaled"][sel], params, S, centers=centers[sel], alpha=alpha,
                                  radius=radius, out=out[sel])
@@ -581,14 +630,16 @@ class GazePredictor:
 
     @torch.no_grad()
     def render_attention(self, frames_u8, result, head=None, alpha=0.4, radius=5, points=None, out=None, *, pixel_format="rgb24",
-                         matrix="bt601", full_range=False):
+                         matrix="bt601", full_range=False, out_format=None):
         """The fusion attention maps of predict(attention=True) drawn onto the clip: frames_u8 uint8 (B, T, H, W, 3) on the device
         (the frames that were predicted) and the result dict (it must hold "attention_maps") -> uint8 (B, T, H, W, 3): the map
         of `head` (None: the head mean) of every input frame blended over the crop the model saw -- one ops.gaze_overlay call
         over the B * T frames.  The crop is predict()'s: identity for S x S frames, else short side to S and centre crop.
         points (optional, (B, T, 2) on the crop, e.g. result["points"]): a disc of `radius` pixels at each (NaN: that frame comes
         back untouched).  out=frames_u8 renders in place.  pixel_format "nv12" | "i420": frames_u8 is uint8 (B, T, H * 3 / 2, W); the
-        frames are converted into `out` (inputs.yuv_to_rgb) and drawn over there: out must not alias the input."""
+        frames are converted into `out` (inputs.yuv_to_rgb) and drawn over there: out must not alias the input.  out_format: as
+        render_track takes it; in the frames' own 4:2:0 layout the result is uint8 (B, T, H * 3 / 2, W) and out=frames_u8 is
+        allowed."""
         if not torch.is_tensor(frames_u8) or not frames_u8.is_cuda:
             raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
         if "attention_maps" not in result:
@@ -604,7 +655,10 @@ class GazePredictor:
         g = nheads if head is None else int(head)
         if head is not None and not 0 <= g < nheads:
             raise ValueError(f"head must be None (the head mean) or lie in [0, {nheads}), got {head!r}")
-        if fmt:
+        yuv_out = _overlay_yuv(out_format, fmt)
+        if yuv_out:
+            out = _render_out_yuv(frames_u8, out)
+        elif fmt:
             out = _render_out(frames_u8, out, H, W, fmt)
         elif out is not None and (out.shape != frames_u8.shape or out.dtype != torch.uint8 or not out.is_contiguous()):
             raise ValueError(f"out must be contiguous uint8 {tuple(frames_u8.shape)}, got {tuple(out.shape)} {out.dtype}")
@@ -619,18 +673,23 @@ class GazePredictor:
                 centers = marker_centers(points_to_source(points.reshape(B * T, 2), row, S), H, W)
             if out is None:
                 out = torch.empty_like(frames_u8)
+            picture = maps[:, g].reshape(B * T, maps.shape[3], maps.shape[4])
+            if yuv_out:
+                ops.gaze_overlay_yuv(frames_u8.view(B * T, H * 3 // 2, W), picture, params, S, centers=centers, alpha=alpha,
+                                     radius=radius, out=out.view(B * T, H * 3 // 2, W), **fmt)
+                return out
             if fmt:
                 from . import inputs
                 src = inputs.yuv_to_rgb(frames_u8, out=out, **fmt)
             else:
                 src = frames_u8
-            ops.gaze_overlay(src.view(B * T, H, W, 3), maps[:, g].reshape(B * T, maps.shape[3], maps.shape[4]), params, S,
+            ops.gaze_overlay(src.view(B * T, H, W, 3), picture, params, S,
                              centers=centers, alpha=alpha, radius=radius, out=out.view(B * T, H, W, 3))
         return out
 
     @torch.no_grad()
     def render_attention_track(self, frames_u8, track, head=None, alpha=0.4, radius=5, points=None, out=None, chunk=None, *,
-                               pixel_format="rgb24", matrix="bt601", full_range=False):
+                               pixel_format="rgb24", matrix="bt601", full_range=False, out_format=None):
         """The attention track of predict_video(attention_track=True) drawn onto its recording: frames_u8 uint8 (N, H, W, 3) on
         the device and the track (it must hold "attention_maps" and "attention_count") -> uint8 (N, H, W, 3): on every frame a
         pair landed on, or the fill reached ("attention_filled"), the map of `head` (None: the head mean) blended over the crop
@@ -638,7 +697,9 @@ class GazePredictor:
         (N, 2) on the crop, e.g. the gaze track's "points"): a disc of `radius` pixels where the point is finite; a drawn frame
         without a point gets no disc (its marker centre lies radius + 1 pixels right of the frame).  chunk: frames per launch
         (default: all).  out=frames_u8 renders in place.  pixel_format "nv12" | "i420": frames_u8 is the 4:2:0 recording uint8
-        (N, H * 3 / 2, W); each chunk is converted into `out` (inputs.yuv_to_rgb) and drawn over there: out must not alias it."""
+        (N, H * 3 / 2, W); each chunk is converted into `out` (inputs.yuv_to_rgb) and drawn over there: out must not alias it.
+        out_format: as render_track takes it; in the frames' own 4:2:0 layout the result is uint8 (N, H * 3 / 2, W) and
+        out=frames_u8 is allowed."""
         if not torch.is_tensor(frames_u8) or not frames_u8.is_cuda:
             raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
         if "attention_maps" not in track or "attention_count" not in track:
@@ -646,7 +707,10 @@ class GazePredictor:
                              "with attention_track=True")
         H, W, fmt = _picture_hw(frames_u8, 1, pixel_format, matrix, full_range)
         N = frames_u8.shape[0]
-        if fmt:
+        yuv_out = _overlay_yuv(out_format, fmt)
+        if yuv_out:
+            out = _render_out_yuv(frames_u8, out)
+        elif fmt:
             out = _render_out(frames_u8, out, H, W, fmt)
         maps, count = track["attention_maps"], track["attention_count"]
         if maps.dim() != 4 or maps.shape[0] != N or tuple(count.shape) != (N,):
@@ -680,6 +744,10 @@ class GazePredictor:
             from . import inputs
             for a in range(0, N, step):
                 sel = slice(a, min(a + step, N))
+                if yuv_out:
+                    ops.gaze_overlay_yuv(frames_u8[sel], picture[sel], params, S, centers=centers[sel], alpha=alpha, radius=radius,
+                                         out=out[sel], **fmt)
+                    continue
                 src = inputs.yuv_to_rgb(frames_u8[sel], out=out[sel], **fmt) if fmt else frames_u8[sel]
                 ops.gaze_overlay(src, picture[sel], params, S, centers=centers[sel], alpha=alpha, radius=radius,
                                  out=out[sel])
@@ -688,7 +756,7 @@ class GazePredictor:
     @torch.no_grad()
     def predict_video(self, frames_u8, wav, fps=None, stride=None, batch=None, return_heatmaps=True, overlay=False, fill=None,
                       max_gap=None, attention_track=False, sample_rate=None, *, pixel_format="rgb24", matrix="bt601",
-                      full_range=False):
+                      full_range=False, overlay_format=None):
         """A whole recording in, one gaze track out: frames_u8 uint8 (N, H, W, 3) and wav fp32 (n,) at 24 kHz, both resident on
         the device -> {"points": (N, 2), "peak": (N,), "count": (N,) int32 = windows that predicted the frame, "heatmaps" and
         "rescaled": (N, S/4, S/4) (left out with return_heatmaps=False), "windows": their number}, on the device.
@@ -727,8 +795,9 @@ class GazePredictor:
 
         pixel_format "nv12" | "i420" (with matrix "bt601" | "bt709", full_range): frames_u8 is the 4:2:0 recording uint8
         (N, H * 3 / 2, W), half the bytes of RGB; the windows are sampled straight out of it (inputs.clip_sample in that format,
-        no RGB copy of the recording) and every entry equals, bit for bit, that of the converted recording.  "overlay" stays
-        RGB uint8 (N, H, W, 3)."""
+        no RGB copy of the recording) and every entry equals, bit for bit, that of the converted recording.  "overlay" is
+        RGB uint8 (N, H, W, 3) unless overlay_format names the recording's own layout ("nv12" | "i420"; needs overlay=True):
+        then it is drawn in that format, uint8 (N, H * 3 / 2, W) (render_track(out_format=...))."""
         if fill not in (None, "hold", "linear"):
             raise ValueError(f"fill must be None, \"hold\" or \"linear\", got {fill!r}")
         if fill is None and max_gap is not None:
@@ -738,6 +807,9 @@ class GazePredictor:
                 raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
         from . import inputs
         H, W, fmt = _picture_hw(frames_u8, 1, pixel_format, matrix, full_range)
+        if overlay_format is not None and not overlay:
+            raise ValueError("overlay_format belongs to the overlay: pass overlay=True")
+        _overlay_yuv(overlay_format, fmt, "overlay_format")
         _check_video_wav(wav, sample_rate)
         if sample_rate is not None:
             with torch.cuda.device(self.device):
@@ -800,7 +872,7 @@ class GazePredictor:
                     track = fill_attention_track(track, mode=fill, max_gap=max_gap, plan=plan)
             if overlay:
                 track["points_source"] = points_to_source(track["points"], row, S)
-                track["overlay"] = self.render_track(frames_u8, track, **fmt)
+                track["overlay"] = self.render_track(frames_u8, track, out_format=overlay_format, **fmt)
             if not return_heatmaps and "heatmaps" in track:
                 del track["heatmaps"], track["rescaled"]
         track["windows"] = nwin

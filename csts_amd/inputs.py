@@ -434,6 +434,77 @@ def yuv_to_rgb_host(frames_yuv, pixel_format: str, matrix: str = "bt601", full_r
     return out
 
 
+# {YR, YG, YB, UR, UG, UB, VR, VG, VB} = round(c * 2^20) of (matrix, full_range): the inverse tables of include/csts_hip.h, restated
+RGB_TABLES = {("bt601", False): (269262, 528618, 102662, -155423, -305128, 460551, 460551, -385654, -74897),
+              ("bt601", True): (313524, 615514, 119538, -176932, -347356, 524288, 524288, -439026, -85262),
+              ("bt709", False): (191455, 644067, 65019, -105533, -355018, 460551, 460551, -418321, -42230),
+              ("bt709", True): (222927, 749942, 75707, -120138, -404150, 524288, 524288, -476214, -48074)}
+
+
+def _rgb_hw(shape, what="frames"):
+    """lead, H, W of packed RGB pictures (..., H, W, 3) that are to become 4:2:0 ones: ValueError for another shape, odd H or W."""
+    if len(shape) < 3 or int(shape[-1]) != 3:
+        raise ValueError(f"{what} must be uint8 (..., H, W, 3) packed RGB, got {tuple(shape)}")
+    H, W = int(shape[-3]), int(shape[-2])
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError(f"4:2:0 pictures need even H and W, got H {H}, W {W}")
+    return tuple(int(d) for d in shape[:-3]), H, W
+
+
+def rgb_to_yuv(frames_u8: torch.Tensor, pixel_format: str, matrix: str = "bt601", full_range: bool = False,
+               out: torch.Tensor = None) -> torch.Tensor:
+    """Packed RGB uint8 (..., H, W, 3), H and W even -> 4:2:0 pictures uint8 (..., H * 3 / 2, W) in `pixel_format` ("nv12" |
+    "i420") by the inverse integer rule of include/csts_hip.h (luma per pixel, chroma from the sums of each 2 x 2 block; `matrix`
+    "bt601" | "bt709", limited range unless full_range), one streaming launch (csts_rgb_to_yuv).  The input may start at any
+    byte.  out: a contiguous uint8 (..., H * 3 / 2, W) GPU tensor to write into, at any byte as well; it must not share memory
+    with the input."""
+    layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
+    if layout == 0:
+        raise ValueError("rgb_to_yuv writes 'nv12' or 'i420' pictures; rgb24 needs no conversion")
+    if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8:
+        raise ValueError(f"frames must be a uint8 tensor (..., H, W, 3), got {getattr(frames_u8, 'dtype', type(frames_u8))}")
+    lead, H, W = _rgb_hw(frames_u8.shape)
+    N = 1
+    for d in lead:
+        N *= d
+    if N < 1:
+        raise ValueError(f"frames hold no picture: {tuple(frames_u8.shape)}")
+    shape = lead + (H * 3 // 2, W)
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != shape or
+                            not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous uint8 {shape} tensor")
+    _gpu(frames_u8)
+    x = frames_u8.contiguous()
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+    else:
+        _gpu(out)
+        a, b = x.data_ptr(), out.data_ptr()
+        if out.device != x.device or (a < b + out.numel() and b < a + x.numel()):
+            raise ValueError("out must be on the frames' device and must not share memory with them")
+    with torch.cuda.device(x.device):
+        L.check(L.load().csts_rgb_to_yuv(x.data_ptr(), out.data_ptr(), N, H, W, layout, mat, fr, _s()), "csts_rgb_to_yuv")
+    return out
+
+
+def rgb_to_yuv_host(frames_u8, pixel_format: str, matrix: str = "bt601", full_range: bool = False):
+    """rgb_to_yuv on the CPU (csts_rgb_to_yuv_host, the same functions): numpy uint8 (..., H, W, 3) -> (..., H * 3 / 2, W)."""
+    import numpy as np
+    layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
+    if layout == 0:
+        raise ValueError("rgb_to_yuv_host writes 'nv12' or 'i420' pictures; rgb24 needs no conversion")
+    x = np.ascontiguousarray(frames_u8)
+    if x.dtype != np.uint8:
+        raise ValueError(f"frames must be uint8, got {x.dtype}")
+    lead, H, W = _rgb_hw(x.shape)
+    N = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    if N < 1:
+        raise ValueError(f"frames hold no picture: {x.shape}")
+    out = np.empty(lead + (H * 3 // 2, W), dtype=np.uint8)
+    L.check(L.load().csts_rgb_to_yuv_host(x.ctypes.data, out.ctypes.data, N, H, W, layout, mat, fr), "csts_rgb_to_yuv_host")
+    return out
+
+
 def spatial_sampling(frames_u8: torch.Tensor, labels: torch.Tensor, crop_size: int, *, train: bool, min_scale: int = 0,
                      max_scale: int = 0, spatial_idx: int = 1, random_flip: bool = True, inverse_uniform: bool = False,
                      mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225), generator=None, return_params: bool = False,

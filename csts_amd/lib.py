@@ -274,6 +274,8 @@ SYMBOLS = {
     "csts_resample_stream": (_I, [vp, _I, _I, i64, i64, i64, vp, _I, _I, _I, i64, i64, vp, vp]),
     "csts_yuv_to_rgb": (_I, [vp, vp, i64, _I, _I, _I, _I, _I, vp]),
     "csts_yuv_to_rgb_host": (_I, [vp, vp, i64, _I, _I, _I, _I, _I]),
+    "csts_rgb_to_yuv": (_I, [vp, vp, i64, _I, _I, _I, _I, _I, vp]),
+    "csts_rgb_to_yuv_host": (_I, [vp, vp, i64, _I, _I, _I, _I, _I]),
     "csts_spatial_sample_yuv": (_I, [vp, vp, vp, _I, _I, _I, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),
     "csts_clip_sample_yuv": (_I, [vp, i64, vp, vp, vp, _I, _I, _I, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),
     "csts_batch_sample_yuv": (_I, [vp, i64, vp, vp, vp, vp, _I, _I, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),
@@ -301,6 +303,7 @@ SYMBOLS = {
     "csts_gaze_track": (_I, [vp, vp, vp, i64, _I, _I, vp, vp, vp, vp, vp, vp]),
     "csts_gaze_track_fill": (_I, [vp, vp, i64, _I, _I, _I, _I, vp, vp, vp, vp, vp, vp]),
     "csts_gaze_overlay": (_I, [vp, vp, vp, vp, vp, i64, _I, _I, _I, _I, _I, _F, _I, vp]),
+    "csts_gaze_overlay_yuv": (_I, [vp, vp, vp, vp, vp, i64, _I, _I, _I, _I, _I, _F, _I, _I, _I, _I, vp]),
     "csts_audio_pixel_attn": (_I, [vp, _I, vp, _I, _I, _I, _I, _I, _I, _I, _I, _F, vp, vp, vp, vp, vp]),
     "csts_attention_track": (_I, [vp, vp, vp, i64, _I, _I, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp]),
     "csts_attention_rescale": (_I, [vp, vp, _I, i64, _I, _I, _I, vp, vp, vp]),

@@ -2845,6 +2845,51 @@ def gaze_overlay(frames_u8, rescaled, params, crop_size, centers=None, alpha=0.4
     return out
 
 
+def gaze_overlay_yuv(frames_yuv, rescaled, params, crop_size, pixel_format, matrix="bt601", full_range=False, centers=None,
+                     alpha=0.4, radius=5, out=None):
+    """csts_gaze_overlay_yuv: gaze_overlay drawn onto 4:2:0 frames uint8 (N, H * 3 / 2, W) in `pixel_format` ("nv12" | "i420",
+    with `matrix` and `full_range` as inputs.yuv_to_rgb takes them) -> uint8 of the same shape and layout, 1.5 bytes in and 1.5
+    out per pixel and no RGB picture in memory.  With D = gaze_overlay(inputs.yuv_to_rgb(frames), ...) and M the drawn mask
+    (inside the crop of a frame with centre X >= 0 or centers=None, or under the disc), out = where(M, inputs.rgb_to_yuv(D),
+    frames), M per pixel for luma and per 2 x 2 block (any) for chroma: an untouched frame, row pair or block comes back byte
+    for byte, and a drawn pixel is re-encoded even at alpha = 0.  Every other argument as gaze_overlay takes it; frames and out
+    may start at any byte; out=frames_yuv renders in place.  One launch, no host sync.  The rule is stated in
+    include/csts_hip.h."""
+    from .inputs import check_pixel_format, _yuv_hw
+    layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
+    if layout == 0:
+        raise ValueError("gaze_overlay_yuv draws 'nv12' or 'i420' frames; packed RGB goes through gaze_overlay")
+    _need_gpu(frames_yuv, rescaled, centers, out)
+    if frames_yuv.dtype != torch.uint8 or frames_yuv.dim() != 3:
+        raise ValueError(f"{pixel_format} frames must be uint8 (N, H * 3 / 2, W), got {tuple(frames_yuv.shape)} {frames_yuv.dtype}")
+    H, W = _yuv_hw(frames_yuv.shape, pixel_format)
+    N = frames_yuv.shape[0]
+    if rescaled.dtype != torch.float32 or rescaled.dim() != 3 or rescaled.shape[0] != N:
+        raise ValueError(f"rescaled must be fp32 ({N}, mh, mw), got {tuple(rescaled.shape)} {rescaled.dtype}")
+    if centers is not None and (centers.dtype != torch.int32 or tuple(centers.shape) != (N, 2)):
+        raise ValueError(f"centers must be int32 ({N}, 2), got {tuple(centers.shape)} {centers.dtype}")
+    alpha, radius, S = float(alpha), int(radius), int(crop_size)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha must lie in [0, 1], got {alpha}")
+    if radius < 0 or S < 1 or N < 1:
+        raise ValueError(f"gaze_overlay_yuv needs N >= 1 frames, crop_size >= 1 and radius >= 0, got {N}, {S} and {radius}")
+    if not frames_yuv.is_contiguous():
+        raise ValueError("frames must be contiguous (N, H * 3 / 2, W)")
+    if out is None:
+        out = torch.empty_like(frames_yuv)
+    elif out.dtype != torch.uint8 or out.shape != frames_yuv.shape or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous uint8 {tuple(frames_yuv.shape)}, got {tuple(out.shape)} {out.dtype}")
+    a, b, nbytes = frames_yuv.data_ptr(), out.data_ptr(), frames_yuv.numel()
+    if a != b and a < b + nbytes and b < a + nbytes:
+        raise ValueError("out must be the frames themselves (in place) or share no memory with them")
+    par = _overlay_params(params, S, frames_yuv.device)
+    maps = rescaled.detach().contiguous()
+    cen = None if centers is None else centers.contiguous()
+    L.check(_lib().csts_gaze_overlay_yuv(_p(frames_yuv), _p(maps), _p(cen), _p(par), _p(out), N, H, W, S, maps.shape[1],
+                                         maps.shape[2], alpha, radius, layout, mat, fr, _stream()), "csts_gaze_overlay_yuv")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- fusion attention maps
 def audio_pixel_attn(qkv, lse, thw, heads, n_frames, crop_size):
     """csts_audio_pixel_attn on what the spatial fusion block's forward holds: qkv (B, N, 3C) packed q | k | v rows (fp32 or the

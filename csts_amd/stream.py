@@ -347,7 +347,7 @@ class GazeStream:
 
     def __init__(self, predictor, fps=None, stride=None, segment=None, batch=1, max_chunk=32, pixel_format="rgb24",
                  matrix="bt601", full_range=False, sample_rate=None, input_rate=None, live=None, max_gap=None, overlay=False,
-                 alpha=0.4, radius=5):
+                 alpha=0.4, radius=5, overlay_format=None):
         check_stream_rate(sample_rate)
         if live is not None and live not in LIVE_MODES:
             raise ValueError(f"live must be None or one of {LIVE_MODES}, got {live!r}")
@@ -365,6 +365,11 @@ class GazeStream:
         self.fmt = {}
         if inputs.check_pixel_format(pixel_format, matrix, full_range)[0]:
             self.fmt = {"pixel_format": pixel_format, "matrix": matrix, "full_range": bool(full_range)}
+        if overlay_format is not None and not overlay:
+            raise ValueError("overlay_format belongs to the overlay: pass overlay=True")
+        from .infer import _overlay_yuv
+        # the overlay in the pushed frames' own 4:2:0 layout (render_track(out_format=...)) instead of RGB
+        self.overlay_format = overlay_format if _overlay_yuv(overlay_format, self.fmt, "overlay_format") else None
         self.batch, self.max_chunk = int(batch), int(max_chunk)
         if self.batch < 1 or self.max_chunk < 1:
             raise ValueError(f"batch and max_chunk must be positive, got {batch} and {max_chunk}")
@@ -514,7 +519,8 @@ class GazeStream:
         rows["known"] = torch.full((K,), self.next_window, dtype=torch.int32, device=dev)
         rows["points_source"] = points_to_source(rows["points"], self.predictor._video_params_row(*self.hw), self.S)
         if self.overlay:
-            rows["overlay"] = self.predictor.render_track(chunk, rows, alpha=self.alpha, radius=self.radius, **self.fmt)
+            rows["overlay"] = self.predictor.render_track(chunk, rows, alpha=self.alpha, radius=self.radius,
+                                                          out_format=self.overlay_format, **self.fmt)
         return rows
 
     def _live_empty(self, device):
@@ -528,7 +534,8 @@ class GazeStream:
         out = {k: torch.empty(shape, dtype=dt, device=device) for k, (shape, dt) in shapes.items()}
         if self.overlay:
             H, W = self.hw if self.hw is not None else (0, 0)
-            out["overlay"] = torch.empty((0, H, W, 3), dtype=torch.uint8, device=device)
+            shape = (0, H * 3 // 2, W) if self.overlay_format else (0, H, W, 3)
+            out["overlay"] = torch.empty(shape, dtype=torch.uint8, device=device)
         return out
 
     def _push(self, frames, wav, want_live):
@@ -1008,9 +1015,10 @@ class GazeLiveGroup(GazeStreamGroup):
     (tools/predict.py --videos still refuses --live and --overlay)."""
 
     def __init__(self, predictor, streams, live, fps=None, stride=None, segment=None, batch=4, max_chunk=32, pixel_format="rgb24",
-                 matrix="bt601", full_range=False, input_rate=None, max_gap=None, overlay=False, alpha=0.4, radius=5):
+                 matrix="bt601", full_range=False, input_rate=None, max_gap=None, overlay=False, alpha=0.4, radius=5,
+                 overlay_format=None):
         from . import ops
-        from .infer import default_max_gap
+        from .infer import default_max_gap, _overlay_yuv
         if live not in LIVE_MODES:
             raise ValueError(f"live must be one of {LIVE_MODES}, got {live!r}")
         plan = plan_stream(predictor.cfg, fps=fps, stride=stride, segment=segment)
@@ -1021,6 +1029,11 @@ class GazeLiveGroup(GazeStreamGroup):
             raise ValueError(f"max_gap must be positive, got {max_gap}")
         if not 0.0 <= self.alpha <= 1.0 or self.radius < 0:
             raise ValueError(f"alpha must lie in [0, 1] and radius be >= 0, got {alpha} and {radius}")
+        if overlay_format is not None and not overlay:
+            raise ValueError("overlay_format belongs to the overlay: pass overlay=True")
+        group_fmt = {"pixel_format": pixel_format} if pixel_format in ("nv12", "i420") else {}
+        # the overlay in the pushed frames' own 4:2:0 layout (render_track(out_format=...)) instead of RGB
+        self.overlay_format = overlay_format if _overlay_yuv(overlay_format, group_fmt, "overlay_format") else None
         super().__init__(predictor, streams, fps=fps, stride=stride, segment=segment, batch=batch, max_chunk=max_chunk,
                          pixel_format=pixel_format, matrix=matrix, full_range=full_range, input_rate=input_rate)
         self.track_slots = live_ring_slots(self.plan, self.max_chunk, self.max_gap)
@@ -1071,7 +1084,8 @@ class GazeLiveGroup(GazeStreamGroup):
         from .infer import points_to_source
         rows["points_source"] = points_to_source(rows["points"], self._rows[i], self.S)
         if self.overlay:
-            rows["overlay"] = self.predictor.render_track(chunk, rows, alpha=self.alpha, radius=self.radius, **self.fmt)
+            rows["overlay"] = self.predictor.render_track(chunk, rows, alpha=self.alpha, radius=self.radius,
+                                                          out_format=self.overlay_format, **self.fmt)
         return rows
 
     def _live_empty(self, i):
@@ -1085,7 +1099,8 @@ class GazeLiveGroup(GazeStreamGroup):
         out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
         if self.overlay:
             H, W = self.hw[i] if self.hw[i] is not None else (0, 0)
-            out["overlay"] = torch.empty((0, H, W, 3), dtype=torch.uint8, device=dev)
+            shape = (0, H * 3 // 2, W) if self.overlay_format else (0, H, W, 3)
+            out["overlay"] = torch.empty(shape, dtype=torch.uint8, device=dev)
         return out
 
     # ---- the interface ---------------------------------------------------------------------------------------------------------

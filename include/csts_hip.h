@@ -612,9 +612,30 @@ int csts_audio_gather(const float* spec_arena, const int64_t* specs, const int* 
  *        the RGB function on yuv_to_rgb of the pictures.  Every guarantee of the RGB functions holds: tables read on the DEVICE
  *        when the kernel runs, no host sync, no allocation, graph-capturable, bad params or a bad clip row give a NaN clip and
  *        read nothing, no byte at or past the end of the source is read, W <= 6000, source and out 16-byte aligned.  Odd H or W
- *        is refused (-1) where it is an argument and gives a NaN clip where it stands in a device table. */
+ *        is refused (-1) where it is an argument and gives a NaN clip where it stands in a device table.
+ *      The inverse rule, rgb_to_yuv (rgb_luma / rgb_chroma of yuv_shared.h), all int32, >> the arithmetic shift:
+ *        luma, per pixel:        Y = clamp(((YR R + YG G + YB B + 2^19) >> 20) + yoff, 0, 255)
+ *        chroma, per 2 x 2 block, SR, SG, SB = the sums of its four pixels per channel (0..1020) -- a box filter, the counterpart
+ *        of the nearest-chroma decode, where the four pixels share one pair:
+ *                                U = clamp(((UR SR + UG SG + UB SB + 2^21) >> 22) + 128, 0, 255),  V likewise with VR, VG, VB
+ *      {YR, YG, YB | UR, UG, UB | VR, VG, VB} = round(c 2^20) of the rationals c = {ty Kr, ty Kg, ty Kb | -tc Kr / (2 (1 - Kb)),
+ *      -tc Kg / (2 (1 - Kb)), tc / 2 | tc / 2, -tc Kg / (2 (1 - Kr)), -tc Kb / (2 (1 - Kr))}, ty = 219/255 and tc = 224/255
+ *      (limited) or 1 (full):
+ *        bt601 limited {269262, 528618, 102662 | -155423, -305128, 460551 | 460551, -385654, -74897}
+ *        bt601 full    {313524, 615514, 119538 | -176932, -347356, 524288 | 524288, -439026, -85262}
+ *        bt709 limited {191455, 644067, 65019 | -105533, -355018, 460551 | 460551, -418321, -42230}
+ *        bt709 full    {222927, 749942, 75707 | -120138, -404150, 524288 | 524288, -476214, -48074}
+ *      The accumulators stay within 2^29 (524288 * 1020 + 2^21) in magnitude and every output is within 1 of floor(real-valued matrix + 0.5) (a
+ *      coefficient is off by at most 2^-21 per term).  YUV -> RGB -> YUV is not the identity.
+ *      rgb_to_yuv: frames (N, H, W, 3) RGB -> out (N, H * 3 / 2, W) in `layout`, H and W even, one streaming pass with the
+ *        staging of yuv_to_rgb: input and output may start at any byte and must not overlap.  H <= 131070.  rgb_to_yuv_host:
+ *        the same functions over HOST memory. */
 enum { CSTS_YUV_NV12 = 1, CSTS_YUV_I420 = 2 };
 enum { CSTS_YUV_BT601 = 0, CSTS_YUV_BT709 = 1 };
+int csts_rgb_to_yuv(const uint8_t* frames_nhwc, uint8_t* out_yuv, int64_t N, int H, int W, int layout, int matrix, int full_range,
+                    hipStream_t stream);
+int csts_rgb_to_yuv_host(const uint8_t* frames_nhwc, uint8_t* out_yuv, int64_t N, int H, int W, int layout, int matrix,
+                         int full_range);
 int csts_yuv_to_rgb(const uint8_t* frames_yuv, uint8_t* out_nhwc, int64_t N, int H, int W, int layout, int matrix, int full_range,
                     hipStream_t stream);
 int csts_yuv_to_rgb_host(const uint8_t* frames_yuv, uint8_t* out_nhwc, int64_t N, int H, int W, int layout, int matrix,
@@ -777,6 +798,26 @@ int csts_gaze_track_fill(const float* heatmaps, const int* count, int64_t F, int
  *      S <= 4096, N * ceil(H / 32) < 2^31. */
 int csts_gaze_overlay(const uint8_t* frames_nhwc, const float* rescaled, const int* centers, const int* params, uint8_t* out,
                       int64_t N, int H, int W, int S, int mh, int mw, float alpha, int radius, hipStream_t stream);
+
+/* ---- gaze overlay in 4:2:0 (csts_amd/csrc/overlay.hip): the same picture drawn onto NV12 / I420 frames (the layouts and colour
+ *      rules of "4:2:0 YUV frames" above) and written in the same layout: 1.5 bytes in and 1.5 bytes out per pixel, no RGB picture
+ *      in memory.  frames_yuv and out (N, H * 3 / 2, W) uint8, at any byte; every other argument as csts_gaze_overlay takes it.
+ *      Let D be what csts_gaze_overlay gives on csts_yuv_to_rgb(frames_yuv), and M the drawn mask: a pixel is in M when it lies
+ *      inside the crop of a frame whose centre X is not negative (or centers is NULL), or under the disc -- geometry only,
+ *      whatever alpha and the pixel's value.  Then
+ *        luma of a pixel in M        = the luma rule of rgb_to_yuv on D at that pixel;   outside M = its source byte;
+ *        chroma of a 2 x 2 block with at least one pixel in M = the chroma rule on the sums of D over its four pixels (the undrawn
+ *                                      ones are the forward rule of their source bytes);   with none = its source bytes,
+ *      i.e. out = where(M, rgb_to_yuv(D), frames), M per pixel for luma and per block (any) for chroma.  The shaded RGB is that
+ *      of csts_gaze_overlay bit for bit (the same functions).  Consequences: an untouched frame, row pair or block comes back byte
+ *      for byte; a drawn pixel at alpha = 0 is re-encoded and may differ from its source luma (YUV -> RGB -> Y is not the
+ *      identity).  out == frames_yuv renders in place (a workgroup reads its bytes before it writes them and none reads bytes
+ *      another writes); any other overlap is refused (-1), as are odd H or W, W > 8192, H > 65534, mh * mw >
+ *      CSTS_GAZE_DECODE_MAX_HW, and nothing is written then.  One launch, no allocation, no host read: graph-capturable.
+ *      N * ceil(H / 32) * ceil(W / 2048) < 2^31. */
+int csts_gaze_overlay_yuv(const uint8_t* frames_yuv, const float* rescaled, const int* centers, const int* params, uint8_t* out,
+                          int64_t N, int H, int W, int S, int mh, int mw, float alpha, int radius, int layout, int matrix,
+                          int full_range, hipStream_t stream);
 
 /* ---- fusion attention maps (csts_amd/csrc/fusion_maps.hip): the audio-visual correlation map of the spatial fusion block, what
  *      vis_av_st_fusion of slowfast/visualization/visualization.py:172-228 draws per head: for every frame, how strongly each image

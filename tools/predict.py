@@ -45,8 +45,10 @@ were.
 4:2:0 pictures (--clip and --video): instead of frames_u8 the npz may hold frames_yuv uint8 (B, T, H * 3 / 2, W) / (N, H * 3 / 2, W)
 with a pixel_format entry ("nv12" or "i420") and optionally yuv_matrix ("bt601", the default, or "bt709") and yuv_full_range;
 --pixel-format, --yuv-matrix and --yuv-full-range override the entries.  The pictures are uploaded and sampled in that format
-(half the bytes of RGB); overlays stay RGB uint8 (N, H, W, 3).  An npz holding both frames_u8 and frames_yuv is an error.  The
-json_stats line then carries "pixel_format".
+(half the bytes of RGB); overlays are RGB uint8 (N, H, W, 3) unless --overlay-format nv12 | i420 names the recording's own layout:
+overlay / live_overlay are then drawn in that format, uint8 (N, H * 3 / 2, W) (GazePredictor.render_track(out_format=...)), --out
+gains the entry overlay_pixel_format, and --overlay-dir writes its PNGs from inputs.yuv_to_rgb_host of them.  An npz holding both
+frames_u8 and frames_yuv is an error.  The json_stats line then carries "pixel_format".
 --stream [--chunk K] (with --video): the recording is replayed through csts_amd.GazeStream (GazePredictor.stream) in pushes of K
 frames (default 8) with the matching audio -- the samples up to frame_end * 24000 / fps, the rest with the last push -- as a live
 source would deliver it, and closed.  --out receives the same entries as --video, the track folded from the emitted windows by
@@ -83,6 +85,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from csts_amd.config import assert_and_infer_cfg, load_yaml      # noqa: E402
 from csts_amd.infer import GazePredictor                         # noqa: E402
+from csts_amd import inputs                                      # noqa: E402
 from csts_amd.inputs import AUDIO_RATE                           # noqa: E402
 
 CLIP_KEYS = ("frames_u8", "wav", "frames_idx", "frame_length")
@@ -102,6 +105,8 @@ def parse_args(argv=None):
     p.add_argument("--overlay", action="store_true", help="with --video: add points_source and the rendered overlay to --out")
     p.add_argument("--overlay-dir", default=None, type=str, help="with --video: also write overlay frames as PNGs here (implies --overlay)")
     p.add_argument("--overlay-every", default=1, type=int, help="write every K-th frame to --overlay-dir")
+    p.add_argument("--overlay-format", default=None, choices=("rgb24", "nv12", "i420"),
+                   help="with --overlay on a 4:2:0 recording: draw the overlay in the recording's own layout instead of RGB")
     p.add_argument("--fill", default=None, choices=["hold", "linear"], help="with --video: fill the frames between predictions")
     p.add_argument("--max-gap", default=None, type=int, help="with --fill: widest distance between two predictions that is filled")
     p.add_argument("--attention", action="store_true", help="add the fusion attention maps to --out (one clip, not --video)")
@@ -166,6 +171,8 @@ def parse_args(argv=None):
         p.error("--max-gap must be positive")
     if args.overlay_every < 1:
         p.error("--overlay-every must be positive")
+    if args.overlay_format is not None and not (args.overlay or args.overlay_dir):
+        p.error("--overlay-format names the format of the overlay: it needs --overlay or --overlay-dir")
     if args.stream and args.video is None and args.videos is None:
         p.error("--stream replays a recording as a live stream: it needs --video")
     if args.chunk is not None and not args.stream:
@@ -222,14 +229,16 @@ def waveform(z, rate, dev):
     return (wav if rate is not None and wav.dtype == torch.int16 else wav.float()).to(dev)
 
 
-def replay_stream(predictor, frames, wav, fps, stride, chunk, fmt, rate=None, live=None, max_gap=None, overlay=False):
+def replay_stream(predictor, frames, wav, fps, stride, chunk, fmt, rate=None, live=None, max_gap=None, overlay=False,
+                  overlay_format=None):
     """The recording pushed through GazePredictor.stream in pushes of `chunk` frames with the matching audio, then closed ->
     (the track by track_from_windows with "windows" = their number, the window numbers in emission order, the dropped count).
     rate: the rate wav, (n,) or (C, n), was recorded at; the stream resamples it (input_rate).  live "hold" | "linear": the pushes
     go through push_live and the track gains "live" = the rows of all N frames (GazeStream.push_live's dict) and "live_max_gap"."""
     from fractions import Fraction
     from csts_amd import track_from_windows
-    stream = predictor.stream(fps=fps, stride=stride, input_rate=rate, live=live, max_gap=max_gap, overlay=overlay, **fmt)
+    stream = predictor.stream(fps=fps, stride=stride, input_rate=rate, live=live, max_gap=max_gap, overlay=overlay,
+                              overlay_format=overlay_format, **fmt)
     N, n = frames.shape[0], wav.shape[-1]
     per = Fraction(AUDIO_RATE if rate is None else rate) / stream.plan["fps"]     # samples per frame
     results, rows, sent = [], [], 0
@@ -342,7 +351,9 @@ def predict_group(args, predictor, dev):
         print("json_stats: " + json.dumps(record), flush=True)
 
 
-def write_pngs(overlay, directory, every):
+def write_pngs(overlay, directory, every, fmt=None):
+    """Every `every`-th overlay frame as a PNG.  fmt: the format keywords of a 4:2:0 overlay (N, H * 3 / 2, W), whose frames are
+    converted by the library's own rule on the host (inputs.yuv_to_rgb_host); None for RGB (N, H, W, 3)."""
     try:
         from PIL import Image
     except ImportError:
@@ -350,7 +361,8 @@ def write_pngs(overlay, directory, every):
         return
     os.makedirs(directory, exist_ok=True)
     for i in range(0, overlay.shape[0], every):
-        Image.fromarray(overlay[i]).save(os.path.join(directory, f"frame_{i:06d}.png"))
+        picture = overlay[i] if fmt is None else inputs.yuv_to_rgb_host(overlay[i], **fmt)
+        Image.fromarray(picture).save(os.path.join(directory, f"frame_{i:06d}.png"))
 
 
 def write_attention(predictor, frames_u8, out, directory, fmt):
@@ -381,6 +393,10 @@ def main(argv=None):
         with np.load(npz) as z:
             if "frames_u8" in z.files or "frames_yuv" in z.files:
                 pics = pictures(z, args, npz, lead=1 if args.video is not None else 2)
+    overlay_yuv = args.overlay_format in ("nv12", "i420")
+    if overlay_yuv and pics is not None and pics[1].get("pixel_format") != args.overlay_format:
+        raise SystemExit(f"--overlay-format {args.overlay_format} draws the overlay in the recording's own layout, and "
+                         f"{npz} holds {pics[1].get('pixel_format', 'rgb24')} frames")
     cfg = assert_and_infer_cfg(load_yaml(args.cfg_file, ["NUM_GPUS", 1] + list(args.opts or [])))
     if not torch.cuda.is_available():
         raise SystemExit("tools/predict.py needs an MI355X: there is no CPU fallback")
@@ -403,13 +419,15 @@ def main(argv=None):
                 try:
                     out, stream_windows, dropped = replay_stream(predictor, frames, waveform(z, rate, dev), fps, args.stride,
                                                                  8 if args.chunk is None else args.chunk, fmt, rate, live=args.live,
-                                                                 max_gap=args.max_gap, overlay=bool(args.overlay or args.overlay_dir))
+                                                                 max_gap=args.max_gap, overlay=bool(args.overlay or args.overlay_dir),
+                                                                 overlay_format=args.overlay_format)
                 except ValueError as e:
                     raise SystemExit(str(e))
             else:
                 out = predictor.predict_video(frames, waveform(z, rate, dev), sample_rate=rate,
                                               fps=fps, stride=args.stride, overlay=bool(args.overlay or args.overlay_dir),
-                                              fill=args.fill, max_gap=args.max_gap, attention_track=attention_track, **fmt)
+                                              fill=args.fill, max_gap=args.max_gap, attention_track=attention_track,
+                                              overlay_format=args.overlay_format, **fmt)
             if args.attention_overlay is not None:
                 head = None if args.attention_overlay == "mean" else int(args.attention_overlay)
                 out["attention_overlay"] = predictor.render_attention_track(frames, out, head=head, points=out["points"], **fmt)
@@ -427,9 +445,12 @@ def main(argv=None):
         if args.live is not None:
             live_keys = ("points", "peak", "count", "known", "filled", "points_source") + (("overlay",) if "overlay" in out["live"] else ())
             arrays.update({"live_" + k: out["live"][k].cpu().numpy() for k in live_keys})
+        if args.overlay_format is not None:
+            arrays["overlay_pixel_format"] = np.array(args.overlay_format)
         np.savez(args.out, **arrays, **rates)
         if args.overlay_dir is not None:
-            write_pngs(arrays["live_overlay" if args.live is not None else "overlay"], args.overlay_dir, args.overlay_every)
+            write_pngs(arrays["live_overlay" if args.live is not None else "overlay"], args.overlay_dir, args.overlay_every,
+                       fmt if overlay_yuv else None)
         record = {"_type": "predict_video", "checkpoint": predictor.checkpoint_path, "source": args.video,
                   "graph": predictor.graph, "out": args.out, "windows": out["windows"],
                   "frames": int(arrays["count"].shape[0]),
