@@ -12,6 +12,11 @@
 // the same ov_shade(), so their bytes agree.  Rows that neither touch the crop nor the marker are copied (or skipped in place).
 // gaze_overlay_yuv_kernel (below) draws the same picture onto 4:2:0 frames and writes 4:2:0 frames, through the same ov_axis and
 // ov_shade.
+// group_gaze_overlay_kernel / group_gaze_overlay_yuv_kernel draw the frames of several jobs, each of its own H x W, in one launch
+// from a job table, and group_points_source_kernel computes their marker centres: what a live group needs per tick.
+#include <algorithm>
+#include <vector>
+
 #include "yuv_shared.h"
 
 namespace {
@@ -60,36 +65,25 @@ __device__ __forceinline__ uint32_t ov_shade(uint32_t rgb, const OvRow& r, uint2
   return cr | (cg << 8) | (cb << 16);
 }
 
-// grid N * ceil(H / OV_ROWS), 256 threads; dynamic LDS: OV_ROWS row entries, the JET table, the map, W column entries
+// One band of one frame, by the 256 threads of a workgroup: rows [Y0, Y0 + nrows) of a frame of H x W, src / dst the first byte of
+// the band in the frame and in the output, m the frame's map, (cX, cY) its marker centre (marked: it has one), crop: the frame is
+// drawn and (nh, nw, y0, x0) hold an S x S crop.  Everything but the pixels is uniform over the workgroup.  Dynamic LDS: OV_ROWS
+// row entries, the JET table, the map, W column entries.  gaze_overlay_kernel and group_gaze_overlay_kernel are this function
+// under two ways of finding the band, so their bytes agree.
 template <bool VEC>
-__global__ __launch_bounds__(256) void gaze_overlay_kernel(const uint8_t* frames, const float* __restrict__ rescaled,
-                                                           const int* __restrict__ centers, const int* __restrict__ params,
-                                                           uint8_t* out, int bands, int H, int W, int S, int mh, int mw, float alpha,
-                                                           int radius) {
-  extern __shared__ __align__(16) uint8_t lds[];
+__device__ __forceinline__ void ov_band(uint8_t* lds, const uint8_t* src, uint8_t* dst, const float* __restrict__ m, int cX, int cY,
+                                        bool marked, bool crop, int nh, int nw, int y0, int x0, int Y0, int nrows, int H, int W, int S,
+                                        int mh, int mw, float alpha, int radius) {
   OvRow* rows = reinterpret_cast<OvRow*>(lds);
   float* lut = reinterpret_cast<float*>(rows + OV_ROWS);
   float* map = lut + 256 * 3;                                   // 16-byte aligned
   uint2* cols = reinterpret_cast<uint2*>(map + ((mh * mw + 1) & ~1));
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int64_t n = blockIdx.x / bands;
-  const int Y0 = (blockIdx.x % bands) * OV_ROWS;
-  const int nrows = min(OV_ROWS, H - Y0);
-  const int64_t band_off = (n * H + Y0) * W * 3;
-  const uint8_t* src = frames + band_off;
-  uint8_t* dst = out + band_off;
   const bool in_place = src == dst;
   const int64_t row_bytes = (int64_t)W * 3;
 
-  const int cX = centers ? centers[2 * n] : 0, cY = centers ? centers[2 * n + 1] : 0;
-  const bool marked = centers && cX >= 0;
-  const int nh = params[0], nw = params[1], y0 = params[2], x0 = params[3];
-  const bool crop = (!centers || cX >= 0) && nh >= S && nw >= S && nh <= (1 << 24) && nw <= (1 << 24) && y0 >= 0 && x0 >= 0 &&
-                    y0 <= nh - S && x0 <= nw - S;
-
   if (crop) {                                                   // uniform over the workgroup
     const int cells = mh * mw;
-    const float* m = rescaled + n * cells;
     if ((cells & 3) == 0 && (reinterpret_cast<uintptr_t>(m) & 15) == 0) {
       for (int k = tid * 4; k < cells; k += 256 * 4) *reinterpret_cast<float4*>(map + k) = *reinterpret_cast<const float4*>(m + k);
     } else {
@@ -169,6 +163,29 @@ __global__ __launch_bounds__(256) void gaze_overlay_kernel(const uint8_t* frames
   }
 }
 
+// whether a frame with these centre and params is drawn inside its crop (the rule of include/csts_hip.h)
+__device__ __forceinline__ bool ov_crop(bool centers, int cX, int nh, int nw, int y0, int x0, int S) {
+  return (!centers || cX >= 0) && nh >= S && nw >= S && nh <= (1 << 24) && nw <= (1 << 24) && y0 >= 0 && x0 >= 0 && y0 <= nh - S &&
+         x0 <= nw - S;
+}
+
+// grid N * ceil(H / OV_ROWS), 256 threads; dynamic LDS as ov_band states it
+template <bool VEC>
+__global__ __launch_bounds__(256) void gaze_overlay_kernel(const uint8_t* frames, const float* __restrict__ rescaled,
+                                                           const int* __restrict__ centers, const int* __restrict__ params,
+                                                           uint8_t* out, int bands, int H, int W, int S, int mh, int mw, float alpha,
+                                                           int radius) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  const int64_t n = blockIdx.x / bands;
+  const int Y0 = (blockIdx.x % bands) * OV_ROWS;
+  const int64_t band_off = (n * H + Y0) * W * 3;
+  const int cX = centers ? centers[2 * n] : 0, cY = centers ? centers[2 * n + 1] : 0;
+  const int nh = params[0], nw = params[1], y0 = params[2], x0 = params[3];
+  ov_band<VEC>(lds, frames + band_off, out + band_off, rescaled + n * mh * mw, cX, cY, centers && cX >= 0,
+               ov_crop(centers != nullptr, cX, nh, nw, y0, x0, S), nh, nw, y0, x0, Y0, min(OV_ROWS, H - Y0), H, W, S, mh, mw, alpha,
+               radius);
+}
+
 // ---- the same picture drawn in 4:2:0 (NV12 / I420 in, the same layout out; include/csts_hip.h states the rule) ----------------------
 // 1.5 bytes in and 1.5 bytes out per pixel; the RGB picture exists only in registers.  A workgroup owns OVY_BAND pairs of luma rows
 // of one frame and the chroma rows those pairs share (nv12: chroma row cy belongs to row pair cy; i420: row cy of U and row cy of
@@ -197,15 +214,19 @@ struct OvyFrame {
   bool marked, crop;
 };
 
-__device__ __forceinline__ OvyFrame ovy_frame(const int* __restrict__ centers, const int* __restrict__ params, int64_t n, int S) {
+// n: the frame's row of centers; (nh, nw, y0, x0): its params
+__device__ __forceinline__ OvyFrame ovy_frame(const int* __restrict__ centers, int64_t n, int nh, int nw, int y0, int x0, int S) {
   OvyFrame f;
   f.cX = centers ? centers[2 * n] : 0;
   f.cY = centers ? centers[2 * n + 1] : 0;
   f.marked = centers && f.cX >= 0;
-  f.nh = params[0], f.nw = params[1], f.y0 = params[2], f.x0 = params[3];
-  f.crop = (!centers || f.cX >= 0) && f.nh >= S && f.nw >= S && f.nh <= (1 << 24) && f.nw <= (1 << 24) && f.y0 >= 0 && f.x0 >= 0 &&
-           f.y0 <= f.nh - S && f.x0 <= f.nw - S;
+  f.nh = nh, f.nw = nw, f.y0 = y0, f.x0 = x0;
+  f.crop = ov_crop(centers != nullptr, f.cX, nh, nw, y0, x0, S);
   return f;
+}
+
+__device__ __forceinline__ OvyFrame ovy_frame(const int* __restrict__ centers, const int* __restrict__ params, int64_t n, int S) {
+  return ovy_frame(centers, n, params[0], params[1], params[2], params[3], S);
 }
 
 // The tables of a workgroup, staged by its 256 threads (no barrier inside): the frame's map m, alpha * JET(q), one entry per luma
@@ -310,35 +331,33 @@ __device__ __forceinline__ void ovy_block(int (&Y)[2][2], int& U, int& V, int X,
   rgb_chroma(kr, SR, SG, SB, U, V);
 }
 
-// grid N * bands, 256 threads; W % 4 == 0, frames and out 4-byte aligned.  Dynamic LDS: 2 OVY_BAND row entries, the JET table, the
-// map, W column entries.
+// The row pairs [P0, P0 + OVY_BAND) of one frame on the vector path, by the 256 threads of a workgroup: frames / out the first byte of
+// the FRAME (4-byte aligned, W % 4 == 0) and of its output, m its map, f what ovy_frame says of it.  Dynamic LDS: 2 OVY_BAND row
+// entries, the JET table, the map, W column entries.  gaze_overlay_yuv_vec_kernel and group_gaze_overlay_yuv_kernel are this
+// function under two ways of finding the frame, so their bytes agree.
 template <bool NV12>
-__global__ __launch_bounds__(256) void gaze_overlay_yuv_vec_kernel(const uint8_t* frames, uint8_t* out, const float* __restrict__ rescaled,
-                                                                   const int* __restrict__ centers, const int* __restrict__ params,
-                                                                   int bands, int H, int W, int S, int mh, int mw, float alpha,
-                                                                   int radius, YuvCoef kf, RgbCoef kr) {
-  extern __shared__ __align__(16) uint8_t lds[];
+__device__ __forceinline__ void ovy_vec_band(uint8_t* lds, const uint8_t* frames, uint8_t* out, const float* __restrict__ m,
+                                             const OvyFrame& f, int P0, int H, int W, int S, int mh, int mw, float alpha, int radius,
+                                             const YuvCoef& kf, const RgbCoef& kr) {
   OvRow* rows = reinterpret_cast<OvRow*>(lds);
   float* lut = reinterpret_cast<float*>(rows + 2 * OVY_BAND);
   float* map = lut + 256 * 3;                                   // 16-byte aligned
   uint2* cols = reinterpret_cast<uint2*>(map + ((mh * mw + 3) & ~3));
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int64_t n = blockIdx.x / bands;
-  const int P0 = (blockIdx.x % bands) * OVY_BAND, npairs = min(OVY_BAND, (H >> 1) - P0);
+  const int npairs = min(OVY_BAND, (H >> 1) - P0);
   const int hw = W >> 1;
   const bool in_place = frames == out;
-  const OvyFrame f = ovy_frame(centers, params, n, S);
   if (!f.crop && !f.marked && in_place) return;                 // uniform: nothing of this frame is drawn
-  ovy_tables(rows, lut, map, cols, rescaled + n * mh * mw, f, alpha, 2 * P0, 2 * npairs, 0, W, H, W, S, mh, mw, tid);
+  ovy_tables(rows, lut, map, cols, m, f, alpha, 2 * P0, 2 * npairs, 0, W, H, W, S, mh, mw, tid);
   __syncthreads();
 
   const float oma = 1.0f - alpha;
-  const int64_t f0 = n * yuv_frame_bytes(H, W), c0 = f0 + (int64_t)H * W, vplane = (int64_t)(H >> 1) * hw;
+  const int64_t c0 = (int64_t)H * W, vplane = (int64_t)(H >> 1) * hw;
   for (int pr = wv; pr < npairs; pr += 4) {                     // everything about the row pair is wave-uniform
     const int cy = P0 + pr;
     const OvyPair p = ovy_pair(rows + 2 * pr, cy, f, radius);
     if (!p.drawn && in_place) continue;
-    const int64_t l0 = f0 + (int64_t)(2 * cy) * W, q0 = c0 + (int64_t)cy * (NV12 ? W : hw);
+    const int64_t l0 = (int64_t)(2 * cy) * W, q0 = c0 + (int64_t)cy * (NV12 ? W : hw);
     for (int g = lane; g < (W >> 2); g += 64) {
       uint32_t a = *reinterpret_cast<const uint32_t*>(frames + l0 + 4 * g);
       uint32_t b = *reinterpret_cast<const uint32_t*>(frames + l0 + W + 4 * g);
@@ -373,6 +392,166 @@ __global__ __launch_bounds__(256) void gaze_overlay_yuv_vec_kernel(const uint8_t
       }
     }
   }
+}
+
+// grid N * bands, 256 threads; W % 4 == 0, frames and out 4-byte aligned; dynamic LDS as ovy_vec_band states it
+template <bool NV12>
+__global__ __launch_bounds__(256) void gaze_overlay_yuv_vec_kernel(const uint8_t* frames, uint8_t* out, const float* __restrict__ rescaled,
+                                                                   const int* __restrict__ centers, const int* __restrict__ params,
+                                                                   int bands, int H, int W, int S, int mh, int mw, float alpha,
+                                                                   int radius, YuvCoef kf, RgbCoef kr) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  const int64_t n = blockIdx.x / bands, f0 = n * yuv_frame_bytes(H, W);
+  const OvyFrame f = ovy_frame(centers, params, n, S);
+  ovy_vec_band<NV12>(lds, frames + f0, out + f0, rescaled + n * mh * mw, f, (int)(blockIdx.x % bands) * OVY_BAND, H, W, S, mh, mw, alpha,
+                     radius, kf, kr);
+}
+
+// ---- the overlays of a group: one launch over jobs of different sizes (include/csts_hip.h, "gaze overlay of a group") --------------
+// jobs int64 [njobs][OVG_JOB]: one row per job, read through the scalar path -- every index below is uniform over the workgroup.
+// A workgroup finds its job by binary search over the first-workgroup column, then its frame and band inside the job, and from
+// there on it is ov_band / ovy_vec_band on that frame: the single-tensor kernels' code, hence their bytes.
+constexpr int OVG_JOB = 13;
+enum { OVG_SRC = 0, OVG_DST, OVG_K, OVG_H, OVG_W, OVG_NH, OVG_NW, OVG_Y0, OVG_X0, OVG_FLIP, OVG_ROW0, OVG_WG0, OVG_VEC };
+
+// the last job j whose column `col` is <= key; the column ascends and starts at 0 <= key
+__device__ __forceinline__ int ovg_find(const int64_t* __restrict__ jobs, int njobs, int col, int64_t key) {
+  int lo = 0, hi = njobs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (jobs[(int64_t)mid * OVG_JOB + col] <= key) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// A workgroup's place in the table: its job row, the frame k of the job and the band of the frame; nullptr (the workgroup writes
+// nothing) when the device table does not hold what the launch was sized for: a frame past the job's K, a W wider than the LDS
+// of the launch (max_w), a size out of range.
+__device__ __forceinline__ const int64_t* ovg_place(const int64_t* __restrict__ jobs, int njobs, int max_w, int64_t* k, int* band) {
+  const int64_t* job = jobs + (int64_t)ovg_find(jobs, njobs, OVG_WG0, blockIdx.x) * OVG_JOB;
+  const int64_t H = job[OVG_H], W = job[OVG_W], local = (int64_t)blockIdx.x - job[OVG_WG0];
+  if (H < 1 || H > 65535 || W < 1 || W > max_w || local < 0) return nullptr;
+  const int64_t bands = (H + OV_ROWS - 1) / OV_ROWS;
+  *k = local / bands;
+  *band = (int)(local % bands);
+  return *k < job[OVG_K] ? job : nullptr;
+}
+
+// grid = the sum of K * ceil(H / OV_ROWS) over the jobs, 256 threads; dynamic LDS: ov_band's at the widest W of the call (max_w)
+__global__ __launch_bounds__(256) void group_gaze_overlay_kernel(const int64_t* __restrict__ jobs, int njobs, int max_w,
+                                                                 const float* __restrict__ rescaled, const int* __restrict__ centers,
+                                                                 int S, int mh, int mw, float alpha, int radius) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  int64_t k;
+  int band;
+  const int64_t* job = ovg_place(jobs, njobs, max_w, &k, &band);
+  if (!job) return;
+  const int H = (int)job[OVG_H], W = (int)job[OVG_W], Y0 = band * OV_ROWS;
+  const int nh = (int)job[OVG_NH], nw = (int)job[OVG_NW], y0 = (int)job[OVG_Y0], x0 = (int)job[OVG_X0];
+  const int64_t n = job[OVG_ROW0] + k, band_off = (k * H + Y0) * W * 3;
+  const uint8_t* src = reinterpret_cast<const uint8_t*>(job[OVG_SRC]) + band_off;
+  uint8_t* dst = reinterpret_cast<uint8_t*>(job[OVG_DST]) + band_off;
+  const int cX = centers ? centers[2 * n] : 0, cY = centers ? centers[2 * n + 1] : 0;
+  const bool marked = centers && cX >= 0, crop = ov_crop(centers != nullptr, cX, nh, nw, y0, x0, S);
+  const float* m = rescaled + n * mh * mw;
+  const int nrows = min(OV_ROWS, H - Y0);
+  if (job[OVG_VEC]) ov_band<true>(lds, src, dst, m, cX, cY, marked, crop, nh, nw, y0, x0, Y0, nrows, H, W, S, mh, mw, alpha, radius);
+  else ov_band<false>(lds, src, dst, m, cX, cY, marked, crop, nh, nw, y0, x0, Y0, nrows, H, W, S, mh, mw, alpha, radius);
+}
+
+// the same for 4:2:0 jobs, all on the vector path (the entry refuses a job that is not); grid and LDS as above (ovy_vec_band's)
+template <bool NV12>
+__global__ __launch_bounds__(256) void group_gaze_overlay_yuv_kernel(const int64_t* __restrict__ jobs, int njobs, int max_w,
+                                                                     const float* __restrict__ rescaled,
+                                                                     const int* __restrict__ centers, int S, int mh, int mw,
+                                                                     float alpha, int radius, YuvCoef kf, RgbCoef kr) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  int64_t k;
+  int band;
+  const int64_t* job = ovg_place(jobs, njobs, max_w, &k, &band);
+  if (!job || !job[OVG_VEC]) return;
+  const int H = (int)job[OVG_H], W = (int)job[OVG_W];
+  if ((H & 1) || (W & 3)) return;
+  const int64_t n = job[OVG_ROW0] + k, f0 = k * yuv_frame_bytes(H, W);
+  const OvyFrame f = ovy_frame(centers, n, (int)job[OVG_NH], (int)job[OVG_NW], (int)job[OVG_Y0], (int)job[OVG_X0], S);
+  ovy_vec_band<NV12>(lds, reinterpret_cast<const uint8_t*>(job[OVG_SRC]) + f0, reinterpret_cast<uint8_t*>(job[OVG_DST]) + f0,
+                     rescaled + n * mh * mw, f, band * OVY_BAND, H, W, S, mh, mw, alpha, radius, kf, kr);
+}
+
+// points on the crop -> points on the source frame and marker centres, one thread per row: infer.points_to_source followed by
+// infer.marker_centers under the row's job (found by binary search over the first-row column).  Plain IEEE double arithmetic, the
+// operations torch performs in torch's order (the file is compiled without contraction): multiply, add, divide; multiply, floor.
+__global__ __launch_bounds__(256) void group_points_source_kernel(const int64_t* __restrict__ jobs, int njobs,
+                                                                  const float* __restrict__ points, double* __restrict__ points_source,
+                                                                  int* __restrict__ centers, int64_t P, int S) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= P) return;
+  const int64_t* job = jobs + (int64_t)ovg_find(jobs, njobs, OVG_ROW0, p) * OVG_JOB;
+  const double x = (double)points[2 * p], y = (double)points[2 * p + 1], s = (double)S;
+  const double xs = (x * s + (double)job[OVG_X0]) / (double)job[OVG_NW];
+  const double ys = (y * s + (double)job[OVG_Y0]) / (double)job[OVG_NH];
+  points_source[2 * p] = xs;
+  points_source[2 * p + 1] = ys;
+  const bool bad = xs != xs || ys != ys;
+  centers[2 * p] = bad ? -1 : (int)floor(xs * (double)job[OVG_W]);
+  centers[2 * p + 1] = bad ? -1 : (int)floor(ys * (double)job[OVG_H]);
+}
+
+// The host copy of a job table, checked row by row as the single-tensor entries check their tensor -> the widest W, or -1.  *rows:
+// the sum of K; *grid: the sum of K * bands.
+int ovg_check(const int64_t* jobs_host, int njobs, bool yuv, bool pointers, int64_t* rows, int64_t* grid) {
+  CSTS_REQUIRE(jobs_host && njobs >= 1 && njobs <= 65535, "the host copy of the job table is missing, or 1 <= njobs <= 65535 fails");
+  int64_t P = 0, G = 0, max_w = 0;
+  for (int j = 0; j < njobs; ++j) {
+    const int64_t* job = jobs_host + (int64_t)j * OVG_JOB;
+    const int64_t K = job[OVG_K], H = job[OVG_H], W = job[OVG_W];
+    CSTS_REQUIRE(K >= 1 && K < ((int64_t)1 << 31) && H >= 1 && H <= 65535 && W >= 1 && W <= OV_MAX_W,
+                 "a job has bad sizes (K >= 1, 1 <= H <= 65535, 1 <= W <= 8192)");
+    // the overlays index rescaled / centers with it (rows may be left out between jobs), group_points_source searches it
+    CSTS_REQUIRE(pointers ? job[OVG_ROW0] >= P : job[OVG_ROW0] == P,
+                 "a job's first row lies before the end of the job before it, or (points) is not the number of rows before it");
+    CSTS_REQUIRE(job[OVG_WG0] == G, "a job's first workgroup is not the number of workgroups of the jobs before it");
+    if (yuv) CSTS_REQUIRE(H >= 2 && W >= 2 && (H & 1) == 0 && (W & 1) == 0 && H <= 65534, "4:2:0 frames need even H, W >= 2, H <= 65534");
+    if (pointers) {
+      const int64_t a = job[OVG_SRC], b = job[OVG_DST], v = job[OVG_VEC];
+      CSTS_REQUIRE(a != 0 && b != 0, "a job has a null source or destination");
+      CSTS_REQUIRE(v == 0 || (v == 1 && (W & 3) == 0 && (a & 3) == 0 && (b & 3) == 0),
+                   "a job's vector flag is set but W % 4 != 0 or its frames or out are not 4-byte aligned");
+      if (yuv) CSTS_REQUIRE(v == 1, "the 4:2:0 group launch takes vector-path jobs only (W % 4 == 0, 4-byte aligned): send the job "
+                                    "through csts_gaze_overlay_yuv");
+    }
+    P = job[OVG_ROW0] + K;
+    G += K * cdiv(H, OV_ROWS);
+    CSTS_REQUIRE(P < ((int64_t)1 << 31) && G < ((int64_t)1 << 31), "the frames and the workgroups of a call must stay below 2^31");
+    max_w = std::max(max_w, W);
+  }
+  *rows = P;
+  *grid = G;
+  return (int)max_w;
+}
+
+// No job may write what another job reads or writes; a job may write its own frames (dst == src).  The destinations are sorted,
+// so neighbours show every overlap among them, and every source is looked up among them.  bytes(job) -> the bytes of its frames.
+template <typename Bytes>
+int ovg_disjoint(const int64_t* jobs_host, int njobs, Bytes bytes) {
+  struct Span { int64_t lo, hi; int job; };
+  std::vector<Span> dst(njobs);
+  for (int j = 0; j < njobs; ++j) {
+    const int64_t* job = jobs_host + (int64_t)j * OVG_JOB;
+    dst[j] = {job[OVG_DST], job[OVG_DST] + bytes(job), j};
+  }
+  std::sort(dst.begin(), dst.end(), [](const Span& a, const Span& b) { return a.lo < b.lo; });
+  for (int j = 1; j < njobs; ++j) CSTS_REQUIRE(dst[j - 1].hi <= dst[j].lo, "the outputs of two jobs overlap");
+  for (int j = 0; j < njobs; ++j) {
+    const int64_t* job = jobs_host + (int64_t)j * OVG_JOB;
+    const int64_t lo = job[OVG_SRC], hi = lo + bytes(job);
+    // the first destination that ends after lo; the ones behind it start at or after its end
+    auto it = std::upper_bound(dst.begin(), dst.end(), lo, [](int64_t v, const Span& s) { return v < s.hi; });
+    if (it != dst.end() && it->job == j && it->lo == lo) ++it;  // in place: the job's own frames
+    CSTS_REQUIRE(it == dst.end() || it->lo >= hi, "a job's out overlaps frames: its own (other than in place) or another job's");
+  }
+  return 0;
 }
 
 // LDS spans of one row pair of a tile of tw pixels: two luma rows of *lcap bytes, then the chroma: one interleaved row (nv12) or a
@@ -546,6 +725,73 @@ extern "C" int csts_gaze_overlay_yuv(const uint8_t* frames_yuv, const float* res
   hipLaunchKernelGGL(gaze_overlay_yuv_kernel, dim3((unsigned)(N * bands * xtiles)), dim3(256), lds, stream, frames_yuv - lo, lo,
                      lo + bytes, out - olo, olo, rescaled, centers, params, (int)bands, (int)xtiles, twn, H, W, S, mh, mw, alpha, radius,
                      layout, kf, kr);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_group_gaze_overlay(const int64_t* jobs, const int64_t* jobs_host, int njobs, const float* rescaled,
+                                       const int* centers, int S, int mh, int mw, float alpha, int radius, hipStream_t stream) {
+  int64_t rows, grid;
+  const int max_w = ovg_check(jobs_host, njobs, false, true, &rows, &grid);
+  if (max_w < 0) return -1;
+  CSTS_REQUIRE(jobs && rescaled, "bad args (jobs and rescaled must not be NULL)");
+  CSTS_REQUIRE(S >= 1 && S <= 4096, "bad sizes (1 <= S <= 4096)");
+  CSTS_REQUIRE(mh >= 1 && mw >= 1 && (int64_t)mh * mw <= CSTS_GAZE_DECODE_MAX_HW, "1 <= mh * mw <= CSTS_GAZE_DECODE_MAX_HW (the map is staged in LDS)");
+  CSTS_REQUIRE(alpha >= 0.f && alpha <= 1.f, "0 <= alpha <= 1");
+  CSTS_REQUIRE(radius >= 0, "radius >= 0");
+  if (ovg_disjoint(jobs_host, njobs, [](const int64_t* job) { return job[OVG_K] * job[OVG_H] * job[OVG_W] * 3; })) return -1;
+  const int lds = OV_ROWS * (int)sizeof(OvRow) + 256 * 3 * (int)sizeof(float) + ((mh * mw + 1) & ~1) * (int)sizeof(float) + max_w * (int)sizeof(uint2);
+  if (lds > 65536) CSTS_REQUIRE(csts_dyn_lds_optin(reinterpret_cast<const void*>(&group_gaze_overlay_kernel), lds), "LDS opt-in");
+  hipLaunchKernelGGL(group_gaze_overlay_kernel, dim3((unsigned)grid), dim3(256), lds, stream, jobs, njobs, max_w, rescaled, centers, S,
+                     mh, mw, alpha, radius);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_group_gaze_overlay_yuv(const int64_t* jobs, const int64_t* jobs_host, int njobs, const float* rescaled,
+                                           const int* centers, int S, int mh, int mw, float alpha, int radius, int layout, int matrix,
+                                           int full_range, hipStream_t stream) {
+  CSTS_REQUIRE(yuv_args_ok(layout, matrix), "layout must be CSTS_YUV_NV12 or CSTS_YUV_I420, matrix CSTS_YUV_BT601 or CSTS_YUV_BT709");
+  int64_t rows, grid;
+  const int max_w = ovg_check(jobs_host, njobs, true, true, &rows, &grid);
+  if (max_w < 0) return -1;
+  CSTS_REQUIRE(jobs && rescaled, "bad args (jobs and rescaled must not be NULL)");
+  CSTS_REQUIRE(S >= 1 && S <= 4096, "bad sizes (1 <= S <= 4096)");
+  CSTS_REQUIRE(mh >= 1 && mw >= 1 && (int64_t)mh * mw <= CSTS_GAZE_DECODE_MAX_HW, "1 <= mh * mw <= CSTS_GAZE_DECODE_MAX_HW (the map is staged in LDS)");
+  CSTS_REQUIRE(alpha >= 0.f && alpha <= 1.f, "0 <= alpha <= 1");
+  CSTS_REQUIRE(radius >= 0, "radius >= 0");
+  if (ovg_disjoint(jobs_host, njobs, [](const int64_t* job) { return job[OVG_K] * yuv_frame_bytes((int)job[OVG_H], (int)job[OVG_W]); }))
+    return -1;
+  const int lds = 2 * OVY_BAND * (int)sizeof(OvRow) + 256 * 3 * (int)sizeof(float) + ((mh * mw + 3) & ~3) * (int)sizeof(float) +
+                  max_w * (int)sizeof(uint2);
+  const YuvCoef kf = yuv_coef(matrix, full_range);
+  const RgbCoef kr = rgb_coef(matrix, full_range);
+  const bool nv12 = layout == CSTS_YUV_NV12;
+  const void* fn = nv12 ? reinterpret_cast<const void*>(&group_gaze_overlay_yuv_kernel<true>)
+                        : reinterpret_cast<const void*>(&group_gaze_overlay_yuv_kernel<false>);
+  if (lds > 65536) CSTS_REQUIRE(csts_dyn_lds_optin(fn, lds), "LDS opt-in");
+  if (nv12) hipLaunchKernelGGL(group_gaze_overlay_yuv_kernel<true>, dim3((unsigned)grid), dim3(256), lds, stream, jobs, njobs, max_w,
+                               rescaled, centers, S, mh, mw, alpha, radius, kf, kr);
+  else hipLaunchKernelGGL(group_gaze_overlay_yuv_kernel<false>, dim3((unsigned)grid), dim3(256), lds, stream, jobs, njobs, max_w, rescaled,
+                          centers, S, mh, mw, alpha, radius, kf, kr);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_group_points_source(const int64_t* jobs, const int64_t* jobs_host, int njobs, const float* points, int S,
+                                        double* points_source, int* centers, hipStream_t stream) {
+  int64_t rows, grid;
+  if (ovg_check(jobs_host, njobs, false, false, &rows, &grid) < 0) return -1;
+  CSTS_REQUIRE(jobs && points && points_source && centers, "bad args (jobs, points, points_source and centers must not be NULL)");
+  CSTS_REQUIRE(S >= 1 && S <= 4096, "bad sizes (1 <= S <= 4096)");
+  for (int j = 0; j < njobs; ++j) {
+    const int64_t* job = jobs_host + (int64_t)j * OVG_JOB;
+    CSTS_REQUIRE(job[OVG_NH] >= 1 && job[OVG_NW] >= 1 && job[OVG_NH] <= (1 << 24) && job[OVG_NW] <= (1 << 24) && job[OVG_Y0] >= 0 &&
+                     job[OVG_X0] >= 0 && job[OVG_Y0] <= (1 << 24) && job[OVG_X0] <= (1 << 24),
+                 "a job's params row is out of range (1 <= new h, new w <= 2^24, 0 <= y0, x0 <= 2^24)");
+  }
+  hipLaunchKernelGGL(group_points_source_kernel, dim3((unsigned)cdiv(rows, 256)), dim3(256), 0, stream, jobs, njobs, points,
+                     points_source, centers, rows, S);
   CSTS_LAUNCH_CHECK();
   return 0;
 }

@@ -240,6 +240,39 @@ def marker_centers(points_source, H, W):
     return torch.where(bad, torch.full_like(c, -1.0), c).to(torch.int32)
 
 
+OVERLAY_BAND_ROWS = 32                                        # frame rows per workgroup of the overlay kernels (OV_ROWS)
+
+
+def overlay_group_table(sizes, vector=None):
+    """The host rule of a grouped overlay launch (ops.group_gaze_overlay, ops.group_points_source; include/csts_hip.h, "gaze
+    overlay of a group"): sizes is a list of (K, H, W), one per job, vector the per-job flags of the 4-pixel path (None: a job is
+    on it when W % 4 == 0; a flag set on a job whose W % 4 != 0 is a ValueError) -> {"first_row": int64 (J,), the index of a job's
+    first row in the concatenated rescaled / centers = the sum of the K before it; "first_workgroup": int64 (J,), the sum of
+    K * bands of the jobs before it; "bands": int64 (J,) = ceil(H / 32); "vector": int64 (J,) 0 / 1; "rows": the sum of K;
+    "grid": the sum of K * bands}.  Workgroup g belongs to the last job j with first_workgroup[j] <= g, which the kernel finds
+    by binary search; inside it, frame (g - first_workgroup[j]) // bands[j] and band (g - first_workgroup[j]) % bands[j].  A job
+    with K < 1 or a non-positive size is a ValueError naming the job.  Pure numpy: no GPU."""
+    import numpy as np
+    sizes = [tuple(int(v) for v in s) for s in sizes]
+    J = len(sizes)
+    flags = [None] * J if vector is None else list(vector)
+    if len(flags) != J:
+        raise ValueError(f"vector must hold one flag per job ({J}), got {len(flags)}")
+    first_row, first_wg, bands, vec = (np.zeros(J, dtype=np.int64) for _ in range(4))
+    rows = grid = 0
+    for j, size in enumerate(sizes):
+        if len(size) != 3 or min(size) < 1:
+            raise ValueError(f"job {j}: (K, H, W) must be three positive integers, got {size}")
+        K, H, W = size
+        v = W % 4 == 0 if flags[j] is None else bool(flags[j])
+        if v and W % 4:
+            raise ValueError(f"job {j}: the vector path takes 4 pixels a lane and needs W % 4 == 0, got W {W}")
+        first_row[j], first_wg[j], bands[j], vec[j] = rows, grid, -(-H // OVERLAY_BAND_ROWS), int(v)
+        rows += K
+        grid += K * int(bands[j])
+    return {"first_row": first_row, "first_workgroup": first_wg, "bands": bands, "vector": vec, "rows": rows, "grid": grid}
+
+
 def _core(model):
     return model.module if hasattr(model, "module") else model
 
@@ -561,8 +594,10 @@ class GazePredictor:
         every pushed frame of every slot answered with its row of a gaze track computed from the windows of its own slot that
         have run by then, filled at most max_gap frames apart; overlay=True adds the frames drawn over.  live: "hold" or
         "linear", required.  The tracks of all slots live in one arena and a round folds and answers them with one launch each
-        (ops.group_live_add, ops.group_live_rows), whatever the number of slots.  The other keywords are stream_group()'s and
-        stream()'s.  GazeLiveGroup states the order of work and the contract; group_live_schedule is the rule on the host."""
+        (ops.group_live_add, ops.group_live_rows), whatever the number of slots; their points on the source frames and their
+        overlays are one launch each as well, whatever the sizes (ops.group_points_source, ops.group_gaze_overlay).  The other
+        keywords are stream_group()'s and stream()'s.  GazeLiveGroup states the order of work and the contract;
+        group_live_schedule is the rule on the host."""
         from .stream import GazeLiveGroup
         return GazeLiveGroup(self, streams, live, fps=fps, stride=stride, segment=segment, batch=batch, max_chunk=max_chunk,
                              pixel_format=pixel_format, matrix=matrix, full_range=full_range, input_rate=input_rate,

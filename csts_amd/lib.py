@@ -304,6 +304,9 @@ SYMBOLS = {
     "csts_gaze_track_fill": (_I, [vp, vp, i64, _I, _I, _I, _I, vp, vp, vp, vp, vp, vp]),
     "csts_gaze_overlay": (_I, [vp, vp, vp, vp, vp, i64, _I, _I, _I, _I, _I, _F, _I, vp]),
     "csts_gaze_overlay_yuv": (_I, [vp, vp, vp, vp, vp, i64, _I, _I, _I, _I, _I, _F, _I, _I, _I, _I, vp]),
+    "csts_group_gaze_overlay": (_I, [vp, vp, _I, vp, vp, _I, _I, _I, _F, _I, vp]),
+    "csts_group_gaze_overlay_yuv": (_I, [vp, vp, _I, vp, vp, _I, _I, _I, _F, _I, _I, _I, _I, vp]),
+    "csts_group_points_source": (_I, [vp, vp, _I, vp, _I, vp, vp, vp]),
     "csts_audio_pixel_attn": (_I, [vp, _I, vp, _I, _I, _I, _I, _I, _I, _I, _I, _F, vp, vp, vp, vp, vp]),
     "csts_attention_track": (_I, [vp, vp, vp, i64, _I, _I, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp]),
     "csts_attention_rescale": (_I, [vp, vp, _I, i64, _I, _I, _I, vp, vp, vp]),

@@ -2798,6 +2798,11 @@ def _overlay_params(params, crop_size, device):
         if params.dtype != torch.int32 or params.numel() != 5:
             raise ValueError(f"params must hold 5 int32 values (new h, new w, y0, x0, flip), got {tuple(params.shape)} {params.dtype}")
         return params.contiguous()
+    return torch.tensor(_host_params_row(params, crop_size), dtype=torch.int32, device=device)
+
+
+def _host_params_row(params, crop_size):
+    """A params row given on the host, checked against the sampler's range: [new h, new w, y0, x0, 0]."""
     import numpy as np
     row = np.asarray(params)
     if row.size != 5 or not np.issubdtype(row.dtype, np.integer):
@@ -2808,7 +2813,7 @@ def _overlay_params(params, crop_size, device):
     S = int(crop_size)
     if nh < S or nw < S or not 0 <= y0 <= nh - S or not 0 <= x0 <= nw - S:
         raise ValueError(f"params {(nh, nw, y0, x0)} do not hold a {S} x {S} crop")
-    return torch.tensor([nh, nw, y0, x0, 0], dtype=torch.int32, device=device)
+    return [nh, nw, y0, x0, 0]
 
 
 def gaze_overlay(frames_u8, rescaled, params, crop_size, centers=None, alpha=0.4, radius=5, out=None):
@@ -2887,6 +2892,179 @@ def gaze_overlay_yuv(frames_yuv, rescaled, params, crop_size, pixel_format, matr
     cen = None if centers is None else centers.contiguous()
     L.check(_lib().csts_gaze_overlay_yuv(_p(frames_yuv), _p(maps), _p(cen), _p(par), _p(out), N, H, W, S, maps.shape[1],
                                          maps.shape[2], alpha, radius, layout, mat, fr, _stream()), "csts_gaze_overlay_yuv")
+    return out
+
+
+# ----------------------------------------------------------------------------------------- gaze overlay of a group
+_OVG_COLS = 13      # job row of include/csts_hip.h: src, dst, K, H, W, new h, new w, y0, x0, flip, first row, first workgroup, vector
+
+
+def _disjoint_jobs(src, dst, nbytes):
+    """No job may write what another reads or writes; a job may write its own frames (dst == src).  int64 arrays, one entry a job."""
+    import numpy as np
+    order = np.argsort(dst, kind="stable")
+    lo, hi = dst[order], (dst + nbytes)[order]
+    clash = np.nonzero(hi[:-1] > lo[1:])[0]
+    if clash.size:
+        a, b = sorted((int(order[clash[0]]), int(order[clash[0] + 1])))
+        raise ValueError(f"job {b}: out overlaps the out of job {a}")
+    for j in range(len(src)):
+        k = int(np.searchsorted(hi, src[j], side="right"))       # the first out that ends after the job's first source byte
+        if k < len(lo) and int(order[k]) == j and lo[k] == src[j]:
+            k += 1                                               # in place
+        if k < len(lo) and lo[k] < src[j] + nbytes[j]:
+            other = int(order[k])
+            raise ValueError(f"job {other}: out overlaps the frames of job {j}" if other != j else
+                             f"job {j}: out must be the frames themselves (in place) or share no memory with them")
+
+
+def group_gaze_overlay(jobs, rescaled, centers, crop_size, alpha=0.4, radius=5, outs=None, pixel_format="rgb24", matrix="bt601",
+                       full_range=False):
+    """gaze_overlay / gaze_overlay_yuv for several jobs of different sizes in ONE launch (csts_group_gaze_overlay / _yuv): jobs is a
+    list of (frames, params_row) -- frames uint8 (K, H, W, 3) on the device, or (K, H * 3 / 2, W) in the one 4:2:0 pixel_format
+    (with matrix and full_range) of the call, each job of its own K, H, W; params_row its five integers on the HOST -- and
+    rescaled fp32 (P, mh, mw), centers int32 (P, 2) or None hold the rows of all jobs in job order, P = the sum of K.  Returns
+    the list of outputs, out[j] = gaze_overlay(frames_j, rescaled[rows of j], params_row_j, crop_size, centers[rows of j], alpha,
+    radius) byte for byte (gaze_overlay_yuv in a 4:2:0 format).  outs: None, or one entry per job, each None or the tensor to
+    draw into; outs[j] may be the frames of job j themselves (in place).  The outputs that are not given are views of ONE
+    allocation, each starting at a 16-byte boundary.  No job's out may overlap another job's frames or out.  Validation is
+    gaze_overlay's per job, the messages prefixed "job j: ", all on the host before anything is launched; the table goes up in
+    one copy.  Inside the launch a job takes the 4-pixel path when W % 4 == 0 and frames and out are 4-byte aligned, else the byte
+    path (packed RGB); a 4:2:0 job that cannot take the 4-pixel path goes through gaze_overlay_yuv, one launch for that job."""
+    import numpy as np
+    from .inputs import check_pixel_format, _yuv_hw, _upload
+    from .infer import overlay_group_table
+    layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
+    jobs = list(jobs)
+    J = len(jobs)
+    if J < 1 or J > 65535:
+        raise ValueError(f"group_gaze_overlay takes 1..65535 jobs a call, got {J}")
+    outs = [None] * J if outs is None else list(outs)
+    if len(outs) != J:
+        raise ValueError(f"outs must hold one entry per job ({J}), got {len(outs)}")
+    alpha, radius, S = float(alpha), int(radius), int(crop_size)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha must lie in [0, 1], got {alpha}")
+    if radius < 0 or S < 1:
+        raise ValueError(f"group_gaze_overlay needs crop_size >= 1 and radius >= 0, got {S} and {radius}")
+    _need_gpu(rescaled, centers)
+    sizes, rows, shapes = [], [], []
+    for j, job in enumerate(jobs):
+        try:
+            frames, row = job
+            _need_gpu(frames, outs[j])
+            if layout:
+                if frames.dtype != torch.uint8 or frames.dim() != 3:
+                    raise ValueError(f"{pixel_format} frames must be uint8 (K, H * 3 / 2, W), got {tuple(frames.shape)} {frames.dtype}")
+                H, W = _yuv_hw(frames.shape, pixel_format)
+            else:
+                if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+                    raise ValueError(f"frames must be uint8 (K, H, W, 3), got {tuple(frames.shape)} {frames.dtype}")
+                H, W = int(frames.shape[1]), int(frames.shape[2])
+            K = int(frames.shape[0])
+            if K < 1 or H < 1 or W < 1:
+                raise ValueError(f"frames must hold K >= 1 frames of H, W >= 1, got {tuple(frames.shape)}")
+            if W > 8192 or H > 65535:
+                raise ValueError(f"frames wider than 8192 or taller than 65535 pixels are not supported, got {H} x {W}")
+            if not frames.is_contiguous():
+                raise ValueError("frames must be contiguous")
+            o = outs[j]
+            if o is not None and (o.dtype != torch.uint8 or o.shape != frames.shape or not o.is_contiguous()):
+                raise ValueError(f"out must be contiguous uint8 {tuple(frames.shape)}, got {tuple(o.shape)} {o.dtype}")
+            rows.append(_host_params_row(row, S))
+        except L.CstsError as e:
+            raise L.CstsError(f"job {j}: {e}") from None
+        except (ValueError, TypeError) as e:
+            raise ValueError(f"job {j}: {e}") from None
+        sizes.append((K, H, W))
+        shapes.append(frames.shape)
+    P = sum(s[0] for s in sizes)
+    if rescaled.dtype != torch.float32 or rescaled.dim() != 3 or rescaled.shape[0] != P:
+        raise ValueError(f"rescaled must be fp32 ({P}, mh, mw), one row per frame of the jobs, got {tuple(rescaled.shape)} {rescaled.dtype}")
+    if centers is not None and (centers.dtype != torch.int32 or tuple(centers.shape) != (P, 2)):
+        raise ValueError(f"centers must be int32 ({P}, 2), got {tuple(centers.shape)} {centers.dtype}")
+    dev = jobs[0][0].device
+    nbytes = np.asarray([int(np.prod(s)) for s in shapes], dtype=np.int64)
+    fresh = [j for j in range(J) if outs[j] is None]
+    if fresh:                                                    # one allocation, every view at a 16-byte boundary
+        offs = np.concatenate([[0], np.cumsum((nbytes[fresh] + 15) // 16 * 16)])
+        buf = torch.empty(int(offs[-1]), dtype=torch.uint8, device=dev)
+        for j, o in zip(fresh, offs[:-1]):
+            outs[j] = buf[int(o):int(o) + int(nbytes[j])].view(shapes[j])
+    src = np.asarray([job[0].data_ptr() for job in jobs], dtype=np.int64)
+    dst = np.asarray([o.data_ptr() for o in outs], dtype=np.int64)
+    _disjoint_jobs(src, dst, nbytes)
+    maps = rescaled.detach().contiguous()
+    cen = None if centers is None else centers.contiguous()
+    vector = [W % 4 == 0 and int(a) % 4 == 0 and int(b) % 4 == 0 for (_, _, W), a, b in zip(sizes, src, dst)]
+    first_row = overlay_group_table(sizes, vector)["first_row"]
+    take = list(range(J))
+    if layout:                                                   # the tiled byte path of 4:2:0 stays with the single-tensor kernel
+        take = [j for j in range(J) if vector[j]]
+        for j in range(J):
+            if not vector[j]:
+                sel = slice(int(first_row[j]), int(first_row[j]) + sizes[j][0])
+                gaze_overlay_yuv(jobs[j][0], maps[sel], rows[j], S, pixel_format, matrix=matrix, full_range=full_range,
+                                 centers=None if cen is None else cen[sel], alpha=alpha, radius=radius, out=outs[j])
+    if take:
+        t = overlay_group_table([sizes[j] for j in take], [vector[j] for j in take])
+        table = np.zeros((len(take), _OVG_COLS), dtype=np.int64)
+        table[:, 0], table[:, 1] = src[take], dst[take]
+        table[:, 2:5] = np.asarray([sizes[j] for j in take], dtype=np.int64)
+        table[:, 5:10] = np.asarray([rows[j] for j in take], dtype=np.int64)
+        table[:, 10], table[:, 11], table[:, 12] = first_row[take], t["first_workgroup"], t["vector"]
+        (d_jobs,) = _upload(dev, table)
+        args = (_p(d_jobs), table.ctypes.data, len(take), _p(maps), _p(cen), S, maps.shape[1], maps.shape[2], alpha, radius)
+        with torch.cuda.device(dev):
+            if layout:
+                L.check(_lib().csts_group_gaze_overlay_yuv(*args, layout, mat, fr, _stream()), "csts_group_gaze_overlay_yuv")
+            else:
+                L.check(_lib().csts_group_gaze_overlay(*args, _stream()), "csts_group_gaze_overlay")
+    return outs
+
+
+def group_points_source(points, jobs, crop_size):
+    """infer.points_to_source followed by infer.marker_centers for the rows of several jobs in ONE launch
+    (csts_group_points_source): points fp32 (P, 2) on the device, the rows of all jobs in job order; jobs a HOST list of (K,
+    params_row, H, W) -- K rows under that params row (new h, new w, y0, x0, flip) on a source of H x W; P = the sum of K ->
+    {"points_source": fp64 (P, 2), "centers": int32 (P, 2)}: x_src = (x S + x0) / new w in IEEE double arithmetic and
+    X = floor(x_src W), likewise y; a NaN point stays NaN and gets the centre (-1, -1).  Bit for bit what the two torch functions
+    give per job, on either device."""
+    import numpy as np
+    from .inputs import _upload
+    from .infer import overlay_group_table
+    _need_gpu(points)
+    jobs = [tuple(job) for job in jobs]
+    J, S = len(jobs), int(crop_size)
+    if J < 1 or J > 65535 or S < 1:
+        raise ValueError(f"group_points_source takes 1..65535 jobs and crop_size >= 1, got {J} and {S}")
+    table = np.zeros((J, _OVG_COLS), dtype=np.int64)
+    sizes = []
+    for j, job in enumerate(jobs):
+        try:
+            K, row, H, W = job
+            row = np.asarray(row)
+            if row.size != 5 or not np.issubdtype(row.dtype, np.integer):
+                raise ValueError(f"params must hold 5 integers (new h, new w, y0, x0, flip), got {job[1]!r}")
+            nh, nw, y0, x0, flip = (int(v) for v in row.reshape(5))
+            if not (1 <= nh <= 1 << 24 and 1 <= nw <= 1 << 24 and 0 <= y0 <= 1 << 24 and 0 <= x0 <= 1 << 24):
+                raise ValueError(f"params {(nh, nw, y0, x0)} are out of range (1 <= new h, new w <= 2^24, 0 <= y0, x0 <= 2^24)")
+            sizes.append((int(K), int(H), int(W)))
+            table[j, 2:10] = (int(K), int(H), int(W), nh, nw, y0, x0, flip)
+        except (ValueError, TypeError) as e:
+            raise ValueError(f"job {j}: {e}") from None
+    t = overlay_group_table(sizes, [False] * J)
+    table[:, 10], table[:, 11] = t["first_row"], t["first_workgroup"]
+    P = t["rows"]
+    if points.dtype != torch.float32 or tuple(points.shape) != (P, 2):
+        raise ValueError(f"points must be fp32 ({P}, 2), one row per frame of the jobs, got {tuple(points.shape)} {points.dtype}")
+    x = points.detach().contiguous()
+    out = {"points_source": torch.empty(P, 2, dtype=torch.float64, device=x.device),
+           "centers": torch.empty(P, 2, dtype=torch.int32, device=x.device)}
+    (d_jobs,) = _upload(x.device, table)
+    with torch.cuda.device(x.device):
+        L.check(_lib().csts_group_points_source(_p(d_jobs), table.ctypes.data, J, _p(x), S, _p(out["points_source"]),
+                                                _p(out["centers"]), _stream()), "csts_group_points_source")
     return out
 
 

@@ -12,7 +12,9 @@ recordings at once: its slots share one arena of rings, a tick's frames and samp
 (inputs.group_stft, inputs.group_ingest) and the windows of different slots that are ready together share a forward;
 ``group_schedule`` states on the host which windows share a batch.  ``GazeLiveGroup`` adds the live track to a group: the track
 rings of all slots share one arena, and a round folds its windows and answers its frames with one launch each
-(ops.group_live_add, ops.group_live_rows; ``group_live_schedule`` is the rule on the host)."""
+(ops.group_live_add, ops.group_live_rows; ``group_live_schedule`` is the rule on the host); what depends on a slot's own H x W --
+the points on the source frame and the overlay -- is one launch each as well, from a job table over slots of different sizes
+(ops.group_points_source, ops.group_gaze_overlay; ``infer.overlay_group_table`` is the rule on the host)."""
 from __future__ import annotations
 
 import numbers
@@ -989,7 +991,12 @@ class GazeLiveGroup(GazeStreamGroup):
       4. ONE ops.group_live_add: all the windows the round ran, over all slots, in (slot, window) order -- the rows a batch was
          padded with are not among them;
       5. ONE ops.group_live_rows: the frames the round took in, over all slots, in (slot, frame) order; the result is split per
-         slot.
+         slot;
+      6. ONE ops.group_points_source: the "points_source" and the marker centres of those rows, each under its slot's own params
+         row and H x W (infer.points_to_source and marker_centers, bit for bit);
+      7. with overlay=True, ONE ops.group_gaze_overlay: the round's chunks of all slots, each of its own size, drawn by one launch
+         from a job table (csts_group_gaze_overlay; csts_group_gaze_overlay_yuv when overlay_format names the frames' own
+         4:2:0 layout), into views of one allocation.
     That is GazeStream._push's order -- audio, frames, ready windows, fold, rows -- for every slot, so with results_i the windows
     the group emitted for slot i and known_i = group_live_schedule(plan, ticks, max_chunk, input_rate)[i],
 
@@ -1003,16 +1010,19 @@ class GazeLiveGroup(GazeStreamGroup):
     exactly a GazeStream.push_live dict ("frame_idx", "known", "points", "peak", "count", "neighbours", "filled", "rescaled",
     "points_source", and "overlay" with overlay=True); the rows of different rounds are concatenated in frame order, and a slot
     that pushed no frames gets the K = 0 dict.  push() folds the windows it runs as well, so push and push_live may be mixed; a
-    frame is only answered by the push_live that takes it in.  "points_source" and "overlay" are computed per slot, since each
-    slot has its own H x W: the overlay is predictor.render_track on that slot's frames of the round in the group's pixel
-    format, i.e. csts_gaze_overlay, one launch per slot and round.  A single overlay launch over slots of different sizes is
-    a follow-up.
+    frame is only answered by the push_live that takes it in.  "points_source" and "overlay" depend on a slot's own H x W; they
+    are computed for all slots together (steps 6 and 7) and each slot's are views of the round's: the bytes are those of
+    infer.points_to_source and of predictor.render_track on that slot's frames of the round, and a chunk that is not 4-byte
+    aligned takes the byte path (packed RGB) or the single-tensor 4:2:0 kernel inside ops.group_gaze_overlay, as render_track
+    sends it there.  One case stays per slot: 4:2:0 frames with an RGB overlay (pixel_format "nv12" | "i420" without
+    overlay_format) go through predictor.render_track, one inputs.yuv_to_rgb and one csts_gaze_overlay per slot and round,
+    because the RGB picture has to be made first; a grouped yuv_to_rgb is a later change.
 
     close() behaves as in the base class; the closing windows are not folded, as in GazeStream.close (no frame arrives after
     them).  reset(slot) reopens a closed slot and, unlike the base class's, writes to the device: see there.
 
-    Out of scope: live attention maps, one overlay launch for all slots, different plans per slot, and the command line
-    (tools/predict.py --videos still refuses --live and --overlay)."""
+    Out of scope: live attention maps, different plans per slot, and the command line (tools/predict.py --videos still refuses
+    --live and --overlay)."""
 
     def __init__(self, predictor, streams, live, fps=None, stride=None, segment=None, batch=4, max_chunk=32, pixel_format="rgb24",
                  matrix="bt601", full_range=False, input_rate=None, max_gap=None, overlay=False, alpha=0.4, radius=5,
@@ -1046,7 +1056,7 @@ class GazeLiveGroup(GazeStreamGroup):
 
     # ---- device work -----------------------------------------------------------------------------------------------------------
     def _round_done(self, ran, chunks):
-        """Steps 4 and 5 of a round: fold the windows it ran, then answer the frames it took in."""
+        """Steps 4 to 7 of a round: fold the windows it ran, answer the frames it took in, then their points_source and overlay."""
         import numpy as np
         import torch
         from . import ops
@@ -1074,18 +1084,26 @@ class GazeLiveGroup(GazeStreamGroup):
         rows["frame_idx"] = torch.from_numpy(frame_of).to(dev)
         known = np.concatenate([np.full(took[i], self.next_window[i], dtype=np.int32) for i, _ in chunks])
         rows["known"] = torch.from_numpy(known).to(dev)
+        # step 6: what depends on a slot's own H x W, for all slots at once
+        src = ops.group_points_source(rows["points"], [(took[i], self._rows[i], *self.hw[i]) for i, _ in chunks], self.S)
+        rows["points_source"] = src["points_source"]
+        overlays = None
+        if self.overlay and (not self.fmt or self.overlay_format):       # step 7; 4:2:0 in with RGB out stays per slot
+            overlays = ops.group_gaze_overlay([(chunk, self._rows[i]) for i, chunk in chunks], rows["rescaled"], src["centers"],
+                                              self.S, alpha=self.alpha, radius=self.radius, **self.fmt)
         at = 0
-        for i, chunk in chunks:
-            self._answers[i].append(self._slot_rows({k: v[at:at + took[i]] for k, v in rows.items()}, i, chunk))
+        for n, (i, chunk) in enumerate(chunks):
+            self._answers[i].append(self._slot_rows({k: v[at:at + took[i]] for k, v in rows.items()}, chunk,
+                                                    None if overlays is None else overlays[n]))
             at += took[i]
 
-    def _slot_rows(self, rows, i, chunk):
-        """What depends on slot i's H x W, added to its rows of one round: "points_source", and "overlay" on `chunk`, the frames."""
-        from .infer import points_to_source
-        rows["points_source"] = points_to_source(rows["points"], self._rows[i], self.S)
+    def _slot_rows(self, rows, chunk, overlay):
+        """Slot i's rows of one round, sliced from the round's; `overlay` its part of the round's overlay launch, or None when
+        there is none: then, with overlay=True, the slot's 4:2:0 frames are drawn in RGB by render_track."""
         if self.overlay:
-            rows["overlay"] = self.predictor.render_track(chunk, rows, alpha=self.alpha, radius=self.radius,
-                                                          out_format=self.overlay_format, **self.fmt)
+            rows["overlay"] = overlay if overlay is not None else \
+                self.predictor.render_track(chunk, rows, alpha=self.alpha, radius=self.radius, out_format=self.overlay_format,
+                                            **self.fmt)
         return rows
 
     def _live_empty(self, i):

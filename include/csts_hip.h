@@ -819,6 +819,51 @@ int csts_gaze_overlay_yuv(const uint8_t* frames_yuv, const float* rescaled, cons
                           int64_t N, int H, int W, int S, int mh, int mw, float alpha, int radius, int layout, int matrix,
                           int full_range, hipStream_t stream);
 
+/* ---- gaze overlay of a group (csts_amd/csrc/overlay.hip, csts_amd.GazeLiveGroup): the frames several streams pushed in one tick,
+ *      each stream of its own H x W, drawn by ONE launch from a job table, and their marker centres by one more.
+ *      jobs int64 [njobs][13], one row per job, in DEVICE memory, read when the kernel runs:
+ *        {0 source address, 1 destination address, 2 K frames, 3 H, 4 W, 5 new h, 6 new w, 7 y0, 8 x0, 9 flip (ignored, as
+ *         csts_gaze_overlay ignores it), 10 first row, 11 first workgroup, 12 vector flag}
+ *      columns 5..9 are the job's params row; first row = where the job's K rows start in rescaled [P][mh * mw] fp32 and centers
+ *      int32 [P][2] (NULL: no markers): the sum of K of the jobs before it when the table holds every job of P = the sum of K
+ *      (group_points_source requires that), and at least that for the overlays, whose table may leave jobs out; first workgroup =
+ *      the sum of K * ceil(H / 32) of the table's jobs before it.  The frames of a job are uint8 (K, H, W, 3), or (K, H * 3 / 2, W) in the one 4:2:0
+ *      layout, matrix and range of the call.  S, mh, mw, alpha and radius are one per call.  jobs_host is the HOST copy of the same
+ *      table: the entry validates it and sizes the launch from it before anything is launched, as csts_group_ingest does
+ *      (csts_amd.infer.overlay_group_table is the rule of columns 10..12 in Python).
+ *      The grid is the sum of K * ceil(H / 32) over the jobs.  A workgroup finds its job by binary search over column 11 (the
+ *      table is read through the scalar path: every index is uniform over the workgroup), then frame (g - first workgroup) /
+ *      bands and band (g - first workgroup) % bands, and from there on runs the code of csts_gaze_overlay /
+ *      csts_gaze_overlay_yuv's vector kernel on that band (one device function each): out of job j equals
+ *      csts_gaze_overlay(frames_j, rescaled[first row ..], centers[first row ..], params_j) byte for byte.
+ *      group_gaze_overlay: the vector flag chooses, per job, the 96-bit path (4 pixels a lane) or the byte path inside the one
+ *        launch; it may be set only when W % 4 == 0 and source and destination are 4-byte aligned, and may always be clear.
+ *      group_gaze_overlay_yuv: every job must be on the vector path (flag 1: W % 4 == 0, 4-byte aligned); a job that is not goes
+ *        through csts_gaze_overlay_yuv on its own (csts_amd.ops.group_gaze_overlay does that).  Even H, W; H <= 65534.
+ *      The dynamic LDS is that of the WIDEST job of the call (8 bytes a column + the map + 3.5 KB): a wide job lowers the
+ *      occupancy of the narrow jobs beside it (with a 64 x 64 map a workgroup takes 19.5 KB + 8 W bytes of a CU's 160 KB: five
+ *      workgroups a CU at W = 1088, four at W = 1920, one at W = 8192).  The launch is not split for that: a tick's streams
+ *      come from like cameras, and a second launch costs more than the occupancy.  csts_dyn_lds_optin is called above 64 KB.
+ *      A job whose row on the device disagrees with the launch (frame past K, W wider than the LDS) writes nothing.
+ *      In place (destination == source) is legal per job.  Otherwise no job's destination may overlap its own source, another
+ *      job's source or another job's destination: refused (-1), as are njobs outside 1..65535, a null address, K < 1, H > 65535,
+ *      W > 8192, a first row or first workgroup that is not the running sum, a vector flag on a job that cannot take it, P or
+ *      the grid >= 2^31.  One launch, no allocation, no host read of device memory, no atomics: graph-capturable.
+ *      group_points_source: points fp32 [P][2] = (x, y) on the S x S crop (csts_gaze_decode's `points`) -> points_source fp64
+ *        [P][2] and centers int32 [P][2]; columns 0, 1 and 12 of the table are not read.  For row p of job j (binary search over
+ *        column 10), in IEEE double arithmetic without contraction, each operation rounded once:
+ *          x_src = ((double)x * S + x0) / new w,  y_src = ((double)y * S + y0) / new h     (points_source)
+ *          X = (int)floor(x_src * W),  Y = (int)floor(y_src * H);  a NaN in either coordinate gives centers (-1, -1) and leaves
+ *          the NaN in points_source
+ *        -- csts_amd.infer.points_to_source followed by marker_centers, bit for bit.  One thread per row, one launch. */
+int csts_group_gaze_overlay(const int64_t* jobs, const int64_t* jobs_host, int njobs, const float* rescaled, const int* centers,
+                            int S, int mh, int mw, float alpha, int radius, hipStream_t stream);
+int csts_group_gaze_overlay_yuv(const int64_t* jobs, const int64_t* jobs_host, int njobs, const float* rescaled, const int* centers,
+                                int S, int mh, int mw, float alpha, int radius, int layout, int matrix, int full_range,
+                                hipStream_t stream);
+int csts_group_points_source(const int64_t* jobs, const int64_t* jobs_host, int njobs, const float* points, int S,
+                             double* points_source, int* centers, hipStream_t stream);
+
 /* ---- fusion attention maps (csts_amd/csrc/fusion_maps.hip): the audio-visual correlation map of the spatial fusion block, what
  *      vis_av_st_fusion of slowfast/visualization/visualization.py:172-228 draws per head: for every frame, how strongly each image
  *      region attends to that frame's audio token.  It reads what the block's forward already holds and forms no (N, N) matrix.
