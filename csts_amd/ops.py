@@ -2421,6 +2421,23 @@ def egonce(sim, temperature=0.05):
 _DECODE_OUTPUTS = ("preds", "rescaled", "points", "peak")
 
 
+def _wanted(want, allowed, table, device):
+    """The outputs of a wrapper that computes only what `want` names: {name: an empty tensor} for the rows (name, shape, dtype)
+    of `table` that are wanted.  A name outside `allowed`, or no name at all, is a ValueError."""
+    want = tuple(want)
+    if not want or [k for k in want if k not in allowed]:
+        raise ValueError(f"want must name some of {allowed}, got {want}")
+    return {k: torch.empty(shape, dtype=dt, device=device) for k, shape, dt in table if k in want}
+
+
+def _track_table(n, h, w):
+    """The per-frame outputs of the track wrappers for n frames of h x w maps, as _wanted takes them; each wrapper allows its own
+    subset of the names."""
+    f32, i32 = torch.float32, torch.int32
+    return (("heatmaps", (n, h, w), f32), ("rescaled", (n, h, w), f32), ("points", (n, 2), f32), ("peak", (n,), f32),
+            ("count", (n,), i32), ("neighbours", (n, 2), i32))
+
+
 def gaze_decode(logits, temperature=2.0, want=_DECODE_OUTPUTS):
     """csts_gaze_decode on the (B, 1, T, H, W) model output (fp32 or the library's 16-bit type): one read of each frame's logits
     gives preds = frame_softmax(logits, temperature) and rescaled = its per-frame min-max rescale (tools/test_avgaze_net.py:68-70),
@@ -2431,19 +2448,13 @@ def gaze_decode(logits, temperature=2.0, want=_DECODE_OUTPUTS):
     if logits.requires_grad and torch.is_grad_enabled():
         raise L.CstsError("gaze_decode is the inference head: it has no backward (call it under torch.no_grad(), or use "
                           "frame_softmax for a differentiable heat map)")
-    want = tuple(want)
-    unknown = [k for k in want if k not in _DECODE_OUTPUTS]
-    if unknown or not want:
-        raise ValueError(f"want must name some of {_DECODE_OUTPUTS}, got {want}")
     if logits.dim() != 5 or logits.shape[1] != 1:
         raise ValueError(f"logits must be (B, 1, T, H, W), got {tuple(logits.shape)}")
-    x = logits.detach().contiguous()
-    B, _, T, H, W = x.shape
-    dev = x.device
-    out = {}
-    for k, shape in (("preds", x.shape), ("rescaled", x.shape), ("points", (B, T, 2)), ("peak", (B, T))):
-        if k in want:
-            out[k] = torch.empty(shape, dtype=torch.float32, device=dev)
+    B, _, T, H, W = logits.shape
+    f32 = torch.float32
+    out = _wanted(want, _DECODE_OUTPUTS, (("preds", logits.shape, f32), ("rescaled", logits.shape, f32), ("points", (B, T, 2), f32),
+                                          ("peak", (B, T), f32)), logits.device)
+    x = logits.detach().contiguous()                             # after `want` is checked: a refusal launches nothing
     L.check(_lib().csts_gaze_decode(_p(x), _dt(x), B * T, H, W, float(temperature), _p(out.get("preds")), _p(out.get("rescaled")),
                                     _p(out.get("points")), _p(out.get("peak")), _stream()), "csts_gaze_decode")
     return out
@@ -2471,10 +2482,6 @@ def gaze_track(preds, target_idx, n_frames, want=_TRACK_OUTPUTS):
     Targets outside [0, n_frames) are dropped.  The row lists are built on the device (stable sort by target; the list
     bounds by a binary search of the sorted targets, which unlike torch.bincount reads nothing back): no host sync."""
     _need_gpu(preds, target_idx)
-    want = tuple(want)
-    unknown = [k for k in want if k not in _TRACK_OUTPUTS]
-    if unknown or not want:
-        raise ValueError(f"want must name some of {_TRACK_OUTPUTS}, got {want}")
     if preds.dim() != 3 or preds.dtype != torch.float32:
         raise ValueError(f"preds must be fp32 (P, H, W), got {tuple(preds.shape)} {preds.dtype}")
     P, H, W = preds.shape
@@ -2483,15 +2490,9 @@ def gaze_track(preds, target_idx, n_frames, want=_TRACK_OUTPUTS):
         raise ValueError(f"target_idx must be int64 ({P},), got {tuple(target_idx.shape)} {target_idx.dtype}")
     if n_frames < 1 or P < 1:
         raise ValueError(f"gaze_track needs P >= 1 maps and n_frames >= 1, got {P} and {n_frames}")
+    out = _wanted(want, _TRACK_OUTPUTS, _track_table(n_frames, H, W), preds.device)
     x = preds.detach().contiguous()
-    dev = x.device
     order, offsets = _target_lists(target_idx, n_frames)
-    out = {}
-    for k, shape, dt in (("heatmaps", (n_frames, H, W), torch.float32), ("rescaled", (n_frames, H, W), torch.float32),
-                         ("points", (n_frames, 2), torch.float32), ("peak", (n_frames,), torch.float32),
-                         ("count", (n_frames,), torch.int32)):
-        if k in want:
-            out[k] = torch.empty(shape, dtype=dt, device=dev)
     L.check(_lib().csts_gaze_track(_p(x), _p(order), _p(offsets), n_frames, H, W, _p(out.get("heatmaps")), _p(out.get("rescaled")),
                                    _p(out.get("points")), _p(out.get("peak")), _p(out.get("count")), _stream()), "csts_gaze_track")
     return out
@@ -2511,10 +2512,6 @@ def gaze_track_fill(heatmaps, count, mode="linear", max_gap=9, want=_FILL_OUTPUT
     Returns a dict of the outputs named in `want` (new tensors: the inputs are not written).  One launch, no host sync: it can
     be captured in a graph.  The rule is stated in include/csts_hip.h and restated on the host by infer.fill_plan."""
     _need_gpu(heatmaps, count)
-    want = tuple(want)
-    unknown = [k for k in want if k not in _FILL_OUTPUTS]
-    if unknown or not want:
-        raise ValueError(f"want must name some of {_FILL_OUTPUTS}, got {want}")
     if mode not in _FILL_MODES:
         raise ValueError(f"mode must be one of {_FILL_MODES}, got {mode!r}")
     if heatmaps.dim() != 3 or heatmaps.dtype != torch.float32:
@@ -2524,14 +2521,9 @@ def gaze_track_fill(heatmaps, count, mode="linear", max_gap=9, want=_FILL_OUTPUT
         raise ValueError(f"count must be int32 ({F},), got {tuple(count.shape)} {count.dtype}")
     if F < 1:
         raise ValueError(f"gaze_track_fill needs F >= 1 frames, got {F}")
+    out = _wanted(want, _FILL_OUTPUTS, _track_table(F, H, W), heatmaps.device)
     x = heatmaps.detach().contiguous()
     c = count.contiguous()
-    dev = x.device
-    out = {}
-    for k, shape, dt in (("heatmaps", (F, H, W), torch.float32), ("rescaled", (F, H, W), torch.float32),
-                         ("points", (F, 2), torch.float32), ("peak", (F,), torch.float32), ("neighbours", (F, 2), torch.int32)):
-        if k in want:
-            out[k] = torch.empty(shape, dtype=dt, device=dev)
     L.check(_lib().csts_gaze_track_fill(_p(x), _p(c), F, H, W, _FILL_MODES.index(mode), int(max_gap), _p(out.get("heatmaps")),
                                         _p(out.get("rescaled")), _p(out.get("points")), _p(out.get("peak")),
                                         _p(out.get("neighbours")), _stream()), "csts_gaze_track_fill")
@@ -2545,34 +2537,80 @@ _LIVE_OUTPUTS = ("heatmaps", "rescaled", "points", "peak", "count", "neighbours"
 def live_track_ring(slots, h, w, device):
     """An empty track ring of `slots` frames of h x w maps on `device`: {"sum" fp32 (slots, h, w) zeros, "count" int32 (slots,)
     zeros, "frame" int64 (slots,) -1}.  Frame t lives in slot t mod slots (include/csts_hip.h, live gaze track)."""
-    slots, h, w = int(slots), int(h), int(w)
-    if slots < 1 or slots > 65535 or h < 1 or w < 1 or h * w > L.GAZE_DECODE_MAX_HW:
-        raise ValueError(f"a track ring holds 1..65535 slots of maps with h * w <= {L.GAZE_DECODE_MAX_HW}, got {slots} of {h} x {w}")
+    return _new_track_ring((), slots, h, w, device)
+
+
+def _ring_sizes_ok(lead, Rt, h, w):
+    """The sizes a track ring, or with lead = (streams,) an arena of them, may have; ValueError otherwise."""
+    if Rt < 1 or Rt > 65535 or h < 1 or w < 1 or h * w > L.GAZE_DECODE_MAX_HW:
+        raise ValueError(f"a track ring holds 1..65535 slots of maps with h * w <= {L.GAZE_DECODE_MAX_HW}, got {Rt} of {h} x {w}")
+    if lead and (lead[0] < 1 or lead[0] > 65535 or lead[0] * Rt >= 2 ** 31):
+        raise ValueError(f"a track arena holds 1..65535 rings and fewer than 2^31 slots, got {lead[0]} rings of {Rt}")
+
+
+def _new_track_ring(lead, slots, h, w, device):
+    """live_track_ring (lead = ()) and group_live_ring (lead = (streams,)): the same three tensors under `lead`."""
+    lead, slots, h, w = tuple(int(v) for v in lead), int(slots), int(h), int(w)
+    _ring_sizes_ok(lead, slots, h, w)
     device = torch.device(device)
     if device.type != "cuda":
-        raise L.CstsError("the track ring lives on MI355X only (there is no CPU fallback)")
-    return {"sum": torch.zeros(slots, h, w, dtype=torch.float32, device=device),
-            "count": torch.zeros(slots, dtype=torch.int32, device=device),
-            "frame": torch.full((slots,), -1, dtype=torch.int64, device=device)}
+        raise L.CstsError(f"the track {'arena' if lead else 'ring'} lives on MI355X only (there is no CPU fallback)")
+    return {"sum": torch.zeros(*lead, slots, h, w, dtype=torch.float32, device=device),
+            "count": torch.zeros(*lead, slots, dtype=torch.int32, device=device),
+            "frame": torch.full((*lead, slots), -1, dtype=torch.int64, device=device)}
 
 
-def _check_live_ring(ring):
-    """The three tensors of a track ring, checked: (sum, count, frame, Rt, h, w)."""
+def _check_live_ring(ring, arena=False):
+    """The three tensors of a track ring, or of an arena of rings, checked: (sum, count, frame, streams, Rt, h, w); streams is
+    None for a single ring."""
     try:
         s, c, f = ring["sum"], ring["count"], ring["frame"]
     except (KeyError, TypeError, IndexError):
-        raise ValueError("ring must be a dict with \"sum\", \"count\" and \"frame\" (ops.live_track_ring)")
+        raise ValueError(f"ring must be a dict with \"sum\", \"count\" and \"frame\" (ops.{'group_live_ring' if arena else 'live_track_ring'})")
     _need_gpu(s, c, f)
-    if s.dim() != 3 or s.dtype != torch.float32 or not s.is_contiguous():
-        raise ValueError(f"ring[\"sum\"] must be contiguous fp32 (Rt, h, w), got {tuple(s.shape)} {s.dtype}")
-    Rt, h, w = s.shape
-    if c.dtype != torch.int32 or tuple(c.shape) != (Rt,) or not c.is_contiguous():
-        raise ValueError(f"ring[\"count\"] must be contiguous int32 ({Rt},), got {tuple(c.shape)} {c.dtype}")
-    if f.dtype != torch.int64 or tuple(f.shape) != (Rt,) or not f.is_contiguous():
-        raise ValueError(f"ring[\"frame\"] must be contiguous int64 ({Rt},), got {tuple(f.shape)} {f.dtype}")
-    if Rt < 1 or Rt > 65535 or h * w < 1 or h * w > L.GAZE_DECODE_MAX_HW:
-        raise ValueError(f"a track ring holds 1..65535 slots of maps with h * w <= {L.GAZE_DECODE_MAX_HW}, got {Rt} of {h} x {w}")
-    return s, c, f, Rt, h, w
+    if s.dim() != (4 if arena else 3) or s.dtype != torch.float32 or not s.is_contiguous():
+        raise ValueError(f"ring[\"sum\"] must be contiguous fp32 ({'streams, ' if arena else ''}Rt, h, w), got {tuple(s.shape)} {s.dtype}")
+    slots = tuple(s.shape[:-2])                                  # (Rt,), or (streams, Rt) in an arena: one count and tag each
+    if c.dtype != torch.int32 or tuple(c.shape) != slots or not c.is_contiguous():
+        raise ValueError(f"ring[\"count\"] must be contiguous int32 {slots}, got {tuple(c.shape)} {c.dtype}")
+    if f.dtype != torch.int64 or tuple(f.shape) != slots or not f.is_contiguous():
+        raise ValueError(f"ring[\"frame\"] must be contiguous int64 {slots}, got {tuple(f.shape)} {f.dtype}")
+    Rt, h, w = s.shape[-3:]
+    _ring_sizes_ok(slots[:-1], Rt, h, w)
+    return s, c, f, (slots[0] if arena else None), Rt, h, w
+
+
+def _check_live_maps(name, maps, target_idx, h, w):
+    """The maps and device targets of live_track_add / group_live_add, checked against the ring's h x w -> P, their number."""
+    if maps.dim() != 3 or maps.dtype != torch.float32 or tuple(maps.shape[1:]) != (h, w):
+        raise ValueError(f"maps must be fp32 (P, {h}, {w}), got {tuple(maps.shape)} {maps.dtype}")
+    P = maps.shape[0]
+    if target_idx.dtype != torch.int64 or tuple(target_idx.shape) != (P,):
+        raise ValueError(f"target_idx must be int64 ({P},), got {tuple(target_idx.shape)} {target_idx.dtype}")
+    if P < 1 or P > 65535:
+        raise ValueError(f"{name} takes 1..65535 maps a call, got {P}")
+    return P
+
+
+def _live_host_table(values, n, name, of):
+    """The host copy of a device table of n integers, as an int64 numpy array."""
+    import numpy as np
+    if torch.is_tensor(values):
+        raise ValueError(f"{name} is the host copy of {of}: a sequence or numpy array of ints, not a tensor")
+    host = np.asarray(values)
+    if host.shape != (n,) or not np.issubdtype(host.dtype, np.integer):
+        raise ValueError(f"{name} must hold the {n} entries of {of} as integers on the host, got shape {host.shape} {host.dtype}")
+    return host.astype(np.int64)
+
+
+def _check_rows_mode(mode, max_gap):
+    """The fill rule of live_track_rows / group_live_rows, checked -> max_gap as an int."""
+    if mode not in _FILL_MODES:
+        raise ValueError(f"mode must be one of {_FILL_MODES}, got {mode!r}")
+    max_gap = int(max_gap)
+    if max_gap < 1 or max_gap > L.GAZE_FILL_MAX_GAP:
+        raise ValueError(f"max_gap must lie in 1..{L.GAZE_FILL_MAX_GAP}, got {max_gap}")
+    return max_gap
 
 
 def live_track_add(maps, target_idx, targets, ring, live_from=0):
@@ -2584,21 +2622,10 @@ def live_track_add(maps, target_idx, targets, ring, live_from=0):
     that what cannot be written is refused before the launch and without a host sync: a negative target, and a target
     t >= live_from + Rt, which would overwrite the slot of frame t - Rt >= live_from.  live_from: the lowest frame whose row may
     still be asked for, minus max_gap - 1 (a row reads that far back).  One launch, no atomics, no host sync."""
-    import numpy as np
     _need_gpu(maps, target_idx)
-    s, c, f, Rt, h, w = _check_live_ring(ring)
-    if maps.dim() != 3 or maps.dtype != torch.float32 or tuple(maps.shape[1:]) != (h, w):
-        raise ValueError(f"maps must be fp32 (P, {h}, {w}), got {tuple(maps.shape)} {maps.dtype}")
-    P = maps.shape[0]
-    if target_idx.dtype != torch.int64 or tuple(target_idx.shape) != (P,):
-        raise ValueError(f"target_idx must be int64 ({P},), got {tuple(target_idx.shape)} {target_idx.dtype}")
-    if P < 1 or P > 65535:
-        raise ValueError(f"live_track_add takes 1..65535 maps a call, got {P}")
-    if torch.is_tensor(targets):
-        raise ValueError("targets are the host copy of target_idx: a sequence or numpy array of ints, not a tensor")
-    host = np.asarray(targets)
-    if host.shape != (P,) or not np.issubdtype(host.dtype, np.integer):
-        raise ValueError(f"targets must hold the {P} targets as integers on the host, got shape {host.shape} {host.dtype}")
+    s, c, f, _, Rt, h, w = _check_live_ring(ring)
+    P = _check_live_maps("live_track_add", maps, target_idx, h, w)
+    host = _live_host_table(targets, P, "targets", "target_idx")
     live_from = int(live_from)
     if int(host.min()) < 0:
         raise ValueError(f"targets must be frame numbers >= 0, got {int(host.min())}")
@@ -2618,25 +2645,12 @@ def live_track_rows(ring, f0, K, mode="linear", max_gap=9, want=_LIVE_OUTPUTS):
     (K, h, w), points (K, 2), peak (K,), count int32 (K,) (0 on a filled or unpredicted frame) and neighbours int32 (K, 2).  A
     slot that holds another frame counts as empty.  Returns the outputs named in `want`; the others are not computed.  The ring
     is only read.  One launch, no host sync: it can be captured in a graph."""
-    s, c, f, Rt, h, w = _check_live_ring(ring)
-    want = tuple(want)
-    unknown = [k for k in want if k not in _LIVE_OUTPUTS]
-    if unknown or not want:
-        raise ValueError(f"want must name some of {_LIVE_OUTPUTS}, got {want}")
-    if mode not in _FILL_MODES:
-        raise ValueError(f"mode must be one of {_FILL_MODES}, got {mode!r}")
-    f0, K, max_gap = int(f0), int(K), int(max_gap)
+    s, c, f, _, Rt, h, w = _check_live_ring(ring)
+    max_gap = _check_rows_mode(mode, max_gap)
+    f0, K = int(f0), int(K)
     if f0 < 0 or K < 1 or K > 65535 or f0 + K + max_gap >= 2 ** 31:
         raise ValueError(f"live_track_rows answers 1..65535 frames from f0 >= 0 with f0 + K + max_gap < 2^31, got f0 {f0}, K {K}")
-    if max_gap < 1 or max_gap > L.GAZE_FILL_MAX_GAP:
-        raise ValueError(f"max_gap must lie in 1..{L.GAZE_FILL_MAX_GAP}, got {max_gap}")
-    dev = s.device
-    out = {}
-    for k, shape, dt in (("heatmaps", (K, h, w), torch.float32), ("rescaled", (K, h, w), torch.float32),
-                         ("points", (K, 2), torch.float32), ("peak", (K,), torch.float32), ("count", (K,), torch.int32),
-                         ("neighbours", (K, 2), torch.int32)):
-        if k in want:
-            out[k] = torch.empty(shape, dtype=dt, device=dev)
+    out = _wanted(want, _LIVE_OUTPUTS, _track_table(K, h, w), s.device)
     L.check(_lib().csts_live_track_rows(_p(s), _p(c), _p(f), Rt, f0, K, h, w, _FILL_MODES.index(mode), max_gap,
                                         _p(out.get("heatmaps")), _p(out.get("rescaled")), _p(out.get("points")), _p(out.get("peak")),
                                         _p(out.get("count")), _p(out.get("neighbours")), _stream()), "csts_live_track_rows")
@@ -2648,49 +2662,7 @@ def group_live_ring(streams, slots, h, w, device):
     """An empty arena of `streams` track rings of `slots` frames of h x w maps on `device`: {"sum" fp32 (streams, slots, h, w)
     zeros, "count" int32 (streams, slots) zeros, "frame" int64 (streams, slots) -1}.  Frame t of slot i lives at [i, t mod slots];
     the ring of slot i is the ring live_track_ring(slots, h, w) describes (include/csts_hip.h, live track of a stream group)."""
-    streams, slots, h, w = int(streams), int(slots), int(h), int(w)
-    if slots < 1 or slots > 65535 or h < 1 or w < 1 or h * w > L.GAZE_DECODE_MAX_HW:
-        raise ValueError(f"a track ring holds 1..65535 slots of maps with h * w <= {L.GAZE_DECODE_MAX_HW}, got {slots} of {h} x {w}")
-    if streams < 1 or streams > 65535 or streams * slots >= 2 ** 31:
-        raise ValueError(f"a track arena holds 1..65535 rings and fewer than 2^31 slots, got {streams} rings of {slots}")
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise L.CstsError("the track arena lives on MI355X only (there is no CPU fallback)")
-    return {"sum": torch.zeros(streams, slots, h, w, dtype=torch.float32, device=device),
-            "count": torch.zeros(streams, slots, dtype=torch.int32, device=device),
-            "frame": torch.full((streams, slots), -1, dtype=torch.int64, device=device)}
-
-
-def _check_group_live_ring(ring):
-    """The three tensors of a track arena, checked: (sum, count, frame, streams, Rt, h, w)."""
-    try:
-        s, c, f = ring["sum"], ring["count"], ring["frame"]
-    except (KeyError, TypeError, IndexError):
-        raise ValueError("ring must be a dict with \"sum\", \"count\" and \"frame\" (ops.group_live_ring)")
-    _need_gpu(s, c, f)
-    if s.dim() != 4 or s.dtype != torch.float32 or not s.is_contiguous():
-        raise ValueError(f"ring[\"sum\"] must be contiguous fp32 (streams, Rt, h, w), got {tuple(s.shape)} {s.dtype}")
-    n, Rt, h, w = s.shape
-    if c.dtype != torch.int32 or tuple(c.shape) != (n, Rt) or not c.is_contiguous():
-        raise ValueError(f"ring[\"count\"] must be contiguous int32 ({n}, {Rt}), got {tuple(c.shape)} {c.dtype}")
-    if f.dtype != torch.int64 or tuple(f.shape) != (n, Rt) or not f.is_contiguous():
-        raise ValueError(f"ring[\"frame\"] must be contiguous int64 ({n}, {Rt}), got {tuple(f.shape)} {f.dtype}")
-    if Rt < 1 or Rt > 65535 or h * w < 1 or h * w > L.GAZE_DECODE_MAX_HW:
-        raise ValueError(f"a track ring holds 1..65535 slots of maps with h * w <= {L.GAZE_DECODE_MAX_HW}, got {Rt} of {h} x {w}")
-    if n < 1 or n > 65535 or n * Rt >= 2 ** 31:
-        raise ValueError(f"a track arena holds 1..65535 rings and fewer than 2^31 slots, got {n} rings of {Rt}")
-    return s, c, f, n, Rt, h, w
-
-
-def _live_host_table(values, n, name, of):
-    """The host copy of a device table of n integers, as an int64 numpy array."""
-    import numpy as np
-    if torch.is_tensor(values):
-        raise ValueError(f"{name} is the host copy of {of}: a sequence or numpy array of ints, not a tensor")
-    host = np.asarray(values)
-    if host.shape != (n,) or not np.issubdtype(host.dtype, np.integer):
-        raise ValueError(f"{name} must hold the {n} entries of {of} as integers on the host, got shape {host.shape} {host.dtype}")
-    return host.astype(np.int64)
+    return _new_track_ring((streams,), slots, h, w, device)
 
 
 def group_live_add(maps, target_idx, stream_of, targets, streams_host, ring, live_from):
@@ -2705,16 +2677,10 @@ def group_live_add(maps, target_idx, stream_of, targets, streams_host, ring, liv
     the arena untouched.  One launch, no atomics, no host sync."""
     import numpy as np
     _need_gpu(maps, target_idx, stream_of)
-    s, c, f, n, Rt, h, w = _check_group_live_ring(ring)
-    if maps.dim() != 3 or maps.dtype != torch.float32 or tuple(maps.shape[1:]) != (h, w):
-        raise ValueError(f"maps must be fp32 (P, {h}, {w}), got {tuple(maps.shape)} {maps.dtype}")
-    P = maps.shape[0]
-    if target_idx.dtype != torch.int64 or tuple(target_idx.shape) != (P,):
-        raise ValueError(f"target_idx must be int64 ({P},), got {tuple(target_idx.shape)} {target_idx.dtype}")
+    s, c, f, n, Rt, h, w = _check_live_ring(ring, arena=True)
+    P = _check_live_maps("group_live_add", maps, target_idx, h, w)
     if stream_of.dtype != torch.int32 or tuple(stream_of.shape) != (P,):
         raise ValueError(f"stream_of must be int32 ({P},), got {tuple(stream_of.shape)} {stream_of.dtype}")
-    if P < 1 or P > 65535:
-        raise ValueError(f"group_live_add takes 1..65535 maps a call, got {P}")
     host_t = _live_host_table(targets, P, "targets", "target_idx")
     host_s = _live_host_table(streams_host, P, "streams_host", "stream_of")
     if torch.is_tensor(live_from):
@@ -2746,16 +2712,8 @@ def group_live_rows(ring, stream_of, frame_of, mode="linear", max_gap=9, want=_L
     0, neighbours (-1, -1)).  The outputs are live_track_rows', K rows in the order of the tables, those named in `want`.  The
     arena is only read.  One launch, no host sync."""
     import numpy as np
-    s, c, f, n, Rt, h, w = _check_group_live_ring(ring)
-    want = tuple(want)
-    unknown = [k for k in want if k not in _LIVE_OUTPUTS]
-    if unknown or not want:
-        raise ValueError(f"want must name some of {_LIVE_OUTPUTS}, got {want}")
-    if mode not in _FILL_MODES:
-        raise ValueError(f"mode must be one of {_FILL_MODES}, got {mode!r}")
-    max_gap = int(max_gap)
-    if max_gap < 1 or max_gap > L.GAZE_FILL_MAX_GAP:
-        raise ValueError(f"max_gap must lie in 1..{L.GAZE_FILL_MAX_GAP}, got {max_gap}")
+    s, c, f, n, Rt, h, w = _check_live_ring(ring, arena=True)
+    max_gap = _check_rows_mode(mode, max_gap)
     K = len(frame_of)
     if K < 1 or K > 65535:
         raise ValueError(f"group_live_rows answers 1..65535 frames a call, got {K}")
@@ -2765,15 +2723,9 @@ def group_live_rows(ring, stream_of, frame_of, mode="linear", max_gap=9, want=_L
         raise ValueError(f"group_live_rows answers frames >= 0 with frame + max_gap < 2^31, got {int(host_f.min())}..{int(host_f.max())}")
     if int(host_s.min()) < -2 ** 31 or int(host_s.max()) >= 2 ** 31:
         raise ValueError("stream_of holds int32 stream numbers")
-    dev = s.device
-    streams_dev = torch.from_numpy(host_s.astype(np.int32)).to(dev)
-    frames_dev = torch.from_numpy(host_f).to(dev)
-    out = {}
-    for k, shape, dt in (("heatmaps", (K, h, w), torch.float32), ("rescaled", (K, h, w), torch.float32),
-                         ("points", (K, 2), torch.float32), ("peak", (K,), torch.float32), ("count", (K,), torch.int32),
-                         ("neighbours", (K, 2), torch.int32)):
-        if k in want:
-            out[k] = torch.empty(shape, dtype=dt, device=dev)
+    out = _wanted(want, _LIVE_OUTPUTS, _track_table(K, h, w), s.device)
+    streams_dev = torch.from_numpy(host_s.astype(np.int32)).to(s.device)
+    frames_dev = torch.from_numpy(host_f).to(s.device)
     L.check(_lib().csts_group_live_rows(_p(s), _p(c), _p(f), n, Rt, _p(streams_dev), _p(frames_dev), K, h, w,
                                         _FILL_MODES.index(mode), max_gap, _p(out.get("heatmaps")), _p(out.get("rescaled")),
                                         _p(out.get("points")), _p(out.get("peak")), _p(out.get("count")), _p(out.get("neighbours")),
@@ -2801,19 +2753,49 @@ def _overlay_params(params, crop_size, device):
     return torch.tensor(_host_params_row(params, crop_size), dtype=torch.int32, device=device)
 
 
-def _host_params_row(params, crop_size):
-    """A params row given on the host, checked against the sampler's range: [new h, new w, y0, x0, 0]."""
+def _parse_params_row(params):
+    """A params row given on the host as five Python ints: (new h, new w, y0, x0, flip)."""
     import numpy as np
     row = np.asarray(params)
     if row.size != 5 or not np.issubdtype(row.dtype, np.integer):
         raise ValueError(f"params must hold 5 integers (new h, new w, y0, x0, flip), got {params!r}")
-    nh, nw, y0, x0, flip = (int(v) for v in row.reshape(5))
+    return tuple(int(v) for v in row.reshape(5))
+
+
+def _host_params_row(params, crop_size):
+    """A params row given on the host, checked against the sampler's range: [new h, new w, y0, x0, 0]."""
+    nh, nw, y0, x0, flip = _parse_params_row(params)
     if flip != 0:
         raise ValueError("gaze_overlay draws test-mode crops, which are never flipped: params has flip != 0")
     S = int(crop_size)
     if nh < S or nw < S or not 0 <= y0 <= nh - S or not 0 <= x0 <= nw - S:
         raise ValueError(f"params {(nh, nw, y0, x0)} do not hold a {S} x {S} crop")
     return [nh, nw, y0, x0, 0]
+
+
+def _check_overlay_args(name, pairs, rescaled, centers, alpha, radius, crop_size, per_job=False):
+    """What gaze_overlay, gaze_overlay_yuv and group_gaze_overlay (`name`) check alike -> (alpha, radius, crop_size) as float, int,
+    int.  pairs: [(frames, out or None)], the frames already checked for dtype and dimensions; rescaled fp32 (N, mh, mw) and
+    centers int32 (N, 2) or None hold one row per frame of all the pairs.  alpha lies in [0, 1], radius is >= 0, crop_size and N
+    are >= 1; frames are contiguous and an `out` is a contiguous uint8 tensor of its frames' shape, the message about pair j
+    prefixed "job j: " with per_job."""
+    N = sum([int(frames.shape[0]) for frames, _ in pairs])
+    if rescaled.dtype != torch.float32 or rescaled.dim() != 3 or rescaled.shape[0] != N:
+        raise ValueError(f"rescaled must be fp32 ({N}, mh, mw), got {tuple(rescaled.shape)} {rescaled.dtype}")
+    if centers is not None and (centers.dtype != torch.int32 or tuple(centers.shape) != (N, 2)):
+        raise ValueError(f"centers must be int32 ({N}, 2), got {tuple(centers.shape)} {centers.dtype}")
+    alpha, radius, S = float(alpha), int(radius), int(crop_size)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha must lie in [0, 1], got {alpha}")
+    if radius < 0 or S < 1 or N < 1:
+        raise ValueError(f"{name} needs N >= 1 frames, crop_size >= 1 and radius >= 0, got {N}, {S} and {radius}")
+    for j, (frames, out) in enumerate(pairs):
+        job = f"job {j}: " if per_job else ""
+        if not frames.is_contiguous():
+            raise ValueError(f"{job}frames must be contiguous")
+        if out is not None and (out.dtype != torch.uint8 or out.shape != frames.shape or not out.is_contiguous()):
+            raise ValueError(f"{job}out must be contiguous uint8 {tuple(frames.shape)}, got {tuple(out.shape)} {out.dtype}")
+    return alpha, radius, S
 
 
 def gaze_overlay(frames_u8, rescaled, params, crop_size, centers=None, alpha=0.4, radius=5, out=None):
@@ -2827,21 +2809,9 @@ def gaze_overlay(frames_u8, rescaled, params, crop_size, centers=None, alpha=0.4
     if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
         raise ValueError(f"frames must be uint8 (N, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
     N, H, W, _ = frames_u8.shape
-    if rescaled.dtype != torch.float32 or rescaled.dim() != 3 or rescaled.shape[0] != N:
-        raise ValueError(f"rescaled must be fp32 ({N}, mh, mw), got {tuple(rescaled.shape)} {rescaled.dtype}")
-    if centers is not None and (centers.dtype != torch.int32 or tuple(centers.shape) != (N, 2)):
-        raise ValueError(f"centers must be int32 ({N}, 2), got {tuple(centers.shape)} {centers.dtype}")
-    alpha, radius, S = float(alpha), int(radius), int(crop_size)
-    if not 0.0 <= alpha <= 1.0:
-        raise ValueError(f"alpha must lie in [0, 1], got {alpha}")
-    if radius < 0 or S < 1 or N < 1:
-        raise ValueError(f"gaze_overlay needs N >= 1 frames, crop_size >= 1 and radius >= 0, got {N}, {S} and {radius}")
-    if not frames_u8.is_contiguous():
-        raise ValueError("frames must be contiguous (N, H, W, 3)")
+    alpha, radius, S = _check_overlay_args("gaze_overlay", [(frames_u8, out)], rescaled, centers, alpha, radius, crop_size)
     if out is None:
         out = torch.empty_like(frames_u8)
-    elif out.dtype != torch.uint8 or out.shape != frames_u8.shape or not out.is_contiguous():
-        raise ValueError(f"out must be contiguous uint8 {tuple(frames_u8.shape)}, got {tuple(out.shape)} {out.dtype}")
     par = _overlay_params(params, S, frames_u8.device)
     maps = rescaled.detach().contiguous()
     cen = None if centers is None else centers.contiguous()
@@ -2869,21 +2839,9 @@ def gaze_overlay_yuv(frames_yuv, rescaled, params, crop_size, pixel_format, matr
         raise ValueError(f"{pixel_format} frames must be uint8 (N, H * 3 / 2, W), got {tuple(frames_yuv.shape)} {frames_yuv.dtype}")
     H, W = _yuv_hw(frames_yuv.shape, pixel_format)
     N = frames_yuv.shape[0]
-    if rescaled.dtype != torch.float32 or rescaled.dim() != 3 or rescaled.shape[0] != N:
-        raise ValueError(f"rescaled must be fp32 ({N}, mh, mw), got {tuple(rescaled.shape)} {rescaled.dtype}")
-    if centers is not None and (centers.dtype != torch.int32 or tuple(centers.shape) != (N, 2)):
-        raise ValueError(f"centers must be int32 ({N}, 2), got {tuple(centers.shape)} {centers.dtype}")
-    alpha, radius, S = float(alpha), int(radius), int(crop_size)
-    if not 0.0 <= alpha <= 1.0:
-        raise ValueError(f"alpha must lie in [0, 1], got {alpha}")
-    if radius < 0 or S < 1 or N < 1:
-        raise ValueError(f"gaze_overlay_yuv needs N >= 1 frames, crop_size >= 1 and radius >= 0, got {N}, {S} and {radius}")
-    if not frames_yuv.is_contiguous():
-        raise ValueError("frames must be contiguous (N, H * 3 / 2, W)")
+    alpha, radius, S = _check_overlay_args("gaze_overlay_yuv", [(frames_yuv, out)], rescaled, centers, alpha, radius, crop_size)
     if out is None:
         out = torch.empty_like(frames_yuv)
-    elif out.dtype != torch.uint8 or out.shape != frames_yuv.shape or not out.is_contiguous():
-        raise ValueError(f"out must be contiguous uint8 {tuple(frames_yuv.shape)}, got {tuple(out.shape)} {out.dtype}")
     a, b, nbytes = frames_yuv.data_ptr(), out.data_ptr(), frames_yuv.numel()
     if a != b and a < b + nbytes and b < a + nbytes:
         raise ValueError("out must be the frames themselves (in place) or share no memory with them")
@@ -2942,12 +2900,8 @@ def group_gaze_overlay(jobs, rescaled, centers, crop_size, alpha=0.4, radius=5, 
     outs = [None] * J if outs is None else list(outs)
     if len(outs) != J:
         raise ValueError(f"outs must hold one entry per job ({J}), got {len(outs)}")
-    alpha, radius, S = float(alpha), int(radius), int(crop_size)
-    if not 0.0 <= alpha <= 1.0:
-        raise ValueError(f"alpha must lie in [0, 1], got {alpha}")
-    if radius < 0 or S < 1:
-        raise ValueError(f"group_gaze_overlay needs crop_size >= 1 and radius >= 0, got {S} and {radius}")
     _need_gpu(rescaled, centers)
+    S = int(crop_size)
     sizes, rows, shapes = [], [], []
     for j, job in enumerate(jobs):
         try:
@@ -2966,11 +2920,6 @@ def group_gaze_overlay(jobs, rescaled, centers, crop_size, alpha=0.4, radius=5, 
                 raise ValueError(f"frames must hold K >= 1 frames of H, W >= 1, got {tuple(frames.shape)}")
             if W > 8192 or H > 65535:
                 raise ValueError(f"frames wider than 8192 or taller than 65535 pixels are not supported, got {H} x {W}")
-            if not frames.is_contiguous():
-                raise ValueError("frames must be contiguous")
-            o = outs[j]
-            if o is not None and (o.dtype != torch.uint8 or o.shape != frames.shape or not o.is_contiguous()):
-                raise ValueError(f"out must be contiguous uint8 {tuple(frames.shape)}, got {tuple(o.shape)} {o.dtype}")
             rows.append(_host_params_row(row, S))
         except L.CstsError as e:
             raise L.CstsError(f"job {j}: {e}") from None
@@ -2978,11 +2927,8 @@ def group_gaze_overlay(jobs, rescaled, centers, crop_size, alpha=0.4, radius=5, 
             raise ValueError(f"job {j}: {e}") from None
         sizes.append((K, H, W))
         shapes.append(frames.shape)
-    P = sum(s[0] for s in sizes)
-    if rescaled.dtype != torch.float32 or rescaled.dim() != 3 or rescaled.shape[0] != P:
-        raise ValueError(f"rescaled must be fp32 ({P}, mh, mw), one row per frame of the jobs, got {tuple(rescaled.shape)} {rescaled.dtype}")
-    if centers is not None and (centers.dtype != torch.int32 or tuple(centers.shape) != (P, 2)):
-        raise ValueError(f"centers must be int32 ({P}, 2), got {tuple(centers.shape)} {centers.dtype}")
+    alpha, radius, S = _check_overlay_args("group_gaze_overlay", [(job[0], o) for job, o in zip(jobs, outs)], rescaled, centers, alpha,
+                                           radius, S, per_job=True)
     dev = jobs[0][0].device
     nbytes = np.asarray([int(np.prod(s)) for s in shapes], dtype=np.int64)
     fresh = [j for j in range(J) if outs[j] is None]
@@ -3043,10 +2989,7 @@ def group_points_source(points, jobs, crop_size):
     for j, job in enumerate(jobs):
         try:
             K, row, H, W = job
-            row = np.asarray(row)
-            if row.size != 5 or not np.issubdtype(row.dtype, np.integer):
-                raise ValueError(f"params must hold 5 integers (new h, new w, y0, x0, flip), got {job[1]!r}")
-            nh, nw, y0, x0, flip = (int(v) for v in row.reshape(5))
+            nh, nw, y0, x0, flip = _parse_params_row(row)
             if not (1 <= nh <= 1 << 24 and 1 <= nw <= 1 << 24 and 0 <= y0 <= 1 << 24 and 0 <= x0 <= 1 << 24):
                 raise ValueError(f"params {(nh, nw, y0, x0)} are out of range (1 <= new h, new w <= 2^24, 0 <= y0, x0 <= 2^24)")
             sizes.append((int(K), int(H), int(W)))

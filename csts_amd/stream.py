@@ -14,7 +14,9 @@ recordings at once: its slots share one arena of rings, a tick's frames and samp
 rings of all slots share one arena, and a round folds its windows and answers its frames with one launch each
 (ops.group_live_add, ops.group_live_rows; ``group_live_schedule`` is the rule on the host); what depends on a slot's own H x W --
 the points on the source frame and the overlay -- is one launch each as well, from a job table over slots of different sizes
-(ops.group_points_source, ops.group_gaze_overlay; ``infer.overlay_group_table`` is the rule on the host)."""
+(ops.group_points_source, ops.group_gaze_overlay; ``infer.overlay_group_table`` is the rule on the host).  What a stream and a
+slot of a group do alike on the host is written once, in the functions from ``check_live_args`` to ``live_empty`` that the three
+classes call; each class keeps its own device calls and its own allocation timing."""
 from __future__ import annotations
 
 import numbers
@@ -291,6 +293,183 @@ def track_from_windows(results, n_frames, want=("points", "peak", "count", "heat
     return track
 
 
+# ---- the host rules of one stream: GazeStream follows them on its scalars, the groups on each slot's entries -------------------------
+
+def _open(s, predictor, fps, stride, segment, max_chunk, pixel_format, matrix, full_range, input_rate):
+    """The fields every stream class derives from its predictor, plan and format arguments, set on `s`: input_rate, fmt,
+    predictor, plan, S, T, mean, std, R, ring_cols.  Returns ring_sizes(plan, max_chunk, S)."""
+    from . import inputs
+    s.input_rate = None if input_rate is None else inputs.check_sample_rate(input_rate, "input_rate")
+    s.fmt = {}
+    if inputs.check_pixel_format(pixel_format, matrix, full_range)[0]:
+        s.fmt = {"pixel_format": pixel_format, "matrix": matrix, "full_range": bool(full_range)}
+    s.predictor = predictor
+    cfg = predictor.cfg
+    s.plan = plan_stream(cfg, fps=fps, stride=stride, segment=segment)
+    s.S, s.T = int(cfg.DATA.TEST_CROP_SIZE), int(cfg.DATA.NUM_FRAMES)
+    s.mean, s.std = tuple(cfg.DATA.MEAN), tuple(cfg.DATA.STD)
+    sizes = ring_sizes(s.plan, max_chunk, s.S)
+    s.R, s.ring_cols = sizes["slots"], sizes["ring_cols"]
+    return sizes
+
+
+def check_live_args(plan, max_chunk, crop_size, fmt, live, max_gap, overlay, alpha, radius, overlay_format, required=False):
+    """The live and overlay arguments of a constructor, checked as GazeStream documents them -> (max_gap, overlay_format,
+    track_slots, track_bytes), (None, None, 0, 0) without live.  required: live may not be None (a GazeLiveGroup).  fmt: the
+    format keywords of the frames, {} for packed RGB.  overlay_format comes back as None unless it names their 4:2:0 layout;
+    track_bytes counts the ring's fp32 sums plus a count and a frame tag per slot."""
+    from .infer import _overlay_yuv, default_max_gap
+    if required and live not in LIVE_MODES:
+        raise ValueError(f"live must be one of {LIVE_MODES}, got {live!r}")
+    if live is not None and live not in LIVE_MODES:
+        raise ValueError(f"live must be None or one of {LIVE_MODES}, got {live!r}")
+    if overlay and live is None:
+        raise ValueError("overlay=True draws the live track onto the pushed frames: it needs live=\"hold\" or live=\"linear\"")
+    if max_gap is not None and live is None:
+        raise ValueError("max_gap is the gap the live track fills: it needs live=\"hold\" or live=\"linear\"")
+    if overlay_format is not None and not overlay:
+        raise ValueError("overlay_format belongs to the overlay: pass overlay=True")
+    # the overlay in the pushed frames' own 4:2:0 layout (render_track(out_format=...)) instead of RGB
+    overlay_format = overlay_format if _overlay_yuv(overlay_format, fmt, "overlay_format") else None
+    if live is None:
+        return None, None, 0, 0
+    check_live_plan(plan)
+    gap = default_max_gap(plan) if max_gap is None else int(max_gap)
+    if gap < 1:
+        raise ValueError(f"max_gap must be positive, got {max_gap}")
+    if not 0.0 <= float(alpha) <= 1.0 or int(radius) < 0:
+        raise ValueError(f"alpha must lie in [0, 1] and radius be >= 0, got {alpha} and {radius}")
+    track_slots = live_ring_slots(plan, max_chunk, gap)
+    side = int(crop_size) // 4                               # the model's heat maps are S/4 x S/4
+    return gap, overlay_format, track_slots, track_slots * (side * side * 4 + 4 + 8)
+
+
+def check_piece(who, closed, hw, fmt, resampler, frames, wav):
+    """What a push checks and counts of one piece before anything is consumed -> (k, hw, m_in, m): k frames of hw = (H, W) (the
+    stream's `hw` when there are no frames), m_in samples as they were pushed, m 24 kHz samples they make final (the
+    resampler's check and count, which consume nothing).  A closed stream, an input that is not a GPU tensor (CstsError; `who`
+    names the class), a wrong shape or dtype, and an H x W other than the stream's are refused."""
+    import torch
+    from . import lib as L
+    from .infer import _picture_hw
+    if closed:
+        raise ValueError("the stream is closed: push() after close()")
+    for t in (frames, wav):
+        if t is not None and (not torch.is_tensor(t) or not t.is_cuda):
+            raise L.CstsError(f"{who} runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
+    k = m = m_in = 0
+    if frames is not None:
+        H, W, _ = _picture_hw(frames, 1, fmt.get("pixel_format", "rgb24"), fmt.get("matrix", "bt601"), fmt.get("full_range", False))
+        if hw is not None and (H, W) != hw:
+            raise ValueError(f"the stream's frames are {hw[0]} x {hw[1]} (fixed by the first push), got {H} x {W}")
+        k, hw = frames.shape[0], (H, W)
+    if wav is not None and resampler is not None:
+        m_in = resampler.check(wav)
+        m = resampler.count(m_in, wav)                       # the 24 kHz samples this piece makes final
+    elif wav is not None:
+        if wav.dim() != 1 or wav.dtype != torch.float32:
+            raise ValueError(f"wav must be an fp32 (m,) waveform at {AUDIO_RATE} Hz, got {tuple(wav.shape)} {wav.dtype}")
+        m_in = m = wav.numel()
+    return k, hw, m_in, m
+
+
+def audio_tail_step(samples, cols, tail, tail_base, piece, n_total, ring_cols):
+    """The audio step of a stream with `samples` 24 kHz samples taken, columns [0, cols) final and the waveform tail `tail` (None
+    before the first audio) starting at sample tail_base: take `piece` (1-D, possibly empty) -> (samples, cols, tail, tail_base,
+    buf, ranges).  buf = tail + piece, starting at the OLD tail_base, is the buffer to launch on; ranges [(f0, f1)] are the
+    columns to compute from it, ascending, each at most one turn of the ring.  Column f is final once sample 120 f + 119 is in;
+    n_total >= 0: the signal has ended, the columns are the offline STFT's (csts_stft_frames).  The new tail starts at the first
+    sample column `cols` reads; it is a view of buf, which the caller clones so that buf can go."""
+    import torch
+    buf = piece if tail is None else torch.cat([tail, piece])
+    samples += piece.numel()
+    final = samples // STFT_HOP
+    if n_total >= 0:
+        final = max(final, 1 + (samples + 2 * (STFT_N_FFT // 2) - STFT_N_FFT) // STFT_HOP)
+    ranges = [(f0, min(f0 + ring_cols, final)) for f0 in range(cols, final, ring_cols)]
+    cols = max(cols, final)
+    keep = max(0, STFT_HOP * cols + (STFT_N_FFT - STFT_WIN) // 2 - STFT_N_FFT // 2)
+    keep = max(keep, tail_base)
+    return samples, cols, buf[keep - tail_base:], keep, buf, ranges
+
+
+def closing_flush(plan, slots, ring_cols, next_window, samples, held):
+    """How many of the `held` samples a resampler gives up at close() the spectrum ring still takes (ring_limits)."""
+    return max(0, min(held, ring_limits(stream_window(plan, next_window), slots, ring_cols)[1] - samples))
+
+
+def closing_windows(plan, next_window, frames, cols, started=True):
+    """The windows close() runs: from next_window on, every window whose frames are in and whose last audio column lies inside
+    the `cols` final columns (the padded last column included).  started: some frame has been pushed."""
+    ready, w = [], next_window
+    nxt = stream_window(plan, w)
+    while started and nxt["ready_frames"] <= frames and int(nxt["audio_centers"].max()) + HALF_WIDTH <= cols:
+        ready.append(w)
+        w += 1
+        nxt = stream_window(plan, w)
+    return ready
+
+
+def dropped_windows(plan, next_window, frames):
+    """The windows from next_window on that began -- their first input frame was pushed -- and will not run."""
+    w = next_window
+    while int(stream_window(plan, w)["frames_idx"][0]) < frames:
+        w += 1
+    return w - next_window
+
+
+def pad_rows(rows, batch):
+    """A batch of `batch` rows: a short one is padded by repeating its last row, so one graph shape serves every batch."""
+    return rows + [rows[-1]] * (batch - len(rows))
+
+
+def crop_audio(audio, S):
+    """S frequency bins x S columns around each frame, as predict_video cuts them (nothing to cut at S = AUDIO_WIDTH)."""
+    if S == AUDIO_WIDTH:
+        return audio
+    o = (AUDIO_WIDTH - S) // 2
+    return audio[:, :, :, :S, o:o + S].contiguous()
+
+
+def window_result(r, out, b, stream=None):
+    """The dict of one emitted window: r its stream_window, row b of predict_batch's `out`; a group names the slot in "stream"."""
+    res = {} if stream is None else {"stream": stream}
+    res.update({"window": r["window"], "frames_idx": r["frames_idx"], "target_idx": r["target_idx"], "points": out["points"][b],
+                "peak": out["peak"][b], "heatmaps": out["heatmaps"][b], "rescaled": out["rescaled"][b]})
+    return res
+
+
+def live_fields(rows, frame_idx, known):
+    """What a live answer adds to the rows of ops.live_track_rows / group_live_rows, in place: "filled" (no prediction of its own,
+    but neighbours to fill from), "frame_idx" int64 (K,) and "known" int32 (K,), the windows each row was computed from."""
+    rows["filled"] = (rows["count"] == 0) & (rows["neighbours"][:, 0] >= 0)
+    rows["frame_idx"] = frame_idx
+    rows["known"] = known
+    return rows
+
+
+def live_empty(side, device, hw=None, overlay=False, overlay_format=None):
+    """The live dict of a push without frames, K = 0: every field of push_live with its shape and dtype; with overlay the frames'
+    shape at the stream's H x W (0 x 0 before the first frame), (0, H * 3 / 2, W) when overlay_format names a 4:2:0 layout."""
+    import torch
+    shapes = {"frame_idx": ((0,), torch.int64), "known": ((0,), torch.int32), "points": ((0, 2), torch.float32),
+              "peak": ((0,), torch.float32), "count": ((0,), torch.int32), "neighbours": ((0, 2), torch.int32),
+              "filled": ((0,), torch.bool), "rescaled": ((0, side, side), torch.float32),
+              "points_source": ((0, 2), torch.float64)}
+    out = {k: torch.empty(shape, dtype=dt, device=device) for k, (shape, dt) in shapes.items()}
+    if overlay:
+        H, W = hw if hw is not None else (0, 0)
+        shape = (0, H * 3 // 2, W) if overlay_format else (0, H, W, 3)
+        out["overlay"] = torch.empty(shape, dtype=torch.uint8, device=device)
+    return out
+
+
+def _cat_rows(rows):
+    """The live dicts of several steps or rounds as one, in frame order."""
+    import torch
+    return rows[0] if len(rows) == 1 else {key: torch.cat([r[key] for r in rows], dim=0) for key in rows[0]}
+
+
 class GazeStream:
     """Gaze prediction while the recording is still running (reach it through GazePredictor.stream).
 
@@ -351,63 +530,28 @@ class GazeStream:
                  matrix="bt601", full_range=False, sample_rate=None, input_rate=None, live=None, max_gap=None, overlay=False,
                  alpha=0.4, radius=5, overlay_format=None):
         check_stream_rate(sample_rate)
-        if live is not None and live not in LIVE_MODES:
-            raise ValueError(f"live must be None or one of {LIVE_MODES}, got {live!r}")
-        if overlay and live is None:
-            raise ValueError("overlay=True draws the live track onto the pushed frames: it needs live=\"hold\" or live=\"linear\"")
-        if max_gap is not None and live is None:
-            raise ValueError("max_gap is the gap the live track fills: it needs live=\"hold\" or live=\"linear\"")
         from . import inputs
         if input_rate is not None and sample_rate is not None:
             raise ValueError(f"sample_rate={sample_rate!r} says the audio is pushed at {AUDIO_RATE} Hz as it is, input_rate="
                              f"{input_rate!r} that it is resampled from that rate: pass one of them")
-        self.input_rate = None if input_rate is None else inputs.check_sample_rate(input_rate, "input_rate")
-        self.resampler = None if input_rate is None else inputs.StreamResampler(self.input_rate)
-        self.input_samples = 0                               # source samples consumed (= samples without input_rate)
-        self.fmt = {}
-        if inputs.check_pixel_format(pixel_format, matrix, full_range)[0]:
-            self.fmt = {"pixel_format": pixel_format, "matrix": matrix, "full_range": bool(full_range)}
-        if overlay_format is not None and not overlay:
-            raise ValueError("overlay_format belongs to the overlay: pass overlay=True")
-        from .infer import _overlay_yuv
-        # the overlay in the pushed frames' own 4:2:0 layout (render_track(out_format=...)) instead of RGB
-        self.overlay_format = overlay_format if _overlay_yuv(overlay_format, self.fmt, "overlay_format") else None
         self.batch, self.max_chunk = int(batch), int(max_chunk)
         if self.batch < 1 or self.max_chunk < 1:
             raise ValueError(f"batch and max_chunk must be positive, got {batch} and {max_chunk}")
-        self.predictor = predictor
-        cfg = predictor.cfg
-        self.plan = plan_stream(cfg, fps=fps, stride=stride, segment=segment)
-        self.S, self.T = int(cfg.DATA.TEST_CROP_SIZE), int(cfg.DATA.NUM_FRAMES)
-        self.mean, self.std = tuple(cfg.DATA.MEAN), tuple(cfg.DATA.STD)
-        self.capacity = ring_sizes(self.plan, self.max_chunk, self.S)
-        self.R, self.ring_cols = self.capacity["slots"], self.capacity["ring_cols"]
+        self.capacity = _open(self, predictor, fps, stride, segment, self.max_chunk, pixel_format, matrix, full_range, input_rate)
+        self.live, self.overlay, self.alpha, self.radius = live, bool(overlay), float(alpha), int(radius)
+        self.max_gap, self.overlay_format, self.track_slots, track_bytes = check_live_args(
+            self.plan, self.max_chunk, self.S, self.fmt, live, max_gap, overlay, alpha, radius, overlay_format)
+        if live is not None:
+            self.capacity = dict(self.capacity, track_slots=self.track_slots, track_bytes=track_bytes)
+        self.resampler = None if input_rate is None else inputs.StreamResampler(self.input_rate)
+        self.input_samples = 0                               # source samples consumed (= samples without input_rate)
         self.frames = self.samples = self.cols = 0          # pushed so far; columns [0, cols) are final
         self.next_window, self.dropped, self.closed = 0, 0, False
         self.hw = None
-        self._next = stream_window(self.plan, 0)
-        self._crops = self._spec = self._tail = self._params = None
+        self._crops = self._spec = self._tail = self._params = self._track = None
         self._tail_base = 0                                  # the stream position of _tail[0]
-        self.live, self.overlay, self.alpha, self.radius = live, bool(overlay), float(alpha), int(radius)
-        self.max_gap, self.track_slots, self._track = None, 0, None
-        if live is not None:
-            from .infer import default_max_gap
-            check_live_plan(self.plan)
-            self.max_gap = default_max_gap(self.plan) if max_gap is None else int(max_gap)
-            if self.max_gap < 1:
-                raise ValueError(f"max_gap must be positive, got {max_gap}")
-            if not 0.0 <= self.alpha <= 1.0 or self.radius < 0:
-                raise ValueError(f"alpha must lie in [0, 1] and radius be >= 0, got {alpha} and {radius}")
-            self.track_slots = live_ring_slots(self.plan, self.max_chunk, self.max_gap)
-            side = self.S // 4                               # the model's heat maps are S/4 x S/4
-            self.capacity = dict(self.capacity, track_slots=self.track_slots,
-                                 track_bytes=self.track_slots * (side * side * 4 + 4 + 8))
 
     # ---- host arithmetic -------------------------------------------------------------------------------------------------------
-    def _limits(self, nxt):
-        """(frames, samples) the rings take while window `nxt` is the oldest one that has not run."""
-        return ring_limits(nxt, self.R, self.ring_cols)
-
     def _steps(self, k, m):
         """The steps a push of k frames and m samples is worked off in: [(frames, samples, [windows])]; ValueError when stuck."""
         return stream_steps(self.plan, self.R, self.ring_cols, self.max_chunk, self.frames, self.samples, self.next_window, k, m)
@@ -425,18 +569,12 @@ class GazeStream:
         from . import inputs
         if self._spec is None:
             self._spec = torch.zeros(STFT_N_FFT // 2 + 1, self.ring_cols, dtype=torch.float32, device=piece.device)
-        buf = piece if self._tail is None else torch.cat([self._tail, piece])
-        self.samples += piece.numel()
-        cols = self.samples // STFT_HOP                     # column f is final once sample 120 f + 119 is in
-        if n_total >= 0:                                    # the signal ended: the columns of the offline STFT (csts_stft_frames)
-            cols = max(cols, 1 + (self.samples + 2 * (STFT_N_FFT // 2) - STFT_N_FFT) // STFT_HOP)
-        for f0 in range(self.cols, cols, self.ring_cols):   # at most one turn of the ring per launch
-            inputs.stream_stft(buf.contiguous(), self._tail_base, f0, min(f0 + self.ring_cols, cols), self._spec, n_total=n_total)
-        self.cols = max(self.cols, cols)
-        keep = max(0, STFT_HOP * self.cols + (STFT_N_FFT - STFT_WIN) // 2 - STFT_N_FFT // 2)      # first sample column `cols` reads
-        keep = max(keep, self._tail_base)
-        self._tail = buf[keep - self._tail_base:].clone()
-        self._tail_base = keep
+        base = self._tail_base
+        self.samples, self.cols, tail, self._tail_base, buf, ranges = audio_tail_step(
+            self.samples, self.cols, self._tail, base, piece, n_total, self.ring_cols)
+        for f0, f1 in ranges:                                # at most one turn of the ring per launch
+            inputs.stream_stft(buf.contiguous(), base, f0, f1, self._spec, n_total=n_total)
+        self._tail = tail.clone()
 
     def _ingest(self, chunk):
         import torch
@@ -452,26 +590,18 @@ class GazeStream:
         import numpy as np
         import torch
         from . import inputs
-        dev = self._crops.device
-        S, T, nb = self.S, self.T, self.batch
+        dev, nb = self._crops.device, self.batch
         results = []
         for g in range(0, len(windows), nb):
             group = [stream_window(self.plan, w) for w in windows[g:g + nb]]
-            rows = group + [group[-1]] * (nb - len(group))              # pad by repeating the last window
+            rows = pad_rows(group, nb)
             slots = np.stack([r["frames_idx"] % self.R for r in rows]).astype(np.int32)
             centers = np.stack([r["audio_centers"] for r in rows]).astype(np.int64)
             video = inputs.stream_gather(self._crops, torch.from_numpy(slots).to(dev))
             audio = inputs.stream_audio_windows(self._spec, self.cols - 1, torch.from_numpy(centers).to(dev), centers, AUDIO_WIDTH)
-            if S != AUDIO_WIDTH:   # S frequency bins x S columns around each frame, as predict_video cuts them
-                o = (AUDIO_WIDTH - S) // 2
-                audio = audio[:, :, :, :S, o:o + S].contiguous()
-            out = self.predictor.predict_batch({"video": video, "audio": audio})
-            for i, r in enumerate(group):
-                results.append({"window": r["window"], "frames_idx": r["frames_idx"], "target_idx": r["target_idx"],
-                                "points": out["points"][i], "peak": out["peak"][i], "heatmaps": out["heatmaps"][i],
-                                "rescaled": out["rescaled"][i]})
+            out = self.predictor.predict_batch({"video": video, "audio": crop_audio(audio, self.S)})
+            results += [window_result(r, out, i) for i, r in enumerate(group)]
         self.next_window = windows[-1] + 1
-        self._next = stream_window(self.plan, self.next_window)
         return results
 
     # ---- the interface ---------------------------------------------------------------------------------------------------------
@@ -516,59 +646,23 @@ class GazeStream:
             self._track = ops.live_track_ring(self.track_slots, side, side, dev)
         rows = ops.live_track_rows(self._track, f0, K, mode=self.live, max_gap=self.max_gap,
                                    want=("rescaled", "points", "peak", "count", "neighbours"))
-        rows["filled"] = (rows["count"] == 0) & (rows["neighbours"][:, 0] >= 0)
-        rows["frame_idx"] = torch.arange(f0, f0 + K, dtype=torch.int64, device=dev)
-        rows["known"] = torch.full((K,), self.next_window, dtype=torch.int32, device=dev)
+        live_fields(rows, torch.arange(f0, f0 + K, dtype=torch.int64, device=dev),
+                    torch.full((K,), self.next_window, dtype=torch.int32, device=dev))
         rows["points_source"] = points_to_source(rows["points"], self.predictor._video_params_row(*self.hw), self.S)
         if self.overlay:
             rows["overlay"] = self.predictor.render_track(chunk, rows, alpha=self.alpha, radius=self.radius,
                                                           out_format=self.overlay_format, **self.fmt)
         return rows
 
-    def _live_empty(self, device):
-        """The live dict of a push without frames."""
-        import torch
-        side = self.S // 4
-        shapes = {"frame_idx": ((0,), torch.int64), "known": ((0,), torch.int32), "points": ((0, 2), torch.float32),
-                  "peak": ((0,), torch.float32), "count": ((0,), torch.int32), "neighbours": ((0, 2), torch.int32),
-                  "filled": ((0,), torch.bool), "rescaled": ((0, side, side), torch.float32),
-                  "points_source": ((0, 2), torch.float64)}
-        out = {k: torch.empty(shape, dtype=dt, device=device) for k, (shape, dt) in shapes.items()}
-        if self.overlay:
-            H, W = self.hw if self.hw is not None else (0, 0)
-            shape = (0, H * 3 // 2, W) if self.overlay_format else (0, H, W, 3)
-            out["overlay"] = torch.empty(shape, dtype=torch.uint8, device=device)
-        return out
-
     def _push(self, frames, wav, want_live):
         import torch
-        from . import lib as L
-        from .infer import _picture_hw
-        if self.closed:
-            raise ValueError("the stream is closed: push() after close()")
-        for t in (frames, wav):
-            if t is not None and (not torch.is_tensor(t) or not t.is_cuda):
-                raise L.CstsError("GazeStream runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
-        k = m = 0
-        if frames is not None:
-            H, W, _ = _picture_hw(frames, 1, self.fmt.get("pixel_format", "rgb24"), self.fmt.get("matrix", "bt601"),
-                                  self.fmt.get("full_range", False))
-            if self.hw is not None and (H, W) != self.hw:
-                raise ValueError(f"the stream's frames are {self.hw[0]} x {self.hw[1]} (fixed by the first push), got {H} x {W}")
-            k = frames.shape[0]
-        if wav is not None and self.resampler is not None:
-            m_in = self.resampler.check(wav)
-            m = self.resampler.count(m_in, wav)              # the 24 kHz samples this piece makes final
-        elif wav is not None:
-            if wav.dim() != 1 or wav.dtype != torch.float32:
-                raise ValueError(f"wav must be an fp32 (m,) waveform at {AUDIO_RATE} Hz, got {tuple(wav.shape)} {wav.dtype}")
-            m_in = m = wav.numel()
+        k, hw, m_in, m = check_piece("GazeStream", self.closed, self.hw, self.fmt, self.resampler, frames, wav)
         steps = self._steps(k, m)                            # raises before anything is consumed, the resampler included
         results, rows = [], []
         fa = sa = 0
         with torch.no_grad(), torch.cuda.device(self.predictor.device):
             if k and self.hw is None:
-                self._setup(H, W, frames.device)
+                self._setup(*hw, frames.device)
             if wav is not None:
                 self.input_samples += m_in
                 if self.resampler is not None:
@@ -591,8 +685,8 @@ class GazeStream:
                 return results, None
             if not rows:
                 dev = frames.device if frames is not None else (wav.device if wav is not None else self.predictor.device)
-                return results, self._live_empty(dev)
-            live = rows[0] if len(rows) == 1 else {key: torch.cat([r[key] for r in rows], dim=0) for key in rows[0]}
+                return results, live_empty(self.S // 4, dev, self.hw, self.overlay, self.overlay_format)
+            live = _cat_rows(rows)
         return results, live
 
     def close(self, wav_pad=True):
@@ -608,23 +702,15 @@ class GazeStream:
         with torch.no_grad(), torch.cuda.device(self.predictor.device):
             if self.resampler is not None:                   # the outputs held back; as many of them as the spectrum ring takes
                 rest = self.resampler.close()
-                rest = rest[:max(0, min(rest.numel(), self._limits(self._next)[1] - self.samples))]
+                rest = rest[:closing_flush(self.plan, self.R, self.ring_cols, self.next_window, self.samples, rest.numel())]
                 if rest.numel():
                     self._audio(rest)
             if wav_pad and self._tail is not None:
                 self._audio(self._tail[:0], n_total=self.samples)
-            ready, w, nxt = [], self.next_window, self._next
-            while self._crops is not None and nxt["ready_frames"] <= self.frames and \
-                    int(nxt["audio_centers"].max()) + HALF_WIDTH <= self.cols:
-                ready.append(w)
-                w += 1
-                nxt = stream_window(self.plan, w)
+            ready = closing_windows(self.plan, self.next_window, self.frames, self.cols, started=self._crops is not None)
             if ready:
                 results = self._run(ready)
-        w = self.next_window
-        while int(stream_window(self.plan, w)["frames_idx"][0]) < self.frames:
-            self.dropped += 1
-            w += 1
+        self.dropped += dropped_windows(self.plan, self.next_window, self.frames)
         return results
 
 
@@ -730,17 +816,7 @@ class GazeStreamGroup:
         self.streams, self.batch, self.max_chunk = int(streams), int(batch), int(max_chunk)
         if self.streams < 1 or self.batch < 1 or self.max_chunk < 1:
             raise ValueError(f"streams, batch and max_chunk must be positive, got {streams}, {batch} and {max_chunk}")
-        self.input_rate = None if input_rate is None else inputs.check_sample_rate(input_rate, "input_rate")
-        self.fmt = {}
-        if inputs.check_pixel_format(pixel_format, matrix, full_range)[0]:
-            self.fmt = {"pixel_format": pixel_format, "matrix": matrix, "full_range": bool(full_range)}
-        self.predictor = predictor
-        cfg = predictor.cfg
-        self.plan = plan_stream(cfg, fps=fps, stride=stride, segment=segment)
-        self.S, self.T = int(cfg.DATA.TEST_CROP_SIZE), int(cfg.DATA.NUM_FRAMES)
-        self.mean, self.std = tuple(cfg.DATA.MEAN), tuple(cfg.DATA.STD)
-        sizes = ring_sizes(self.plan, self.max_chunk, self.S)
-        self.R, self.ring_cols = sizes["slots"], sizes["ring_cols"]
+        sizes = _open(self, predictor, fps, stride, segment, self.max_chunk, pixel_format, matrix, full_range, input_rate)
         self.capacity = dict(sizes, streams=self.streams, total_bytes=self.streams * (sizes["crop_bytes"] + sizes["spec_bytes"]))
         n = self.streams
         self.frames, self.samples, self.input_samples, self.cols = [0] * n, [0] * n, [0] * n, [0] * n
@@ -759,29 +835,7 @@ class GazeStreamGroup:
 
     def _plan_slot(self, i, frames, wav):
         """What GazeStream._push checks and counts before it consumes anything, on slot i: (k, (H, W), m_in, m, steps)."""
-        import torch
-        from . import lib as L
-        from .infer import _picture_hw
-        if self.closed[i]:
-            raise ValueError("the stream is closed: push() after close()")
-        for t in (frames, wav):
-            if t is not None and (not torch.is_tensor(t) or not t.is_cuda):
-                raise L.CstsError("GazeStreamGroup runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
-        k = m = m_in = 0
-        hw = self.hw[i]
-        if frames is not None:
-            H, W, _ = _picture_hw(frames, 1, self.fmt.get("pixel_format", "rgb24"), self.fmt.get("matrix", "bt601"),
-                                  self.fmt.get("full_range", False))
-            if hw is not None and (H, W) != hw:
-                raise ValueError(f"the stream's frames are {hw[0]} x {hw[1]} (fixed by the first push), got {H} x {W}")
-            k, hw = frames.shape[0], (H, W)
-        if wav is not None and self._resamplers[i] is not None:
-            m_in = self._resamplers[i].check(wav)
-            m = self._resamplers[i].count(m_in, wav)
-        elif wav is not None:
-            if wav.dim() != 1 or wav.dtype != torch.float32:
-                raise ValueError(f"wav must be an fp32 (m,) waveform at {AUDIO_RATE} Hz, got {tuple(wav.shape)} {wav.dtype}")
-            m_in = m = wav.numel()
+        k, hw, m_in, m = check_piece("GazeStreamGroup", self.closed[i], self.hw[i], self.fmt, self._resamplers[i], frames, wav)
         steps = stream_steps(self.plan, self.R, self.ring_cols, self.max_chunk, self.frames[i], self.samples[i],
                              self.next_window[i], k, m)
         return k, hw, m_in, m, steps
@@ -789,26 +843,17 @@ class GazeStreamGroup:
     # ---- device work -----------------------------------------------------------------------------------------------------------
     def _audio(self, jobs):
         """jobs: [(slot, the next samples of that slot, n_total)], distinct slots: the columns they complete, in one launch."""
-        import torch
         from . import inputs
         pending = []
         for i, piece, n_total in jobs:
-            buf = piece if self._tail[i] is None else torch.cat([self._tail[i], piece])
-            self.samples[i] += piece.numel()
-            cols = self.samples[i] // STFT_HOP               # column f is final once sample 120 f + 119 is in
-            if n_total >= 0:                                 # the signal ended: the columns of the offline STFT
-                cols = max(cols, 1 + (self.samples[i] + 2 * (STFT_N_FFT // 2) - STFT_N_FFT) // STFT_HOP)
-            pending.append([buf.contiguous(), self._tail_base[i], self.cols[i], cols, i, n_total])
-            self.cols[i] = max(self.cols[i], cols)
-            keep = max(0, STFT_HOP * self.cols[i] + (STFT_N_FFT - STFT_WIN) // 2 - STFT_N_FFT // 2)
-            keep = max(keep, self._tail_base[i])
-            self._tail[i] = buf[keep - self._tail_base[i]:].clone()
-            self._tail_base[i] = keep
-        while any(p[2] < p[3] for p in pending):             # at most one turn of a ring per launch
-            turn = [(buf, base, f0, min(f0 + self.ring_cols, f1), i, n_total) for buf, base, f0, f1, i, n_total in pending if f0 < f1]
-            inputs.group_stft(turn, self._spec)
-            for p in pending:
-                p[2] = min(p[2] + self.ring_cols, p[3])
+            base = self._tail_base[i]
+            self.samples[i], self.cols[i], tail, self._tail_base[i], buf, ranges = audio_tail_step(
+                self.samples[i], self.cols[i], self._tail[i], base, piece, n_total, self.ring_cols)
+            pending.append((buf.contiguous(), base, ranges, i, n_total))
+            self._tail[i] = tail.clone()
+        for t in range(max((len(p[2]) for p in pending), default=0)):       # at most one turn of a ring per launch
+            inputs.group_stft([(buf, base, *ranges[t], i, n_total) for buf, base, ranges, i, n_total in pending if t < len(ranges)],
+                              self._spec)
 
     def _ingest(self, jobs):
         """jobs: [(slot, the next frames of that slot)]: the frames of them some window reads, sampled in one launch."""
@@ -832,22 +877,15 @@ class GazeStreamGroup:
         S = self.S
         self.batches.append(list(rows))
         group = [(i, stream_window(self.plan, w)) for i, w in rows]
-        padded = group + [group[-1]] * (self.batch - len(group))
+        padded = pad_rows(group, self.batch)
         slots = np.stack([i * self.R + r["frames_idx"] % self.R for i, r in padded]).astype(np.int32)
         centers = np.stack([r["audio_centers"] for _, r in padded]).astype(np.int64)
         video = inputs.stream_gather(self._crops.view(-1, 3, S, S), torch.from_numpy(slots).to(self._crops.device))
         audio = inputs.group_audio_windows(self._spec, [i for i, _ in padded], [c - 1 for c in self.cols], centers, AUDIO_WIDTH)
-        if S != AUDIO_WIDTH:   # S frequency bins x S columns around each frame, as predict_video cuts them
-            o = (AUDIO_WIDTH - S) // 2
-            audio = audio[:, :, :, :S, o:o + S].contiguous()
-        out = self.predictor.predict_batch({"video": video, "audio": audio})
-        results = []
-        for b, (i, r) in enumerate(group):
-            results.append({"stream": i, "window": r["window"], "frames_idx": r["frames_idx"], "target_idx": r["target_idx"],
-                            "points": out["points"][b], "peak": out["peak"][b], "heatmaps": out["heatmaps"][b],
-                            "rescaled": out["rescaled"][b]})
+        out = self.predictor.predict_batch({"video": video, "audio": crop_audio(audio, S)})
+        for i, r in group:
             self.next_window[i] = r["window"] + 1
-        return results
+        return [window_result(r, out, b, stream=i) for b, (i, r) in enumerate(group)]
 
     # ---- the interface ---------------------------------------------------------------------------------------------------------
     def push(self, pieces):
@@ -914,29 +952,18 @@ class GazeStreamGroup:
                 self.closed[i] = True
                 if self._resamplers[i] is not None:          # the outputs held back; as many of them as the spectrum ring takes
                     rest = self._resamplers[i].close()
-                    limit = ring_limits(stream_window(self.plan, self.next_window[i]), self.R, self.ring_cols)[1]
-                    rest = rest[:max(0, min(rest.numel(), limit - self.samples[i]))]
+                    rest = rest[:closing_flush(self.plan, self.R, self.ring_cols, self.next_window[i], self.samples[i], rest.numel())]
                     if rest.numel():
                         flush.append((i, rest, -1))
             self._audio(flush)
             self._audio([(i, self._tail[i][:0], self.samples[i]) for i in slots if self._tail[i] is not None])
-            rows = []
-            for i in slots:
-                w = self.next_window[i]
-                nxt = stream_window(self.plan, w)
-                while self.hw[i] is not None and nxt["ready_frames"] <= self.frames[i] and \
-                        int(nxt["audio_centers"].max()) + HALF_WIDTH <= self.cols[i]:
-                    rows.append((i, w))
-                    w += 1
-                    nxt = stream_window(self.plan, w)
+            rows = [(i, w) for i in slots for w in closing_windows(self.plan, self.next_window[i], self.frames[i], self.cols[i],
+                                                                   started=self.hw[i] is not None)]
             for g in range(0, len(rows), self.batch):
                 for r in self._run(rows[g:g + self.batch]):
                     out[r["stream"]].append(r)
         for i in slots:
-            w = self.next_window[i]
-            while int(stream_window(self.plan, w)["frames_idx"][0]) < self.frames[i]:
-                self.dropped[i] += 1
-                w += 1
+            self.dropped[i] += dropped_windows(self.plan, self.next_window[i], self.frames[i])
         return out
 
     def reset(self, slot):
@@ -1028,29 +1055,17 @@ class GazeLiveGroup(GazeStreamGroup):
                  matrix="bt601", full_range=False, input_rate=None, max_gap=None, overlay=False, alpha=0.4, radius=5,
                  overlay_format=None):
         from . import ops
-        from .infer import default_max_gap, _overlay_yuv
-        if live not in LIVE_MODES:
-            raise ValueError(f"live must be one of {LIVE_MODES}, got {live!r}")
-        plan = plan_stream(predictor.cfg, fps=fps, stride=stride, segment=segment)
-        check_live_plan(plan)
+        cfg = predictor.cfg                                  # the live arguments are refused before the base class allocates
         self.live, self.overlay, self.alpha, self.radius = live, bool(overlay), float(alpha), int(radius)
-        self.max_gap = default_max_gap(plan) if max_gap is None else int(max_gap)
-        if self.max_gap < 1:
-            raise ValueError(f"max_gap must be positive, got {max_gap}")
-        if not 0.0 <= self.alpha <= 1.0 or self.radius < 0:
-            raise ValueError(f"alpha must lie in [0, 1] and radius be >= 0, got {alpha} and {radius}")
-        if overlay_format is not None and not overlay:
-            raise ValueError("overlay_format belongs to the overlay: pass overlay=True")
-        group_fmt = {"pixel_format": pixel_format} if pixel_format in ("nv12", "i420") else {}
-        # the overlay in the pushed frames' own 4:2:0 layout (render_track(out_format=...)) instead of RGB
-        self.overlay_format = overlay_format if _overlay_yuv(overlay_format, group_fmt, "overlay_format") else None
+        self.max_gap, self.overlay_format, self.track_slots, track_bytes = check_live_args(
+            plan_stream(cfg, fps=fps, stride=stride, segment=segment), max_chunk, cfg.DATA.TEST_CROP_SIZE,
+            {"pixel_format": pixel_format} if pixel_format in ("nv12", "i420") else {}, live, max_gap, overlay, alpha, radius,
+            overlay_format, required=True)
         super().__init__(predictor, streams, fps=fps, stride=stride, segment=segment, batch=batch, max_chunk=max_chunk,
                          pixel_format=pixel_format, matrix=matrix, full_range=full_range, input_rate=input_rate)
-        self.track_slots = live_ring_slots(self.plan, self.max_chunk, self.max_gap)
-        side = self.S // 4                                   # the model's heat maps are S/4 x S/4
-        track_bytes = self.track_slots * (side * side * 4 + 4 + 8)
         self.capacity = dict(self.capacity, track_slots=self.track_slots, track_bytes=track_bytes,
                              total_bytes=self.capacity["total_bytes"] + self.streams * track_bytes)
+        side = self.S // 4
         self._track = ops.group_live_ring(self.streams, self.track_slots, side, side, predictor.device)
         self._answers = None                                 # {slot: [row dicts]} while a push_live runs
 
@@ -1080,10 +1095,8 @@ class GazeLiveGroup(GazeStreamGroup):
                                    want=("rescaled", "points", "peak", "count", "neighbours"))
         dev = rows["count"].device
         # what GazeStream._live_rows adds to its rows, for all slots at once; the slots take views of it
-        rows["filled"] = (rows["count"] == 0) & (rows["neighbours"][:, 0] >= 0)
-        rows["frame_idx"] = torch.from_numpy(frame_of).to(dev)
         known = np.concatenate([np.full(took[i], self.next_window[i], dtype=np.int32) for i, _ in chunks])
-        rows["known"] = torch.from_numpy(known).to(dev)
+        live_fields(rows, torch.from_numpy(frame_of).to(dev), torch.from_numpy(known).to(dev))
         # step 6: what depends on a slot's own H x W, for all slots at once
         src = ops.group_points_source(rows["points"], [(took[i], self._rows[i], *self.hw[i]) for i, _ in chunks], self.S)
         rows["points_source"] = src["points_source"]
@@ -1106,41 +1119,20 @@ class GazeLiveGroup(GazeStreamGroup):
                                             **self.fmt)
         return rows
 
-    def _live_empty(self, i):
-        """The live dict of a slot that pushed no frames."""
-        import torch
-        side, dev = self.S // 4, self.predictor.device
-        shapes = {"frame_idx": ((0,), torch.int64), "known": ((0,), torch.int32), "points": ((0, 2), torch.float32),
-                  "peak": ((0,), torch.float32), "count": ((0,), torch.int32), "neighbours": ((0, 2), torch.int32),
-                  "filled": ((0,), torch.bool), "rescaled": ((0, side, side), torch.float32),
-                  "points_source": ((0, 2), torch.float64)}
-        out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
-        if self.overlay:
-            H, W = self.hw[i] if self.hw[i] is not None else (0, 0)
-            shape = (0, H * 3 // 2, W) if self.overlay_format else (0, H, W, 3)
-            out["overlay"] = torch.empty(shape, dtype=torch.uint8, device=dev)
-        return out
-
     # ---- the interface ---------------------------------------------------------------------------------------------------------
     def push_live(self, pieces):
         """push(pieces) -> (windows, live): windows is what push returns; live is {slot: the GazeStream.push_live dict of the frames
         that slot pushed in this tick, in frame order} for the slots of pieces (K = 0 for a slot without frames).  A tick that is
         refused answers nothing and consumes nothing, as push's."""
-        import torch
         self._answers = {i: [] for i in range(self.streams)}
         try:
             windows = self.push(pieces)
             answers = self._answers
         finally:
             self._answers = None
-        live = {}
-        for i in windows:
-            rows = answers[i]
-            if not rows:
-                live[i] = self._live_empty(i)
-            else:
-                live[i] = rows[0] if len(rows) == 1 else {key: torch.cat([r[key] for r in rows], dim=0) for key in rows[0]}
-        return windows, live
+        side, dev = self.S // 4, self.predictor.device
+        return windows, {i: _cat_rows(answers[i]) if answers[i] else live_empty(side, dev, self.hw[i], self.overlay, self.overlay_format)
+                         for i in windows}
 
     def reset(self, slot):
         """Reopen the closed slot `slot` as a fresh stream.  Unlike the base class's, this reset writes to the device: it sets the
