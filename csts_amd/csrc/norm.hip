@@ -1,16 +1,18 @@
 // LayerNorm forward / backward (K2 of SURVEY.md 2.3) and the shared partial-sum reducer.
 // Reference: block norms nn.LayerNorm(C, eps=1e-6) (attention.py:192,214) and the per-head
 // nn.LayerNorm(hd, eps=1e-5) applied to pooled q/k/v (attention.py:108,112,116) -- same kernel, rows = B*N*h.
-// One wave per row, row kept in registers (C <= 768 -> <= 12 values per lane), two-pass statistics in fp32.
+// A group of GL lanes per row, the row kept in registers (C <= 768), two-pass statistics in fp32.
 // HBM-bound: algorithmic bytes = rows*C*(in + out) (+ 8 B/row of statistics).
 #include "common.h"
+
+#include <utility>
 
 namespace {
 
 constexpr int MAXV = 12;  // C <= 768
 constexpr int LN_BWD_WAVES = 8;  // 512-thread blocks: few, fat partial rows for the second-stage reduction
 
-// compile-time dtypes: no branch sits between a load and the next one, so a wave keeps R rows x NV loads in flight
+// compile-time dtypes: no branch sits between a load and the next one, so a lane group keeps R rows x NCH loads in flight
 template <bool F32> __device__ __forceinline__ float ldt(const void* p, int64_t i) {
   if constexpr (F32) return reinterpret_cast<const float*>(p)[i];
   else return h16_lo((unsigned)reinterpret_cast<const unsigned short*>(p)[i]);
@@ -19,182 +21,6 @@ template <bool F32> __device__ __forceinline__ void stt(void* p, int64_t i, floa
   if constexpr (F32) reinterpret_cast<float*>(p)[i] = v;
   else reinterpret_cast<bf16*>(p)[i] = (bf16)v;
 }
-
-// one wave handles R rows per iteration (R*NV independent loads), two-pass statistics in registers
-// optional input of the forward kernels: x + addend is what gets normalised, and the sum is written to `sum` (dtype of x):
-// the decoder's `feat + en_feat` skip (custom_multimodal_builder.py:467-479) folded into the next block's norm1.  What is normalised
-// is the sum AS STORED (a 16-bit sum is rounded first): mean / rstd are those of `sum`, the x the backward reads with them
-struct FwdAdd {
-  const void* addend = nullptr;
-  void* sum = nullptr;
-};
-template <int NV, int R, bool XF32, bool YF32>
-__global__ __launch_bounds__(256) void ln_fwd_kernel(const void* __restrict__ x, const float* __restrict__ gamma,
-                                                     const float* __restrict__ beta, void* __restrict__ y,
-                                                     float* __restrict__ mean, float* __restrict__ rstd, int64_t rows,
-                                                     int C, float eps, FwdAdd fa) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-  float gm[NV], bt[NV];
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const int c = lane + 64 * j;
-    gm[j] = c < C ? gamma[c] : 0.f;
-    bt[j] = c < C ? beta[c] : 0.f;
-  }
-  const float invC = 1.f / C;
-  for (int64_t row0 = wave * R; row0 < rows; row0 += nwaves * R) {
-    float v[R][NV];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int64_t row = min(row0 + r, rows - 1);
-#pragma unroll
-      for (int j = 0; j < NV; ++j) {
-        const int c = lane + 64 * j;
-        v[r][j] = ldt<XF32>(x, row * C + min(c, C - 1));
-        if (fa.addend) {                                         // wave-uniform
-          v[r][j] += ldt<XF32>(fa.addend, row * C + min(c, C - 1));
-          if constexpr (!XF32) v[r][j] = (float)(bf16)v[r][j];   // normalise the sum as stored: the x the backward reads with this mean / rstd
-          if (c < C && row0 + r < rows) stt<XF32>(fa.sum, row * C + c, v[r][j]);
-        }
-      }
-    }
-    float mu[R], rs[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      float s = 0.f;
-#pragma unroll
-      for (int j = 0; j < NV; ++j) s += (lane + 64 * j < C) ? v[r][j] : 0.f;
-      mu[r] = wave_sum(s) * invC;
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      float q = 0.f;
-#pragma unroll
-      for (int j = 0; j < NV; ++j) {
-        const float d = (lane + 64 * j < C) ? v[r][j] - mu[r] : 0.f;
-        q += d * d;
-      }
-      rs[r] = rsqrtf(wave_sum(q) * invC + eps);
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int64_t row = row0 + r;
-      if (row >= rows) break;
-#pragma unroll
-      for (int j = 0; j < NV; ++j) {
-        const int c = lane + 64 * j;
-        if (c < C) stt<YF32>(y, row * C + c, (v[r][j] - mu[r]) * rs[r] * gm[j] + bt[j]);
-      }
-      if (lane == 0) {
-        if (mean) mean[row] = mu[r];
-        if (rstd) rstd[row] = rs[r];
-      }
-    }
-  }
-}
-
-// optional extras of the backward kernels: a bf16 copy of dx (+ per-sample scale applied to the copy only: row r uses
-// scale[r / rps]) and a second incoming gradient (LayerNorm output with two consumers)
-struct Copy16 {
-  bf16* p = nullptr;
-  const float* scale = nullptr;
-  int64_t rps = 1;
-  const void* dy2 = nullptr;     // a second incoming gradient of the same shape / dtype as dy: the kernel reads dy + dy2
-};
-// dx = rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * gamma
-// per-wave partial dgamma/dbeta are summed through LDS and written to ws[block][2*C]
-template <int NV, int R, bool DYF32, bool XF32>
-__global__ __launch_bounds__(512) void ln_bwd_kernel(const void* __restrict__ dy, const void* __restrict__ x,
-                                                     const float* __restrict__ gamma, const float* __restrict__ mean,
-                                                     const float* __restrict__ rstd, void* __restrict__ dx,
-                                                     const void* __restrict__ addend, float* __restrict__ ws, int64_t rows,
-                                                     int C, const float* __restrict__ gamma1, Copy16 dx16) {
-  extern __shared__ __attribute__((aligned(16))) float red[];  // [LN_BWD_WAVES][2*C]
-  // blockIdx.y = segment: a second tensor of the same shape stacked behind the first (rows each), with its own gamma and
-  // its own partial rows (the k and v LayerNorms of one attention in one launch)
-  const int64_t ro = (int64_t)blockIdx.y * rows;
-  if (blockIdx.y == 1) gamma = gamma1;
-  ws += (int64_t)blockIdx.y * gridDim.x * 2 * C;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t wave = (int64_t)blockIdx.x * LN_BWD_WAVES + w;
-  const int64_t nwaves = (int64_t)gridDim.x * LN_BWD_WAVES;
-  float dg[NV], db[NV], gm[NV];
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    dg[j] = 0.f; db[j] = 0.f;
-    const int c = lane + 64 * j;
-    gm[j] = c < C ? gamma[c] : 0.f;
-  }
-  const float invC = 1.f / C;
-  for (int64_t row0 = wave * R; row0 < rows; row0 += nwaves * R) {
-    float d[R][NV], xv[R][NV], ad[R][NV], mu[R], rs[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int64_t row = ro + min(row0 + r, rows - 1);
-      mu[r] = mean[row];
-      rs[r] = rstd[row];
-#pragma unroll
-      for (int j = 0; j < NV; ++j) {
-        const int64_t i = row * C + min(lane + 64 * j, C - 1);
-        d[r][j] = ldt<DYF32>(dy, i);
-        if (dx16.dy2) d[r][j] += ldt<DYF32>(dx16.dy2, i);    // wave-uniform test
-        xv[r][j] = ldt<XF32>(x, i);
-        ad[r][j] = addend ? ldt<XF32>(addend, i) : 0.f;     // residual-branch gradient folded into dx (wave-uniform test)
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const bool live = row0 + r < rows;
-      float s1 = 0.f, s2 = 0.f, xh[NV], g[NV];
-#pragma unroll
-      for (int j = 0; j < NV; ++j) {
-        const bool ok = live && (lane + 64 * j < C);
-        const float dd = ok ? d[r][j] : 0.f;
-        xh[j] = ok ? (xv[r][j] - mu[r]) * rs[r] : 0.f;
-        g[j] = dd * gm[j];
-        dg[j] += dd * xh[j];
-        db[j] += dd;
-        s1 += g[j];
-        s2 += g[j] * xh[j];
-      }
-      s1 = wave_sum(s1) * invC;
-      s2 = wave_sum(s2) * invC;
-      if (live) {
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-          const int c = lane + 64 * j;
-          if (c < C) {
-            const float val = rs[r] * (g[j] - s1 - xh[j] * s2) + ad[r][j];
-            stt<XF32>(dx, (ro + row0 + r) * C + c, val);
-            // the copy the next GEMMs read (they round to bf16 anyway), times the per-sample drop-path scale of the
-            // branch that consumes it when the caller knows it (saves that branch a scale_rows pass over dx)
-            if (dx16.p) dx16.p[(ro + row0 + r) * C + c] = (bf16)(dx16.scale ? val * dx16.scale[(row0 + r) / dx16.rps] : val);
-          }
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const int c = lane + 64 * j;
-    if (c < C) { red[w * 2 * C + c] = dg[j]; red[w * 2 * C + C + c] = db[j]; }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) {
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < LN_BWD_WAVES; ++k) t += red[k * 2 * C + i];
-    ws[(int64_t)blockIdx.x * 2 * C + i] = t;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Vectorised forms (C % 8 == 0, the only case the model produces: C in {96, 192, 384, 768}): a group of GL lanes owns a
-// row, every lane NCH chunks of 8 consecutive channels -> 16-byte loads / stores instead of one element per lane per
-// instruction, statistics by shuffles inside the group, 64 / GL rows per wave and R rows in flight per group.
-// ---------------------------------------------------------------------------------------------------------------
 template <bool F32> __device__ __forceinline__ void ld8t(const void* p, int64_t i, float (&o)[8]) {
   if constexpr (F32) {
     const float4* q = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p) + i);
@@ -220,6 +46,15 @@ template <bool F32> __device__ __forceinline__ void st8t(void* p, int64_t i, con
     *reinterpret_cast<bf16x8*>(reinterpret_cast<bf16*>(p) + i) = v;
   }
 }
+// a chunk of W consecutive channels: one element, or 16 bytes (32 of fp32) at once
+template <int W, bool F32> __device__ __forceinline__ void ldw(const void* p, int64_t i, float (&o)[W]) {
+  if constexpr (W == 8) ld8t<F32>(p, i, o);
+  else o[0] = ldt<F32>(p, i);
+}
+template <int W, bool F32> __device__ __forceinline__ void stw(void* p, int64_t i, const float (&o)[W]) {
+  if constexpr (W == 8) st8t<F32>(p, i, o);
+  else stt<F32>(p, i, o[0]);
+}
 template <int GL> __device__ __forceinline__ float group_sum(float v) {
 #pragma unroll
   for (int o = GL / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -239,116 +74,186 @@ __device__ __forceinline__ int64_t xcd_block(int64_t bid, int64_t nwg) {
 #endif
 }
 
-template <int GL, int NCH, int R, bool XF32, bool YF32>
-__global__ __launch_bounds__(256) void ln_fwd_vec_kernel(const void* __restrict__ x, const float* __restrict__ gamma,
-                                                         const float* __restrict__ beta, void* __restrict__ y,
-                                                         float* __restrict__ mean, float* __restrict__ rstd, int64_t rows,
-                                                         int C, float eps, FwdAdd fa) {
-  const int sub = threadIdx.x % GL;
-  const int64_t grp = (xcd_block(blockIdx.x, gridDim.x) * 256 + threadIdx.x) / GL, ngrp = (int64_t)gridDim.x * 256 / GL;
-  int c0[NCH];
-  bool act[NCH];
-  float gm[NCH][8], bt[NCH][8];
+// ---------------------------------------------------------------------------------------------------------------
+// One kernel body per direction.  A group of GL lanes owns a row and every lane NCH chunks of W consecutive channels, chunk i
+// of lane `sub` starting at channel (sub + GL i) W; statistics by shuffles inside the group, 64 / GL rows per wave and R rows
+// in flight per group.  Two roles:
+//   W = 8  C % 8 == 0 and every operand 16-byte aligned (all the model produces: C in {96, 192, 384, 768}): 16-byte loads and
+//          stores, GL = 16 / 32 / 64 by C, XCD-contiguous row ranges.
+//   W = 1  everything else: one channel per lane and chunk, a whole wave per row (GL = 64, channel lane + 64 i), plain
+//          workgroup order.  In the backward kernel the block -> rows map decides what each partial row of the workspace holds,
+//          and so the bits of dgamma / dbeta: the XCD map must stay out of this role.
+// ---------------------------------------------------------------------------------------------------------------
+// A lane's chunks.  on(i): chunk i lies inside the row; at(i): its first channel, clamped into the row so that every lane may
+// load; st(i): the same for a store, which happens under on(i) only, where the clamp changes nothing.  W = 8 forms on and at once
+// per lane.  W = 1 forms all three anew from the compile-time i at each use and keeps nothing: there a lane has up to 12 chunks,
+// and a live predicate and clamped offset per chunk cost the 12-chunk forms a wave per SIMD (forward) or spill (backward).
+template <int W, int GL, int NCH> struct Lane {
+  int sub, C;
+  int c0[W == 8 ? NCH : 1];
+  bool act[W == 8 ? NCH : 1];
+  // called once per chunk before anything else, interleaved with the parameter loads (the order the W = 8 schedule was tuned in)
+  __device__ __forceinline__ void form(int i) {
+    if constexpr (W == 8) {
+      const int c = (sub + GL * i) * 8;
+      act[i] = c < C;
+      c0[i] = min(c, C - 8);
+    }
+  }
+  __device__ __forceinline__ bool on(int i) const {
+    if constexpr (W == 8) return act[i];
+    else return sub + GL * i < C;
+  }
+  __device__ __forceinline__ int st(int i) const {
+    if constexpr (W == 8) return c0[i];
+    else return sub + GL * i;
+  }
+  __device__ __forceinline__ int at(int i) const {
+    if constexpr (W == 8) return c0[i];
+    else return min(sub + GL * i, C - 1);
+  }
+  // gamma / beta of chunk i; the one-channel role reads nothing for a chunk outside the row
+  __device__ __forceinline__ void param(const float* p, int i, float (&o)[W]) const {
+    if constexpr (W == 8) ld8t<true>(p, at(i), o);
+    else o[0] = on(i) ? p[sub + GL * i] : 0.f;
+  }
+};
+
+// optional input of the forward kernel: x + addend is what gets normalised, and the sum is written to `sum` (dtype of x):
+// the decoder's `feat + en_feat` skip (custom_multimodal_builder.py:467-479) folded into the next block's norm1.  What is normalised
+// is the sum AS STORED (a 16-bit sum is rounded first): mean / rstd are those of `sum`, the x the backward reads with them
+struct FwdAdd {
+  const void* addend = nullptr;
+  void* sum = nullptr;
+};
+template <int W, int GL, int NCH, int R, bool XF32, bool YF32>
+__global__ __launch_bounds__(256) void ln_fwd_kernel(const void* __restrict__ x, const float* __restrict__ gamma,
+                                                     const float* __restrict__ beta, void* __restrict__ y,
+                                                     float* __restrict__ mean, float* __restrict__ rstd, int64_t rows,
+                                                     int C, float eps, FwdAdd fa) {
+  const int64_t bid = W == 8 ? xcd_block(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+  const int64_t grp = (bid * 256 + threadIdx.x) / GL, ngrp = (int64_t)gridDim.x * 256 / GL;
+  Lane<W, GL, NCH> ln{(int)(threadIdx.x % GL), C};
+  float gm[NCH][W], bt[NCH][W];
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
-    const int c = (sub + GL * i) * 8;
-    act[i] = c < C;
-    c0[i] = min(c, C - 8);
-    ld8t<true>(gamma, c0[i], gm[i]);
-    ld8t<true>(beta, c0[i], bt[i]);
+    ln.form(i);
+    ln.param(gamma, i, gm[i]);
+    ln.param(beta, i, bt[i]);
   }
   const float invC = 1.f / C;
   for (int64_t row0 = grp * R; row0 < rows; row0 += ngrp * R) {
-    float v[R][NCH][8];
+    float v[R][NCH][W];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const int64_t row = min(row0 + r, rows - 1);
 #pragma unroll
       for (int i = 0; i < NCH; ++i) {
-        ld8t<XF32>(x, row * C + c0[i], v[r][i]);
-        if (fa.addend) {
-          float a2[8];
-          ld8t<XF32>(fa.addend, row * C + c0[i], a2);
+        ldw<W, XF32>(x, row * C + ln.at(i), v[r][i]);
+        if (fa.addend) {                                         // wave-uniform
+          float a2[W];
+          ldw<W, XF32>(fa.addend, row * C + ln.at(i), a2);
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
+          for (int j = 0; j < W; ++j) {
             v[r][i][j] += a2[j];
-            if constexpr (!XF32) v[r][i][j] = (float)(bf16)v[r][i][j];   // the sum as stored (see ln_fwd_kernel)
+            if constexpr (!XF32) v[r][i][j] = (float)(bf16)v[r][i][j];   // normalise the sum as stored: the x the backward reads with this mean / rstd
           }
-          if (act[i] && row0 + r < rows) st8t<XF32>(fa.sum, row * C + c0[i], v[r][i]);
+          if (ln.on(i) && row0 + r < rows) stw<W, XF32>(fa.sum, row * C + ln.st(i), v[r][i]);
         }
       }
     }
+    // Mean, rstd and the stores of a row.  W = 8 takes its rows one after the other; W = 1 takes its R rows through one phase after
+    // the other (PH = 3 passes: the shuffles of up to four rows in flight together) -- the order each role was scheduled and timed
+    // in.  The arithmetic of a row is the same either way.
+    constexpr int PH = W == 8 ? 1 : 3;
+    float mu[R], rs[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-      float s = 0.f;
+    for (int ph = 0; ph < PH; ++ph)
 #pragma unroll
-      for (int i = 0; i < NCH; ++i)
-        if (act[i]) {
+      for (int r = 0; r < R; ++r) {
+        if (PH == 1 || ph == 0) {
+          float s = 0.f;
 #pragma unroll
-          for (int j = 0; j < 8; ++j) s += v[r][i][j];
+          for (int i = 0; i < NCH; ++i)
+            if (ln.on(i)) {
+#pragma unroll
+              for (int j = 0; j < W; ++j) s += v[r][i][j];
+            }
+          mu[r] = group_sum<GL>(s) * invC;
         }
-      const float mu = group_sum<GL>(s) * invC;
-      float q = 0.f;
+        if (PH == 1 || ph == 1) {
+          float q = 0.f;
 #pragma unroll
-      for (int i = 0; i < NCH; ++i)
-        if (act[i]) {
+          for (int i = 0; i < NCH; ++i)
+            if (ln.on(i)) {
 #pragma unroll
-          for (int j = 0; j < 8; ++j) { const float d = v[r][i][j] - mu; q += d * d; }
+              for (int j = 0; j < W; ++j) { const float d = v[r][i][j] - mu[r]; q += d * d; }
+            }
+          rs[r] = rsqrtf(group_sum<GL>(q) * invC + eps);
         }
-      const float rs = rsqrtf(group_sum<GL>(q) * invC + eps);
-      const int64_t row = row0 + r;
-      if (row < rows) {
+        const int64_t row = row0 + r;
+        if ((PH == 1 || ph == 2) && row < rows) {
 #pragma unroll
-        for (int i = 0; i < NCH; ++i)
-          if (act[i]) {
-            float o[8];
+          for (int i = 0; i < NCH; ++i)
+            if (ln.on(i)) {
+              float o[W];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = (v[r][i][j] - mu) * rs * gm[i][j] + bt[i][j];
-            st8t<YF32>(y, row * C + c0[i], o);
+              for (int j = 0; j < W; ++j) o[j] = (v[r][i][j] - mu[r]) * rs[r] * gm[i][j] + bt[i][j];
+              stw<W, YF32>(y, row * C + ln.st(i), o);
+            }
+          if (ln.sub == 0) {
+            if (mean) mean[row] = mu[r];
+            if (rstd) rstd[row] = rs[r];
           }
-        if (sub == 0) {
-          if (mean) mean[row] = mu;
-          if (rstd) rstd[row] = rs;
         }
       }
-    }
   }
 }
 
+// optional extras of the backward kernel: a bf16 copy of dx (+ per-sample scale applied to the copy only: row r uses
+// scale[r / rps]) and a second incoming gradient (LayerNorm output with two consumers)
+struct Copy16 {
+  bf16* p = nullptr;
+  const float* scale = nullptr;
+  int64_t rps = 1;
+  const void* dy2 = nullptr;     // a second incoming gradient of the same shape / dtype as dy: the kernel reads dy + dy2
+};
 #ifndef CSTS_LN_BWD_R
-#define CSTS_LN_BWD_R 1            // rows per lane group and pass of ln_bwd_vec_kernel at C <= 512.  Round 5: 1 instead of 2 (-0.1 ms per step, profiles/r5_stencil_ab.txt)
+#define CSTS_LN_BWD_R 1            // rows per lane group and pass of the W = 8 ln_bwd_kernel at C <= 512.  Round 5: 1 instead of 2 (-0.1 ms per step, profiles/r5_stencil_ab.txt)
 #endif
 #ifndef CSTS_LN_BWD_MINW
-#define CSTS_LN_BWD_MINW 1         // minimum waves per SIMD ln_bwd_vec_kernel is compiled for (A/B builds: 6 with R = 1)
+#define CSTS_LN_BWD_MINW 1         // minimum waves per SIMD ln_bwd_kernel is compiled for (A/B builds: 6 with R = 1)
 #endif
-template <int GL, int NCH, int R, bool DYF32, bool XF32>
-__global__ __launch_bounds__(512, CSTS_LN_BWD_MINW) void ln_bwd_vec_kernel(const void* __restrict__ dy, const void* __restrict__ x,
+// dx = rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * gamma
+// per-group partial dgamma/dbeta are summed through LDS and written to ws[block][2*C]
+template <int W, int GL, int NCH, int R, bool DYF32, bool XF32>
+__global__ __launch_bounds__(512, CSTS_LN_BWD_MINW) void ln_bwd_kernel(const void* __restrict__ dy, const void* __restrict__ x,
                                                          const float* __restrict__ gamma, const float* __restrict__ mean,
                                                          const float* __restrict__ rstd, void* __restrict__ dx,
                                                          const void* __restrict__ addend, float* __restrict__ ws, int64_t rows,
                                                          int C, const float* __restrict__ gamma1, Copy16 dx16) {
   extern __shared__ __attribute__((aligned(16))) float red[];  // [512 / GL groups][2*C]
-  const int64_t ro = (int64_t)blockIdx.y * rows;               // segment (second stacked tensor), see ln_bwd_kernel
+  // blockIdx.y = segment: a second tensor of the same shape stacked behind the first (rows each), with its own gamma and
+  // its own partial rows (the k and v LayerNorms of one attention in one launch)
+  const int64_t ro = (int64_t)blockIdx.y * rows;
   if (blockIdx.y == 1) gamma = gamma1;
   ws += (int64_t)blockIdx.y * gridDim.x * 2 * C;
-  const int sub = threadIdx.x % GL, gib = threadIdx.x / GL;    // group in block
+  const int gib = threadIdx.x / GL;                            // group in block
   constexpr int GPB = 512 / GL;
-  const int64_t grp = xcd_block(blockIdx.x, gridDim.x) * GPB + gib, ngrp = (int64_t)gridDim.x * GPB;
-  int c0[NCH];
-  bool act[NCH];
-  float gm[NCH][8], dg[NCH][8], db[NCH][8];
+  const int64_t bid = W == 8 ? xcd_block(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+  const int64_t grp = bid * GPB + gib, ngrp = (int64_t)gridDim.x * GPB;
+  Lane<W, GL, NCH> ln{(int)(threadIdx.x % GL), C};
+  float gm[NCH][W], dg[NCH][W], db[NCH][W];
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
-    const int c = (sub + GL * i) * 8;
-    act[i] = c < C;
-    c0[i] = min(c, C - 8);
-    ld8t<true>(gamma, c0[i], gm[i]);
+    ln.form(i);
+    ln.param(gamma, i, gm[i]);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { dg[i][j] = 0.f; db[i][j] = 0.f; }
+    for (int j = 0; j < W; ++j) { dg[i][j] = 0.f; db[i][j] = 0.f; }
   }
   const float invC = 1.f / C;
   for (int64_t row0 = grp * R; row0 < rows; row0 += ngrp * R) {
-    float d[R][NCH][8], xv[R][NCH][8], ad[R][NCH][8], mu[R], rs[R];
+    float d[R][NCH][W], xv[R][NCH][W], ad[R][NCH][W], mu[R], rs[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const int64_t row = ro + min(row0 + r, rows - 1);
@@ -356,18 +261,18 @@ __global__ __launch_bounds__(512, CSTS_LN_BWD_MINW) void ln_bwd_vec_kernel(const
       rs[r] = rstd[row];
 #pragma unroll
       for (int i = 0; i < NCH; ++i) {
-        ld8t<DYF32>(dy, row * C + c0[i], d[r][i]);
-        if (dx16.dy2) {
-          float d2[8];
-          ld8t<DYF32>(dx16.dy2, row * C + c0[i], d2);
+        ldw<W, DYF32>(dy, row * C + ln.at(i), d[r][i]);
+        if (dx16.dy2) {                                          // wave-uniform test
+          float d2[W];
+          ldw<W, DYF32>(dx16.dy2, row * C + ln.at(i), d2);
 #pragma unroll
-          for (int j = 0; j < 8; ++j) d[r][i][j] += d2[j];
+          for (int j = 0; j < W; ++j) d[r][i][j] += d2[j];
         }
-        ld8t<XF32>(x, row * C + c0[i], xv[r][i]);
-        if (addend) ld8t<XF32>(addend, row * C + c0[i], ad[r][i]);
+        ldw<W, XF32>(x, row * C + ln.at(i), xv[r][i]);
+        if (addend) ldw<W, XF32>(addend, row * C + ln.at(i), ad[r][i]);   // residual-branch gradient folded into dx (wave-uniform test)
         else {
 #pragma unroll
-          for (int j = 0; j < 8; ++j) ad[r][i][j] = 0.f;
+          for (int j = 0; j < W; ++j) ad[r][i][j] = 0.f;
         }
       }
     }
@@ -375,12 +280,12 @@ __global__ __launch_bounds__(512, CSTS_LN_BWD_MINW) void ln_bwd_vec_kernel(const
     for (int r = 0; r < R; ++r) {
       const bool live = row0 + r < rows;
       float s1 = 0.f, s2 = 0.f;
-      float xh[NCH][8], g[NCH][8];
+      float xh[NCH][W], g[NCH][W];
 #pragma unroll
       for (int i = 0; i < NCH; ++i) {
-        const bool ok = live && act[i];
+        const bool ok = live && ln.on(i);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
+        for (int j = 0; j < W; ++j) {
           const float dd = ok ? d[r][i][j] : 0.f;
           xh[i][j] = ok ? (xv[r][i][j] - mu[r]) * rs[r] : 0.f;
           g[i][j] = dd * gm[i][j];
@@ -396,18 +301,20 @@ __global__ __launch_bounds__(512, CSTS_LN_BWD_MINW) void ln_bwd_vec_kernel(const
         const int64_t row = ro + row0 + r;
 #pragma unroll
         for (int i = 0; i < NCH; ++i)
-          if (act[i]) {
-            float o[8];
+          if (ln.on(i)) {
+            float o[W];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = rs[r] * (g[i][j] - s1 - xh[i][j] * s2) + ad[r][i][j];
-            st8t<XF32>(dx, row * C + c0[i], o);
-            if (dx16.p) {                                        // the copy the next GEMMs read (see ln_bwd_kernel)
+            for (int j = 0; j < W; ++j) o[j] = rs[r] * (g[i][j] - s1 - xh[i][j] * s2) + ad[r][i][j];
+            stw<W, XF32>(dx, row * C + ln.st(i), o);
+            // the copy the next GEMMs read (they round to bf16 anyway), times the per-sample drop-path scale of the
+            // branch that consumes it when the caller knows it (saves that branch a scale_rows pass over dx)
+            if (dx16.p) {
               if (dx16.scale) {
                 const float sc = dx16.scale[(row0 + r) / dx16.rps];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) o[j] *= sc;
+                for (int j = 0; j < W; ++j) o[j] *= sc;
               }
-              st8t<false>(dx16.p, row * C + c0[i], o);
+              stw<W, false>(dx16.p, row * C + ln.st(i), o);
             }
           }
       }
@@ -415,17 +322,17 @@ __global__ __launch_bounds__(512, CSTS_LN_BWD_MINW) void ln_bwd_vec_kernel(const
   }
 #pragma unroll
   for (int i = 0; i < NCH; ++i)
-    if (act[i]) {
+    if (ln.on(i)) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        red[gib * 2 * C + c0[i] + j] = dg[i][j];
-        red[gib * 2 * C + C + c0[i] + j] = db[i][j];
+      for (int j = 0; j < W; ++j) {
+        red[gib * 2 * C + ln.st(i) + j] = dg[i][j];
+        red[gib * 2 * C + C + ln.st(i) + j] = db[i][j];
       }
     }
   __syncthreads();
   for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) {
     float t = 0.f;
-#pragma unroll 4
+#pragma unroll(W == 8 ? 4 : GPB)   // each role's own unrolling; the order of the sum is ascending k either way
     for (int k = 0; k < GPB; ++k) t += red[k * 2 * C + i];
     ws[(int64_t)blockIdx.x * 2 * C + i] = t;
   }
@@ -544,68 +451,43 @@ extern "C" int csts_reduce_rows(const float* ws, float* out, int64_t nrows, int6
   return 0;
 }
 
-template <int NV, int R>
-static void ln_fwd_launch(bool xf, bool yf, dim3 grid, hipStream_t st, const void* x, const float* g, const float* b, void* y,
-                          float* mean, float* rstd, int64_t rows, int C, float eps, FwdAdd fa) {
-  if (xf && yf) hipLaunchKernelGGL((ln_fwd_kernel<NV, R, true, true>), grid, dim3(256), 0, st, x, g, b, y, mean, rstd, rows, C, eps, fa);
-  else if (xf) hipLaunchKernelGGL((ln_fwd_kernel<NV, R, true, false>), grid, dim3(256), 0, st, x, g, b, y, mean, rstd, rows, C, eps, fa);
-  else if (yf) hipLaunchKernelGGL((ln_fwd_kernel<NV, R, false, true>), grid, dim3(256), 0, st, x, g, b, y, mean, rstd, rows, C, eps, fa);
-  else hipLaunchKernelGGL((ln_fwd_kernel<NV, R, false, false>), grid, dim3(256), 0, st, x, g, b, y, mean, rstd, rows, C, eps, fa);
+// ---------------------------------------------------------------------------------------------------------------
+// The LayerNorm launches.  Every instantiated form {W, GL, NCH, R} of a direction stands in LN_FORMS once; ln_form() is the
+// one place that decides which of them serves a call, and grids, LDS and workspace sizes follow from the form it names.
+// ---------------------------------------------------------------------------------------------------------------
+#ifndef CSTS_LN_FWD_R
+#define CSTS_LN_FWD_R 2            // rows per lane group and pass of the W = 8 ln_fwd_kernel at C <= 512 (A/B build: 1)
+#endif
+#ifndef CSTS_LN_BWD_CAP
+#define CSTS_LN_BWD_CAP 512        // workgroups of a LayerNorm-backward launch (two 512-thread workgroups per CU; A/B builds: 768 with CSTS_LN_BWD_MINW=6)
+#endif
+struct LnForm { int W, GL, NCH, R; };
+template <bool BWD> static constexpr LnForm LN_FORMS[8] = {
+    {8, 16, 1, BWD ? CSTS_LN_BWD_R : CSTS_LN_FWD_R}, {8, 32, 1, BWD ? CSTS_LN_BWD_R : CSTS_LN_FWD_R},   // C <= 128, <= 256
+    {8, 64, 1, BWD ? CSTS_LN_BWD_R : CSTS_LN_FWD_R}, {8, 64, 2, BWD ? 1 : 2},                           // C <= 512, <= 768
+    {1, 64, 2, 4}, {1, 64, 3, 4}, {1, 64, 6, 2}, {1, 64, 12, 1}};                                       // C <= 128, <= 192, <= 384, <= 768
+static size_t ln_bwd_lds(const LnForm& f, int C) { return (size_t)(512 / f.GL) * 2 * C * sizeof(float); }   // [groups][2*C] partials
+// The index into LN_FORMS of the form that serves 0 < C <= 768.  `aligned`: every operand is 16-byte aligned (and whatever else
+// the entry asks of its shapes); 8 channels per lane need that, C % 8 == 0 and, backward, the partials inside 64 KiB of LDS.
+static int ln_form(bool bwd, int C, bool aligned) {
+  const int vec = C <= 128 ? 0 : (C <= 256 ? 1 : (C <= 512 ? 2 : 3));
+  if (aligned && C % 8 == 0 && !(bwd && ln_bwd_lds(LN_FORMS<true>[vec], C) > 65536)) return vec;
+  return 4 + (C <= 128 ? 0 : (C <= 192 ? 1 : (C <= 384 ? 2 : 3)));
 }
-template <int NV, int R>
-static void ln_bwd_launch(bool df, bool xf, dim3 grid, size_t sh, hipStream_t st, const void* dy, const void* x, const float* g,
-                          const float* mean, const float* rstd, void* dx, const void* addend, float* ws, int64_t rows, int C,
-                          const float* g1 = nullptr, Copy16 dx16 = Copy16{}) {
-  if (df && xf) hipLaunchKernelGGL((ln_bwd_kernel<NV, R, true, true>), grid, dim3(64 * LN_BWD_WAVES), sh, st, dy, x, g, mean, rstd, dx, addend, ws, rows, C, g1, dx16);
-  else if (df) hipLaunchKernelGGL((ln_bwd_kernel<NV, R, true, false>), grid, dim3(64 * LN_BWD_WAVES), sh, st, dy, x, g, mean, rstd, dx, addend, ws, rows, C, g1, dx16);
-  else if (xf) hipLaunchKernelGGL((ln_bwd_kernel<NV, R, false, true>), grid, dim3(64 * LN_BWD_WAVES), sh, st, dy, x, g, mean, rstd, dx, addend, ws, rows, C, g1, dx16);
-  else hipLaunchKernelGGL((ln_bwd_kernel<NV, R, false, false>), grid, dim3(64 * LN_BWD_WAVES), sh, st, dy, x, g, mean, rstd, dx, addend, ws, rows, C, g1, dx16);
-}
-template <int GL, int NCH, int R>
-static void ln_fwd_vec_launch(bool xf, bool yf, dim3 grid, hipStream_t st, const void* x, const float* g, const float* b, void* y,
-                              float* mean, float* rstd, int64_t rows, int C, float eps, FwdAdd fa) {
-  if (xf && yf) hipLaunchKernelGGL((ln_fwd_vec_kernel<GL, NCH, R, true, true>), grid, dim3(256), 0, st, x, g, b, y, mean, rstd, rows, C, eps, fa);
-  else if (xf) hipLaunchKernelGGL((ln_fwd_vec_kernel<GL, NCH, R, true, false>), grid, dim3(256), 0, st, x, g, b, y, mean, rstd, rows, C, eps, fa);
-  else if (yf) hipLaunchKernelGGL((ln_fwd_vec_kernel<GL, NCH, R, false, true>), grid, dim3(256), 0, st, x, g, b, y, mean, rstd, rows, C, eps, fa);
-  else hipLaunchKernelGGL((ln_fwd_vec_kernel<GL, NCH, R, false, false>), grid, dim3(256), 0, st, x, g, b, y, mean, rstd, rows, C, eps, fa);
-}
-template <int GL, int NCH, int R>
-static void ln_bwd_vec_launch(bool df, bool xf, dim3 grid, size_t sh, hipStream_t st, const void* dy, const void* x, const float* g,
-                              const float* mean, const float* rstd, void* dx, const void* addend, float* ws, int64_t rows, int C,
-                              const float* g1, Copy16 dx16) {
-  if (df && xf) hipLaunchKernelGGL((ln_bwd_vec_kernel<GL, NCH, R, true, true>), grid, dim3(512), sh, st, dy, x, g, mean, rstd, dx, addend, ws, rows, C, g1, dx16);
-  else if (df) hipLaunchKernelGGL((ln_bwd_vec_kernel<GL, NCH, R, true, false>), grid, dim3(512), sh, st, dy, x, g, mean, rstd, dx, addend, ws, rows, C, g1, dx16);
-  else if (xf) hipLaunchKernelGGL((ln_bwd_vec_kernel<GL, NCH, R, false, true>), grid, dim3(512), sh, st, dy, x, g, mean, rstd, dx, addend, ws, rows, C, g1, dx16);
-  else hipLaunchKernelGGL((ln_bwd_vec_kernel<GL, NCH, R, false, false>), grid, dim3(512), sh, st, dy, x, g, mean, rstd, dx, addend, ws, rows, C, g1, dx16);
-}
-// vector kernels: C % 8 == 0 and every pointer 16-byte aligned
-static bool ln_vec_ok(int C, std::initializer_list<const void*> ptrs) {
-  if (C % 8 != 0 || C < 8 || C > 1024) return false;
+static bool all_aligned16(std::initializer_list<const void*> ptrs) {
   for (const void* q : ptrs)
     if (q != nullptr && !aligned16(q)) return false;
   return true;
 }
-static int ln_group_lanes(int C) { return C <= 128 ? 16 : (C <= 256 ? 32 : 64); }
-#ifndef CSTS_LN_FWD_R
-#define CSTS_LN_FWD_R 2            // rows per lane group and pass of ln_fwd_vec_kernel at C <= 512 (A/B build: 1)
-#endif
-static int64_t ln_fwd_vec_blocks(int64_t rows, int C) { return std::min<int64_t>(cdiv(rows * ln_group_lanes(C), 256 * (C <= 512 ? CSTS_LN_FWD_R : 2)), 4096); }
-static bool ln_bwd_vec(bool df, bool xf, dim3 grid, hipStream_t st, const void* dy, const void* x, const float* g, const float* mean,
-                       const float* rstd, void* dx, const void* addend, float* ws, int64_t rows, int C, const float* g1, Copy16 dx16) {
-  const size_t sh = (size_t)(512 / ln_group_lanes(C)) * 2 * C * sizeof(float);
-  if (sh > 65536) return false;
-  if (C <= 128) ln_bwd_vec_launch<16, 1, CSTS_LN_BWD_R>(df, xf, grid, sh, st, dy, x, g, mean, rstd, dx, addend, ws, rows, C, g1, dx16);
-  else if (C <= 256) ln_bwd_vec_launch<32, 1, CSTS_LN_BWD_R>(df, xf, grid, sh, st, dy, x, g, mean, rstd, dx, addend, ws, rows, C, g1, dx16);
-  else if (C <= 512) ln_bwd_vec_launch<64, 1, CSTS_LN_BWD_R>(df, xf, grid, sh, st, dy, x, g, mean, rstd, dx, addend, ws, rows, C, g1, dx16);
-  else ln_bwd_vec_launch<64, 2, 1>(df, xf, grid, sh, st, dy, x, g, mean, rstd, dx, addend, ws, rows, C, g1, dx16);
-  return true;
+// The grid of a backward launch, and with it the partial rows of the workspace, is that of the one-channel form whichever
+// form runs: the workspace is sized before the operands are known.
+static int64_t ln_bwd_blocks(int64_t rows, int C) {
+  return std::min<int64_t>(cdiv(rows, LN_BWD_WAVES * LN_FORMS<true>[ln_form(true, C, false)].R), CSTS_LN_BWD_CAP);
 }
-static int rows_per_wave(int C) { return C <= 192 ? 4 : (C <= 384 ? 2 : 1); }
-static int64_t ln_fwd_blocks(int64_t rows, int C) { return std::min<int64_t>(cdiv(rows, 4 * rows_per_wave(C)), 4096); }
-#ifndef CSTS_LN_BWD_CAP
-#define CSTS_LN_BWD_CAP 512        // workgroups of a LayerNorm-backward launch (two 512-thread workgroups per CU; A/B builds: 768 with CSTS_LN_BWD_MINW=6)
-#endif
-static int64_t ln_bwd_blocks(int64_t rows, int C) { return std::min<int64_t>(cdiv(rows, LN_BWD_WAVES * rows_per_wave(C)), CSTS_LN_BWD_CAP); }
+// k = 4 form + 2 (first dtype is fp32) + (second dtype is fp32) as a compile-time constant: the one dispatch of both directions
+template <class F, int... K> static void ln_pick(int k, F&& launch, std::integer_sequence<int, K...>) {
+  ((k == K ? launch(std::integral_constant<int, K>{}) : void()), ...);
+}
 
 extern "C" int csts_layernorm_fwd(const void* x, int x_dt, const float* gamma, const float* beta, void* y, int y_dt,
                                   float* mean, float* rstd, int64_t rows, int C, float eps, hipStream_t stream) {
@@ -618,29 +500,39 @@ extern "C" int csts_layernorm_fwd_add(const void* x, const void* addend, void* s
   CSTS_REQUIRE(x && gamma && beta && y, "null pointer");
   CSTS_REQUIRE((addend == nullptr) == (sum_out == nullptr), "addend and sum_out: both or neither");
   CSTS_REQUIRE(rows > 0 && C > 0 && C <= 64 * MAXV, "C must be in (0, 768]");
-  const bool xf = x_dt == CSTS_F32, yf = y_dt == CSTS_F32;
   FwdAdd fa;
   fa.addend = addend; fa.sum = sum_out;
-  if (ln_vec_ok(C, {x, y, gamma, beta, addend, sum_out})) {
-    const dim3 vgrid((unsigned)ln_fwd_vec_blocks(rows, C));
-    if (C <= 128) ln_fwd_vec_launch<16, 1, CSTS_LN_FWD_R>(xf, yf, vgrid, stream, x, gamma, beta, y, mean, rstd, rows, C, eps, fa);
-    else if (C <= 256) ln_fwd_vec_launch<32, 1, CSTS_LN_FWD_R>(xf, yf, vgrid, stream, x, gamma, beta, y, mean, rstd, rows, C, eps, fa);
-    else if (C <= 512) ln_fwd_vec_launch<64, 1, CSTS_LN_FWD_R>(xf, yf, vgrid, stream, x, gamma, beta, y, mean, rstd, rows, C, eps, fa);
-    else ln_fwd_vec_launch<64, 2, 2>(xf, yf, vgrid, stream, x, gamma, beta, y, mean, rstd, rows, C, eps, fa);
-    CSTS_LAUNCH_CHECK();
-    return 0;
-  }
-  const dim3 grid((unsigned)ln_fwd_blocks(rows, C));
-  if (C <= 128) ln_fwd_launch<2, 4>(xf, yf, grid, stream, x, gamma, beta, y, mean, rstd, rows, C, eps, fa);
-  else if (C <= 192) ln_fwd_launch<3, 4>(xf, yf, grid, stream, x, gamma, beta, y, mean, rstd, rows, C, eps, fa);
-  else if (C <= 384) ln_fwd_launch<6, 2>(xf, yf, grid, stream, x, gamma, beta, y, mean, rstd, rows, C, eps, fa);
-  else ln_fwd_launch<12, 1>(xf, yf, grid, stream, x, gamma, beta, y, mean, rstd, rows, C, eps, fa);
+  const int form = ln_form(false, C, all_aligned16({x, y, gamma, beta, addend, sum_out}));
+  const LnForm& f = LN_FORMS<false>[form];
+  const dim3 grid((unsigned)std::min<int64_t>(cdiv(rows * f.GL, 256 * f.R), 4096));
+  ln_pick(4 * form + 2 * (x_dt == CSTS_F32) + (y_dt == CSTS_F32), [&](auto k) {
+    constexpr LnForm F = LN_FORMS<false>[decltype(k)::value / 4];
+    hipLaunchKernelGGL((ln_fwd_kernel<F.W, F.GL, F.NCH, F.R, (decltype(k)::value & 2) != 0, (decltype(k)::value & 1) != 0>), grid,
+                       dim3(256), 0, stream, x, gamma, beta, y, mean, rstd, rows, C, eps, fa);
+  }, std::make_integer_sequence<int, 32>{});
   CSTS_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" size_t csts_layernorm_bwd_workspace(int64_t rows, int C) {
   return (size_t)ln_bwd_blocks(rows, C) * 2 * C * sizeof(float);
+}
+
+// One backward launch over `segs` stacked tensors (gamma[s]; ws holds ln_bwd_blocks partial rows of each) and, unless dgb[0] is
+// NULL (the deferred second stage), the reduction of each segment's partial rows into dgb[s] = dgamma | dbeta.
+static void ln_bwd_launch(int segs, bool aligned, const void* dy, int dy_dt, const void* x, int x_dt, const float* const (&gamma)[2],
+                          const float* mean, const float* rstd, void* dx, const void* addend, float* const (&dgb)[2], float* ws,
+                          int64_t rows, int C, Copy16 c16, hipStream_t stream) {
+  const int form = ln_form(true, C, aligned);
+  const int64_t nb = ln_bwd_blocks(rows, C);
+  const dim3 grid((unsigned)nb, (unsigned)segs);
+  const size_t sh = ln_bwd_lds(LN_FORMS<true>[form], C);
+  ln_pick(4 * form + 2 * (dy_dt == CSTS_F32) + (x_dt == CSTS_F32), [&](auto k) {
+    constexpr LnForm F = LN_FORMS<true>[decltype(k)::value / 4];
+    hipLaunchKernelGGL((ln_bwd_kernel<F.W, F.GL, F.NCH, F.R, (decltype(k)::value & 2) != 0, (decltype(k)::value & 1) != 0>), grid,
+                       dim3(512), sh, stream, dy, x, gamma[0], mean, rstd, dx, addend, ws, rows, C, gamma[1], c16);
+  }, std::make_integer_sequence<int, 32>{});
+  for (int s = 0; s < segs && dgb[0] != nullptr; ++s) csts_reduce_rows_launch(ws + s * nb * 2 * C, dgb[s], nb, 2 * C, 1.f, stream);
 }
 
 extern "C" int csts_layernorm_bwd(const void* dy, int dy_dt, const void* x, int x_dt, const float* gamma,
@@ -667,28 +559,9 @@ extern "C" int csts_layernorm_bwd_ex(const void* dy, const void* dy2, int dy_dt,
   CSTS_REQUIRE(dx_dt == x_dt, "dx must have the dtype of x");
   const int64_t nb = ln_bwd_blocks(rows, C);
   CSTS_REQUIRE(ws_bytes >= (size_t)nb * 2 * C * sizeof(float), "workspace too small");
-  const dim3 grid((unsigned)nb);
-  const size_t sh = (size_t)LN_BWD_WAVES * 2 * C * sizeof(float);
-  float* ws = reinterpret_cast<float*>(workspace);
-  const bool df = dy_dt == CSTS_F32, xf = x_dt == CSTS_F32;
-  if (ln_vec_ok(C, {dy, dy2, x, dx, addend, dx_bf16, gamma}) &&
-      ln_bwd_vec(df, xf, grid, stream, dy, x, gamma, mean, rstd, dx, addend, ws, rows, C, nullptr, c16)) {
-    CSTS_LAUNCH_CHECK();
-    if (dgamma != nullptr) {
-      csts_reduce_rows_launch(ws, dgamma, nb, 2 * C, 1.f, stream);
-      CSTS_LAUNCH_CHECK();
-    }
-    return 0;
-  }
-  if (C <= 128) ln_bwd_launch<2, 4>(df, xf, grid, sh, stream, dy, x, gamma, mean, rstd, dx, addend, ws, rows, C, nullptr, c16);
-  else if (C <= 192) ln_bwd_launch<3, 4>(df, xf, grid, sh, stream, dy, x, gamma, mean, rstd, dx, addend, ws, rows, C, nullptr, c16);
-  else if (C <= 384) ln_bwd_launch<6, 2>(df, xf, grid, sh, stream, dy, x, gamma, mean, rstd, dx, addend, ws, rows, C, nullptr, c16);
-  else ln_bwd_launch<12, 1>(df, xf, grid, sh, stream, dy, x, gamma, mean, rstd, dx, addend, ws, rows, C, nullptr, c16);
+  ln_bwd_launch(1, all_aligned16({dy, dy2, x, dx, addend, dx_bf16, gamma}), dy, dy_dt, x, x_dt, {gamma, nullptr}, mean, rstd, dx,
+                addend, {dgamma, nullptr}, reinterpret_cast<float*>(workspace), rows, C, c16, stream);
   CSTS_LAUNCH_CHECK();
-  if (dgamma != nullptr) {
-    csts_reduce_rows_launch(ws, dgamma, nb, 2 * C, 1.f, stream);
-    CSTS_LAUNCH_CHECK();
-  }
   return 0;
 }
 
@@ -703,29 +576,9 @@ extern "C" int csts_layernorm_bwd2(const void* dy, int dy_dt, const void* x, int
   CSTS_REQUIRE((dgb0 == nullptr) == (dgb1 == nullptr), "dgb0/dgb1: both or neither (neither = deferred second stage)");
   const int64_t nb = ln_bwd_blocks(rows, C);
   CSTS_REQUIRE(ws_bytes >= (size_t)2 * nb * 2 * C * sizeof(float), "workspace too small");
-  const dim3 grid((unsigned)nb, 2);
-  const size_t sh = (size_t)LN_BWD_WAVES * 2 * C * sizeof(float);
-  float* ws = reinterpret_cast<float*>(workspace);
-  const bool df = dy_dt == CSTS_F32, xf = x_dt == CSTS_F32;
-  if (ln_vec_ok(C, {dy, x, dx, gamma0, gamma1}) && ((rows * C) % 8 == 0) &&
-      ln_bwd_vec(df, xf, grid, stream, dy, x, gamma0, mean, rstd, dx, nullptr, ws, rows, C, gamma1, Copy16{})) {
-    CSTS_LAUNCH_CHECK();
-    if (dgb0 != nullptr) {
-      csts_reduce_rows_launch(ws, dgb0, nb, 2 * C, 1.f, stream);
-      csts_reduce_rows_launch(ws + nb * 2 * C, dgb1, nb, 2 * C, 1.f, stream);
-      CSTS_LAUNCH_CHECK();
-    }
-    return 0;
-  }
-  if (C <= 128) ln_bwd_launch<2, 4>(df, xf, grid, sh, stream, dy, x, gamma0, mean, rstd, dx, nullptr, ws, rows, C, gamma1);
-  else if (C <= 192) ln_bwd_launch<3, 4>(df, xf, grid, sh, stream, dy, x, gamma0, mean, rstd, dx, nullptr, ws, rows, C, gamma1);
-  else if (C <= 384) ln_bwd_launch<6, 2>(df, xf, grid, sh, stream, dy, x, gamma0, mean, rstd, dx, nullptr, ws, rows, C, gamma1);
-  else ln_bwd_launch<12, 1>(df, xf, grid, sh, stream, dy, x, gamma0, mean, rstd, dx, nullptr, ws, rows, C, gamma1);
+  // (rows * C) % 8 == 0: the second segment starts rows * C elements in and must be 16-byte aligned as well
+  ln_bwd_launch(2, all_aligned16({dy, x, dx, gamma0, gamma1}) && ((rows * C) % 8 == 0), dy, dy_dt, x, x_dt, {gamma0, gamma1}, mean,
+                rstd, dx, nullptr, {dgb0, dgb1}, reinterpret_cast<float*>(workspace), rows, C, Copy16{}, stream);
   CSTS_LAUNCH_CHECK();
-  if (dgb0 != nullptr) {
-    csts_reduce_rows_launch(ws, dgb0, nb, 2 * C, 1.f, stream);
-    csts_reduce_rows_launch(ws + nb * 2 * C, dgb1, nb, 2 * C, 1.f, stream);
-    CSTS_LAUNCH_CHECK();
-  }
   return 0;
 }

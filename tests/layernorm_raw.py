@@ -3,7 +3,7 @@ _batched / _wide -- against the fp64 reference and the bars of tests/layernorm_r
 (bf16 library) and tests/layernorm_worker.py (a child process on the fp16 library); not a test module itself.
 
 Every tensor of a call is a Buf: n elements inside a wider flat buffer, GUARD elements in front and behind, optionally `mis`
-elements further in, which breaks the 16-byte alignment the vector kernels need and so reaches the scalar kernels at C % 8 == 0.
+elements further in, which breaks the 16-byte alignment the W = 8 forms of the kernels need and so reaches the W = 1 forms at C % 8 == 0.
   inputs : the whole buffer is NaN except the operand itself: a kernel that reads outside it ends with a non-finite output (lanes
            and rows past the end read CLAMPED addresses of the operand itself).
   outputs: the operand is pre-filled with one NaN bit pattern, everything else with another (the sentinel).  After the call every
@@ -104,6 +104,14 @@ def _k(got, ref, S, dtype):
     return _ratio_at(excess, LR.U * S)
 
 
+OUTPUTS = None                                   # a list (tools/ln_digest.py): every run_* appends (name, output Buf)
+
+
+def _record(name, **bufs):
+    if OUTPUTS is not None:
+        OUTPUTS.extend((f"{name} | {k}", b) for k, b in bufs.items() if b is not None)
+
+
 def _mis(mis, name):
     return mis[1] if mis is not None and mis[0] == name else 0
 
@@ -125,7 +133,7 @@ def fwd_grid(rows, C, vec):
 
 
 def bwd_grid(rows, C, vec):
-    """The same for a backward launch (one segment).  The vector kernel takes one row per lane group and pass."""
+    """The same for a backward launch (one segment).  The W = 8 form takes one row per lane group and pass."""
     want = -(-rows // (LN_BWD_WAVES * rows_per_wave(C)))
     nb = min(want, LN_BWD_CAP)
     return nb, want, nb * (512 // group_lanes(C) if vec else LN_BWD_WAVES * rows_per_wave(C))
@@ -179,6 +187,7 @@ def run_fwd(rows, C, xdt, ydt, dev, kind="plain", seed=1, eps=1e-6, mis=None, st
     if keep is not None:
         keep.update(y=y.view().clone(), mean=mean.view().clone(), rstd=rstd.view().clone(), sum=None if s is None else s.view().clone(),
                     gamma=g32, ref=f)
+    _record(r["name"], y=y, mean=mean, rstd=rstd, sum_out=s)
     return [r]
 
 
@@ -291,6 +300,7 @@ def run_bwd(rows, C, dydt, xdt, dev, kind="plain", seed=2, eps=1e-6, mis=None, d
             r["copy_equal"] = torch.equal(c16.view(), p.dx.view())
     if keep is not None:
         keep.update(dx=p.dx.view().clone(), dgb=dgb.view().clone(), ws=ws.view().clone(), copy=None if c16 is None else c16.view().clone())
+    _record(name, dx=p.dx, copy16=c16, ws=ws, dgb=dgb)
     return [r]
 
 
@@ -310,6 +320,7 @@ def run_bwd2(rows, C, dydt, xdt, dev, kinds=("plain", "offset"), seed=3, eps=1e-
     torch.cuda.synchronize()
     ok = ws.finite() and ws.guards_ok() and dgbs[0].guards_ok() and dgbs[1].guards_ok()
     res = [p.result(f"bwd2[{i}] rows {rows} C {C} dy {tag(dydt)} x {tag(xdt)} {kinds[i]}", i, dgbs[i].view(), ok) for i in range(2)]
+    _record(f"bwd2 rows {rows} C {C} dy {tag(dydt)} x {tag(xdt)}", dx=p.dx, ws=ws, dgb0=dgbs[0], dgb1=dgbs[1])
     one = {}
     run_bwd(rows, C, dydt, xdt, dev, kind=kinds[0], seed=seed, eps=eps, keep=one)
     res[0]["seg0_equal"] = (torch.equal(one["dx"], p.dx.view()[:n]) and torch.equal(one["dgb"], dgbs[0].view())
@@ -404,8 +415,8 @@ KINDS = ("plain", "offset")
 def small_table(C, pairs):
     """The small-instantiation runs of one C as (rows, dtype pair, value set): every rows of SMALL_ROWS once, with the dtype pairs and
     the value sets dealt round-robin (six rows: every pair and both sets at every C), then every pair on both sets at rows = 33 -- a
-    ragged last pass of the forward vector kernels (2 rows per group) and of the scalar kernels (4 / 2 rows per wave), and more rows
-    than one pass of the backward vector kernels covers at C 136 to 192 and 264 to 384 (a second trip of some lane groups)."""
+    ragged last pass of the forward W = 8 forms (2 rows per group) and of the W = 1 forms (4 / 2 rows per wave), and more rows
+    than one pass of the backward W = 8 forms covers at C 136 to 192 and 264 to 384 (a second trip of some lane groups)."""
     ci = (VEC_C + SCALAR_C).index(C)
     t = [(rows, pairs[(i + ci) % len(pairs)], KINDS[i % 2]) for i, rows in enumerate(SMALL_ROWS)]
     return t + [(33, pr, k) for pr in pairs for k in KINDS]
@@ -427,7 +438,7 @@ def small_bwd(C, dev, pairs, eps=1e-6):
 
 
 def fwd_add_cases(dev, H):
-    """csts_layernorm_fwd_add: fp32 and 16-bit x, vector and scalar C, odd rows (a ragged last pass of every form)."""
+    """csts_layernorm_fwd_add: fp32 and 16-bit x, W = 8 and W = 1 widths, odd rows (a ragged last pass of every form)."""
     res = []
     for C in (8, 96, 100, 191, 384, 768):
         for xdt, ydt in ((F, F), (F, H), (H, H), (H, F)):
@@ -447,3 +458,45 @@ def bwd_ex_cases(dev, H, C):
         res += run_bwd(70, C, F, F, dev, kind="plain", seed=C + 2, copy=copy, dy2=True, addend=True)
         res += run_bwd(70, C, H, F, dev, kind="offset", seed=C + 3, copy=copy)
     return res + run_bwd(140, C, F, F, dev, kind="plain", seed=C + 4, copy=70)
+
+
+def misaligned_cases(dev, H, C):
+    """One operand at a time off its 16-byte alignment (fp32: one element; 16-bit: one and three) at a width the W = 8 forms would
+    otherwise take."""
+    res = []
+    for op in ("x", "y", "gamma", "beta"):
+        res += run_fwd(33, C, F, F, dev, kind="offset", seed=C, mis=(op, 1))
+    for op, k in (("x", 1), ("x", 3), ("y", 1), ("y", 3)):
+        res += run_fwd(33, C, H, H, dev, kind="offset", seed=C + 1, mis=(op, k))
+    for op in ("addend", "sum"):
+        res += run_fwd(33, C, F, H, dev, kind="offset", seed=C + 2, mis=(op, 1), add="plain")
+        res += run_fwd(33, C, H, F, dev, kind="plain", seed=C + 3, mis=(op, 3), add="plain")
+    for op in ("dy", "x", "dx", "gamma", "addend", "copy"):
+        res += run_bwd(33, C, F, F, dev, kind="offset", seed=C + 4, mis=(op, 1), addend=True, copy="plain")
+    for op, k in (("dy", 1), ("dy", 3), ("x", 3), ("dx", 1), ("addend", 3), ("dy2", 1)):
+        res += run_bwd(33, C, H, H, dev, kind="offset", seed=C + 5, mis=(op, k), addend=True, dy2=True)
+    return res
+
+
+MISALIGNED_C = (96, 192, 384, 768)
+
+
+def fwd_trips(H):
+    """Grid-stride trips of a forward launch: (C, rows, x dtype, y dtype), rows just past the 4096-workgroup cap."""
+    return [(96, 131072 + 35, H, H), (768, 32768 + 9, F, H), (100, 65536 + 7, F, F)]
+
+
+def bwd_trips(H):
+    """The same for a backward launch: (C, rows, dy dtype, x dtype, whether the grid is capped at 512)."""
+    return [(96, 16384 + 37, F, F, True), (192, 8192 + 19, H, F, False), (192, 16384 + 19, F, H, True), (384, 4096 + 9, H, H, False),
+            (384, 8192 + 9, F, F, True), (768, 4096 + 9, H, F, True), (100, 16384 + 5, F, F, True), (383, 8192 + 3, H, H, True),
+            (767, 4096 + 3, F, H, True)]
+
+
+DEFERRED = [(96, 77), (100, 300), (192, 2100), (768, 4096 + 9)]         # (C, rows): 3, 10, 66 and 512 partial rows
+BWD2 = [(C, rows) for C in (8, 96, 192) for rows in (5, 77, 16384 + 37)] + [(7, 5), (100, 77), (191, 16384 + 37)]
+
+
+def bwd2_pairs(C, rows, H):
+    """The (dy, x) dtype pairs test_bwd2 runs at (C, rows)."""
+    return ((F, F), (H, H)) if rows < 1000 else (((H, F),) if C != 96 else ((F, H),))

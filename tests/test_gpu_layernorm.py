@@ -18,20 +18,22 @@ mean and rstd of the x they read, rounded to fp32.  Smallest row variance per ca
 0.032 (C 7), 0.036 (C 8, 16421 rows), 0.12 (C 8, 16), >= 0.37 at C >= 24 -- no such row is near zero; exactly 0 at C = 1 (a row
 of one element) and in test_flat_rows (1e-8 and the constant row, on purpose); 2.3e-11 in the fp16 subnormal set (on purpose).
 
-Which test runs which kernel (every one with XF32 / YF32 resp. DYF32 / XF32 both ways: the dtype pairs are dealt over the rows):
-  ln_fwd_kernel / ln_bwd_kernel <2,4>   C 1, 7, 63, 65, 100   <3,4>  C 129, 191   <6,2>  C 250, 383   <12,1>  C 500, 767
+Which test runs which kernel.  ln_fwd_kernel / ln_bwd_kernel <W, GL, NCH, R, ...> are one template per direction: W = 8 channels
+per lane and chunk (C % 8 == 0, every operand 16-byte aligned) or W = 1 (everything else, a whole wave per row).  Every form runs
+with XF32 / YF32 resp. DYF32 / XF32 both ways: the dtype pairs are dealt over the rows.
+  W = 1:  <1,64,2,4>   C 1, 7, 63, 65, 100   <1,64,3,4>  C 129, 191   <1,64,6,2>  C 250, 383   <1,64,12,1>  C 500, 767
       test_small_forward / _backward; at C 96 / 192 / 384 / 768 through a misaligned operand: test_scalar_kernels_at_model_widths
-  ln_fwd_vec_kernel / ln_bwd_vec_kernel <16,1>  C 8, 16, 24, 40, 96, 128 (1, 2, 3, 5, 12, 16 of 16 lanes active)
-      <32,1>  C 136, 192, 256 (17, 24, 32 of 32)   <64,1>  C 264, 384, 512 (33, 48, 64 of 64)   <64,2>  C 520, 768 (second chunk: 1, 32 lanes)
+  W = 8:  <8,16,1>  C 8, 16, 24, 40, 96, 128 (1, 2, 3, 5, 12, 16 of 16 lanes active)   <8,32,1>  C 136, 192, 256 (17, 24, 32 of 32)
+      <8,64,1>  C 264, 384, 512 (33, 48, 64 of 64)   <8,64,2>  C 520, 768 (second chunk: 1, 32 lanes)   (R: 2 forward, 1 backward)
       test_small_forward / _backward
-  segment 1 of both backward kernels (blockIdx.y == 1, gamma1, the workspace offset): test_bwd2
+  segment 1 of both roles of the backward kernel (blockIdx.y == 1, gamma1, the workspace offset): test_bwd2
   reduce_rows_kernel<2> nrows 1, 2, 3, 8   <8> 9, 63, 64   <32> 65, 129, 515: test_reduce_rows; as the second stage of a deferred
       backward (3, 10, 66, 512 partial rows): test_bwd_deferred_second_stage
   reduce_rows_batched_kernel: test_reduce_rows_batched     reduce_rows_wide_kernel: test_reduce_rows_wide*
   libcsts_hip_f16.so, all of the LayerNorm cases above but the trips: test_fp16_library
-Grid-stride trips (computed grid | cap): forward vector C 96, 131107 rows: 4098 | 4096 workgroups of 32 rows; C 768, 32777 rows:
-4098 | 4096 of 8 rows; forward scalar C 100, 65543 rows: 4097 | 4096 of 16 rows.  Backward (cap 512): C 96, 16421 rows: 514
-workgroups of 32 rows; C 192, 16403: 513 of 16; C 384, 8201: 513 of 8; C 768, 4105: 514 of 8; scalar C 100, 16389: 513 of 32;
+Grid-stride trips (computed grid | cap): forward W = 8 C 96, 131107 rows: 4098 | 4096 workgroups of 32 rows; C 768, 32777 rows:
+4098 | 4096 of 8 rows; forward W = 1 C 100, 65543 rows: 4097 | 4096 of 16 rows.  Backward (cap 512): C 96, 16421 rows: 514
+workgroups of 32 rows; C 192, 16403: 513 of 16; C 384, 8201: 513 of 8; C 768, 4105: 514 of 8; W = 1 C 100, 16389: 513 of 32;
 C 383, 8195: 513 of 16; C 767, 4099: 513 of 8.  C 192 with 8211 rows and C 384 with 4105 launch 257 workgroups, not capped, and
 still take two trips (see test_grid_stride_backward).  csts_reduce_rows_wide: 4097 | 4096 workgroups.
 
@@ -39,24 +41,25 @@ A bug these tests found, fixed in norm.hip: csts_layernorm_fwd_add with 16-bit x
 storing the rounded one (test_fwd_add_16bit_sum_consumed_by_backward).  The model's residual stream is fp32: its results are unchanged.
 
 Mutation check (scratch builds of norm.hip loaded through CSTS_HIP_LIB, one arithmetic-only change each, no new address and no
-longer loop).  Of the 108 tests here that run the bf16 library, on MI355X, each mutant fails:
-  20  (a) ln_fwd_vec_kernel computes the variance as E[x^2] - mean^2
-          (test_small_forward 14: every vector C; test_flat_rows 3, test_grid_stride_forward 2, test_fwd_add)
-  43  (b) group_sum starts at GL / 4: half the group left out
+longer loop).  The counts were taken while each role (W = 8, W = 1) was a kernel text of its own: a mutant changed the one role
+it names.  Of the 108 tests here that run the bf16 library, on MI355X, each mutant fails:
+  20  (a) the W = 8 role of ln_fwd_kernel computes the variance as E[x^2] - mean^2
+          (test_small_forward 14: every W = 8 width; test_flat_rows 3, test_grid_stride_forward 2, test_fwd_add)
+  43  (b) group_sum starts at GL / 4 in the W = 8 role: half the group left out
           (test_small_forward 10 and test_small_backward 10: every C whose active lanes fill more than half a group; test_grid_stride_* 8, test_bwd2 6,
           test_bwd_deferred_second_stage 3, test_bwd_ex 2, test_flat_rows 2, test_fwd_add*, 2)
-  17  (c) ln_bwd_vec_kernel leaves the rows of a group's later trips out of dg
-          (test_grid_stride_backward 6: every vector case; test_small_backward 4: C 136, 192, 264, 384, where 33 rows are more than
+  17  (c) the W = 8 role of ln_bwd_kernel leaves the rows of a group's later trips out of dg
+          (test_grid_stride_backward 6: every W = 8 case; test_small_backward 4: C 136, 192, 264, 384, where 33 rows are more than
           one pass; test_bwd2 4, test_bwd_deferred_second_stage 2, test_bwd_ex 1)
-   3  (d) ln_bwd_kernel keeps gamma for blockIdx.y == 1 (test_bwd2: C 7, 100, 191 -- the three scalar cases)
+   3  (d) the W = 1 role of ln_bwd_kernel keeps gamma for blockIdx.y == 1 (test_bwd2: C 7, 100, 191 -- the three W = 1 cases)
    3  (e) reduce_rows_kernel<8> adds red[r] in the reverse order (test_reduce_rows 9, 63, 64: the bits differ, the bars still hold)
-  15  (f) ln_fwd_kernel takes lane + 64 j <= C into the variance
-          (test_small_forward 10: every scalar C but 1; test_scalar_kernels_at_model_widths 96 -- at 192, 384 and 768 no lane has
+  15  (f) the W = 1 role of ln_fwd_kernel takes lane + 64 j <= C into the variance
+          (test_small_forward 10: every W = 1 width but 1; test_scalar_kernels_at_model_widths 96 -- at 192, 384 and 768 no lane has
           lane + 64 j == C, the mutant is the same kernel there; test_flat_rows, test_grid_stride_forward, test_fwd_add* 1 each)
 Of these, test_layernorm, test_layernorm_backward_two_gradients_and_scaled_copy and test_layernorm_with_folded_skip_add of
 tests/test_gpu_ops.py (fp32 x, aligned, C in 96 / 192 / 200 / 384 / 768, zero-mean rows, whole-tensor rel-L2 at 2e-6 to 1e-4) cannot
 see (a) -- on zero-mean data the one-pass rstd is as good as the two-pass one -- nor (d) (no call of csts_layernorm_bwd2), (e) (a
-reordering inside 1e-4) and (f) (the scalar kernels never run); (b) they would see, and (c) at C = 192 and 384, where 210 rows
+reordering inside 1e-4) and (f) (the W = 1 forms never run); (b) they would see, and (c) at C = 192 and 384, where 210 rows
 are several trips.  The mutants were not run against them on the GPU.
 """
 import json
@@ -140,28 +143,16 @@ def test_flat_rows(C):
     _hold(f"flat C {C}", res)
 
 
-# ------------------------------------------------------------------------------------- scalar kernels at model widths
-@pytest.mark.parametrize("C", [96, 192, 384, 768])
+# ------------------------------------------------------------------------------------- the W = 1 forms at model widths
+@pytest.mark.parametrize("C", R.MISALIGNED_C)
 def test_scalar_kernels_at_model_widths(C):
-    """One operand at a time off its 16-byte alignment (fp32: one element; 16-bit: one and three): the dispatch must take
-    ln_fwd_kernel / ln_bwd_kernel.  Their summation order differs from the vector kernels', so only the fp64 bars apply."""
-    res = []
-    for op in ("x", "y", "gamma", "beta"):
-        res += R.run_fwd(33, C, F, F, DEV, kind="offset", seed=C, mis=(op, 1))
-    for op, k in (("x", 1), ("x", 3), ("y", 1), ("y", 3)):
-        res += R.run_fwd(33, C, H, H, DEV, kind="offset", seed=C + 1, mis=(op, k))
-    for op in ("addend", "sum"):
-        res += R.run_fwd(33, C, F, H, DEV, kind="offset", seed=C + 2, mis=(op, 1), add="plain")
-        res += R.run_fwd(33, C, H, F, DEV, kind="plain", seed=C + 3, mis=(op, 3), add="plain")
-    for op in ("dy", "x", "dx", "gamma", "addend", "copy"):
-        res += R.run_bwd(33, C, F, F, DEV, kind="offset", seed=C + 4, mis=(op, 1), addend=True, copy="plain")
-    for op, k in (("dy", 1), ("dy", 3), ("x", 3), ("dx", 1), ("addend", 3), ("dy2", 1)):
-        res += R.run_bwd(33, C, H, H, DEV, kind="offset", seed=C + 5, mis=(op, k), addend=True, dy2=True)
-    _hold(f"misaligned C {C}", res)
+    """One operand at a time off its 16-byte alignment (fp32: one element; 16-bit: one and three): the dispatch must take the
+    W = 1 forms of ln_fwd_kernel / ln_bwd_kernel.  Their summation order differs from the W = 8 forms', so only the fp64 bars apply."""
+    _hold(f"misaligned C {C}", R.misaligned_cases(DEV, H, C))
 
 
 # ------------------------------------------------------------------------------------- grid-stride trips
-_FWD_TRIPS = [(96, 131072 + 35, H, H), (768, 32768 + 9, F, H), (100, 65536 + 7, F, F)]
+_FWD_TRIPS = R.fwd_trips(H)
 
 
 @pytest.mark.parametrize("C,rows,xdt,ydt", _FWD_TRIPS, ids=[f"C{c}-rows{r}" for c, r, _, _ in _FWD_TRIPS])
@@ -172,15 +163,13 @@ def test_grid_stride_forward(C, rows, xdt, ydt):
     _hold(f"fwd trips C {C} rows {rows}", R.run_fwd(rows, C, xdt, ydt, DEV, kind="offset", seed=C))
 
 
-_BWD_TRIPS = [(96, 16384 + 37, F, F, True), (192, 8192 + 19, H, F, False), (192, 16384 + 19, F, H, True), (384, 4096 + 9, H, H, False),
-              (384, 8192 + 9, F, F, True), (768, 4096 + 9, H, F, True), (100, 16384 + 5, F, F, True), (383, 8192 + 3, H, H, True),
-              (767, 4096 + 3, F, H, True)]
+_BWD_TRIPS = R.bwd_trips(H)
 
 
 @pytest.mark.parametrize("C,rows,dydt,xdt,capped", _BWD_TRIPS, ids=[f"C{c}-rows{r}" for c, r, _, _, _ in _BWD_TRIPS])
 def test_grid_stride_backward(C, rows, dydt, xdt, capped):
     """Rows past what one pass of a backward launch covers, on offset values, so that the rows of a group's second trip matter to
-    dgamma.  The grid is cdiv(rows, 8 waves x rows_per_wave(C)) capped at 512.  At C = 192 and 384 the vector kernel's lane groups
+    dgamma.  The grid is cdiv(rows, 8 waves x rows_per_wave(C)) capped at 512.  At C = 192 and 384 the W = 8 form's lane groups
     take one row per pass and a workgroup holds half as many groups as that formula gives it rows, so every launch of more than 16
     (8) rows takes a second trip, capped or not: 8192 + 19 and 4096 + 9 rows do so on 257 workgroups, 16384 + 19 and 8192 + 9 on
     the capped 512."""
@@ -219,7 +208,7 @@ def test_bwd_ex(C):
     _hold(f"bwd_ex C {C}", res)
 
 
-@pytest.mark.parametrize("C,rows", [(96, 77), (100, 300), (192, 2100), (768, 4096 + 9)])
+@pytest.mark.parametrize("C,rows", R.DEFERRED)
 def test_bwd_deferred_second_stage(C, rows):
     """dgamma == NULL: the call writes the partial rows only; csts_reduce_rows over csts_layernorm_bwd_workspace / (2 C 4) rows
     finishes them (3, 10, 66 and 512 rows: reduce_rows_kernel<2>, <8>, <32>, <32>), bit for bit what the non-deferred call gives."""
@@ -231,16 +220,13 @@ def test_bwd_deferred_second_stage(C, rows):
 
 
 # ------------------------------------------------------------------------------------- csts_layernorm_bwd2
-_BWD2 = [(C, rows) for C in (8, 96, 192) for rows in (5, 77, 16384 + 37)] + [(7, 5), (100, 77), (191, 16384 + 37)]
-
-
-@pytest.mark.parametrize("C,rows", _BWD2, ids=[f"C{c}-rows{r}" for c, r in _BWD2])
+@pytest.mark.parametrize("C,rows", R.BWD2, ids=[f"C{c}-rows{r}" for c, r in R.BWD2])
 def test_bwd2(C, rows):
     """Two stacked tensors, gamma0 != gamma1, plain values in segment 0 and offset values in segment 1.  C = 7 with 5 rows and
-    C = 100 with 77: (rows C) % 8 != 0, and an odd C: the scalar kernel with blockIdx.y == 1.  (With C % 8 == 0 the product is
+    C = 100 with 77: (rows C) % 8 != 0, and an odd C: the W = 1 form with blockIdx.y == 1.  (With C % 8 == 0 the product is
     always a multiple of 8: that condition can only turn away what C % 8 != 0 has turned away already.)"""
     res = []
-    for dydt, xdt in ((F, F), (H, H)) if rows < 1000 else (((H, F),) if C != 96 else ((F, H),)):
+    for dydt, xdt in R.bwd2_pairs(C, rows, H):
         res += R.run_bwd2(rows, C, dydt, xdt, DEV, seed=C + rows)
     assert all(r.get("seg0_equal", True) is True for r in res)
     _hold(f"bwd2 C {C} rows {rows}", res)
