@@ -332,35 +332,36 @@ __device__ __forceinline__ void ovy_block(int (&Y)[2][2], int& U, int& V, int X,
 }
 
 // The row pairs [P0, P0 + OVY_BAND) of one frame on the vector path, by the 256 threads of a workgroup: frames / out the first byte of
-// the FRAME (4-byte aligned, W % 4 == 0) and of its output, m its map, f what ovy_frame says of it.  Dynamic LDS: 2 OVY_BAND row
+// the FRAME (4-byte aligned, W % 4 == 0) and of its output, m its map, f what ovy_frame says of it.  The frame is the H x W window of
+// the surface sf (Ws % 4 == 0, left % 4 == 0: every row of the window starts on a dword as well); out is a surface like it.  Dynamic LDS: 2 OVY_BAND row
 // entries, the JET table, the map, W column entries.  gaze_overlay_yuv_vec_kernel and group_gaze_overlay_yuv_kernel are this
 // function under two ways of finding the frame, so their bytes agree.
 template <bool NV12>
 __device__ __forceinline__ void ovy_vec_band(uint8_t* lds, const uint8_t* frames, uint8_t* out, const float* __restrict__ m,
-                                             const OvyFrame& f, int P0, int H, int W, int S, int mh, int mw, float alpha, int radius,
-                                             const YuvCoef& kf, const RgbCoef& kr) {
+                                             const OvyFrame& f, int P0, int H, int W, const YuvSurf& sf, int S, int mh, int mw,
+                                             float alpha, int radius, const YuvCoef& kf, const RgbCoef& kr) {
   OvRow* rows = reinterpret_cast<OvRow*>(lds);
   float* lut = reinterpret_cast<float*>(rows + 2 * OVY_BAND);
   float* map = lut + 256 * 3;                                   // 16-byte aligned
   uint2* cols = reinterpret_cast<uint2*>(map + ((mh * mw + 3) & ~3));
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int npairs = min(OVY_BAND, (H >> 1) - P0);
-  const int hw = W >> 1;
+  const int Ws = sf.Ws;
   const bool in_place = frames == out;
   if (!f.crop && !f.marked && in_place) return;                 // uniform: nothing of this frame is drawn
   ovy_tables(rows, lut, map, cols, m, f, alpha, 2 * P0, 2 * npairs, 0, W, H, W, S, mh, mw, tid);
   __syncthreads();
 
   const float oma = 1.0f - alpha;
-  const int64_t c0 = (int64_t)H * W, vplane = (int64_t)(H >> 1) * hw;
+  const int64_t vplane = yuv_vplane(sf);
   for (int pr = wv; pr < npairs; pr += 4) {                     // everything about the row pair is wave-uniform
     const int cy = P0 + pr;
     const OvyPair p = ovy_pair(rows + 2 * pr, cy, f, radius);
     if (!p.drawn && in_place) continue;
-    const int64_t l0 = (int64_t)(2 * cy) * W, q0 = c0 + (int64_t)cy * (NV12 ? W : hw);
+    const int64_t l0 = yuv_luma_row(sf, 2 * cy), q0 = yuv_chroma_row(sf, cy, NV12);
     for (int g = lane; g < (W >> 2); g += 64) {
       uint32_t a = *reinterpret_cast<const uint32_t*>(frames + l0 + 4 * g);
-      uint32_t b = *reinterpret_cast<const uint32_t*>(frames + l0 + W + 4 * g);
+      uint32_t b = *reinterpret_cast<const uint32_t*>(frames + l0 + Ws + 4 * g);
       uint32_t c;                                               // U0 | V0 << 8 | U1 << 16 | V1 << 24
       if (NV12) {
         c = *reinterpret_cast<const uint32_t*>(frames + q0 + 4 * g);
@@ -383,7 +384,7 @@ __device__ __forceinline__ void ovy_vec_band(uint8_t* lds, const uint8_t* frames
         }
       }
       *reinterpret_cast<uint32_t*>(out + l0 + 4 * g) = a;
-      *reinterpret_cast<uint32_t*>(out + l0 + W + 4 * g) = b;
+      *reinterpret_cast<uint32_t*>(out + l0 + Ws + 4 * g) = b;
       if (NV12) {
         *reinterpret_cast<uint32_t*>(out + q0 + 4 * g) = c;
       } else {
@@ -394,17 +395,17 @@ __device__ __forceinline__ void ovy_vec_band(uint8_t* lds, const uint8_t* frames
   }
 }
 
-// grid N * bands, 256 threads; W % 4 == 0, frames and out 4-byte aligned; dynamic LDS as ovy_vec_band states it
+// grid N * bands, 256 threads; W, Ws, left % 4 == 0, frames and out 4-byte aligned; dynamic LDS as ovy_vec_band states it
 template <bool NV12>
 __global__ __launch_bounds__(256) void gaze_overlay_yuv_vec_kernel(const uint8_t* frames, uint8_t* out, const float* __restrict__ rescaled,
                                                                    const int* __restrict__ centers, const int* __restrict__ params,
-                                                                   int bands, int H, int W, int S, int mh, int mw, float alpha,
-                                                                   int radius, YuvCoef kf, RgbCoef kr) {
+                                                                   int bands, int H, int W, YuvSurf sf, int S, int mh, int mw,
+                                                                   float alpha, int radius, YuvCoef kf, RgbCoef kr) {
   extern __shared__ __align__(16) uint8_t lds[];
-  const int64_t n = blockIdx.x / bands, f0 = n * yuv_frame_bytes(H, W);
+  const int64_t n = blockIdx.x / bands, f0 = n * yuv_frame_bytes(sf);
   const OvyFrame f = ovy_frame(centers, params, n, S);
-  ovy_vec_band<NV12>(lds, frames + f0, out + f0, rescaled + n * mh * mw, f, (int)(blockIdx.x % bands) * OVY_BAND, H, W, S, mh, mw, alpha,
-                     radius, kf, kr);
+  ovy_vec_band<NV12>(lds, frames + f0, out + f0, rescaled + n * mh * mw, f, (int)(blockIdx.x % bands) * OVY_BAND, H, W, sf, S, mh, mw,
+                     alpha, radius, kf, kr);
 }
 
 // ---- the overlays of a group: one launch over jobs of different sizes (include/csts_hip.h, "gaze overlay of a group") --------------
@@ -476,7 +477,7 @@ __global__ __launch_bounds__(256) void group_gaze_overlay_yuv_kernel(const int64
   const int64_t n = job[OVG_ROW0] + k, f0 = k * yuv_frame_bytes(H, W);
   const OvyFrame f = ovy_frame(centers, n, (int)job[OVG_NH], (int)job[OVG_NW], (int)job[OVG_Y0], (int)job[OVG_X0], S);
   ovy_vec_band<NV12>(lds, reinterpret_cast<const uint8_t*>(job[OVG_SRC]) + f0, reinterpret_cast<uint8_t*>(job[OVG_DST]) + f0,
-                     rescaled + n * mh * mw, f, band * OVY_BAND, H, W, S, mh, mw, alpha, radius, kf, kr);
+                     rescaled + n * mh * mw, f, band * OVY_BAND, H, W, yuv_tight(H, W), S, mh, mw, alpha, radius, kf, kr);
 }
 
 // points on the crop -> points on the source frame and marker centres, one thread per row: infer.points_to_source followed by
@@ -563,12 +564,12 @@ __host__ __device__ inline int ovy_pair_bytes(int tw, int* lcap, int* ccap) {
 }
 
 // grid N * bands * xtiles, 256 threads.  src / dst: the addresses of frames / out rounded DOWN to 16 bytes, the tensors are the
-// bytes [lo, hi) / from olo on.  twn: pixels of a full tile (a multiple of 16).  Dynamic LDS: 2 OVY_BAND row entries, the JET table,
+// bytes [lo, hi) / from olo on; the frames are the H x W windows of the surfaces sf, out holds surfaces like them.  twn: pixels of a full tile (a multiple of 16).  Dynamic LDS: 2 OVY_BAND row entries, the JET table,
 // the map, twn column entries, OVY_PAIRS source spans and OVY_PAIRS images.
 __global__ __launch_bounds__(256) void gaze_overlay_yuv_kernel(const uint8_t* src, int64_t lo, int64_t hi, uint8_t* dst, int64_t olo,
                                                                const float* __restrict__ rescaled, const int* __restrict__ centers,
                                                                const int* __restrict__ params, int bands, int xtiles, int twn, int H,
-                                                               int W, int S, int mh, int mw, float alpha, int radius, int layout,
+                                                               int W, YuvSurf sf, int S, int mh, int mw, float alpha, int radius, int layout,
                                                                YuvCoef kf, RgbCoef kr) {
   extern __shared__ __align__(16) uint8_t lds[];
   OvRow* rows = reinterpret_cast<OvRow*>(lds);
@@ -582,7 +583,7 @@ __global__ __launch_bounds__(256) void gaze_overlay_yuv_kernel(const uint8_t* sr
   const int tid = threadIdx.x;
   const int xt = blockIdx.x % xtiles, band = (blockIdx.x / xtiles) % bands;
   const int64_t n = blockIdx.x / xtiles / bands;
-  const int x0 = xt * twn, tw = min(twn, W - x0), hw = W >> 1, ht = tw >> 1;
+  const int x0 = xt * twn, tw = min(twn, W - x0), ht = tw >> 1;
   const int P0 = band * OVY_BAND, npairs = min(OVY_BAND, (H >> 1) - P0);
   const bool nv12 = layout == CSTS_YUV_NV12;
   const bool in_place = src == dst && lo == olo;
@@ -593,7 +594,7 @@ __global__ __launch_bounds__(256) void gaze_overlay_yuv_kernel(const uint8_t* sr
   __syncthreads();
 
   const float oma = 1.0f - alpha;
-  const int64_t fin = lo + n * yuv_frame_bytes(H, W), fout = olo + n * yuv_frame_bytes(H, W);
+  const int64_t fin = lo + n * yuv_frame_bytes(sf), fout = olo + n * yuv_frame_bytes(sf);
   const int base[4] = {0, lcap, 2 * lcap, 2 * lcap + ccap};    // where the four spans of a pair lie in its LDS bytes
   const int len[4] = {tw, tw, nv12 ? tw : ht, ht};
   for (int pp = 0; pp < npairs; pp += OVY_PAIRS) {
@@ -610,8 +611,8 @@ __global__ __launch_bounds__(256) void gaze_overlay_yuv_kernel(const uint8_t* sr
       pair[q] = ovy_pair(rows + 2 * (pp + q), cy, f, radius);
       live[q] = !in_place || pair[q].drawn;
       if (!live[q]) continue;
-      const int64_t lum = (int64_t)(2 * cy) * W + x0, chr = (int64_t)H * W + (nv12 ? (int64_t)cy * W + x0 : (int64_t)cy * hw + (x0 >> 1));
-      const int64_t off[4] = {lum, lum + W, chr, chr + (int64_t)(H >> 1) * hw};
+      const int64_t lum = yuv_luma_row(sf, 2 * cy) + x0, chr = yuv_chroma_row(sf, cy, nv12) + (nv12 ? x0 : x0 >> 1);
+      const int64_t off[4] = {lum, lum + sf.Ws, chr, chr + yuv_vplane(sf)};
       uint8_t* d = in + q * pair_bytes;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -684,17 +685,20 @@ extern "C" int csts_gaze_overlay(const uint8_t* frames_nhwc, const float* rescal
   return 0;
 }
 
-extern "C" int csts_gaze_overlay_yuv(const uint8_t* frames_yuv, const float* rescaled, const int* centers, const int* params,
-                                     uint8_t* out, int64_t N, int H, int W, int S, int mh, int mw, float alpha, int radius, int layout,
-                                     int matrix, int full_range, hipStream_t stream) {
+extern "C" int csts_gaze_overlay_yuv_win(const uint8_t* frames_yuv, const float* rescaled, const int* centers, const int* params,
+                                         uint8_t* out, int64_t N, int H, int W, int Hs, int Ws, int top, int left, int S, int mh,
+                                         int mw, float alpha, int radius, int layout, int matrix, int full_range,
+                                         hipStream_t stream) {
   CSTS_REQUIRE(frames_yuv && rescaled && params && out, "bad args (frames, rescaled, params and out must not be NULL)");
   CSTS_REQUIRE(yuv_args_ok(layout, matrix), "layout must be CSTS_YUV_NV12 or CSTS_YUV_I420, matrix CSTS_YUV_BT601 or CSTS_YUV_BT709");
   CSTS_REQUIRE(H >= 2 && W >= 2 && (H & 1) == 0 && (W & 1) == 0, "4:2:0 frames need even H, W >= 2");
+  const YuvSurf sf = {Hs, Ws, top, left};
+  CSTS_REQUIRE(yuv_surf_ok(H, W, sf), YUV_SURF_MSG);
   CSTS_REQUIRE(N >= 1 && H <= 65534 && W <= OV_MAX_W && S >= 1 && S <= 4096, "bad sizes (N >= 1, H <= 65534, W <= 8192, S <= 4096)");
   CSTS_REQUIRE(mh >= 1 && mw >= 1 && (int64_t)mh * mw <= CSTS_GAZE_DECODE_MAX_HW, "1 <= mh * mw <= CSTS_GAZE_DECODE_MAX_HW (the map is staged in LDS)");
   CSTS_REQUIRE(alpha >= 0.f && alpha <= 1.f, "0 <= alpha <= 1");
   CSTS_REQUIRE(radius >= 0, "radius >= 0");
-  const int64_t fb = yuv_frame_bytes(H, W);
+  const int64_t fb = yuv_frame_bytes(sf);
   CSTS_REQUIRE(N <= ((int64_t)1 << 62) / fb, "bad sizes (N H W 3 / 2 overflows)");
   const int64_t bytes = N * fb;
   CSTS_REQUIRE(out == frames_yuv || frames_yuv + bytes <= out || out + bytes <= frames_yuv,
@@ -704,16 +708,21 @@ extern "C" int csts_gaze_overlay_yuv(const uint8_t* frames_yuv, const float* res
   const int tables = 2 * OVY_BAND * (int)sizeof(OvRow) + 256 * 3 * (int)sizeof(float) + ((mh * mw + 3) & ~3) * (int)sizeof(float);
   const YuvCoef kf = yuv_coef(matrix, full_range);
   const RgbCoef kr = rgb_coef(matrix, full_range);
-  if ((W & 3) == 0 && (reinterpret_cast<uintptr_t>(frames_yuv) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0) {
+  if (out != frames_yuv && (Hs != H || Ws != W)) {
+    // the bytes around the window come over as they are, and the window is then drawn in place on the copy: the same bytes
+    CSTS_REQUIRE(hipMemcpyAsync(out, frames_yuv, (size_t)bytes, hipMemcpyDeviceToDevice, stream) == hipSuccess, "copying the surface");
+    frames_yuv = out;
+  }
+  if (((W | Ws | left) & 3) == 0 && (reinterpret_cast<uintptr_t>(frames_yuv) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0) {
     const int lds = tables + W * (int)sizeof(uint2);
     const bool nv12 = layout == CSTS_YUV_NV12;
     const void* fn = nv12 ? reinterpret_cast<const void*>(&gaze_overlay_yuv_vec_kernel<true>)
                           : reinterpret_cast<const void*>(&gaze_overlay_yuv_vec_kernel<false>);
     if (lds > 65536) CSTS_REQUIRE(csts_dyn_lds_optin(fn, lds), "LDS opt-in");
     if (nv12) hipLaunchKernelGGL(gaze_overlay_yuv_vec_kernel<true>, dim3((unsigned)(N * bands)), dim3(256), lds, stream, frames_yuv,
-                                 out, rescaled, centers, params, (int)bands, H, W, S, mh, mw, alpha, radius, kf, kr);
+                                 out, rescaled, centers, params, (int)bands, H, W, sf, S, mh, mw, alpha, radius, kf, kr);
     else hipLaunchKernelGGL(gaze_overlay_yuv_vec_kernel<false>, dim3((unsigned)(N * bands)), dim3(256), lds, stream, frames_yuv, out,
-                            rescaled, centers, params, (int)bands, H, W, S, mh, mw, alpha, radius, kf, kr);
+                            rescaled, centers, params, (int)bands, H, W, sf, S, mh, mw, alpha, radius, kf, kr);
     CSTS_LAUNCH_CHECK();
     return 0;
   }
@@ -723,10 +732,17 @@ extern "C" int csts_gaze_overlay_yuv(const uint8_t* frames_yuv, const float* res
   if (lds > 65536) CSTS_REQUIRE(csts_dyn_lds_optin(reinterpret_cast<const void*>(&gaze_overlay_yuv_kernel), lds), "LDS opt-in");
   const int64_t lo = (int64_t)(reinterpret_cast<uintptr_t>(frames_yuv) & 15), olo = (int64_t)(reinterpret_cast<uintptr_t>(out) & 15);
   hipLaunchKernelGGL(gaze_overlay_yuv_kernel, dim3((unsigned)(N * bands * xtiles)), dim3(256), lds, stream, frames_yuv - lo, lo,
-                     lo + bytes, out - olo, olo, rescaled, centers, params, (int)bands, (int)xtiles, twn, H, W, S, mh, mw, alpha, radius,
-                     layout, kf, kr);
+                     lo + bytes, out - olo, olo, rescaled, centers, params, (int)bands, (int)xtiles, twn, H, W, sf, S, mh, mw, alpha,
+                     radius, layout, kf, kr);
   CSTS_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int csts_gaze_overlay_yuv(const uint8_t* frames_yuv, const float* rescaled, const int* centers, const int* params,
+                                     uint8_t* out, int64_t N, int H, int W, int S, int mh, int mw, float alpha, int radius, int layout,
+                                     int matrix, int full_range, hipStream_t stream) {
+  return csts_gaze_overlay_yuv_win(frames_yuv, rescaled, centers, params, out, N, H, W, H, W, 0, 0, S, mh, mw, alpha, radius, layout,
+                                   matrix, full_range, stream);
 }
 
 extern "C" int csts_group_gaze_overlay(const int64_t* jobs, const int64_t* jobs_host, int njobs, const float* rescaled,

@@ -90,15 +90,15 @@ __global__ __launch_bounds__(256) void stream_ingest_kernel(const uint8_t* __res
   sample_rows(chunk, chunk_bytes, 0, frame, H, W, params, false, ring, slot, 0, 1, S, rowcap, mean, inv_std, lds);
 }
 
-// the same for a chunk of 4:2:0 frames; dynamic LDS sample_yuv_lds_bytes(W)
-__global__ __launch_bounds__(256) void stream_ingest_yuv_kernel(const uint8_t* __restrict__ chunk, int K, int H, int W,
+// the same for a chunk of 4:2:0 frames, the H x W pictures of the surfaces sf; dynamic LDS sample_yuv_lds_bytes(W)
+__global__ __launch_bounds__(256) void stream_ingest_yuv_kernel(const uint8_t* __restrict__ chunk, int K, int H, int W, YuvSurf sf,
                                                                 const int* __restrict__ pairs, const int* __restrict__ params,
                                                                 float* __restrict__ ring, int R, int S, int64_t chunk_bytes, int lcap,
                                                                 int ccap, int layout, YuvCoef k, float3 mean, float3 inv_std) {
   extern __shared__ __align__(16) uint8_t lds[];
   int frame, slot;
   if (!ingest_pair_ok(pairs, blockIdx.y, K, R, &frame, &slot)) return;
-  sample_rows_yuv(chunk, chunk_bytes, 0, frame, H, W, params, false, ring, slot, 0, 1, S, lcap, ccap, layout, k, mean, inv_std, lds);
+  sample_rows_yuv(chunk, chunk_bytes, 0, frame, H, W, sf, params, false, ring, slot, 0, 1, S, lcap, ccap, layout, k, mean, inv_std, lds);
 }
 
 // grid (blocks over S * S / V, 3 * T, B), 256 threads.  out[b][c][t] = ring[slots[b][t]][c]; a slot outside [0, R) gives NaN.
@@ -446,8 +446,8 @@ __global__ __launch_bounds__(256) void group_ingest_yuv_kernel(const int64_t* __
   const int H = (int)job[3], W = (int)job[4];
   int lcap, ccap;
   if (sample_yuv_lds_bytes(W, &lcap, &ccap) > lds_bytes || job[5] != lcap) return;
-  sample_rows_yuv(reinterpret_cast<const uint8_t*>(job[0]), job[1], 0, frame, H, W, params + 5 * j, false, arena, slot, 0, 1, S, lcap,
-                  ccap, layout, k, mean, inv_std, lds);
+  sample_rows_yuv(reinterpret_cast<const uint8_t*>(job[0]), job[1], 0, frame, H, W, yuv_tight(H, W), params + 5 * j, false, arena, slot,
+                  0, 1, S, lcap, ccap, layout, k, mean, inv_std, lds);
 }
 
 // the host copy of an ingest job table: every row as csts_stream_ingest asks it of its chunk -> the widest row's LDS bytes, or -1
@@ -532,21 +532,31 @@ extern "C" int csts_stream_ingest(const uint8_t* chunk_khwc, int K, int H, int W
   return 0;
 }
 
-extern "C" int csts_stream_ingest_yuv(const uint8_t* chunk_yuv, int K, int H, int W, const int* pairs, int npairs, const int* params,
-                                      float* ring, int R, int S, const float mean[3], const float std[3], int layout, int matrix,
-                                      int full_range, hipStream_t stream) {
+extern "C" int csts_stream_ingest_yuv_win(const uint8_t* chunk_yuv, int K, int H, int W, int Hs, int Ws, int top, int left,
+                                          const int* pairs, int npairs, const int* params, float* ring, int R, int S,
+                                          const float mean[3], const float std[3], int layout, int matrix, int full_range,
+                                          hipStream_t stream) {
   if (ingest_check(chunk_yuv, pairs, params, ring, mean, std, K, H, W, npairs, R, S)) return -1;
   CSTS_REQUIRE(yuv_args_ok(layout, matrix), "layout must be CSTS_YUV_NV12 or CSTS_YUV_I420, matrix CSTS_YUV_BT601 or CSTS_YUV_BT709");
   CSTS_REQUIRE(H >= 2 && W >= 2 && (H & 1) == 0 && (W & 1) == 0, "4:2:0 frames need even H, W >= 2");
+  const YuvSurf sf = {Hs, Ws, top, left};
+  CSTS_REQUIRE(yuv_surf_ok(H, W, sf), YUV_SURF_MSG);
   int lcap, ccap;
   const int lds = sample_yuv_lds_bytes(W, &lcap, &ccap);
   if (lds > 65536) CSTS_REQUIRE(csts_dyn_lds_optin(reinterpret_cast<const void*>(&stream_ingest_yuv_kernel), lds), "LDS opt-in");
   const float3 m = make_float3(mean[0], mean[1], mean[2]), is = make_float3(1.f / std[0], 1.f / std[1], 1.f / std[2]);
   hipLaunchKernelGGL(stream_ingest_yuv_kernel, dim3((unsigned)cdiv(S, SAMPLE_ROWS), npairs), dim3(256), lds, stream, chunk_yuv, K, H, W,
-                     pairs, params, ring, R, S, (int64_t)K * yuv_frame_bytes(H, W), lcap, ccap, layout, yuv_coef(matrix, full_range), m,
-                     is);
+                     sf, pairs, params, ring, R, S, (int64_t)K * yuv_frame_bytes(sf), lcap, ccap, layout, yuv_coef(matrix, full_range),
+                     m, is);
   CSTS_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int csts_stream_ingest_yuv(const uint8_t* chunk_yuv, int K, int H, int W, const int* pairs, int npairs, const int* params,
+                                      float* ring, int R, int S, const float mean[3], const float std[3], int layout, int matrix,
+                                      int full_range, hipStream_t stream) {
+  return csts_stream_ingest_yuv_win(chunk_yuv, K, H, W, H, W, 0, 0, pairs, npairs, params, ring, R, S, mean, std, layout, matrix,
+                                    full_range, stream);
 }
 
 extern "C" int csts_stream_gather(const float* ring, int R, const int* slots, float* out, int B, int T, int S, hipStream_t stream) {

@@ -15,6 +15,10 @@
 //
 // spatial / clip / batch_sample_yuv: the pixel pass of spatial.hip and batch.hip reading 4:2:0 pictures in place
 // (sample_rows_yuv, yuv_shared.h): bit for bit the RGB pass on the converted pictures, without the converted pictures.
+//
+// Decoder surfaces (the *_win entry points, include/csts_hip.h): the pictures are windows of padded surfaces.  Every kernel takes a
+// YuvSurf (yuv_shared.h) next to H, W and forms its addresses from it; a tight picture is the surface {H, W, 0, 0}, so the tight
+// entry points are the same launches of the same kernels.
 #include "yuv_shared.h"
 
 namespace {
@@ -25,26 +29,27 @@ constexpr int YUV_OUTCAP = 3 * YUV_TW + 32;      // the image of one output row 
 
 // grid (ceil(W / YUV_TW), H / 2, min(N, 65535)), 256 threads.  src is the recording's address rounded DOWN to 16 bytes; the
 // recording is the bytes [lo, hi) from there.  out likewise: the output's address rounded down, its first byte olo bytes from there
-// (the output may start at any byte as well: a chunk of a larger tensor).
+// (the output may start at any byte as well: a chunk of a larger tensor).  The pictures are the H x W windows of the surfaces sf;
+// the output is tight.
 __global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const uint8_t* __restrict__ src, int64_t lo, int64_t hi,
-                                                         uint8_t* __restrict__ out, int64_t olo, int64_t N, int H, int W, int layout,
-                                                         YuvCoef k) {
+                                                         uint8_t* __restrict__ out, int64_t olo, int64_t N, int H, int W, YuvSurf sf,
+                                                         int layout, YuvCoef k) {
   __shared__ __align__(16) uint8_t in[4][YUV_INCAP];
   __shared__ __align__(16) uint8_t img[2][YUV_OUTCAP];
   const int tid = threadIdx.x;
-  const int x0 = blockIdx.x * YUV_TW, tw = min(YUV_TW, W - x0), cy = blockIdx.y, hw = W >> 1;
+  const int x0 = blockIdx.x * YUV_TW, tw = min(YUV_TW, W - x0), cy = blockIdx.y;
   const bool nv12 = layout == CSTS_YUV_NV12;
   for (int64_t n = blockIdx.z; n < N; n += gridDim.z) {
-    const int64_t f0 = lo + n * yuv_frame_bytes(H, W), l0 = f0 + (int64_t)(2 * cy) * W + x0, c0 = f0 + (int64_t)H * W;
+    const int64_t f0 = lo + n * yuv_frame_bytes(sf), l0 = f0 + yuv_luma_row(sf, 2 * cy) + x0;
+    const int64_t q = f0 + yuv_chroma_row(sf, cy, nv12) + (nv12 ? x0 : x0 >> 1);
     int sh[4];
     sh[0] = yuv_stage(in[0], src, l0, l0 + tw, lo, hi, tid, 256);
-    sh[1] = yuv_stage(in[1], src, l0 + W, l0 + W + tw, lo, hi, tid, 256);
+    sh[1] = yuv_stage(in[1], src, l0 + sf.Ws, l0 + sf.Ws + tw, lo, hi, tid, 256);
     if (nv12) {
-      const int64_t q = c0 + (int64_t)cy * W + x0;
       sh[2] = yuv_stage(in[2], src, q, q + tw, lo, hi, tid, 256);
       sh[3] = sh[2] + 1;
     } else {
-      const int64_t q = c0 + (int64_t)cy * hw + (x0 >> 1), q1 = q + (int64_t)(H >> 1) * hw;
+      const int64_t q1 = q + yuv_vplane(sf);
       sh[2] = yuv_stage(in[2], src, q, q + (tw >> 1), lo, hi, tid, 256);
       sh[3] = yuv_stage(in[3], src, q1, q1 + (tw >> 1), lo, hi, tid, 256);
     }
@@ -166,16 +171,17 @@ __device__ __forceinline__ bool clip_row_ok_yuv(const int64_t* __restrict__ row,
 
 // grid (ceil(S / 4), T, B), 256 threads; dynamic LDS: sample_yuv_lds_bytes.
 // INDEXED: src is a video of nsrc frames and frames_idx [B][T] names the frame of each (b, t); otherwise frame (b, t) is b * T + t.
+// The pictures are the H x W windows of the surfaces sf.
 template <bool INDEXED>
 __global__ __launch_bounds__(256) void sample_yuv_kernel(const uint8_t* __restrict__ src, const int* __restrict__ frames_idx,
                                                          int64_t nsrc, const int* __restrict__ params, float* __restrict__ out, int T,
-                                                         int H, int W, int S, int64_t src_bytes, int lcap, int ccap, int layout,
+                                                         int H, int W, YuvSurf sf, int S, int64_t src_bytes, int lcap, int ccap, int layout,
                                                          YuvCoef k, float3 mean, float3 inv_std) {
   extern __shared__ __align__(16) uint8_t lds[];
   const int t = blockIdx.y, b = blockIdx.z;
   int64_t frame = (int64_t)b * T + t;
   if (INDEXED) frame = min(max((int64_t)frames_idx[frame], (int64_t)0), nsrc - 1);     // as temporal_sampling clamps
-  sample_rows_yuv(src, src_bytes, 0, frame, H, W, params + 5 * b, false, out, b, t, T, S, lcap, ccap, layout, k, mean, inv_std, lds);
+  sample_rows_yuv(src, src_bytes, 0, frame, H, W, sf, params + 5 * b, false, out, b, t, T, S, lcap, ccap, layout, k, mean, inv_std, lds);
 }
 
 __global__ __launch_bounds__(256) void batch_sample_yuv_kernel(const uint8_t* __restrict__ arena, int64_t arena_bytes,
@@ -189,22 +195,23 @@ __global__ __launch_bounds__(256) void batch_sample_yuv_kernel(const uint8_t* __
   const bool ok = clip_row_ok_yuv(row, arena_bytes, max_W);   // uniform over the workgroup (one clip)
   int64_t frame = 0;
   if (ok) frame = min(max((int64_t)frames_idx[(int64_t)b * T + t], (int64_t)0), row[1] - 1);     // as temporal_sampling clamps
-  sample_rows_yuv(arena, arena_bytes, ok ? row[0] : 0, frame, ok ? (int)row[2] : 2, ok ? (int)row[3] : 2, params + 5 * b, !ok, out, b,
-                  t, T, S, lcap, ccap, layout, k, mean, inv_std, lds);
+  const int H = ok ? (int)row[2] : 2, W = ok ? (int)row[3] : 2;
+  sample_rows_yuv(arena, arena_bytes, ok ? row[0] : 0, frame, H, W, yuv_tight(H, W), params + 5 * b, !ok, out, b, t, T, S, lcap, ccap,
+                  layout, k, mean, inv_std, lds);
 }
 
 template <bool INDEXED>
 int launch_sample_yuv(const uint8_t* src, const int* frames_idx, int64_t nsrc, const int* params, float* out, int B, int T, int H,
-                      int W, int S, const float mean[3], const float std[3], int layout, int matrix, int full_range,
+                      int W, const YuvSurf& sf, int S, const float mean[3], const float std[3], int layout, int matrix, int full_range,
                       hipStream_t stream) {
   int lcap, ccap;
   const int lds = sample_yuv_lds_bytes(W, &lcap, &ccap);
   if (lds > 65536)
     CSTS_REQUIRE(csts_dyn_lds_optin(reinterpret_cast<const void*>(&sample_yuv_kernel<INDEXED>), lds), "LDS opt-in");
   const float3 m = make_float3(mean[0], mean[1], mean[2]), is = make_float3(1.f / std[0], 1.f / std[1], 1.f / std[2]);
-  const int64_t src_bytes = nsrc * yuv_frame_bytes(H, W);
+  const int64_t src_bytes = nsrc * yuv_frame_bytes(sf);
   hipLaunchKernelGGL(sample_yuv_kernel<INDEXED>, dim3((unsigned)cdiv(S, SAMPLE_ROWS), T, B), dim3(256), lds, stream, src, frames_idx,
-                     nsrc, params, out, T, H, W, S, src_bytes, lcap, ccap, layout, yuv_coef(matrix, full_range), m, is);
+                     nsrc, params, out, T, H, W, sf, S, src_bytes, lcap, ccap, layout, yuv_coef(matrix, full_range), m, is);
   CSTS_LAUNCH_CHECK();
   return 0;
 }
@@ -215,40 +222,42 @@ int yuv_frame_check(int64_t N, int H, int W, int layout, int matrix) {
   return 0;
 }
 
-}  // namespace
-
-extern "C" int csts_yuv_to_rgb(const uint8_t* frames_yuv, uint8_t* out_nhwc, int64_t N, int H, int W, int layout, int matrix,
-                               int full_range, hipStream_t stream) {
+// csts_yuv_to_rgb(_win) once the window is known to lie in its surface
+int yuv_to_rgb_run(const uint8_t* frames_yuv, uint8_t* out_nhwc, int64_t N, int H, int W, const YuvSurf& sf, int layout, int matrix,
+                   int full_range, hipStream_t stream) {
   CSTS_REQUIRE(frames_yuv && out_nhwc, "bad args");
   if (yuv_frame_check(N, H, W, layout, matrix)) return -1;
-  CSTS_REQUIRE(H <= 131070 && N <= ((int64_t)1 << 62) / ((int64_t)H * W * 3), "bad sizes (H <= 131070)");
-  const int64_t lo = (int64_t)(reinterpret_cast<uintptr_t>(frames_yuv) & 15), bytes = N * yuv_frame_bytes(H, W);
+  CSTS_REQUIRE(H <= 131070 && N <= ((int64_t)1 << 62) / ((int64_t)sf.Hs * sf.Ws * 3), "bad sizes (H <= 131070)");
+  const int64_t lo = (int64_t)(reinterpret_cast<uintptr_t>(frames_yuv) & 15), bytes = N * yuv_frame_bytes(sf);
   const int64_t olo = (int64_t)(reinterpret_cast<uintptr_t>(out_nhwc) & 15);
   const uint8_t* a = frames_yuv, *o = out_nhwc;
   CSTS_REQUIRE(a + bytes <= o || o + N * H * W * 3 <= a, "the output must not overlap the input");
   hipLaunchKernelGGL(yuv_to_rgb_kernel, dim3((unsigned)cdiv(W, YUV_TW), H / 2, (unsigned)std::min<int64_t>(N, 65535)), dim3(256), 0,
-                     stream, frames_yuv - lo, lo, lo + bytes, out_nhwc - olo, olo, N, H, W, layout, yuv_coef(matrix, full_range));
+                     stream, frames_yuv - lo, lo, lo + bytes, out_nhwc - olo, olo, N, H, W, sf, layout,
+                     yuv_coef(matrix, full_range));
   CSTS_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int csts_yuv_to_rgb_host(const uint8_t* frames_yuv, uint8_t* out_nhwc, int64_t N, int H, int W, int layout, int matrix,
-                                    int full_range) {
+int yuv_to_rgb_host_run(const uint8_t* frames_yuv, uint8_t* out_nhwc, int64_t N, int H, int W, const YuvSurf& sf, int layout,
+                        int matrix, int full_range) {
   CSTS_REQUIRE(frames_yuv && out_nhwc, "bad args");
   if (yuv_frame_check(N, H, W, layout, matrix)) return -1;
   const YuvCoef k = yuv_coef(matrix, full_range);
-  const int64_t fb = yuv_frame_bytes(H, W), hw = W / 2;
+  const bool nv12 = layout == CSTS_YUV_NV12;
+  const int64_t fb = yuv_frame_bytes(sf), vplane = yuv_vplane(sf);
   for (int64_t n = 0; n < N; ++n) {
     const uint8_t* f = frames_yuv + n * fb;
-    const uint8_t* c = f + (int64_t)H * W;
     uint8_t* o = out_nhwc + n * H * W * 3;
     for (int y = 0; y < H; ++y) {
+      const uint8_t* l = f + yuv_luma_row(sf, y);
+      const uint8_t* c = f + yuv_chroma_row(sf, y >> 1, nv12);
       for (int x = 0; x < W; ++x) {
-        const int cx = x >> 1, cy = y >> 1;
-        const int U = layout == CSTS_YUV_NV12 ? c[(int64_t)cy * W + 2 * cx] : c[cy * hw + cx];
-        const int V = layout == CSTS_YUV_NV12 ? c[(int64_t)cy * W + 2 * cx + 1] : c[(H / 2) * hw + cy * hw + cx];
+        const int cx = x >> 1;
+        const int U = nv12 ? c[2 * cx] : c[cx];
+        const int V = nv12 ? c[2 * cx + 1] : c[vplane + cx];
         int R, G, B;
-        yuv_pixel(k, f[(int64_t)y * W + x], U, V, R, G, B);
+        yuv_pixel(k, l[x], U, V, R, G, B);
         uint8_t* d = o + ((int64_t)y * W + x) * 3;
         d[0] = (uint8_t)R;
         d[1] = (uint8_t)G;
@@ -257,6 +266,32 @@ extern "C" int csts_yuv_to_rgb_host(const uint8_t* frames_yuv, uint8_t* out_nhwc
     }
   }
   return 0;
+}
+
+}  // namespace
+
+extern "C" int csts_yuv_to_rgb(const uint8_t* frames_yuv, uint8_t* out_nhwc, int64_t N, int H, int W, int layout, int matrix,
+                               int full_range, hipStream_t stream) {
+  return yuv_to_rgb_run(frames_yuv, out_nhwc, N, H, W, yuv_tight(H, W), layout, matrix, full_range, stream);
+}
+
+extern "C" int csts_yuv_to_rgb_win(const uint8_t* frames_yuv, uint8_t* out_nhwc, int64_t N, int H, int W, int Hs, int Ws, int top,
+                                   int left, int layout, int matrix, int full_range, hipStream_t stream) {
+  const YuvSurf sf = {Hs, Ws, top, left};
+  CSTS_REQUIRE(yuv_surf_ok(H, W, sf), YUV_SURF_MSG);
+  return yuv_to_rgb_run(frames_yuv, out_nhwc, N, H, W, sf, layout, matrix, full_range, stream);
+}
+
+extern "C" int csts_yuv_to_rgb_host(const uint8_t* frames_yuv, uint8_t* out_nhwc, int64_t N, int H, int W, int layout, int matrix,
+                                    int full_range) {
+  return yuv_to_rgb_host_run(frames_yuv, out_nhwc, N, H, W, yuv_tight(H, W), layout, matrix, full_range);
+}
+
+extern "C" int csts_yuv_to_rgb_win_host(const uint8_t* frames_yuv, uint8_t* out_nhwc, int64_t N, int H, int W, int Hs, int Ws, int top,
+                                        int left, int layout, int matrix, int full_range) {
+  const YuvSurf sf = {Hs, Ws, top, left};
+  CSTS_REQUIRE(yuv_surf_ok(H, W, sf), YUV_SURF_MSG);
+  return yuv_to_rgb_host_run(frames_yuv, out_nhwc, N, H, W, sf, layout, matrix, full_range);
 }
 
 extern "C" int csts_rgb_to_yuv(const uint8_t* frames_nhwc, uint8_t* out_yuv, int64_t N, int H, int W, int layout, int matrix,
@@ -312,26 +347,44 @@ extern "C" int csts_rgb_to_yuv_host(const uint8_t* frames_nhwc, uint8_t* out_yuv
   return 0;
 }
 
+extern "C" int csts_spatial_sample_yuv_win(const uint8_t* frames_yuv, const int* params, float* out, int B, int T, int H, int W,
+                                           int Hs, int Ws, int top, int left, int S, const float mean[3], const float std[3],
+                                           int layout, int matrix, int full_range, hipStream_t stream) {
+  CSTS_REQUIRE(frames_yuv && params && out && mean && std, "bad args");
+  if (yuv_frame_check(1, H, W, layout, matrix)) return -1;
+  const YuvSurf sf = {Hs, Ws, top, left};
+  CSTS_REQUIRE(yuv_surf_ok(H, W, sf), YUV_SURF_MSG);
+  CSTS_REQUIRE(B > 0 && T > 0 && S > 0 && S <= 4096 && W <= 6000 && B <= 65535 && T <= 65535, "bad sizes (W <= 6000, S <= 4096)");
+  CSTS_REQUIRE(aligned16(frames_yuv) && aligned16(out), "frames and output must be 16-byte aligned");
+  return launch_sample_yuv<false>(frames_yuv, nullptr, (int64_t)B * T, params, out, B, T, H, W, sf, S, mean, std, layout, matrix,
+                                  full_range, stream);
+}
+
 extern "C" int csts_spatial_sample_yuv(const uint8_t* frames_yuv, const int* params, float* out, int B, int T, int H, int W, int S,
                                        const float mean[3], const float std[3], int layout, int matrix, int full_range,
                                        hipStream_t stream) {
-  CSTS_REQUIRE(frames_yuv && params && out && mean && std, "bad args");
-  if (yuv_frame_check(1, H, W, layout, matrix)) return -1;
-  CSTS_REQUIRE(B > 0 && T > 0 && S > 0 && S <= 4096 && W <= 6000 && B <= 65535 && T <= 65535, "bad sizes (W <= 6000, S <= 4096)");
-  CSTS_REQUIRE(aligned16(frames_yuv) && aligned16(out), "frames and output must be 16-byte aligned");
-  return launch_sample_yuv<false>(frames_yuv, nullptr, (int64_t)B * T, params, out, B, T, H, W, S, mean, std, layout, matrix,
-                                  full_range, stream);
+  return csts_spatial_sample_yuv_win(frames_yuv, params, out, B, T, H, W, H, W, 0, 0, S, mean, std, layout, matrix, full_range, stream);
+}
+
+extern "C" int csts_clip_sample_yuv_win(const uint8_t* video_yuv, int64_t N, const int* frames_idx, const int* params, float* out,
+                                        int B, int T, int H, int W, int Hs, int Ws, int top, int left, int S, const float mean[3],
+                                        const float std[3], int layout, int matrix, int full_range, hipStream_t stream) {
+  CSTS_REQUIRE(video_yuv && frames_idx && params && out && mean && std, "bad args");
+  if (yuv_frame_check(N, H, W, layout, matrix)) return -1;
+  const YuvSurf sf = {Hs, Ws, top, left};
+  CSTS_REQUIRE(yuv_surf_ok(H, W, sf), YUV_SURF_MSG);
+  CSTS_REQUIRE(B > 0 && T > 0 && T <= SPATIAL_MAX_T && S > 0 && S <= 4096 && W <= 6000 && B <= 65535,
+               "bad sizes (T <= 64, W <= 6000, S <= 4096)");
+  CSTS_REQUIRE(aligned16(video_yuv) && aligned16(out), "video and output must be 16-byte aligned");
+  return launch_sample_yuv<true>(video_yuv, frames_idx, N, params, out, B, T, H, W, sf, S, mean, std, layout, matrix, full_range,
+                                 stream);
 }
 
 extern "C" int csts_clip_sample_yuv(const uint8_t* video_yuv, int64_t N, const int* frames_idx, const int* params, float* out, int B,
                                     int T, int H, int W, int S, const float mean[3], const float std[3], int layout, int matrix,
                                     int full_range, hipStream_t stream) {
-  CSTS_REQUIRE(video_yuv && frames_idx && params && out && mean && std, "bad args");
-  if (yuv_frame_check(N, H, W, layout, matrix)) return -1;
-  CSTS_REQUIRE(B > 0 && T > 0 && T <= SPATIAL_MAX_T && S > 0 && S <= 4096 && W <= 6000 && B <= 65535,
-               "bad sizes (T <= 64, W <= 6000, S <= 4096)");
-  CSTS_REQUIRE(aligned16(video_yuv) && aligned16(out), "video and output must be 16-byte aligned");
-  return launch_sample_yuv<true>(video_yuv, frames_idx, N, params, out, B, T, H, W, S, mean, std, layout, matrix, full_range, stream);
+  return csts_clip_sample_yuv_win(video_yuv, N, frames_idx, params, out, B, T, H, W, H, W, 0, 0, S, mean, std, layout, matrix,
+                                  full_range, stream);
 }
 
 extern "C" int csts_batch_sample_yuv(const uint8_t* arena_u8, int64_t arena_bytes, const int64_t* clips, const int* frames_idx,

@@ -60,6 +60,36 @@ __host__ __device__ __forceinline__ void rgb_chroma(const RgbCoef& k, int SR, in
 // bytes of one frame; H, W even
 __host__ __device__ __forceinline__ int64_t yuv_frame_bytes(int64_t H, int64_t W) { return H * W / 2 * 3; }
 
+// Where the H x W picture lies in the tensor that holds it ("decoder surfaces", include/csts_hip.h): the tensor is a tight 4:2:0
+// picture of Hs x Ws (pitch Ws, chroma from byte Hs * Ws of a frame), the picture its window at row `top`, column `left`; all even.
+// Addresses (frame stride, row and plane offsets) come from here; clamps, scales and LDS sizes from H and W.  A tight picture is
+// {H, W, 0, 0}, and then every offset below is the tight one.
+struct YuvSurf {
+  int Hs, Ws, top, left;
+};
+
+__host__ __device__ __forceinline__ YuvSurf yuv_tight(int H, int W) { return YuvSurf{H, W, 0, 0}; }
+
+__host__ __device__ __forceinline__ int64_t yuv_frame_bytes(const YuvSurf& s) { return yuv_frame_bytes(s.Hs, s.Ws); }
+
+// byte of luma (y, 0) of the picture, counted from the frame's first byte
+__host__ __device__ __forceinline__ int64_t yuv_luma_row(const YuvSurf& s, int y) { return (int64_t)(s.top + y) * s.Ws + s.left; }
+
+// byte of chroma row cy, pair 0: the U byte; nv12: V follows it, i420: V lies yuv_vplane further on
+__host__ __device__ __forceinline__ int64_t yuv_chroma_row(const YuvSurf& s, int cy, bool nv12) {
+  const int64_t r = (s.top >> 1) + cy, c0 = (int64_t)s.Hs * s.Ws;
+  return nv12 ? c0 + r * s.Ws + s.left : c0 + r * (s.Ws >> 1) + (s.left >> 1);
+}
+
+__host__ __device__ __forceinline__ int64_t yuv_vplane(const YuvSurf& s) { return (int64_t)(s.Hs >> 1) * (s.Ws >> 1); }
+
+// the window of a surface as include/csts_hip.h defines it
+inline bool yuv_surf_ok(int H, int W, const YuvSurf& s) {
+  return ((s.Hs | s.Ws | s.top | s.left | H | W) & 1) == 0 && H >= 2 && W >= 2 && s.top >= 0 && s.left >= 0 && s.Hs >= H &&
+         s.Ws >= W && s.Ws <= CSTS_YUV_MAX_WS && s.top <= s.Hs - H && s.left <= s.Ws - W;
+}
+#define YUV_SURF_MSG "bad window (top, left, H, W even, H, W >= 2, inside the Hs x Ws surface; Ws <= CSTS_YUV_MAX_WS = 32768)"
+
 // Stage the bytes [beg, end) of src into dst as the 16-byte chunks of src that cover them (src is 16-byte aligned, offsets count
 // from it; dst is 16-byte aligned LDS of at least end - beg + 30 bytes rounded up to 16); returns where byte `beg` lies in dst.
 // Only bytes inside [lo, hi) are read (zeros stand in for the others).  Called by `nthr` threads numbered `tid`.
@@ -100,11 +130,12 @@ __host__ __device__ inline int sample_yuv_lds_bytes(int W, int* lcap, int* ccap)
   return SAMPLE_ROWS * (2 * *lcap + 4 * *ccap);
 }
 
-// sample_rows for a recording of 4:2:0 frames (H * 3 / 2 rows of W bytes; H, W even -- the caller passes bad otherwise): the same
-// geometry, the same staging and, after the four taps of a pixel are converted to integer R, G, B, the same fp32 expressions in the
-// same order, so the output equals sample_rows on the converted recording bit for bit.  lds: sample_yuv_lds_bytes.
+// sample_rows for a recording of 4:2:0 frames (the H x W pictures of the surfaces sf; H, W even -- the caller passes bad otherwise,
+// and a window that lies inside its surface): the same geometry, the same staging and, after the four taps of a pixel are converted
+// to integer R, G, B, the same fp32 expressions in the same order, so the output equals sample_rows on the converted recording bit
+// for bit.  lds: sample_yuv_lds_bytes.
 __device__ __forceinline__ void sample_rows_yuv(const uint8_t* __restrict__ src, int64_t src_bytes, int64_t base, int64_t frame,
-                                                int H, int W, const int* __restrict__ par, bool bad, float* __restrict__ out, int b,
+                                                int H, int W, const YuvSurf& sf, const int* __restrict__ par, bool bad, float* __restrict__ out, int b,
                                                 int t, int T, int S, int lcap, int ccap, int layout, const YuvCoef& k, float3 mean,
                                                 float3 inv_std, uint8_t* lds) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -126,22 +157,21 @@ __device__ __forceinline__ void sample_rows_yuv(const uint8_t* __restrict__ src,
   const float ly = fy - (float)ya;
   const int xlo = min((int)fmaxf(((float)x0 + 0.5f) * sx - 0.5f, 0.f), W - 1);
   const int xhi = min((int)fmaxf(((float)(x0 + S - 1) + 0.5f) * sx - 0.5f, 0.f) + 1, W - 1);
-  const int clo = xlo >> 1, chi = xhi >> 1, hw = W >> 1;       // chroma columns the span reads
+  const int clo = xlo >> 1, chi = xhi >> 1;                    // chroma columns the span reads
   uint8_t* rows = lds + wv * (2 * lcap + 4 * ccap);
   const bool nv12 = layout == CSTS_YUV_NV12;
   // LDS byte of luma x of row r: yo[r] + x; of the chroma pair cx: nv12 uo[r] + 2 cx (U), + 1 (V); i420 uo[r] + cx, vo[r] + cx
   int yo[2], uo[2], vo[2];
-  const int64_t f0 = base + frame * yuv_frame_bytes(H, W), c0 = f0 + (int64_t)H * W;
+  const int64_t f0 = base + frame * yuv_frame_bytes(sf);
   for (int r = 0; r < 2; ++r) {
     const int y = r ? yb : ya;
-    const int64_t l0 = f0 + (int64_t)y * W;
+    const int64_t l0 = f0 + yuv_luma_row(sf, y), q0 = f0 + yuv_chroma_row(sf, y >> 1, nv12);
     if (row_ok) yo[r] = r * lcap + yuv_stage(rows + r * lcap, src, l0 + xlo, l0 + xhi + 1, 0, src_bytes, lane, 64) - xlo;
     if (nv12) {
-      const int64_t q0 = c0 + (int64_t)(y >> 1) * W;
       uint8_t* d = rows + 2 * lcap + r * lcap;
       if (row_ok) uo[r] = (int)(d - rows) + yuv_stage(d, src, q0 + 2 * clo, q0 + 2 * chi + 2, 0, src_bytes, lane, 64) - 2 * clo;
     } else {
-      const int64_t q0 = c0 + (int64_t)(y >> 1) * hw, q1 = q0 + (int64_t)(H >> 1) * hw;
+      const int64_t q1 = q0 + yuv_vplane(sf);
       uint8_t* du = rows + 2 * lcap + r * ccap;
       uint8_t* dv = du + 2 * ccap;
       if (row_ok) {

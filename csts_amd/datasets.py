@@ -250,6 +250,9 @@ class ClipStore:
                 if missing:
                     raise ValueError(f"{path} lacks {missing}: a clip holds frames_u8 (or frames_yuv with pixel_format), wav and "
                                      "optionally fps")
+                if "yuv_window" in z.files:
+                    raise ValueError(f"{path} holds a yuv_window entry: the clip store packs tight 4:2:0 pictures only, repack the "
+                                     "surfaces first (inputs.yuv_window)")
                 frames, H, W, fmt = clip_pictures(z, path)
                 wav = z["wav"]
                 rate = np.asarray(z["sample_rate"]).reshape(-1) if "sample_rate" in z.files else None

@@ -353,20 +353,26 @@ class GraphedEvalStep:
         return self.out
 
 
-def _picture_hw(frames, lead, pixel_format, matrix, full_range):
+def _picture_hw(frames, lead, pixel_format, matrix, full_range, window=None):
     """H, W and the format keywords of a picture argument with `lead` leading dimensions: packed RGB uint8 (..., H, W, 3) -> (H,
     W, {}), or with pixel_format "nv12" | "i420" 4:2:0 uint8 (..., H * 3 / 2, W) -> (H, W, the three keywords to pass on).
-    ValueError for an unknown format or matrix, a shape of the other kind, odd H or W."""
+    window (top, left, H, W): the frames are 4:2:0 surfaces and the pictures their windows (inputs.check_window): H, W are the
+    window's and the keywords carry it.  ValueError for an unknown format or matrix, a shape of the other kind, odd H or W, a
+    bad window or a window of packed RGB."""
     from . import inputs
     names = "(B, T" if lead == 2 else "(N"
     if inputs.check_pixel_format(pixel_format, matrix, full_range)[0] == 0:
+        inputs.check_window(frames.shape, pixel_format, window)
         if frames.dtype != torch.uint8 or frames.dim() != lead + 3 or frames.shape[-1] != 3:
             raise ValueError(f"frames must be uint8 {names}, H, W, 3), got {tuple(frames.shape)} {frames.dtype}")
         return int(frames.shape[-3]), int(frames.shape[-2]), {}
     if frames.dtype != torch.uint8 or frames.dim() != lead + 2:
         raise ValueError(f"{pixel_format} frames must be uint8 {names}, H * 3 / 2, W), got {tuple(frames.shape)} {frames.dtype}")
-    H, W = inputs._yuv_hw(frames.shape, pixel_format)
-    return H, W, {"pixel_format": pixel_format, "matrix": matrix, "full_range": bool(full_range)}
+    H, W = inputs.window_size(frames.shape, pixel_format, window)
+    fmt = {"pixel_format": pixel_format, "matrix": matrix, "full_range": bool(full_range)}
+    if window is not None:
+        fmt["window"] = tuple(int(v) for v in window)
+    return H, W, fmt
 
 
 def _render_out(frames, out, H, W, fmt):
@@ -468,7 +474,7 @@ class GazePredictor:
 
     @torch.no_grad()
     def predict(self, frames_u8, wav, frames_idx, frame_length, labels=None, attention=False, sample_rate=None, *,
-                pixel_format="rgb24", matrix="bt601", full_range=False):
+                pixel_format="rgb24", matrix="bt601", full_range=False, window=None):
         """frames_u8 uint8 (B, T, H, W, 3), wav fp32 (B, n) at 24 kHz, frames_idx (B, T) = the sampled frames' positions on the
         clip's time axis of `frame_length` frames -> {"points": (B, T, 2) (x, y) in [0, 1), "peak": (B, T),
         "heatmaps": (B, T, S/4, S/4), "rescaled": same shape} on the device, S = DATA.TEST_CROP_SIZE.
@@ -479,14 +485,16 @@ class GazePredictor:
         sample_rate: None (wav is at 24 kHz: today's path, no extra launch), or the rate wav was recorded at: wav, floating or
         int16, (B, n) or (B, C, n), is first brought to 24 kHz mono on the device (inputs.resample_audio).
         pixel_format "nv12" | "i420" (with matrix "bt601" | "bt709", full_range): frames_u8 is uint8 (B, T, H * 3 / 2, W), 4:2:0
-        pictures sampled in place (inputs.spatial_sample); the result is that of the converted RGB frames, bit for bit."""
+        pictures sampled in place (inputs.spatial_sample); the result is that of the converted RGB frames, bit for bit.
+        window (top, left, H, W), 4:2:0 only: the frames are decoder surfaces (B, T, Hs * 3 / 2, Ws) and the pictures their windows
+        (inputs.check_window), read in place: the result is that of inputs.yuv_window of the frames, bit for bit."""
         if sample_rate is not None:
             sample_rate = _check_rate(sample_rate)
         for t in (frames_u8, wav, frames_idx) + ((labels,) if labels is not None else ()):
             if not torch.is_tensor(t) or not t.is_cuda:
                 raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
         from . import inputs
-        H, W, fmt = _picture_hw(frames_u8, 2, pixel_format, matrix, full_range)
+        H, W, fmt = _picture_hw(frames_u8, 2, pixel_format, matrix, full_range, window)
         B, T = frames_u8.shape[:2]
         if sample_rate is not None:
             if wav.dim() not in (2, 3) or wav.shape[0] != B:
@@ -554,12 +562,14 @@ class GazePredictor:
 
     def stream(self, fps=None, stride=None, segment=None, batch=1, max_chunk=32, pixel_format="rgb24", matrix="bt601",
                full_range=False, sample_rate=None, input_rate=None, live=None, max_gap=None, overlay=False, alpha=0.4, radius=5,
-               overlay_format=None):
+               overlay_format=None, window=None):
         """A live stream on this predictor (csts_amd.stream.GazeStream): push(frames, wav) takes frames and 24 kHz audio in whatever
         pieces they arrive and returns the windows each piece completes; close() ends it.  The windows are plan_stream's (fps an
         int or a Fraction, stride in frames); `batch` windows run per predict_batch call; `max_chunk` sizes the two device rings,
         which do not grow with the stream (GazeStream states the capacities).  pixel_format "nv12" | "i420": the pushed frames
-        are 4:2:0 pictures.  input_rate=R: the audio is pushed at R Hz, (m,) or (C, m), floating or int16, and resampled to 24 kHz
+        are 4:2:0 pictures; window (top, left, H, W): they are decoder surfaces and the pictures their windows
+        (inputs.check_window), H x W the stream's source size; an RGB overlay shows the window, a 4:2:0 one is the surface.
+        input_rate=R: the audio is pushed at R Hz, (m,) or (C, m), floating or int16, and resampled to 24 kHz
         mono on the device with the filter state carried from push to push (inputs.StreamResampler): the track of
         inputs.resample_audio on the whole waveform, bit for bit.  sample_rate: None or 24000, the audio as it is; another rate
         there is a ValueError (it keeps no filter state), and so are both keywords together.
@@ -571,24 +581,26 @@ class GazePredictor:
         return GazeStream(self, fps=fps, stride=stride, segment=segment, batch=batch, max_chunk=max_chunk,
                           pixel_format=pixel_format, matrix=matrix, full_range=full_range, sample_rate=sample_rate,
                           input_rate=input_rate, live=live, max_gap=max_gap, overlay=overlay, alpha=alpha, radius=radius,
-                          overlay_format=overlay_format)
+                          overlay_format=overlay_format, window=window)
 
     def stream_group(self, streams, fps=None, stride=None, segment=None, batch=4, max_chunk=32, pixel_format="rgb24",
-                     matrix="bt601", full_range=False, input_rate=None):
+                     matrix="bt601", full_range=False, input_rate=None, window=None):
         """`streams` live streams on this predictor, served together (csts_amd.stream.GazeStreamGroup): push({slot: (frames,
         wav)}) is one tick -- what all the slots pushed goes into one arena of rings with one launch per stage, and the windows
         that become ready in the same tick are predicted together, `batch` per predict_batch call, whichever slot they belong
         to; close(slot) / close() end a slot / all of them, reset(slot) reopens one.  The keywords are stream()'s and hold for
         every slot; each slot has its own source size.  live=, overlay= and attention are not part of a group (the live
-        track of a group is live_group()).  GazeStreamGroup states the tick rule and the contract; group_schedule is the rule
-        on the host."""
+        track of a group is live_group()).  A group takes tight pictures only: a window is a ValueError.  GazeStreamGroup
+        states the tick rule and the contract; group_schedule is the rule on the host."""
         from .stream import GazeStreamGroup
+        from .inputs import no_window
+        no_window(window, "GazeStreamGroup")
         return GazeStreamGroup(self, streams, fps=fps, stride=stride, segment=segment, batch=batch, max_chunk=max_chunk,
                                pixel_format=pixel_format, matrix=matrix, full_range=full_range, input_rate=input_rate)
 
     def live_group(self, streams, live, fps=None, stride=None, segment=None, batch=4, max_chunk=32, pixel_format="rgb24",
                    matrix="bt601", full_range=False, input_rate=None, max_gap=None, overlay=False, alpha=0.4, radius=5,
-                   overlay_format=None):
+                   overlay_format=None, window=None):
         """stream_group() with the live track of stream(live=...) on every slot (csts_amd.stream.GazeLiveGroup, forecast plans):
         push_live({slot: (frames, wav)}) is one tick and returns (windows, {slot: the push_live dict of that slot's frames}) --
         every pushed frame of every slot answered with its row of a gaze track computed from the windows of its own slot that
@@ -597,8 +609,10 @@ class GazePredictor:
         (ops.group_live_add, ops.group_live_rows), whatever the number of slots; their points on the source frames and their
         overlays are one launch each as well, whatever the sizes (ops.group_points_source, ops.group_gaze_overlay).  The other
         keywords are stream_group()'s and stream()'s.  GazeLiveGroup states the order of work and the contract;
-        group_live_schedule is the rule on the host."""
+        group_live_schedule is the rule on the host.  A window is a ValueError, as in stream_group()."""
         from .stream import GazeLiveGroup
+        from .inputs import no_window
+        no_window(window, "GazeLiveGroup")
         return GazeLiveGroup(self, streams, live, fps=fps, stride=stride, segment=segment, batch=batch, max_chunk=max_chunk,
                              pixel_format=pixel_format, matrix=matrix, full_range=full_range, input_rate=input_rate,
                              max_gap=max_gap, overlay=overlay, alpha=alpha, radius=radius, overlay_format=overlay_format)
@@ -616,7 +630,7 @@ class GazePredictor:
 
     @torch.no_grad()
     def render_track(self, frames_u8, track, alpha=0.4, radius=5, out=None, chunk=None, *, pixel_format="rgb24", matrix="bt601",
-                     full_range=False, out_format=None):
+                     full_range=False, out_format=None, window=None):
         """The track of predict_video drawn onto its recording: frames_u8 uint8 (N, H, W, 3) on the device and the dict
         predict_video returned (it must hold "rescaled" and "points") -> uint8 (N, H, W, 3): the heat map of every predicted
         frame blended over the crop the model saw and a disc at the gaze point (ops.gaze_overlay, csts_gaze_overlay); frames no
@@ -627,12 +641,14 @@ class GazePredictor:
         out_format: None / "rgb24" (the RGB result above), or the frames' own 4:2:0 layout ("nv12" | "i420", equal to
         pixel_format; matrix and range are the input's): the overlay is drawn in that format (ops.gaze_overlay_yuv), the result
         is uint8 (N, H * 3 / 2, W) -- where(drawn, rgb_to_yuv(the RGB result), frames), see include/csts_hip.h -- and
-        out=frames_u8 renders in place."""
+        out=frames_u8 renders in place.  window (top, left, H, W), 4:2:0 only: the frames are decoder surfaces and the pictures
+        their windows (the window predict_video was given): the RGB result is (N, H, W, 3) of the window; the 4:2:0 result has the
+        surfaces' shape, drawn inside the window and byte for byte the input around it."""
         if not torch.is_tensor(frames_u8) or not frames_u8.is_cuda:
             raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
         if "rescaled" not in track or "points" not in track:
             raise ValueError("render_track needs the track's \"rescaled\" and \"points\": call predict_video with return_heatmaps=True")
-        H, W, fmt = _picture_hw(frames_u8, 1, pixel_format, matrix, full_range)
+        H, W, fmt = _picture_hw(frames_u8, 1, pixel_format, matrix, full_range, window)
         N = frames_u8.shape[0]
         yuv_out = _overlay_yuv(out_format, fmt)
         if yuv_out:
@@ -665,7 +681,7 @@ class GazePredictor:
 
     @torch.no_grad()
     def render_attention(self, frames_u8, result, head=None, alpha=0.4, radius=5, points=None, out=None, *, pixel_format="rgb24",
-                         matrix="bt601", full_range=False, out_format=None):
+                         matrix="bt601", full_range=False, out_format=None, window=None):
         """The fusion attention maps of predict(attention=True) drawn onto the clip: frames_u8 uint8 (B, T, H, W, 3) on the device
         (the frames that were predicted) and the result dict (it must hold "attention_maps") -> uint8 (B, T, H, W, 3): the map
         of `head` (None: the head mean) of every input frame blended over the crop the model saw -- one ops.gaze_overlay call
@@ -674,12 +690,12 @@ class GazePredictor:
         back untouched).  out=frames_u8 renders in place.  pixel_format "nv12" | "i420": frames_u8 is uint8 (B, T, H * 3 / 2, W); the
         frames are converted into `out` (inputs.yuv_to_rgb) and drawn over there: out must not alias the input.  out_format: as
         render_track takes it; in the frames' own 4:2:0 layout the result is uint8 (B, T, H * 3 / 2, W) and out=frames_u8 is
-        allowed."""
+        allowed.  window: as render_track takes it (the window predict() was given)."""
         if not torch.is_tensor(frames_u8) or not frames_u8.is_cuda:
             raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
         if "attention_maps" not in result:
             raise ValueError("render_attention needs the result's \"attention_maps\": call predict with attention=True")
-        H, W, fmt = _picture_hw(frames_u8, 2, pixel_format, matrix, full_range)
+        H, W, fmt = _picture_hw(frames_u8, 2, pixel_format, matrix, full_range, window)
         if not frames_u8.is_contiguous():
             raise ValueError("frames must be contiguous")
         B, T = frames_u8.shape[:2]
@@ -710,8 +726,9 @@ class GazePredictor:
                 out = torch.empty_like(frames_u8)
             picture = maps[:, g].reshape(B * T, maps.shape[3], maps.shape[4])
             if yuv_out:
-                ops.gaze_overlay_yuv(frames_u8.view(B * T, H * 3 // 2, W), picture, params, S, centers=centers, alpha=alpha,
-                                     radius=radius, out=out.view(B * T, H * 3 // 2, W), **fmt)
+                surface = (B * T,) + tuple(frames_u8.shape[2:])
+                ops.gaze_overlay_yuv(frames_u8.view(surface), picture, params, S, centers=centers, alpha=alpha, radius=radius,
+                                     out=out.view(surface), **fmt)
                 return out
             if fmt:
                 from . import inputs
@@ -724,7 +741,7 @@ class GazePredictor:
 
     @torch.no_grad()
     def render_attention_track(self, frames_u8, track, head=None, alpha=0.4, radius=5, points=None, out=None, chunk=None, *,
-                               pixel_format="rgb24", matrix="bt601", full_range=False, out_format=None):
+                               pixel_format="rgb24", matrix="bt601", full_range=False, out_format=None, window=None):
         """The attention track of predict_video(attention_track=True) drawn onto its recording: frames_u8 uint8 (N, H, W, 3) on
         the device and the track (it must hold "attention_maps" and "attention_count") -> uint8 (N, H, W, 3): on every frame a
         pair landed on, or the fill reached ("attention_filled"), the map of `head` (None: the head mean) blended over the crop
@@ -734,13 +751,13 @@ class GazePredictor:
         (default: all).  out=frames_u8 renders in place.  pixel_format "nv12" | "i420": frames_u8 is the 4:2:0 recording uint8
         (N, H * 3 / 2, W); each chunk is converted into `out` (inputs.yuv_to_rgb) and drawn over there: out must not alias it.
         out_format: as render_track takes it; in the frames' own 4:2:0 layout the result is uint8 (N, H * 3 / 2, W) and
-        out=frames_u8 is allowed."""
+        out=frames_u8 is allowed.  window: as render_track takes it."""
         if not torch.is_tensor(frames_u8) or not frames_u8.is_cuda:
             raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
         if "attention_maps" not in track or "attention_count" not in track:
             raise ValueError("render_attention_track needs the track's \"attention_maps\" and \"attention_count\": call predict_video "
                              "with attention_track=True")
-        H, W, fmt = _picture_hw(frames_u8, 1, pixel_format, matrix, full_range)
+        H, W, fmt = _picture_hw(frames_u8, 1, pixel_format, matrix, full_range, window)
         N = frames_u8.shape[0]
         yuv_out = _overlay_yuv(out_format, fmt)
         if yuv_out:
@@ -791,7 +808,7 @@ class GazePredictor:
     @torch.no_grad()
     def predict_video(self, frames_u8, wav, fps=None, stride=None, batch=None, return_heatmaps=True, overlay=False, fill=None,
                       max_gap=None, attention_track=False, sample_rate=None, *, pixel_format="rgb24", matrix="bt601",
-                      full_range=False, overlay_format=None):
+                      full_range=False, overlay_format=None, window=None):
         """A whole recording in, one gaze track out: frames_u8 uint8 (N, H, W, 3) and wav fp32 (n,) at 24 kHz, both resident on
         the device -> {"points": (N, 2), "peak": (N,), "count": (N,) int32 = windows that predicted the frame, "heatmaps" and
         "rescaled": (N, S/4, S/4) (left out with return_heatmaps=False), "windows": their number}, on the device.
@@ -832,7 +849,13 @@ class GazePredictor:
         (N, H * 3 / 2, W), half the bytes of RGB; the windows are sampled straight out of it (inputs.clip_sample in that format,
         no RGB copy of the recording) and every entry equals, bit for bit, that of the converted recording.  "overlay" is
         RGB uint8 (N, H, W, 3) unless overlay_format names the recording's own layout ("nv12" | "i420"; needs overlay=True):
-        then it is drawn in that format, uint8 (N, H * 3 / 2, W) (render_track(out_format=...))."""
+        then it is drawn in that format, uint8 (N, H * 3 / 2, W) (render_track(out_format=...)).
+
+        window (top, left, H, W), 4:2:0 only: frames_u8 holds decoder surfaces (N, Hs * 3 / 2, Ws) -- rows of a pitch Ws, a coded
+        height Hs, the chroma behind Hs * Ws bytes -- and the recording is their windows (inputs.check_window), read in place:
+        every entry equals that of inputs.yuv_window(frames_u8, ...), bit for bit, and "points_source" is normalised on the
+        window's H x W.  An RGB "overlay" is (N, H, W, 3) of the window; a 4:2:0 one has the surfaces' shape and equals the input
+        outside the window."""
         if fill not in (None, "hold", "linear"):
             raise ValueError(f"fill must be None, \"hold\" or \"linear\", got {fill!r}")
         if fill is None and max_gap is not None:
@@ -841,7 +864,7 @@ class GazePredictor:
             if not torch.is_tensor(t) or not t.is_cuda:
                 raise L.CstsError("GazePredictor runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
         from . import inputs
-        H, W, fmt = _picture_hw(frames_u8, 1, pixel_format, matrix, full_range)
+        H, W, fmt = _picture_hw(frames_u8, 1, pixel_format, matrix, full_range, window)
         if overlay_format is not None and not overlay:
             raise ValueError("overlay_format belongs to the overlay: pass overlay=True")
         _overlay_yuv(overlay_format, fmt, "overlay_format")

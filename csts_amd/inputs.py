@@ -380,18 +380,106 @@ def _yuv_hw(shape, pixel_format, what="frames"):
     return H, W
 
 
+YUV_MAX_WS = 32768      # CSTS_YUV_MAX_WS of include/csts_hip.h: the widest surface row the *_win entry points take
+
+
+def check_window(shape, pixel_format, window, what="frames"):
+    """The window (top, left, H, W) of 4:2:0 surfaces of `shape` (..., Hs * 3 / 2, Ws), checked: -> (top, left, H, W) as ints,
+    or None for window None (the whole surface).  The picture is the H x W pixels whose first is luma (top, left) of the surface
+    ("Decoder surfaces", include/csts_hip.h).  ValueError, naming the value: a window given with rgb24, not four integers, an odd
+    or negative value, H or W below 2, top + H > Hs, left + W > Ws, Ws > YUV_MAX_WS."""
+    if window is None:
+        return None
+    top, left, H, W = window_values(pixel_format, window)
+    Hs, Ws = _yuv_hw(shape, pixel_format, what)
+    if top + H > Hs:
+        raise ValueError(f"window top {top} + H {H} = {top + H} exceeds the surface height {Hs}")
+    if left + W > Ws:
+        raise ValueError(f"window left {left} + W {W} = {left + W} exceeds the surface width {Ws}")
+    if Ws > YUV_MAX_WS:
+        raise ValueError(f"a windowed surface is at most {YUV_MAX_WS} bytes wide, got Ws {Ws}")
+    return top, left, H, W
+
+
+def window_values(pixel_format, window):
+    """The rules of check_window that need no surface: -> (top, left, H, W) as ints."""
+    if check_pixel_format(pixel_format)[0] == 0:
+        raise ValueError(f"window {window!r} is given with pixel_format 'rgb24': a window selects the picture inside a 4:2:0 "
+                         "surface ('nv12' | 'i420')")
+    try:
+        vals = [int(v) for v in window]
+        exact = all(v == w for v, w in zip(vals, window))
+    except (TypeError, ValueError):
+        vals, exact = [], False
+    if len(vals) != 4 or not exact:
+        raise ValueError(f"window must be four integers (top, left, H, W), got {window!r}")
+    top, left, H, W = vals
+    for name, v in (("top", top), ("left", left), ("H", H), ("W", W)):
+        if v < 0:
+            raise ValueError(f"window {name} {v} is negative (window {tuple(vals)})")
+        if v % 2:
+            raise ValueError(f"window {name} {v} is odd: 4:2:0 windows start and end on a chroma sample (window {tuple(vals)})")
+    if H < 2 or W < 2:
+        raise ValueError(f"window H {H}, W {W} must be at least 2")
+    return top, left, H, W
+
+
+def _yuv_geom(shape, pixel_format, window, what="frames"):
+    """H, W of the picture and the surface arguments of a *_win entry point: (H, W, None) for a tight call -- no window, or the
+    window that is the whole surface: today's call -- else (H, W, (Hs, Ws, top, left))."""
+    Hs, Ws = _yuv_hw(shape, pixel_format, what)
+    win = check_window(shape, pixel_format, window, what)
+    if win is None or win == (0, 0, Hs, Ws):
+        return Hs, Ws, None
+    return win[2], win[3], (Hs, Ws, win[0], win[1])
+
+
+def window_size(shape, pixel_format, window, what="frames"):
+    """H, W of the picture a call with `window` sees in 4:2:0 surfaces of `shape`."""
+    return _yuv_geom(shape, pixel_format, window, what)[:2]
+
+
+def no_window(window, who):
+    """The refusal of the callers that take tight pictures only."""
+    if window is not None:
+        raise ValueError(f"{who} takes tight 4:2:0 pictures only, no window: repack the surface first (inputs.yuv_window)")
+
+
+def yuv_window(frames, pixel_format: str, window):
+    """The repack: the tight 4:2:0 pictures (..., H * 3 / 2, W) of the window (top, left, H, W) of surfaces (..., Hs * 3 / 2, Ws),
+    by plain slicing (a torch tensor or a numpy array in, the same kind out, a new contiguous one).  The oracle of every
+    window= keyword: f(surface, ..., window=w) == f(yuv_window(surface, pixel_format, w), ...), bit for bit.  window None
+    returns the surfaces themselves."""
+    win = check_window(frames.shape, pixel_format, window)
+    if win is None:
+        return frames
+    top, left, H, W = win
+    Hs, Ws = _yuv_hw(frames.shape, pixel_format)
+    lead = tuple(frames.shape[:-2])
+    cat = torch.cat if torch.is_tensor(frames) else __import__("numpy").concatenate
+    luma = frames[..., top:top + H, left:left + W]
+    if pixel_format == "nv12":
+        chroma = frames[..., Hs + top // 2:Hs + (top + H) // 2, left:left + W]
+        return cat([luma, chroma], -2)
+    planes = frames[..., Hs:, :].reshape(lead + (2, Hs // 2, Ws // 2))
+    planes = planes[..., top // 2:(top + H) // 2, left // 2:(left + W) // 2]
+    return cat([luma, planes.reshape(lead + (H // 2, W))], -2)
+
+
 def yuv_to_rgb(frames_yuv: torch.Tensor, pixel_format: str, matrix: str = "bt601", full_range: bool = False,
-               out: torch.Tensor = None) -> torch.Tensor:
+               out: torch.Tensor = None, *, window=None) -> torch.Tensor:
     """4:2:0 pictures uint8 (..., H * 3 / 2, W) in `pixel_format` ("nv12" | "i420") -> packed RGB uint8 (..., H, W, 3) by the
     integer rule of include/csts_hip.h (nearest chroma, `matrix` "bt601" | "bt709", limited range unless full_range), one
     streaming launch (csts_yuv_to_rgb).  The input may start at any byte.  out: a contiguous uint8 (..., H, W, 3) GPU tensor to
-    write into, at any byte as well (a slice of a larger tensor); it must not share memory with the input."""
+    write into, at any byte as well (a slice of a larger tensor); it must not share memory with the input.  window (top, left,
+    H, W): the frames are surfaces (..., Hs * 3 / 2, Ws) and the pictures their windows (check_window), read in place
+    (csts_yuv_to_rgb_win); the result is the (..., H, W, 3) of the window."""
     layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
     if layout == 0:
         raise ValueError("yuv_to_rgb converts 'nv12' or 'i420' pictures; rgb24 needs no conversion")
     if not torch.is_tensor(frames_yuv) or frames_yuv.dtype != torch.uint8:
         raise ValueError(f"frames must be a uint8 tensor (..., H * 3 / 2, W), got {getattr(frames_yuv, 'dtype', type(frames_yuv))}")
-    H, W = _yuv_hw(frames_yuv.shape, pixel_format)
+    H, W, surf = _yuv_geom(frames_yuv.shape, pixel_format, window)
     lead = tuple(frames_yuv.shape[:-2])
     N = 1
     for d in lead:
@@ -411,12 +499,17 @@ def yuv_to_rgb(frames_yuv: torch.Tensor, pixel_format: str, matrix: str = "bt601
         if out.device != x.device or (a < b + out.numel() and b < a + x.numel()):
             raise ValueError("out must be on the frames' device and must not share memory with them")
     with torch.cuda.device(x.device):
-        L.check(L.load().csts_yuv_to_rgb(x.data_ptr(), out.data_ptr(), N, H, W, layout, mat, fr, _s()), "csts_yuv_to_rgb")
+        if surf:
+            L.check(L.load().csts_yuv_to_rgb_win(x.data_ptr(), out.data_ptr(), N, H, W, *surf, layout, mat, fr, _s()),
+                    "csts_yuv_to_rgb_win")
+        else:
+            L.check(L.load().csts_yuv_to_rgb(x.data_ptr(), out.data_ptr(), N, H, W, layout, mat, fr, _s()), "csts_yuv_to_rgb")
     return out
 
 
-def yuv_to_rgb_host(frames_yuv, pixel_format: str, matrix: str = "bt601", full_range: bool = False):
-    """yuv_to_rgb on the CPU (csts_yuv_to_rgb_host, the same pixel function): numpy uint8 (..., H * 3 / 2, W) -> (..., H, W, 3)."""
+def yuv_to_rgb_host(frames_yuv, pixel_format: str, matrix: str = "bt601", full_range: bool = False, *, window=None):
+    """yuv_to_rgb on the CPU (csts_yuv_to_rgb_host, the same pixel function): numpy uint8 (..., H * 3 / 2, W) -> (..., H, W, 3);
+    window as yuv_to_rgb takes it (csts_yuv_to_rgb_win_host)."""
     import numpy as np
     layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
     if layout == 0:
@@ -424,13 +517,17 @@ def yuv_to_rgb_host(frames_yuv, pixel_format: str, matrix: str = "bt601", full_r
     x = np.ascontiguousarray(frames_yuv)
     if x.dtype != np.uint8:
         raise ValueError(f"frames must be uint8, got {x.dtype}")
-    H, W = _yuv_hw(x.shape, pixel_format)
+    H, W, surf = _yuv_geom(x.shape, pixel_format, window)
     lead = tuple(x.shape[:-2])
     N = int(np.prod(lead, dtype=np.int64)) if lead else 1
     if N < 1:
         raise ValueError(f"frames hold no picture: {x.shape}")
     out = np.empty(lead + (H, W, 3), dtype=np.uint8)
-    L.check(L.load().csts_yuv_to_rgb_host(x.ctypes.data, out.ctypes.data, N, H, W, layout, mat, fr), "csts_yuv_to_rgb_host")
+    if surf:
+        L.check(L.load().csts_yuv_to_rgb_win_host(x.ctypes.data, out.ctypes.data, N, H, W, *surf, layout, mat, fr),
+                "csts_yuv_to_rgb_win_host")
+    else:
+        L.check(L.load().csts_yuv_to_rgb_host(x.ctypes.data, out.ctypes.data, N, H, W, layout, mat, fr), "csts_yuv_to_rgb_host")
     return out
 
 
@@ -452,15 +549,17 @@ def _rgb_hw(shape, what="frames"):
 
 
 def rgb_to_yuv(frames_u8: torch.Tensor, pixel_format: str, matrix: str = "bt601", full_range: bool = False,
-               out: torch.Tensor = None) -> torch.Tensor:
+               out: torch.Tensor = None, *, window=None) -> torch.Tensor:
     """Packed RGB uint8 (..., H, W, 3), H and W even -> 4:2:0 pictures uint8 (..., H * 3 / 2, W) in `pixel_format` ("nv12" |
     "i420") by the inverse integer rule of include/csts_hip.h (luma per pixel, chroma from the sums of each 2 x 2 block; `matrix`
     "bt601" | "bt709", limited range unless full_range), one streaming launch (csts_rgb_to_yuv).  The input may start at any
     byte.  out: a contiguous uint8 (..., H * 3 / 2, W) GPU tensor to write into, at any byte as well; it must not share memory
-    with the input."""
+    with the input.  It writes tight pictures only: a window (writing into a decoder surface) is refused."""
     layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
     if layout == 0:
         raise ValueError("rgb_to_yuv writes 'nv12' or 'i420' pictures; rgb24 needs no conversion")
+    if window is not None:
+        raise ValueError("rgb_to_yuv writes tight 4:2:0 pictures only: writing the window of a surface is not supported")
     if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8:
         raise ValueError(f"frames must be a uint8 tensor (..., H, W, 3), got {getattr(frames_u8, 'dtype', type(frames_u8))}")
     lead, H, W = _rgb_hw(frames_u8.shape)
@@ -508,7 +607,8 @@ def rgb_to_yuv_host(frames_u8, pixel_format: str, matrix: str = "bt601", full_ra
 def spatial_sampling(frames_u8: torch.Tensor, labels: torch.Tensor, crop_size: int, *, train: bool, min_scale: int = 0,
                      max_scale: int = 0, spatial_idx: int = 1, random_flip: bool = True, inverse_uniform: bool = False,
                      mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225), generator=None, return_params: bool = False,
-                     key: torch.Tensor = None, pixel_format: str = "rgb24", matrix: str = "bt601", full_range: bool = False):
+                     key: torch.Tensor = None, pixel_format: str = "rgb24", matrix: str = "bt601", full_range: bool = False,
+                     window=None):
     """slowfast/datasets/utils.py::spatial_sampling(..., gaze_loc=labels) on the device, fused with frame normalisation.
 
     frames_u8 uint8 (B, T, H, W, 3), labels (B, T, L >= 2) with x, y in columns 0, 1 -> video fp32 (B, 3, T, S, S) and the
@@ -518,14 +618,17 @@ def spatial_sampling(frames_u8: torch.Tensor, labels: torch.Tensor, crop_size: i
     device generator when None), so the call needs no host sync, can be captured in a graph and follows torch.manual_seed.
     train=False: short side resized to crop_size and the uniform crop `spatial_idx` (0, 1, 2); no draw.  key: an int64 (1,)
     device tensor to use instead of the draw (the kernel reads it when it runs).  include/csts_hip.h states the rule.
-    pixel_format "nv12" | "i420": frames_u8 is uint8 (B, T, H * 3 / 2, W), 4:2:0 pictures sampled in place (spatial_sample)."""
+    pixel_format "nv12" | "i420": frames_u8 is uint8 (B, T, H * 3 / 2, W), 4:2:0 pictures sampled in place (spatial_sample);
+    window (top, left, H, W): the pictures are the windows of surfaces (B, T, Hs * 3 / 2, Ws) (check_window), and the rule runs
+    on the window's H x W."""
     yuv = check_pixel_format(pixel_format, matrix, full_range)[0] != 0
     if yuv:
         if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4:
             raise ValueError(f"{pixel_format} frames must be uint8 (B, T, H * 3 / 2, W), got {tuple(frames_u8.shape)} "
                              f"{frames_u8.dtype}")
-        (B, T), (H, W) = frames_u8.shape[:2], _yuv_hw(frames_u8.shape, pixel_format)
+        (B, T), (H, W) = frames_u8.shape[:2], window_size(frames_u8.shape, pixel_format, window)
     else:
+        check_window(frames_u8.shape, pixel_format, window)
         if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 5 or frames_u8.shape[-1] != 3:
             raise ValueError(f"frames must be uint8 (B, T, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
         B, T, H, W, _ = frames_u8.shape
@@ -566,24 +669,28 @@ def spatial_sampling(frames_u8: torch.Tensor, labels: torch.Tensor, crop_size: i
     L.check(lib.csts_spatial_params(key.data_ptr() if key is not None else None, lab.data_ptr(), B, T, ncol, H, W, S, min_scale,
                                      max_scale, idx, int(bool(random_flip)), int(bool(inverse_uniform)), params.data_ptr(),
                                      new_labels.data_ptr(), _s()), "csts_spatial_params")
-    video = spatial_sample(x, params, S, mean=mean, std=std, pixel_format=pixel_format, matrix=matrix, full_range=full_range)
+    video = spatial_sample(x, params, S, mean=mean, std=std, pixel_format=pixel_format, matrix=matrix, full_range=full_range,
+                           window=window)
     return (video, new_labels, params) if return_params else (video, new_labels)
 
 
 def spatial_sample(frames_u8: torch.Tensor, params: torch.Tensor, crop_size: int, mean=(0.45, 0.45, 0.45),
                    std=(0.225, 0.225, 0.225), *, pixel_format: str = "rgb24", matrix: str = "bt601",
-                   full_range: bool = False) -> torch.Tensor:
+                   full_range: bool = False, window=None) -> torch.Tensor:
     """The pixel pass of spatial_sampling alone: uint8 (B, T, H, W, 3) + int32 params (B, 5) = new h, new w, y0, x0, flip ->
     fp32 (B, 3, T, S, S) = normalised bilinear resize (F.interpolate, align_corners=False) + crop + horizontal flip.
     pixel_format "nv12" | "i420": frames_u8 is uint8 (B, T, H * 3 / 2, W), 4:2:0 pictures read in place
-    (csts_spatial_sample_yuv); the result is, bit for bit, spatial_sample(yuv_to_rgb(frames, ...), params, S)."""
+    (csts_spatial_sample_yuv); the result is, bit for bit, spatial_sample(yuv_to_rgb(frames, ...), params, S).  window (top,
+    left, H, W): the pictures are the windows of surfaces (B, T, Hs * 3 / 2, Ws), read in place (csts_spatial_sample_yuv_win)."""
     layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
+    surf = None
     if layout:
         if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4:
             raise ValueError(f"{pixel_format} frames must be uint8 (B, T, H * 3 / 2, W), got {tuple(frames_u8.shape)} "
                              f"{frames_u8.dtype}")
-        (B, T), (H, W) = frames_u8.shape[:2], _yuv_hw(frames_u8.shape, pixel_format)
+        (B, T), (H, W, surf) = frames_u8.shape[:2], _yuv_geom(frames_u8.shape, pixel_format, window)
     else:
+        check_window(frames_u8.shape, pixel_format, window)
         if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 5 or frames_u8.shape[-1] != 3:
             raise ValueError(f"frames must be uint8 (B, T, H, W, 3), got {tuple(frames_u8.shape)} {frames_u8.dtype}")
         B, T, H, W, _ = frames_u8.shape
@@ -597,6 +704,10 @@ def spatial_sample(frames_u8: torch.Tensor, params: torch.Tensor, crop_size: int
     out = torch.empty(B, 3, T, S, S, dtype=torch.float32, device=x.device)
     f3 = C.c_float * 3
     par = params.contiguous()
+    if surf:
+        L.check(L.load().csts_spatial_sample_yuv_win(x.data_ptr(), par.data_ptr(), out.data_ptr(), B, T, H, W, *surf, S, f3(*mean),
+                                                     f3(*std), layout, mat, fr, _s()), "csts_spatial_sample_yuv_win")
+        return out
     if layout:
         L.check(L.load().csts_spatial_sample_yuv(x.data_ptr(), par.data_ptr(), out.data_ptr(), B, T, H, W, S, f3(*mean), f3(*std),
                                                  layout, mat, fr, _s()), "csts_spatial_sample_yuv")
@@ -608,19 +719,23 @@ def spatial_sample(frames_u8: torch.Tensor, params: torch.Tensor, crop_size: int
 
 def clip_sample(video_u8: torch.Tensor, frames_idx: torch.Tensor, params: torch.Tensor, crop_size: int,
                 mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225), *, pixel_format: str = "rgb24", matrix: str = "bt601",
-                full_range: bool = False) -> torch.Tensor:
+                full_range: bool = False, window=None) -> torch.Tensor:
     """spatial_sample of clips that are windows of ONE resident video, without gathering them first: video uint8 (N, H, W, 3),
     frames_idx int32 (B, T) frame numbers (clamped to [0, N - 1] on the device, as the reference's temporal_sampling clamps),
     params int32 (B, 5) -> fp32 (B, 3, T, S, S), bit for bit spatial_sample(video[frames_idx], params, S).  The table is read
     by the kernel when it runs: no host sync, graph-capturable (csts_clip_sample).  pixel_format "nv12" | "i420": the video is
-    uint8 (N, H * 3 / 2, W), 4:2:0 pictures read in place (csts_clip_sample_yuv), bit for bit clip_sample of yuv_to_rgb(video)."""
+    uint8 (N, H * 3 / 2, W), 4:2:0 pictures read in place (csts_clip_sample_yuv), bit for bit clip_sample of yuv_to_rgb(video).
+    window (top, left, H, W): the video holds surfaces (N, Hs * 3 / 2, Ws) and its pictures are their windows
+    (csts_clip_sample_yuv_win)."""
     layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
+    surf = None
     if layout:
         if video_u8.dtype != torch.uint8 or video_u8.dim() != 3 or video_u8.shape[0] < 1:
             raise ValueError(f"{pixel_format} video must be uint8 (N >= 1, H * 3 / 2, W), got {tuple(video_u8.shape)} "
                              f"{video_u8.dtype}")
-        N, (H, W) = video_u8.shape[0], _yuv_hw(video_u8.shape, pixel_format, "video")
+        N, (H, W, surf) = video_u8.shape[0], _yuv_geom(video_u8.shape, pixel_format, window, "video")
     else:
+        check_window(video_u8.shape, pixel_format, window)
         if video_u8.dtype != torch.uint8 or video_u8.dim() != 4 or video_u8.shape[-1] != 3 or video_u8.shape[0] < 1:
             raise ValueError(f"video must be uint8 (N >= 1, H, W, 3), got {tuple(video_u8.shape)} {video_u8.dtype}")
         N, H, W, _ = video_u8.shape
@@ -641,6 +756,10 @@ def clip_sample(video_u8: torch.Tensor, frames_idx: torch.Tensor, params: torch.
     out = torch.empty(B, 3, T, S, S, dtype=torch.float32, device=x.device)
     f3 = C.c_float * 3
     idx, par = frames_idx.contiguous(), params.contiguous()
+    if surf:
+        L.check(L.load().csts_clip_sample_yuv_win(x.data_ptr(), N, idx.data_ptr(), par.data_ptr(), out.data_ptr(), B, T, H, W, *surf,
+                                                  S, f3(*mean), f3(*std), layout, mat, fr, _s()), "csts_clip_sample_yuv_win")
+        return out
     if layout:
         L.check(L.load().csts_clip_sample_yuv(x.data_ptr(), N, idx.data_ptr(), par.data_ptr(), out.data_ptr(), B, T, H, W, S,
                                               f3(*mean), f3(*std), layout, mat, fr, _s()), "csts_clip_sample_yuv")
@@ -721,20 +840,23 @@ def stream_audio_windows(ring: torch.Tensor, newest: int, centers: torch.Tensor,
 
 def stream_ingest(chunk_u8: torch.Tensor, pairs: torch.Tensor, params_row: torch.Tensor, ring: torch.Tensor,
                   mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225), *, pixel_format: str = "rgb24", matrix: str = "bt601",
-                  full_range: bool = False) -> torch.Tensor:
+                  full_range: bool = False, window=None) -> torch.Tensor:
     """The used frames of one pushed chunk, sampled once into a ring of normalised crops (csts_stream_ingest): chunk uint8
     (K, H, W, 3), pairs int32 (P, 2) = (frame in chunk, slot) on the device, params_row int32 (5,) = new h, new w, y0, x0, flip
     (one test-mode row for the stream), ring fp32 (R, 3, S, S) -> ring[slot] = clip_sample(chunk, [[frame]], params_row[None],
     S)[0, :, 0], bit for bit.  A chunk frame no pair names is not read, and no other slot is written.  The table is read by the
     kernel when it runs; a pair outside the chunk or the ring writes nothing.  P == 0 launches nothing.  pixel_format "nv12" |
-    "i420": the chunk is uint8 (K, H * 3 / 2, W), read in place (csts_stream_ingest_yuv).  Returns the ring."""
+    "i420": the chunk is uint8 (K, H * 3 / 2, W), read in place (csts_stream_ingest_yuv); window (top, left, H, W): the chunk
+    holds surfaces (K, Hs * 3 / 2, Ws) and its frames are their windows (csts_stream_ingest_yuv_win).  Returns the ring."""
     layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
+    surf = None
     if layout:
         if chunk_u8.dtype != torch.uint8 or chunk_u8.dim() != 3 or chunk_u8.shape[0] < 1:
             raise ValueError(f"{pixel_format} chunk must be uint8 (K >= 1, H * 3 / 2, W), got {tuple(chunk_u8.shape)} "
                              f"{chunk_u8.dtype}")
-        K, (H, W) = chunk_u8.shape[0], _yuv_hw(chunk_u8.shape, pixel_format, "chunk")
+        K, (H, W, surf) = chunk_u8.shape[0], _yuv_geom(chunk_u8.shape, pixel_format, window, "chunk")
     else:
+        check_window(chunk_u8.shape, pixel_format, window)
         if chunk_u8.dtype != torch.uint8 or chunk_u8.dim() != 4 or chunk_u8.shape[-1] != 3 or chunk_u8.shape[0] < 1:
             raise ValueError(f"chunk must be uint8 (K >= 1, H, W, 3), got {tuple(chunk_u8.shape)} {chunk_u8.dtype}")
         K, H, W, _ = chunk_u8.shape
@@ -757,7 +879,11 @@ def stream_ingest(chunk_u8: torch.Tensor, pairs: torch.Tensor, params_row: torch
     f3 = C.c_float * 3
     tab, par = pairs.contiguous(), params_row.contiguous()
     with torch.cuda.device(ring.device):
-        if layout:
+        if surf:
+            L.check(L.load().csts_stream_ingest_yuv_win(x.data_ptr(), K, H, W, *surf, tab.data_ptr(), P, par.data_ptr(),
+                                                        ring.data_ptr(), R, S, f3(*mean), f3(*std), layout, mat, fr, _s()),
+                    "csts_stream_ingest_yuv_win")
+        elif layout:
             L.check(L.load().csts_stream_ingest_yuv(x.data_ptr(), K, H, W, tab.data_ptr(), P, par.data_ptr(), ring.data_ptr(), R, S,
                                                     f3(*mean), f3(*std), layout, mat, fr, _s()), "csts_stream_ingest_yuv")
         else:
@@ -899,7 +1025,7 @@ def group_audio_windows(rings: torch.Tensor, stream_of, newest, centers, width: 
 
 
 def group_ingest(jobs, pairs, arena: torch.Tensor, mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225), *,
-                 pixel_format: str = "rgb24", matrix: str = "bt601", full_range: bool = False) -> torch.Tensor:
+                 pixel_format: str = "rgb24", matrix: str = "bt601", full_range: bool = False, window=None) -> torch.Tensor:
     """stream_ingest for several streams in ONE launch (csts_group_ingest / _yuv): jobs is a list of (chunk, params_row) -- chunk
     uint8 (K, H, W, 3) on the device, or (K, H * 3 / 2, W) in the one pixel_format of the call, each job of its own size;
     params_row the five test-mode integers new h, new w, y0, x0, flip of that job, on the HOST -- and pairs a HOST table (P, 3) =
@@ -907,8 +1033,9 @@ def group_ingest(jobs, pairs, arena: torch.Tensor, mean=(0.45, 0.45, 0.45), std=
     [[frame]], params_row[None], S)[0, :, 0], bit for bit.  A chunk frame no pair names is not read and no other slot is
     written; a pair whose job, frame or slot is out of range writes nothing; the tables go up in one copy and are read by the
     kernel when it runs.  A chunk that does not start at a 16-byte boundary is copied first, as stream_ingest does.  P == 0
-    launches nothing.  Returns the arena."""
+    launches nothing.  The chunks are tight pictures: a window is refused.  Returns the arena."""
     import numpy as np
+    no_window(window, "group_ingest")
     layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
     if arena.dtype != torch.float32 or arena.dim() != 4 or arena.shape[1] != 3 or arena.shape[2] != arena.shape[3] or \
             not arena.is_contiguous() or arena.data_ptr() % 16:
@@ -1017,7 +1144,7 @@ def batch_params(labels: torch.Tensor, clips: torch.Tensor, crop_size: int, *, t
 
 def batch_sample(arena_u8: torch.Tensor, clips: torch.Tensor, frames_idx: torch.Tensor, params: torch.Tensor, crop_size: int,
                  clips_host, mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225), out: torch.Tensor = None, *,
-                 pixel_format: str = "rgb24", matrix: str = "bt601", full_range: bool = False) -> torch.Tensor:
+                 pixel_format: str = "rgb24", matrix: str = "bt601", full_range: bool = False, window=None) -> torch.Tensor:
     """clip_sample for clips of B different recordings in ONE launch (csts_batch_sample): arena_u8 uint8 (bytes,) holds the
     recordings back to back at any byte, clips int64 (B, 4) = {byte offset, N, H, W} on the device, frames_idx int32 (B, T)
     (clamped to [0, N_b - 1] on the device), params int32 (B, 5) -> fp32 (B, 3, T, S, S); clip b is, bit for bit,
@@ -1025,8 +1152,9 @@ def batch_sample(arena_u8: torch.Tensor, clips: torch.Tensor, frames_idx: torch.
     the arena with N, H, W >= 1 (ValueError) -- the device reads the tables when the kernel runs and gives a NaN clip for a row
     that does not, so a captured launch stays safe when the tables are rewritten.  pixel_format "nv12" | "i420": the recordings
     are 4:2:0 pictures (csts_batch_sample_yuv); the table keeps its columns with H the luma height (H, W even), a recording
-    occupies N H W 3 / 2 bytes and clip b is clip_sample of it in that format."""
+    occupies N H W 3 / 2 bytes and clip b is clip_sample of it in that format.  The recordings are tight: a window is refused."""
     import numpy as np
+    no_window(window, "batch_sample")
     layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
     if arena_u8.dtype != torch.uint8 or arena_u8.dim() != 1 or arena_u8.numel() < 3:
         raise ValueError(f"the arena must be uint8 (bytes,), got {tuple(arena_u8.shape)} {arena_u8.dtype}")
@@ -1146,19 +1274,23 @@ def spatial_uniforms_host(key: int, first: int, count: int):
 
 
 def assemble_batch(frames_u8, wav, frames_idx, frame_length, labels, spatial=None, *, pixel_format: str = "rgb24",
-                   matrix: str = "bt601", full_range: bool = False):
+                   matrix: str = "bt601", full_range: bool = False, window=None):
     """uint8 frames (B, T, H, W, 3), waveform (B, n), sampled frame indices (B, T), gaze labels (B, T, 3) -> the batch
     dict the training step takes (video, audio, labels_hm, labels).  spatial: None (frames normalised at the size they
     come in), or the keyword arguments of spatial_sampling (crop_size, train, ...): the video is spatially sampled, and
     the heat maps ((S/4)^2) and the returned labels are the transformed ones (ego4d_avgaze_forecast.py:302-326).
     pixel_format "nv12" | "i420": the frames are 4:2:0 pictures uint8 (B, T, H * 3 / 2, W); with spatial they are sampled in
-    place, without it they are converted (yuv_to_rgb) and normalised."""
+    place, without it they are converted (yuv_to_rgb) and normalised; window (top, left, H, W): they are surfaces (B, T,
+    Hs * 3 / 2, Ws) and the pictures their windows, read in place either way."""
     yuv = check_pixel_format(pixel_format, matrix, full_range)[0] != 0
-    fmt = dict(pixel_format=pixel_format, matrix=matrix, full_range=full_range) if yuv else {}
+    fmt = dict(pixel_format=pixel_format, matrix=matrix, full_range=full_range, window=window) if yuv else {}
     if yuv:
         if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4:
             raise ValueError(f"{pixel_format} frames must be uint8 (B, T, H * 3 / 2, W), got {tuple(frames_u8.shape)}")
         _yuv_hw(frames_u8.shape, pixel_format)
+        check_window(frames_u8.shape, pixel_format, window)
+    else:
+        check_window(getattr(frames_u8, "shape", ()), pixel_format, window)
     if spatial is None:
         return {"video": normalize_frames(yuv_to_rgb(frames_u8, **fmt) if yuv else frames_u8),
                 "audio": audio_windows(stft_logpower(wav), frames_idx, frame_length),

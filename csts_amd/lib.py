@@ -279,10 +279,17 @@ SYMBOLS = {
     "csts_spatial_sample_yuv": (_I, [vp, vp, vp, _I, _I, _I, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),
     "csts_clip_sample_yuv": (_I, [vp, i64, vp, vp, vp, _I, _I, _I, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),
     "csts_batch_sample_yuv": (_I, [vp, i64, vp, vp, vp, vp, _I, _I, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),
+    "csts_yuv_to_rgb_win": (_I, [vp, vp, i64, _I, _I, _I, _I, _I, _I, _I, _I, _I, vp]),
+    "csts_yuv_to_rgb_win_host": (_I, [vp, vp, i64, _I, _I, _I, _I, _I, _I, _I, _I, _I]),
+    "csts_spatial_sample_yuv_win": (_I, [vp, vp, vp, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),
+    "csts_clip_sample_yuv_win": (_I, [vp, i64, vp, vp, vp, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I,
+                                 vp]),
     "csts_stream_stft": (_I, [vp, i64, i64, i64, i64, i64, vp, _I, _I, _I, _I, _F, vp]),
     "csts_stream_audio_windows": (_I, [vp, _I, i64, vp, vp, _I, _I, _I, _I, vp]),
     "csts_stream_ingest": (_I, [vp, _I, _I, _I, vp, _I, vp, vp, _I, _I, C.c_float * 3, C.c_float * 3, vp]),
     "csts_stream_ingest_yuv": (_I, [vp, _I, _I, _I, vp, _I, vp, vp, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I, vp]),
+    "csts_stream_ingest_yuv_win": (_I, [vp, _I, _I, _I, _I, _I, _I, _I, vp, _I, vp, vp, _I, _I, C.c_float * 3, C.c_float * 3, _I, _I, _I,
+                                   vp]),
     "csts_stream_gather": (_I, [vp, _I, vp, vp, _I, _I, _I, vp]),
     "csts_group_stft": (_I, [vp, vp, _I, vp, _I, _I, _I, _I, _I, _F, vp]),
     "csts_group_audio_windows": (_I, [vp, _I, _I, vp, vp, vp, vp, _I, _I, _I, _I, vp]),
@@ -304,6 +311,7 @@ SYMBOLS = {
     "csts_gaze_track_fill": (_I, [vp, vp, i64, _I, _I, _I, _I, vp, vp, vp, vp, vp, vp]),
     "csts_gaze_overlay": (_I, [vp, vp, vp, vp, vp, i64, _I, _I, _I, _I, _I, _F, _I, vp]),
     "csts_gaze_overlay_yuv": (_I, [vp, vp, vp, vp, vp, i64, _I, _I, _I, _I, _I, _F, _I, _I, _I, _I, vp]),
+    "csts_gaze_overlay_yuv_win": (_I, [vp, vp, vp, vp, vp, i64, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _I, _I, vp]),
     "csts_group_gaze_overlay": (_I, [vp, vp, _I, vp, vp, _I, _I, _I, _F, _I, vp]),
     "csts_group_gaze_overlay_yuv": (_I, [vp, vp, _I, vp, vp, _I, _I, _I, _F, _I, _I, _I, _I, vp]),
     "csts_group_points_source": (_I, [vp, vp, _I, vp, _I, vp, vp, vp]),

@@ -2821,7 +2821,7 @@ def gaze_overlay(frames_u8, rescaled, params, crop_size, centers=None, alpha=0.4
 
 
 def gaze_overlay_yuv(frames_yuv, rescaled, params, crop_size, pixel_format, matrix="bt601", full_range=False, centers=None,
-                     alpha=0.4, radius=5, out=None):
+                     alpha=0.4, radius=5, out=None, window=None):
     """csts_gaze_overlay_yuv: gaze_overlay drawn onto 4:2:0 frames uint8 (N, H * 3 / 2, W) in `pixel_format` ("nv12" | "i420",
     with `matrix` and `full_range` as inputs.yuv_to_rgb takes them) -> uint8 of the same shape and layout, 1.5 bytes in and 1.5
     out per pixel and no RGB picture in memory.  With D = gaze_overlay(inputs.yuv_to_rgb(frames), ...) and M the drawn mask
@@ -2829,15 +2829,17 @@ def gaze_overlay_yuv(frames_yuv, rescaled, params, crop_size, pixel_format, matr
     frames), M per pixel for luma and per 2 x 2 block (any) for chroma: an untouched frame, row pair or block comes back byte
     for byte, and a drawn pixel is re-encoded even at alpha = 0.  Every other argument as gaze_overlay takes it; frames and out
     may start at any byte; out=frames_yuv renders in place.  One launch, no host sync.  The rule is stated in
-    include/csts_hip.h."""
-    from .inputs import check_pixel_format, _yuv_hw
+    include/csts_hip.h.  window (top, left, H, W): the frames are surfaces (N, Hs * 3 / 2, Ws) and the pictures their windows
+    (inputs.check_window; csts_gaze_overlay_yuv_win): out is a surface as well, its window the overlay of the window and every
+    byte around it the input's (not written at all in place; otherwise the surface is copied first, one more device copy)."""
+    from .inputs import check_pixel_format, _yuv_geom
     layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
     if layout == 0:
         raise ValueError("gaze_overlay_yuv draws 'nv12' or 'i420' frames; packed RGB goes through gaze_overlay")
     _need_gpu(frames_yuv, rescaled, centers, out)
     if frames_yuv.dtype != torch.uint8 or frames_yuv.dim() != 3:
         raise ValueError(f"{pixel_format} frames must be uint8 (N, H * 3 / 2, W), got {tuple(frames_yuv.shape)} {frames_yuv.dtype}")
-    H, W = _yuv_hw(frames_yuv.shape, pixel_format)
+    H, W, surf = _yuv_geom(frames_yuv.shape, pixel_format, window)
     N = frames_yuv.shape[0]
     alpha, radius, S = _check_overlay_args("gaze_overlay_yuv", [(frames_yuv, out)], rescaled, centers, alpha, radius, crop_size)
     if out is None:
@@ -2848,6 +2850,11 @@ def gaze_overlay_yuv(frames_yuv, rescaled, params, crop_size, pixel_format, matr
     par = _overlay_params(params, S, frames_yuv.device)
     maps = rescaled.detach().contiguous()
     cen = None if centers is None else centers.contiguous()
+    if surf:
+        L.check(_lib().csts_gaze_overlay_yuv_win(_p(frames_yuv), _p(maps), _p(cen), _p(par), _p(out), N, H, W, *surf, S, maps.shape[1],
+                                                 maps.shape[2], alpha, radius, layout, mat, fr, _stream()),
+                "csts_gaze_overlay_yuv_win")
+        return out
     L.check(_lib().csts_gaze_overlay_yuv(_p(frames_yuv), _p(maps), _p(cen), _p(par), _p(out), N, H, W, S, maps.shape[1],
                                          maps.shape[2], alpha, radius, layout, mat, fr, _stream()), "csts_gaze_overlay_yuv")
     return out
@@ -2877,7 +2884,7 @@ def _disjoint_jobs(src, dst, nbytes):
 
 
 def group_gaze_overlay(jobs, rescaled, centers, crop_size, alpha=0.4, radius=5, outs=None, pixel_format="rgb24", matrix="bt601",
-                       full_range=False):
+                       full_range=False, window=None):
     """gaze_overlay / gaze_overlay_yuv for several jobs of different sizes in ONE launch (csts_group_gaze_overlay / _yuv): jobs is a
     list of (frames, params_row) -- frames uint8 (K, H, W, 3) on the device, or (K, H * 3 / 2, W) in the one 4:2:0 pixel_format
     (with matrix and full_range) of the call, each job of its own K, H, W; params_row its five integers on the HOST -- and
@@ -2888,9 +2895,11 @@ def group_gaze_overlay(jobs, rescaled, centers, crop_size, alpha=0.4, radius=5, 
     allocation, each starting at a 16-byte boundary.  No job's out may overlap another job's frames or out.  Validation is
     gaze_overlay's per job, the messages prefixed "job j: ", all on the host before anything is launched; the table goes up in
     one copy.  Inside the launch a job takes the 4-pixel path when W % 4 == 0 and frames and out are 4-byte aligned, else the byte
-    path (packed RGB); a 4:2:0 job that cannot take the 4-pixel path goes through gaze_overlay_yuv, one launch for that job."""
+    path (packed RGB); a 4:2:0 job that cannot take the 4-pixel path goes through gaze_overlay_yuv, one launch for that job.
+    The frames are tight pictures: a window is refused."""
     import numpy as np
-    from .inputs import check_pixel_format, _yuv_hw, _upload
+    from .inputs import check_pixel_format, _yuv_hw, _upload, no_window
+    no_window(window, "group_gaze_overlay")
     from .infer import overlay_group_table
     layout, mat, fr = check_pixel_format(pixel_format, matrix, full_range)
     jobs = list(jobs)

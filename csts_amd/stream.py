@@ -295,14 +295,17 @@ def track_from_windows(results, n_frames, want=("points", "peak", "count", "heat
 
 # ---- the host rules of one stream: GazeStream follows them on its scalars, the groups on each slot's entries -------------------------
 
-def _open(s, predictor, fps, stride, segment, max_chunk, pixel_format, matrix, full_range, input_rate):
+def _open(s, predictor, fps, stride, segment, max_chunk, pixel_format, matrix, full_range, input_rate, window=None):
     """The fields every stream class derives from its predictor, plan and format arguments, set on `s`: input_rate, fmt,
-    predictor, plan, S, T, mean, std, R, ring_cols.  Returns ring_sizes(plan, max_chunk, S)."""
+    predictor, plan, S, T, mean, std, R, ring_cols.  Returns ring_sizes(plan, max_chunk, S).  window: the window of the pushed
+    4:2:0 surfaces (GazeStream only); it joins fmt and is checked against the surface when the first frames arrive."""
     from . import inputs
     s.input_rate = None if input_rate is None else inputs.check_sample_rate(input_rate, "input_rate")
     s.fmt = {}
     if inputs.check_pixel_format(pixel_format, matrix, full_range)[0]:
         s.fmt = {"pixel_format": pixel_format, "matrix": matrix, "full_range": bool(full_range)}
+    if window is not None:
+        s.fmt["window"] = inputs.window_values(pixel_format, window)
     s.predictor = predictor
     cfg = predictor.cfg
     s.plan = plan_stream(cfg, fps=fps, stride=stride, segment=segment)
@@ -359,7 +362,8 @@ def check_piece(who, closed, hw, fmt, resampler, frames, wav):
             raise L.CstsError(f"{who} runs on MI355X only: inputs must be GPU tensors (there is no CPU fallback)")
     k = m = m_in = 0
     if frames is not None:
-        H, W, _ = _picture_hw(frames, 1, fmt.get("pixel_format", "rgb24"), fmt.get("matrix", "bt601"), fmt.get("full_range", False))
+        H, W, _ = _picture_hw(frames, 1, fmt.get("pixel_format", "rgb24"), fmt.get("matrix", "bt601"), fmt.get("full_range", False),
+                              fmt.get("window"))
         if hw is not None and (H, W) != hw:
             raise ValueError(f"the stream's frames are {hw[0]} x {hw[1]} (fixed by the first push), got {H} x {W}")
         k, hw = frames.shape[0], (H, W)
@@ -448,9 +452,10 @@ def live_fields(rows, frame_idx, known):
     return rows
 
 
-def live_empty(side, device, hw=None, overlay=False, overlay_format=None):
+def live_empty(side, device, hw=None, overlay=False, overlay_format=None, surface=None):
     """The live dict of a push without frames, K = 0: every field of push_live with its shape and dtype; with overlay the frames'
-    shape at the stream's H x W (0 x 0 before the first frame), (0, H * 3 / 2, W) when overlay_format names a 4:2:0 layout."""
+    shape at the stream's H x W (0 x 0 before the first frame), (0, H * 3 / 2, W) when overlay_format names a 4:2:0 layout --
+    (0,) + surface when the stream reads the windows of surfaces of that (Hs * 3 / 2, Ws)."""
     import torch
     shapes = {"frame_idx": ((0,), torch.int64), "known": ((0,), torch.int32), "points": ((0, 2), torch.float32),
               "peak": ((0,), torch.float32), "count": ((0,), torch.int32), "neighbours": ((0, 2), torch.int32),
@@ -459,7 +464,7 @@ def live_empty(side, device, hw=None, overlay=False, overlay_format=None):
     out = {k: torch.empty(shape, dtype=dt, device=device) for k, (shape, dt) in shapes.items()}
     if overlay:
         H, W = hw if hw is not None else (0, 0)
-        shape = (0, H * 3 // 2, W) if overlay_format else (0, H, W, 3)
+        shape = ((0,) + tuple(surface) if surface else (0, H * 3 // 2, W)) if overlay_format else (0, H, W, 3)
         out["overlay"] = torch.empty(shape, dtype=torch.uint8, device=device)
     return out
 
@@ -523,12 +528,17 @@ class GazeStream:
     change by a bit with live on.  An estimation plan (targets inside the observed span) is refused: it has nothing to show on
     an arriving frame.
 
+    Decoder surfaces (window=(top, left, H, W), 4:2:0 formats only): the pushed frames are surfaces uint8 (K, Hs * 3 / 2, Ws) and
+    the stream's pictures their windows (inputs.check_window), ingested in place (csts_stream_ingest_yuv_win): H x W is the
+    stream's source size, every window and live row equals that of a stream fed inputs.yuv_window of the same pushes, bit for
+    bit; an RGB overlay is (K, H, W, 3) of the window, a 4:2:0 overlay has the surfaces' shape and equals them outside the window.
+
     Out of scope: attention maps per streamed window, a delayed display for estimation plans, and equality with predict_video.
     sample_rate= still names the rate the audio is pushed at as it is, 24 kHz only."""
 
     def __init__(self, predictor, fps=None, stride=None, segment=None, batch=1, max_chunk=32, pixel_format="rgb24",
                  matrix="bt601", full_range=False, sample_rate=None, input_rate=None, live=None, max_gap=None, overlay=False,
-                 alpha=0.4, radius=5, overlay_format=None):
+                 alpha=0.4, radius=5, overlay_format=None, window=None):
         check_stream_rate(sample_rate)
         from . import inputs
         if input_rate is not None and sample_rate is not None:
@@ -537,7 +547,8 @@ class GazeStream:
         self.batch, self.max_chunk = int(batch), int(max_chunk)
         if self.batch < 1 or self.max_chunk < 1:
             raise ValueError(f"batch and max_chunk must be positive, got {batch} and {max_chunk}")
-        self.capacity = _open(self, predictor, fps, stride, segment, self.max_chunk, pixel_format, matrix, full_range, input_rate)
+        self.capacity = _open(self, predictor, fps, stride, segment, self.max_chunk, pixel_format, matrix, full_range, input_rate,
+                              window)
         self.live, self.overlay, self.alpha, self.radius = live, bool(overlay), float(alpha), int(radius)
         self.max_gap, self.overlay_format, self.track_slots, track_bytes = check_live_args(
             self.plan, self.max_chunk, self.S, self.fmt, live, max_gap, overlay, alpha, radius, overlay_format)
@@ -547,7 +558,7 @@ class GazeStream:
         self.input_samples = 0                               # source samples consumed (= samples without input_rate)
         self.frames = self.samples = self.cols = 0          # pushed so far; columns [0, cols) are final
         self.next_window, self.dropped, self.closed = 0, 0, False
-        self.hw = None
+        self.hw = self._surface = None                       # H x W of the pictures; (Hs * 3 / 2, Ws) under a window
         self._crops = self._spec = self._tail = self._params = self._track = None
         self._tail_base = 0                                  # the stream position of _tail[0]
 
@@ -663,6 +674,7 @@ class GazeStream:
         with torch.no_grad(), torch.cuda.device(self.predictor.device):
             if k and self.hw is None:
                 self._setup(*hw, frames.device)
+                self._surface = tuple(frames.shape[1:]) if "window" in self.fmt else None
             if wav is not None:
                 self.input_samples += m_in
                 if self.resampler is not None:
@@ -685,7 +697,7 @@ class GazeStream:
                 return results, None
             if not rows:
                 dev = frames.device if frames is not None else (wav.device if wav is not None else self.predictor.device)
-                return results, live_empty(self.S // 4, dev, self.hw, self.overlay, self.overlay_format)
+                return results, live_empty(self.S // 4, dev, self.hw, self.overlay, self.overlay_format, self._surface)
             live = _cat_rows(rows)
         return results, live
 
@@ -810,9 +822,10 @@ class GazeStreamGroup:
     GazePredictor.live_group).  Out of scope: attention maps; different plans per slot; equality with predict_video."""
 
     def __init__(self, predictor, streams, fps=None, stride=None, segment=None, batch=4, max_chunk=32, pixel_format="rgb24",
-                 matrix="bt601", full_range=False, input_rate=None):
+                 matrix="bt601", full_range=False, input_rate=None, window=None):
         import torch
         from . import inputs
+        inputs.no_window(window, type(self).__name__)        # the grouped kernels take tight pictures only
         self.streams, self.batch, self.max_chunk = int(streams), int(batch), int(max_chunk)
         if self.streams < 1 or self.batch < 1 or self.max_chunk < 1:
             raise ValueError(f"streams, batch and max_chunk must be positive, got {streams}, {batch} and {max_chunk}")
@@ -1053,8 +1066,9 @@ class GazeLiveGroup(GazeStreamGroup):
 
     def __init__(self, predictor, streams, live, fps=None, stride=None, segment=None, batch=4, max_chunk=32, pixel_format="rgb24",
                  matrix="bt601", full_range=False, input_rate=None, max_gap=None, overlay=False, alpha=0.4, radius=5,
-                 overlay_format=None):
-        from . import ops
+                 overlay_format=None, window=None):
+        from . import ops, inputs
+        inputs.no_window(window, "GazeLiveGroup")
         cfg = predictor.cfg                                  # the live arguments are refused before the base class allocates
         self.live, self.overlay, self.alpha, self.radius = live, bool(overlay), float(alpha), int(radius)
         self.max_gap, self.overlay_format, self.track_slots, track_bytes = check_live_args(

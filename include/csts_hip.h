@@ -585,7 +585,7 @@ int csts_audio_gather(const float* spec_arena, const int64_t* specs, const int* 
 
 /* ---- 4:2:0 YUV frames (csts_amd/csrc/yuv.hip, yuv_shared.h; csts_amd/inputs.py): pictures the way video sources deliver them --
  *      NV12 from hardware decoders, I420 (yuv420p) from software ones -- 1.5 bytes per pixel, converted where they are read.
- *      Layouts.  One frame is H * 3 / 2 rows of W bytes, H and W even, rows unpadded:
+ *      Layouts.  One frame is H * 3 / 2 rows of W bytes, H and W even, rows unpadded (padded rows: "Decoder surfaces" below):
  *        CSTS_YUV_NV12: the Y plane H x W, then H / 2 rows of interleaved U V U V ...
  *        CSTS_YUV_I420: the Y plane H x W, then the U plane (H/2) x (W/2), then the V plane (H/2) x (W/2), each contiguous.
  *      Pixel (y, x) uses Y[y][x] and the chroma sample (y >> 1, x >> 1): nearest replication, no chroma interpolation.
@@ -629,9 +629,31 @@ int csts_audio_gather(const float* spec_arena, const int64_t* specs, const int* 
  *      coefficient is off by at most 2^-21 per term).  YUV -> RGB -> YUV is not the identity.
  *      rgb_to_yuv: frames (N, H, W, 3) RGB -> out (N, H * 3 / 2, W) in `layout`, H and W even, one streaming pass with the
  *        staging of yuv_to_rgb: input and output may start at any byte and must not overlap.  H <= 131070.  rgb_to_yuv_host:
- *        the same functions over HOST memory. */
+ *        the same functions over HOST memory.
+ *      Decoder surfaces (the *_win entry points).  A decoder delivers a picture inside an allocation: rows of a pitch wider than
+ *        the picture, a coded height taller than it, the chroma plane behind pitch * coded height.  A SURFACE is what the tensor
+ *        holds: a tight frame of the allocated size, Hs * 3 / 2 rows of Ws bytes in `layout` exactly as above (chroma from byte
+ *        Hs * Ws of a frame; i420: U then V, Hs / 2 rows of Ws / 2 bytes each).  A WINDOW (top, left, H, W) is the picture inside
+ *        it: all four even, H, W >= 2, top + H <= Hs, left + W <= Ws; luma (y, x) of the picture is luma (top + y, left + x) of the
+ *        surface and its chroma sample (y >> 1, x >> 1) is sample (top / 2 + (y >> 1), left / 2 + (x >> 1)).  A decoder's
+ *        surface is the window (0, 0, H, W); a region of interest is any other.  Each *_win function takes the arguments of its
+ *        tight twin and Hs, Ws, top, left next to H, W, and equals, bit for bit, the twin on the tight H x W copy of the window:
+ *          f_win(surface, ..., H, W, Hs, Ws, top, left)  ==  f(repack(surface), ..., H, W)
+ *        No byte of the surface outside the window takes part in a result.  Addresses come from the surface (frame stride
+ *        Hs Ws 3 / 2, row pitch Ws, plane offsets Hs Ws and (Hs / 2)(Ws / 2)); clamps, scales, marker and crop geometry, grids and
+ *        LDS sizes come from H and W: every limit the twin states for H and W holds for the window (W <= 6000 for the samplers
+ *        and the ingest, W <= 8192 and H <= 65534 for the overlay, H <= 131070 for yuv_to_rgb).  The surface's first byte obeys
+ *        the twin's alignment rule; the window starts wherever it starts.  Ws <= CSTS_YUV_MAX_WS.  A bad window -- an odd value,
+ *        H or W below 2, a window that leaves the surface, Ws over the limit -- returns -1 before any launch.  The tight entry
+ *        points are the *_win ones at Hs = H, Ws = W, top = left = 0: one kernel each.
+ *        csts_gaze_overlay_yuv_win: out is a surface like frames_yuv, (N, Hs * 3 / 2, Ws).  Its window is csts_gaze_overlay_yuv of
+ *        the window (the per-pixel luma rule, the per-block chroma rule); every byte outside the window equals the byte of
+ *        frames_yuv.  In place (out == frames_yuv) the bytes outside are not written at all; otherwise, unless the window is the
+ *        whole surface, the surface is first copied (one device-to-device copy on `stream`) and the window drawn in place on the copy.
+ *        csts_yuv_to_rgb_win: out is the tight (N, H, W, 3). */
 enum { CSTS_YUV_NV12 = 1, CSTS_YUV_I420 = 2 };
 enum { CSTS_YUV_BT601 = 0, CSTS_YUV_BT709 = 1 };
+#define CSTS_YUV_MAX_WS 32768
 int csts_rgb_to_yuv(const uint8_t* frames_nhwc, uint8_t* out_yuv, int64_t N, int H, int W, int layout, int matrix, int full_range,
                     hipStream_t stream);
 int csts_rgb_to_yuv_host(const uint8_t* frames_nhwc, uint8_t* out_yuv, int64_t N, int H, int W, int layout, int matrix,
@@ -648,6 +670,16 @@ int csts_clip_sample_yuv(const uint8_t* video_yuv, int64_t N, const int* frames_
 int csts_batch_sample_yuv(const uint8_t* arena_u8, int64_t arena_bytes, const int64_t* clips, const int* frames_idx,
                           const int* params, float* out, int B, int T, int S, int max_W, const float mean[3], const float std[3],
                           int layout, int matrix, int full_range, hipStream_t stream);
+int csts_yuv_to_rgb_win(const uint8_t* frames_yuv, uint8_t* out_nhwc, int64_t N, int H, int W, int Hs, int Ws, int top, int left,
+                        int layout, int matrix, int full_range, hipStream_t stream);
+int csts_yuv_to_rgb_win_host(const uint8_t* frames_yuv, uint8_t* out_nhwc, int64_t N, int H, int W, int Hs, int Ws, int top, int left,
+                             int layout, int matrix, int full_range);
+int csts_spatial_sample_yuv_win(const uint8_t* frames_yuv, const int* params, float* out, int B, int T, int H, int W, int Hs, int Ws,
+                                int top, int left, int S, const float mean[3], const float std[3], int layout, int matrix,
+                                int full_range, hipStream_t stream);
+int csts_clip_sample_yuv_win(const uint8_t* video_yuv, int64_t N, const int* frames_idx, const int* params, float* out, int B, int T,
+                             int H, int W, int Hs, int Ws, int top, int left, int S, const float mean[3], const float std[3],
+                             int layout, int matrix, int full_range, hipStream_t stream);
 
 /* ---- audio at any sample rate (csts_amd/csrc/resample.hip, csts_amd/inputs.py::resample_audio): band-limited resampling by the
  *      rational ratio up / down (reduced: gcd 1), the step the reference does offline with ffmpeg (data/preprocess.py::
@@ -818,6 +850,10 @@ int csts_gaze_overlay(const uint8_t* frames_nhwc, const float* rescaled, const i
 int csts_gaze_overlay_yuv(const uint8_t* frames_yuv, const float* rescaled, const int* centers, const int* params, uint8_t* out,
                           int64_t N, int H, int W, int S, int mh, int mw, float alpha, int radius, int layout, int matrix,
                           int full_range, hipStream_t stream);
+/* the same on the window of a decoder surface ("Decoder surfaces" above): frames_yuv and out (N, Hs * 3 / 2, Ws) */
+int csts_gaze_overlay_yuv_win(const uint8_t* frames_yuv, const float* rescaled, const int* centers, const int* params, uint8_t* out,
+                              int64_t N, int H, int W, int Hs, int Ws, int top, int left, int S, int mh, int mw, float alpha,
+                              int radius, int layout, int matrix, int full_range, hipStream_t stream);
 
 /* ---- gaze overlay of a group (csts_amd/csrc/overlay.hip, csts_amd.GazeLiveGroup): the frames several streams pushed in one tick,
  *      each stream of its own H x W, drawn by ONE launch from a job table, and their marker centres by one more.
@@ -965,6 +1001,7 @@ int csts_attention_rescale(const float* mixed, const int* valid, int nmaps_per_f
  *        csts_clip_sample(...)[0, :, 0] of that frame bit for bit.  A chunk frame no pair names is not read and no other slot is
  *        written.  A pair with the frame outside [0, K) or the slot outside [0, R) writes nothing; bad params give a NaN slot.  No
  *        byte at or past the end of the chunk is read; chunk and ring 16-byte aligned, W <= 6000, 1 <= npairs <= 65535.
+ *        stream_ingest_yuv_win: the chunk is (K, Hs * 3 / 2, Ws) and its frames are the windows ("Decoder surfaces" above).
  *      stream_gather: out fp32 (B, 3, T, S, S), out[b][:, t] = ring[slots[b][t]]; slots int32 [B][T]; a slot outside [0, R) gives
  *        a NaN frame and reads nothing.  T <= 64, B <= 65535. */
 int csts_stream_stft(const float* buf, int64_t s_base, int64_t m, int64_t n_total, int64_t f0, int64_t f1, float* ring, int ring_cols,
@@ -976,6 +1013,9 @@ int csts_stream_ingest(const uint8_t* chunk_khwc, int K, int H, int W, const int
 int csts_stream_ingest_yuv(const uint8_t* chunk_yuv, int K, int H, int W, const int* pairs, int npairs, const int* params, float* ring,
                            int R, int S, const float mean[3], const float std[3], int layout, int matrix, int full_range,
                            hipStream_t stream);
+int csts_stream_ingest_yuv_win(const uint8_t* chunk_yuv, int K, int H, int W, int Hs, int Ws, int top, int left, const int* pairs,
+                               int npairs, const int* params, float* ring, int R, int S, const float mean[3], const float std[3],
+                               int layout, int matrix, int full_range, hipStream_t stream);
 int csts_stream_gather(const float* ring, int R, const int* slots, float* out, int B, int T, int S, hipStream_t stream);
 
 /* ---- stream group (csts_amd/csrc/stream.hip, csts_amd.GazeStreamGroup): N streams share one arena of crop rings, fp32

@@ -49,6 +49,11 @@ with a pixel_format entry ("nv12" or "i420") and optionally yuv_matrix ("bt601",
 overlay / live_overlay are then drawn in that format, uint8 (N, H * 3 / 2, W) (GazePredictor.render_track(out_format=...)), --out
 gains the entry overlay_pixel_format, and --overlay-dir writes its PNGs from inputs.yuv_to_rgb_host of them.  An npz holding both
 frames_u8 and frames_yuv is an error.  The json_stats line then carries "pixel_format".
+Decoder surfaces: frames_yuv may hold padded surfaces (..., Hs * 3 / 2, Ws) -- a row pitch and a coded height larger than the
+picture -- with the entry yuv_window int (4,) = (top, left, H, W), the picture inside them (csts_amd.inputs.check_window);
+--yuv-window TOP LEFT H W overrides the entry.  Both need frames_yuv.  The surfaces are uploaded as they are and read in place; the
+result is that of the repacked pictures (inputs.yuv_window).  --out and the json_stats line carry yuv_window; an RGB overlay and
+the --overlay-dir PNGs show the window, a 4:2:0 overlay has the surfaces' shape.  --videos takes tight pictures only.
 --stream [--chunk K] (with --video): the recording is replayed through csts_amd.GazeStream (GazePredictor.stream) in pushes of K
 frames (default 8) with the matching audio -- the samples up to frame_end * 24000 / fps, the rest with the last push -- as a live
 source would deliver it, and closed.  --out receives the same entries as --video, the track folded from the emitted windows by
@@ -123,6 +128,8 @@ def parse_args(argv=None):
                    help="colour matrix of frames_yuv (default: the npz entry yuv_matrix, else bt601)")
     p.add_argument("--yuv-full-range", default=None, type=int, choices=[0, 1],
                    help="1: frames_yuv is full range, 0: limited (default: the npz entry yuv_full_range, else limited)")
+    p.add_argument("--yuv-window", default=None, nargs=4, type=int, metavar=("TOP", "LEFT", "H", "W"),
+                   help="the picture inside the padded surfaces of frames_yuv (default: the npz entry yuv_window, else the whole)")
     p.add_argument("--stream", action="store_true", help="with --video: replay the recording through GazePredictor.stream")
     p.add_argument("--chunk", default=None, type=int, help="with --stream: frames per push (default 8)")
     p.add_argument("--live", default=None, choices=["hold", "linear"],
@@ -188,9 +195,10 @@ def parse_args(argv=None):
                 "track, with --overlay onto the frames as they arrive)")
     if args.sample_rate is not None and args.sample_rate < 1:
         p.error("--sample-rate must be positive")
-    if (args.pixel_format or args.yuv_matrix or args.yuv_full_range is not None) and args.video is None and args.clip is None \
-            and args.videos is None:
-        p.error("--pixel-format, --yuv-matrix and --yuv-full-range describe recorded pictures: they need --clip or --video")
+    if (args.pixel_format or args.yuv_matrix or args.yuv_full_range is not None or args.yuv_window is not None) \
+            and args.video is None and args.clip is None and args.videos is None:
+        p.error("--pixel-format, --yuv-matrix, --yuv-full-range and --yuv-window describe recorded pictures: they need --clip or "
+                "--video")
     if args.sample_rate is not None and args.video is None and args.clip is None and args.videos is None:
         p.error("--sample-rate is the rate of a recorded waveform: it needs --clip or --video")
     return args
@@ -210,16 +218,26 @@ def source_rate(z, args, path):
 
 def pictures(z, args, path, lead):
     """The pictures of an opened npz (numpy) and the keywords that name their format ({} for frames_u8, packed RGB): frames_yuv
-    with pixel_format [, yuv_matrix, yuv_full_range], each overridden by its flag.  lead: 1 for a video (N, ...), 2 for a clip."""
+    with pixel_format [, yuv_matrix, yuv_full_range, yuv_window], each overridden by its flag.  lead: 1 for a video (N, ...), 2 for
+    a clip."""
     from csts_amd.datasets import clip_pictures
     if "frames_yuv" not in z.files and (args.pixel_format or args.yuv_matrix or args.yuv_full_range is not None):
         raise SystemExit(f"{path} holds no frames_yuv: --pixel-format, --yuv-matrix and --yuv-full-range describe 4:2:0 pictures")
+    if "frames_yuv" not in z.files and (args.yuv_window is not None or "yuv_window" in z.files):
+        raise SystemExit(f"{path} holds no frames_yuv: --yuv-window and the entry yuv_window name the picture inside 4:2:0 surfaces")
     try:
         frames, _, _, fmt = clip_pictures(z, path, args.pixel_format, args.yuv_matrix,
                                           None if args.yuv_full_range is None else bool(args.yuv_full_range), lead=lead)
     except ValueError as e:
         raise SystemExit(str(e))
     kw = {} if fmt[0] == "rgb24" else {"pixel_format": fmt[0], "matrix": fmt[1], "full_range": fmt[2]}
+    window = args.yuv_window if args.yuv_window is not None else (z["yuv_window"] if "yuv_window" in z.files else None)
+    if window is not None:
+        window = np.asarray(window).reshape(-1).tolist()
+        try:
+            kw["window"] = inputs.check_window(frames.shape, fmt[0], window)
+        except ValueError as e:
+            raise SystemExit(f"{path}: {e}")
     return frames, kw
 
 
@@ -324,6 +342,8 @@ def predict_group(args, predictor, dev):
                                  f"{(fps, rate, fmt)} differ from {args.videos[0]}'s {shared}")
             recordings.append((torch.from_numpy(pics).to(dev), waveform(z, rate, dev)))
     fps, rate, fmt = shared
+    if "window" in fmt:
+        raise SystemExit("--videos serves tight 4:2:0 pictures only: yuv_window / --yuv-window belong to --video and --clip")
     chunk = 8 if args.chunk is None else args.chunk
     try:
         done = replay_group(predictor, recordings, fps, args.stride, chunk, args.batch, fmt, rate)
@@ -447,6 +467,8 @@ def main(argv=None):
             arrays.update({"live_" + k: out["live"][k].cpu().numpy() for k in live_keys})
         if args.overlay_format is not None:
             arrays["overlay_pixel_format"] = np.array(args.overlay_format)
+        if "window" in fmt:
+            arrays["yuv_window"] = np.asarray(fmt["window"], dtype=np.int64)
         np.savez(args.out, **arrays, **rates)
         if args.overlay_dir is not None:
             write_pngs(arrays["live_overlay" if args.live is not None else "overlay"], args.overlay_dir, args.overlay_every,
@@ -459,6 +481,8 @@ def main(argv=None):
         record.update({k: int(v) for k, v in rates.items()})
         if fmt:
             record["pixel_format"] = fmt["pixel_format"]
+        if "window" in fmt:
+            record["yuv_window"] = list(fmt["window"])
         if args.fill is not None:
             record.update({"fill": args.fill, "max_gap": int(out["max_gap"]), "filled_frames": int(arrays["filled"].sum())})
         if args.stream:
@@ -496,12 +520,16 @@ def main(argv=None):
         keys += ("audio_attention", "audio_attention_mean", "attention_maps", "attention_range", "temporal_attention")
     arrays = {k: out[k].cpu().numpy() for k in keys}
     rates = {} if rate is None else {"sample_rate": np.int64(rate), "audio_rate": np.int64(AUDIO_RATE)}
+    if "window" in fmt:
+        arrays["yuv_window"] = np.asarray(fmt["window"], dtype=np.int64)
     np.savez(args.out, **arrays, **rates)
     record = {"_type": "predict", "checkpoint": predictor.checkpoint_path, "source": source, "graph": predictor.graph,
               "out": args.out, "shapes": {k: list(v.shape) for k, v in arrays.items()}}
     record.update({k: int(v) for k, v in rates.items()})
     if fmt:
         record["pixel_format"] = fmt["pixel_format"]
+    if "window" in fmt:
+        record["yuv_window"] = list(fmt["window"])
     print("json_stats: " + json.dumps(record), flush=True)
 
 
