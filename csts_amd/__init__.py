@@ -12,6 +12,7 @@ from .infer import fill_track, fill_plan, default_max_gap, fill_attention_track,
 from .stream import GazeStream, plan_stream, stream_window, stream_schedule, track_from_windows  # noqa: F401
 from .stream import stream_live_schedule, live_ring_slots, GazeStreamGroup, group_schedule  # noqa: F401
 from .stream import GazeLiveGroup, group_live_schedule  # noqa: F401
+from .stream import default_attention_age, attention_ring_slots, live_attention_schedule, attention_track_from_windows  # noqa: F401
 from .ops import gaze_overlay, gaze_overlay_yuv, jet_table, audio_pixel_attn, attention_track, attention_rescale  # noqa: F401
 from .ops import group_gaze_overlay, group_points_source  # noqa: F401
 
@@ -21,4 +22,5 @@ __all__ = ["MODEL_REGISTRY", "build_model", "get_cfg", "load_yaml", "assert_and_
            "jet_table", "audio_pixel_attn", "attention_track", "attention_rescale", "fill_attention_track",
            "default_attention_gap", "GazeStream", "plan_stream", "stream_window", "stream_schedule", "track_from_windows",
            "stream_live_schedule", "live_ring_slots", "GazeStreamGroup", "group_schedule",
-           "GazeLiveGroup", "group_live_schedule", "overlay_group_table", "group_gaze_overlay", "group_points_source"]
+           "GazeLiveGroup", "group_live_schedule", "overlay_group_table", "group_gaze_overlay", "group_points_source",
+           "default_attention_age", "attention_ring_slots", "live_attention_schedule", "attention_track_from_windows"]

@@ -15,6 +15,12 @@
 //   apt_accumulate_kernel  one workgroup per (output frame f, head or head mean): walks the frame's pair list, the sum in LDS
 //                          cells each thread owns, then the mean;
 //   apa_rescale_kernel     one workgroup per (f, g): the map into LDS, lattice extrema, rescaled map and range out.
+// The live attention ring (csts_live_attention_add / csts_live_attention_rows, GazeStream(live=..., attention=True)) holds that
+// track's per-frame sums for the frames a running stream still shows: frame t in slot t mod Ra.
+//   live_attention_add_kernel   one workgroup per ring slot: the pairs of newly run windows that land on the slot's frame, added
+//                               by apa_pair_cell in ascending p -- apt_accumulate_kernel's sum, carried from call to call;
+//   live_attention_rows_kernel  one workgroup per (pushed frame, g): the newest frame at most max_age back that holds a map, its
+//                               mean into LDS, then apa_lattice_range / apa_rescale_store as apa_rescale_kernel runs them.
 #include "common.h"
 
 namespace {
@@ -222,6 +228,128 @@ __global__ __launch_bounds__(256) void apa_rescale_kernel(const float* __restric
   apa_rescale_store(m, lo, hi, HW, o, maps, range, tid);
 }
 
+// ---- live attention ring: sum (Ra, Hh + 1, HW) / count (Ra) / tag (Ra), the tag being the frame a slot holds (-1: empty).
+
+// grid (Ra), 256 threads.  Workgroup s OWNS slot s: its (Hh + 1) * HW cells, its count and its tag -- every lane reads tag and
+// count before the barrier, lane 0 writes them after the last cell (the hazard live_add_slot of stream.hip states: a slot split
+// over several workgroups would let one read the tag another has rewritten).  The pairs p = w T + j are walked in ascending p
+// and those with frames[p] = t >= 0, t mod Ra == s are taken by live_add_slot's rule: tag != t -> the slot restarts (sum =
+// 0.f + m_p, count 1, tag t); tag == t -> sum += m_p, count += 1; m_p = apa_pair_cell(.., g, .., apa_axis(j, T, T'), c), the
+// addend of apt_accumulate_kernel.  Two walks as there: the tags alone find the last restart (`start`, -1: the sum in the ring
+// is carried on), the final tag and count; then each thread adds, for its own cells, the pairs from there on that carry the
+// final tag.  frames[] is read by p alone: uniform loads.  VEC: HW % 4 == 0, a thread's 4 cells share g, 128-bit ring accesses.
+template <bool VEC>
+__global__ __launch_bounds__(256) void live_attention_add_kernel(const float* __restrict__ column, const int64_t* __restrict__ frames,
+                                                                 int P, int Hh, int Tp, int HW, int T, float* __restrict__ sum,
+                                                                 int* __restrict__ count, int64_t* __restrict__ tag, int Ra) {
+  const int tid = threadIdx.x, slot = blockIdx.x;
+  int64_t cur = tag[slot];
+  int cnt = count[slot], start = -1, hits = 0;
+  for (int p = 0; p < P; ++p) {
+    const int64_t t = frames[p];
+    if (t < 0 || (int)(t % Ra) != slot) continue;
+    ++hits;
+    if (t != cur) { cur = t; cnt = 1; start = p; } else { ++cnt; }
+  }
+  if (hits == 0) return;                                        // workgroup-uniform: it depends on the table alone
+  __syncthreads();                                              // every lane has read the old tag and count
+  const int first = start < 0 ? 0 : start;
+  const int cells = (Hh + 1) * HW;
+  const int64_t head_stride = (int64_t)Tp * HW;
+  float* dst = sum + (int64_t)slot * cells;
+  constexpr int V = VEC ? 4 : 1;
+  for (int at = tid * V; at < cells; at += 256 * V) {
+    const int g = at / HW, c = at - g * HW;
+    float acc[V];
+#pragma unroll
+    for (int q = 0; q < V; ++q) acc[q] = 0.f;
+    if (start < 0) {
+      if constexpr (VEC) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(dst + at);
+#pragma unroll
+        for (int q = 0; q < V; ++q) acc[q] = v[q];
+      } else {
+        acc[0] = dst[at];
+      }
+    }
+    for (int p = first; p < P; ++p) {
+      if (frames[p] != cur) continue;                           // from `start` on the slot's pairs all carry its final tag (>= 0)
+      const ApaAxis ax = apa_axis(p % T, T, Tp);
+      const float* cb = column + (int64_t)(p / T) * Hh * head_stride;
+#pragma unroll
+      for (int q = 0; q < V; ++q) acc[q] += apa_pair_cell(cb, g, Hh, head_stride, HW, ax, c + q);
+    }
+    if constexpr (VEC) {
+      f32x4 o;
+#pragma unroll
+      for (int q = 0; q < V; ++q) o[q] = acc[q];
+      *reinterpret_cast<f32x4*>(dst + at) = o;
+    } else {
+      dst[at] = acc[0];
+    }
+  }
+  if (tid == 0) { count[slot] = cnt; tag[slot] = cur; }
+}
+
+// grid (K, Hh + 1), 256 threads: workgroup (k, g) answers frame n = f0 + k.  It walks j = n .. max(0, n - max_age) for the first
+// slot whose tag is j and whose count is positive (workgroup-uniform: the ring is only read, by block index alone), stages
+// sum * (1.f / (float)count) -- apt_accumulate_kernel's mean -- in LDS and runs apa_rescale_kernel's two device functions on it.
+// Nothing found: mixed and maps 0, range NaN, out_frame -1, out_count 0.  mixed, maps + range, out_frame, out_count: NULL skips.
+template <bool VEC>
+__global__ __launch_bounds__(256) void live_attention_rows_kernel(const float* __restrict__ sum, const int* __restrict__ count,
+                                                                  const int64_t* __restrict__ tag, int Ra, int64_t f0, int h, int w,
+                                                                  int S, int max_age, float* __restrict__ mixed,
+                                                                  float* __restrict__ maps, float* __restrict__ range,
+                                                                  int64_t* __restrict__ out_frame, int* __restrict__ out_count) {
+  __shared__ __attribute__((aligned(16))) float m[APA_MAX_CELLS];
+  __shared__ ApaAxis ey[2 * APA_MAX_SIDE], ex[2 * APA_MAX_SIDE];
+  __shared__ float red[8];
+  const int tid = threadIdx.x;
+  const int HW = h * w, G = gridDim.y, g = blockIdx.y;
+  const int64_t k = blockIdx.x, n = f0 + k, o = k * G + g;
+  const int64_t lo_j = n - max_age > 0 ? n - max_age : 0;
+  int64_t found = -1;
+  int slot = 0, cnt = 0;
+  for (int64_t j = n; j >= lo_j; --j) {
+    const int s = (int)(j % Ra);
+    if (tag[s] == j && count[s] > 0) { found = j; slot = s; cnt = count[s]; break; }
+  }
+  if (g == 0 && tid == 0) {
+    if (out_frame) out_frame[k] = found;
+    if (out_count) out_count[k] = cnt;
+  }
+  if (found < 0) {
+    for (int c = tid; c < HW; c += 256) {
+      if (mixed) mixed[o * HW + c] = 0.f;
+      if (maps) maps[o * HW + c] = 0.f;
+    }
+    if (maps && tid == 0) { range[2 * o] = NAN; range[2 * o + 1] = NAN; }
+    return;
+  }
+  if (!mixed && !maps) return;
+  const float inv = 1.f / (float)cnt;
+  const float* src = sum + ((int64_t)slot * G + g) * HW;
+  if constexpr (VEC) {
+    for (int c = tid * 4; c < HW; c += 1024) {
+      f32x4 v = *reinterpret_cast<const f32x4*>(src + c);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] *= inv;
+      *reinterpret_cast<f32x4*>(m + c) = v;
+      if (mixed) *reinterpret_cast<f32x4*>(mixed + o * HW + c) = v;
+    }
+  } else {
+    for (int c = tid; c < HW; c += 256) {
+      const float v = src[c] * inv;
+      m[c] = v;
+      if (mixed) mixed[o * HW + c] = v;
+    }
+  }
+  if (!maps) return;
+  float lo, hi;
+  apa_lattice_range(m, ey, ex, red, h, w, S, tid, lo, hi);      // its first barrier orders the writes of m
+  apa_rescale_store(m, lo, hi, HW, o, maps, range, tid);
+}
+
 }  // namespace
 
 extern "C" int csts_audio_pixel_attn(const void* qkv, int dt, const float* lse, int B, int heads, int head_dim, int Tp, int h,
@@ -275,4 +403,44 @@ extern "C" int csts_attention_track(const float* column, const int* order, const
                      heads, Tp, h * w, T, mixed, count);
   CSTS_LAUNCH_CHECK();
   return csts_attention_rescale(mixed, count, heads + 1, F, h, w, S, maps, range, stream);
+}
+
+extern "C" int csts_live_attention_add(const float* column, const int64_t* frames_idx, int Wn, int heads, int Tp, int h, int w, int T,
+                                       float* sum, int* count, int64_t* frame, int Ra, hipStream_t stream) {
+  CSTS_REQUIRE(column && frames_idx && sum && count && frame, "bad args (no pointer may be NULL)");
+  CSTS_REQUIRE(column != sum, "column must not be the ring's sum");
+  CSTS_REQUIRE(Wn >= 1 && heads >= 1 && heads <= 65534 && Ra >= 1 && Ra <= 65535, "Wn >= 1, 1 <= heads <= 65534, 1 <= Ra <= 65535");
+  CSTS_REQUIRE(Tp >= 1 && h >= 1 && w >= 1 && h <= APA_MAX_SIDE && w <= APA_MAX_SIDE && (int64_t)h * w <= APA_MAX_CELLS,
+               "1 <= h, w <= CSTS_AUDIO_PIXEL_MAX_SIDE and h * w <= CSTS_AUDIO_PIXEL_MAX_HW");
+  CSTS_REQUIRE(T >= 1 && T <= 65536 && Tp <= 65536 && (int64_t)Wn * T <= 65535, "1 <= T, T' <= 65536, Wn * T <= 65535");
+  CSTS_REQUIRE((int64_t)(heads + 1) * h * w < ((int64_t)1 << 31), "(heads + 1) * h * w must stay below 2^31");
+  const int HW = h * w;
+  const bool vec = HW % 4 == 0 && aligned16(column) && aligned16(sum);
+  if (vec) hipLaunchKernelGGL(live_attention_add_kernel<true>, dim3((unsigned)Ra), dim3(256), 0, stream, column, frames_idx, Wn * T,
+                              heads, Tp, HW, T, sum, count, frame, Ra);
+  else hipLaunchKernelGGL(live_attention_add_kernel<false>, dim3((unsigned)Ra), dim3(256), 0, stream, column, frames_idx, Wn * T,
+                          heads, Tp, HW, T, sum, count, frame, Ra);
+  CSTS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int csts_live_attention_rows(const float* sum, const int* count, const int64_t* frame, int Ra, int64_t f0, int K, int heads,
+                                        int h, int w, int S, int max_age, float* mixed, float* maps, float* range,
+                                        int64_t* out_frame, int* out_count, hipStream_t stream) {
+  CSTS_REQUIRE(sum && count && frame, "bad args (the ring may not be NULL)");
+  CSTS_REQUIRE((maps == nullptr) == (range == nullptr), "maps and range come together: both or neither");
+  CSTS_REQUIRE(mixed != sum && maps != sum, "no output may be the ring");
+  CSTS_REQUIRE(Ra >= 1 && Ra <= 65535 && heads >= 1 && heads <= 65534 && K >= 1 && K <= 65535, "1 <= Ra, K <= 65535, 1 <= heads <= 65534");
+  CSTS_REQUIRE(h >= 1 && w >= 1 && h <= APA_MAX_SIDE && w <= APA_MAX_SIDE && (int64_t)h * w <= APA_MAX_CELLS,
+               "1 <= h, w <= CSTS_AUDIO_PIXEL_MAX_SIDE and h * w <= CSTS_AUDIO_PIXEL_MAX_HW (the map is staged in LDS)");
+  CSTS_REQUIRE(S >= 1 && S <= 65536 && f0 >= 0 && max_age >= 0 && max_age <= 65535, "1 <= S <= 65536, f0 >= 0, 0 <= max_age <= 65535");
+  if (!mixed && !maps && !out_frame && !out_count) return 0;
+  const bool vec = (h * w) % 4 == 0 && aligned16(sum) && (!mixed || aligned16(mixed));
+  const dim3 grid((unsigned)K, (unsigned)(heads + 1));
+  if (vec) hipLaunchKernelGGL(live_attention_rows_kernel<true>, grid, dim3(256), 0, stream, sum, count, frame, Ra, f0, h, w, S, max_age,
+                              mixed, maps, range, out_frame, out_count);
+  else hipLaunchKernelGGL(live_attention_rows_kernel<false>, grid, dim3(256), 0, stream, sum, count, frame, Ra, f0, h, w, S, max_age,
+                          mixed, maps, range, out_frame, out_count);
+  CSTS_LAUNCH_CHECK();
+  return 0;
 }

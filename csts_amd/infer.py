@@ -172,6 +172,23 @@ def default_attention_gap(plan):
 ATTENTION_TRACK_KEYS = ("attention_maps", "attention_range", "attention_mixed", "attention_count")
 
 
+def attention_grid(cfg, crop_size=None):
+    """(heads, T', h, w) of the spatial fusion block, whose attention predict(attention=True) shows, from the configuration alone:
+    the encoder's last head count (MVIT.NUM_HEADS through MVIT.HEAD_MUL) and the patch grid of a NUM_FRAMES x S x S clip divided
+    by every MVIT.POOL_Q_STRIDE; S = crop_size, default DATA.TEST_CROP_SIZE.  The shipped YAMLs at S = 256: (8, 4, 8, 8).  A
+    stream sizes its attention ring by it before any window has run."""
+    from .model import round_width
+    head_mul = {int(i): m for i, m in cfg.MVIT.HEAD_MUL}
+    heads = int(cfg.MVIT.NUM_HEADS)
+    for i in range(int(cfg.MVIT.DEPTH)):
+        heads = round_width(heads, head_mul.get(i, 1.0))
+    S = int(cfg.DATA.TEST_CROP_SIZE if crop_size is None else crop_size)
+    grid = [n // int(s) for n, s in zip((int(cfg.DATA.NUM_FRAMES), S, S), cfg.MVIT.PATCH_STRIDE)]
+    for row in cfg.MVIT.POOL_Q_STRIDE:
+        grid = [n // int(s) for n, s in zip(grid, row[1:])]
+    return (int(heads),) + tuple(int(n) for n in grid)
+
+
 def fill_attention_track(track, mode="linear", max_gap=None, plan=None, crop_size=None):
     """The attention track of predict_video(attention_track=True) with the frames between neighbouring hit frames filled, as
     fill_track fills the gaze track.  track: a dict with "attention_mixed" fp32 (N, heads + 1, h, w) and "attention_count" int32
@@ -562,7 +579,7 @@ class GazePredictor:
 
     def stream(self, fps=None, stride=None, segment=None, batch=1, max_chunk=32, pixel_format="rgb24", matrix="bt601",
                full_range=False, sample_rate=None, input_rate=None, live=None, max_gap=None, overlay=False, alpha=0.4, radius=5,
-               overlay_format=None, window=None):
+               overlay_format=None, window=None, attention=False, max_age=None, attention_overlay=None):
         """A live stream on this predictor (csts_amd.stream.GazeStream): push(frames, wav) takes frames and 24 kHz audio in whatever
         pieces they arrive and returns the windows each piece completes; close() ends it.  The windows are plan_stream's (fps an
         int or a Fraction, stride in frames); `batch` windows run per predict_batch call; `max_chunk` sizes the two device rings,
@@ -576,12 +593,18 @@ class GazePredictor:
         live="hold" | "linear" (forecast plans): push_live(frames, wav) also answers every pushed frame with its row of a gaze
         track computed from the windows that have run by then -- the forecast drawn on the frame it was made for, when that frame
         arrives -- filled at most max_gap frames apart (default: default_max_gap of the plan); overlay=True (needs live) adds
-        the frames drawn over with `alpha` and `radius` as render_track takes them.  GazeStream states the causal rule."""
+        the frames drawn over with `alpha` and `radius` as render_track takes them.  GazeStream states the causal rule.
+        attention=True: every window also carries the fusion attention maps of predict_batch(attention=True)
+        (stream.attention_track_from_windows folds them into predict_video(attention_track=True)'s format); with live= every
+        pushed frame is also answered with the newest attention map at most max_age frames old (default:
+        stream.default_attention_age of the plan), and attention_overlay="mean" | head index (needs overlay=True) adds the
+        frames with that map drawn over.  GazeStream states the rule."""
         from .stream import GazeStream
         return GazeStream(self, fps=fps, stride=stride, segment=segment, batch=batch, max_chunk=max_chunk,
                           pixel_format=pixel_format, matrix=matrix, full_range=full_range, sample_rate=sample_rate,
                           input_rate=input_rate, live=live, max_gap=max_gap, overlay=overlay, alpha=alpha, radius=radius,
-                          overlay_format=overlay_format, window=window)
+                          overlay_format=overlay_format, window=window, attention=attention, max_age=max_age,
+                          attention_overlay=attention_overlay)
 
     def stream_group(self, streams, fps=None, stride=None, segment=None, batch=4, max_chunk=32, pixel_format="rgb24",
                      matrix="bt601", full_range=False, input_rate=None, window=None):

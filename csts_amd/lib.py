@@ -318,6 +318,8 @@ SYMBOLS = {
     "csts_audio_pixel_attn": (_I, [vp, _I, vp, _I, _I, _I, _I, _I, _I, _I, _I, _F, vp, vp, vp, vp, vp]),
     "csts_attention_track": (_I, [vp, vp, vp, i64, _I, _I, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp]),
     "csts_attention_rescale": (_I, [vp, vp, _I, i64, _I, _I, _I, vp, vp, vp]),
+    "csts_live_attention_add": (_I, [vp, vp, _I, _I, _I, _I, _I, _I, vp, vp, vp, _I, vp]),
+    "csts_live_attention_rows": (_I, [vp, vp, vp, _I, i64, _I, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, vp]),
 }
 
 

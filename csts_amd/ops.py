@@ -3131,3 +3131,131 @@ def attention_rescale(mixed, crop_size, valid=None):
     L.check(_lib().csts_attention_rescale(_p(x), _p(v), G, F_, h, w, S, _p(out["maps"]), _p(out["range"]), _stream()),
             "csts_attention_rescale")
     return out
+
+
+# ----------------------------------------------------------------------------------------- live attention ring
+_LIVE_ATTENTION_OUTPUTS = ("mixed", "maps", "range", "frame", "count")
+
+
+def live_attention_ring(slots, heads, h, w, device):
+    """An empty attention ring of `slots` frames of heads + 1 maps of h x w on `device`: {"sum" fp32 (slots, heads + 1, h, w)
+    zeros, "count" int32 (slots,) zeros, "frame" int64 (slots,) -1, "newest": -1}.  Frame t lives in slot t mod slots
+    (include/csts_hip.h, live attention ring).  "newest" is a host int, the highest frame added so far: live_attention_add keeps
+    it, so that it can refuse a pair that would land on a slot holding a newer frame without reading the device."""
+    slots, heads, h, w = int(slots), int(heads), int(h), int(w)
+    if slots < 1 or slots > 65535 or heads < 1 or heads > 65534:
+        raise ValueError(f"an attention ring holds 1..65535 slots of 2..65535 maps, got {slots} slots and {heads} heads")
+    _attention_grid(h, w, "live_attention_ring")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.CstsError("the attention ring lives on MI355X only (there is no CPU fallback)")
+    return {"sum": torch.zeros(slots, heads + 1, h, w, dtype=torch.float32, device=device),
+            "count": torch.zeros(slots, dtype=torch.int32, device=device),
+            "frame": torch.full((slots,), -1, dtype=torch.int64, device=device), "newest": -1}
+
+
+def _check_attention_ring(ring):
+    """The tensors of an attention ring, checked: (sum, count, frame, Ra, heads, h, w)."""
+    try:
+        s, c, f, newest = ring["sum"], ring["count"], ring["frame"], ring["newest"]
+    except (KeyError, TypeError, IndexError):
+        raise ValueError("ring must be a dict with \"sum\", \"count\", \"frame\" and \"newest\" (ops.live_attention_ring)")
+    _need_gpu(s, c, f)
+    if s.dim() != 4 or s.dtype != torch.float32 or not s.is_contiguous() or s.shape[1] < 2:
+        raise ValueError(f"ring[\"sum\"] must be contiguous fp32 (Ra, heads + 1, h, w), got {tuple(s.shape)} {s.dtype}")
+    Ra, G, h, w = s.shape
+    if c.dtype != torch.int32 or tuple(c.shape) != (Ra,) or not c.is_contiguous():
+        raise ValueError(f"ring[\"count\"] must be contiguous int32 ({Ra},), got {tuple(c.shape)} {c.dtype}")
+    if f.dtype != torch.int64 or tuple(f.shape) != (Ra,) or not f.is_contiguous():
+        raise ValueError(f"ring[\"frame\"] must be contiguous int64 ({Ra},), got {tuple(f.shape)} {f.dtype}")
+    if isinstance(newest, bool) or not isinstance(newest, int):
+        raise ValueError(f"ring[\"newest\"] must be a host int (the highest frame added so far, -1: none), got {newest!r}")
+    if Ra < 1 or Ra > 65535 or G > 65535:
+        raise ValueError(f"an attention ring holds 1..65535 slots of 2..65535 maps, got {Ra} slots of {G} maps")
+    _attention_grid(h, w, "the attention ring")
+    return s, c, f, Ra, G - 1, h, w
+
+
+def live_attention_add(column, frames_idx, frames_host, ring, live_from=0):
+    """csts_live_attention_add: the audio_attention of the windows a step ran -- column fp32 (Wn, heads, T', h, w) -- and
+    frames_idx int64 (Wn, T) on the device, the video frame each window's input frame j shows, folded into the attention ring
+    (ops.live_attention_ring) in place.  Pair p = w T + j adds, for every head and the head mean, the map attention_track mixes
+    for it to the slot of frames_idx[w, j]: a slot whose frame tag differs restarts (sum = 0 + map, count 1, retagged), a slot
+    whose tag matches is added to and its count bumped, in ascending p -- the order and the arithmetic of ops.attention_track
+    when the windows come in the order they ran.  frames_host: the same (Wn, T) frames on the HOST (a numpy array or nested
+    sequence of ints; the stream has them from stream_window), so that what cannot be written is refused before the launch and
+    without a host sync:
+      a negative frame;
+      a frame t >= live_from + Ra, which would restart the slot of frame t - Ra >= live_from.  live_from: the lowest frame a row
+      still to come may read (its frame minus max_age);
+      a pair whose frame lies Ra or more below the highest frame added before it (ring["newest"], or an earlier pair of this
+      call): it could land on a slot that holds a NEWER frame and would wipe that frame out.
+    A refusal writes nothing.  One launch, no atomics, no host sync: the launch can be captured in a graph, but ring["newest"]
+    is host state set when this function runs: a replay of the graph does not move it, so the third refusal only tracks eager
+    calls, and a caller who replays keeps the two conditions themselves (stream.attention_ring_slots)."""
+    import numpy as np
+    _need_gpu(column, frames_idx)
+    s, c, f, Ra, heads, h, w = _check_attention_ring(ring)
+    if column.dim() != 5 or column.dtype != torch.float32 or tuple(column.shape[1:2] + column.shape[3:]) != (heads, h, w):
+        raise ValueError(f"column must be fp32 (Wn, {heads}, T', {h}, {w}), got {tuple(column.shape)} {column.dtype}")
+    Wn, _, Tp = column.shape[:3]
+    if frames_idx.dtype != torch.int64 or frames_idx.dim() != 2 or frames_idx.shape[0] != Wn:
+        raise ValueError(f"frames_idx must be int64 ({Wn}, T), got {tuple(frames_idx.shape)} {frames_idx.dtype}")
+    T = frames_idx.shape[1]
+    if Wn < 1 or T < 1 or Tp < 1 or Wn * T > 65535:
+        raise ValueError(f"live_attention_add takes 1..65535 (window, input frame) pairs a call, got {Wn} windows of {T}")
+    if not torch.is_tensor(frames_host):                         # a tensor is refused by _live_host_table, with its message
+        frames_host = np.asarray(frames_host)
+        if frames_host.shape != (Wn, T):
+            raise ValueError(f"frames_host must hold the ({Wn}, {T}) entries of frames_idx as integers on the host, got shape "
+                             f"{frames_host.shape}")
+        frames_host = frames_host.reshape(-1)
+    host = _live_host_table(frames_host, Wn * T, "frames_host", "frames_idx").reshape(Wn, T)
+    live_from = int(live_from)
+    if int(host.min()) < 0:
+        raise ValueError(f"frames must be frame numbers >= 0, got {int(host.min())}")
+    if int(host.max()) >= live_from + Ra:
+        t = int(host.max())
+        raise ValueError(f"the attention ring holds {Ra} frames: frame {t} would overwrite the slot of frame {t - Ra}, which is still "
+                         f"inside the live span (it starts at frame {live_from}); nothing was written")
+    flat = host.reshape(-1)
+    before = np.maximum.accumulate(np.concatenate([[int(ring["newest"])], flat]))      # [p]: the highest frame added before pair p
+    behind = np.nonzero(before[:-1] - flat >= Ra)[0]
+    if behind.size:
+        p = int(behind[0])
+        raise ValueError(f"the attention ring holds {Ra} frames: frame {int(flat[p])} (window row {p // T}) lies {int(before[p] - flat[p])} "
+                         f"below frame {int(before[p])}, which was added before it, and could land on the slot of a newer frame; "
+                         "nothing was written")
+    x = column.detach().contiguous()
+    L.check(_lib().csts_live_attention_add(_p(x), _p(frames_idx.contiguous()), Wn, heads, Tp, h, w, T, _p(s), _p(c), _p(f), Ra,
+                                           _stream()), "csts_live_attention_add")
+    ring["newest"] = int(before[-1])
+
+
+def live_attention_rows(ring, f0, K, crop_size, max_age, want=_LIVE_ATTENTION_OUTPUTS):
+    """csts_live_attention_rows: the attention rows of frames f0 .. f0 + K - 1 out of the attention ring, by the rule HOLD THE
+    NEWEST MAP.  With A = ops.attention_track of everything added so far (n_frames = n + 1) and g = the largest frame in
+    [max(0, n - max_age), n] with A["count"][g] > 0, row n is {"frame": g (int64, -1 when there is none), "count":
+    A["count"][g] (int32, 0), "mixed": A["mixed"][g], "maps": A["maps"][g], "range": A["range"][g]} -- (K,), (K,),
+    (K, heads + 1, h, w) twice and (K, heads + 1, 2) -- bit for bit, as long as no frame of [n - max_age, n] has been recycled
+    (live_attention_add's live_from).  A row without a g has zero maps and a NaN range.  crop_size: the S of the lattice the
+    extrema are taken on.  Returns the outputs named in `want`; the others are not computed (maps and range are computed
+    together).  The ring is only read.  One launch, no host sync: it can be captured in a graph."""
+    s, c, f, Ra, heads, h, w = _check_attention_ring(ring)
+    f0, K, S, max_age = int(f0), int(K), int(crop_size), int(max_age)
+    if f0 < 0 or K < 1 or K > 65535 or f0 + K >= 2 ** 62:
+        raise ValueError(f"live_attention_rows answers 1..65535 frames from f0 >= 0, got f0 {f0}, K {K}")
+    if max_age < 0 or max_age > 65535 or S < 1 or S > 65536:
+        raise ValueError(f"max_age must lie in 0..65535 and crop_size in 1..65536, got {max_age} and {S}")
+    f32 = torch.float32
+    table = (("mixed", (K, heads + 1, h, w), f32), ("maps", (K, heads + 1, h, w), f32), ("range", (K, heads + 1, 2), f32),
+             ("frame", (K,), torch.int64), ("count", (K,), torch.int32))
+    out = _wanted(want, _LIVE_ATTENTION_OUTPUTS, table, s.device)
+    pair = dict(out)                                             # the kernel writes maps and range together
+    if ("maps" in out) != ("range" in out):
+        pair.update(_wanted(("maps", "range"), _LIVE_ATTENTION_OUTPUTS, table, s.device))
+        pair.update(out)
+    L.check(_lib().csts_live_attention_rows(_p(s), _p(c), _p(f), Ra, f0, K, heads, h, w, S, max_age, _p(pair.get("mixed")),
+                                            _p(pair.get("maps")), _p(pair.get("range")), _p(pair.get("frame")), _p(pair.get("count")),
+                                            _stream()), "csts_live_attention_rows")
+    return out

@@ -7,7 +7,9 @@ window reads which frames and columns, and when it is ready -- is pure arithmeti
 ``stream_schedule``); the device side is the four kernels of csts_amd/csrc/stream.hip behind inputs.stream_stft,
 inputs.stream_audio_windows, inputs.stream_ingest and inputs.stream_gather.  With ``live=`` a forecast stream also answers
 every pushed frame with its row of a gaze track, out of a third ring (``stream_live_schedule``, ``live_ring_slots``;
-ops.live_track_add and ops.live_track_rows, the live-track kernels of stream.hip).  ``GazeStreamGroup`` serves several
+ops.live_track_add and ops.live_track_rows, the live-track kernels of stream.hip), and with ``attention=True`` as well with
+the newest fusion attention map, out of a fourth (``live_attention_schedule``, ``attention_ring_slots``;
+ops.live_attention_add and ops.live_attention_rows, fusion_maps.hip).  ``GazeStreamGroup`` serves several
 recordings at once: its slots share one arena of rings, a tick's frames and samples go in with one launch per stage
 (inputs.group_stft, inputs.group_ingest) and the windows of different slots that are ready together share a forward;
 ``group_schedule`` states on the host which windows share a batch.  ``GazeLiveGroup`` adds the live track to a group: the track
@@ -293,6 +295,94 @@ def track_from_windows(results, n_frames, want=("points", "peak", "count", "heat
     return track
 
 
+# ---- live attention: the attention track lands on the frames a window SAW, so a live row holds the newest map -----------------------
+
+def default_attention_age(plan):
+    """The default max_age of a live attention row: stride - 1 + max(0, observed - 1 - inputs[-1]).
+
+    Push the recording in step, frame n together with its 24000 / fps samples.  Window w (origin o = w * stride) needs frame
+    o + inputs[-1], and audio no further than the end of its observed span: its last centre column is at most c1 - 129 with
+    c1 = floor((o + observed) * cols_per_frame), so ready_samples < (o + observed) * 24000 / fps, which is in once frame
+    o + observed - 1 is.  It therefore runs in the step of a frame r(w) with  o + inputs[-1] <= r(w) <= o + max(inputs[-1],
+    observed - 1).  While window w is the last that ran, n <= r(w + 1) - 1, the newest frame with a map is o + inputs[-1] (every
+    earlier window ends lower), so a row's age is at most
+        r(w + 1) - 1 - (o + inputs[-1]) <= stride - 1 + max(0, observed - 1 - inputs[-1]),
+    and every frame from r(0) on finds a map.  Where inputs[-1] == observed - 1 -- both shipped forecast plans -- r(w) is exact,
+    frame r(w + 1) - 1 has exactly this age, and no smaller max_age serves: 63 on the Ego4D plan, 39 on the Aria one, stride - 1
+    whatever the stride.  (A window whose last input lies before the end of its observed span may run a little earlier than the
+    bound says; the default is then safe, not minimal.)"""
+    last, observed, stride = int(max(plan["inputs"])), int(plan["observed"]), int(plan["stride"])
+    return stride - 1 + max(0, observed - 1 - last)
+
+
+def attention_ring_slots(plan, max_chunk, max_age):
+    """The capacity Ra of the live attention ring (frame t in slot t mod Ra): max(inputs[-1] - inputs[0] - stride + 1,
+    max_chunk + max_age), at least 1.  Unlike the targets of the gaze ring, input frames do not ascend from window to window:
+    window w + 1's first input lies before window w's last.  Two conditions, both independent of how the recording is pushed:
+
+      a write never meets a NEWER frame in its slot.  Windows run in order and a window's pairs land in ascending frame order.
+              Everything written before window w (origin o) is at most o - stride + inputs[-1]; window w writes frames
+              >= o + inputs[0].  A write of frame t meets a newer frame t' only if t' = t + k Ra was written before, k >= 1, so
+              t' - t <= inputs[-1] - inputs[0] - stride: impossible iff  Ra > inputs[-1] - inputs[0] - stride.  Tight: windows
+              w - 1 and w write exactly frames that far apart.  Inside one window a later pair's frame is never lower.
+      a restart never recycles a frame some row still reads.  Take a step after which F frames are in; it took dk <= max_chunk
+              of them, and their rows are computed after the step's windows have been added.  Row n reads frames n - max_age .. n;
+              the rows of this step and of every later one belong to frames >= F - dk, so the lowest frame still read is
+              L = F - dk - max_age >= F - max_chunk - max_age.  A window runs once its last input frame is in, so every frame
+              written so far is <= F - 1, and writing t recycles t - Ra (and frames further back):
+              F - 1 - Ra < F - max_chunk - max_age  <=>  Ra >= max_chunk + max_age.
+              A window that runs LATE because its audio lags (the crop ring bounds how late: frames_max of ring_limits) only
+              makes F larger for the same writes; the frames it writes lie even further below F - 1.
+    The larger bound serves both.  Ego4D forecast plan, max_chunk 32, default max_age 63: max(0, 95) = 95 slots, 95 * 9 * 64
+    fp32 = 219 KB of 8 x 8 maps; stride 9, max_age 8: max(55, 40) = 55 slots."""
+    max_chunk, max_age = int(max_chunk), int(max_age)
+    if max_chunk < 1 or max_age < 0:
+        raise ValueError(f"max_chunk must be positive and max_age >= 0, got {max_chunk} and {max_age}")
+    spread = int(max(plan["inputs"])) - int(min(plan["inputs"])) - int(plan["stride"])
+    return max(1, spread + 1, max_chunk + max_age)
+
+
+def live_attention_schedule(plan, pushes, max_chunk=32, max_age=None, input_rate=None):
+    """The live attention of every frame of the given pushes, on the host: a list of (known, attention_frame), one pair per frame
+    in frame order.  known is stream_live_schedule's: the windows that have run when the frame's step finishes.  attention_frame
+    is the largest frame in [max(0, n - max_age), n] that is an input frame of one of the windows 0 .. known - 1
+    (stream_window's "frames_idx"), -1 when there is none: the frame whose map the live row of n holds.  It follows from
+    stream_steps and stream_window alone.  max_age: None takes default_attention_age(plan)."""
+    max_age = default_attention_age(plan) if max_age is None else int(max_age)
+    if max_age < 0:
+        raise ValueError(f"max_age must be >= 0, got {max_age}")
+    known = stream_live_schedule(plan, pushes, max_chunk=max_chunk, input_rate=input_rate)
+    seen, ran, out = set(), 0, []
+    for n, kn in enumerate(known):
+        for w in range(ran, kn):
+            seen.update(int(f) for f in stream_window(plan, w)["frames_idx"])
+        ran = max(ran, kn)
+        out.append((kn, next((g for g in range(n, max(0, n - max_age) - 1, -1) if g in seen), -1)))
+    return out
+
+
+def attention_track_from_windows(results, n_frames, crop_size):
+    """The windows a GazeStream(attention=True) emitted, folded into predict_video(attention_track=True)'s format by ONE
+    ops.attention_track call: results (a list of push() / close() results, in any grouping) -> {"attention_maps",
+    "attention_range", "attention_mixed", "attention_count" (infer.ATTENTION_TRACK_KEYS), "temporal_attention_windows" (windows,
+    n, n), "attention_crop_size"}.  crop_size: the S of the lattice (DATA.TEST_CROP_SIZE).  fill_attention_track and
+    render_attention_track work on it unchanged.  Input frames at or past n_frames are dropped."""
+    import numpy as np
+    import torch
+    from . import ops
+    results = list(results)
+    if not results:
+        raise ValueError("attention_track_from_windows needs at least one emitted window")
+    if any("audio_attention" not in r for r in results):
+        raise ValueError("attention_track_from_windows needs the windows' \"audio_attention\": open the stream with attention=True")
+    column = torch.stack([r["audio_attention"] for r in results], dim=0)
+    frames = np.stack([np.asarray(r["frames_idx"], dtype=np.int64) for r in results])
+    att = ops.attention_track(column, torch.from_numpy(frames).to(column.device), int(n_frames), frames.shape[1], int(crop_size))
+    return {"attention_maps": att["maps"], "attention_range": att["range"], "attention_mixed": att["mixed"],
+            "attention_count": att["count"], "temporal_attention_windows": torch.stack([r["temporal_attention"] for r in results]),
+            "attention_crop_size": int(crop_size)}
+
+
 # ---- the host rules of one stream: GazeStream follows them on its scalars, the groups on each slot's entries -------------------------
 
 def _open(s, predictor, fps, stride, segment, max_chunk, pixel_format, matrix, full_range, input_rate, window=None):
@@ -345,6 +435,40 @@ def check_live_args(plan, max_chunk, crop_size, fmt, live, max_gap, overlay, alp
     track_slots = live_ring_slots(plan, max_chunk, gap)
     side = int(crop_size) // 4                               # the model's heat maps are S/4 x S/4
     return gap, overlay_format, track_slots, track_slots * (side * side * 4 + 4 + 8)
+
+
+def check_attention_args(cfg, plan, max_chunk, crop_size, live, overlay, attention, max_age, attention_overlay):
+    """The attention arguments of GazeStream, checked as it documents them -> (max_age, head, attention_slots, attention_bytes,
+    (heads, h, w)); (None, False, 0, 0, None) unless both live and attention are on.  head: the `head` render_attention_track
+    takes for attention_overlay ("mean" -> None), False without an attention overlay.  attention_bytes counts the ring's fp32
+    sums plus a count and a frame tag per slot."""
+    from .infer import attention_grid
+    both = live is not None and bool(attention)
+    if max_age is not None and not both:
+        raise ValueError("max_age is the age up to which a live row holds the newest attention map: it needs live=\"hold\" or "
+                         "live=\"linear\" and attention=True")
+    if attention_overlay is not None and not both:
+        raise ValueError("attention_overlay draws the live attention onto the pushed frames: it needs live=\"hold\" or "
+                         "live=\"linear\" and attention=True")
+    if attention_overlay is not None and not overlay:
+        raise ValueError("attention_overlay belongs to the overlay: pass overlay=True")
+    if not both:
+        return None, False, 0, 0, None
+    age = default_attention_age(plan) if max_age is None else int(max_age)
+    if age < 0 or age > 65535:
+        raise ValueError(f"max_age must lie in 0..65535, got {max_age}")
+    heads, _, h, w = attention_grid(cfg, crop_size)
+    head = False
+    if attention_overlay is not None:
+        if attention_overlay == "mean":
+            head = None
+        elif isinstance(attention_overlay, bool) or not isinstance(attention_overlay, numbers.Integral) \
+                or not 0 <= int(attention_overlay) < heads:
+            raise ValueError(f"attention_overlay must be \"mean\" (the head mean) or a head index in [0, {heads}), got {attention_overlay!r}")
+        else:
+            head = int(attention_overlay)
+    slots = attention_ring_slots(plan, max_chunk, age)
+    return age, head, slots, slots * ((heads + 1) * h * w * 4 + 4 + 8), (heads, h, w)
 
 
 def check_piece(who, closed, hw, fmt, resampler, frames, wav):
@@ -435,11 +559,15 @@ def crop_audio(audio, S):
     return audio[:, :, :, :S, o:o + S].contiguous()
 
 
-def window_result(r, out, b, stream=None):
-    """The dict of one emitted window: r its stream_window, row b of predict_batch's `out`; a group names the slot in "stream"."""
+def window_result(r, out, b, stream=None, attention=False):
+    """The dict of one emitted window: r its stream_window, row b of predict_batch's `out`; a group names the slot in "stream".
+    attention: also row b of the attention entries of predict_batch(attention=True) (infer.ATTENTION_OUTPUTS)."""
     res = {} if stream is None else {"stream": stream}
     res.update({"window": r["window"], "frames_idx": r["frames_idx"], "target_idx": r["target_idx"], "points": out["points"][b],
                 "peak": out["peak"][b], "heatmaps": out["heatmaps"][b], "rescaled": out["rescaled"][b]})
+    if attention:
+        from .infer import ATTENTION_OUTPUTS
+        res.update({k: out[k][b] for k in ATTENTION_OUTPUTS})
     return res
 
 
@@ -452,20 +580,28 @@ def live_fields(rows, frame_idx, known):
     return rows
 
 
-def live_empty(side, device, hw=None, overlay=False, overlay_format=None, surface=None):
+def live_empty(side, device, hw=None, overlay=False, overlay_format=None, surface=None, attention=None, attention_overlay=False):
     """The live dict of a push without frames, K = 0: every field of push_live with its shape and dtype; with overlay the frames'
     shape at the stream's H x W (0 x 0 before the first frame), (0, H * 3 / 2, W) when overlay_format names a 4:2:0 layout --
-    (0,) + surface when the stream reads the windows of surfaces of that (Hs * 3 / 2, Ws)."""
+    (0,) + surface when the stream reads the windows of surfaces of that (Hs * 3 / 2, Ws).  attention: (heads, h, w) of a stream
+    with live attention, which adds the six attention entries behind "points_source"; attention_overlay: and the second overlay."""
     import torch
     shapes = {"frame_idx": ((0,), torch.int64), "known": ((0,), torch.int32), "points": ((0, 2), torch.float32),
               "peak": ((0,), torch.float32), "count": ((0,), torch.int32), "neighbours": ((0, 2), torch.int32),
               "filled": ((0,), torch.bool), "rescaled": ((0, side, side), torch.float32),
               "points_source": ((0, 2), torch.float64)}
+    if attention is not None:
+        heads, h, w = attention
+        shapes.update({"attention_frame": ((0,), torch.int64), "attention_count": ((0,), torch.int32),
+                       "attention_mixed": ((0, heads + 1, h, w), torch.float32), "attention_maps": ((0, heads + 1, h, w), torch.float32),
+                       "attention_range": ((0, heads + 1, 2), torch.float32), "attention_age": ((0,), torch.int64)})
     out = {k: torch.empty(shape, dtype=dt, device=device) for k, (shape, dt) in shapes.items()}
     if overlay:
         H, W = hw if hw is not None else (0, 0)
         shape = ((0,) + tuple(surface) if surface else (0, H * 3 // 2, W)) if overlay_format else (0, H, W, 3)
         out["overlay"] = torch.empty(shape, dtype=torch.uint8, device=device)
+        if attention is not None and attention_overlay:
+            out["attention_overlay"] = torch.empty(shape, dtype=torch.uint8, device=device)
     return out
 
 
@@ -533,12 +669,28 @@ class GazeStream:
     stream's source size, every window and live row equals that of a stream fed inputs.yuv_window of the same pushes, bit for
     bit; an RGB overlay is (K, H, W, 3) of the window, a 4:2:0 overlay has the surfaces' shape and equals them outside the window.
 
-    Out of scope: attention maps per streamed window, a delayed display for estimation plans, and equality with predict_video.
+    Attention (attention=True): every window runs predict_batch(attention=True) and its result also carries its rows of
+    "audio_attention", "audio_attention_mean", "attention_maps", "attention_range" and "temporal_attention"; the gaze entries
+    keep their bits, and attention_track_from_windows folds the emitted windows into predict_video(attention_track=True)'s
+    format.  With live= as well, push_live also answers every frame with the fusion attention.  That track lands on the frames a
+    window SAW, so when frame n arrives no window that shows n can have run and there are no two neighbours to fill between:
+    the live rule is HOLD THE NEWEST MAP.  With A = ops.attention_track(the audio_attention of results[:known(n)], their
+    frames_idx, n_frames = n + 1, T, S) and g the largest frame in [max(0, n - max_age), n] with A["count"][g] > 0, the row has
+    "attention_frame" = g (-1: none), "attention_count" = A["count"][g] (0), "attention_mixed", "attention_maps" and
+    "attention_range" = rows g of A (zero maps and a NaN range without a g) and "attention_age" = n - g (-1), bit for bit for
+    the same pushes.  max_age defaults to default_attention_age(plan).  The sums live in a fourth ring, fp32 (Ra, heads + 1, h,
+    w) with a count and a frame tag per slot, Ra = attention_ring_slots(plan, max_chunk, max_age) (95 slots, 219 KB on the
+    Ego4D forecast plan): ops.live_attention_add folds each step's windows in, ops.live_attention_rows reads the rows out.
+    attention_overlay="mean" | head index (needs overlay=True) adds "attention_overlay": render_attention_track of the pushed
+    frames with those rows and the gaze rows' points, in the overlay's format; a row without a map comes back byte for byte,
+    and "overlay" stays the gaze overlay.  With attention=False nothing changes and no launch is added.
+
+    Out of scope: a delayed display for estimation plans, attention in the stream groups, and equality with predict_video.
     sample_rate= still names the rate the audio is pushed at as it is, 24 kHz only."""
 
     def __init__(self, predictor, fps=None, stride=None, segment=None, batch=1, max_chunk=32, pixel_format="rgb24",
                  matrix="bt601", full_range=False, sample_rate=None, input_rate=None, live=None, max_gap=None, overlay=False,
-                 alpha=0.4, radius=5, overlay_format=None, window=None):
+                 alpha=0.4, radius=5, overlay_format=None, window=None, attention=False, max_age=None, attention_overlay=None):
         check_stream_rate(sample_rate)
         from . import inputs
         if input_rate is not None and sample_rate is not None:
@@ -554,12 +706,17 @@ class GazeStream:
             self.plan, self.max_chunk, self.S, self.fmt, live, max_gap, overlay, alpha, radius, overlay_format)
         if live is not None:
             self.capacity = dict(self.capacity, track_slots=self.track_slots, track_bytes=track_bytes)
+        self.attention = bool(attention)
+        self.max_age, self._attention_head, self.attention_slots, attention_bytes, self._attention_shape = check_attention_args(
+            predictor.cfg, self.plan, self.max_chunk, self.S, live, overlay, attention, max_age, attention_overlay)
+        if self.attention_slots:
+            self.capacity = dict(self.capacity, attention_slots=self.attention_slots, attention_bytes=attention_bytes)
         self.resampler = None if input_rate is None else inputs.StreamResampler(self.input_rate)
         self.input_samples = 0                               # source samples consumed (= samples without input_rate)
         self.frames = self.samples = self.cols = 0          # pushed so far; columns [0, cols) are final
         self.next_window, self.dropped, self.closed = 0, 0, False
         self.hw = self._surface = None                       # H x W of the pictures; (Hs * 3 / 2, Ws) under a window
-        self._crops = self._spec = self._tail = self._params = self._track = None
+        self._crops = self._spec = self._tail = self._params = self._track = self._attention_ring = None
         self._tail_base = 0                                  # the stream position of _tail[0]
 
     # ---- host arithmetic -------------------------------------------------------------------------------------------------------
@@ -610,8 +767,9 @@ class GazeStream:
             centers = np.stack([r["audio_centers"] for r in rows]).astype(np.int64)
             video = inputs.stream_gather(self._crops, torch.from_numpy(slots).to(dev))
             audio = inputs.stream_audio_windows(self._spec, self.cols - 1, torch.from_numpy(centers).to(dev), centers, AUDIO_WIDTH)
-            out = self.predictor.predict_batch({"video": video, "audio": crop_audio(audio, self.S)})
-            results += [window_result(r, out, i) for i, r in enumerate(group)]
+            batch = {"video": video, "audio": crop_audio(audio, self.S)}
+            out = self.predictor.predict_batch(batch, attention=True) if self.attention else self.predictor.predict_batch(batch)
+            results += [window_result(r, out, i, attention=self.attention) for i, r in enumerate(group)]
         self.next_window = windows[-1] + 1
         return results
 
@@ -645,6 +803,18 @@ class GazeStream:
         targets = np.concatenate([np.asarray(r["target_idx"], dtype=np.int64) for r in results])
         ops.live_track_add(maps, torch.from_numpy(targets).to(maps.device), targets, self._track,
                            live_from=max(0, f_start - self.max_gap + 1))
+        if self.attention:
+            column = torch.stack([r["audio_attention"] for r in results], dim=0)
+            frames = np.stack([np.asarray(r["frames_idx"], dtype=np.int64) for r in results])
+            ops.live_attention_add(column, torch.from_numpy(frames).to(column.device), frames, self._attention(column.device),
+                                   live_from=max(0, f_start - self.max_age))
+
+    def _attention(self, device):
+        """The attention ring, allocated when the first window is folded in or the first row asked for."""
+        from . import ops
+        if self._attention_ring is None:
+            self._attention_ring = ops.live_attention_ring(self.attention_slots, *self._attention_shape, device)
+        return self._attention_ring
 
     def _live_rows(self, f0, chunk):
         """The live rows of the step's frames f0 .. f0 + K - 1 (chunk: those frames as they were pushed)."""
@@ -660,9 +830,17 @@ class GazeStream:
         live_fields(rows, torch.arange(f0, f0 + K, dtype=torch.int64, device=dev),
                     torch.full((K,), self.next_window, dtype=torch.int32, device=dev))
         rows["points_source"] = points_to_source(rows["points"], self.predictor._video_params_row(*self.hw), self.S)
+        if self.attention:
+            att = ops.live_attention_rows(self._attention(dev), f0, K, self.S, self.max_age)
+            rows.update({"attention_" + k: att[k] for k in ("frame", "count", "mixed", "maps", "range")})
+            rows["attention_age"] = torch.where(att["frame"] >= 0, rows["frame_idx"] - att["frame"], torch.full_like(att["frame"], -1))
         if self.overlay:
             rows["overlay"] = self.predictor.render_track(chunk, rows, alpha=self.alpha, radius=self.radius,
                                                           out_format=self.overlay_format, **self.fmt)
+            if self._attention_head is not False:
+                rows["attention_overlay"] = self.predictor.render_attention_track(
+                    chunk, rows, head=self._attention_head, alpha=self.alpha, radius=self.radius, points=rows["points"],
+                    out_format=self.overlay_format, **self.fmt)
         return rows
 
     def _push(self, frames, wav, want_live):
@@ -697,7 +875,8 @@ class GazeStream:
                 return results, None
             if not rows:
                 dev = frames.device if frames is not None else (wav.device if wav is not None else self.predictor.device)
-                return results, live_empty(self.S // 4, dev, self.hw, self.overlay, self.overlay_format, self._surface)
+                return results, live_empty(self.S // 4, dev, self.hw, self.overlay, self.overlay_format, self._surface,
+                                           attention=self._attention_shape, attention_overlay=self._attention_head is not False)
             live = _cat_rows(rows)
         return results, live
 

@@ -1117,6 +1117,45 @@ int csts_group_live_rows(const float* sum, const int* count, const int64_t* fram
                          const int64_t* frame_of, int K, int H, int W, int mode, int max_gap, float* heatmaps, float* rescaled,
                          float* points, float* peak, int* out_count, int* neighbours, hipStream_t stream);
 
+/* ---- live attention ring (csts_amd/csrc/fusion_maps.hip, GazeStream(live=..., attention=True)): the whole-recording attention
+ *      track lands on the frames a window SAW, so when frame n arrives no window that shows n can have run: there is nothing to
+ *      fill between.  The live rule is HOLD THE NEWEST MAP: frame n shows the map of the newest frame at most max_age back that
+ *      some window that has run did see.  The per-frame sums of csts_attention_track live in a ring of Ra slots whose size does
+ *      not depend on the length of the stream: sum fp32 [Ra][heads + 1][h * w], count int32 [Ra], frame int64 [Ra] = the frame a
+ *      slot holds, -1 when empty; frame t lives in slot t mod Ra.  All in DEVICE memory.
+ *      live_attention_add: column [Wn][heads][T'][h * w] fp32 and frames_idx int64 [Wn][T] of the windows a step ran.  The pairs
+ *        p = w T + j are walked in ascending p, each adding m_p of csts_attention_track, for every g in [0, heads], to the slot
+ *        of t = frames_idx[p] by the rule of csts_live_track_add:
+ *          t < 0:                  the pair is skipped
+ *          frame[t mod Ra] != t:   the slot restarts: sum = 0.f + m_p, count = 1, frame = t
+ *          frame[t mod Ra] == t:   sum += m_p, count += 1
+ *        so a slot's sum is (((0 + m_p0) + m_p1) + ...) over the pairs that land on its frame, in the order of the calls and in
+ *        ascending p inside one: the sum of csts_attention_track over the windows added so far, in the order they ran.  ONE
+ *        workgroup owns a whole slot -- all (heads + 1) h w cells, the count and the tag: plain loads and stores, no atomics.  A
+ *        slot no pair names is not touched.  Input frames do not ascend from window to window (window w + 1's first input lies
+ *        before window w's last), so the caller keeps two conditions (csts_amd.ops.live_attention_add refuses what breaks them,
+ *        csts_amd.attention_ring_slots sizes the ring for them): a pair never lands on a slot that holds a NEWER frame, and
+ *        never on one whose frame is still to be read.  1 <= Wn T <= 65535, 1 <= Ra <= 65535, h, w as csts_attention_track.
+ *      live_attention_rows: the K frames n = f0 .. f0 + K - 1; grid (K, heads + 1).  With c(t) = count[t mod Ra] when
+ *        frame[t mod Ra] == t, else 0:
+ *          g*           = the largest t in [max(0, n - max_age), n] with c(t) > 0
+ *          out_frame[k] = g*, or -1 when there is none;  out_count[k] = c(g*), or 0
+ *          mixed[k][g]  = sum[g* mod Ra][g] * (1.f / (float)c(g*)): the mean of csts_attention_track
+ *          maps[k][g], range[k][g] = csts_attention_rescale of mixed[k][g], by its device functions
+ *          none:          mixed and maps 0, range (NaN, NaN)
+ *        Row n therefore equals rows g* of csts_attention_track over everything added so far (F = n + 1), bit for bit, as long
+ *        as no frame of [n - max_age, n] has been recycled.  mixed, maps [K][heads + 1][h * w], range [K][heads + 1][2] fp32,
+ *        out_frame [K] int64, out_count [K] int32; each may be NULL and is then skipped, except that maps and range come
+ *        together; with all NULL nothing is launched.  The ring is only read.  f0 >= 0, 1 <= K <= 65535, 0 <= max_age <= 65535.
+ *      128-bit accesses when h * w is a multiple of 4 and the buffers are 16-byte aligned.  One launch each; no allocation, no
+ *      synchronisation, no host read: graph-capturable.  Both refuse (-1) before the launch and need no GPU to do so.  Added
+ *      entry points leave CSTS_ABI_VERSION as it is: no existing signature or struct changes. */
+int csts_live_attention_add(const float* column, const int64_t* frames_idx, int Wn, int heads, int Tp, int h, int w, int T, float* sum,
+                            int* count, int64_t* frame, int Ra, hipStream_t stream);
+int csts_live_attention_rows(const float* sum, const int* count, const int64_t* frame, int Ra, int64_t f0, int K, int heads, int h,
+                             int w, int S, int max_age, float* mixed, float* maps, float* range, int64_t* out_frame, int* out_count,
+                             hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,8 +61,15 @@ csts_amd.track_from_windows, plus stream_windows (the window numbers, in the ord
 json_stats line gains "stream", "chunk" and "dropped".  A recording at another rate (sample_rate entry or --sample-rate) is pushed
 at that rate, int16 and (C, n) as stored -- the samples up to frame_end * rate / fps -- and resampled inside the stream with the
 filter state carried from push to push (GazePredictor.stream(input_rate=rate)); --out records sample_rate and audio_rate as the
-offline path does.  --fps must then be integral (a stream places its audio by the exact ratio of columns to frames); --overlay,
---fill and the attention flags are not part of the stream.
+offline path does.  --fps must then be integral (a stream places its audio by the exact ratio of columns to frames); --overlay
+(without --live), --fill and --attention are not part of the stream.
+--stream --attention-track: the stream runs with attention=True and --out also receives the attention track entries of
+--attention-track, folded from the emitted windows by csts_amd.attention_track_from_windows.  With --live it also receives
+live_attention_frame (N,) int64 (the frame whose map a row holds, -1: none), live_attention_count (N,), live_attention_maps
+(N, heads + 1, h, w) and live_attention_range (N, heads + 1, 2): the newest map at most default_attention_age(plan) frames old
+(GazeStream states the rule), and with --overlay --attention-overlay HEAD|mean live_attention_overlay, the frames with that map
+drawn over as they arrived.  What the stream refuses (--attention-overlay without --live and --overlay) is refused with its
+message.
 --videos A.npz B.npz ... --stream [--chunk K] [--batch B]: the recordings are replayed as the slots of ONE csts_amd.GazeStreamGroup
 (GazePredictor.stream_group(len(videos), batch=B)): every tick pushes the next K frames of every recording that still has some,
 with the samples that belong to them, cut exactly as --video --stream cuts one recording; a recording that ends is closed.  The
@@ -188,9 +195,8 @@ def parse_args(argv=None):
         p.error("--chunk must be positive")
     if args.live is not None and not args.stream:
         p.error("--live answers the frames of a replayed stream: it needs --stream")
-    offline_extras = args.fill or args.attention_track or args.attention_overlay is not None
-    if args.stream and (offline_extras or ((args.overlay or args.overlay_dir) and args.live is None)):
-        p.error("--stream emits windows as they complete: --overlay, --fill and the attention flags are not part of it (fold the "
+    if args.stream and (args.fill or ((args.overlay or args.overlay_dir) and args.live is None)):
+        p.error("--stream emits windows as they complete: --overlay and --fill are not part of it (fold the "
                 "windows with csts_amd.track_from_windows, then fill_track / render_track; --live hold|linear draws the live "
                 "track, with --overlay onto the frames as they arrive)")
     if args.sample_rate is not None and args.sample_rate < 1:
@@ -248,15 +254,18 @@ def waveform(z, rate, dev):
 
 
 def replay_stream(predictor, frames, wav, fps, stride, chunk, fmt, rate=None, live=None, max_gap=None, overlay=False,
-                  overlay_format=None):
+                  overlay_format=None, attention=False, attention_overlay=None):
     """The recording pushed through GazePredictor.stream in pushes of `chunk` frames with the matching audio, then closed ->
     (the track by track_from_windows with "windows" = their number, the window numbers in emission order, the dropped count).
     rate: the rate wav, (n,) or (C, n), was recorded at; the stream resamples it (input_rate).  live "hold" | "linear": the pushes
-    go through push_live and the track gains "live" = the rows of all N frames (GazeStream.push_live's dict) and "live_max_gap"."""
+    go through push_live and the track gains "live" = the rows of all N frames (GazeStream.push_live's dict) and "live_max_gap".
+    attention: the stream runs with attention=True and the track gains attention_track_from_windows' entries; attention_overlay
+    ("mean" or a head index) is the stream's."""
     from fractions import Fraction
-    from csts_amd import track_from_windows
+    from csts_amd import attention_track_from_windows, track_from_windows
+    more = {"attention": True, "attention_overlay": attention_overlay} if attention else {}
     stream = predictor.stream(fps=fps, stride=stride, input_rate=rate, live=live, max_gap=max_gap, overlay=overlay,
-                              overlay_format=overlay_format, **fmt)
+                              overlay_format=overlay_format, **more, **fmt)
     N, n = frames.shape[0], wav.shape[-1]
     per = Fraction(AUDIO_RATE if rate is None else rate) / stream.plan["fps"]     # samples per frame
     results, rows, sent = [], [], 0
@@ -276,6 +285,8 @@ def replay_stream(predictor, frames, wav, fps, stride, chunk, fmt, rate=None, li
         raise SystemExit(f"the stream of {N} frames and {n} samples completed no window (one window observes "
                          f"{stream.plan['observed']} frames)")
     track = track_from_windows(results, N)
+    if attention:
+        track.update(attention_track_from_windows(results, N, stream.S))
     if live is not None:
         track["live"] = {k: torch.cat([r[k] for r in rows], dim=0) for k in rows[0]}
         track["live_max_gap"] = stream.max_gap
@@ -440,7 +451,10 @@ def main(argv=None):
                     out, stream_windows, dropped = replay_stream(predictor, frames, waveform(z, rate, dev), fps, args.stride,
                                                                  8 if args.chunk is None else args.chunk, fmt, rate, live=args.live,
                                                                  max_gap=args.max_gap, overlay=bool(args.overlay or args.overlay_dir),
-                                                                 overlay_format=args.overlay_format)
+                                                                 overlay_format=args.overlay_format, attention=attention_track,
+                                                                 attention_overlay=args.attention_overlay
+                                                                 if args.attention_overlay in (None, "mean")
+                                                                 else int(args.attention_overlay))
                 except ValueError as e:
                     raise SystemExit(str(e))
             else:
@@ -448,7 +462,7 @@ def main(argv=None):
                                               fps=fps, stride=args.stride, overlay=bool(args.overlay or args.overlay_dir),
                                               fill=args.fill, max_gap=args.max_gap, attention_track=attention_track,
                                               overlay_format=args.overlay_format, **fmt)
-            if args.attention_overlay is not None:
+            if args.attention_overlay is not None and not args.stream:
                 head = None if args.attention_overlay == "mean" else int(args.attention_overlay)
                 out["attention_overlay"] = predictor.render_attention_track(frames, out, head=head, points=out["points"], **fmt)
         keys = ("points", "peak", "count", "rescaled", "heatmaps") + (("points_source", "overlay") if "overlay" in out else ())
@@ -456,7 +470,7 @@ def main(argv=None):
         if attention_track:
             keys += ("attention_maps", "attention_range", "attention_mixed", "attention_count", "temporal_attention_windows")
             keys += ("attention_neighbours", "attention_filled") if args.fill is not None else ()
-            keys += ("attention_overlay",) if args.attention_overlay is not None else ()
+            keys += ("attention_overlay",) if args.attention_overlay is not None and not args.stream else ()
         arrays = {k: out[k].cpu().numpy() for k in keys}
         rates = {} if rate is None else {"sample_rate": np.int64(rate), "audio_rate": np.int64(AUDIO_RATE)}
         if args.stream:
@@ -464,6 +478,9 @@ def main(argv=None):
             arrays["stream_dropped"] = np.int64(dropped)
         if args.live is not None:
             live_keys = ("points", "peak", "count", "known", "filled", "points_source") + (("overlay",) if "overlay" in out["live"] else ())
+            if attention_track:
+                live_keys += ("attention_frame", "attention_count", "attention_maps", "attention_range")
+                live_keys += ("attention_overlay",) if "attention_overlay" in out["live"] else ()
             arrays.update({"live_" + k: out["live"][k].cpu().numpy() for k in live_keys})
         if args.overlay_format is not None:
             arrays["overlay_pixel_format"] = np.array(args.overlay_format)
